@@ -11,6 +11,11 @@ stem+backbone+neck+head -> DFL decode -> EfficientNMS(0.25/0.65/100) -> restore/
 custom_nms(0.45) dedupe -> inflate -> crop+nearest-resize+normalize -> ViT-B/16 -> wrapper head -> argmax.
 Crops per image are capped at --crops (default 4, SURVEY.md 8(d) "fixed-R mode") so the
 classifier work per step is deterministic; the cap is part of the reported config.
+
+A plain run sets up, warms up, times --steps steps and prints the JSON line.  --full adds the measurements
+that take runs of their own: roofline.traffic from two rocprofv3 --pmc child runs (before the timed run) and
+the CPU baseline (after it).  --dump-outputs DIR writes what the last timed step returned as DIR/<name>.npy
+(float32 / float64); inputs and weights are seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -27,6 +32,52 @@ import torch  # noqa: E402
 MFMA_PEAK_TFLOPS = 2500.0        # bf16 dense, MI355X_MICROARCH.md chip table
 DOMINANT_KERNEL = "gemm_p9_kernel"       # what profiles/pmc_traffic.json must have been collected for
 ROUND_TAG = "r03"
+DUMP_LIMIT_BYTES = 64 << 20      # --dump-outputs: all files together
+
+
+def _masked_rows(t, n):
+    """t (B, slots, ...) with rows >= n[b] zeroed: the kernels leave them unspecified (torch.empty), and a dump must not
+    carry whatever the allocator handed out."""
+    keep = torch.arange(t.shape[1])[None, :] < n.long()[:, None]
+    return torch.where(keep.view(keep.shape + (1,) * (t.dim() - 2)), t, torch.zeros_like(t))
+
+
+def _sample_rows(t, n, seed):
+    """A fixed, seeded sample of n rows of t (all rows if it has no more), in row order."""
+    if t.shape[0] <= n:
+        return t
+    idx = torch.randperm(t.shape[0], generator=torch.Generator().manual_seed(seed))[:n].sort().values
+    return t[idx.to(t.device)]
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: {name: tensor} -> d/<name>.npy; floating tensors as float32 (bf16 converts exactly), integer ones as
+    float64 (exact for every int32)."""
+    import numpy as np
+    conv = {}
+    for k, t in arrays.items():
+        t = t.detach().cpu()
+        conv[k] = (t.float() if t.is_floating_point() else t.double()).numpy()
+    total = sum(a.nbytes for a in conv.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(d, exist_ok=True)
+    for k, a in conv.items():
+        np.save(os.path.join(d, k + ".npy"), a)
+    print(f"[bench] wrote {len(conv)} arrays ({total} bytes) to {d}", file=sys.stderr)
+
+
+def infer_outputs(out):
+    """The tensors of the pipeline's result dict, entries past each valid count zeroed: NMS slots past num_dets, detection
+    slots past det_count, crop rows past crop_total."""
+    o = {k: v.detach().cpu() for k, v in out.items() if torch.is_tensor(v)}
+    for k in ("bboxes", "scores", "labels"):
+        o[k] = _masked_rows(o[k], o["num_dets"][:, 0])
+    for k in ("det_box", "det_score", "det_label", "crop_rect", "crop_ok"):
+        o[k] = _masked_rows(o[k], o["det_count"])
+    for k in ("crop_list", "cls_logits", "cls_label"):
+        o[k] = _masked_rows(o[k][None], o["crop_total"][:1])[0]
+    return o
 
 
 def _cpu_loop(imgs, yolo_sd, vit_sd, vit_name, crops, budget_s, max_images):
@@ -102,11 +153,13 @@ def bench_train(args, rank, world, dev, dist):
         dist.barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss, _ = tr.step(patches, labels, 1e-4)
+        loss, logits = tr.step(patches, labels, 1e-4)
     torch.cuda.synchronize()
     if dist is not None:
         dist.barrier()
     dt = max_over_ranks(time.perf_counter() - t0, None if os.environ.get("YV_BENCH_REHEARSAL") == "1" else dev)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"loss": loss, "logits": logits})
     if rank == 0:
         flop = 3.0 * 35.13e9 * R                       # fwd + bwd ~ 3 x forward
         print(json.dumps({"metric": "ViT-B/16 fine-tune images/sec (fwd+bwd+SGD)", "value": world * R * args.steps / dt,
@@ -157,6 +210,8 @@ def bench_train_yolo(args, rank, world, dev, dist):
     if dist is not None:
         dist.barrier()
     dt = max_over_ranks(time.perf_counter() - t0, None if os.environ.get("YV_BENCH_REHEARSAL") == "1" else dev)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"loss": loss})
     if rank == 0:
         flop = 3.0 * 28.60e9 * B                       # fwd + bwd ~ 3 x forward
         print(json.dumps({"metric": "YOLOv8s training images/sec (fwd+loss+bwd+SGD)", "value": world * B * args.steps / dt,
@@ -218,7 +273,13 @@ def bench_postproc(args, dev):
     res["nms"] = timed(lambda: yvhip.efficient_nms(boxes, scores))
     res["nms_single_kernel"] = timed(lambda: yvhip.efficient_nms(boxes, scores, single_kernel=True))
     res["crop"] = timed(lambda: yvhip.crop_resize_norm(images, cl, total, B * R, 224, 16, layout=2, out=out))
-    num = yvhip.efficient_nms(boxes, scores)[0]
+    num, nb, ns, nl = yvhip.efficient_nms(boxes, scores)
+    if args.dump_outputs:
+        # the crop output is B*R*196 x 768 (77 MB as float32 at batch 32): a fixed sample of 4,096 rows
+        dump_outputs(args.dump_outputs, {"num_dets": num, "bboxes": _masked_rows(nb.cpu(), num[:, 0].cpu()),
+                                         "scores": _masked_rows(ns.cpu(), num[:, 0].cpu()),
+                                         "labels": _masked_rows(nl.cpu(), num[:, 0].cpu()),
+                                         "crop_rows": _sample_rows(out, 4096, seed=4321)})
     nms_bytes = B * (A * (16 + 4 * nc) + 2404)
     crop_bytes = B * R * 451584
     peak = 8000.0
@@ -342,7 +403,15 @@ def main():
     ap.add_argument("--mode", choices=["infer", "train", "train-yolo", "postproc"], default="infer",
                     help="infer = headline metric (configs[1]); train = ViT-B/16 fine-tune step (configs[2]); "
                          "train-yolo = YOLOv8s training step (configs[3])")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: roofline.traffic live (two rocprofv3 --pmc child "
+                         "runs before the timed run, unless --no-traffic) and the CPU baseline (unless --no-cpu-baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy (float32 / float64, "
+                         "at most 64 MB; rank 0's outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         # plain `python bench.py --gpus N`: become the launcher.  Nothing in this process has touched HIP yet (importing torch
@@ -355,8 +424,8 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     live = None
-    if (args.mode == "infer" and args.models == "base" and args.dtype == "bf16" and world == 1 and "RANK" not in os.environ
-            and not args.no_traffic and os.environ.get("YV_BENCH_DRY") != "1"):
+    if (args.full and args.mode == "infer" and args.models == "base" and args.dtype == "bf16" and world == 1
+            and "RANK" not in os.environ and not args.no_traffic and os.environ.get("YV_BENCH_DRY") != "1"):
         # before this process initialises HIP (importing torch and counting devices does not): the children are started, never exec'ed
         tail = [a for f in ("--batch", "--crops") for a in (f, str(getattr(args, f[2:])))]
         tail += [f for f, on in (("--no-overlap", args.no_overlap), ("--no-split", args.no_split)) if on]
@@ -439,6 +508,8 @@ def main():
     from yvhip.dist import max_over_ranks
     dt = max_over_ranks(dt, None if os.environ.get("YV_BENCH_REHEARSAL") == "1" else dev)
 
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, infer_outputs(out))
     if rank == 0:
         flops = sum(f for f, _, _ in recs)
         ms = sum(e0.elapsed_time(e1) for _, e0, e1 in recs)
@@ -497,7 +568,7 @@ def main():
                          "concurrent_launches": runner is not None and not args.no_split,
                          "alg_flop_per_launch": flops / max(n_launch, 1)},
         }
-        if world == 1 and not args.no_cpu_baseline and not large:
+        if args.full and world == 1 and not args.no_cpu_baseline and not large:
             line["cpu_baseline"] = cpu_baseline(yolo_sd, vit_sd, vit_name, R)
         print(json.dumps(line), flush=True)
     if dist is not None:

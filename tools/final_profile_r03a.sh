@@ -4,7 +4,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/r03f
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-python3 $R/bench.py --steps 20 --warmup 5 > $O/bench_line.json 2> $O/bench_line.err
+python3 $R/bench.py --full --steps 20 --warmup 5 > $O/bench_line.json 2> $O/bench_line.err
 echo "bench done"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --steps 12 --warmup 3 --no-cpu-baseline --no-traffic > $O/bench_under_rocprof.json 2> $O/stats.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_single -- python3 $R/bench.py --steps 12 --warmup 3 --no-cpu-baseline --no-traffic --no-overlap > $O/bench_single_under_rocprof.json 2> $O/stats_single.err
