@@ -245,6 +245,40 @@ int yv_conv2d(const yv_view* in0, const yv_view* in1, int B, int Hout, int Wout,
               const void* weight, const float* bias, int Cout, void* out, int out_ld, const void* res, int res_ld,
               int flags, void* stream);
 
+/* MXFP8 convolutions (BASELINE.json configs[4]: FP8 detector convolutions; opt-in, YoloEngine(dtype="mxfp8")).
+ * An "MX map" is an NHWC activation in the operand format of the block-scaled MFMA: e4m3 bytes q (B,H,W,ld) and one E8M0
+ * scale byte per (pixel, 32-channel block) s (B,H,W,ld/32).  A view points at the first channel it reads in both arrays
+ * (q + c_off, s + c_off/32); c_off, c and ld are multiples of 32.  up = 1: read through a nearest 2x upsample (1x1 only). */
+typedef struct yv_mx_view {
+    const void* q;   /* e4m3 bytes                                    */
+    const void* s;   /* E8M0 scales, pixel stride ld/32 bytes         */
+    int ld;          /* bytes (= channels) between consecutive pixels */
+    int c;           /* channels read from this view                  */
+    int up;          /* 0 | 1                                         */
+} yv_mx_view;
+
+/* bf16 NHWC view x (pixels rows, pixel stride ldx elements, C channels read) -> MX map (q pixel stride ldq bytes, scales
+ * pixel stride ldq/32 bytes), the rule of yv_quant_mxfp8: e = ceil(log2(amax/448)) per 32 channels of a pixel (all-zero
+ * blocks e = -127), q = RNE_e4m3(x * 2^-e).  C, ldq multiples of 32, ldx of 8; x, q 16-byte aligned. */
+int yv_quant_mxfp8_map(const void* x, long long ldx, long long pixels, int C, void* q, long long ldq, void* scales,
+                       void* stream);
+
+/* yv_conv2d on MX operands: in0 (+ in1, 1x1 only) MX maps, wq (Cout, Kpad) e4m3 with K order (ky,kx,cin) zero-padded to
+ * Kpad = k*k*Cin rounded up to 128, wscale K-step-major (Kpad/128, w_rows_pad, 4) exactly as yv_quant_mxfp8 writes it.
+ * Epilogue as yv_conv2d (bias, SiLU, bf16 residual), then either or both of
+ *   out_bf16: bf16 view with pixel stride out_ld (f32 with YV_EPI_OUT_F32),
+ *   out_q / out_scales: MX map (pixel strides outq_ld / outq_ld/32 bytes) of the bf16-rounded result - byte-identical to
+ *   out_bf16 followed by yv_quant_mxfp8_map (not with YV_EPI_OUT_F32).
+ * NULL for an output that is not wanted.  Requires Cin % 32 == 0 per source, Cout % 32 == 0.  Each image and the weights
+ * stay below 2 GB (larger batches are taken in sub-batches). */
+int yv_conv2d_mxfp8(const yv_mx_view* in0, const yv_mx_view* in1, int B, int Hout, int Wout, int ksize, int stride,
+                    const void* wq, const void* wscale, long long w_rows_pad, const float* bias, int Cout, void* out_bf16,
+                    int out_ld, void* out_q, void* out_scales, int outq_ld, const void* res, int res_ld, int flags,
+                    void* stream);
+/* Diagnostic: the kernel instance yv_conv2d_mxfp8 launches for this shape (0: 128 x 64 tiles, 1: 128 x 128 tiles), or
+ * a negative YV_ERR_* code if the shape is not accepted. */
+int yv_conv2d_mxfp8_instance(int B, int Hout, int Wout, int ksize, int stride, int Cin, int Cout);
+
 /* One launch for a whole C2f block of the detector backbone (ultralytics C2f with shortcut, as in layers model.2 / model.4 of the
  * YOLOv8 models the reference loads - utils/utils.py:126, test.ipynb): cv1 (1x1, 2c -> 2c), n bottlenecks of two 3x3 layers
  * c -> c with the residual add, cv2 (1x1, (2+n)c -> 2c), SiLU after every layer (BN folded).  x (B,H,W,>=2c) bf16 with pixel

@@ -42,7 +42,9 @@ def _guess_scale_nc(sd):
 
 
 class TRTModule(torch.nn.Module):
-    def __init__(self, weight: Union[str, dict], device: Optional[torch.device] = None, size: int = 640) -> None:
+    def __init__(self, weight: Union[str, dict], device: Optional[torch.device] = None, size: int = 640,
+                 dtype: str = "bf16") -> None:
+        """dtype: "bf16" (default) or "mxfp8" (the detector's eligible convolutions on MXFP8 operands, engines.mx_conv_plan)."""
         super().__init__()
         self.device = torch.device(device) if device is not None else torch.device('cuda:0')
         if isinstance(weight, dict):
@@ -59,7 +61,7 @@ class TRTModule(torch.nn.Module):
                 raise yvhip.YvError(f"{weight}: expected a YOLOv8 state dict (ultralytics key layout)")
         sd = fold_batchnorm(sd)
         self.scale, self.nc = _guess_scale_nc(sd)
-        self.engine = engines.YoloEngine(sd, self.scale, self.nc, size, device=str(self.device))
+        self.engine = engines.YoloEngine(sd, self.scale, self.nc, size, device=str(self.device), dtype=dtype)
         self.size = size
         self.inp_info = [Tensor('images', torch.float32, (1, 3, size, size))]
         self.out_info = [Tensor('num_dets', torch.int32, (1, 1)), Tensor('bboxes', torch.float32, (1, 100, 4)),

@@ -1164,6 +1164,359 @@ __global__ __launch_bounds__(256) void quant_mx_kernel(const uint16_t* __restric
 }
 
 // ---------------------------------------------------------------------------------------------
+// MXFP8 convolution (cgemm_mx_kernel; BASELINE.json configs[4]: FP8 detector convolutions, opt-in).  cgemm_dma_kernel's
+// structure - per-lane pixel offsets, tap-validity bits, everything that changes along K in the DMA's scalar offset - on
+// the block-scaled MFMA of gemm_mx_kernel: e4m3 bytes, so a 128-byte LDS row is one 128-deep K step, half the DMA
+// instructions, LDS bytes and L2 reads per flop of the bf16 kernel.
+//   Inputs are MX maps (yv_mx_view): e4m3 NHWC bytes + one E8M0 scale per (pixel, 32-channel block).  With Cin % 128 != 0 a
+//   K step straddles taps (or the two sources of a 1 x 1), but each of its four 32-element blocks lies inside ONE tap and
+//   ONE source.  So the LDS tile is stored BLOCK-major, [block 0..3][row][32 B], and wave w fetches block w of every row:
+//   one wave-instruction = 32 rows x 32 B of one block, whose (tap, source, channel base) is wave-uniform and travels in the
+//   scalar offset exactly as in cgemm_dma_kernel - no per-lane select, no per-element work, for any Cin % 32 == 0.
+//   Inside a 32-byte row the two 16-byte halves are swapped on rows with bit 3 set (source side of the DMA, undone on the
+//   fragment read): the ds_read_b128 of 16 rows x one half are then conflict free.
+//   Fragment of lane (row r, group g) (layout of test_mx_mfma_layout): K chunks g and 4 + g of the step = half g & 1 of
+//   blocks g >> 1 and 2 + (g >> 1).  Scales: lane (r, g) supplies the scale of block g of row r - for the activation the
+//   byte of block g at ITS tap pixel (zero-data taps read scale 0), for the weight byte g of the K-step-major dword
+//   yv_quant_mxfp8 writes.  They are loaded into registers one K step ahead, behind the DMA of that step.
+//   K is zero-padded to a multiple of 128 (the weight's padding is zeros, the activation's padding blocks read zeros).
+//   Epilogue: finish_tile (bias, SiLU, bf16 shortcut, bf16 / f32 output), or - when an MX-map output is wanted - the bf16
+//   staged epilogue followed by the rule of yv_quant_mxfp8_map on the bf16-rounded values (byte-identical to the bf16
+//   output quantised afterwards), with or without the bf16 store.
+// ---------------------------------------------------------------------------------------------
+struct ConvMxArgs {
+    GemmArgs g;                 // a0 / a1 -> e4m3 bytes (lda0 / lda1: bytes per pixel), w -> (N, K) e4m3, K = padded depth
+    const uint8_t* s0;          // per-pixel scales of the sources (pixel stride lda / 32 bytes)
+    const uint8_t* s1;
+    int kreal;                  // k * k * Cin
+    const uint8_t* sw;          // weight scales (K / 128, rows_w, 4)
+    long long rows_w;
+    uint8_t* oq;                // MX-map output (pixel stride ldq bytes, scales ldq / 32) or null
+    uint8_t* os;
+    int ldq;
+};
+
+// E8M0 exponent of a 32-element block: ceil(log2(amax / 448)) (all-zero blocks -127), as quant_mx_kernel
+__device__ __forceinline__ int mx_block_exp(float amax) {
+    int e = -127;
+    if (amax > 0.f) {
+        int ex;
+        const float mant = frexpf(amax * (1.0f / 448.0f), &ex);
+        e = mant == 0.5f ? ex - 1 : ex;
+        e = e < -127 ? -127 : (e > 127 ? 127 : e);
+    }
+    return e;
+}
+
+template <int MF>
+__device__ __forceinline__ void epilogue_conv_mx(const ConvMxArgs& a, f32x4 (&acc)[4][MF], int M, int m0, int n0,
+                                                 int wrow_m, int wrow_n, int lane, unsigned char* stage) {
+    const GemmArgs& g = a.g;
+    const int flags = g.flags;
+    const int fr = lane & 15, fq = lane >> 4;
+    const int nb = n0 + wrow_n;
+#pragma unroll
+    for (int j = 0; j < MF; ++j)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int n = nb + i * 16 + fq * 4;
+            float4 b = make_float4(0.f, 0.f, 0.f, 0.f);
+            if ((flags & YV_EPI_BIAS) && n < g.N) b = *(const float4*)(g.bias + n);
+            float v[4] = {acc[i][j][0] + b.x, acc[i][j][1] + b.y, acc[i][j][2] + b.z, acc[i][j][3] + b.w};
+            if (flags & YV_EPI_SILU) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) v[q] = silu_f(v[q]);
+            }
+            const int row = j * 16 + fr, c16 = i * 2 + (fq >> 1);
+            *(uint2*)(stage + row * 128 + ((c16 ^ (row & 7)) << 4) + (fq & 1) * 8) =
+                make_uint2(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]));
+        }
+#pragma unroll
+    for (int it = 0; it < MF * 2; ++it) {
+        const int row = it * 8 + (lane >> 3), ch = lane & 7;
+        const int m = m0 + wrow_m + row, n = nb + ch * 8;
+        uint4 pk = *(const uint4*)(stage + row * 128 + ((ch ^ (row & 7)) << 4));
+        if (m < M && n < g.N) {           // (N % 32 == 0: the four lanes of a 32-channel block agree)
+            if (flags & YV_EPI_RES_BF16) {
+                const uint4 rr = *(const uint4*)(g.res + (long long)m * g.ldres + n);
+                const uint32_t x[4] = {pk.x, pk.y, pk.z, pk.w}, y[4] = {rr.x, rr.y, rr.z, rr.w};
+                uint32_t o[4];
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+                    o[q] = pack_bf16x2(bf16_to_f32((uint16_t)(x[q] & 0xffff)) + bf16_to_f32((uint16_t)(y[q] & 0xffff)),
+                                       bf16_to_f32((uint16_t)(x[q] >> 16)) + bf16_to_f32((uint16_t)(y[q] >> 16)));
+                pk = make_uint4(o[0], o[1], o[2], o[3]);
+            }
+            if (g.out) *(uint4*)((uint16_t*)g.out + (long long)m * g.ldo + n) = pk;
+            const uint32_t x[4] = {pk.x, pk.y, pk.z, pk.w};
+            float f[8];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) { f[2 * q] = bf16_to_f32((uint16_t)(x[q] & 0xffff)); f[2 * q + 1] = bf16_to_f32((uint16_t)(x[q] >> 16)); }
+            float amax = 0.f;
+#pragma unroll
+            for (int q = 0; q < 8; ++q) amax = fmaxf(amax, fabsf(f[q]));
+            amax = fmaxf(amax, __shfl_xor(amax, 1, 64));
+            amax = fmaxf(amax, __shfl_xor(amax, 2, 64));
+            const int e = mx_block_exp(amax);
+            const float inv = ldexpf(1.0f, -e);
+            int p0 = 0, p1 = 0;
+            p0 = __builtin_amdgcn_cvt_pk_fp8_f32(f[0] * inv, f[1] * inv, p0, false);
+            p0 = __builtin_amdgcn_cvt_pk_fp8_f32(f[2] * inv, f[3] * inv, p0, true);
+            p1 = __builtin_amdgcn_cvt_pk_fp8_f32(f[4] * inv, f[5] * inv, p1, false);
+            p1 = __builtin_amdgcn_cvt_pk_fp8_f32(f[6] * inv, f[7] * inv, p1, true);
+            *(uint2*)(a.oq + (long long)m * a.ldq + n) = make_uint2((uint32_t)p0, (uint32_t)p1);
+            if ((ch & 3) == 0) a.os[(long long)m * (a.ldq >> 5) + (n >> 5)] = (uint8_t)(e + 127);
+        }
+    }
+}
+
+template <int BN, int WM, int WN>
+__global__ __launch_bounds__(256) void cgemm_mx_kernel(ConvMxArgs a) {
+    const GemmArgs& g = a.g;
+    constexpr int BM = 128, NW = 4;
+    static_assert(WM * WN == NW, "four waves");
+    constexpr int MF = BM / WM / 16, NF = BN / WN / 16;
+    static_assert(NF == 4 && (MF % 2) == 0, "staged epilogue shapes");
+    constexpr int A_BYTES = BM * 128, W_BYTES = BN * 128, STAGE = A_BYTES + W_BYTES;
+    constexpr int A_INS = BM / 32, W_INS = BN / 32;            // wave-instructions per wave and K step: 32 rows x one block
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int M = g.M;
+    int bid = blockIdx.x;
+    {
+        const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, x = bid & 7;
+        bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
+    }
+    const int tm = bid / g.tiles_n, tn = bid - tm * g.tiles_n;
+    const int m0 = tm * BM, n0 = tn * BN;
+    if (m0 >= M) return;
+
+    constexpr uint32_t OOB = 0x80000000u;
+    const int Cin = g.c0 + g.c1, KK = g.ksize * g.ksize;
+    const int hw = g.Hout * g.Wout;
+    const int sld0 = g.lda0 >> 5, sld1 = g.lda1 >> 5;
+    // pixel geometry of an output row: source pixel offsets (in pixels) and the 3 x 3 tap-validity bits
+    auto geom = [&](int m, int& p0, int& p1, uint32_t& taps) __attribute__((always_inline)) {
+        const int mc = m < M ? m : M - 1;
+        const int b = mc / hw, rem = mc - b * hw;
+        const int oy = rem / g.Wout;
+        const int cy = oy * g.stride, cx = (rem - oy * g.Wout) * g.stride;
+        p0 = ((b * (g.Hin >> g.up0) + (cy >> g.up0)) * (g.Win >> g.up0) + (cx >> g.up0));
+        p1 = g.c1 ? ((b * (g.Hin >> g.up1) + (cy >> g.up1)) * (g.Win >> g.up1) + (cx >> g.up1)) : 0;
+        taps = 0;
+        if (m < M) {
+            if (g.ksize == 3) {
+#pragma unroll
+                for (int t = 0; t < 9; ++t) {
+                    const int iy = cy + t / 3 - 1, ix = cx + t % 3 - 1;
+                    taps |= (iy >= 0 && iy < g.Hin && ix >= 0 && ix < g.Win) ? (1u << t) : 0u;
+                }
+            } else {
+                taps = 1u;
+            }
+        }
+    };
+    // DMA lanes: lane l writes half l & 1 of row l >> 1 of a 32-row piece; the half it fetches is swapped on rows with bit 3 set
+    const int lr = lane >> 1, hsrc = ((lane & 1) ^ ((lr >> 3) & 1)) << 4;
+    uint32_t a_off0[A_INS], a_off1[A_INS], a_taps[A_INS], w_off[W_INS];
+#pragma unroll
+    for (int j = 0; j < A_INS; ++j) {
+        int p0, p1;
+        geom(m0 + j * 32 + lr, p0, p1, a_taps[j]);
+        a_off0[j] = (uint32_t)(p0 * g.lda0 + hsrc);
+        a_off1[j] = (uint32_t)(p1 * g.lda1 + hsrc);
+    }
+#pragma unroll
+    for (int j = 0; j < W_INS; ++j) {
+        int n = n0 + j * 32 + lr;
+        n = n < g.N ? n : g.N - 1;
+        w_off[j] = (uint32_t)(n * g.K + hsrc);
+    }
+    const int wm = wave / WN, wn = wave - wm * WN;
+    const int wrow_m = wm * (BM / WM), wrow_n = wn * (BN / WN);
+    const int fr = lane & 15, fq = lane >> 4;
+    // scale lanes: lane (fr, fq) of fragment row j / column i
+    int s_pix0[MF], s_pix1[MF];
+    uint32_t s_taps[MF];
+#pragma unroll
+    for (int j = 0; j < MF; ++j) {
+        int p0, p1;
+        geom(m0 + wrow_m + j * 16 + fr, p0, p1, s_taps[j]);
+        s_pix0[j] = p0 * sld0;
+        s_pix1[j] = p1 * sld1;
+    }
+    const uint8_t* sw_row[NF];
+#pragma unroll
+    for (int i = 0; i < NF; ++i) {
+        int n = n0 + wrow_n + i * 16 + fr;
+        n = n < g.N ? n : g.N - 1;
+        sw_row[i] = a.sw + (long long)n * 4 + fq;
+    }
+
+    // source 0's descriptor starts one row + one pixel before the tensor (3 x 3 only): the scalar offset is unsigned
+    const uint32_t bias0 = g.ksize == 3 ? (uint32_t)((g.Win + 1) * g.lda0) : 0u;
+    const auto rs0 = __builtin_amdgcn_make_buffer_rsrc((void*)((const unsigned char*)g.a0 - bias0), 0, 0x7fffffff, 0x00020000);
+    const auto rs1 = __builtin_amdgcn_make_buffer_rsrc((void*)(g.c1 ? g.a1 : g.a0), 0, 0x7fffffff, 0x00020000);
+    const auto rsW = __builtin_amdgcn_make_buffer_rsrc((void*)g.w, 0, 0x7fffffff, 0x00020000);
+
+    // (tap, channel) of the K position this wave's block / this lane's scale block has in the NEXT step to be fetched
+    int wt = 0, wc = 32 * wave;
+    while (wc >= Cin) { wc -= Cin; ++wt; }
+    int lt = 0, lc = 32 * fq;
+    while (lc >= Cin) { lc -= Cin; ++lt; }
+
+    auto issue = [&](int kt, int buf) __attribute__((always_inline)) {
+        unsigned char* A = smem + buf * STAGE + wave * (BM * 32);
+        unsigned char* W = smem + buf * STAGE + A_BYTES + wave * (BN * 32);
+        if (wt >= KK) {                                          // K padding: zeros
+#pragma unroll
+            for (int j = 0; j < A_INS; ++j)
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rs0, (lptr_t)(A + j * 1024), 16, (int)OOB, 0, 0, 0);
+        } else if (g.c1 && wc >= g.c0) {                         // second source of a two-source 1 x 1
+#pragma unroll
+            for (int j = 0; j < A_INS; ++j)
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rs1, (lptr_t)(A + j * 1024), 16,
+                                                         (int)((a_taps[j] & 1u) ? a_off1[j] : OOB), wc - g.c0, 0, 0);
+        } else {
+            uint32_t so = (uint32_t)wc;
+            if (g.ksize == 3) {
+                const int ky = wt >= 6 ? 2 : (wt >= 3 ? 1 : 0), kx = wt - ky * 3;
+                so = bias0 + (uint32_t)(((ky - 1) * g.Win + (kx - 1)) * g.lda0 + wc);
+            }
+#pragma unroll
+            for (int j = 0; j < A_INS; ++j)
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rs0, (lptr_t)(A + j * 1024), 16,
+                                                         (int)(((a_taps[j] >> wt) & 1u) ? a_off0[j] : OOB), (int)so, 0, 0);
+        }
+#pragma unroll
+        for (int j = 0; j < W_INS; ++j)
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsW, (lptr_t)(W + j * 1024), 16, (int)w_off[j], kt * 128 + 32 * wave, 0, 0);
+        wc += 128;
+        while (wc >= Cin) { wc -= Cin; ++wt; }
+    };
+    int sca[MF], scw[NF];
+    auto load_scales = [&](int kt) __attribute__((always_inline)) {
+#pragma unroll
+        for (int j = 0; j < MF; ++j) {
+            int s = 0;
+            if (lt < KK) {
+                if (g.c1 && lc >= g.c0) {
+                    if (s_taps[j] & 1u) s = a.s1[s_pix1[j] + ((lc - g.c0) >> 5)];
+                } else if ((s_taps[j] >> lt) & 1u) {
+                    int d = 0;
+                    if (g.ksize == 3) {
+                        const int ky = lt >= 6 ? 2 : (lt >= 3 ? 1 : 0), kx = lt - ky * 3;
+                        d = ((ky - 1) * g.Win + (kx - 1)) * sld0;
+                    }
+                    s = a.s0[s_pix0[j] + d + (lc >> 5)];
+                }
+            }
+            sca[j] = s;
+        }
+#pragma unroll
+        for (int i = 0; i < NF; ++i) scw[i] = sw_row[i][(long long)kt * a.rows_w * 4];
+        lc += 128;
+        while (lc >= Cin) { lc -= Cin; ++lt; }
+    };
+
+    f32x4 acc[NF][MF];
+#pragma unroll
+    for (int i = 0; i < NF; ++i)
+#pragma unroll
+        for (int j = 0; j < MF; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    const int nk = g.K >> 7;
+    issue(0, 0);
+    load_scales(0);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    const int hrd = ((fq & 1) << 4);
+    for (int kt = 0; kt < nk; ++kt) {
+        const int cur = kt & 1;
+        int sa_c[MF], sw_c[NF];
+#pragma unroll
+        for (int j = 0; j < MF; ++j) sa_c[j] = sca[j];
+#pragma unroll
+        for (int i = 0; i < NF; ++i) sw_c[i] = scw[i];
+        if (kt + 1 < nk) { issue(kt + 1, cur ^ 1); load_scales(kt + 1); }
+        const unsigned char* A = smem + cur * STAGE;
+        const unsigned char* W = A + A_BYTES;
+        i32x8 fa[MF], fw[NF];
+#pragma unroll
+        for (int j = 0; j < MF; ++j) {
+            const int rr = wrow_m + j * 16 + fr;
+            const int o = rr * 32 + (hrd ^ ((rr & 8) << 1));
+            const u32x4 lo = *(const u32x4*)(A + (fq >> 1) * (BM * 32) + o);
+            const u32x4 hi = *(const u32x4*)(A + (2 + (fq >> 1)) * (BM * 32) + o);
+            fa[j] = (i32x8){(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3], (int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
+        }
+#pragma unroll
+        for (int i = 0; i < NF; ++i) {
+            const int rr = wrow_n + i * 16 + fr;
+            const int o = rr * 32 + (hrd ^ ((rr & 8) << 1));
+            const u32x4 lo = *(const u32x4*)(W + (fq >> 1) * (BN * 32) + o);
+            const u32x4 hi = *(const u32x4*)(W + (2 + (fq >> 1)) * (BN * 32) + o);
+            fw[i] = (i32x8){(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3], (int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
+        }
+#pragma unroll
+        for (int i = 0; i < NF; ++i)
+#pragma unroll
+            for (int j = 0; j < MF; ++j)
+                // inline asm, as in gemm_p9_kernel<MX> (the builtin's register allocation spilled there); operands come from
+                // LDS reads and scale loads the compiler waits for (inputs of the statement): the s_nop covers a just-written
+                // operand, the accumulator chains MFMA -> MFMA
+#if defined(__HIP_DEVICE_COMPILE__)       // (the host pass cannot place 32-byte "v" operands)
+                asm volatile("s_nop 1\n\tv_mfma_scale_f32_16x16x128_f8f6f4 %0, %1, %2, %0, %3, %4 op_sel_hi:[0,0,0]"
+                             : "+v"(acc[i][j]) : "v"(fw[i]), "v"(fa[j]), "v"(sw_c[i]), "v"(sa_c[j]));
+#endif
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+    }
+    // the last MFMAs' results are read by ordinary VALU code next: their write-back latency is not tracked for asm
+    asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 7" ::: "memory");
+    if (a.oq) epilogue_conv_mx<MF>(a, acc, M, m0, n0, wrow_m, wrow_n, lane, smem + wave * (MF * 16 * 128));
+    else finish_tile<MF, NF>(a.g, acc, M, m0, n0, wrow_m, wrow_n, lane, wave, smem);
+}
+
+// bf16 NHWC view -> MX map (yv_quant_mxfp8_map): one thread per (pixel, 32-channel block), the arithmetic of quant_mx_kernel
+__global__ __launch_bounds__(256) void quant_mx_map_kernel(const uint16_t* __restrict__ x, long long ldx, long long pixels, int C,
+                                                           uint8_t* __restrict__ q, long long ldq, uint8_t* __restrict__ sc) {
+    const int kb = C >> 5;
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= pixels * kb) return;
+    const long long p = idx / kb;
+    const int b = (int)(idx - p * kb);
+    const uint16_t* src = x + p * ldx + b * 32;
+    float v[32];
+    float amax = 0.f;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const uint4 u = *(const uint4*)(src + c * 8);
+        const uint32_t w[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            v[c * 8 + 2 * i] = bf16_to_f32((uint16_t)(w[i] & 0xffff));
+            v[c * 8 + 2 * i + 1] = bf16_to_f32((uint16_t)(w[i] >> 16));
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 32; ++i) amax = fmaxf(amax, fabsf(v[i]));
+    const int e = mx_block_exp(amax);
+    const float inv = ldexpf(1.0f, -e);
+    uint32_t out[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        int pq = 0;
+        pq = __builtin_amdgcn_cvt_pk_fp8_f32(v[4 * i] * inv, v[4 * i + 1] * inv, pq, false);
+        pq = __builtin_amdgcn_cvt_pk_fp8_f32(v[4 * i + 2] * inv, v[4 * i + 3] * inv, pq, true);
+        out[i] = (uint32_t)pq;
+    }
+    uint4* dst = (uint4*)(q + p * ldq + b * 32);
+    dst[0] = make_uint4(out[0], out[1], out[2], out[3]);
+    dst[1] = make_uint4(out[4], out[5], out[6], out[7]);
+    sc[p * (ldq >> 5) + b] = (uint8_t)(e + 127);
+}
+
+// ---------------------------------------------------------------------------------------------
 // 256 x 256 x 64 "8-phase" schedule (cdna_hip_programming.md section 5 template, re-derived for this operand
 // convention; the non-persistent round-1 kernel of this shape was removed in round 3, gemm_p8_kernel below is its
 // persistent form).  8 waves = 2 groups (wm = 0/1, 128 activation rows each) x 4 (64 weight rows each); one
@@ -2440,6 +2793,15 @@ int launch_cdma(GemmArgs& g, hipStream_t st) {
     return yv_launch_status();
 }
 
+template <int BN, int WM, int WN>
+int launch_cmx(ConvMxArgs& a, hipStream_t st) {       // two LDS stages of 128 + BN rows: <= 64 KB
+    a.g.tiles_m = (a.g.M + 127) / 128;
+    a.g.tiles_n = (a.g.N + BN - 1) / BN;
+    auto kern = cgemm_mx_kernel<BN, WM, WN>;
+    hipLaunchKernelGGL(kern, dim3(a.g.tiles_m * a.g.tiles_n), dim3(256), 2 * (128 + BN) * 128, st, a);
+    return yv_launch_status();
+}
+
 template <int MODE>
 int dispatch(GemmArgs& g, hipStream_t st) {
     if constexpr (MODE == 1) {
@@ -2907,4 +3269,128 @@ extern "C" int yv_conv2d_ws(const yv_view* in0, const yv_view* in1, int B, int H
                             int res_ld, int flags, void* ws, size_t ws_bytes, void* stream) {
     return conv_impl(in0, in1, B, Hout, Wout, ksize, stride, weight, bias, Cout, out, out_ld, res, res_ld, flags, ws, ws_bytes,
                      stream);
+}
+
+// ---------------------------------------------------------------------------------------------------- MXFP8 convolutions
+extern "C" int yv_quant_mxfp8_map(const void* x, long long ldx, long long pixels, int C, void* q, long long ldq, void* scales,
+                                  void* stream) {
+    if (!x || !q || !scales || pixels < 0 || C <= 0 || (C & 31) || (ldx & 7) || (ldq & 31) || ldx < C || ldq < C) return YV_ERR_ARG;
+    if (((uintptr_t)x | (uintptr_t)q) & 15) return YV_ERR_ARG;
+    if (pixels == 0) return YV_OK;
+    const long long items = pixels * (C >> 5);
+    hipLaunchKernelGGL(quant_mx_map_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const uint16_t*)x, ldx, pixels, C, (uint8_t*)q, ldq, (uint8_t*)scales);
+    return yv_launch_status();
+}
+
+// instance of cgemm_mx_kernel for M output pixels, N output channels: the rule of the bf16 kernel (conv_dma 8) - 128-wide
+// tiles for the layers of the large maps (>= 100 k output pixels) with more than 64 output channels, else 64-wide
+static int conv_mx_pick(long long M, int N) { return (M >= 100000 && N > 64) ? 1 : 0; }
+
+static int conv_mx_impl_one(const yv_mx_view* in0, const yv_mx_view* in1, int B, int Hout, int Wout, int ksize, int stride,
+                            const void* wq, const void* wscale, long long w_rows_pad, const float* bias, int Cout,
+                            void* out, int out_ld, void* out_q, void* out_s, int outq_ld, const void* res, int res_ld,
+                            int flags, void* stream) {
+    const bool two = in1 && in1->q;
+    const int c1 = two ? in1->c : 0;
+    const int Cin = in0->c + c1;
+    const long long kpad = ((long long)ksize * ksize * Cin + 127) / 128 * 128;
+    {   // 32-bit byte offsets: each source (+ one row and one pixel before it, 3 x 3) and the weights
+        const long long px = (long long)B * Hout * stride * Wout * stride;
+        if ((px + Wout * stride + 1) * in0->ld >= 0x7fffffffLL || (two && px * in1->ld >= 0x7fffffffLL) ||
+            (long long)Cout * kpad >= 0x7fffffffLL)
+            return YV_ERR_LIMIT;
+    }
+    ConvMxArgs a = {};
+    GemmArgs& g = a.g;
+    g.a0 = (const uint16_t*)in0->q; g.lda0 = in0->ld; g.c0 = in0->c; g.up0 = in0->up;
+    a.s0 = (const uint8_t*)in0->s;
+    if (two) { g.a1 = (const uint16_t*)in1->q; g.lda1 = in1->ld; g.c1 = c1; g.up1 = in1->up; a.s1 = (const uint8_t*)in1->s; }
+    g.Hin = Hout * stride; g.Win = Wout * stride;
+    g.Hout = Hout; g.Wout = Wout; g.ksize = ksize; g.stride = stride;
+    g.w = (const uint16_t*)wq; g.bias = bias;
+    g.M = B * Hout * Wout; g.N = Cout; g.K = (int)kpad;
+    g.out = out; g.ldo = out ? out_ld : 8; g.res = (const uint16_t*)res; g.ldres = res_ld; g.flags = flags;
+    g.splitk = 1;
+    // (the MX-map epilogue is always the staged one: "staged_epilogue" = 0 only switches the bf16 / f32-only launches)
+    g.staged = (g_opt_staged || out_q) && epi_can_stage(g);
+    if (out_q && !g.staged) return YV_ERR_ARG;
+    a.kreal = ksize * ksize * Cin;
+    a.sw = (const uint8_t*)wscale; a.rows_w = w_rows_pad;
+    a.oq = (uint8_t*)out_q; a.os = (uint8_t*)out_s; a.ldq = outq_ld;
+    const hipStream_t st = (hipStream_t)stream;
+    if (conv_mx_pick(g.M, Cout) == 1)
+        return launch_cmx<128, 2, 2>(a, st);
+    return launch_cmx<64, 4, 1>(a, st);
+}
+
+static int conv_mx_check(const yv_mx_view* in0, const yv_mx_view* in1, int B, int Hout, int Wout, int ksize, int stride,
+                         int Cout) {
+    if (!in0 || !in0->q || !in0->s || B <= 0 || Hout <= 0 || Wout <= 0 || Cout <= 0 || (Cout & 31)) return YV_ERR_ARG;
+    if (!(ksize == 1 || ksize == 3) || !(stride == 1 || stride == 2)) return YV_ERR_ARG;
+    const bool two = in1 && in1->q;
+    if (two && (ksize != 1 || !in1->s)) return YV_ERR_ARG;
+    if (ksize == 3 && in0->up) return YV_ERR_ARG;                 // the fused 2x upsample is a property of 1 x 1 inputs
+    if (in0->c <= 0 || (in0->c & 31) || (in0->ld & 31) || in0->ld < in0->c || (in0->up & ~1) || ((uintptr_t)in0->q & 15))
+        return YV_ERR_ARG;
+    if (two && (in1->c <= 0 || (in1->c & 31) || (in1->ld & 31) || in1->ld < in1->c || (in1->up & ~1) || ((uintptr_t)in1->q & 15)))
+        return YV_ERR_ARG;
+    if ((long long)B * Hout * Wout > 0x7fffffffLL) return YV_ERR_LIMIT;
+    return YV_OK;
+}
+
+extern "C" int yv_conv2d_mxfp8(const yv_mx_view* in0, const yv_mx_view* in1, int B, int Hout, int Wout, int ksize, int stride,
+                               const void* wq, const void* wscale, long long w_rows_pad, const float* bias, int Cout,
+                               void* out_bf16, int out_ld, void* out_q, void* out_scales, int outq_ld, const void* res,
+                               int res_ld, int flags, void* stream) {
+    int rc = conv_mx_check(in0, in1, B, Hout, Wout, ksize, stride, Cout);
+    if (rc != YV_OK) return rc;
+    if (!wq || !wscale || w_rows_pad < Cout || (!out_bf16 && !out_q)) return YV_ERR_ARG;
+    if (flags & ~(YV_EPI_BIAS | YV_EPI_SILU | YV_EPI_RES_BF16 | YV_EPI_OUT_F32)) return YV_ERR_ARG;
+    if ((flags & YV_EPI_BIAS) && !bias) return YV_ERR_ARG;
+    if ((flags & YV_EPI_RES_BF16) && (!res || (res_ld & 7) || ((uintptr_t)res & 15))) return YV_ERR_ARG;
+    if ((flags & YV_EPI_OUT_F32) && (!out_bf16 || out_q)) return YV_ERR_ARG;
+    if (out_bf16 && ((out_ld & 3) || out_ld < Cout)) return YV_ERR_ARG;
+    if (out_q && (!out_scales || (outq_ld & 31) || outq_ld < Cout || ((uintptr_t)out_q & 15))) return YV_ERR_ARG;
+    if (((uintptr_t)wq & 15)) return YV_ERR_ARG;
+    // sub-batches keep each source below 2 GB (images are independent), as yv_conv2d
+    const long long Hin = (long long)Hout * stride, Win = (long long)Wout * stride;
+    const bool two = in1 && in1->q;
+    const long long s0 = (Hin >> in0->up) * (Win >> in0->up) * in0->ld;
+    const long long s1 = two ? (Hin >> in1->up) * (Win >> in1->up) * in1->ld : 0;
+    const long long cap = 0x7ffffff0LL;
+    long long nb = (cap - (Win + 1) * in0->ld) / s0;
+    if (two && cap / s1 < nb) nb = cap / s1;
+    if (nb < 1) return YV_ERR_LIMIT;                              // a single image beyond 2 GB
+    if (nb > B) nb = B;
+    const long long opix = (long long)Hout * Wout;
+    const long long esz = (flags & YV_EPI_OUT_F32) ? 4 : 2;
+    for (long long b0 = 0; b0 < B; b0 += nb) {
+        const int n = (int)(B - b0 < nb ? B - b0 : nb);
+        yv_mx_view v0 = *in0, v1 = two ? *in1 : yv_mx_view{};
+        v0.q = (const unsigned char*)in0->q + b0 * s0;
+        v0.s = (const unsigned char*)in0->s + b0 * (s0 >> 5);
+        if (two) { v1.q = (const unsigned char*)in1->q + b0 * s1; v1.s = (const unsigned char*)in1->s + b0 * (s1 >> 5); }
+        rc = conv_mx_impl_one(&v0, two ? &v1 : nullptr, n, Hout, Wout, ksize, stride, wq, wscale, w_rows_pad, bias, Cout,
+                              out_bf16 ? (unsigned char*)out_bf16 + b0 * opix * out_ld * esz : nullptr, out_ld,
+                              out_q ? (unsigned char*)out_q + b0 * opix * outq_ld : nullptr,
+                              out_q ? (unsigned char*)out_scales + b0 * opix * (outq_ld >> 5) : nullptr, outq_ld,
+                              res ? (const unsigned char*)res + b0 * opix * res_ld * 2 : nullptr, res_ld, flags, stream);
+        if (rc != YV_OK) return rc;
+    }
+    return YV_OK;
+}
+
+extern "C" int yv_conv2d_mxfp8_instance(int B, int Hout, int Wout, int ksize, int stride, int Cin, int Cout) {
+    if (Cin <= 0 || (Cin & 31)) return YV_ERR_ARG;
+    unsigned char dummy[16] __attribute__((aligned(16)));
+    const yv_mx_view v = {dummy, dummy, Cin, Cin, 0};
+    const int rc = conv_mx_check(&v, nullptr, B, Hout, Wout, ksize, stride, Cout);
+    if (rc != YV_OK) return rc;
+    // first sub-batch of a dense source (pixel stride = Cin), as yv_conv2d_mxfp8 would take it
+    const long long Win = (long long)Wout * stride, s0 = (long long)Hout * stride * Win * Cin;
+    long long nb = (0x7ffffff0LL - (Win + 1) * Cin) / s0;
+    if (nb < 1) return YV_ERR_LIMIT;
+    if (nb > B) nb = B;
+    return conv_mx_pick(nb * Hout * Wout, Cout);
 }

@@ -47,6 +47,10 @@ class yv_view(C.Structure):
     _fields_ = [("ptr", _vp), ("ld", _i), ("c", _i), ("up", _i)]
 
 
+class yv_mx_view(C.Structure):
+    _fields_ = [("q", _vp), ("s", _vp), ("ld", _i), ("c", _i), ("up", _i)]
+
+
 _SIGS = {
     "yv_version": (_i, []),
     "yv_error_string": (C.c_char_p, [_i]),
@@ -61,6 +65,10 @@ _SIGS = {
     "yv_layernorm_mxfp8": (_i, [_vp, _sz, _vp, _vp, _i, _i, _f, _vp, _sz, _vp, C.c_longlong, _vp, _i, _vp]),
     "yv_mx_probe": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp]),
     "yv_quant_mxfp8": (_i, [_vp, C.c_longlong, C.c_longlong, _i, _vp, C.c_longlong, _vp, C.c_longlong, _vp]),
+    "yv_quant_mxfp8_map": (_i, [_vp, C.c_longlong, C.c_longlong, _i, _vp, C.c_longlong, _vp, _vp]),
+    "yv_conv2d_mxfp8": (_i, [C.POINTER(yv_mx_view), C.POINTER(yv_mx_view), _i, _i, _i, _i, _i, _vp, _vp, C.c_longlong, _vp, _i,
+                             _vp, _i, _vp, _vp, _i, _vp, _i, _i, _vp]),
+    "yv_conv2d_mxfp8_instance": (_i, [_i, _i, _i, _i, _i, _i, _i]),
     "yv_linear_mxfp8": (_i, [_vp, C.c_longlong, _vp, C.c_longlong, _vp, _vp, C.c_longlong, _vp, _i, _i, _i, _vp, _i, _i, _vp,
                              _i, _vp]),
     "yv_custom_nms_ws_bytes": (_sz, [_i, _i]),
@@ -855,6 +863,81 @@ def linear_mxfp8(aq: torch.Tensor, a_scale: torch.Tensor, wq: torch.Tensor, w_sc
         lib.yv_set_launch_timing(None, None)
         hook(M, N, K, e0, e1)
     return out
+
+
+# ------------------------------------------------------------- MXFP8 convolutions (YoloEngine(dtype="mxfp8"))
+def mx_map(B: int, H: int, W: int, C: int, device) -> tuple:
+    """An MX map: e4m3 bytes (B,H,W,C) uint8 + E8M0 scales (B,H,W,C/32) uint8 (C a multiple of 32)."""
+    assert C % 32 == 0
+    return (torch.zeros((B, H, W, C), dtype=torch.uint8, device=device),
+            torch.zeros((B, H, W, C // 32), dtype=torch.uint8, device=device))
+
+
+def mx_view(m: tuple, c_off: int, c: int, up: int = 0) -> "yv_mx_view":
+    """MX map (q, s) -> operand view of channels [c_off, c_off+c) (multiples of 32)."""
+    q, s = m
+    assert q.dtype == torch.uint8 and s.dtype == torch.uint8 and q.is_cuda and q.is_contiguous() and s.is_contiguous()
+    assert c_off % 32 == 0 and c % 32 == 0 and q.shape[-1] == 32 * s.shape[-1]
+    return yv_mx_view(C.c_void_p(q.data_ptr() + c_off), C.c_void_p(s.data_ptr() + c_off // 32), q.shape[-1], c, up)
+
+
+def quant_mxfp8_map(x: torch.Tensor, out: tuple, c_off: int = 0, c: Optional[int] = None, out_c_off: int = 0):
+    """bf16 NHWC x, channels [c_off, c_off+c) -> channels [out_c_off, ...) of the MX map `out` (rule of quant_mxfp8)."""
+    q, s = out
+    _chk_dev(x, q, s)
+    c = x.shape[-1] - c_off if c is None else c
+    assert x.dtype == torch.bfloat16 and c_off % 8 == 0 and out_c_off % 32 == 0
+    pixels = x.numel() // x.shape[-1]
+    assert q.numel() // q.shape[-1] == pixels
+    check(lib.yv_quant_mxfp8_map(C.c_void_p(x.data_ptr() + 2 * c_off), x.shape[-1], pixels, c,
+                                 C.c_void_p(q.data_ptr() + out_c_off), q.shape[-1], C.c_void_p(s.data_ptr() + out_c_off // 32),
+                                 _st()), "yv_quant_mxfp8_map")
+    return out
+
+
+def pad_k128(w: torch.Tensor) -> torch.Tensor:
+    """(Cout, K) -> (Cout, Kpad) with K zero-padded to a multiple of 128 (the MX convolution's weight depth)."""
+    K = w.shape[1]
+    kp = (K + 127) // 128 * 128
+    return w if kp == K else torch.cat([w, w.new_zeros(w.shape[0], kp - K)], 1).contiguous()
+
+
+def quant_conv_weight_mxfp8(w: torch.Tensor):
+    """Convolution weight (Cout, k*k*Cin) bf16, K order (ky,kx,cin) -> (wq (Cout, Kpad) e4m3, scales (Kpad/128, rows_pad, 4))."""
+    return quant_mxfp8(pad_k128(w.to(torch.bfloat16)).contiguous())
+
+
+def conv2d_mxfp8(in0: "yv_mx_view", in1: Optional["yv_mx_view"], B: int, Hout: int, Wout: int, ksize: int, stride: int,
+                 wq: torch.Tensor, wscale: torch.Tensor, bias: Optional[torch.Tensor], out: Optional[torch.Tensor] = None,
+                 out_c_off: int = 0, flags: int = 0, res: Optional[torch.Tensor] = None, res_c_off: int = 0,
+                 out_mx: Optional[tuple] = None, outq_c_off: int = 0):
+    """MXFP8 conv2d + bias (+SiLU, + bf16 residual): writes the bf16 (f32 with EPI_OUT_F32) view of `out` at channel offset
+    out_c_off and / or the MX map `out_mx` at channel offset outq_c_off (the bf16-rounded result, quantised)."""
+    _chk_dev(wq, wscale, bias, out, res)
+    Cout = wq.shape[0]
+    if bias is not None:
+        flags |= EPI_BIAS
+    esz = 4 if (flags & EPI_OUT_F32) else 2
+    optr = None if out is None else C.c_void_p(out.data_ptr() + esz * out_c_off)
+    rptr = None if res is None else C.c_void_p(res.data_ptr() + 2 * res_c_off)
+    qptr = sptr = None
+    qld = 0
+    if out_mx is not None:
+        q, s = out_mx
+        _chk_dev(q, s)
+        assert outq_c_off % 32 == 0
+        qptr, sptr, qld = C.c_void_p(q.data_ptr() + outq_c_off), C.c_void_p(s.data_ptr() + outq_c_off // 32), q.shape[-1]
+    check(lib.yv_conv2d_mxfp8(C.byref(in0), C.byref(in1) if in1 is not None else None, B, Hout, Wout, ksize, stride,
+                              _p(wq), _p(wscale), wscale.shape[1], _p(bias), Cout, optr, 0 if out is None else out.shape[-1],
+                              qptr, sptr, qld, rptr, 0 if res is None else res.shape[-1], flags, _st()), "yv_conv2d_mxfp8")
+    return out
+
+
+def conv2d_mxfp8_instance(B: int, Hout: int, Wout: int, ksize: int, stride: int, Cin: int, Cout: int) -> int:
+    """Kernel instance yv_conv2d_mxfp8 launches for this shape (0: 128 x 64 tiles, 1: 128 x 128 tiles)."""
+    r = lib.yv_conv2d_mxfp8_instance(B, Hout, Wout, ksize, stride, Cin, Cout)
+    check(min(r, 0), "yv_conv2d_mxfp8_instance")
+    return r
 
 
 def layernorm_mxfp8(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, q: torch.Tensor, scales: torch.Tensor, rows: int,

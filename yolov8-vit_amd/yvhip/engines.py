@@ -21,7 +21,7 @@ import torch
 from .guard import StepGuard
 from . import (set_option, EPI_GELU, EPI_OUT_F32, EPI_POSEMB, EPI_RES_BF16, EPI_RES_F32, EPI_SILU, YvError, attention, attention_mxfp8,
                cls_rows,
-               c2f_fused, conv2d, detect_decode, detect_tail, layernorm, layernorm_mxfp8, linear, linear_mxfp8, linear_mxfp8_q, quant_mxfp8, require_gpu, sppf_pool, stem_conv, view,
+               c2f_fused, conv2d, conv2d_mxfp8, detect_decode, mx_map, mx_view, quant_conv_weight_mxfp8, quant_mxfp8_map, detect_tail, layernorm, layernorm_mxfp8, linear, linear_mxfp8, linear_mxfp8_q, quant_mxfp8, require_gpu, sppf_pool, stem_conv, view,
                wrapper_head)
 
 # --------------------------------------------------------------------------------------- YOLOv8
@@ -110,6 +110,71 @@ def init_yolo_state(scale: str = "n", nc: int = 5, seed: int = 42, head_gain: fl
     return sd
 
 
+def _fused_c2f_block(p: dict) -> bool:
+    """The C2f blocks YoloEngine runs as one yv_c2f_fused launch (c <= 32)."""
+    c = p["cout"] // 2
+    return "a" not in p and p["add"] and p["cin"] == p["cout"] and c in (16, 32) and p["n"] in (1, 2)
+
+
+# layer kinds (kernel size, stride, whether Cin % 128 == 0) whose MXFP8 launches measured slower than the bf16 ones on the
+# MI355X (tools/conv_mx_bench.py under rocprofv3, YOLOv8m at 64 images, profiles/conv_mx_layers.txt; DESIGN.md section 10):
+# the 1 x 1 layers, +19 % / +21 %.  They stay bf16.
+MX_SLOW_KINDS: Tuple[Tuple[int, int, bool], ...] = ((1, 1, False), (1, 1, True))
+# narrowest layers kept in bf16 for accuracy: a convolution reading or writing fewer than 96 channels stays bf16.  Measured
+# (tools/mx_plan_accuracy.py): with every eligible layer YOLOv8n's smallest per-anchor cosine against the bf16 engine is 0.975,
+# with this floor 0.996 (s 0.992, m 0.994) - the floor of 0.99 holds for every scale.
+MX_MIN_WIDTH = 96
+
+
+def mx_conv_plan(scale: str, nc: int = 5, speed_filter: bool = True, min_width: Optional[int] = None) -> List[str]:
+    """Convolutions YoloEngine(dtype="mxfp8") runs on the block-scaled MXFP8 kernel (yv_conv2d_mxfp8), in execution order.
+    A convolution qualifies when every channel count and channel offset it reads (input views, concat sources) and its
+    output channels are multiples of 32 (one E8M0 scale per 32 channels of a pixel).  Stays bf16: the stem (3 input
+    channels), model.1 of scales whose stem writes 48 / 16 / 32 channels below that, whole C2f blocks whose hidden width
+    c is not a multiple of 32 (their bottleneck chunks straddle scale blocks; YOLOv8m model.2, c = 48), the fused C2f
+    blocks (one yv_c2f_fused launch), SPPF's cv2 (reads the bf16 max-pool chunks) and the last 1 x 1 convolutions of the
+    head (read by yv_detect_tail / the decode); then the layer kinds of MX_SLOW_KINDS (speed_filter) and the layers
+    narrower than MX_MIN_WIDTH channels (min_width overrides it)."""
+    a32 = lambda *v: all(x % 32 == 0 for x in v)
+    cand: List[Tuple[str, int, int, List[int], int]] = []        # (key, k, stride, source widths, cout)
+    width = {}
+    for idx, kind, p in yolo_layers(scale):
+        pre = f"model.{idx}."
+        width[idx] = p["cout"]
+        if kind == "conv" and a32(p["cin"], p["cout"], width[idx - 1]):
+            cand.append((pre + "conv", 3, 2, [p["cin"]], p["cout"]))
+        elif kind == "c2f" and not _fused_c2f_block(p):
+            c = p["cout"] // 2
+            srcs = [width[p["a"][0]], width[p["b"][0]]] if "a" in p else [p["cin"]]
+            if not a32(c, *srcs):
+                continue
+            cand.append((pre + "cv1.conv", 1, 1, srcs, 2 * c))
+            for j in range(p["n"]):
+                cand += [(pre + f"m.{j}.cv1.conv", 3, 1, [c], c), (pre + f"m.{j}.cv2.conv", 3, 1, [c], c)]
+            cand.append((pre + "cv2.conv", 1, 1, [(2 + p["n"]) * c], p["cout"]))
+        elif kind == "sppf" and a32(p["cin"], p["cin"] // 2):
+            cand.append((pre + "cv1.conv", 1, 1, [p["cin"]], p["cin"] // 2))
+    ch = (_c(256, scale), _c(512, scale), _c(1024, scale))
+    c2 = max(16, ch[0] // 4, REG_MAX * 4)
+    c3 = max(ch[0], min(nc, 100))
+    for s in range(3):
+        if a32(ch[s], c2 + c3):
+            cand.append((f"det{s}.0", 3, 1, [ch[s]], c2 + c3))
+        if a32(c2):
+            cand.append((f"model.22.cv2.{s}.1.conv", 3, 1, [c2], c2))
+        if a32(c2, c3):
+            cand.append((f"model.22.cv3.{s}.1.conv", 3, 1, [c3], c3))
+    mw = MX_MIN_WIDTH if min_width is None else min_width
+    out: List[str] = []
+    for key, k, st, srcs, co in cand:
+        if speed_filter and (k, st, sum(srcs) % 128 == 0) in MX_SLOW_KINDS:
+            continue
+        if min(*srcs, co) < mw:
+            continue
+        out.append(key)
+    return out
+
+
 def _khwc(w: torch.Tensor) -> torch.Tensor:
     """(Cout,Cin,k,k) f32 -> (Cout, k*k*Cin) bf16 with K order (ky,kx,cin)."""
     co = w.shape[0]
@@ -120,10 +185,16 @@ class YoloEngine:
     """images (B,S,S,3) u8 RGB on the device -> boxes (B,A,4) f32 xyxy, scores (B,A,nc) f32."""
 
     def __init__(self, state: Dict[str, torch.Tensor], scale: str = "n", nc: int = 5, size: int = 640,
-                 device: str = "cuda:0"):
+                 device: str = "cuda:0", dtype: str = "bf16"):
+        """dtype "bf16" (default) or "mxfp8": the convolutions of mx_conv_plan(scale, nc) then run on OCP e4m3 operands with
+        one E8M0 scale per 32 input channels (yv_conv2d_mxfp8; weights quantised once here), their inputs kept as MX maps
+        next to the bf16 activations; the rest of the network is unchanged."""
         require_gpu()
         if size % 32:
             raise YvError("input size must be a multiple of 32")
+        if dtype not in ("bf16", "mxfp8"):
+            raise YvError("dtype must be 'bf16' or 'mxfp8'")
+        self.dtype = dtype
         self.scale, self.nc, self.size, self.dev = scale, nc, size, torch.device(device)
         self.layers = yolo_layers(scale)
         self.w: Dict[str, torch.Tensor] = {}
@@ -162,6 +233,14 @@ class YoloEngine:
         # fused Detect tail (yv_detect_tail: last 1 x 1 convolutions + DFL decode + sigmoid in one launch, bit-identical)
         self.fused_tail = self.c2 == 64 and nc <= 16 and self.c3 in (64, 128, 192)
         self.fused_c2f = True                    # backbone C2f blocks with c <= 32 in one launch each (yv_c2f_fused)
+        self.mx_layers: List[str] = mx_conv_plan(scale, nc) if dtype == "mxfp8" else []
+        self.wq: Dict[str, tuple] = {}
+        self._specs: Dict[str, tuple] = {}
+        if self.mx_layers:
+            for key in self.mx_layers:           # (e4m3 (Cout, Kpad), K-step-major scales)
+                self.wq[key] = quant_conv_weight_mxfp8(self.w[key])
+            self._specs = {sp[0]: sp for sp in self._conv_specs()}
+            torch.cuda.synchronize(self.dev)
         self._bufs: Dict[int, dict] = {}
         self.guard = StepGuard()                 # one replay of the launch list at a time (callers may be threads)
         self.A = sum((size // s) ** 2 for s in (8, 16, 32))
@@ -191,6 +270,13 @@ class YoloEngine:
             bufs[f"det{s}.hc"] = bf(hs, self.c2 + self.c3)
             bufs[f"det{s}.box"] = f32(hs, 4 * REG_MAX)
             bufs[f"det{s}.cls"] = f32(hs, self.ncp)
+        if self.mx_layers:
+            # every bf16 activation an MX convolution reads gets an MX map next to it, written by its producers
+            flat = {f"{k}{i}": t for k in ("out", "y", "t") for i, t in bufs[k].items()}
+            flat.update({f"det{s}.{x}": bufs[f"det{s}.{x}"] for s in range(3) for x in ("hb", "hc")})
+            bufs["flat"] = flat
+            bufs["mx"] = {n: mx_map(B, flat[n].shape[1], flat[n].shape[2], flat[n].shape[3], self.dev)
+                          for n in self._mx_sources()}
         self._bufs[B] = bufs
         return bufs
 
@@ -219,6 +305,120 @@ class YoloEngine:
         conv2d(view(y, 0, (2 + p["n"]) * c), None, B, h, h, 1, 1, self.w[pre + "cv2.conv"], self.b[pre + "cv2.conv"],
                out, 0, EPI_SILU)
 
+    # -- MXFP8 detector (dtype="mxfp8")
+    def _conv_specs(self):
+        """Every convolution of the step in order: (key, sources [(buffer, c_off, c, up)], k, stride, out buffer, out c_off,
+        residual c_off or None).  Buffers: out{idx}, y{idx}, t{idx}, det{s}.hb / .hc."""
+        specs = []
+        for idx, kind, p in self.layers:
+            pre = f"model.{idx}."
+            if kind == "conv":
+                specs.append((pre + "conv", [(f"out{idx - 1}", 0, p["cin"], 0)], 3, 2, f"out{idx}", 0, None))
+            elif kind == "c2f":
+                if "a" not in p and self.fused_c2f and _fused_c2f_block(p):
+                    continue
+                c = p["cout"] // 2
+                if "a" in p:
+                    (ia, ua), (ib, ub) = p["a"], p["b"]
+                    wa, wb = self.layers_by_idx[ia]["cout"], self.layers_by_idx[ib]["cout"]
+                    srcs = [(f"out{ia}", 0, wa, ua), (f"out{ib}", 0, wb, ub)]
+                else:
+                    srcs = [(f"out{idx - 1}", 0, p["cin"], 0)]
+                specs.append((pre + "cv1.conv", srcs, 1, 1, f"y{idx}", 0, None))
+                for j in range(p["n"]):
+                    src = (1 + j) * c
+                    specs.append((pre + f"m.{j}.cv1.conv", [(f"y{idx}", src, c, 0)], 3, 1, f"t{idx}", 0, None))
+                    specs.append((pre + f"m.{j}.cv2.conv", [(f"t{idx}", 0, c, 0)], 3, 1, f"y{idx}", src + c,
+                                  src if p["add"] else None))
+                specs.append((pre + "cv2.conv", [(f"y{idx}", 0, (2 + p["n"]) * c, 0)], 1, 1, f"out{idx}", 0, None))
+            elif kind == "sppf":
+                specs.append((pre + "cv1.conv", [(f"out{idx - 1}", 0, p["cin"], 0)], 1, 1, f"y{idx}", 0, None))
+        c2, c3 = self.c2, self.c3
+        for s, fidx in enumerate((15, 18, 21)):
+            w = self.layers_by_idx[fidx]["cout"]
+            specs.append((f"det{s}.0", [(f"out{fidx}", 0, w, 0)], 3, 1, f"det{s}.hb", 0, None))
+            specs.append((f"model.22.cv2.{s}.1.conv", [(f"det{s}.hb", 0, c2, 0)], 3, 1, f"det{s}.hc", 0, None))
+            specs.append((f"model.22.cv3.{s}.1.conv", [(f"det{s}.hb", c2, c3, 0)], 3, 1, f"det{s}.hc", c2, None))
+        return specs
+
+    @property
+    def layers_by_idx(self):
+        return {idx: p for idx, _, p in self.layers}
+
+    def _mx_sources(self):
+        mx = set(self.mx_layers)
+        return sorted({b for key, srcs, *_ in self._specs.values() if key in mx for b, *_ in srcs})
+
+    def _produced(self, bufs, name: str, c_off: int, c: int):
+        """A bf16 producer wrote channels [c_off, c_off+c) of `name`: bring its MX map up to date."""
+        if name in bufs["mx"]:
+            quant_mxfp8_map(bufs["flat"][name], bufs["mx"][name], c_off, c, c_off)
+
+    def _conv(self, bufs, B: int, h: int, spec):
+        key, srcs, k, st, oname, ooff, roff = spec
+        out = bufs["flat"][oname]
+        flags = EPI_SILU | (EPI_RES_BF16 if roff is not None else 0)
+        res = out if roff is not None else None
+        cout = self.b[key].shape[0]
+        if key in self.wq:
+            wq, ws = self.wq[key]
+            v = [mx_view(bufs["mx"][b], off, c, up) for b, off, c, up in srcs]
+            conv2d_mxfp8(v[0], v[1] if len(v) > 1 else None, B, h, h, k, st, wq, ws, self.b[key], out, ooff, flags,
+                         res=res, res_c_off=roff or 0, out_mx=bufs["mx"].get(oname), outq_c_off=ooff)
+        else:
+            v = [view(bufs["flat"][b], off, c, up) for b, off, c, up in srcs]
+            conv2d(v[0], v[1] if len(v) > 1 else None, B, h, h, k, st, self.w[key], self.b[key], out, ooff, flags,
+                   res=res, res_c_off=roff or 0)
+            self._produced(bufs, oname, ooff, cout)
+
+    def _forward_raw_mx(self, images: torch.Tensor, B: int, bufs: dict, tail: bool):
+        """_forward_raw with the convolutions of self.mx_layers on MX operands (same launch order otherwise)."""
+        o = bufs["out"]
+        specs = self._specs
+        for idx, kind, p in self.layers:
+            pre = f"model.{idx}."
+            h = bufs["h"][idx]
+            if kind == "stem":
+                stem_conv(images, self.w[pre + "conv"], self.b[pre + "conv"], o[0])
+                self._produced(bufs, "out0", 0, p["cout"])
+            elif kind == "conv":
+                self._conv(bufs, B, h, specs[pre + "conv"])
+            elif kind == "c2f":
+                if "a" not in p and self.fused_c2f and _fused_c2f_block(p):
+                    self._c2f(idx, p, view(o[idx - 1], 0, p["cin"]), None, B, bufs)
+                    self._produced(bufs, f"out{idx}", 0, p["cout"])
+                    continue
+                self._conv(bufs, B, h, specs[pre + "cv1.conv"])
+                for j in range(p["n"]):
+                    self._conv(bufs, B, h, specs[pre + f"m.{j}.cv1.conv"])
+                    self._conv(bufs, B, h, specs[pre + f"m.{j}.cv2.conv"])
+                self._conv(bufs, B, h, specs[pre + "cv2.conv"])
+            elif kind == "sppf":
+                y = bufs["y"][idx]
+                c_ = p["cin"] // 2
+                self._conv(bufs, B, h, specs[pre + "cv1.conv"])
+                sppf_pool(y, c_)
+                conv2d(view(y, 0, 4 * c_), None, B, h, h, 1, 1, self.w[pre + "cv2.conv"], self.b[pre + "cv2.conv"],
+                       o[idx], 0, EPI_SILU)
+                self._produced(bufs, f"out{idx}", 0, p["cout"])
+        box_l, cls_l = [], []
+        c2, c3 = self.c2, self.c3
+        for s, fidx in enumerate((15, 18, 21)):
+            hs = bufs["h"][fidx]
+            hc = bufs[f"det{s}.hc"]
+            for key in (f"det{s}.0", f"model.22.cv2.{s}.1.conv", f"model.22.cv3.{s}.1.conv"):
+                self._conv(bufs, B, hs, specs[key])
+            if not tail:
+                box_l.append(hc)
+                continue
+            k = f"model.22.cv2.{s}.2"
+            conv2d(view(hc, 0, c2), None, B, hs, hs, 1, 1, self.w[k], self.b[k], bufs[f"det{s}.box"], 0, EPI_OUT_F32)
+            k = f"model.22.cv3.{s}.2.pad"
+            conv2d(view(hc, c2, c3), None, B, hs, hs, 1, 1, self.w[k], self.b[k], bufs[f"det{s}.cls"], 0, EPI_OUT_F32)
+            box_l.append(bufs[f"det{s}.box"])
+            cls_l.append(bufs[f"det{s}.cls"])
+        return box_l, cls_l
+
     def forward_raw(self, images: torch.Tensor):
         """Runs backbone+neck+head; returns per-scale (box logits f32, class logits f32) NHWC tensors.  Called with `self.guard`
         held (as __call__ does) the engine-owned buffers themselves are returned - valid until the caller leaves the guard;
@@ -239,6 +439,8 @@ class YoloEngine:
         if S != self.size or images.shape[2] != self.size:
             raise YvError(f"engine built for {self.size}x{self.size}")
         bufs = self._buffers(B)
+        if self.mx_layers:
+            return self._forward_raw_mx(images, B, bufs, tail)
         o = bufs["out"]
         for idx, kind, p in self.layers:
             pre = f"model.{idx}."
