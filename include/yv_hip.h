@@ -81,6 +81,30 @@ int yv_linear_mxfp8(const void* Aq, long long lda, const void* Ascale, long long
                     long long w_rows_pad, const float* bias, int M, int N, int K, void* out, int ldo, int flags,
                     const int32_t* m_dev, int m_mul, void* stream);
 
+/* MXFP8 training (VitTrainer(dtype="mxfp8")).
+ * yv_quant_mxfp8_2d: x (T, C) bf16 (row stride ldx, C a multiple of 128) read once -> either or both of
+ *   row form    q (T, C) bytes (row stride ldq) + scales (C/128, rows_pad, 4): exactly what yv_quant_mxfp8 writes;
+ *   column form qt (C, T_pad) bytes (row stride ldqt) + scales_t (T_pad/128, c_rows_pad, 4): exactly what yv_quant_mxfp8
+ *               writes for x^T with T zero-padded to T_pad (a multiple of 128): the token-reduction operands of a weight
+ *               gradient.  Pass null q / scales or qt / scales_t to skip a form. */
+int yv_quant_mxfp8_2d(const void* x, long long ldx, long long T, int C, void* q, long long ldq, void* scales, long long rows_pad,
+                      void* qt, long long ldqt, void* scales_t, long long c_rows_pad, long long T_pad, void* stream);
+/* yv_linear_mxfp8 with the training epilogues of yv_linear_ex: YV_EPI_RES_F32 with a separate f32 residual source res_f32
+ * (same layout as out; null: read-modify-write of out), YV_EPI_SAVE_PRE (with YV_EPI_GELU; pre-activation -> aux) and
+ * YV_EPI_GELU_BWD (out = bf16(acc + bias) * gelu'(aux)); aux is bf16 with row stride ldaux (multiple of 8). */
+int yv_linear_mxfp8_ex(const void* Aq, long long lda, const void* Ascale, long long a_rows_pad, const void* Wq, const void* Wscale,
+                       long long w_rows_pad, const float* bias, int M, int N, int K, void* out, int ldo, int flags,
+                       const float* res_f32, void* aux, int ldaux, void* stream);
+/* Diagnostic: the kernel instance an MX linear of this shape and flags launches with dense operands (0: 128 x 128 tiles,
+ * gemm_mx_kernel; 1: the persistent kernel), or a negative YV_ERR_* code if the arguments are not accepted. */
+int yv_linear_mxfp8_instance(int M, int N, int K, int flags);
+/* MX weight gradient: dW (N, K) f32 (row stride ldw) = dY^T . X over T_pad tokens, from the column forms of
+ * yv_quant_mxfp8_2d: dYt (N, T_pad) bytes (row stride ldy) + scales (T_pad/128, dy_rows_pad, 4), Xt (K, T_pad) bytes (row
+ * stride ldx) + scales (T_pad/128, x_rows_pad, 4).  Split over tokens through the stream's workspace (yv_set_workspace);
+ * option "wgrad_mx_split" > 0 forces the number of slices (1 = no split). */
+int yv_wgrad_mxfp8(const void* dYt, long long ldy, const void* sdy, long long dy_rows_pad, const void* Xt, long long ldx,
+                   const void* sx, long long x_rows_pad, int T_pad, int N, int K, float* dW, int ldw, void* stream);
+
 /* Measurement hook (bench.py): the NEXT LDS-DMA GEMM launch issued by the calling thread (yv_linear / yv_linear_ex /
  * yv_linear_nn) records its start / stop timestamps into these hipEvent_t handles through hipExtLaunchKernel, i.e. from
  * the kernel's own dispatch packet.  Either may be null; the setting is consumed by that launch. */

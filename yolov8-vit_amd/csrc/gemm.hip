@@ -1008,6 +1008,11 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_mx_kernel(MxArgs a) {
         const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, x = bid & 7;
         bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
     }
+    // split-K (the MX weight gradient, yv_wgrad_mxfp8: few output tiles, long token reduction): the slices of one tile are
+    // neighbouring workgroups; partial sums go to g.partial, splitk_reduce_kernel adds them in slice order
+    const int nsplit = g.splitk > 1 ? g.splitk : 1;
+    const int slice = bid % nsplit;
+    bid /= nsplit;
     int tm, tn;
     {
         const int GM = g.group_m, per = GM * g.tiles_n;
@@ -1019,6 +1024,7 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_mx_kernel(MxArgs a) {
     }
     const int m0 = tm * BM, n0 = tn * BN;
     if (m0 >= M) return;
+    const long long ldwb = g.ldw > 0 ? g.ldw : g.K;            // W row stride in bytes (0: dense, K)
     const int lrow = lane >> 3, lch = lane & 7;
     const uint8_t* a_src[A_INS];
     const uint8_t* w_src[W_INS];
@@ -1032,7 +1038,7 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_mx_kernel(MxArgs a) {
     for (int j = 0; j < W_INS; ++j) {
         const int r = (j * NW + wave) * 8 + lrow;
         int n = n0 + r; n = n < g.N ? n : g.N - 1;
-        w_src[j] = (const uint8_t*)g.w + (long long)n * g.K + ((lch ^ (r & 7)) << 4);
+        w_src[j] = (const uint8_t*)g.w + (long long)n * ldwb + ((lch ^ (r & 7)) << 4);
     }
     // scale DMA: the tile's BM A dwords then its BN W dwords, 4 dwords (16 bytes) per lane, lane-linear in LDS; the
     // (BM + BN) / 256 wave-instructions are dealt to waves 0, 1, ...
@@ -1063,12 +1069,13 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_mx_kernel(MxArgs a) {
     for (int i = 0; i < NF; ++i)
 #pragma unroll
         for (int j = 0; j < MF; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    const int nk = g.K >> 7;
-    issue(0, 0);
+    const int nk_all = g.K >> 7;
+    const int kt0 = (int)((long long)nk_all * slice / nsplit), nk = (int)((long long)nk_all * (slice + 1) / nsplit);
+    issue(kt0, 0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    for (int kt = 0; kt < nk; ++kt) {
-        const int cur = kt & 1;
+    for (int kt = kt0; kt < nk; ++kt) {
+        const int cur = (kt - kt0) & 1;
         if (kt + 1 < nk) issue(kt + 1, cur ^ 1);
         const unsigned char* A = smem + cur * STAGE;
         const unsigned char* W = A + A_BYTES;
@@ -1098,6 +1105,20 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_mx_kernel(MxArgs a) {
                 acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fw[i], fa[j], acc[i][j], 0, 0, 0, scw[i], 0, sca[j]);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
+    }
+    if (nsplit > 1) {                          // raw partial sums; the epilogue runs in splitk_reduce_kernel
+        float* P = g.partial + (long long)slice * g.M * g.N;
+#pragma unroll
+        for (int j = 0; j < MF; ++j) {
+            const int m = m0 + wrow_m + j * 16 + fr;
+            if (m >= M) continue;
+#pragma unroll
+            for (int i = 0; i < NF; ++i) {
+                const int n = n0 + wrow_n + i * 16 + fq * 4;
+                if (n < g.N) *(float4*)(P + (long long)m * g.N + n) = make_float4(acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]);
+            }
+        }
+        return;
     }
     finish_tile<MF, NF>(g, acc, M, m0, n0, wrow_m, wrow_n, lane, wave, smem);
 }
@@ -1514,6 +1535,86 @@ __global__ __launch_bounds__(256) void quant_mx_map_kernel(const uint16_t* __res
     dst[0] = make_uint4(out[0], out[1], out[2], out[3]);
     dst[1] = make_uint4(out[4], out[5], out[6], out[7]);
     sc[p * (ldq >> 5) + b] = (uint8_t)(e + 127);
+}
+
+// 32 bf16-representable values -> 8 dwords of e4m3 bytes; returns the block exponent (the arithmetic of quant_mx_kernel)
+__device__ __forceinline__ int mx_quant32(const float (&v)[32], uint32_t (&out)[8]) {
+    float amax = 0.f;
+#pragma unroll
+    for (int i = 0; i < 32; ++i) amax = fmaxf(amax, fabsf(v[i]));
+    const int e = mx_block_exp(amax);
+    const float inv = ldexpf(1.0f, -e);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        int pq = 0;
+        pq = __builtin_amdgcn_cvt_pk_fp8_f32(v[4 * i] * inv, v[4 * i + 1] * inv, pq, false);
+        pq = __builtin_amdgcn_cvt_pk_fp8_f32(v[4 * i + 2] * inv, v[4 * i + 3] * inv, pq, true);
+        out[i] = (uint32_t)pq;
+    }
+    return e;
+}
+
+// Two-form quantiser (yv_quant_mxfp8_2d; the MX trainer's operands).  A workgroup stages a tile of 64 rows (t) x 128 columns
+// (c) of the bf16 input in LDS (rows past T read as zeros) and writes, from the one read:
+//   row form:    thread (row tid / 4, block tid % 4): the 32-column block of quant_mx_kernel - bytes and scale identical;
+//   column form: thread (column tid % 128, half tid / 128): the 32 rows of that column as one MX block of the TRANSPOSE, i.e.
+//                bytes (C, T_pad) (row stride ldqt) and scales K-step-major along t, (T_pad/128, c_rows_pad, 4) - what
+//                quant_mx_kernel writes for x^T padded with zero rows up to T_pad (the weight-gradient operands).
+// LDS rows are 272 bytes (16-byte pad): the row-form reads of a wave (16 rows x 4 blocks) spread over the banks; the column-form
+// reads of a wave are 64 consecutive bf16 of one row.
+__global__ __launch_bounds__(256) void quant_mx_2d_kernel(const uint16_t* __restrict__ x, long long ldx, long long T, int C,
+                                                          uint8_t* __restrict__ q, long long ldq, uint8_t* __restrict__ sc,
+                                                          long long rows_pad, uint8_t* __restrict__ qt, long long ldqt,
+                                                          uint8_t* __restrict__ sct, long long c_rows_pad) {
+    constexpr int PITCH = 272;
+    __shared__ __attribute__((aligned(16))) unsigned char tile[64 * PITCH];
+    const int tid = threadIdx.x;
+    const long long t0 = (long long)blockIdx.x * 64;
+    const int c0 = blockIdx.y * 128;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int id = tid + 256 * i, r = id >> 4, ch = id & 15;
+        uint4 u = make_uint4(0u, 0u, 0u, 0u);
+        if (t0 + r < T) u = *(const uint4*)(x + (t0 + r) * ldx + c0 + ch * 8);
+        *(uint4*)(tile + r * PITCH + ch * 16) = u;
+    }
+    __syncthreads();
+    if (q) {
+        const int r = tid >> 2, b = tid & 3;
+        const long long t = t0 + r;
+        if (t < T) {
+            float v[32];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const uint4 u = *(const uint4*)(tile + r * PITCH + b * 64 + c * 16);
+                const uint32_t w[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    v[c * 8 + 2 * i] = bf16_to_f32((uint16_t)(w[i] & 0xffff));
+                    v[c * 8 + 2 * i + 1] = bf16_to_f32((uint16_t)(w[i] >> 16));
+                }
+            }
+            uint32_t out[8];
+            const int e = mx_quant32(v, out);
+            uint4* dst = (uint4*)(q + t * ldq + c0 + b * 32);
+            dst[0] = make_uint4(out[0], out[1], out[2], out[3]);
+            dst[1] = make_uint4(out[4], out[5], out[6], out[7]);
+            sc[((long long)(c0 >> 7) * rows_pad + t) * 4 + b] = (uint8_t)(e + 127);
+        }
+    }
+    if (qt) {
+        const int c = tid & 127, h = tid >> 7;
+        float v[32];
+#pragma unroll
+        for (int i = 0; i < 32; ++i) v[i] = bf16_to_f32(*(const uint16_t*)(tile + (h * 32 + i) * PITCH + c * 2));
+        uint32_t out[8];
+        const int e = mx_quant32(v, out);
+        const long long tb = (t0 >> 5) + h;                      // 32-row block of t
+        uint4* dst = (uint4*)(qt + (long long)(c0 + c) * ldqt + tb * 32);
+        dst[0] = make_uint4(out[0], out[1], out[2], out[3]);
+        dst[1] = make_uint4(out[4], out[5], out[6], out[7]);
+        sct[((tb >> 2) * c_rows_pad + c0 + c) * 4 + (tb & 3)] = (uint8_t)(e + 127);
+    }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2027,7 +2128,6 @@ template <int MF, bool F32OUT, int DIAG = 0 /* tools/gemm_lab.hip only: cycle su
                              its activation / weight pieces (issued by waves 0 / 1) */>
 __global__ __launch_bounds__(512) void gemm_p9_kernel(GemmArgs g) {
     constexpr int NF = 4, P = (MF + 1) / 2;
-    static_assert(!MX || EXT == 0, "MX: no trainer epilogues");
     static_assert(EXT == 0 || (!F32OUT && MF <= 7), "aux epilogues: bf16 output, tiles of up to 224 rows (registers)");
     constexpr int MF0 = (MF + 1) / 2, MF1 = MF - MF0;          // DMA halves of the activation rows of a group (piece bookkeeping of p8)
     constexpr int RG = MF * 16, BM = 2 * RG;
@@ -2580,6 +2680,19 @@ int launch_p9(GemmArgs& g, hipStream_t st, int rows = 0, bool mx = false) {
         }
     }
     if (best <= 192 && best >= 160 && !even_nk) best = 224;
+    // MX trainer epilogues.  Reached by tests/test_gpu_mx_train.py::test_mx_linear_ex_epilogues: 160 rows by the ViT-B/16 shapes
+    // (M = 6,304, N = 3,072, K = 768), 224 by the ViT-L/16 shapes (N = 4,096, K = 1,024) and by an odd K / 128 (K = 640);
+    // each height (160 / 192 / 224) also forced through "linear_p8_rows" by test_mx_linear_ex_persistent_tile_heights
+    if (mx && ext == 1) switch (best) {           // MX trainer: fc1 forward (GELU + saved pre-activation)
+        case 192: return launch_p9_inst<6, false, 1, true>(g, st, n_cu);
+        case 160: return launch_p9_inst<5, false, 1, true>(g, st, n_cu);
+        default: return launch_p9_inst<7, false, 1, true>(g, st, n_cu);
+    }
+    if (mx && ext == 2) switch (best) {           // MX trainer: fc2 data gradient (GELU backward)
+        case 192: return launch_p9_inst<6, false, 2, true>(g, st, n_cu);
+        case 160: return launch_p9_inst<5, false, 2, true>(g, st, n_cu);
+        default: return launch_p9_inst<7, false, 2, true>(g, st, n_cu);
+    }
     if (mx) switch (best) {
         case 224: return f32out ? launch_p9_inst<7, true, 0, true>(g, st, n_cu) : launch_p9_inst<7, false, 0, true>(g, st, n_cu);
         case 192: return f32out ? launch_p9_inst<6, true, 0, true>(g, st, n_cu) : launch_p9_inst<6, false, 0, true>(g, st, n_cu);
@@ -2871,7 +2984,8 @@ extern "C" int yv_quant_mxfp8(const void* x, long long ldx, long long rows, int 
 static int linear_mx_impl(const void* Aq, long long lda, const void* Ascale, long long a_rows_pad, const void* Wq,
                           const void* Wscale, long long w_rows_pad, const float* bias, int M, int N, int K, void* out,
                           int ldo, int flags, const int32_t* m_dev, int m_mul, void* out_q, long long ldq, void* out_scales,
-                          long long out_rows_pad, void* stream);
+                          long long out_rows_pad, void* stream, const float* res_f32 = nullptr, void* aux = nullptr,
+                          int ldaux = 0);
 
 extern "C" int yv_linear_mxfp8(const void* Aq, long long lda, const void* Ascale, long long a_rows_pad, const void* Wq,
                                const void* Wscale, long long w_rows_pad, const float* bias, int M, int N, int K, void* out,
@@ -2891,22 +3005,84 @@ extern "C" int yv_linear_mxfp8_q(const void* Aq, long long lda, const void* Asca
                           flags | YV_EPI_OUT_MXFP8, m_dev, m_mul, out_q, ldq, out_scales, out_rows_pad, stream);
 }
 
+// Instance of an MX linear (0: gemm_mx_kernel 128 x 128, 1: persistent gemm_p9_kernel<..., MX>).  One rule for
+// linear_mx_impl and the diagnostic yv_linear_mxfp8_instance.  Instances reached by tests/test_gpu_mx_train.py:
+//   1 with SAVE_PRE / GELU_BWD / RES_F32 epilogues: test_mx_linear_ex_epilogues (M = 6,304 / 12,608 shapes; the tile height inside
+//     the persistent kernel is launch_p9's choice: see the tests named at its MX switch arms);
+//   0 with the same epilogues: test_mx_linear_ex_epilogues (N = 768 at M = 6,304, M < 2,048) and every split-K weight gradient
+//     (test_wgrad_mxfp8_exact).
+static int mx_linear_pick(int M, int N, int K, long long lda, int ldo, long long a_rows, long long w_rows, int flags, int ldaux) {
+    const int nkm = K >> 7;
+    const bool f32o = flags & (YV_EPI_RES_F32 | YV_EPI_OUT_F32);
+    const bool ext = flags & (YV_EPI_SAVE_PRE | YV_EPI_GELU_BWD);
+    if (g_opt_p8 >= 3 && g_opt_variant == 1 && !(N & 255) && N <= 4096 && nkm >= 2 && M >= 2048 &&
+        !((flags & YV_EPI_GELU) && f32o) && !((flags & YV_EPI_OUT_MXFP8) && f32o) && !(f32o && (nkm & 1)) &&
+        (long long)((M + 159) / 160) * (N >> 8) >= 192 &&
+        (long long)(M - 1) * lda + K < 0x7fffffffLL && (long long)N * K < 0x7fffffffLL &&
+        ((long long)(M - 1) * ldo + N) * 4 < 0x7fffffffLL && (long long)(K >> 7) * a_rows * 4 < 0x7fffffffLL &&
+        (long long)(K >> 7) * w_rows * 4 < 0x7fffffffLL && (!ext || ((long long)(M - 1) * ldaux + N) * 2 < 0x7fffffffLL))
+        return 1;
+    return 0;
+}
+
+// gemm_mx_kernel<128, 128, 2, 2> (split-K when g.splitk > 1: partials into g.partial, then splitk_reduce_kernel)
+static int launch_mx128(MxArgs& a, hipStream_t stream) {
+    GemmArgs& g = a.g;
+    g.tiles_m = (g.M + 127) / 128; g.tiles_n = (g.N + 127) / 128;
+    const int S = g.splitk > 1 ? g.splitk : 1;
+    // (a 4-stage ring with ONE workgroup per CU and three K steps in flight was built in round 1, measured 35 % slower than two
+    // co-resident 2-stage workgroups, and removed in round 2: see DESIGN.md section 6, "MX deep ring")
+    const int threads = 256;
+    const size_t lds = 2 * (size_t)(128 * 128 * 2 + 1024);
+    auto kern = gemm_mx_kernel<128, 128, 2, 2>;
+    if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+        return YV_ERR_LAUNCH;
+    const unsigned grid = (unsigned)(g.tiles_m * g.tiles_n * S);
+    if (t_time_start || t_time_stop) {
+        hipExtLaunchKernelGGL(kern, dim3(grid), dim3(threads), (uint32_t)lds, stream, t_time_start, t_time_stop, 0, a);
+        t_time_start = t_time_stop = nullptr;
+    } else {
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, stream, a);
+    }
+    if (S > 1) {
+        const long long items = (long long)g.M * (g.N >> 2);
+        hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, stream, g);
+    }
+    return yv_launch_status();
+}
+
+// flags of the MX linears' epilogues: yv_linear_mxfp8 (+ YV_EPI_OUT_MXFP8 from yv_linear_mxfp8_q) and, with a separate f32
+// residual source / the bf16 side tensor, the training forms of yv_linear_mxfp8_ex
+static bool mx_flags_ok(int flags, const float* res_f32, const void* aux, int ldaux) {
+    if (flags & ~(YV_EPI_BIAS | YV_EPI_GELU | YV_EPI_RES_F32 | YV_EPI_OUT_F32 | YV_EPI_OUT_MXFP8 | YV_EPI_SAVE_PRE | YV_EPI_GELU_BWD))
+        return false;
+    if (res_f32 && !(flags & YV_EPI_RES_F32)) return false;
+    const bool ext = flags & (YV_EPI_SAVE_PRE | YV_EPI_GELU_BWD);
+    if (ext && (!aux || ldaux <= 0 || (ldaux & 7) || ((uintptr_t)aux & 15))) return false;
+    if (ext && (flags & (YV_EPI_OUT_F32 | YV_EPI_RES_F32 | YV_EPI_OUT_MXFP8))) return false;        // bf16 output only
+    if ((flags & YV_EPI_SAVE_PRE) && ((flags & YV_EPI_GELU_BWD) || !(flags & YV_EPI_GELU))) return false;
+    if ((flags & YV_EPI_GELU_BWD) && (flags & YV_EPI_GELU)) return false;
+    if (!ext && aux) return false;
+    return true;
+}
+
 static int linear_mx_impl(const void* Aq, long long lda, const void* Ascale, long long a_rows_pad, const void* Wq,
                           const void* Wscale, long long w_rows_pad, const float* bias, int M, int N, int K, void* out,
                           int ldo, int flags, const int32_t* m_dev, int m_mul, void* out_q, long long ldq, void* out_scales,
-                          long long out_rows_pad, void* stream) {
+                          long long out_rows_pad, void* stream, const float* res_f32, void* aux, int ldaux) {
     if (!Aq || !Ascale || !Wq || !Wscale || !out || M < 0 || N <= 0 || K <= 0) return YV_ERR_ARG;
     if ((K & 127) || (lda & 15) || (N & 7) || (ldo & 7)) return YV_ERR_ARG;             // whole 128-element K steps
     if (a_rows_pad < M || (a_rows_pad & 127) || w_rows_pad < N || (w_rows_pad & 127)) return YV_ERR_ARG;
     if (((uintptr_t)Ascale | (uintptr_t)Wscale) & 15) return YV_ERR_ARG;
     if ((flags & YV_EPI_BIAS) && !bias) return YV_ERR_ARG;
-    if (flags & ~(YV_EPI_BIAS | YV_EPI_GELU | YV_EPI_RES_F32 | YV_EPI_OUT_F32 | YV_EPI_OUT_MXFP8)) return YV_ERR_ARG;
-    if (((uintptr_t)Aq | (uintptr_t)Wq | (uintptr_t)out) & 15) return YV_ERR_ARG;
+    if (!mx_flags_ok(flags, res_f32, aux, ldaux)) return YV_ERR_ARG;
+    if (((uintptr_t)Aq | (uintptr_t)Wq | (uintptr_t)out | (uintptr_t)res_f32) & 15) return YV_ERR_ARG;
     if (M == 0) return YV_OK;
     MxArgs a = {};
     GemmArgs& g = a.g;
     g.a0 = (const uint16_t*)Aq; g.lda0 = (int)lda; g.w = (const uint16_t*)Wq; g.bias = bias; g.M = M; g.N = N; g.K = K;
     g.out = out; g.ldo = ldo; g.flags = flags; g.m_dev = m_dev; g.m_mul = m_mul;
+    g.resf = res_f32; g.aux = (uint16_t*)aux; g.ldaux = ldaux;
     g.ksize = 1; g.stride = 1; g.splitk = 1;
     g.staged = epi_can_stage(g);
     if (!g.staged) return YV_ERR_ARG;
@@ -2915,34 +3091,82 @@ static int linear_mx_impl(const void* Aq, long long lda, const void* Ascale, lon
     g.mxq = (uint8_t*)out_q; g.ldmxq = ldq; g.mxs = (uint8_t*)out_scales; g.mx_rows = out_rows_pad;
     // persistent free-running kernel (round 3): the bf16 schedule with one block-scaled MFMA per fragment pair and K tile
     g.mx_sa = a.sa; g.mx_sw = a.sw; g.mx_rows_a = a.rows_a; g.mx_rows_w = a.rows_w;
-    {
-        const int nkm = K >> 7;
-        const bool f32o = flags & (YV_EPI_RES_F32 | YV_EPI_OUT_F32);
-        if (g_opt_p8 >= 3 && g_opt_variant == 1 && !(N & 255) && N <= 4096 && nkm >= 2 && M >= 2048 &&
-            !((flags & YV_EPI_GELU) && f32o) && !((flags & YV_EPI_OUT_MXFP8) && f32o) && !(f32o && (nkm & 1)) &&
-            (long long)((M + 159) / 160) * (N >> 8) >= 192 &&
-            (long long)(M - 1) * lda + K < 0x7fffffffLL && (long long)N * K < 0x7fffffffLL &&
-            ((long long)(M - 1) * ldo + N) * 4 < 0x7fffffffLL && (long long)(K >> 7) * a.rows_a * 4 < 0x7fffffffLL &&
-            (long long)(K >> 7) * a.rows_w * 4 < 0x7fffffffLL)
-            return launch_p9(g, (hipStream_t)stream, 0, true);
-    }
+    if (mx_linear_pick(M, N, K, lda, ldo, a_rows_pad, w_rows_pad, flags, ldaux) == 1)
+        return launch_p9(g, (hipStream_t)stream, 0, true);
     // (a 256 x 128 / 8-wave instance of the same template was measured on the ViT-L shapes: 4-15 % slower than two
     // 128 x 128 workgroups per CU, like its bf16 counterpart, and is not dispatched)
-    g.tiles_m = (M + 127) / 128; g.tiles_n = (N + 127) / 128;
-    // (a 4-stage ring with ONE workgroup per CU and three K steps in flight was built in round 1, measured 35 % slower than two
-    // co-resident 2-stage workgroups, and removed in round 2: see DESIGN.md section 6, "MX deep ring")
-    const int threads = 256;
-    const size_t lds = 2 * (size_t)(128 * 128 * 2 + 1024);
-    auto kern = gemm_mx_kernel<128, 128, 2, 2>;
-    if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return YV_ERR_LAUNCH;
-    if (t_time_start || t_time_stop) {
-        hipExtLaunchKernelGGL(kern, dim3(g.tiles_m * g.tiles_n), dim3(threads), (uint32_t)lds, (hipStream_t)stream, t_time_start,
-                              t_time_stop, 0, a);
-        t_time_start = t_time_stop = nullptr;
-    } else {
-        hipLaunchKernelGGL(kern, dim3(g.tiles_m * g.tiles_n), dim3(threads), lds, (hipStream_t)stream, a);
+    return launch_mx128(a, (hipStream_t)stream);
+}
+
+extern "C" int yv_linear_mxfp8_ex(const void* Aq, long long lda, const void* Ascale, long long a_rows_pad, const void* Wq,
+                                  const void* Wscale, long long w_rows_pad, const float* bias, int M, int N, int K, void* out,
+                                  int ldo, int flags, const float* res_f32, void* aux, int ldaux, void* stream) {
+    if (flags & YV_EPI_OUT_MXFP8) return YV_ERR_ARG;
+    return linear_mx_impl(Aq, lda, Ascale, a_rows_pad, Wq, Wscale, w_rows_pad, bias, M, N, K, out, ldo, flags, nullptr, 1,
+                          nullptr, 0, nullptr, 0, stream, res_f32, aux, ldaux);
+}
+
+extern "C" int yv_linear_mxfp8_instance(int M, int N, int K, int flags) {
+    if (M <= 0 || N <= 0 || K <= 0 || (K & 127) || (N & 7) || (flags & YV_EPI_OUT_MXFP8)) return YV_ERR_ARG;
+    // dense operands (lda = K, ldo = ldaux = N) and scale rows rounded up to 128, as the trainer allocates them
+    const bool ext = flags & (YV_EPI_SAVE_PRE | YV_EPI_GELU_BWD);
+    static unsigned char dummy[16] __attribute__((aligned(16)));
+    if (!mx_flags_ok(flags, nullptr, ext ? (const void*)dummy : nullptr, ext ? N : 0)) return YV_ERR_ARG;
+    return mx_linear_pick(M, N, K, K, N, (M + 127) / 128 * 128LL, (N + 127) / 128 * 128LL, flags, N);
+}
+
+int g_opt_wgrad_mx_split = 0;      // > 0: forced number of token slices of the MX weight gradient ("wgrad_mx_split"; 1 = off)
+
+// dW (N, K) f32 = dY^T . X over T_pad tokens from the column forms of yv_quant_mxfp8_2d: dYt (N, T_pad) and Xt (K, T_pad) e4m3
+// bytes (row strides ldy / ldx bytes) with their token-block scales (T_pad/128, rows_pad, 4).  gemm_mx_kernel with M = N,
+// N = K, K = T_pad; the split over tokens follows yv_wgrad's matrix-shaped rule (one round of two workgroups per CU).
+extern "C" int yv_wgrad_mxfp8(const void* dYt, long long ldy, const void* sdy, long long dy_rows_pad, const void* Xt, long long ldx,
+                              const void* sx, long long x_rows_pad, int T_pad, int N, int K, float* dW, int ldw, void* stream) {
+    if (!dYt || !sdy || !Xt || !sx || !dW || T_pad <= 0 || N <= 0 || K <= 0) return YV_ERR_ARG;
+    if ((T_pad & 127) || ldy < T_pad || ldx < T_pad || (ldy & 15) || (ldx & 15) || (N & 7) || (K & 7) || ldw < K || (ldw & 3))
+        return YV_ERR_ARG;
+    if (dy_rows_pad < N || (dy_rows_pad & 127) || x_rows_pad < K || (x_rows_pad & 127)) return YV_ERR_ARG;
+    if (((uintptr_t)dYt | (uintptr_t)Xt | (uintptr_t)dW | (uintptr_t)sdy | (uintptr_t)sx) & 15) return YV_ERR_ARG;
+    if ((long long)(N - 1) * ldy + T_pad >= 0x7fffffffLL || (long long)(K - 1) * ldx + T_pad >= 0x7fffffffLL) return YV_ERR_LIMIT;
+    MxArgs a = {};
+    GemmArgs& g = a.g;
+    g.a0 = (const uint16_t*)dYt; g.lda0 = (int)ldy; g.w = (const uint16_t*)Xt; g.ldw = (int)ldx;
+    g.M = N; g.N = K; g.K = T_pad; g.out = dW; g.ldo = ldw; g.flags = YV_EPI_OUT_F32; g.m_mul = 1;
+    g.ksize = 1; g.stride = 1; g.splitk = 1;
+    g.staged = epi_can_stage(g);
+    if (!g.staged) return YV_ERR_ARG;
+    g.group_m = g_opt_group_m > 0 ? g_opt_group_m : 8;
+    a.sa = (const uint8_t*)sdy; a.sw = (const uint8_t*)sx; a.rows_a = dy_rows_pad; a.rows_w = x_rows_pad;
+    void* ws = nullptr; size_t wsb = 0;
+    if (ws_lookup(stream, &ws, &wsb)) {
+        const long long tiles = (long long)((N + 127) / 128) * ((K + 127) / 128);
+        const int nk = T_pad >> 7;
+        int S = g_opt_wgrad_mx_split > 0 ? g_opt_wgrad_mx_split : (int)(512 / tiles);
+        if (g_opt_wgrad_mx_split <= 0 && S > nk / 2) S = nk / 2;      // at least two 128-token K steps per slice
+        if (S > nk) S = nk;
+        if (S > 16) S = 16;
+        const size_t fit = wsb / ((size_t)N * K * sizeof(float));
+        if ((size_t)S > fit) S = (int)fit;
+        if (S >= 2) { g.splitk = S; g.partial = (float*)ws; }
     }
+    return launch_mx128(a, (hipStream_t)stream);
+}
+
+extern "C" int yv_quant_mxfp8_2d(const void* x, long long ldx, long long T, int C, void* q, long long ldq, void* scales,
+                                 long long rows_pad, void* qt, long long ldqt, void* scales_t, long long c_rows_pad,
+                                 long long T_pad, void* stream) {
+    if (!x || T <= 0 || C <= 0 || (C & 127) || (ldx & 7) || ldx < C || ((uintptr_t)x & 15)) return YV_ERR_ARG;
+    if (!q && !qt) return YV_ERR_ARG;
+    if ((q == nullptr) != (scales == nullptr) || (qt == nullptr) != (scales_t == nullptr)) return YV_ERR_ARG;
+    if (q && ((ldq & 15) || ldq < C || rows_pad < T || (rows_pad & 127) || ((uintptr_t)q & 15))) return YV_ERR_ARG;
+    if (qt && (T_pad < T || (T_pad & 127) || ldqt < T_pad || (ldqt & 15) || c_rows_pad < C || (c_rows_pad & 127) ||
+               ((uintptr_t)qt & 15)))
+        return YV_ERR_ARG;
+    const long long rows = qt ? T_pad : (T + 63) / 64 * 64;
+    if (rows / 64 > 0x7fffffffLL) return YV_ERR_LIMIT;
+    hipLaunchKernelGGL(quant_mx_2d_kernel, dim3((unsigned)(rows / 64), (unsigned)(C / 128)), dim3(256), 0, (hipStream_t)stream,
+                       (const uint16_t*)x, ldx, T, C, (uint8_t*)q, ldq, (uint8_t*)scales, rows_pad, (uint8_t*)qt, ldqt,
+                       (uint8_t*)scales_t, c_rows_pad);
     return yv_launch_status();
 }
 
@@ -2967,6 +3191,7 @@ extern "C" int yv_set_option(const char* key, int value) {
     if (!strcmp(key, "linear_p8_sched")) { g_opt_p8_sched = value; return YV_OK; }
     if (!strcmp(key, "conv_splitk")) { g_opt_splitk = value; return YV_OK; }
     if (!strcmp(key, "linear_splitk")) { g_opt_linear_splitk = value; return YV_OK; }
+    if (!strcmp(key, "wgrad_mx_split")) { g_opt_wgrad_mx_split = value; return YV_OK; }
     if (!strcmp(key, "conv_dma")) { g_opt_conv_dma = value; return YV_OK; }
     return YV_ERR_ARG;
 }
@@ -2986,6 +3211,7 @@ extern "C" int yv_get_option(const char* key, int* value) {
     if (!strcmp(key, "linear_p8_sched")) { *value = g_opt_p8_sched; return YV_OK; }
     if (!strcmp(key, "conv_splitk")) { *value = g_opt_splitk; return YV_OK; }
     if (!strcmp(key, "linear_splitk")) { *value = g_opt_linear_splitk; return YV_OK; }
+    if (!strcmp(key, "wgrad_mx_split")) { *value = g_opt_wgrad_mx_split; return YV_OK; }
     if (!strcmp(key, "conv_dma")) { *value = g_opt_conv_dma; return YV_OK; }
     return YV_ERR_ARG;
 }

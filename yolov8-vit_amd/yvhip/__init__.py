@@ -71,6 +71,12 @@ _SIGS = {
     "yv_conv2d_mxfp8_instance": (_i, [_i, _i, _i, _i, _i, _i, _i]),
     "yv_linear_mxfp8": (_i, [_vp, C.c_longlong, _vp, C.c_longlong, _vp, _vp, C.c_longlong, _vp, _i, _i, _i, _vp, _i, _i, _vp,
                              _i, _vp]),
+    "yv_quant_mxfp8_2d": (_i, [_vp, C.c_longlong, C.c_longlong, _i, _vp, C.c_longlong, _vp, C.c_longlong, _vp, C.c_longlong, _vp,
+                               C.c_longlong, C.c_longlong, _vp]),
+    "yv_linear_mxfp8_ex": (_i, [_vp, C.c_longlong, _vp, C.c_longlong, _vp, _vp, C.c_longlong, _vp, _i, _i, _i, _vp, _i, _i, _vp,
+                                _vp, _i, _vp]),
+    "yv_linear_mxfp8_instance": (_i, [_i, _i, _i, _i]),
+    "yv_wgrad_mxfp8": (_i, [_vp, C.c_longlong, _vp, C.c_longlong, _vp, C.c_longlong, _vp, C.c_longlong, _i, _i, _i, _vp, _i, _vp]),
     "yv_custom_nms_ws_bytes": (_sz, [_i, _i]),
     "yv_custom_nms": (_i, [_vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _sz, _vp]),
     "yv_efficient_nms": (_i, [_vp, _vp, _i, _i, _i, _f, _f, _i, _i, _vp, _vp, _vp, _vp, _vp]),
@@ -863,6 +869,132 @@ def linear_mxfp8(aq: torch.Tensor, a_scale: torch.Tensor, wq: torch.Tensor, w_sc
         lib.yv_set_launch_timing(None, None)
         hook(M, N, K, e0, e1)
     return out
+
+
+# ------------------------------------------------------------- MXFP8 training (VitTrainer(dtype="mxfp8"))
+def r128(n: int) -> int:
+    return (n + 127) // 128 * 128
+
+
+def _mx_shape_check(what: str, t: Optional[torch.Tensor], dtype, rows: int, cols: int, exact_cols: bool = False):
+    """Host-side size check of a caller-provided buffer (the C ABI sees pointers and strides only): a 2-D tensor of `dtype`
+    with at least `rows` rows and `cols` (exactly `cols` with exact_cols) columns."""
+    if t is None:
+        return
+    if t.dtype != dtype or t.dim() != 2 or t.shape[0] < rows or (t.shape[1] != cols if exact_cols else t.shape[1] < cols):
+        raise YvError(f"{what}: expected {dtype} ({'>=' if rows else ''}{rows}, {'' if exact_cols else '>='}{cols}), "
+                      f"got {t.dtype} {tuple(t.shape)}")
+
+
+def _mx_scale_check(what: str, s: Optional[torch.Tensor], ksteps: int, rows: int):
+    """K-step-major E8M0 scales: uint8 (ksteps, >= rows, 4), contiguous (the C ABI takes shape[1] as the padded row count)."""
+    if s is None:
+        return
+    if s.dtype != torch.uint8 or s.dim() != 3 or s.shape[0] != ksteps or s.shape[1] < rows or s.shape[2] != 4 or \
+            not s.is_contiguous():
+        raise YvError(f"{what}: expected contiguous uint8 ({ksteps}, >={rows}, 4) scales, got {s.dtype} {tuple(s.shape)}")
+
+
+def _mx_device_check(what: str, *ts):
+    for t_ in ts:
+        if t_ is not None and (not t_.is_cuda or t_.stride(-1) != 1):
+            raise YvError(f"{what}: operands must be device tensors with unit column stride")
+
+
+def quant_mxfp8_2d(x: torch.Tensor, q: Optional[torch.Tensor] = None, scales: Optional[torch.Tensor] = None,
+                   qt: Optional[torch.Tensor] = None, scales_t: Optional[torch.Tensor] = None, rows: Optional[int] = None,
+                   row_form: bool = True, col_form: bool = True):
+    """x (T, C) bf16 (unit column stride; any row stride) read once -> the row form (q (T, C) uint8, scales (C/128, T_pad', 4)),
+    bytes and scales of quant_mxfp8(x), and / or the column form (qt (C, T_pad) uint8, scales_t (T_pad/128, C_pad, 4)), those of
+    quant_mxfp8 applied to x^T zero-padded to T_pad = T rounded up to 128 (the column form's width: qt.shape[1]).
+    Returns (q, scales, qt, scales_t) with None for a form not written."""
+    if x.dtype != torch.bfloat16 or x.dim() != 2:
+        raise YvError("quant_mxfp8_2d: x must be a 2-D bf16 tensor")
+    T = x.shape[0] if rows is None else rows
+    Cc = x.shape[1]
+    if T > x.shape[0] or T <= 0 or Cc % 128:
+        raise YvError(f"quant_mxfp8_2d: {T} rows of a {tuple(x.shape)} tensor (C a multiple of 128)")
+    dev = x.device
+    if row_form:
+        q = torch.empty((T, Cc), dtype=torch.uint8, device=dev) if q is None else q
+        scales = torch.zeros((Cc // 128, r128(T), 4), dtype=torch.uint8, device=dev) if scales is None else scales
+        _mx_shape_check("quant_mxfp8_2d row form", q, torch.uint8, T, Cc)
+        _mx_scale_check("quant_mxfp8_2d row form", scales, Cc // 128, T)
+    else:
+        q = scales = None
+    if col_form:
+        qt = torch.empty((Cc, r128(T)), dtype=torch.uint8, device=dev) if qt is None else qt
+        _mx_shape_check("quant_mxfp8_2d column form", qt, torch.uint8, Cc, r128(T))
+        if qt.shape[1] % 128:
+            raise YvError(f"quant_mxfp8_2d column form: width {qt.shape[1]} is not a multiple of 128")
+        scales_t = torch.zeros((qt.shape[1] // 128, r128(Cc), 4), dtype=torch.uint8, device=dev) if scales_t is None else scales_t
+        _mx_scale_check("quant_mxfp8_2d column form", scales_t, qt.shape[1] // 128, Cc)
+    else:
+        qt = scales_t = None
+    _mx_device_check("quant_mxfp8_2d", x, q, scales, qt, scales_t)
+    check(lib.yv_quant_mxfp8_2d(_p(x), x.stride(0), T, Cc, _p(q), 0 if q is None else q.stride(0), _p(scales),
+                                0 if scales is None else scales.shape[1], _p(qt), 0 if qt is None else qt.stride(0), _p(scales_t),
+                                0 if scales_t is None else scales_t.shape[1], 0 if qt is None else qt.shape[1], _st()),
+          "yv_quant_mxfp8_2d")
+    return q, scales, qt, scales_t
+
+
+def linear_mxfp8_ex(aq: torch.Tensor, a_scale: torch.Tensor, wq: torch.Tensor, w_scale: torch.Tensor,
+                    bias: Optional[torch.Tensor], out: torch.Tensor, flags: int = 0, res_f32: Optional[torch.Tensor] = None,
+                    aux: Optional[torch.Tensor] = None, M: Optional[int] = None):
+    """Training form of linear_mxfp8 (the MX counterpart of linear_ex): separate f32 residual source, saved pre-activation,
+    GELU backward.  aq (>=M, K) / wq (N, K) e4m3 bytes with their K-step-major scales; out (>=M, >=N) bf16, or f32 with
+    EPI_OUT_F32 / EPI_RES_F32; res_f32 f32 with the row stride of out; aux bf16 (>=M, >=N)."""
+    if aq.dim() != 2 or wq.dim() != 2:
+        raise YvError("linear_mxfp8_ex: aq and wq must be 2-D")
+    Mr = aq.shape[0] if M is None else M
+    K, N = aq.shape[1], wq.shape[0]
+    if Mr > aq.shape[0] or Mr < 0:
+        raise YvError(f"linear_mxfp8_ex: M = {Mr} rows of a {tuple(aq.shape)} operand")
+    _mx_shape_check("linear_mxfp8_ex aq", aq, torch.uint8, Mr, K)
+    _mx_shape_check("linear_mxfp8_ex wq", wq, torch.uint8, N, K, exact_cols=True)
+    _mx_scale_check("linear_mxfp8_ex a_scale", a_scale, K // 128, Mr)
+    _mx_scale_check("linear_mxfp8_ex w_scale", w_scale, K // 128, N)
+    f32o = bool(flags & (EPI_OUT_F32 | EPI_RES_F32))
+    _mx_shape_check("linear_mxfp8_ex out", out, torch.float32 if f32o else torch.bfloat16, Mr, N)
+    _mx_shape_check("linear_mxfp8_ex res_f32", res_f32, torch.float32, Mr, N)
+    _mx_shape_check("linear_mxfp8_ex aux", aux, torch.bfloat16, Mr, N)
+    if res_f32 is not None and res_f32.stride(0) != out.stride(0):
+        raise YvError("linear_mxfp8_ex: res_f32 must have the row stride of out")
+    if bias is not None and (bias.dtype != torch.float32 or bias.dim() != 1 or bias.numel() < N):
+        raise YvError(f"linear_mxfp8_ex: bias must be f32 with >= {N} entries")
+    _mx_device_check("linear_mxfp8_ex", aq, a_scale, wq, w_scale, bias, out, res_f32, aux)
+    if bias is not None:
+        flags |= EPI_BIAS
+    check(lib.yv_linear_mxfp8_ex(_p(aq), aq.stride(0), _p(a_scale), a_scale.shape[1], _p(wq), _p(w_scale), w_scale.shape[1],
+                                 _p(bias), Mr, N, K, _p(out), out.stride(0), flags, _p(res_f32), _p(aux),
+                                 0 if aux is None else aux.stride(0), _st()), "yv_linear_mxfp8_ex")
+    return out
+
+
+def linear_mxfp8_instance(M: int, N: int, K: int, flags: int = 0) -> int:
+    """Kernel instance an MX linear launches for this shape (0: gemm_mx_kernel 128 x 128, 1: the persistent kernel)."""
+    r = lib.yv_linear_mxfp8_instance(M, N, K, flags)
+    check(min(r, 0), "yv_linear_mxfp8_instance")
+    return r
+
+
+def wgrad_mxfp8(dyt: torch.Tensor, dy_scale: torch.Tensor, xt: torch.Tensor, x_scale: torch.Tensor, dw: torch.Tensor):
+    """dw (N, K) f32 (any row stride) = dY^T . X over T_pad tokens from the column forms of quant_mxfp8_2d: dyt (N, T_pad),
+    xt (K, T_pad) uint8 with their token-block scales (T_pad/128, >= N / K, 4)."""
+    if dyt.dim() != 2 or xt.dim() != 2:
+        raise YvError("wgrad_mxfp8: dyt and xt must be 2-D")
+    N, K, Tp = dyt.shape[0], xt.shape[0], dyt.shape[1]
+    _mx_shape_check("wgrad_mxfp8 dyt", dyt, torch.uint8, N, Tp, exact_cols=True)
+    _mx_shape_check("wgrad_mxfp8 xt", xt, torch.uint8, K, Tp, exact_cols=True)
+    _mx_scale_check("wgrad_mxfp8 dy_scale", dy_scale, Tp // 128, N)
+    _mx_scale_check("wgrad_mxfp8 x_scale", x_scale, Tp // 128, K)
+    if dw.dtype != torch.float32 or tuple(dw.shape) != (N, K):
+        raise YvError(f"wgrad_mxfp8: dw must be f32 ({N}, {K}), got {dw.dtype} {tuple(dw.shape)}")
+    _mx_device_check("wgrad_mxfp8", dyt, dy_scale, xt, x_scale, dw)
+    check(lib.yv_wgrad_mxfp8(_p(dyt), dyt.stride(0), _p(dy_scale), dy_scale.shape[1], _p(xt), xt.stride(0), _p(x_scale),
+                             x_scale.shape[1], Tp, N, K, _p(dw), dw.stride(0), _st()), "yv_wgrad_mxfp8")
+    return dw
 
 
 # ------------------------------------------------------------- MXFP8 convolutions (YoloEngine(dtype="mxfp8"))

@@ -12,6 +12,15 @@ Memory layout (sized for 288 GB of HBM: nothing is recomputed except softmax pro
     read, so neither W^T copies nor transposed activations exist; wgrad operands carry 64-row zero padding.
 Gradients arrive in exactly the reverse of the flat order (head first, patch-embed last), so a bucket is
 complete - and its all-reduce can start - as soon as backward has passed its lowest offset.
+
+dtype="mxfp8" (opt-in): the four block linears (qkv, proj, fc1, fc2) run all three of their GEMMs on
+MXFP8 operands (e4m3 + one E8M0 scale per 32 elements of the reduction axis): forward Y = X . W^T and data gradient
+dX = dY . W on the block-scaled MFMA with the trainer epilogues (yv_linear_mxfp8_ex), weight gradient dW = dY^T . X from
+the token-quantised column forms of both operands (yv_wgrad_mxfp8).  Every bf16 activation / gradient operand is quantised by
+ONE pass of yv_quant_mxfp8_2d that writes the row form (for the forward / data-gradient GEMM) and the column form (for the
+weight gradient); the weights are re-quantised from the bf16 mirror after every optimizer step (W row-wise and, from the same
+read, W^T row-wise).  Patch-embed, heads, attention, LayerNorm, GELU, the residual stream, master weights, gradients, SGD and
+the all-reduce keep their bf16 / f32 form; the structure of forward, backward and optimizer step is that of dtype="bf16".
 """
 from __future__ import annotations
 
@@ -21,8 +30,8 @@ import torch
 
 from . import (EPI_GELU, EPI_GELU_BWD, EPI_OUT_F32, EPI_POSEMB, EPI_RES_F32, EPI_SAVE_PRE, YvError, attention_bwd,
                attention_train, cast_colsum, cls_rows, colsum_bf16, head_bwd, layernorm, layernorm_bwd, lib,
-               linear, linear_ex, linear_nn, loss_fwd_bwd, require_gpu, sgd_step, token_reduce, transpose_bf16_batched, wgrad,
-               wrapper_head)
+               linear, linear_ex, linear_mxfp8_ex, linear_nn, loss_fwd_bwd, quant_mxfp8_2d, r128, require_gpu, sgd_step,
+               token_reduce, transpose_bf16_batched, wgrad, wgrad_mxfp8, wrapper_head)
 from .engines import vit_cfg
 
 
@@ -30,12 +39,26 @@ def _r64(n: int) -> int:
     return (n + 63) // 64 * 64
 
 
+BLOCK_LINEARS = ("attn.qkv.weight", "attn.proj.weight", "mlp.fc1.weight", "mlp.fc2.weight")
+
+
+def check_train_dtype(dtype: str, D: int):
+    """The recipes VitTrainer accepts: "bf16" (default) and "mxfp8" (D, 3D and 4D - every reduction and output width of the
+    block linears - multiples of 128, i.e. D % 128 == 0: ViT-B/16, B/8, L/16 and the vit_tiny*_test models)."""
+    if dtype not in ("bf16", "mxfp8"):
+        raise YvError(f"VitTrainer dtype must be 'bf16' or 'mxfp8', not {dtype!r}")
+    if dtype == "mxfp8" and D % 128:
+        raise YvError(f"VitTrainer(dtype='mxfp8') needs an embedding width that is a multiple of 128 (got {D})")
+
+
 class VitTrainer:
     def __init__(self, state: Dict[str, torch.Tensor], name: str, num_classes: int = 5, img: int = 224,
                  device: str = "cuda:0", momentum: float = 0.9, weight_decay: float = 1e-3,
-                 bucket_mb: float = 32.0):
-        require_gpu()
+                 bucket_mb: float = 32.0, dtype: str = "bf16"):
         self.P_, self.D, self.L, self.H = vit_cfg(name)
+        check_train_dtype(dtype, self.D)
+        require_gpu()
+        self.dtype = dtype
         self.name, self.nc, self.img, self.dev = name, num_classes, img, torch.device(device)
         self.tok = (img // self.P_) ** 2
         self.N = self.tok + 1
@@ -74,12 +97,23 @@ class VitTrainer:
         # an ordinary linear on W^T and runs on the persistent forward GEMM (round 3; the transposing-read kernel on the master
         # layout ran at 0.12 of the MFMA roof and was a quarter of the step).  Refreshed after every optimizer step by four
         # batched transposes (one per linear of a block, batch = depth): 170 MB read + 170 MB written, ~1 % of a step.
-        self.P16T = torch.zeros(o, dtype=torch.bfloat16, device=self.dev)
+        # (dtype="mxfp8": no reader - the data gradients take W^T from the column form of the weight quantiser - not allocated)
+        self.P16T = torch.zeros(o, dtype=torch.bfloat16, device=self.dev) if dtype == "bf16" else None
         self.blk_stride = (self.off["model.blocks.1.attn.qkv.weight"] - self.off["model.blocks.0.attn.qkv.weight"]) if self.L > 1 else 0
         for i in range(1, self.L):
             for w in ("attn.qkv.weight", "attn.proj.weight", "mlp.fc1.weight", "mlp.fc2.weight"):
                 if self.off[f"model.blocks.{i}.{w}"] - self.off[f"model.blocks.0.{w}"] != i * self.blk_stride:
                     raise YvError("state dict: blocks are not laid out with one stride")
+        # ---- MXFP8 weight operands (dtype="mxfp8"): per block linear W (N, K) row-wise and W^T (K, N) row-wise, both quantised
+        # from the bf16 mirror by one yv_quant_mxfp8_2d pass (its column form of W IS W^T quantised along N)
+        self.wmx: Dict[str, tuple] = {}
+        if dtype == "mxfp8":
+            u8 = lambda *s: torch.zeros(s, dtype=torch.uint8, device=self.dev)
+            for i in range(self.L):
+                for w in BLOCK_LINEARS:
+                    key = f"model.blocks.{i}.{w}"
+                    N_, K_ = self.gemm_w[key][0], self.gemm_w[key][1]
+                    self.wmx[key] = (u8(N_, K_), u8(K_ // 128, r128(N_), 4), u8(K_, N_), u8(N_ // 128, r128(K_), 4))
         self.P16.copy_(self.P)                               # initial cast (plumbing); afterwards the SGD kernel mirrors
         self.refresh_working_copies()
         self._bufs: Dict[int, dict] = {}
@@ -118,6 +152,11 @@ class VitTrainer:
         """Only the 1000 -> 1024 padded head copies need touching: everything else is a view of the mirror."""
         self.w_head_pad[:1000].copy_(self.gemm_w["model.head.weight"][2])
         self.b_head_pad[:1000].copy_(self.p("model.head.bias"))
+        if self.dtype == "mxfp8":
+            # MX operands of the block linears (this recipe has no transposed bf16 mirror)
+            for key, (wq, ws, wtq, wts) in self.wmx.items():
+                quant_mxfp8_2d(self.gemm_w[key][2], wq, ws, wtq, wts)
+            return
         for w in ("attn.qkv.weight", "attn.proj.weight", "mlp.fc1.weight", "mlp.fc2.weight"):
             key = "model.blocks.0." + w
             N, K = self.gemm_w[key][0], self.gemm_w[key][1]
@@ -163,6 +202,18 @@ class VitTrainer:
                           done=None) for _ in range(2)],
                  ws=f32(max(int(lib.yv_colsum_ws_floats(M, 4 * D)), int(lib.yv_layernorm_bwd_ws_floats(M, D)), 2 * R * 128) + 64),
                  ws_w=f32(int(lib.yv_colsum_ws_floats(M, 4 * D)) + 64))          # scratch of the column sums on the side stream
+        if self.dtype == "mxfp8":
+            # MX operands.  Row forms (GEMM A operands, consumed by the next GEMM on the main stream): one set per width.  Column
+            # forms (weight-gradient operands, (C, Mq) with the tokens zero-padded to Mq = M rounded up to 128): the forward's
+            # activations per block (read by backward), the gradients double-buffered by block parity like b["dy"]
+            u8 = lambda *s: torch.zeros(s, dtype=torch.uint8, device=dev)
+            Mq = r128(M)
+            row = lambda C: (u8(M, C), u8(C // 128, Mq, 4))
+            col = lambda C: (u8(C, Mq), u8(Mq // 128, r128(C), 4))
+            b.update(Mq=Mq, rq={C: row(C) for C in (D, 3 * D, 4 * D)},
+                     xc=[dict(h1=col(D), o=col(D), h2=col(D), g=col(4 * D)) for _ in range(L)])
+            for S in b["dy"]:
+                S.update(c_fc2=col(D), c_wide=col(4 * D), c_proj=col(D), c_qkv=col(3 * D))
         self._bufs[R] = b
         return b
 
@@ -181,6 +232,9 @@ class VitTrainer:
         for i in range(L):
             k = f"model.blocks.{i}."
             xin, xmid, xout = b["x"][2 * i], b["x"][2 * i + 1], b["x"][2 * i + 2]
+            if self.dtype == "mxfp8":
+                self._block_forward_mx(b, i, xin, xmid, xout)
+                continue
             layernorm(xin, self.p(k + "norm1.weight"), self.p(k + "norm1.bias"), b["h1"][i], M, D, D, D)
             linear(b["h1"][i], W(k + "attn.qkv.weight"), self.p(k + "attn.qkv.bias"), b["qkv"][i])
             attention_train(b["qkv"][i], R, N, H, b["o"][i], b["lse"][i])
@@ -197,6 +251,71 @@ class VitTrainer:
         wrapper_head(b["feats"], w1t, self.p("fc.1.bias"), self.p("fc.3.weight"), self.p("fc.3.bias"), R, self.nc,
                      b["logits"], b["labels"])
         return b["logits"]
+
+    # ---- MXFP8 block linears (dtype="mxfp8") -------------------------------------------------------------
+    def _quant(self, b: dict, x: torch.Tensor, col: Optional[tuple]):
+        """bf16 (M, C) operand -> its row form (the shared A operand of width C) and, if `col`, its column form: one read."""
+        q, s = b["rq"][x.shape[1]]
+        quant_mxfp8_2d(x, q, s, *(col if col is not None else (None, None)), col_form=col is not None)
+        return q, s
+
+    def _mx_linear(self, key: str, a: tuple, bias, out, transposed: bool = False, **kw):
+        """out = a . W^T (forward) or a . W (transposed: the data gradient, on the W^T operand) with the MX trainer epilogues."""
+        wq, ws, wtq, wts = self.wmx[key]
+        linear_mxfp8_ex(a[0], a[1], wtq if transposed else wq, wts if transposed else ws, bias, out, **kw)
+
+    def _block_forward_mx(self, b: dict, i: int, xin, xmid, xout):
+        k = f"model.blocks.{i}."
+        D, N, H, M = self.D, self.N, self.H, b["M"]
+        R = M // N
+        X = b["xc"][i]                                       # column forms kept for the block's weight gradients
+        layernorm(xin, self.p(k + "norm1.weight"), self.p(k + "norm1.bias"), b["h1"][i], M, D, D, D)
+        self._mx_linear(k + "attn.qkv.weight", self._quant(b, b["h1"][i], X["h1"]), self.p(k + "attn.qkv.bias"), b["qkv"][i])
+        attention_train(b["qkv"][i], R, N, H, b["o"][i], b["lse"][i])
+        self._mx_linear(k + "attn.proj.weight", self._quant(b, b["o"][i], X["o"]), self.p(k + "attn.proj.bias"), xmid,
+                        flags=EPI_RES_F32, res_f32=xin)
+        layernorm(xmid, self.p(k + "norm2.weight"), self.p(k + "norm2.bias"), b["h2"][i], M, D, D, D)
+        self._mx_linear(k + "mlp.fc1.weight", self._quant(b, b["h2"][i], X["h2"]), self.p(k + "mlp.fc1.bias"), b["g"][i],
+                        flags=EPI_GELU | EPI_SAVE_PRE, aux=b["u"][i])
+        self._mx_linear(k + "mlp.fc2.weight", self._quant(b, b["g"][i], X["g"]), self.p(k + "mlp.fc2.bias"), xout,
+                        flags=EPI_RES_F32, res_f32=xmid)
+
+    def _block_backward_mx(self, b: dict, i: int, S: dict, main, xin, xmid):
+        """The block's data-gradient chain on the main stream (every incoming gradient quantised once: row form for the
+        data gradient, column form for the weight gradient), then its weight gradients on the side stream."""
+        k = f"model.blocks.{i}."
+        D, N, H, M = self.D, self.N, self.H, b["M"]
+        R = M // N
+        dx = b["dx"]
+        dxb_fc2, dxb_proj, dwide, dqkv = S["dxb_fc2"][:M], S["dxb_proj"][:M], S["dwide"][:M], S["dqkv"][:M]
+        # MLP branch
+        cast_colsum(dx, dxb_fc2, self.g(k + "mlp.fc2.bias"), b["ws"])
+        self._mx_linear(k + "mlp.fc2.weight", self._quant(b, dxb_fc2, S["c_fc2"]), None, dwide, transposed=True,
+                        flags=EPI_GELU_BWD, aux=b["u"][i])
+        self._mx_linear(k + "mlp.fc1.weight", self._quant(b, dwide, S["c_wide"]), None, b["dnar"], transposed=True)
+        layernorm_bwd(xmid, D, self.p(k + "norm2.weight"), b["dnar"], D, M, D, dx, D,
+                      self.g(k + "norm2.weight"), self.g(k + "norm2.bias"), b["ws"])
+        # attention branch
+        cast_colsum(dx, dxb_proj, self.g(k + "attn.proj.bias"), b["ws"])
+        self._mx_linear(k + "attn.proj.weight", self._quant(b, dxb_proj, S["c_proj"]), None, b["dnar"], transposed=True)
+        attention_bwd(b["qkv"][i], b["o"][i], b["dnar"], b["lse"][i], R, N, H, dqkv, b["delta"])
+        self._mx_linear(k + "attn.qkv.weight", self._quant(b, dqkv, S["c_qkv"]), None, b["dnar"], transposed=True)
+        layernorm_bwd(xin, D, self.p(k + "norm1.weight"), b["dnar"], D, M, D, dx, D,
+                      self.g(k + "norm1.weight"), self.g(k + "norm1.bias"), b["ws"])
+        ev = torch.cuda.Event()
+        ev.record(main)
+        X = b["xc"][i]
+        with torch.cuda.stream(self.s_w):
+            self.s_w.wait_event(ev)
+            colsum_bf16(dwide, self.g(k + "mlp.fc1.bias"), b["ws_w"])
+            colsum_bf16(dqkv, self.g(k + "attn.qkv.bias"), b["ws_w"])
+            for w, dy, x in (("mlp.fc2.weight", "c_fc2", "g"), ("mlp.fc1.weight", "c_wide", "h2"),
+                             ("attn.proj.weight", "c_proj", "o"), ("attn.qkv.weight", "c_qkv", "h1")):
+                N_, K_ = self.gemm_w[k + w][0], self.gemm_w[k + w][1]
+                wgrad_mxfp8(S[dy][0], S[dy][1], X[x][0], X[x][1], self.g(k + w).reshape(N_, K_))
+            self._launch_ready_buckets(self.off[k + "norm1.weight"])
+            S["done"] = torch.cuda.Event()
+            S["done"].record(self.s_w)
 
     # ---- backward ---------------------------------------------------------------------------------------
     def _wgrad(self, key: str, dy_full: torch.Tensor, x_full: torch.Tensor):
@@ -238,6 +357,9 @@ class VitTrainer:
             S = b["dy"][i & 1]
             if S["done"] is not None:
                 main.wait_event(S["done"])                     # block i+2's weight gradients have read this set
+            if self.dtype == "mxfp8":
+                self._block_backward_mx(b, i, S, main, xin, xmid)
+                continue
             dxb_fc2, dxb_proj, dwide, dqkv = S["dxb_fc2"][:M], S["dxb_proj"][:M], S["dwide"][:M], S["dqkv"][:M]
             # MLP branch
             cast_colsum(dx, dxb_fc2, self.g(k + "mlp.fc2.bias"), b["ws"])
