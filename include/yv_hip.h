@@ -203,6 +203,22 @@ int yv_letterbox(const uint8_t* src, int B, int Hc, int Wc, const int32_t* geom,
  * out (B*(S/P)^2, 3*P*P) bf16 patch-major rows (same layout as yv_crop_resize_norm layout 2). */
 int yv_augment_patchify(const float* x, int B, int S, int P, const float* geo, const int32_t* idx, void* out, void* stream);
 
+/* Classifier training / validation crops straight out of decoded source images (device-resident crop loader): replaces
+ * crop_image + the Resize / Normalize head of both transforms + the per-item tensor work of build_dataset
+ * (utils/trainClass.py:70-93, :199-221, :250-273), fused with what yv_augment_patchify does.  Per output value it is exactly
+ * yv_augment_patchify applied to the S x S crop that yv_crop_resize_norm (layout 0) would produce; that crop is never stored.
+ *   pool   (pool_bytes) u8: every source image, RGB, row-major, tightly packed, one after the other;
+ *   table  (n_images, 3) i64 rows {byte offset into the pool, width, height};
+ *   plan   (B, 5) i32 rows {image id, x0, y0, x1, y1}: crop rectangle, right / bottom exclusive (the crop_list convention);
+ *   geo (B, 6 + 2S) f32, idx (B, 36 + 2S) i32: the records of yv_augment_patchify (identity records for validation).
+ * layout 2: out = (B*(S/P)^2, 3*P*P) bf16 patch-major rows; layout 0: out = (B,3,S,S) f32 CHW (P unused).  S % 8 == 0.
+ * Every input is clamped, never trusted: image id to [0, n_images-1]; width / height to [1, 2^24]; rectangle extents
+ * w = max(x1-x0, 1), h = max(y1-y0, 1); table entries mapx / mapy to [0, S-1]; source column
+ * clamp(x0 + min(floor(m * (1/(S/w))), w-1), 0, width-1) (f64, rows alike); tap byte address clamp(offset + 3*(row*width + col),
+ * 0, pool_bytes-3); channel ids to [0,2], hole count to [0,8], affine coordinates to [-4S, 4S] (NaN -> -4S). */
+int yv_train_crops(const uint8_t* pool, size_t pool_bytes, const int64_t* table, int n_images, const int32_t* plan, int B, int S,
+                   int P, const float* geo, const int32_t* idx, int layout, void* out, void* stream);
+
 /* Detector training augmentation, what `model.train()` (utils/trainYolo.py:28) applies by default: Mosaic(4) ->
  * RandomPerspective(scale, translate) -> HSV gains -> horizontal flip in one gather pass per output image.
  * tiles (n_tiles,S,S,3) u8: sources resized to long side S in the top-left corner of their slot (yv_letterbox, fill 114).

@@ -260,13 +260,21 @@ def train_one_epoch(net, netp, trainloader, CELoss, optimizer, lr, batch_size, e
         if optimizer is not None:
             for grp in optimizer.param_groups:
                 grp['lr'] = cur_lr
-        x = inputs.to(tr.dev).float().contiguous()
-        labels = targets.to(tr.dev).argmax(1).to(torch.int32).contiguous()
-        if aug is not None:
-            geo, idx = aug.sample(x.shape[0])
-            patches = yvhip.augment_patchify(x, torch.from_numpy(geo).to(tr.dev), torch.from_numpy(idx).to(tr.dev), tr.P_)
+        if hasattr(inputs, "patch_operand"):
+            # device-resident crop loader (build_dataloader(device_pool=True)): the batch is a plan; crop, resize, normalise and
+            # the stochastic transforms are one yv_train_crops launch (records drawn here, where the host path draws them)
+            labels = targets.to(tr.dev).argmax(1).to(torch.int32).contiguous()
+            B = inputs.shape[0]
+            geo, idx = aug.sample(B) if aug is not None else inputs.pool.identity_records(B, inputs.size)
+            patches = inputs.patch_operand(geo, idx, tr.P_)
         else:
-            patches = patchify_bf16(x, tr.P_)
+            x = inputs.to(tr.dev).float().contiguous()
+            labels = targets.to(tr.dev).argmax(1).to(torch.int32).contiguous()
+            if aug is not None:
+                geo, idx = aug.sample(x.shape[0])
+                patches = yvhip.augment_patchify(x, torch.from_numpy(geo).to(tr.dev), torch.from_numpy(idx).to(tr.dev), tr.P_)
+            else:
+                patches = patchify_bf16(x, tr.P_)
         loss, logits = tr.step(patches, labels, cur_lr)
         eq, _ = getCorrect(logits.data, targets.to(logits.device).float().data)
         total += targets.size(0)
@@ -348,8 +356,32 @@ class build_dataset(torch.utils.data.Dataset):
         return chw, label.to(torch.int64), obj["path"]
 
 
-def build_dataloader(objects, objects_circle, valid_objects, valid_objects_circle, data_transforms):
-    """utils/trainClass.py:331-341 (train: shuffle, drop_last=False; valid: in order)."""
+def build_device_dataloader(objects, objects_circle, valid_objects, valid_objects_circle, data_transforms, pool=None,
+                            max_bytes=None):
+    """The loaders of build_dataloader with the crops taken on the device (yvhip.crop_loader): every distinct source image is
+    decoded once into a DevicePool on CFG.device (or the given `pool`), batches are plans (image id + rectangle) and
+    `yv_train_crops` produces the operand.  Same samples, rectangles and records as the host loaders after the same set_seed."""
+    from yvhip.crop_loader import DEFAULT_POOL_BYTES, DeviceCropLoader, DevicePool
+    if CFG.img_size[0] != CFG.img_size[1]:
+        raise yvhip.YvError("the device crop loader needs a square CFG.img_size")
+    if pool is None:
+        yvhip.require_gpu()
+        paths = [o["path"] for lst in (objects, objects_circle, valid_objects, valid_objects_circle) for o in lst]
+        pool = DevicePool(paths, device=CFG.device, max_bytes=DEFAULT_POOL_BYTES if max_bytes is None else max_bytes)
+    S = CFG.img_size[0]
+    train_loader = DeviceCropLoader(pool, objects, objects_circle, CFG.train_bs, S, inflate_box, CFG.num_classes, True,
+                                    transforms=data_transforms['train'])
+    valid_loader = DeviceCropLoader(pool, valid_objects, valid_objects_circle, CFG.valid_bs, S, inflate_box, CFG.num_classes,
+                                    False, transforms=data_transforms['valid_test'])
+    return train_loader, valid_loader
+
+
+def build_dataloader(objects, objects_circle, valid_objects, valid_objects_circle, data_transforms, device_pool=False):
+    """utils/trainClass.py:331-341 (train: shuffle, drop_last=False; valid: in order).  `device_pool` (opt-in; True, or a
+    yvhip.crop_loader.DevicePool to reuse): device-resident crop loaders, see build_device_dataloader."""
+    if device_pool:
+        return build_device_dataloader(objects, objects_circle, valid_objects, valid_objects_circle, data_transforms,
+                                       pool=None if device_pool is True else device_pool)
     from torch.utils.data import DataLoader
     train_dataset = build_dataset(objects, objects_circle, val=False, train_val_flag=True, transforms=data_transforms['train'])
     valid_dataset = build_dataset(valid_objects, valid_objects_circle, val=True, train_val_flag=True,
@@ -393,13 +425,15 @@ def train(CFG, log=False, save_path="/app/utils/new_weight/best.pth"):
     init if that file is absent), CFG.epoch epochs of train_one_epoch + valid_one_epoch, best state dict to
     /app/utils/new_weight/best.pth, result.json when `log`.  Training crops get the random inflation of crop_image, the
     deterministic resize + normalise on the host and the stochastic transforms of utils/trainClass.py:199-216 on the
-    device (see _TrainTransform)."""
+    device (see _TrainTransform).  An optional CFG.device_loader (absent / False: the loaders above) takes the crops on the
+    device as well (build_device_dataloader)."""
     data_transforms = build_transforms(CFG)
     objects, objects_circle = xml2pd(CFG.train_path)
     valid_objects, valid_objects_circle = xml2pd(CFG.valid_path)
     if not (objects or objects_circle):
         raise yvhip.YvError(f"no annotated objects under {CFG.train_path}")
-    train_loader, valid_loader = build_dataloader(objects, objects_circle, valid_objects, valid_objects_circle, data_transforms)
+    train_loader, valid_loader = build_dataloader(objects, objects_circle, valid_objects, valid_objects_circle, data_transforms,
+                                                  device_pool=bool(getattr(CFG, "device_loader", False)))
     pretrained = CFG.pretrained if CFG.pretrained and os.path.exists(CFG.pretrained) else None
     if pretrained is None:
         print(f"train: {CFG.pretrained} not found, seeded random initialisation")

@@ -89,6 +89,7 @@ _SIGS = {
     "yv_crop_resize_norm": (_i, [_vp, _i, _i, _i, _sz, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "yv_letterbox": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp]),
     "yv_augment_patchify": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "yv_train_crops": (_i, [_vp, _sz, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp]),
     "yv_mosaic_augment": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "yv_detect_decode": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "yv_detect_tail": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
@@ -365,6 +366,44 @@ def augment_patchify(x: torch.Tensor, geo: torch.Tensor, idx: torch.Tensor, patc
     if out is None:
         out = torch.empty((B * g * g, 3 * patch * patch), dtype=torch.bfloat16, device=x.device)
     check(lib.yv_augment_patchify(_p(x), B, S, patch, _p(geo), _p(idx), _p(out), _st()), "yv_augment_patchify")
+    return out
+
+
+def train_crops(pool: torch.Tensor, table: torch.Tensor, plan: torch.Tensor, geo: torch.Tensor, idx: torch.Tensor,
+                size: int, patch: int, layout: int = 2, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """pool (bytes,) u8 decoded source images, table (n,3) i64 {offset, width, height}, plan (B,5) i32 {image, x0, y0, x1, y1}
+    + one augmentation record per sample (yvhip.augment) -> layout 2: (B*(S/P)^2, 3*P*P) bf16 patch-major rows |
+    layout 0: (B,3,S,S) f32.  Crop + nearest resize + normalise + the record in one pass (yvhip.crop_loader feeds it)."""
+    _chk_dev(pool, table, plan, geo, idx)
+    S = int(size)
+    if pool.dim() != 1 or pool.dtype != torch.uint8 or pool.numel() < 3:
+        raise YvError("train_crops: pool must be a flat u8 tensor of at least 3 bytes")
+    if table.dim() != 2 or table.shape[1] != 3 or table.shape[0] < 1 or table.dtype != torch.int64:
+        raise YvError("train_crops: table must be (n_images, 3) i64 {offset, width, height}")
+    B = plan.shape[0]
+    if tuple(plan.shape) != (B, 5) or plan.dtype != torch.int32:
+        raise YvError("train_crops: plan must be (B, 5) i32 {image, x0, y0, x1, y1}")
+    if S <= 0 or S % 8:
+        raise YvError("train_crops: size must be a positive multiple of 8")
+    if tuple(geo.shape) != (B, 6 + 2 * S) or geo.dtype != torch.float32:
+        raise YvError("train_crops: geo must be (B, 6 + 2S) f32")
+    if tuple(idx.shape) != (B, 36 + 2 * S) or idx.dtype != torch.int32:
+        raise YvError("train_crops: idx must be (B, 36 + 2S) i32")
+    if layout not in (0, 2):
+        raise YvError("train_crops: layout is 0 (f32 CHW) or 2 (bf16 patch-major rows)")
+    if layout == 2:
+        if patch < 8 or patch % 8 or S % patch:
+            raise YvError("train_crops: patch must be a multiple of 8 dividing size")
+        g = S // patch
+        shape, dtype = (B * g * g, 3 * patch * patch), torch.bfloat16
+    else:
+        shape, dtype = (B, 3, S, S), torch.float32
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device=pool.device)
+    elif tuple(out.shape) != shape or out.dtype != dtype or not out.is_cuda or not out.is_contiguous():
+        raise YvError(f"train_crops: out must be a contiguous device tensor {shape} {dtype}")
+    check(lib.yv_train_crops(_p(pool), pool.numel(), _p(table), table.shape[0], _p(plan), B, S, int(patch), _p(geo), _p(idx),
+                             int(layout), _p(out), _st()), "yv_train_crops")
     return out
 
 
