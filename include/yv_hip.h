@@ -366,6 +366,13 @@ int yv_layernorm(const float* x, size_t ldx, const float* gamma, const float* be
  * (ViT-B/8: 785) are tiled with an online softmax. */
 int yv_attention(const void* qkv, int R, int N, int H, float scale, void* out, const int32_t* r_dev, void* stream);
 
+/* Attention of the cls query only (row 0 of each crop), for the last block of the classifier, whose other rows nothing reads:
+ * out[r, h*64 ..] = softmax(q[r, h] . K_r^T * scale) . V_r for r < min(R, r_dev[0]); rows past the count keep their contents.
+ * q (R, H*64) bf16 compact; K and V are read from the ordinary qkv buffer (R*N, 3*H*64) (its q third is not read);
+ * out (R, H*64) bf16 compact.  q, qkv, out 16-byte aligned (YV_ERR_ARG); N <= 8192 (YV_ERR_LIMIT). */
+int yv_attention_cls(const void* q, const void* qkv, int R, int N, int H, float scale, void* out, const int32_t* r_dev,
+                     void* stream);
+
 /* Diagnostic builds of the attention kernel (0 = normal; 1 no K/V loads, 2 no compute, 3 no V^T writes). */
 int yv_attention_debug(int ablate);
 

@@ -37,6 +37,14 @@ elif os.environ.get("E2E_C2F"):
             return r_s.submit(x)
         return run
     opts = [("C2f layer by layer", with_c2f(False)), ("C2f fused", with_c2f(True))]
+elif os.environ.get("E2E_CLS_TAIL"):
+    r_s = PipelinedRunner(pipe, split_classifier=True)
+    def with_tail(flag):
+        def run(x):
+            pipe.vits[0].cls_tail = flag
+            return r_s.submit(x)
+        return run
+    opts = [("last block, all rows", with_tail(False)), ("last block, cls rows", with_tail(True))]
 elif os.environ.get("E2E_SPLIT"):
     opts = [("two streams", runner.submit)] + [(f"split x{k}", PipelinedRunner(pipe, split_classifier=int(k)).submit)
                                                for k in os.environ["E2E_SPLIT"].split(",")]

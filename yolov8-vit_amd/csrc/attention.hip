@@ -606,6 +606,100 @@ int launch_attn(const uint16_t* qkv, int R, int N, int H, float scale, uint16_t*
     return yv_launch_status();
 }
 
+// ---------------------------------------------------------------------------------------------
+// cls-query attention (last block of the classifier: only the cls row of each crop is read after it).  One query against N keys
+// is a streaming pass over K and V (2 * N * 128 B per crop and head) with two dot products per byte pair: no MFMA, no tiling.
+// One workgroup of 256 threads per (crop, head); 8 lanes share a 128-byte K / V row (16 B each), 32 rows per trip.
+//   1. s[n] = q . K[n] * scale (log2 domain) into LDS, 2. block max / exp2 / sum, 3. o = sum_n p[n] V[n] / sum.
+// Every reduction has a fixed order: the result does not depend on the launch.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ void unpack_bf16x8(const u32x4 v, float (&f)[8]) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        f[2 * i] = __uint_as_float(v[i] << 16);
+        f[2 * i + 1] = __uint_as_float(v[i] & 0xffff0000u);
+    }
+}
+
+__global__ __launch_bounds__(256) void attention_cls_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict__ qkv, int R,
+                                                            int N, int H, float scale_log2, uint16_t* __restrict__ out,
+                                                            const int32_t* __restrict__ r_dev) {
+    extern __shared__ __attribute__((aligned(16))) float cls_sm[];       // N scores (padded to 4) | 4 x 64 partial outputs | 8 scalars
+    const int r = blockIdx.x / H, hd = blockIdx.x - r * H;
+    int Rr = R;
+    if (r_dev) { const int c = r_dev[0]; Rr = c < Rr ? c : Rr; }
+    if (r >= Rr) return;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, c = tid & 7, grp = tid >> 3;
+    float* sc = cls_sm;
+    float* part = cls_sm + ((N + 3) & ~3);
+    float* red = part + 256;
+    const long long ld = 3LL * H * 64;
+    const uint16_t* kb = qkv + (long long)r * N * ld + (long long)(H + hd) * 64 + c * 8;
+    const uint16_t* vb = kb + (long long)H * 64;
+    float qf[8];
+    unpack_bf16x8(*(const u32x4*)(q + ((long long)r * H + hd) * 64 + c * 8), qf);
+
+    float mx = -3.0e38f;
+#pragma unroll 4
+    for (int n0 = 0; n0 < N; n0 += 32) {
+        const int n = n0 + grp, nn = n < N ? n : N - 1;
+        float kf[8];
+        unpack_bf16x8(*(const u32x4*)(kb + nn * ld), kf);
+        float d = 0.f;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) d += qf[i] * kf[i];
+        d += __shfl_xor(d, 1, 64);
+        d += __shfl_xor(d, 2, 64);
+        d += __shfl_xor(d, 4, 64);
+        d *= scale_log2;
+        if (n < N) {
+            if (c == 0) sc[n] = d;
+            mx = fmaxf(mx, d);
+        }
+    }
+    mx = wave_max(mx);
+    if (lane == 0) red[wave] = mx;
+    __syncthreads();
+    mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    float sum = 0.f;
+    for (int n = tid; n < N; n += 256) {
+        const float p = __builtin_amdgcn_exp2f(sc[n] - mx);
+        sc[n] = p;
+        sum += p;
+    }
+    sum = wave_sum(sum);
+    if (lane == 0) red[4 + wave] = sum;
+    __syncthreads();
+    sum = (red[4] + red[5]) + (red[6] + red[7]);
+
+    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+    for (int n0 = 0; n0 < N; n0 += 32) {
+        const int n = n0 + grp, nn = n < N ? n : N - 1;
+        float vf[8];
+        unpack_bf16x8(*(const u32x4*)(vb + nn * ld), vf);
+        const float p = n < N ? sc[nn] : 0.f;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) acc[i] += p * vf[i];
+    }
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        float a = acc[i];
+        a += __shfl_xor(a, 8, 64);
+        a += __shfl_xor(a, 16, 64);
+        a += __shfl_xor(a, 32, 64);
+        if (lane < 8) part[wave * 64 + c * 8 + i] = a;
+    }
+    __syncthreads();
+    if (tid < 32) {
+        const int d = tid * 2;
+        const float inv = 1.0f / sum;
+        const float o0 = ((part[d] + part[64 + d]) + (part[128 + d] + part[192 + d])) * inv;
+        const float o1 = ((part[d + 1] + part[64 + d + 1]) + (part[128 + d + 1] + part[192 + d + 1])) * inv;
+        *(uint32_t*)(out + ((long long)r * H + hd) * 64 + d) = pack_bf16x2(o0, o1);
+    }
+}
+
 }  // namespace
 
 static int attention_impl(const void* qkv, int R, int N, int H, float scale, void* out, const int32_t* r_dev, float* lse,
@@ -645,6 +739,18 @@ extern "C" int yv_attention_debug(int ablate) { g_attn_abl = ablate; return YV_O
 extern "C" int yv_attention(const void* qkv, int R, int N, int H, float scale, void* out, const int32_t* r_dev,
                             void* stream) {
     return attention_impl(qkv, R, N, H, scale, out, r_dev, nullptr, stream);
+}
+
+extern "C" int yv_attention_cls(const void* q, const void* qkv, int R, int N, int H, float scale, void* out, const int32_t* r_dev,
+                                void* stream) {
+    if (!q || !qkv || !out || R < 0 || N <= 0 || H <= 0) return YV_ERR_ARG;
+    if (((uintptr_t)q | (uintptr_t)qkv | (uintptr_t)out) & 15) return YV_ERR_ARG;          // 16-byte row chunks
+    if (N > 8192 || (long long)R * H > 0x7fffffffLL) return YV_ERR_LIMIT;                  // the scores of one query live in LDS
+    if (R == 0) return YV_OK;
+    const size_t lds = ((size_t)((N + 3) & ~3) + 256 + 8) * sizeof(float);
+    hipLaunchKernelGGL(attention_cls_kernel, dim3(R * H), dim3(256), lds, (hipStream_t)stream, (const uint16_t*)q,
+                       (const uint16_t*)qkv, R, N, H, scale * 1.4426950408889634f, (uint16_t*)out, r_dev);
+    return yv_launch_status();
 }
 
 extern "C" int yv_attention_mxfp8(const void* qkv, int R, int N, int H, float scale, void* out_q, long long ldq,

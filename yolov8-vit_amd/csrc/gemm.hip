@@ -2826,6 +2826,108 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(GemmArgs g) {
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Skinny-M linear (M <= 256: one row per crop - the classifier's last-block tail on the cls rows, and its head).  Such a product
+// is a pass over the weight matrix (fc2 of ViT-B: 4.7 MB against 64 x 768 outputs); 128 x 128 tiles make 6 .. 24 workgroups of it,
+// each walking the whole K range alone.  Here a workgroup owns 64 rows x 16 columns and its 8 waves each take one eighth of K
+// (N / 16 workgroups per 64 rows: 48 .. 192 for the ViT-B shapes, every one with 8 independent load streams).  A wave reads its
+// MFMA fragments straight from global memory (16 B per lane: 16 weight rows and 64 activation rows per 32-wide K step; no LDS
+// stage, no barrier in the loop - nothing is reused inside a wave), four K steps of loads in flight at a time.
+// The eight partial tiles meet in LDS and are added in slice order 0 .. 7, so the result does not depend on the launch; the
+// epilogue (bias, GELU, f32 residual read-modify-write at any row stride, f32 / bf16 store, device-side row count) runs on the sums.
+// Host: N % 16 == 0, K % 32 == 0, flags within BIAS | GELU | RES_F32 | OUT_F32.
+// ---------------------------------------------------------------------------------------------
+int g_opt_skinny = 256;             // largest M taken by gemm_skinny_kernel ("linear_skinny"; 0 = off)
+
+__global__ __launch_bounds__(512) void gemm_skinny_kernel(GemmArgs g) {
+    constexpr int NW = 8, MF = 4;
+    __shared__ f32x4 red[NW][MF][64];                          // 32 KB
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int fr = lane & 15, fq = lane >> 4;
+    int M = g.M;
+    if (g.m_dev) { long long md = (long long)g.m_dev[0] * g.m_mul; M = md < M ? (int)md : M; }
+    const int tm = blockIdx.x / g.tiles_n, tn = blockIdx.x - tm * g.tiles_n;
+    const int m0 = tm * (16 * MF), n0 = tn * 16;
+    if (m0 >= M) return;
+
+    const int nk = g.K >> 5;
+    const int k0 = (int)((long long)nk * wave / NW), k1 = (int)((long long)nk * (wave + 1) / NW);
+    const uint16_t* wp = g.w + (long long)(n0 + fr) * g.K + fq * 8;
+    const uint16_t* ap[MF];
+#pragma unroll
+    for (int j = 0; j < MF; ++j) {
+        int m = m0 + j * 16 + fr;
+        m = m < g.M ? m : g.M - 1;                              // rows past the end: the last row, never stored
+        ap[j] = g.a0 + (long long)m * g.lda0 + fq * 8;
+    }
+    f32x4 acc[MF];
+#pragma unroll
+    for (int j = 0; j < MF; ++j) acc[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    // U K steps per trip: all their loads are issued before the first MFMA waits, so a wave's 3 (K = 768) .. 12 (K = 3072) steps
+    // cost one to three memory round trips instead of one each (this kernel is bound by latency, not by bytes)
+    constexpr int U = 4;
+    for (int k = k0; k < k1; k += U) {
+        bf16x8 fw[U], fa[U][MF];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int kk = k + u < k1 ? k + u : k1 - 1;         // past the slice: a repeated (cached) load, its MFMAs skipped
+            fw[u] = *(const bf16x8*)(wp + kk * 32);
+#pragma unroll
+            for (int j = 0; j < MF; ++j) fa[u][j] = *(const bf16x8*)(ap[j] + kk * 32);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            if (k + u < k1) {
+#pragma unroll
+                for (int j = 0; j < MF; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fw[u], fa[u][j], acc[j], 0, 0, 0);
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < MF; ++j) red[wave][j][lane] = acc[j];
+    __syncthreads();
+    if (tid >= MF * 64) return;
+    const int j = tid >> 6;
+    f32x4 s = red[0][j][lane];
+#pragma unroll
+    for (int w = 1; w < NW; ++w) s += red[w][j][lane];
+    const int m = m0 + j * 16 + fr, n = n0 + fq * 4;          // lane owns columns n .. n + 3 of row m
+    if (m >= M) return;
+    const int flags = g.flags;
+    float v[4] = {s[0], s[1], s[2], s[3]};
+    if (flags & YV_EPI_BIAS) {
+        const float4 b = *(const float4*)(g.bias + n);
+        v[0] += b.x; v[1] += b.y; v[2] += b.z; v[3] += b.w;
+    }
+    if (flags & YV_EPI_GELU) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) v[q] = gelu_f(v[q]);
+    }
+    if (flags & (YV_EPI_OUT_F32 | YV_EPI_RES_F32)) {
+        float* o = (float*)g.out + (long long)m * g.ldo + n;
+        if (flags & YV_EPI_RES_F32) {
+            const float4 x = *(const float4*)o;
+            v[0] += x.x; v[1] += x.y; v[2] += x.z; v[3] += x.w;
+        }
+        *(float4*)o = make_float4(v[0], v[1], v[2], v[3]);
+    } else {
+        uint16_t* o = (uint16_t*)g.out + (long long)m * g.ldo + n;
+        *(uint2*)o = make_uint2(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]));
+    }
+}
+
+int launch_skinny(GemmArgs& g, hipStream_t st) {
+    g.tiles_m = (g.M + 63) / 64;
+    g.tiles_n = g.N >> 4;
+    if (t_time_start || t_time_stop) {
+        hipExtLaunchKernelGGL(gemm_skinny_kernel, dim3(g.tiles_m * g.tiles_n), dim3(512), 0, st, t_time_start, t_time_stop, 0, g);
+        t_time_start = t_time_stop = nullptr;
+    } else {
+        hipLaunchKernelGGL(gemm_skinny_kernel, dim3(g.tiles_m * g.tiles_n), dim3(512), 0, st, g);
+    }
+    return yv_launch_status();
+}
+
 template <int BM, int BN, int WM, int WN, int ABL = 0, bool WT = false>
 int launch_dma(GemmArgs& g, hipStream_t st) {
     g.tiles_m = (g.M + BM - 1) / BM;
@@ -3191,6 +3293,7 @@ extern "C" int yv_set_option(const char* key, int value) {
     if (!strcmp(key, "linear_p8_sched")) { g_opt_p8_sched = value; return YV_OK; }
     if (!strcmp(key, "conv_splitk")) { g_opt_splitk = value; return YV_OK; }
     if (!strcmp(key, "linear_splitk")) { g_opt_linear_splitk = value; return YV_OK; }
+    if (!strcmp(key, "linear_skinny")) { g_opt_skinny = value; return YV_OK; }
     if (!strcmp(key, "wgrad_mx_split")) { g_opt_wgrad_mx_split = value; return YV_OK; }
     if (!strcmp(key, "conv_dma")) { g_opt_conv_dma = value; return YV_OK; }
     return YV_ERR_ARG;
@@ -3211,6 +3314,7 @@ extern "C" int yv_get_option(const char* key, int* value) {
     if (!strcmp(key, "linear_p8_sched")) { *value = g_opt_p8_sched; return YV_OK; }
     if (!strcmp(key, "conv_splitk")) { *value = g_opt_splitk; return YV_OK; }
     if (!strcmp(key, "linear_splitk")) { *value = g_opt_linear_splitk; return YV_OK; }
+    if (!strcmp(key, "linear_skinny")) { *value = g_opt_skinny; return YV_OK; }
     if (!strcmp(key, "wgrad_mx_split")) { *value = g_opt_wgrad_mx_split; return YV_OK; }
     if (!strcmp(key, "conv_dma")) { *value = g_opt_conv_dma; return YV_OK; }
     return YV_ERR_ARG;
@@ -3238,6 +3342,10 @@ static int linear_impl(const void* A, int lda, const void* W, const float* bias,
     if (res_f32 && (!g.staged || (K % BK) || N <= 64)) return YV_ERR_ARG;
     g.group_m = g_opt_group_m > 0 ? g_opt_group_m : 8;
     g.splitk = 1;
+    // one row per crop (the cls-row tail of the classifier's last block, the head): a weight-streaming pass, see gemm_skinny_kernel
+    if (g_opt_variant == 1 && M <= g_opt_skinny && !(N & 15) && !(K & 31) && !res_f32 && !aux &&
+        !(flags & ~(YV_EPI_BIAS | YV_EPI_GELU | YV_EPI_RES_F32 | YV_EPI_OUT_F32)))
+        return launch_skinny(g, stream);
     if ((K % BK) == 0 && N > 64 && g_opt_variant != 0) {
         // split-K for wgrad-shaped problems (few 128x128 output tiles, long reduction): a 2304x768 weight gradient
         // over 6336 tokens is 108 tiles for 256 CUs; slicing K fills the chip.  Deterministic: partial sums go to

@@ -119,6 +119,7 @@ _SIGS = {
     "yv_linear": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _i, _vp, _i, _vp]),
     "yv_layernorm": (_i, [_vp, _sz, _vp, _vp, _i, _i, _f, _vp, _sz, _vp, _i, _vp]),
     "yv_attention": (_i, [_vp, _i, _i, _i, _f, _vp, _vp, _vp]),
+    "yv_attention_cls": (_i, [_vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp]),
     "yv_attention_debug": (_i, [_i]),
     "yv_cls_rows": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
     "yv_wrapper_head": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _f, _i, _vp, _vp, _vp, _vp]),
@@ -565,7 +566,10 @@ def linear(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], out: 
            pos: Optional[torch.Tensor] = None, tok: int = 0, m_dev: Optional[torch.Tensor] = None, m_mul: int = 1,
            M: Optional[int] = None):
     """out[M,N] (+)= a[M,K] @ w[N,K]^T with the fused epilogue selected by `flags`."""
-    _chk_dev(a, w, bias, out, pos, m_dev)
+    _chk_dev(w, bias, pos, m_dev)
+    for t in (a, out):                       # row-strided 2-D views (every N-th row, a column range) are operands as they are
+        if not t.is_cuda or t.dim() != 2 or t.stride(1) != 1:
+            raise YvError("expected a device matrix with unit column stride")
     Mr = a.shape[0] if M is None else M
     K = a.shape[1]
     N = w.shape[0]
@@ -624,6 +628,15 @@ def attention(qkv: torch.Tensor, R: int, N: int, H: int, out: torch.Tensor, scal
     _chk_dev(qkv, out, r_dev)
     check(lib.yv_attention(_p(qkv), R, N, H, float(64 ** -0.5 if scale is None else scale), _p(out), _p(r_dev),
                            _st()), "yv_attention")
+    return out
+
+
+def attention_cls(q: torch.Tensor, qkv: torch.Tensor, R: int, N: int, H: int, out: torch.Tensor,
+                  scale: Optional[float] = None, r_dev: Optional[torch.Tensor] = None):
+    """Attention of the cls query of each crop: q (R, H*64) compact, K | V from the qkv buffer (R*N, 3*H*64), out (R, H*64)."""
+    _chk_dev(q, qkv, out, r_dev)
+    check(lib.yv_attention_cls(_p(q), _p(qkv), R, N, H, float(64 ** -0.5 if scale is None else scale), _p(out), _p(r_dev),
+                               _st()), "yv_attention_cls")
     return out
 
 

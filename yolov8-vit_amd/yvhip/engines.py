@@ -19,7 +19,7 @@ from typing import Dict, List, Optional, Tuple
 import torch
 
 from .guard import StepGuard
-from . import (set_option, EPI_GELU, EPI_OUT_F32, EPI_POSEMB, EPI_RES_BF16, EPI_RES_F32, EPI_SILU, YvError, attention, attention_mxfp8,
+from . import (set_option, get_option, EPI_GELU, EPI_OUT_F32, EPI_POSEMB, EPI_RES_BF16, EPI_RES_F32, EPI_SILU, YvError, attention, attention_cls, attention_mxfp8,
                cls_rows,
                c2f_fused, conv2d, conv2d_mxfp8, detect_decode, mx_map, mx_view, quant_conv_weight_mxfp8, quant_mxfp8_map, detect_tail, layernorm, layernorm_mxfp8, linear, linear_mxfp8, linear_mxfp8_q, quant_mxfp8, require_gpu, sppf_pool, stem_conv, view,
                wrapper_head)
@@ -548,8 +548,10 @@ class VitEngine:
     through the Network_Wrapper head, class logits (cap, nc) + labels (cap)."""
 
     def __init__(self, state: Dict[str, torch.Tensor], name: str, num_classes: int = 5, img: int = 224,
-                 device: str = "cuda:0", dtype: str = "bf16"):
-        """dtype "bf16" (default) or "mxfp8": the four block linears (qkv, proj, fc1, fc2) then run on OCP e4m3 operands
+                 device: str = "cuda:0", dtype: str = "bf16", cls_tail: bool = True):
+        """cls_tail (bf16 path): the last block runs on the cls rows only - nothing reads its other rows (see _last_block_cls);
+        False gives the full last block.
+        dtype "bf16" (default) or "mxfp8": the four block linears (qkv, proj, fc1, fc2) then run on OCP e4m3 operands
         with one E8M0 scale per 32 K elements through the block-scaled MFMA (BASELINE.json configs[4]); weights are
         quantised once here, activations by yv_quant_mxfp8 in front of each GEMM; everything else (patch-embed, LayerNorm,
         attention, residual stream, heads) keeps its bf16 / f32 form."""
@@ -557,6 +559,7 @@ class VitEngine:
         if dtype not in ("bf16", "mxfp8"):
             raise YvError("dtype must be 'bf16' or 'mxfp8'")
         self.dtype = dtype
+        self.cls_tail = bool(cls_tail)
         self.fuse_attention_quant = os.environ.get("YV_MX_ATTN_FUSED", "1") == "1"     # A/B switch of the mxfp8 path
         self.P, self.D, self.L, self.H = vit_cfg(name)
         if self.D // self.H != 64:
@@ -582,6 +585,9 @@ class VitEngine:
                 n2w=f32(g(p + "norm2.weight")), n2b=f32(g(p + "norm2.bias")),
                 wfc1=bf(g(p + "mlp.fc1.weight")), bfc1=f32(g(p + "mlp.fc1.bias")),
                 wfc2=bf(g(p + "mlp.fc2.weight")), bfc2=f32(g(p + "mlp.fc2.bias"))))
+        if dtype == "bf16":                              # last block, cls tail: the query and the K | V parts of the qkv product
+            last = self.blocks[-1]
+            last["wq"], last["bq"], last["wkv"], last["bkv"] = last["wqkv"][:D], last["bqkv"][:D], last["wqkv"][D:], last["bqkv"][D:]
         if dtype == "mxfp8":
             if D % 128:
                 raise YvError("mxfp8 needs an embedding width that is a multiple of 128")
@@ -623,6 +629,9 @@ class VitEngine:
                 x=z((cap * N, D), torch.float32), h=z((cap * N, D), torch.bfloat16),
                 qkv=z((cap * N, 3 * D), torch.bfloat16), o=z((cap * N, D), torch.bfloat16),
                 g=z((cap * N, 4 * D), torch.bfloat16), c=z((cap, D), torch.bfloat16),
+                # compact cls-row operands of the pruned last block: q, attention output, LN2 output, GELU output
+                tq=z((cap, D), torch.bfloat16), to=z((cap, D), torch.bfloat16), th=z((cap, D), torch.bfloat16),
+                tg=z((cap, 4 * D), torch.bfloat16),
                 **({} if self.dtype != "mxfp8" else dict(          # MXFP8 operand images: bytes + K-step-major block scales
                     q=z((cap * N, D), torch.uint8), qs=z((D // 128, (cap * N + 255) // 256 * 256, 4), torch.uint8),
                     gq=z((cap * N, 4 * D), torch.uint8),
@@ -644,6 +653,16 @@ class VitEngine:
             return feats if outer else feats.clone()         # bare call: a copy that the next replay cannot overwrite
 
     def _backbone(self, patches: torch.Tensor, cap: int, count: Optional[torch.Tensor], slot: int) -> torch.Tensor:
+        if self.cls_tail:
+            return self._backbone_pass(patches, cap, count, slot)
+        skinny = get_option("linear_skinny")            # the full path as it was before the cls tail: its kernels, its bits
+        set_option("linear_skinny", 0)
+        try:
+            return self._backbone_pass(patches, cap, count, slot)
+        finally:
+            set_option("linear_skinny", skinny)
+
+    def _backbone_pass(self, patches: torch.Tensor, cap: int, count: Optional[torch.Tensor], slot: int) -> torch.Tensor:
         b = self._buffers(cap, slot)
         D, N, tok, H = self.D, self.N, self.tok, self.H
         x, h, qkv, o, gbuf = b["x"], b["h"], b["qkv"], b["o"], b["g"]
@@ -656,6 +675,9 @@ class VitEngine:
         for i, blk in enumerate(self.blocks):
             if self.full_cus_from is not None and i == self.full_cus_from:
                 set_option("linear_p8_cus", 0)          # the caller (PipelinedRunner) restores its own setting after the pass
+            if self.cls_tail and i == self.L - 1:
+                self._last_block_cls(b, blk, cap, count)
+                break
             layernorm(x, blk["n1w"], blk["n1b"], h, rows, D, D, D, count_dev=count, rows_per_count=N)
             linear(h, blk["wqkv"], blk["bqkv"], qkv, m_dev=count, m_mul=N)
             attention(qkv, cap, N, H, o, r_dev=count)
@@ -666,6 +688,24 @@ class VitEngine:
         layernorm(x, self.nw, self.nb, b["c"], cap, D, N * D, D, count_dev=count, rows_per_count=1)
         linear(b["c"], self.w_head, self.b_head, b["feats"], flags=EPI_OUT_F32, m_dev=count, m_mul=1)
         return b["feats"]
+
+    def _last_block_cls(self, b: dict, blk: dict, cap: int, count: Optional[torch.Tensor]):
+        """The last block on the cls rows.  The final LayerNorm and the head read row 0 of each crop only, and inside a block token
+        rows meet only in attention, through K and V: so K | V are computed for every row, and the query, the attention, proj, LN2,
+        fc1 and fc2 for the `cap` cls rows.  Only the cls rows of x are updated; the operands in between are compact (cap, *)."""
+        D, N, H = self.D, self.N, self.H
+        x, h, qkv = b["x"], b["h"], b["qkv"]
+        if "xc" not in b:                                                   # views, made once per buffer set
+            b["xc"], b["hc"], b["kv"] = x[::N], h[::N], qkv[:, D:]          # cls rows (row stride N * D); the K | V columns
+        xc = b["xc"]
+        layernorm(x, blk["n1w"], blk["n1b"], h, cap * N, D, D, D, count_dev=count, rows_per_count=N)
+        linear(h, blk["wkv"], blk["bkv"], b["kv"], m_dev=count, m_mul=N)
+        linear(b["hc"], blk["wq"], blk["bq"], b["tq"], m_dev=count, m_mul=1)
+        attention_cls(b["tq"], qkv, cap, N, H, b["to"], r_dev=count)
+        linear(b["to"], blk["wproj"], blk["bproj"], xc, flags=EPI_RES_F32, m_dev=count, m_mul=1)
+        layernorm(x, blk["n2w"], blk["n2b"], b["th"], cap, D, N * D, D, count_dev=count, rows_per_count=1)
+        linear(b["th"], blk["wfc1"], blk["bfc1"], b["tg"], flags=EPI_GELU, m_dev=count, m_mul=1)
+        linear(b["tg"], blk["wfc2"], blk["bfc2"], xc, flags=EPI_RES_F32, m_dev=count, m_mul=1)
 
     def _backbone_mxfp8(self, b: dict, cap: int, count: Optional[torch.Tensor]) -> torch.Tensor:
         """Block linears in MXFP8.  Operand hand-offs: LayerNorm writes the qkv / fc1 operand directly, the fc1 epilogue
