@@ -280,10 +280,29 @@ typedef struct yv_view {
  * Limits: the fused 2x upsample (yv_view.up) is a property of 1x1 inputs (YV_ERR_ARG with ksize 3); the kernel
  * addresses each source and the weights with 32-bit byte offsets: a batch whose source passes 2 GB is taken in
  * sub-batches by this entry, one IMAGE (Hin*Win*ld*2) and the weights (Cout*k*k*Cin*2) must stay below 2 GB
- * (YV_ERR_LIMIT). */
+ * (YV_ERR_LIMIT).
+ * Epilogue order: bias -> SiLU -> + bf16 residual -> store.  With YV_EPI_RES_BF16 and a bf16 output the number of roundings
+ * depends on the route (yv_conv2d_instance reports it):
+ *   direct epilogue (staged bit clear: 16- / 32-wide tiles, an output or residual that is not 16-byte aligned with a stride
+ *   that is a multiple of 8, "staged_epilogue" = 0, split-K):  out = bf16(y + r), ONE rounding;
+ *   staged epilogue (staged bit set: every LDS-DMA route, the 64- / 128-wide tiles otherwise):  out = bf16(bf16(y) + r), the
+ *   activation is rounded to bf16 BEFORE the residual is added, TWO roundings.
+ * Without a residual, and with YV_EPI_OUT_F32, both forms give the same bits. */
 int yv_conv2d(const yv_view* in0, const yv_view* in1, int B, int Hout, int Wout, int ksize, int stride,
               const void* weight, const float* bias, int Cout, void* out, int out_ld, const void* res, int res_ld,
               int flags, void* stream);
+
+/* Diagnostic, host only (no HIP call): the route yv_conv2d_ws takes for this shape under the current options, for dense sources
+ * (pixel stride = c0 / c1, no upsample - neither changes the route) and base pointers aligned to 16 bytes (a base that is not
+ * clears the staged bit and with it every LDS-DMA route); ws_bytes = 0: no workspace (yv_conv2d).  For a batch that is taken in
+ * sub-batches, the route of the first one.  Returns a negative YV_ERR_* code where yv_conv2d rejects the arguments, else
+ *   bits 0-3  kernel instance: 0 .. 3 igemm_kernel with 128 x 16 / 32 / 64 / 128 tiles;
+ *             4 cgemm_dma_kernel<64,4,1,2>, 5 <64,4,1,3>, 6 <64,4,1,4>, 7 <128,2,2,2>, 8 <128,2,2,3>  (<tile width, waves, stages>)
+ *   bit 4 (16) the staged epilogue runs (see yv_conv2d for what that means for the shortcut's rounding)
+ *   bit 5 (32) split-K: partial sums in the workspace, epilogue in the reduce pass
+ *   bit 6 (64) the two-source instantiation of igemm_kernel (c1 > 0; the LDS-DMA kernels have no separate one). */
+int yv_conv2d_instance(int B, int Hout, int Wout, int ksize, int stride, int c0, int c1, int Cout, int out_ld, int res_ld,
+                       int flags, size_t ws_bytes);
 
 /* MXFP8 convolutions (BASELINE.json configs[4]: FP8 detector convolutions; opt-in, YoloEngine(dtype="mxfp8")).
  * An "MX map" is an NHWC activation in the operand format of the block-scaled MFMA: e4m3 bytes q (B,H,W,ld) and one E8M0
@@ -324,8 +343,10 @@ int yv_conv2d_mxfp8_instance(int B, int Hout, int Wout, int ksize, int stride, i
  * c -> c with the residual add, cv2 (1x1, (2+n)c -> 2c), SiLU after every layer (BN folded).  x (B,H,W,>=2c) bf16 with pixel
  * stride ldx, out (B,H,W,>=2c) bf16 with pixel stride ldo; weights (Cout, k*k*Cin) bf16 with K order (ky,kx,cin) and f32
  * biases exactly as yv_conv2d takes them; w_m / b_m: 2n entries {m0.cv1, m0.cv2, m1.cv1, m1.cv2}.  c in {16, 32}, n in {1, 2}
- * (anything else: YV_ERR_ARG - run the block layer by layer).  Same arithmetic per output as the layer-by-layer path
- * (K order, f32 accumulation, bias -> SiLU -> + residual -> one bf16 rounding). */
+ * (anything else: YV_ERR_ARG - run the block layer by layer).  Same arithmetic per output as the layer-by-layer path at these
+ * widths (K order, f32 accumulation, bias -> SiLU -> + residual -> one bf16 rounding: layers of 16 / 32 output channels take
+ * yv_conv2d's direct epilogue.  Wider Bottlenecks, c >= 64, run layer by layer on the staged epilogue, which rounds the
+ * activation to bf16 BEFORE it adds the shortcut - see yv_conv2d). */
 int yv_c2f_fused(const void* x, long long ldx, int B, int H, int W, int c, int n, const void* w_cv1, const float* b_cv1,
                  const void* const* w_m, const float* const* b_m, const void* w_cv2, const float* b_cv2, void* out,
                  long long ldo, void* stream);

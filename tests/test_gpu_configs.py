@@ -1,9 +1,10 @@
 """Full-size GPU parity of the BASELINE.json configurations (configs[1]..configs[4]) against the fp32 CPU oracle.
 
 The kernel-level tests elsewhere use miniature models so that the oracle finishes in a blink; these run every
-configuration's REAL model (ViT-B/16, ViT-L/16, YOLOv8n/s/m at 640 x 640) through the HIP path with a small batch -
-the batch size does not change any kernel's code path except the tile count - and compare with the oracle on the same
-seeded inputs.  Tolerances (north_star "stated fp tolerance"): bf16 path vs fp32 oracle rel-L2 <= 2e-2
+configuration's REAL model (ViT-B/16, ViT-L/16, YOLOv8n/s/m at 640 x 640) through the HIP path with a small batch and compare with the oracle on the same
+seeded inputs.  (The batch size DOES change the route of a convolution: layers with >= 100,000 output pixels and more than 64
+output channels - the 80 x 80 head convolutions from batch 16 up - run cgemm_dma_kernel<128,2,2,2>, which no batch used here
+reaches; tests/test_gpu_conv_routes.py runs that instance, and every other one, against an exact integer reference.)  Tolerances (north_star "stated fp tolerance"): bf16 path vs fp32 oracle rel-L2 <= 2e-2
 on logits / raw head outputs, <= 3e-2 after the whole detect -> crop -> classify chain; integer stages bit-exact.
 Parity is UNPINNED against timm / ultralytics (absent from the reference tree and from this image, see oracle/*.py).
 """

@@ -3017,43 +3017,85 @@ int launch_cmx(ConvMxArgs& a, hipStream_t st) {       // two LDS stages of 128 +
     return yv_launch_status();
 }
 
-template <int MODE>
-int dispatch(GemmArgs& g, hipStream_t st) {
-    if constexpr (MODE == 1) {
-        const int Cin = g.c0 + g.c1;
-        if (g_opt_conv_dma && g.N >= 64 && (Cin % 64) == 0 && (g.c1 == 0 || (g.ksize == 1 && (g.c0 % 64) == 0)) && g.staged &&
-            g.splitk <= 1 && !g.m_dev && (g.K % BK) == 0)
-        {
-            // conv_dma: 1 = two stages (128-wide tiles for Cout > 64), 2 = three stages, 64-wide tiles (two workgroups per CU, four K
-            // steps in flight per CU), 3 = three stages, 128-wide tiles (one workgroup per CU), 4 = four stages, 64-wide tiles,
-            // 5 .. 8 mixtures.  Shipped: 8 = three stages / 64-wide, except the 128-channel layers of the large maps (>= 100 k output
-            // pixels: the 80 x 80 head convolution at batch 32), which read their pixels once on two-stage 128-wide tiles (70 -> 57 us
-            // alone; detect stage 1.175 -> 1.163 ms, YOLOv8m + ViT-L/16 1,376 -> 1,397 images/s; tools/conv_dma_ab.py)
-            if (g_opt_conv_dma == 2) return launch_cdma<64, 4, 1, 3>(g, st);
-            if (g_opt_conv_dma == 3) return g.N > 64 ? launch_cdma<128, 2, 2, 3>(g, st) : launch_cdma<64, 4, 1, 3>(g, st);
-            if (g_opt_conv_dma == 4) return launch_cdma<64, 4, 1, 4>(g, st);
-            if (g_opt_conv_dma == 5) {      // by reduction depth: deep K (>= 1024) three stages / 64-wide, shallow K two stages
-                if (g.K >= 1024) return launch_cdma<64, 4, 1, 3>(g, st);
-                return g.N > 64 ? launch_cdma<128, 2, 2, 2>(g, st) : launch_cdma<64, 4, 1, 2>(g, st);
-            }
-            if (g_opt_conv_dma == 7) {      // by rows: the large maps (>= 100 k output pixels) two stages, 128-wide where Cout allows
-                if (g.M >= 100000) return g.N > 64 ? launch_cdma<128, 2, 2, 2>(g, st) : launch_cdma<64, 4, 1, 2>(g, st);
-                return launch_cdma<64, 4, 1, 3>(g, st);
-            }
-            if (g_opt_conv_dma == 8) {      // as 7, only the 128-wide layers of the large maps
-                if (g.M >= 100000 && g.N > 64) return launch_cdma<128, 2, 2, 2>(g, st);
-                return launch_cdma<64, 4, 1, 3>(g, st);
-            }
-            if (g_opt_conv_dma == 6) {      // as 5, but 64-wide tiles everywhere
-                return g.K >= 1024 ? launch_cdma<64, 4, 1, 3>(g, st) : launch_cdma<64, 4, 1, 2>(g, st);
-            }
-            return g.N > 64 ? launch_cdma<128, 2, 2, 2>(g, st) : launch_cdma<64, 4, 1, 2>(g, st);
-        }
+// Kernel instances of a convolution (the low four bits of yv_conv2d_instance's code, include/yv_hip.h)
+enum ConvKern {
+    CK_IGEMM_16 = 0, CK_IGEMM_32 = 1, CK_IGEMM_64 = 2, CK_IGEMM_128 = 3,              // igemm_kernel<1, 128, BN, ..>
+    CK_CDMA_64_2 = 4, CK_CDMA_64_3 = 5, CK_CDMA_64_4 = 6, CK_CDMA_128_2 = 7, CK_CDMA_128_3 = 8   // cgemm_dma_kernel<BN, .., ST>
+};
+
+int igemm_pick(int N) { return N > 64 ? CK_IGEMM_128 : (N > 32 ? CK_IGEMM_64 : (N > 16 ? CK_IGEMM_32 : CK_IGEMM_16)); }
+
+// The route of one convolution launch: ONE rule for conv_impl_one (which launches it) and yv_conv2d_instance (which reports it).
+// Reads the shape, flags, strides and base pointers of g; writes g.staged and g.splitk (g.partial is the caller's) and returns the
+// kernel instance.
+int conv_route(GemmArgs& g, bool have_ws, size_t ws_bytes) {
+    g.staged = g_opt_staged && epi_can_stage(g);
+    // split-K: deep small-resolution layers (20x20 / 40x40 maps) give 100-400 tiles for 256 CUs and a serial chain of
+    // 9-36 K steps per tile at one workgroup per CU; slicing K puts >= 2 workgroups on every CU and shortens the chain
+    g.splitk = 1;
+    if (have_ws && g_opt_splitk) {
+        const int bn = g.N > 64 ? 128 : (g.N > 32 ? 64 : (g.N > 16 ? 32 : 16));
+        const long long tiles = (long long)((g.M + 127) / 128) * ((g.N + bn - 1) / bn);
+        const int nk = (g.K + BK - 1) / BK;
+        int S = (int)(640 / tiles);
+        if (S > nk / 2) S = nk / 2;
+        if (S > 8) S = 8;
+        if (S >= 2 && (size_t)S * g.M * g.N * sizeof(float) <= ws_bytes && !(g.N & 3)) g.splitk = S;
     }
-    if (g.N > 64) return launch<MODE, 128, 128, 2, 2>(g, st);
-    if (g.N > 32) return launch<MODE, 128, 64, 4, 1>(g, st);
-    if (g.N > 16) return launch<MODE, 128, 32, 4, 1>(g, st);
-    return launch<MODE, 128, 16, 4, 1>(g, st);
+    const int Cin = g.c0 + g.c1;
+    if (g_opt_conv_dma && g.N >= 64 && (Cin % 64) == 0 && (g.c1 == 0 || (g.ksize == 1 && (g.c0 % 64) == 0)) && g.staged &&
+        g.splitk <= 1 && !g.m_dev && (g.K % BK) == 0)
+    {
+        // conv_dma: 1 = two stages (128-wide tiles for Cout > 64), 2 = three stages, 64-wide tiles (two workgroups per CU, four K
+        // steps in flight per CU), 3 = three stages, 128-wide tiles (one workgroup per CU), 4 = four stages, 64-wide tiles,
+        // 5 .. 8 mixtures.  Shipped: 8 = three stages / 64-wide, except the 128-channel layers of the large maps (>= 100 k output
+        // pixels: the 80 x 80 head convolution at batch 32), which read their pixels once on two-stage 128-wide tiles (70 -> 57 us
+        // alone; detect stage 1.175 -> 1.163 ms, YOLOv8m + ViT-L/16 1,376 -> 1,397 images/s; tools/conv_dma_ab.py)
+        const int two_stage = g.N > 64 ? CK_CDMA_128_2 : CK_CDMA_64_2;
+        if (g_opt_conv_dma == 2) return CK_CDMA_64_3;
+        if (g_opt_conv_dma == 3) return g.N > 64 ? CK_CDMA_128_3 : CK_CDMA_64_3;
+        if (g_opt_conv_dma == 4) return CK_CDMA_64_4;
+        if (g_opt_conv_dma == 5)        // by reduction depth: deep K (>= 1024) three stages / 64-wide, shallow K two stages
+            return g.K >= 1024 ? CK_CDMA_64_3 : two_stage;
+        if (g_opt_conv_dma == 7)        // by rows: the large maps (>= 100 k output pixels) two stages, 128-wide where Cout allows
+            return g.M >= 100000 ? two_stage : CK_CDMA_64_3;
+        if (g_opt_conv_dma == 8)        // as 7, only the 128-wide layers of the large maps
+            return (g.M >= 100000 && g.N > 64) ? CK_CDMA_128_2 : CK_CDMA_64_3;
+        if (g_opt_conv_dma == 6)        // as 5, but 64-wide tiles everywhere
+            return g.K >= 1024 ? CK_CDMA_64_3 : CK_CDMA_64_2;
+        return two_stage;
+    }
+    return igemm_pick(g.N);
+}
+
+template <int MODE>
+int launch_igemm(GemmArgs& g, int kern, hipStream_t st) {
+    switch (kern) {
+    case CK_IGEMM_128: return launch<MODE, 128, 128, 2, 2>(g, st);
+    case CK_IGEMM_64: return launch<MODE, 128, 64, 4, 1>(g, st);
+    case CK_IGEMM_32: return launch<MODE, 128, 32, 4, 1>(g, st);
+    default: return launch<MODE, 128, 16, 4, 1>(g, st);
+    }
+}
+
+int launch_conv(GemmArgs& g, int kern, hipStream_t st) {
+    switch (kern) {
+    case CK_CDMA_64_2: return launch_cdma<64, 4, 1, 2>(g, st);
+    case CK_CDMA_64_3: return launch_cdma<64, 4, 1, 3>(g, st);
+    case CK_CDMA_64_4: return launch_cdma<64, 4, 1, 4>(g, st);
+    case CK_CDMA_128_2: return launch_cdma<128, 2, 2, 2>(g, st);
+    case CK_CDMA_128_3: return launch_cdma<128, 2, 2, 3>(g, st);
+    default: return launch_igemm<1>(g, kern, st);
+    }
+}
+
+// the code yv_conv2d_instance documents: the staged bit is set where the staged epilogue RUNS (finish_tile takes it on the 64-column
+// wave tiles only, and a split-K launch leaves the epilogue to splitk_reduce_kernel)
+int conv_instance_code(const GemmArgs& g, int kern) {
+    const bool split = g.splitk > 1;
+    const bool staged = g.staged && !split && kern >= CK_IGEMM_64;
+    const bool two = g.c1 > 0 && kern <= CK_IGEMM_128;
+    return kern | (staged ? 16 : 0) | (split ? 32 : 0) | (two ? 64 : 0);
 }
 
 }  // namespace
@@ -3411,7 +3453,7 @@ static int linear_impl(const void* A, int lda, const void* W, const float* bias,
             default: return launch_dma<128, 128, 2, 2>(g, stream);
         }
     }
-    return dispatch<0>(g, stream);
+    return launch_igemm<0>(g, igemm_pick(g.N), stream);
 }
 
 extern "C" int yv_linear(const void* A, int lda, const void* W, const float* bias, int M, int N, int K, void* out,
@@ -3428,7 +3470,7 @@ extern "C" int yv_linear_ex(const void* A, int lda, const void* W, const float* 
 
 static int conv_impl_one(const yv_view* in0, const yv_view* in1, int B, int Hout, int Wout, int ksize, int stride,
                          const void* weight, const float* bias, int Cout, void* out, int out_ld, const void* res,
-                         int res_ld, int flags, void* ws, size_t ws_bytes, void* stream) {
+                         int res_ld, int flags, void* ws, size_t ws_bytes, void* stream, bool query = false) {
     if (!in0 || !in0->ptr || !weight || !out || B <= 0 || Hout <= 0 || Wout <= 0 || Cout <= 0) return YV_ERR_ARG;
     if (!(ksize == 1 || ksize == 3) || !(stride == 1 || stride == 2)) return YV_ERR_ARG;
     if (in1 && in1->ptr && ksize != 1) return YV_ERR_ARG;
@@ -3458,33 +3500,20 @@ static int conv_impl_one(const yv_view* in0, const yv_view* in1, int B, int Hout
     g.w = (const uint16_t*)weight; g.bias = bias;
     g.M = B * Hout * Wout; g.N = Cout; g.K = ksize * ksize * Cin;
     g.out = out; g.ldo = out_ld; g.res = (const uint16_t*)res; g.ldres = res_ld; g.flags = flags;
-    g.staged = g_opt_staged && epi_can_stage(g);
-    // split-K: deep small-resolution layers (20x20 / 40x40 maps) give 100-400 tiles for 256 CUs and a serial chain of
-    // 9-36 K steps per tile at one workgroup per CU; slicing K puts >= 2 workgroups on every CU and shortens the chain
-    g.splitk = 1;
-    if (ws && g_opt_splitk) {
-        const int bn = g.N > 64 ? 128 : (g.N > 32 ? 64 : (g.N > 16 ? 32 : 16));
-        const long long tiles = (long long)((g.M + 127) / 128) * ((g.N + bn - 1) / bn);
-        const int nk = (g.K + BK - 1) / BK;
-        int S = (int)(640 / tiles);
-        if (S > nk / 2) S = nk / 2;
-        if (S > 8) S = 8;
-        if (S >= 2 && (size_t)S * g.M * g.N * sizeof(float) <= ws_bytes && !(g.N & 3)) {
-            g.splitk = S;
-            g.partial = (float*)ws;
-        }
-    }
-    return dispatch<1>(g, (hipStream_t)stream);
+    const int kern = conv_route(g, ws != nullptr, ws_bytes);
+    if (query) return conv_instance_code(g, kern);                // yv_conv2d_instance: the route, no launch
+    if (g.splitk > 1) g.partial = (float*)ws;
+    return launch_conv(g, kern, (hipStream_t)stream);
 }
 
 // The kernel addresses each source with 32-bit byte offsets (< 2 GB): larger batches are taken in sub-batches, images being
 // independent (e.g. the 48-channel C2f buffer of YOLOv8n at 320 x 320 passes 2 GB at 218 images).
 static int conv_impl(const yv_view* in0, const yv_view* in1, int B, int Hout, int Wout, int ksize, int stride,
                      const void* weight, const float* bias, int Cout, void* out, int out_ld, const void* res,
-                     int res_ld, int flags, void* ws, size_t ws_bytes, void* stream) {
+                     int res_ld, int flags, void* ws, size_t ws_bytes, void* stream, bool query = false) {
     if (!in0 || !in0->ptr || B <= 0 || Hout <= 0 || Wout <= 0 || !out)
         return conv_impl_one(in0, in1, B, Hout, Wout, ksize, stride, weight, bias, Cout, out, out_ld, res, res_ld, flags, ws, ws_bytes,
-                             stream);
+                             stream, query);
     const long long Hin = (long long)Hout * stride, Win = (long long)Wout * stride;
     const bool two = in1 && in1->ptr;
     const long long s0 = (Hin >> in0->up) * (Win >> in0->up) * in0->ld * 2;
@@ -3495,7 +3524,7 @@ static int conv_impl(const yv_view* in0, const yv_view* in1, int B, int Hout, in
     if (two && s1 > 0 && cap / s1 < nb) nb = cap / s1;
     if (nb >= B)
         return conv_impl_one(in0, in1, B, Hout, Wout, ksize, stride, weight, bias, Cout, out, out_ld, res, res_ld, flags, ws, ws_bytes,
-                             stream);
+                             stream, query);
     if (nb < 1) return YV_ERR_LIMIT;                              // a single image beyond 2 GB
     const long long esz = (flags & YV_EPI_OUT_F32) ? 4 : 2;
     for (long long b0 = 0; b0 < B; b0 += nb) {
@@ -3506,8 +3535,8 @@ static int conv_impl(const yv_view* in0, const yv_view* in1, int B, int Hout, in
         const int rc = conv_impl_one(&v0, two ? &v1 : nullptr, n, Hout, Wout, ksize, stride, weight, bias, Cout,
                                      (unsigned char*)out + b0 * Hout * Wout * out_ld * esz, out_ld,
                                      res ? (const unsigned char*)res + b0 * Hout * Wout * res_ld * 2 : nullptr, res_ld, flags, ws, ws_bytes,
-                                     stream);
-        if (rc != YV_OK) return rc;
+                                     stream, query);
+        if (rc != YV_OK || query) return rc;                       // a query reports the first sub-batch
     }
     return YV_OK;
 }
@@ -3603,6 +3632,16 @@ extern "C" int yv_conv2d_ws(const yv_view* in0, const yv_view* in1, int B, int H
                             int res_ld, int flags, void* ws, size_t ws_bytes, void* stream) {
     return conv_impl(in0, in1, B, Hout, Wout, ksize, stride, weight, bias, Cout, out, out_ld, res, res_ld, flags, ws, ws_bytes,
                      stream);
+}
+
+extern "C" int yv_conv2d_instance(int B, int Hout, int Wout, int ksize, int stride, int c0, int c1, int Cout, int out_ld,
+                                  int res_ld, int flags, size_t ws_bytes) {
+    // dense sources (pixel stride = channels read) at 16-byte aligned bases; nothing is dereferenced or launched
+    static unsigned char dummy[16] __attribute__((aligned(16)));
+    if (c0 <= 0 || c1 < 0) return YV_ERR_ARG;
+    const yv_view v0 = {dummy, c0, c0, 0}, v1 = {dummy, c1, c1, 0};
+    return conv_impl(&v0, c1 ? &v1 : nullptr, B, Hout, Wout, ksize, stride, dummy, (const float*)dummy, Cout, dummy, out_ld,
+                     (flags & YV_EPI_RES_BF16) ? dummy : nullptr, res_ld, flags, ws_bytes ? dummy : nullptr, ws_bytes, nullptr, true);
 }
 
 // ---------------------------------------------------------------------------------------------------- MXFP8 convolutions

@@ -114,6 +114,7 @@ _SIGS = {
     "yv_conv_weight_dgrad": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "yv_conv2d": (_i, [C.POINTER(yv_view), C.POINTER(yv_view), _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _i, _vp, _i,
                        _i, _vp]),
+    "yv_conv2d_instance": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _sz]),
     "yv_conv2d_ws": (_i, [C.POINTER(yv_view), C.POINTER(yv_view), _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _i, _vp, _i,
                           _i, _vp, _sz, _vp]),
     "yv_linear": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _i, _vp, _i, _vp]),
@@ -595,7 +596,7 @@ def _conv_workspace(device) -> torch.Tensor:
     """Split-K partial-sum workspace (64 MB f32 per device, allocated once; launches on one stream serialise on it)."""
     key = str(device)
     if key not in _CONV_WS:
-        _CONV_WS[key] = torch.empty((16 * 1024 * 1024,), dtype=torch.float32, device=device)
+        _CONV_WS[key] = torch.empty((CONV_WS_BYTES // 4,), dtype=torch.float32, device=device)
     return _CONV_WS[key]
 
 
@@ -613,6 +614,24 @@ def conv2d(in0: "yv_view", in1: Optional["yv_view"], B: int, Hout: int, Wout: in
                            0 if res is None else res.shape[-1], flags | EPI_BIAS, _p(ws), ws.numel() * 4, _st()),
           "yv_conv2d_ws")
     return out
+
+
+CONV_WS_BYTES = 16 * 1024 * 1024 * 4      # the workspace conv2d passes (what conv2d_instance assumes by default)
+# conv2d_instance codes: kernel instance in the low four bits ...
+CONV_IGEMM_16, CONV_IGEMM_32, CONV_IGEMM_64, CONV_IGEMM_128 = 0, 1, 2, 3
+CONV_DMA_64_2, CONV_DMA_64_3, CONV_DMA_64_4, CONV_DMA_128_2, CONV_DMA_128_3 = 4, 5, 6, 7, 8
+# ... and flag bits: the staged epilogue runs, split-K, the two-source igemm instantiation
+CONV_STAGED, CONV_SPLITK, CONV_TWO = 16, 32, 64
+
+
+def conv2d_instance(B: int, Hout: int, Wout: int, ksize: int, stride: int, c0: int, c1: int, Cout: int, out_ld: int,
+                    res_ld: int = 0, flags: int = 0, ws_bytes: int = CONV_WS_BYTES) -> int:
+    """Route conv2d takes for this shape under the current options (host only, no GPU needed): kernel instance | CONV_STAGED |
+    CONV_SPLITK | CONV_TWO, see yv_conv2d_instance in include/yv_hip.h.  `flags` as conv2d takes them (EPI_BIAS is added);
+    16-byte aligned bases are assumed."""
+    r = lib.yv_conv2d_instance(B, Hout, Wout, ksize, stride, c0, c1, Cout, out_ld, res_ld, flags | EPI_BIAS, ws_bytes)
+    check(min(r, 0), "yv_conv2d_instance")
+    return r
 
 
 def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, y: torch.Tensor, rows: int, D: int,
