@@ -42,5 +42,18 @@ def test_skinny_option_is_known():
     yvhip.set_option("linear_skinny", 0)
     try:
         assert yvhip.get_option("linear_skinny") == 0
+        # options are process-wide, except "linear_p8_cus": it belongs to the thread that set it
+        import threading
+        seen = {}
+        other = threading.Thread(target=lambda: seen.update(cus=yvhip.get_option("linear_p8_cus"),
+                                                            skinny=yvhip.get_option("linear_skinny")))
+        yvhip.set_option("linear_p8_cus", 96)
+        try:
+            assert yvhip.get_option("linear_p8_cus") == 96
+            other.start()
+            other.join()
+        finally:
+            yvhip.set_option("linear_p8_cus", 0)
+        assert seen == {"cus": 0, "skinny": 0}
     finally:
         yvhip.set_option("linear_skinny", 256)

@@ -1,10 +1,11 @@
 // Dev tool (GPU box): stand-alone lab for the classifier GEMMs - no torch, starts in a second.
 //   build:  make -C tools gemm_lab        (hipcc, gfx950; the binary travels with the snapshot)
 //   run:    tools/build/gemm_lab [mode ...]
-// It includes the product translation unit so that every kernel / launcher of csrc/gemm.hip is visible, times variants
+// It includes the product translation units (csrc/gemm.hip, csrc/gemm_persistent.hip) so that every kernel / launcher is visible, times variants
 // interleaved in one process on the ViT-B/16 shapes of the bench (random data), compares outputs bit for bit against the
 // shipped kernel, and runs the DIAG instance of gemm_p8_kernel (per-segment cycle sums).
 #include "../yolov8-vit_amd/csrc/gemm.hip"
+#include "../yolov8-vit_amd/csrc/gemm_persistent.hip"
 #include <vector>
 #include <string>
 #include <algorithm>

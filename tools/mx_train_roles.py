@@ -42,7 +42,7 @@ def main():
     for name, dur, sid in rows:
         if name.startswith("__amd"):
             continue
-        short = name.replace("(anonymous namespace)::", "").replace("void ", "", 1).split("(")[0]
+        short = name.replace("yvgemm::", "").replace("(anonymous namespace)::", "").replace("void ", "", 1).split("(")[0]
         per[short][0] += 1
         per[short][1] += dur
         roles[role(short, sid not in main_streams)] += dur

@@ -577,9 +577,7 @@ int launch_attn_pipe(const uint16_t* qkv, int R, int N, int H, float scale, uint
     const size_t lds = (size_t)5 * NP * 128;                   // K, V double-buffered + this item's query rows
     auto kern = g_attn_abl == 11 ? attention_pipe_kernel<NT, 1> : g_attn_abl == 12 ? attention_pipe_kernel<NT, 2> :
                 g_attn_abl == 13 ? attention_pipe_kernel<NT, 3> : attention_pipe_kernel<NT, 0>;
-    if (lds > 65536 &&
-        hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return YV_ERR_LAUNCH;
+    if (!yv_grant_lds((const void*)kern, lds)) return YV_ERR_LAUNCH;
     // items per workgroup: enough to amortise the pipeline fill, few enough that the grid still fills and balances the chip
     const int items = R * H;
     int per = items / 256;
@@ -597,9 +595,7 @@ int launch_attn(const uint16_t* qkv, int R, int N, int H, float scale, uint16_t*
     const bool single = N <= NP && g_attn_abl != 4;           // ablation 4: the round-1 form of the single-tile case (all groups held)
     auto kern = g_attn_abl == 1 ? attention_kernel<NT, 1> : g_attn_abl == 2 ? attention_kernel<NT, 2> : g_attn_abl == 3 ? attention_kernel<NT, 3> :
                 single ? attention_kernel<NT, 0, true> : attention_kernel<NT, 0, false>;
-    if (lds > 65536 &&
-        hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return YV_ERR_LAUNCH;
+    if (!yv_grant_lds((const void*)kern, lds)) return YV_ERR_LAUNCH;
     const int QB = (N + NP - 1) / NP;
     hipLaunchKernelGGL(kern, dim3(R * H * QB), dim3(NT * 64), lds, st, qkv, N, H, QB, scale * 1.4426950408889634f, out,
                        r_dev, lse, mx);

@@ -238,9 +238,7 @@ int launch_bwd(const uint16_t* qkv, const uint16_t* o, const uint16_t* dout, con
     const size_t lds_kv = (size_t)2 * NP * 128 + 2 * 64 * TS + 2 * NP * 4;
     auto kq = attn_bwd_dq_kernel<NT>;
     auto kkv = attn_bwd_dkv_kernel<NT>;
-    if (hipFuncSetAttribute((const void*)kq, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_q) != hipSuccess ||
-        hipFuncSetAttribute((const void*)kkv, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_kv) != hipSuccess)
-        return YV_ERR_LAUNCH;
+    if (!yv_grant_lds((const void*)kq, lds_q) || !yv_grant_lds((const void*)kkv, lds_kv)) return YV_ERR_LAUNCH;
     const float c = scale * 1.4426950408889634f;
     const int QB = (N + NP - 1) / NP;
     hipLaunchKernelGGL(kq, dim3(R * H * QB), dim3(NT * 64), lds_q, st, qkv, o, dout, lse, N, H, QB, scale, c, dqkv, delta);

@@ -19,7 +19,6 @@
 // K order (tap, channel) and one f32 rounding chain per output: bias -> SiLU -> (+ residual) -> bf16, as the layer kernels'
 // unstaged epilogue (gemm.hip) - tests/test_gpu_models.py compares the two paths.
 #include "yv_common.h"
-#include <atomic>
 
 namespace {
 
@@ -337,14 +336,7 @@ template <int C, int NB, int TT>
 int launch_c2f(C2fArgs& a, hipStream_t st) {
     constexpr int lds = C2fGeo<C, NB, TT>::BYTES;
     static_assert(lds <= 160 * 1024, "LDS");
-    static std::atomic<int> granted[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return YV_ERR_LAUNCH;
-    if (lds > 65536 && !granted[dev].load(std::memory_order_relaxed)) {
-        if (hipFuncSetAttribute((const void*)c2f_fused_kernel<C, NB, TT>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
-            return YV_ERR_LAUNCH;
-        granted[dev].store(1, std::memory_order_relaxed);
-    }
+    if (!yv_grant_lds((const void*)c2f_fused_kernel<C, NB, TT>, lds)) return YV_ERR_LAUNCH;
     a.tiles_x = (a.W + TT - 1) / TT; a.tiles_y = (a.H + TT - 1) / TT;
     const long long grid = (long long)a.tiles_x * a.tiles_y * a.B;
     if (grid > 0x7fffffffLL) return YV_ERR_LIMIT;

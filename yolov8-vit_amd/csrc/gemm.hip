@@ -22,18 +22,16 @@
 #include <type_traits>
 #include <map>
 #include <mutex>
-#include <atomic>
-#include "yv_common.h"
-#include <hip/hip_ext.h>
+#include "gemm_common.h"
+
+using namespace yvgemm;
+
+thread_local hipEvent_t yvgemm::t_time_start = nullptr, yvgemm::t_time_stop = nullptr;   // yv_set_launch_timing: next timed launch (launch_timed)
 
 namespace {
 
-constexpr int BK = 64;            // bf16 elements per K step
-int g_opt_p9_small = 1;              // gemm_p9_kernel: 128 / 96-row tiles allowed ("linear_p9_small")
-int g_opt_p9_small_fixed = 48;       // ... and the fixed part of their cost per K tile, in rows ("linear_p9_small_fixed")
 int g_opt_wgrad_split = 0;           // > 0: forced number of token slices of a matrix-shaped weight gradient (tools/wgrad_bench.py)
 int g_opt_wgrad_cap = 128;          // token slices of a conv-shaped weight gradient (few output tiles, 10^5+ rows)
-thread_local hipEvent_t t_time_start = nullptr, t_time_stop = nullptr;   // yv_set_launch_timing: next gemm_dma launch
 int g_opt_variant = 1;            // 1 = auto; tuning knobs (yv_set_option): linear kernel variant, M-group size, persistent grid
 int g_opt_group_m = 8;
 int g_opt_staged = 1;
@@ -52,87 +50,12 @@ int g_opt_linear_splitk = 1;
 int g_opt_splitk = 0;           // measured neutral end-to-end (tools/e2e_ab.py): the reduce pass costs what the shorter chain saves
 constexpr int THREADS = 256;
 
-struct GemmArgs {
-    // A operand (activations)
-    const uint16_t* a0;
-    const uint16_t* a1;          // second concat source (1x1 conv only) or null
-    int lda0, lda1;              // pixel / row stride in elements
-    int seg_len;                 // gemm_tn only: X column k lives at (k / seg_len) * seg_stride + k % seg_len (0: plain)
-    long long seg_stride;
-    int c0, c1;                  // channels per source (c0 + c1 = Cin); linear: c0 = K
-    int up0, up1;                // nearest-2x upsample flags
-    int Hin, Win;                // logical input grid (after upsample)
-    int Hout, Wout, ksize, stride;
-    // W operand
-    const uint16_t* w;           // (N, K) bf16
-    const float* bias;
-    int M, N, K;
-    // output
-    void* out;
-    int ldo;
-    const uint16_t* res;         // bf16 residual view
-    int ldres;
-    const float* pos;            // pos_embed (tok+1, N) f32
-    int tok;
-    int flags;
-    const int32_t* m_dev;
-    int m_mul;
-    int tiles_m, tiles_n;
-    int group_m;
-    int ldw;                     // WT kernels: row stride of the reduction-major weight (K, N)
-    const float* resf;           // f32 residual source (null: read-modify-write `out`)
-    uint16_t* aux;               // bf16 side buffer: SAVE_PRE target / GELU_BWD pre-activation
-    int ldaux;
-    int cin_shift;               // conv: log2(c0 + c1) when that is a power of two, else -1
-    int tap_uniform;             // conv: (c0 + c1) % 64 == 0, a K step lies inside one tap
-    int splitk;                  // conv only: K range split over `splitk` workgroups per tile (partials in `partial`)
-    float* partial;              // (splitk, M, N) f32
-    int staged;                  // coalesced LDS-staged epilogue usable (alignment / width checked on the host)
-    int sched;                   // gemm_p8: 0 = the grid strides through the tile sequence round by round, 1 = one contiguous
-                                 //          share of the sequence per XCD
-    uint8_t* mxq;                // YV_EPI_OUT_MXFP8: e4m3 image of the output (row stride ldmxq bytes) ...
-    long long ldmxq;
-    uint8_t* mxs;                // ... and its E8M0 block scales, K-step-major (N/128, mx_rows, 4)
-    long long mx_rows;
-    // gemm_p9_kernel<MX>: E8M0 scales of the fp8 operands, K-step-major (K/128, rows, 4) (a0 / w then point at e4m3 bytes, lda0 in bytes)
-    const uint8_t* mx_sa;
-    const uint8_t* mx_sw;
-    long long mx_rows_a, mx_rows_w;
-};
-
 // x * sigmoid(x) through the hardware reciprocal (1 ulp) instead of an IEEE division: the division's scale / fixup sequence was
 // ~12 of the ~20 VALU instructions per output value of every detector convolution, in kernels that are VALU-issue-bound.
 __device__ __forceinline__ float silu_f(float x) { return x * __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
 // 256 bytes of zeros: where a staged chunk is padding (outside the image, past K, past the last row) the conv / linear gather
 // reads THIS instead of branching around the load or masking the data afterwards
 __device__ __attribute__((aligned(256))) uint32_t g_zero_page[64];
-// erf-form GELU through x * sigmoid(x * (p0 + p1 x^2 + p2 x^4)), coefficients fitted (minimax, |x| <= 8) against
-// 0.5 x (1 + erf(x / sqrt 2)): max abs error 2.5e-5 - below half a bf16 step of the output everywhere the output exceeds
-// 0.01 in magnitude.  x^2 is clamped at 64 (beyond |x| = 8 the result is x or 0 to f32 precision; the quartic would turn over).
-__device__ __forceinline__ float gelu_f(float x) {
-    const float x2 = fminf(x * x, 64.0f);
-    float q = fmaf(-7.03039117e-4f * -1.4426950408889634f, x2, 7.40113286e-2f * -1.4426950408889634f);
-    q = fmaf(q, x2, 1.59501573f * -1.4426950408889634f);
-    const float e = __builtin_amdgcn_exp2f(x * q);                  // exp(-z)
-    return x * __builtin_amdgcn_rcpf(1.0f + e);
-}
-
-// (round 1 evaluated erfc by Abramowitz-Stegun 7.1.26: 14 operations per value against 9 here.  ONE definition for every forward
-// kernel: schedules that route a linear through different kernels - full batch vs half batches - must agree bit for bit.)
-// d/dx gelu(x) = Phi(x) + x * phi(x) of the erf form (erfc by Abramowitz-Stegun 7.1.26, |abs err| <= 1.5e-7); the forward's
-// sigmoid fit differs from the erf form by <= 2.5e-5, i.e. this is its derivative to ~1e-4
-__device__ __forceinline__ float gelu_grad_f(float x) {
-    const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f * 0.70710678118654752f, fabsf(x), 1.0f));
-    float p = fmaf(0.5f * 1.061405429f, t, 0.5f * -1.453152027f);
-    p = fmaf(p, t, 0.5f * 1.421413741f);
-    p = fmaf(p, t, 0.5f * -0.284496736f);
-    p = fmaf(p, t, 0.5f * 0.254829592f);
-    const float e = __builtin_amdgcn_exp2f(x * x * -0.72134752044448170368f);     // exp(-x^2/2)
-    const float w = p * t * e;                                                       // 0.5*erfc(|x|/sqrt2)
-    const float cdf = x >= 0.f ? 1.0f - w : w;
-    return cdf + x * e * 0.39894228040143267794f;
-}
-
 template <int MF, int NF>
 __device__ __forceinline__ void epilogue(const GemmArgs& g, f32x4 (&acc)[NF][MF], int M, int m0, int n0, int wrow_m,
                                          int wrow_n, int fr, int fq) {
@@ -638,6 +561,15 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(GemmArgs g) {
     else *(uint2*)((uint16_t*)g.out + (long long)m * g.ldo + n) = make_uint2(pack_bf16x2(v.x, v.y), pack_bf16x2(v.z, v.w));
 }
 
+// the tail of every launcher that may split K: the reduce pass over g.partial when g.splitk > 1, then the status
+int launch_splitk_reduce(const GemmArgs& g, hipStream_t st) {
+    if (g.splitk > 1) {
+        const long long items = (long long)g.M * (g.N >> 2);
+        hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, g);
+    }
+    return yv_launch_status();
+}
+
 
 // ---------------------------------------------------------------------------------------------
 // Linear fast path (K % 64 == 0): both tiles go global -> LDS by LDS-DMA (global_load_lds, 16 B per
@@ -982,7 +914,6 @@ __global__ __launch_bounds__(256) void cgemm_dma_kernel(GemmArgs g) {
 // Scales are read with ordinary byte loads one K step ahead (issued behind the DMA of that step, consumed after the
 // step's vmcnt(0)), so they never add a wait of their own.
 // ---------------------------------------------------------------------------------------------
-typedef int i32x8 __attribute__((ext_vector_type(8)));
 
 struct MxArgs {
     GemmArgs g;                 // a0 / w point at the fp8 bytes (row strides lda0 / K bytes); epilogue fields as usual
@@ -1618,1109 +1549,6 @@ __global__ __launch_bounds__(256) void quant_mx_2d_kernel(const uint16_t* __rest
 }
 
 // ---------------------------------------------------------------------------------------------
-// 256 x 256 x 64 "8-phase" schedule (cdna_hip_programming.md section 5 template, re-derived for this operand
-// convention; the non-persistent round-1 kernel of this shape was removed in round 3, gemm_p8_kernel below is its
-// persistent form).  8 waves = 2 groups (wm = 0/1, 128 activation rows each) x 4 (64 weight rows each); one
-// workgroup per CU, 128 KB of LDS = 2 stages x {A tile, W tile}.  A K tile is consumed in 4 phases, one
-// 64 x 32 quadrant of the wave tile each (16 MFMAs): (m0,n0) (m0,n1) (m1,n1) (m1,n0); every phase is
-//     [ds_read this phase's operand half | issue ONE half-tile of LDS-DMA] barrier [16 MFMA] barrier
-// and the two wave groups run ONE BARRIER APART, so that on every SIMD one wave is in its MFMA segment while
-// its partner reads LDS / issues DMA.  The DMA stream runs 3 half-tiles ahead and is retired once per K
-// tile by a COUNTED s_waitcnt vmcnt(6) (never 0 in the loop), raw s_barrier (a __syncthreads would drain).
-//
-// Half-tiles: A-half h = rows {wm*128 + h*64 + [0,64)} (both groups), W-half h = rows {wn*64 + h*32 + [0,32)}:
-// each half holds what every wave reads in ONE phase, so it dies as a unit:
-//     phase 1 reads A0,W0   phase 2 reads W1   phase 3 reads A1   phase 4 reads nothing  (W0,W1 stay in VGPRs)
-//     restage (one phase after the last read; reads are retired by lgkmcnt(0) BEFORE the phase's first barrier):
-//     phase 1: A1(t+1)   phase 2: A0(t+2)   phase 3: W0(t+2)   phase 4: W1(t+2), then vmcnt(6) = tile t+1 landed
-// RAW: a half-tile is read at the earliest one phase after the wait that retires it (two barriers later, which
-// covers the one-barrier stagger between the groups).
-// ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ void bar() { asm volatile("s_barrier" ::: "memory"); }
-
-// ---------------------------------------------------------------------------------------------
-// Persistent form of the 8-phase schedule (round 2).  One workgroup per CU walks its tiles; what changes against
-// a one-tile-per-workgroup kernel:
-//   * the LDS-DMA stream never drains between tiles: during the last two K tiles of a tile the restage slots load the FIRST two
-//     K tiles of the workgroup's next tile, so the pipeline fill (one HBM/L2 round trip per tile) and the first waits are hidden
-//     behind the epilogue, and the epilogue's stores drain in the shadow of the next main loop instead of in a burst;
-//   * the epilogue does not alias the stage buffers (they are being refilled): every wave transposes 16 output rows at a time
-//     through a private 2 KB slab; the bias vector sits in LDS for the whole launch (a global bias load inside the epilogue
-//     would make hipcc drain the in-flight DMA with vmcnt(0));
-//   * operands are addressed through buffer descriptors (32-bit offsets: half the address registers of flat pointers, which
-//     pays for the second - next tile - offset set; rows past M read as zeros through the range check instead of a clamp);
-//   * GELU by a 9-operation sigmoid form (see gelu_fast_f).
-// LDS map: [stage 0 | stage 1] 2 x 64 KB, 8 slabs x 2 KB, bias 16 KB = 160 KB exactly.
-// Restrictions (checked by the host, everything else takes the 128 x 128 kernel): N % 256 == 0, N <= 4096, K % 64 == 0,
-// bf16 output, flags within {BIAS, GELU}, operand images below 2 GB.
-// ---------------------------------------------------------------------------------------------
-typedef __attribute__((address_space(3))) void* lds_void_t;
-
-// MF0 / MF1: 16-row activation fragments per wave group in the first / second half of its rows; tile = 32 (MF0 + MF1) rows x
-// 256 columns.  (4,4) = 256 rows is the template of the guide; the smaller instances exist for tile-count quantisation: a
-// persistent grid of 256 workgroups runs ceil(tiles / 256) rounds, and e.g. the 297 tiles of a 25,216 x 768 output cost two
-// rounds at 256 rows but 474 tiles = 1.85 rounds of 160-row tiles (-37 %).  The host picks the instance that minimises
-// rounds x rows.  A-operand DMA slots that a smaller tile does not need are issued with an out-of-range offset (the buffer
-// range check turns them into no-ops) so that every wave keeps issuing the same number of DMA instructions per phase, which
-// is what the counted vmcnt relies on.
-template <int MF0, int MF1, bool F32OUT, int DIAG = 0 /* tools/gemm_lab.hip only: per-segment cycle sums into g.partial */>
-__global__ __launch_bounds__(512) void gemm_p8_kernel(GemmArgs g) {
-    constexpr int MF = MF0 + MF1, NF = 4;
-    constexpr int RG = MF * 16, BM = 2 * RG;                   // rows per wave group / per tile
-    constexpr int A_BYTES = 256 * 128, W_BYTES = 256 * 128, STAGE = A_BYTES + W_BYTES;
-    constexpr int SLAB0 = 2 * STAGE, SLAB = 2048, BIAS0 = SLAB0 + 8 * SLAB;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-
-    int M = g.M;
-    if (g.m_dev) { long long md = (long long)g.m_dev[0] * g.m_mul; M = md < M ? (int)md : M; }
-    const int tiles_m = (M + BM - 1) / BM, tiles_n = g.N >> 8;
-    const int ntiles = tiles_m * tiles_n;
-    const int G = gridDim.x;
-    // tile schedule (blockIdx & 7 = XCD under round-robin placement - speed only, never correctness): see GemmArgs::sched
-    int Lx, seq0, seq1, lid;
-    if (g.sched == 1) {
-        const int nx = G < 8 ? G : 8;                           // (grids smaller than 8 blocks: one sequence share per block)
-        const int xcd = (int)blockIdx.x % nx;
-        lid = (int)blockIdx.x / nx;
-        Lx = (G - xcd + nx - 1) / nx;                           // blocks that share this part of the sequence
-        int cum = 0;                                            // blocks of the parts before this one
-        for (int y = 0; y < xcd; ++y) cum += (G - y + nx - 1) / nx;
-        // parts proportional to their block counts: with tiles == blocks every block gets exactly one tile (equal parts would
-        // hand a 29-block XCD 30 tiles and double the launch time)
-        seq0 = (int)((long long)ntiles * cum / G); seq1 = (int)((long long)ntiles * (cum + Lx) / G);
-    } else {
-        // round r covers sequence positions [r G, r G + G); inside a round XCD x walks a contiguous chunk of it
-        const int q = G >> 3, r = G & 7, x = blockIdx.x & 7;
-        lid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + ((int)blockIdx.x >> 3);
-        Lx = G; seq0 = 0; seq1 = ntiles;
-    }
-    if (seq0 + lid >= seq1) return;
-    {   // bias -> LDS once (plain loads, before any DMA is in flight)
-        float* bl = (float*)(smem + BIAS0);
-        for (int i = tid; i < g.N; i += 512) bl[i] = (g.flags & YV_EPI_BIAS) ? g.bias[i] : 0.0f;
-    }
-    const auto rsA = __builtin_amdgcn_make_buffer_rsrc((void*)g.a0, 0, (int)(((long long)(g.M - 1) * g.lda0 + g.K) * 2), 0x00020000);
-    const auto rsW = __builtin_amdgcn_make_buffer_rsrc((void*)g.w, 0, (int)((long long)g.N * g.K * 2), 0x00020000);
-
-    const int wm = wave >> 2, wn = wave & 3;
-    const int wrow_m = wm * RG, wrow_n = wn * 64;
-    const int fr = lane & 15, fq = lane >> 4;
-    const int lrow = lane >> 3, lch = lane & 7;
-    auto coords = [&](int seq, int& m0, int& n0) __attribute__((always_inline)) {   // grouped order: GM consecutive M tiles share a W tile
-        const int GM = g.group_m, per = GM * tiles_n;
-        const int grp = seq / per, first = grp * GM;
-        const int gsz = (tiles_m - first) < GM ? (tiles_m - first) : GM;
-        const int in = seq - grp * per;
-        m0 = (first + in % gsz) * BM;
-        n0 = (in / gsz) << 8;
-    };
-    // A half h of a stage: rows {group * RG + off_h + [0, len_h)} of both groups = 2 * len_h / 8 pieces of 8 rows; piece slots
-    // s = wave * 2 + j (16 per half); slots past the piece count are dummies
-    auto a_piece_row = [&](int h, int s) __attribute__((always_inline)) -> int {      // first tile row of piece s, or -1
-        const int len8 = (h == 0 ? MF0 : MF1) * 2;                                      // pieces per group
-        if (s >= 2 * len8) return -1;
-        const int grp = s / len8, r8 = s - grp * len8;
-        return grp * RG + (h == 0 ? 0 : MF0 * 16) + r8 * 8;
-    };
-    auto set_offsets = [&](uint32_t (&o)[4][2], int m0, int n0) __attribute__((always_inline)) {
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int s_ = wave * 2 + j;
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const int r0 = a_piece_row(h, s_);
-                const int ra = r0 + lrow, m = m0 + ra;
-                o[h][j] = (r0 >= 0 && m < g.M) ? (uint32_t)(((long long)m * g.lda0 + ((lch ^ (ra & 7)) << 3)) * 2) : 0x80000000u;
-                const int rh = s_ * 8 + lrow;
-                const int rw = (rh >> 5) * 64 + h * 32 + (rh & 31);
-                o[2 + h][j] = (uint32_t)(((long long)(n0 + rw) * g.K + ((lch ^ (rw & 7)) << 3)) * 2);
-            }
-        }
-    };
-    auto lds_dst = [&](int kind, int j) __attribute__((always_inline)) -> int {   // wave-uniform destination of a piece inside a stage
-        const int s_ = wave * 2 + j;
-        if (kind < 2) {
-            const int r0 = a_piece_row(kind, s_);
-            return (r0 >= 0 ? r0 : BM) * 128;                   // dummy pieces land in the unused rows BM.. of the A region
-        }
-        const int rb = s_ * 8;
-        return A_BYTES + ((rb >> 5) * 64 + (kind - 2) * 32 + (rb & 31)) * 128;
-    };
-
-    const int nk = g.K / BK;
-    uint32_t ocur[4][2], onxt[4][2];
-    int seq = seq0 + lid, m0, n0, m0n = 0, n0n = 0;
-    coords(seq, m0, n0);
-    set_offsets(ocur, m0, n0);
-    bool has_next = seq + Lx < seq1;
-    if (has_next) { coords(seq + Lx, m0n, n0n); set_offsets(onxt, m0n, n0n); }
-    int gk = 0;                                                // K tiles consumed so far by this workgroup (stage = gk & 1)
-
-    // half-tile `kind` of K tile t of the CURRENT tile into stage `st` / of K tile tt of the NEXT tile (separate functions:
-    // a run-time choice between the two offset sets makes hipcc index them through scratch memory, and scratch loads count
-    // in vmcnt like the DMA does)
-    auto issue_cur = [&](int kind, int t, int st) __attribute__((always_inline)) {
-        unsigned char* base = smem + (st & 1) * STAGE;
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(kind < 2 ? rsA : rsW, (lds_void_t)(base + lds_dst(kind, j)), 16,
-                                                     (int)ocur[kind][j], t * 128, 0, 0);
-    };
-    auto issue_nxt = [&](int kind, int tt, int st) __attribute__((always_inline)) {
-        if (!has_next) return;
-        unsigned char* base = smem + (st & 1) * STAGE;
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(kind < 2 ? rsA : rsW, (lds_void_t)(base + lds_dst(kind, j)), 16,
-                                                     (int)onxt[kind][j], tt * 128, 0, 0);
-    };
-
-    f32x4 acc[NF][MF];
-    bf16x8 fa[4][2], fw[4][2];
-    auto read_a = [&](const unsigned char* A, int h) __attribute__((always_inline)) {
-#pragma unroll
-        for (int j = 0; j < (h == 0 ? MF0 : MF1); ++j) {
-            const int rr = wrow_m + (h == 0 ? 0 : MF0 * 16) + j * 16 + fr;
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) fa[j][ks] = *(const bf16x8*)(A + rr * 128 + (((ks * 4 + fq) ^ (rr & 7)) << 4));
-        }
-    };
-    auto read_w = [&](const unsigned char* W, int h) __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int rr = wrow_n + h * 32 + i * 16 + fr;
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) fw[h * 2 + i][ks] = *(const bf16x8*)(W + rr * 128 + (((ks * 4 + fq) ^ (rr & 7)) << 4));
-        }
-    };
-    auto mma = [&](int mh, int nh) __attribute__((always_inline)) {
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < (mh == 0 ? MF0 : MF1); ++j)
-                    acc[nh * 2 + i][(mh == 0 ? 0 : MF0) + j] =
-                        __builtin_amdgcn_mfma_f32_16x16x32_bf16(fw[nh * 2 + i][ks], fa[j][ks], acc[nh * 2 + i][(mh == 0 ? 0 : MF0) + j], 0, 0, 0);
-        __builtin_amdgcn_s_setprio(0);
-    };
-    auto sync_reads = [&]() __attribute__((always_inline)) {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-        bar();
-        __builtin_amdgcn_sched_barrier(0);
-    };
-    auto sync_mma = [&]() __attribute__((always_inline)) {
-        __builtin_amdgcn_sched_barrier(0);
-        bar();
-        __builtin_amdgcn_sched_barrier(0);
-    };
-
-    // DIAG build: cycle sums per segment of a phase (s_memtime stamps; a stamp is consumed one natural lgkmcnt(0) later, so
-    // that reading it never adds a wait).  [0] read + DMA issue, [1] lgkmcnt wait of phases 1-3, [2] lgkmcnt + vmcnt wait of
-    // phase 4, [3] first barrier, [4] MFMA segment, [5] second barrier, [6] epilogue, [7] phases
-    uint32_t dg[8] = {0, 0, 0, 0, 0, 0, 0, 0}, ds0 = 0, ds1 = 0, dp1 = 0, dp2 = 0, dp3 = 0, dp4 = 0, dp_is4 = 0;
-    auto stamp = [&]() __attribute__((always_inline)) -> uint32_t { return (uint32_t)__builtin_amdgcn_s_memtime(); };
-    auto dg_flush = [&]() __attribute__((always_inline)) {      // right after a natural lgkmcnt(0): every older stamp has landed
-        if constexpr (DIAG) {
-            if (dg[7]) {
-                if (dp_is4) dg[2] += dp2 - dp1; else dg[1] += dp2 - dp1;
-                dg[3] += dp3 - dp2; dg[4] += dp4 - dp3; dg[5] += ds0 - dp4;
-            }
-            dg[0] += ds1 - ds0; dg[7] += 1; dp1 = ds1;
-        }
-    };
-    __syncthreads();                                           // bias image complete (no DMA in flight yet: a plain barrier)
-    // ---- prologue of the first tile: K tile 0 complete, first three half-tiles of K tile 1 in flight (nk >= 2) ----------
-    issue_cur(0, 0, 0); issue_cur(2, 0, 0); issue_cur(3, 0, 0); issue_cur(1, 0, 0);
-    issue_cur(0, 1, 1); issue_cur(2, 1, 1); issue_cur(3, 1, 1);
-    asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    bar();
-    if (wm == 1) bar();                                        // group 1 runs one barrier behind group 0
-
-    // one K tile = 4 phases.  TAIL 0: K tiles t+1, t+2 belong to this tile; 1: t = nk-2 (t+2 is K tile 0 of the next tile);
-    // 2: t = nk-1 (t+1, t+2 are K tiles 0, 1 of the next tile).  Stage of a K tile = parity of the running counter gk.
-    auto ktile = [&](int t, auto tail_c) __attribute__((always_inline)) {
-        constexpr int TAIL = decltype(tail_c)::value;
-        const unsigned char* A = smem + (gk & 1) * STAGE;
-        const unsigned char* W = A + A_BYTES;
-        auto seg_reads = [&](int is4) __attribute__((always_inline)) {     // end of a read segment (DIAG: stamped)
-            if constexpr (DIAG) {
-                if (!is4) ds1 = stamp();                          // phase 4 stamps in front of its vmcnt wait
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                __builtin_amdgcn_sched_barrier(0);
-                dg_flush(); dp_is4 = is4;
-                dp2 = stamp();
-                __builtin_amdgcn_sched_barrier(0);
-                bar();
-                __builtin_amdgcn_sched_barrier(0);
-                dp3 = stamp();
-            } else sync_reads();
-        };
-        auto seg_mma = [&]() __attribute__((always_inline)) {
-            if constexpr (DIAG) {
-                __builtin_amdgcn_sched_barrier(0);
-                dp4 = stamp();
-                bar();
-                __builtin_amdgcn_sched_barrier(0);
-                ds0 = stamp();
-            } else sync_mma();
-        };
-        read_a(A, 0); read_w(W, 0);
-        if constexpr (TAIL == 2) issue_nxt(1, 0, gk + 1); else issue_cur(1, t + 1, gk + 1);
-        seg_reads(0);
-        mma(0, 0);
-        seg_mma();
-        read_w(W, 1);
-        if constexpr (TAIL == 0) issue_cur(0, t + 2, gk); else issue_nxt(0, TAIL - 1, gk);
-        seg_reads(0);
-        mma(0, 1);
-        seg_mma();
-        read_a(A, 1);
-        if constexpr (TAIL == 0) issue_cur(2, t + 2, gk); else issue_nxt(2, TAIL - 1, gk);
-        seg_reads(0);
-        mma(1, 1);
-        seg_mma();
-        if constexpr (TAIL == 0) issue_cur(3, t + 2, gk); else issue_nxt(3, TAIL - 1, gk);
-        if constexpr (DIAG) ds1 = stamp();
-        if (TAIL == 0 || has_next) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");     // three half-tiles stay in flight
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        seg_reads(1);
-        mma(1, 0);
-        seg_mma();
-        ++gk;
-    };
-
-    uint32_t de0_ = 0;
-    const uint32_t dk0 = DIAG ? stamp() : 0;
-    if constexpr (DIAG) ds0 = dk0;
-    for (;;) {
-#pragma unroll
-        for (int i = 0; i < NF; ++i)
-#pragma unroll
-            for (int j = 0; j < MF; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        for (int t = 0; t < nk - 2; ++t) ktile(t, std::integral_constant<int, 0>{});
-        ktile(nk - 2, std::integral_constant<int, 1>{});
-        ktile(nk - 1, std::integral_constant<int, 2>{});
-        // ---- epilogue: 16 rows at a time through this wave's slab; no workgroup barrier (the groups stay one barrier apart) ----
-        {
-            if constexpr (DIAG) de0_ = stamp();
-            unsigned char* slab = smem + SLAB0 + wave * SLAB;
-            const float* bl = (const float*)(smem + BIAS0) + n0 + wrow_n + fq * 4;
-            if constexpr (!F32OUT) {
-                const bool gelu = g.flags & YV_EPI_GELU;
-                uint16_t* outp = (uint16_t*)g.out;
-#pragma unroll
-                for (int j = 0; j < MF; ++j) {
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        const float4 bvi = *(const float4*)(bl + i * 16);
-                        float v0 = acc[i][j][0] + bvi.x, v1 = acc[i][j][1] + bvi.y;
-                        float v2 = acc[i][j][2] + bvi.z, v3 = acc[i][j][3] + bvi.w;
-                        if (gelu) { v0 = gelu_f(v0); v1 = gelu_f(v1); v2 = gelu_f(v2); v3 = gelu_f(v3); }
-                        const int c16 = i * 2 + (fq >> 1);
-                        *(uint2*)(slab + fr * 128 + ((c16 ^ (fr & 7)) << 4) + (fq & 1) * 8) =
-                            make_uint2(pack_bf16x2(v0, v1), pack_bf16x2(v2, v3));
-                    }
-                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the slab is wave-private: LDS executes a wave's ops in order
-#pragma unroll
-                    for (int it = 0; it < 2; ++it) {
-                        const int row = it * 8 + (lane >> 3), ch = lane & 7;
-                        const int m = m0 + wrow_m + j * 16 + row;
-                        const uint4 pk = *(const uint4*)(slab + row * 128 + ((ch ^ (row & 7)) << 4));
-                        if (m < M) *(uint4*)(outp + (long long)m * g.ldo + n0 + wrow_n + ch * 8) = pk;
-                    }
-                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // reads retired before the next chunk overwrites the slab
-                }
-            } else {
-                // f32 output / residual stream (x += A . W^T + b): 16 rows x 32 columns per pass (128-byte row segments).
-                // The residual values are fetched for a half / quarter of the wave tile at once, in the row-segment layout of the
-                // stores (8-12 independent 16-byte loads per lane in flight): fetched chunk by chunk, each of the 16 passes of a tile
-                // waited for its own HBM round trip (proj: 67 us for a 39 us memory floor)
-                // Loads and stores go through a buffer descriptor over the output with an out-of-range offset for rows past M
-                // (reads return 0, writes are dropped) instead of `if (m < M)`: inside a branch hipcc cannot count the memory
-                // operations in flight and waits vmcnt(0) before every use of a fetched residual value - and vmcnt counts STORES
-                // on this chip, so each 16-row pass waited for the previous pass's stores to be acknowledged (proj 57 us / fc2
-                // 131 us against 40 / 118 us with a plain bf16 epilogue).
-                const bool rmw = g.flags & YV_EPI_RES_F32;
-                const auto rsO = __builtin_amdgcn_make_buffer_rsrc(g.out, 0, (int)(((long long)(M - 1) * g.ldo + g.N) * 4), 0x00020000);
-                constexpr int NPART = MF <= 5 ? 2 : 4;             // residual registers in flight: 16 * JA (the accumulators hold 16 * MF)
-                constexpr int JA = (MF + NPART - 1) / NPART;
-                auto out_off = [&](int j, int ip, int it) __attribute__((always_inline)) {
-                    const int row = it * 8 + (lane >> 3), ch = lane & 7;
-                    const int m = m0 + wrow_m + j * 16 + row;
-                    return m < M ? (uint32_t)((m * g.ldo + n0 + wrow_n + ip * 32 + ch * 4) * 4) : 0x80000000u;
-                };
-#pragma unroll
-                for (int half = 0; half < NPART; ++half) {
-                    const int j0 = half * JA, jn = (MF - j0) < JA ? (MF - j0 > 0 ? MF - j0 : 0) : JA;
-                    u32x4 xr[JA][2][2];
-                    if (rmw) {
-#pragma unroll
-                        for (int jj = 0; jj < JA; ++jj)
-#pragma unroll
-                            for (int ip = 0; ip < 2; ++ip)
-#pragma unroll
-                                for (int it = 0; it < 2; ++it)
-                                    xr[jj][ip][it] = __builtin_amdgcn_raw_buffer_load_b128(rsO, jj < jn ? out_off(j0 + jj, ip, it) : 0x80000000u, 0, 0);
-                    }
-#pragma unroll
-                    for (int jj = 0; jj < JA; ++jj) {
-                        if (jj >= jn) continue;
-                        const int j = j0 + jj;
-#pragma unroll
-                        for (int ip = 0; ip < 2; ++ip) {
-#pragma unroll
-                            for (int ii = 0; ii < 2; ++ii) {
-                                const int i = ip * 2 + ii;
-                                const float4 bvi = *(const float4*)(bl + i * 16);
-                                *(float4*)(slab + fr * 128 + (((ii * 4 + fq) ^ (fr & 7)) << 4)) =
-                                    make_float4(acc[i][j][0] + bvi.x, acc[i][j][1] + bvi.y, acc[i][j][2] + bvi.z, acc[i][j][3] + bvi.w);
-                            }
-                            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-                            for (int it = 0; it < 2; ++it) {
-                                const int row = it * 8 + (lane >> 3), ch = lane & 7;
-                                float4 v = *(const float4*)(slab + row * 128 + ((ch ^ (row & 7)) << 4));
-                                if (rmw) {
-                                    const u32x4 x = xr[jj][ip][it];
-                                    v.x += __uint_as_float(x[0]); v.y += __uint_as_float(x[1]);
-                                    v.z += __uint_as_float(x[2]); v.w += __uint_as_float(x[3]);
-                                }
-                                const u32x4 pk = {__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z), __float_as_uint(v.w)};
-                                __builtin_amdgcn_raw_buffer_store_b128(pk, rsO, out_off(j, ip, it), 0, 0);
-                            }
-                            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                        }
-                    }
-                }
-            }
-        }
-        if constexpr (DIAG) {
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            const uint32_t de1 = stamp();
-            dg[6] += de1 - de0_; ds0 = de1;
-        }
-        if (!has_next) break;
-        seq += Lx;
-        m0 = m0n; n0 = n0n;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { ocur[k][0] = onxt[k][0]; ocur[k][1] = onxt[k][1]; }
-        has_next = seq + Lx < seq1;
-        if (has_next) { coords(seq + Lx, m0n, n0n); set_offsets(onxt, m0n, n0n); }
-    }
-    if (wm == 0) bar();                                        // group 0 waits for group 1's last barrier
-    if constexpr (DIAG) {
-        const uint32_t dk1 = stamp();
-        if (lane == 0) {
-            uint32_t* o = (uint32_t*)g.partial + ((long long)blockIdx.x * 8 + wave) * 16;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) o[i] = dg[i];
-            o[8] = dk1 - dk0;
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-template <int MF0, int MF1, bool F32OUT>
-int launch_p8_inst2(GemmArgs& g, hipStream_t st, int n_cu) {
-    constexpr int BM = 32 * (MF0 + MF1);
-    g.tiles_m = (g.M + BM - 1) / BM;
-    g.tiles_n = g.N / 256;
-    const size_t lds = 2 * 65536 + 8 * 2048 + 16384;
-    auto kern = gemm_p8_kernel<MF0, MF1, F32OUT>;
-    if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return YV_ERR_LAUNCH;
-    const int tiles = g.tiles_m * g.tiles_n;
-    const int grid = tiles < n_cu ? tiles : n_cu;
-    if (t_time_start || t_time_stop) {
-        hipExtLaunchKernelGGL(kern, dim3(grid), dim3(512), (uint32_t)lds, st, t_time_start, t_time_stop, 0, g);
-        t_time_start = t_time_stop = nullptr;
-    } else {
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, st, g);
-    }
-    return yv_launch_status();
-}
-
-template <int MF0, int MF1>
-int launch_p8_inst(GemmArgs& g, hipStream_t st, int n_cu) {
-    // the f32 epilogue keeps a residual prefetch next to the accumulators: only the tiles up to 192 rows have the registers for it
-    if constexpr (MF0 + MF1 <= 6) {
-        if (g.flags & (YV_EPI_RES_F32 | YV_EPI_OUT_F32)) return launch_p8_inst2<MF0, MF1, true>(g, st, n_cu);
-    }
-    return launch_p8_inst2<MF0, MF1, false>(g, st, n_cu);
-}
-
-int g_opt_p8_sched = 1;            // tile schedule of the persistent kernel (GemmArgs::sched): "linear_p8_sched"
-thread_local int g_opt_p8_cus = 0; // persistent grid size OF LAUNCHES MADE BY THIS THREAD; 0 = every CU ("linear_p8_cus": leave CUs to concurrent streams)
-int g_opt_p8_rows = 0;             // 0 = pick the tile height per launch; 128 / 160 / 192 / 224 / 256 force it ("linear_p8_rows")
-
-int launch_p8(GemmArgs& g, hipStream_t st) {
-    static int n_cu_dev = 0;                                    // CU count of the device (same value from every thread)
-    if (!n_cu_dev) {
-        int dev = 0; hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return YV_ERR_LAUNCH;
-        n_cu_dev = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    }
-    const int n_cu = (g_opt_p8_cus > 0 && g_opt_p8_cus < n_cu_dev) ? g_opt_p8_cus : n_cu_dev;
-    g.sched = g_opt_p8_sched;
-    // tile height: minimise rounds x (rows + a fixed per-tile cost worth ~24 rows: epilogue, pipeline turn-around)
-    int best = 256;
-    if (g_opt_p8_rows) {
-        best = g_opt_p8_rows < 128 ? 128 : g_opt_p8_rows;          // (96: a tile height of the free-running kernel only)
-        if ((g.flags & (YV_EPI_RES_F32 | YV_EPI_OUT_F32)) && best > 192) best = 192;
-    } else {
-        long long best_cost = -1;
-        const int cand[5] = {256, 224, 192, 160, 128};
-        const bool f32out = g.flags & (YV_EPI_RES_F32 | YV_EPI_OUT_F32);
-        best = f32out ? 192 : 256;
-        for (int c = f32out ? 2 : 0; c < 5; ++c) {
-            const long long tiles = (long long)((g.M + cand[c] - 1) / cand[c]) * (g.N / 256);
-            const long long rounds = (tiles + n_cu - 1) / n_cu;
-            const long long cost = rounds * (cand[c] + 24);
-            if (best_cost < 0 || cost < best_cost) { best_cost = cost; best = cand[c]; }
-        }
-    }
-    switch (best) {
-        case 224: return launch_p8_inst<4, 3>(g, st, n_cu);
-        case 192: return launch_p8_inst<3, 3>(g, st, n_cu);
-        case 160: return launch_p8_inst<3, 2>(g, st, n_cu);
-        case 128: return launch_p8_inst<2, 2>(g, st, n_cu);
-        default: return launch_p8_inst<4, 4>(g, st, n_cu);
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// gemm_p9_kernel (round 3): the persistent tile walk, LDS map and LDS-DMA addressing of gemm_p8_kernel with a FREE-RUNNING main
-// loop.  What the per-segment stamps of the DIAG build showed for gemm_p8_kernel (tools/gemm_lab.hip): a phase costs
-// ~890 cycles where its two MFMA segments need 512; the read segment is not LDS latency but the ISSUE of the two LDS-DMA
-// instructions (~85 cycles each while the four waves of a group issue theirs at once; the waits on landing DMA are ~25 cycles
-// per K tile), and each of the 8 barriers of a K tile costs the last arriver ~65 cycles.  So here:
-//   * ONE barrier per K tile instead of eight.  A wave's program for a K tile is P = ceil(MF / 2) phases of 16 MFMAs (two row
-//     fragments x four column fragments x two 32-deep steps); the fragment reads of phase p+1 are issued at the top of phase p into
-//     the other half of a two-deep register ring (16 registers each), the weight fragments of K tile t+1 replace those of K tile t
-//     in place inside the last phase (after their last use), so LDS latency is covered by the wave's OWN MFMAs and the two waves of
-//     a SIMD are not forced to alternate: whichever has operands issues, and the waves of a workgroup drift apart instead of
-//     bursting on the LDS-DMA path together;
-//   * the sync point S (end of phase P-2: vmcnt(0) + lgkmcnt(0) + barrier) retires K tile t+1 and frees the whole stage of K tile
-//     t at once (its last fragment reads were issued one phase earlier); the 8 DMA instructions per wave and K tile are spread over
-//     the phases that follow S (activation pieces first: they can miss L2; weight pieces last: they never do; none in the phase
-//     that ends in the next S);
-//   * LDS-free epilogue.  bf16 outputs: the weight rows of a wave's 64 columns are PERMUTED on the DMA source side so that MFMA
-//     fragment i, row r holds column (r >> 2) * 16 + i * 4 + (r & 3): a lane's 16 accumulator values of one output row are 16
-//     consecutive columns = two 16-byte stores straight from registers (64-byte row segments per wave-instruction).  f32 outputs
-//     keep the plain order (a lane's four values per fragment are 16 bytes, a fragment's 16 columns one 64-byte segment).  The
-//     slabs, their lgkmcnt round trips (5.5 k cycles per 256 x 256 tile) and 16 KB of LDS are gone.
-// Instances: MF (16-row fragments per wave group; tile = 32 MF rows x 256 columns) in 5..8; K / 64 >= 2, even when P is odd.
-// ---------------------------------------------------------------------------------------------
-template <int V> using ic = std::integral_constant<int, V>;
-#ifndef YV_P9_STORE_AUX
-#define YV_P9_STORE_AUX 0              // cache policy bits of the bf16 output stores (2 = nt: streaming; experiment builds only)
-#endif
-
-template <int MF, bool F32OUT, int DIAG = 0 /* tools/gemm_lab.hip only: cycle sums into g.partial */,
-          int EXT = 0 /* trainer epilogues of the bf16 output: 1 = YV_EPI_SAVE_PRE (fc1 forward), 2 = YV_EPI_GELU_BWD (fc2 data gradient) */,
-          bool MX = false /* OCP MXFP8 operands (e4m3 bytes + one E8M0 scale per 32 K): a 128-byte LDS row is 128 K elements = ONE
-                             block-scaled MFMA (v_mfma_scale_f32_16x16x128_f8f6f4) per fragment pair and K tile; same DMA, LDS images,
-                             fragment reads and schedule, twice the flops per K tile; the two 1 KB scale rows of a K tile travel with
-                             its activation / weight pieces (issued by waves 0 / 1) */>
-__global__ __launch_bounds__(512) void gemm_p9_kernel(GemmArgs g) {
-    constexpr int NF = 4, P = (MF + 1) / 2;
-    static_assert(EXT == 0 || (!F32OUT && MF <= 7), "aux epilogues: bf16 output, tiles of up to 224 rows (registers)");
-    constexpr int MF0 = (MF + 1) / 2, MF1 = MF - MF0;          // DMA halves of the activation rows of a group (piece bookkeeping of p8)
-    constexpr int RG = MF * 16, BM = 2 * RG;
-    constexpr int A_BYTES = 256 * 128, SC0 = 2 * A_BYTES, STAGE = 2 * A_BYTES + (MX ? 2048 : 0), BIAS0 = 2 * STAGE;
-    constexpr int ESZ = MX ? 1 : 2;                               // bytes per operand element; K elements per 128-byte row: 128 / ESZ
-    constexpr int KT = 128 / ESZ;
-    constexpr bool PERM = !F32OUT;
-    static_assert(MF >= 3 && MF <= 8, "tile heights 96..256");
-    static_assert(MF >= 5 || (!MX && EXT == 0), "96 / 128-row tiles: plain bf16 operands only");
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-
-    int M = g.M;
-    if (g.m_dev) { long long md = (long long)g.m_dev[0] * g.m_mul; M = md < M ? (int)md : M; }
-    const int tiles_m = (M + BM - 1) / BM, tiles_n = g.N >> 8;
-    const int ntiles = tiles_m * tiles_n;
-    const int G = gridDim.x;
-    int Lx, seq0, seq1, lid;
-    if (g.sched == 1) {
-        const int nx = G < 8 ? G : 8;
-        const int xcd = (int)blockIdx.x % nx;
-        lid = (int)blockIdx.x / nx;
-        Lx = (G - xcd + nx - 1) / nx;
-        int cum = 0;
-        for (int y = 0; y < xcd; ++y) cum += (G - y + nx - 1) / nx;
-        seq0 = (int)((long long)ntiles * cum / G); seq1 = (int)((long long)ntiles * (cum + Lx) / G);
-    } else {
-        const int q = G >> 3, r = G & 7, x = blockIdx.x & 7;
-        lid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + ((int)blockIdx.x >> 3);
-        Lx = G; seq0 = 0; seq1 = ntiles;
-    }
-    if (seq0 + lid >= seq1) return;
-    {
-        float* bl = (float*)(smem + BIAS0);
-        for (int i = tid; i < g.N; i += 512) bl[i] = (g.flags & YV_EPI_BIAS) ? g.bias[i] : 0.0f;
-    }
-    const auto rsA = __builtin_amdgcn_make_buffer_rsrc((void*)g.a0, 0, (int)(((long long)(g.M - 1) * g.lda0 + g.K) * ESZ), 0x00020000);
-    const auto rsW = __builtin_amdgcn_make_buffer_rsrc((void*)g.w, 0, (int)((long long)g.N * g.K * ESZ), 0x00020000);
-    const int nk_all = g.K / KT;
-    const auto rsSA = __builtin_amdgcn_make_buffer_rsrc((void*)(MX ? (const void*)g.mx_sa : (const void*)g.a0), 0,
-                                                        MX ? (int)((long long)nk_all * g.mx_rows_a * 4) : 16, 0x00020000);
-    const auto rsSW = __builtin_amdgcn_make_buffer_rsrc((void*)(MX ? (const void*)g.mx_sw : (const void*)g.w), 0,
-                                                        MX ? (int)((long long)nk_all * g.mx_rows_w * 4) : 16, 0x00020000);
-    const auto rsO = __builtin_amdgcn_make_buffer_rsrc(g.out, 0, (int)(((long long)(M - 1) * g.ldo + g.N) * (F32OUT ? 4 : 2)), 0x00020000);
-    // f32 residual read from another tensor of the output's layout (trainer: x_mid = x_in + ...), else read-modify-write of `out`
-    const auto rsR = __builtin_amdgcn_make_buffer_rsrc(F32OUT && g.resf ? (void*)g.resf : g.out, 0,
-                                                       (int)(((long long)(M - 1) * g.ldo + g.N) * (F32OUT ? 4 : 2)), 0x00020000);
-    // bf16 side tensor of the trainer epilogues (EXT): pre-activation, written (SAVE_PRE) or read (GELU_BWD)
-    const auto rsX = __builtin_amdgcn_make_buffer_rsrc(EXT ? (void*)g.aux : g.out, 0, (int)(((long long)(M - 1) * (EXT ? g.ldaux : g.ldo) + g.N) * 2), 0x00020000);
-
-    const int wm = wave >> 2, wn = wave & 3;
-    const int wrow_m = wm * RG, wrow_n = wn * 64;
-    const int fr = lane & 15, fq = lane >> 4;
-    const int lrow = lane >> 3, lch = lane & 7;
-    auto coords = [&](int seq, int& m0, int& n0) __attribute__((always_inline)) {
-        const int GM = g.group_m, per = GM * tiles_n;
-        const int grp = seq / per, first = grp * GM;
-        const int gsz = (tiles_m - first) < GM ? (tiles_m - first) : GM;
-        const int in = seq - grp * per;
-        m0 = (first + in % gsz) * BM;
-        n0 = (in / gsz) << 8;
-    };
-    auto a_piece_row = [&](int h, int s) __attribute__((always_inline)) -> int {
-        const int len8 = (h == 0 ? MF0 : MF1) * 2;
-        if (s >= 2 * len8) return -1;
-        const int grp = s / len8, r8 = s - grp * len8;
-        return grp * RG + (h == 0 ? 0 : MF0 * 16) + r8 * 8;
-    };
-    // DMA source offsets.  Activation pieces: per-lane byte offset of (tile row, swizzled chunk) - ONE set, pointed at the next
-    // tile from K tile nk-2 on (the current tile's last activation pieces are issued in K tile nk-3); rows past M get an
-    // out-of-range offset (the range check returns zeros).  Weight pieces: a lane part that never changes + the tile's n0 * K
-    // in the instruction's scalar offset.
-    auto set_a_offsets = [&](uint32_t (&o)[2][2], int m0, bool valid) __attribute__((always_inline)) {
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int s_ = wave * 2 + j;
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const int r0 = a_piece_row(h, s_);
-                const int ra = r0 + lrow, m = m0 + ra;
-                o[h][j] = (valid && r0 >= 0 && m < g.M) ? (uint32_t)((long long)m * g.lda0 * ESZ + ((lch ^ (ra & 7)) << 4)) : 0x80000000u;
-            }
-        }
-    };
-    uint32_t ow[2][2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int rh = (wave * 2 + j) * 8 + lrow;
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int rw = (rh >> 5) * 64 + h * 32 + (rh & 31);          // LDS row of the W tile
-            // PERM: LDS row (block b, fragment i, row r) holds weight row b * 64 + (r >> 2) * 16 + i * 4 + (r & 3)
-            const int rsrc = PERM ? ((rw & ~63) | (((rw & 15) >> 2) << 4) | (((rw >> 4) & 3) << 2) | (rw & 3)) : rw;
-            ow[h][j] = (uint32_t)(rsrc * g.K * ESZ + ((lch ^ (rw & 7)) << 4));
-        }
-    }
-    auto lds_dst = [&](int kind, int j) __attribute__((always_inline)) -> int {
-        const int s_ = wave * 2 + j;
-        if (kind < 2) {
-            const int r0 = a_piece_row(kind, s_);
-            return (r0 >= 0 ? r0 : BM) * 128;
-        }
-        const int rb = s_ * 8;
-        return A_BYTES + ((rb >> 5) * 64 + (kind - 2) * 32 + (rb & 31)) * 128;
-    };
-
-    const int nk = g.K / KT;
-    int sa_row0 = 0;                                             // MX: first activation row of the tile the `oa` offsets point at
-    uint32_t oa[2][2];
-    int seq = seq0 + lid, m0, n0, m0n = 0, n0n = 0;
-    coords(seq, m0, n0);
-    set_a_offsets(oa, m0, true);
-    sa_row0 = m0;
-    bool has_next = seq + Lx < seq1;
-    if (has_next) coords(seq + Lx, m0n, n0n);
-    int gk = 0;                                                // K tiles consumed so far (stage of a K tile = parity)
-
-    // piece `kind` (0, 1 activation halves; 2, 3 weight halves) of K tile k of the tile whose column origin is nb
-    // MX: the K tile's 256 activation-row scale dwords (wave 0, with activation half 0) / weight-row scale dwords (wave 1, with weight
-    // half 0): 1 KB each = one wave instruction; rows past the scale array read zeros (those rows are never stored)
-    auto issue_a = [&](int kind, int k, int st) __attribute__((always_inline)) {
-        unsigned char* base = smem + (st & 1) * STAGE;
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (lds_void_t)(base + lds_dst(kind, j)), 16, (int)oa[kind][j], k * 128, 0, 0);
-        if constexpr (MX) {
-            if (kind == 0 && wave == 0)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsSA, (lds_void_t)(base + SC0), 16, lane * 16,
-                                                         (int)(((long long)k * g.mx_rows_a + sa_row0) * 4), 0, 0);
-        }
-    };
-    auto issue_w = [&](int kind, int k, int st, int nb) __attribute__((always_inline)) {
-        unsigned char* base = smem + (st & 1) * STAGE;
-        const int so = nb * g.K * ESZ + k * 128;
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsW, (lds_void_t)(base + lds_dst(kind, j)), 16, (int)ow[kind - 2][j], so, 0, 0);
-        if constexpr (MX) {
-            if (kind == 2 && wave == 1)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsSW, (lds_void_t)(base + SC0 + 1024), 16, lane * 16,
-                                                         (int)(((long long)k * g.mx_rows_w + nb) * 4), 0, 0);
-        }
-    };
-    // K tile t + d (d in {1, 2}) of this tile or, past its end, of the next tile
-    auto issue_rel = [&](int kind, int t, int d, auto tail_c) __attribute__((always_inline)) {
-        constexpr int TAIL = decltype(tail_c)::value;             // 0: t <= nk-3, 1: t = nk-2, 2: t = nk-1
-        const int st = gk + d;
-        if (kind < 2) issue_a(kind, TAIL + d <= 2 ? t + d : TAIL + d - 3, st);       // `oa` already points at the right tile
-        else if (TAIL + d <= 2) issue_w(kind, t + d, st, n0);
-        else if (has_next) issue_w(kind, TAIL + d - 3, st, n0n);
-    };
-
-    f32x4 acc[NF][MF];
-    bf16x8 fa[2][2][2];                                         // [ring half][row fragment of the pair][k step]
-    bf16x8 fw[4][2];                                            // [column fragment][k step] of the current K tile
-    // MX: a fragment is the 8-register operand of the 128-deep MFMA (chunks fq and 4 + fq of the row), built where it is read
-    i32x8 fa8[2][2], fw8[4];
-    int sca[2][2], scw[4];                                       // this lane's block scale (byte 0) per row fragment
-    auto read_pair = [&](auto half_c, const unsigned char* A, int pr) __attribute__((always_inline)) {
-        constexpr int HALF = decltype(half_c)::value;
-#pragma unroll
-        for (int jj = 0; jj < 2; ++jj) {
-            if (2 * pr + jj >= MF) continue;
-            const int rr = wrow_m + (2 * pr + jj) * 16 + fr;
-            if constexpr (MX) {
-                const u32x4 lo = *(const u32x4*)(A + rr * 128 + ((fq ^ (rr & 7)) << 4));
-                const u32x4 hi = *(const u32x4*)(A + rr * 128 + (((4 + fq) ^ (rr & 7)) << 4));
-                fa8[HALF][jj] = (i32x8){(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3], (int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
-                sca[HALF][jj] = (int)(*(const uint32_t*)(A + SC0 + rr * 4) >> (8 * fq));
-            } else {
-#pragma unroll
-                for (int ks = 0; ks < 2; ++ks) fa[HALF][jj][ks] = *(const bf16x8*)(A + rr * 128 + (((ks * 4 + fq) ^ (rr & 7)) << 4));
-            }
-        }
-    };
-    auto read_w = [&](const unsigned char* W, int ks) __attribute__((always_inline)) {   // W = stage base + A_BYTES
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int rr = wrow_n + i * 16 + fr;
-            if constexpr (MX) {
-                if (ks == 0) {
-                    const u32x4 lo = *(const u32x4*)(W + rr * 128 + ((fq ^ (rr & 7)) << 4));
-                    const u32x4 hi = *(const u32x4*)(W + rr * 128 + (((4 + fq) ^ (rr & 7)) << 4));
-                    fw8[i] = (i32x8){(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3], (int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
-                    // LDS row rr holds weight row (rr & ~63) | ((rr & 15) >> 2) << 4 | ((rr >> 4) & 3) << 2 | (rr & 3) when PERM
-                    const int rs_ = PERM ? ((rr & ~63) | (((rr & 15) >> 2) << 4) | (((rr >> 4) & 3) << 2) | (rr & 3)) : rr;
-                    scw[i] = (int)(*(const uint32_t*)(W + (SC0 - A_BYTES) + 1024 + rs_ * 4) >> (8 * fq));
-                }
-            } else {
-                fw[i][ks] = *(const bf16x8*)(W + rr * 128 + (((ks * 4 + fq) ^ (rr & 7)) << 4));
-            }
-        }
-    };
-    auto mma = [&](auto half_c, int pr, int ks) __attribute__((always_inline)) {
-        constexpr int HALF = decltype(half_c)::value;
-        if constexpr (MX) { if (ks == 0) return; }                // one 128-deep MFMA per fragment pair: issued in the second slot
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int jj = 0; jj < 2; ++jj) {
-                if (2 * pr + jj >= MF) continue;
-                if constexpr (MX) {
-                    // inline asm: around the builtin hipcc's register allocation needs ~100 more VGPRs (every instance spilled 120-360
-                    // registers into the K loop; with bf16 MFMAs in its place none did).  Operands come from LDS reads (waited for by
-                    // the compiler, which sees them as inputs) and a shift issued a phase earlier: no hazard window inside the string
-                    // beyond the s_nop; the accumulator chains MFMA -> MFMA (no wait states) and is next read in the epilogue.
-                    asm volatile("s_nop 1\n\tv_mfma_scale_f32_16x16x128_f8f6f4 %0, %1, %2, %0, %3, %4 op_sel_hi:[0,0,0]"
-                                 : "+v"(acc[i][2 * pr + jj]) : "v"(fw8[i]), "v"(fa8[HALF][jj]), "v"(scw[i]), "v"(sca[HALF][jj]));
-                } else {
-                    acc[i][2 * pr + jj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fw[i][ks], fa[HALF][jj][ks], acc[i][2 * pr + jj], 0, 0, 0);
-                }
-            }
-        __builtin_amdgcn_s_setprio(0);
-    };
-    uint32_t dg[8] = {0, 0, 0, 0, 0, 0, 0, 0}, dtb = 0, dtc = 0;   // DIAG: [0] sync waits [1] barrier waits [2] main loops [3] epilogues
-    auto stamp = [&]() __attribute__((always_inline)) -> uint32_t { return (uint32_t)__builtin_amdgcn_s_memtime(); };   // [4] first sync of a tile [5] tiles [6] syncs
-    // DMA pieces of the window that follows a sync point: phase P-1 (of the K tile of the sync point) takes both activation halves
-    // of K tile t+2, the first phases of the next K tile the weight halves of (its) K tile t+1; phase P-2 - the one that ends in
-    // the next sync point - issues nothing, so the youngest piece has a whole phase to land before it is waited for
-    auto dma_for_phase = [&](int p, int t, auto tail_c) __attribute__((always_inline)) {
-        if constexpr (P == 2) {
-            // 96 / 128-row tiles: the phase that follows the sync point is also the only one that does not end in the next: all eight
-            // pieces of K tile t+2 go here (its stage - K tile t's - is free: the weight fragments of K tile t were read a K tile ago)
-            if (p == 1) { issue_rel(0, t, 2, tail_c); issue_rel(1, t, 2, tail_c); issue_rel(2, t, 2, tail_c); issue_rel(3, t, 2, tail_c); }
-            return;
-        }
-        if (p == P - 1) { issue_rel(0, t, 2, tail_c); issue_rel(1, t, 2, tail_c); return; }
-        if constexpr (P == 4) { if (p < 2) issue_rel(2 + p, t, 1, tail_c); }
-        else { if (p == 0) { issue_rel(2, t, 1, tail_c); issue_rel(3, t, 1, tail_c); } }
-    };
-    // one K tile.  PAR: ring half that holds row pair 0 of this K tile (odd P: alternates).  LASTK: t = nk - 1
-    auto ktile = [&](int t, auto tail_c, auto par_c) __attribute__((always_inline)) {
-        constexpr int TAIL = decltype(tail_c)::value, PAR = decltype(par_c)::value;
-        if constexpr (TAIL == 1) { set_a_offsets(oa, m0n, has_next); sa_row0 = m0n; }   // from here on activation pieces belong to the next tile
-        const unsigned char* A = smem + (gk & 1) * STAGE;
-        const unsigned char* An = smem + ((gk + 1) & 1) * STAGE;
-        auto phase = [&](auto p_c) __attribute__((always_inline)) {
-            constexpr int p = decltype(p_c)::value;
-            constexpr int CUR = (PAR + p) & 1, NXT = CUR ^ 1;
-            if constexpr (p + 1 < P) read_pair(ic<NXT>{}, A, p + 1);
-            else if constexpr (TAIL != 2) read_pair(ic<NXT>{}, An, 0);          // row pair 0 of the next K tile
-            dma_for_phase(p, t, tail_c);
-            mma(ic<CUR>{}, p, 0);
-            if constexpr (p == P - 1 && TAIL != 2 && !MX) {
-                __builtin_amdgcn_sched_barrier(0);
-                read_w(An + A_BYTES, 0);                                        // in place: k step 0 of K tile t had its last use
-            }
-            mma(ic<CUR>{}, p, 1);
-            if constexpr (p == P - 1 && TAIL != 2) {
-                __builtin_amdgcn_sched_barrier(0);
-                if constexpr (MX) read_w(An + A_BYTES, 0);                      // (MX: both halves feed the one MFMA of a fragment pair)
-                else read_w(An + A_BYTES, 1);
-            }
-            if constexpr (p == P - 2) {
-                // sync point: every DMA issued so far (all of K tile t+1) has landed, this wave's fragment reads are retired;
-                // behind the barrier K tile t+1 is visible to every wave and the stage of K tile t is free
-                if constexpr (DIAG) {
-                    __builtin_amdgcn_sched_barrier(0);
-                    const uint32_t ta = stamp();
-                    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-                    __builtin_amdgcn_sched_barrier(0);
-                    if (dg[6]) dg[1] += dtc - dtb;                 // barrier wait of the previous sync point (stamp landed by now)
-                    const uint32_t tb = stamp();
-                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                    __builtin_amdgcn_sched_barrier(0);
-                    dg[0] += tb - ta; if (t == 0) dg[4] += tb - ta; dg[6] += 1; dtb = tb;
-                    bar();
-                    __builtin_amdgcn_sched_barrier(0);
-                    dtc = stamp();
-                } else {
-                    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-                    __builtin_amdgcn_sched_barrier(0);
-                    bar();
-                }
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        };
-        phase(ic<0>{});
-        if constexpr (P > 1) phase(ic<1>{});
-        if constexpr (P > 2) phase(ic<2>{});
-        if constexpr (P > 3) phase(ic<3>{});
-        ++gk;
-    };
-
-    __syncthreads();                                           // bias image complete (no DMA in flight yet)
-    // ---- first tile: K tile 0 complete, the activation halves of K tile 1 in flight ---------------------------------------
-    issue_a(0, 0, 0); issue_a(1, 0, 0); issue_w(2, 0, 0, n0); issue_w(3, 0, 0, n0);
-    issue_a(0, 1, 1); issue_a(1, 1, 1);
-    if constexpr (P == 2) {                                    // (no phase 0 issue of K tile 1's weight halves in this schedule)
-        issue_w(2, 1, 1, n0); issue_w(3, 1, 1, n0);
-        asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    } else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    bar();
-
-    const uint32_t dk0 = DIAG ? stamp() : 0;
-    for (;;) {
-        uint32_t dt0 = 0, dt1 = 0;
-        if constexpr (DIAG) dt0 = stamp();
-#pragma unroll
-        for (int i = 0; i < NF; ++i)
-#pragma unroll
-            for (int j = 0; j < MF; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        {   // tile prologue: weight fragments and row pair 0 of K tile 0 (landed and visible since the previous sync point)
-            const unsigned char* A = smem + (gk & 1) * STAGE;
-            read_w(A + A_BYTES, 0); read_w(A + A_BYTES, 1);
-            read_pair(ic<0>{}, A, 0);
-        }
-        if constexpr (P & 1) {
-            for (int t = 0; t < nk - 2; t += 2) { ktile(t, ic<0>{}, ic<0>{}); ktile(t + 1, ic<0>{}, ic<1>{}); }
-            ktile(nk - 2, ic<1>{}, ic<0>{});
-            ktile(nk - 1, ic<2>{}, ic<1>{});
-        } else {
-            for (int t = 0; t < nk - 2; ++t) ktile(t, ic<0>{}, ic<0>{});
-            ktile(nk - 2, ic<1>{}, ic<0>{});
-            ktile(nk - 1, ic<2>{}, ic<0>{});
-        }
-        // ---- epilogue: straight from the accumulators ------------------------------------------------------------------------
-        if constexpr (DIAG) { dt1 = stamp(); asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); dg[2] += dt1 - dt0; dg[5] += 1; }
-        if constexpr (!F32OUT) {
-            const bool gelu = g.flags & YV_EPI_GELU;
-            const float* bl = (const float*)(smem + BIAS0) + n0 + wrow_n + fq * 16;
-            float4 bv[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) bv[i] = *(const float4*)(bl + i * 4);
-            if constexpr (EXT == 2) {
-                // out = bf16(acc + b) * gelu'(u), u = the pre-activation the forward saved (same rounding steps as the 128 x 128 kernel's
-                // epilogue); u of two row fragments is in flight together
-#pragma unroll
-                for (int j0 = 0; j0 < MF; j0 += 2) {
-                    u32x4 ur[2][2];
-                    uint32_t offx[2];
-#pragma unroll
-                    for (int jj = 0; jj < 2; ++jj) {
-                        const int m = m0 + wrow_m + (j0 + jj) * 16 + fr;
-                        offx[jj] = (j0 + jj < MF && m < M) ? (uint32_t)((m * g.ldaux + n0 + wrow_n + fq * 16) * 2) : 0x80000000u;
-                        ur[jj][0] = __builtin_amdgcn_raw_buffer_load_b128(rsX, offx[jj], 0, 0);
-                        ur[jj][1] = __builtin_amdgcn_raw_buffer_load_b128(rsX, offx[jj] + 16, 0, 0);
-                    }
-#pragma unroll
-                    for (int jj = 0; jj < 2; ++jj) {
-                        if (j0 + jj >= MF) continue;
-                        const int j = j0 + jj;
-                        const int m = m0 + wrow_m + j * 16 + fr;
-                        uint32_t pk[8];
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) {
-                            const uint32_t d01 = pack_bf16x2(acc[i][j][0] + bv[i].x, acc[i][j][1] + bv[i].y);
-                            const uint32_t d23 = pack_bf16x2(acc[i][j][2] + bv[i].z, acc[i][j][3] + bv[i].w);
-                            const uint32_t u01 = ur[jj][i >> 1][(i & 1) * 2], u23 = ur[jj][i >> 1][(i & 1) * 2 + 1];
-                            pk[2 * i] = pack_bf16x2(bf16_to_f32((uint16_t)(d01 & 0xffff)) * gelu_grad_f(bf16_to_f32((uint16_t)(u01 & 0xffff))),
-                                                    bf16_to_f32((uint16_t)(d01 >> 16)) * gelu_grad_f(bf16_to_f32((uint16_t)(u01 >> 16))));
-                            pk[2 * i + 1] = pack_bf16x2(bf16_to_f32((uint16_t)(d23 & 0xffff)) * gelu_grad_f(bf16_to_f32((uint16_t)(u23 & 0xffff))),
-                                                        bf16_to_f32((uint16_t)(d23 >> 16)) * gelu_grad_f(bf16_to_f32((uint16_t)(u23 >> 16))));
-                        }
-                        const uint32_t off = m < M ? (uint32_t)((m * g.ldo + n0 + wrow_n + fq * 16) * 2) : 0x80000000u;
-                        __builtin_amdgcn_raw_buffer_store_b128((u32x4){pk[0], pk[1], pk[2], pk[3]}, rsO, off, 0, 0);
-                        __builtin_amdgcn_raw_buffer_store_b128((u32x4){pk[4], pk[5], pk[6], pk[7]}, rsO, off, 16, 0);
-                    }
-                }
-            } else if (MX && (g.flags & YV_EPI_OUT_MXFP8)) {
-                // the consumer is another MXFP8 GEMM (fc1 -> fc2): the lane's 16 consecutive (bf16-rounded) outputs + the 16 of lane ^ 16
-                // are one 32-column MX block; same arithmetic as the 128 x 128 kernel's epilogue (byte-identical images)
-#pragma unroll
-                for (int j = 0; j < MF; ++j) {
-                    const int m = m0 + wrow_m + j * 16 + fr;
-                    float f[16], amax = 0.f;
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        float v0 = acc[i][j][0] + bv[i].x, v1 = acc[i][j][1] + bv[i].y;
-                        float v2 = acc[i][j][2] + bv[i].z, v3 = acc[i][j][3] + bv[i].w;
-                        if (gelu) { v0 = gelu_f(v0); v1 = gelu_f(v1); v2 = gelu_f(v2); v3 = gelu_f(v3); }
-                        f[4 * i] = bf16_to_f32(f32_to_bf16(v0)); f[4 * i + 1] = bf16_to_f32(f32_to_bf16(v1));
-                        f[4 * i + 2] = bf16_to_f32(f32_to_bf16(v2)); f[4 * i + 3] = bf16_to_f32(f32_to_bf16(v3));
-                    }
-#pragma unroll
-                    for (int q = 0; q < 16; ++q) amax = fmaxf(amax, fabsf(f[q]));
-                    amax = fmaxf(amax, __shfl_xor(amax, 16, 64));
-                    int e = -127;
-                    if (amax > 0.f) {
-                        int ex;
-                        const float mant = frexpf(amax * (1.0f / 448.0f), &ex);
-                        e = mant == 0.5f ? ex - 1 : ex;
-                        e = e < -127 ? -127 : (e > 127 ? 127 : e);
-                    }
-                    const float inv = ldexpf(1.0f, -e);
-                    uint32_t q4[4];
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        int pq = 0;
-                        pq = __builtin_amdgcn_cvt_pk_fp8_f32(f[4 * i] * inv, f[4 * i + 1] * inv, pq, false);
-                        pq = __builtin_amdgcn_cvt_pk_fp8_f32(f[4 * i + 2] * inv, f[4 * i + 3] * inv, pq, true);
-                        q4[i] = (uint32_t)pq;
-                    }
-                    if (m < M) {
-                        const int n = n0 + wrow_n + fq * 16;
-                        *(uint4*)(g.mxq + (long long)m * g.ldmxq + n) = make_uint4(q4[0], q4[1], q4[2], q4[3]);
-                        if (!(fq & 1)) {
-                            const int bk = n >> 5;
-                            g.mxs[((long long)(bk >> 2) * g.mx_rows + m) * 4 + (bk & 3)] = (uint8_t)(e + 127);
-                        }
-                    }
-                }
-            } else {
-#pragma unroll
-                for (int j = 0; j < MF; ++j) {
-                    const int m = m0 + wrow_m + j * 16 + fr;
-                    uint32_t pk[8];
-                    if constexpr (EXT == 1) {                     // the pre-activation, bf16 (the backward's gelu'(u) reads it)
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) {
-                            pk[2 * i] = pack_bf16x2(acc[i][j][0] + bv[i].x, acc[i][j][1] + bv[i].y);
-                            pk[2 * i + 1] = pack_bf16x2(acc[i][j][2] + bv[i].z, acc[i][j][3] + bv[i].w);
-                        }
-                        const uint32_t offx = m < M ? (uint32_t)((m * g.ldaux + n0 + wrow_n + fq * 16) * 2) : 0x80000000u;
-                        __builtin_amdgcn_raw_buffer_store_b128((u32x4){pk[0], pk[1], pk[2], pk[3]}, rsX, offx, 0, 0);
-                        __builtin_amdgcn_raw_buffer_store_b128((u32x4){pk[4], pk[5], pk[6], pk[7]}, rsX, offx, 16, 0);
-                    }
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        float v0 = acc[i][j][0] + bv[i].x, v1 = acc[i][j][1] + bv[i].y;
-                        float v2 = acc[i][j][2] + bv[i].z, v3 = acc[i][j][3] + bv[i].w;
-                        if (gelu) { v0 = gelu_f(v0); v1 = gelu_f(v1); v2 = gelu_f(v2); v3 = gelu_f(v3); }
-                        pk[2 * i] = pack_bf16x2(v0, v1); pk[2 * i + 1] = pack_bf16x2(v2, v3);
-                    }
-                    const uint32_t off = m < M ? (uint32_t)((m * g.ldo + n0 + wrow_n + fq * 16) * 2) : 0x80000000u;
-                    __builtin_amdgcn_raw_buffer_store_b128((u32x4){pk[0], pk[1], pk[2], pk[3]}, rsO, off, 0, YV_P9_STORE_AUX);
-                    __builtin_amdgcn_raw_buffer_store_b128((u32x4){pk[4], pk[5], pk[6], pk[7]}, rsO, off, 16, YV_P9_STORE_AUX);
-                }
-            }
-        } else {
-            const bool rmw = g.flags & YV_EPI_RES_F32;
-            const float* bl = (const float*)(smem + BIAS0) + n0 + wrow_n + fq * 4;
-            float4 bv[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) bv[i] = *(const float4*)(bl + i * 16);
-            constexpr int JA = 2;                                // row fragments whose residual values are in flight together
-#pragma unroll
-            for (int j0 = 0; j0 < MF; j0 += JA) {
-                u32x4 xr[JA][4];
-                uint32_t off[JA];
-#pragma unroll
-                for (int jj = 0; jj < JA; ++jj) {
-                    const int m = m0 + wrow_m + (j0 + jj) * 16 + fr;
-                    off[jj] = (j0 + jj < MF && m < M) ? (uint32_t)((m * g.ldo + n0 + wrow_n + fq * 4) * 4) : 0x80000000u;
-                    if (rmw) {
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) xr[jj][i] = __builtin_amdgcn_raw_buffer_load_b128(rsR, off[jj] + i * 64, 0, 0);
-                    }
-                }
-#pragma unroll
-                for (int jj = 0; jj < JA; ++jj) {
-                    if (j0 + jj >= MF) continue;
-                    const int j = j0 + jj;
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        float v0 = acc[i][j][0] + bv[i].x, v1 = acc[i][j][1] + bv[i].y;
-                        float v2 = acc[i][j][2] + bv[i].z, v3 = acc[i][j][3] + bv[i].w;
-                        if (rmw) {
-                            v0 += __uint_as_float(xr[jj][i][0]); v1 += __uint_as_float(xr[jj][i][1]);
-                            v2 += __uint_as_float(xr[jj][i][2]); v3 += __uint_as_float(xr[jj][i][3]);
-                        }
-                        // the column step goes into the instruction's immediate offset, never into an SGPR soffset: behind a 16-byte
-                        // store with a REGISTER soffset hipcc pads nothing before the next write of the data registers (LLVM takes that
-                        // form to be free of the store-data hazard) and on gfx950 the store then read overwritten values (measured:
-                        // 0.9 % of the outputs wrong, always the columns whose step needed a register: 128 and 192 bytes)
-                        __builtin_amdgcn_raw_buffer_store_b128((u32x4){__float_as_uint(v0), __float_as_uint(v1), __float_as_uint(v2),
-                                                                       __float_as_uint(v3)}, rsO, off[jj] + i * 64, 0, 0);
-                    }
-                }
-            }
-        }
-        if constexpr (DIAG) { const uint32_t dt2 = stamp(); asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); dg[3] += dt2 - dt1; }
-        if (!has_next) break;
-        seq += Lx;
-        m0 = m0n; n0 = n0n;
-        has_next = seq + Lx < seq1;
-        if (has_next) coords(seq + Lx, m0n, n0n);
-    }
-    if constexpr (DIAG) {
-        const uint32_t dk1 = stamp();
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        dg[7] = dk1 - dk0;
-        if (lane == 0) {
-            uint32_t* o = (uint32_t*)g.partial + ((long long)blockIdx.x * 8 + wave) * 16;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) o[i] = dg[i];
-        }
-    }
-}
-
-template <int MF, bool F32OUT, int EXT = 0, bool MX = false>
-int launch_p9_inst(GemmArgs& g, hipStream_t st, int n_cu) {
-    constexpr int BM = 32 * MF;
-    g.tiles_m = (g.M + BM - 1) / BM;
-    g.tiles_n = g.N / 256;
-    const size_t lds = 2 * 65536 + 16384 + (MX ? 4096 : 0);
-    auto kern = gemm_p9_kernel<MF, F32OUT, 0, EXT, MX>;
-    {   // the dynamic-LDS grant belongs to the device's copy of the kernel: once per device and instance
-        static std::atomic<unsigned> granted[2] = {{0u}, {0u}};    // bit d: device d (up to 64 devices)
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return YV_ERR_LAUNCH;
-        if (!((granted[dev >> 5].load(std::memory_order_acquire) >> (dev & 31)) & 1u)) {
-            if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-                return YV_ERR_LAUNCH;
-            granted[dev >> 5].fetch_or(1u << (dev & 31), std::memory_order_release);
-        }
-    }
-    const int tiles = g.tiles_m * g.tiles_n;
-    const int grid = tiles < n_cu ? tiles : n_cu;
-    if (t_time_start || t_time_stop) {
-        hipExtLaunchKernelGGL(kern, dim3(grid), dim3(512), (uint32_t)lds, st, t_time_start, t_time_stop, 0, g);
-        t_time_start = t_time_stop = nullptr;
-    } else {
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, st, g);
-    }
-    return yv_launch_status();
-}
-
-// rows: 0 = choose (minimise rounds x (rows + per-tile cost)), else 160 / 192 / 224 / 256
-int launch_p9(GemmArgs& g, hipStream_t st, int rows = 0, bool mx = false) {
-    static int n_cu_dev = 0;
-    if (!n_cu_dev) {
-        int dev = 0; hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return YV_ERR_LAUNCH;
-        n_cu_dev = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    }
-    const int n_cu = (g_opt_p8_cus > 0 && g_opt_p8_cus < n_cu_dev) ? g_opt_p8_cus : n_cu_dev;
-    g.sched = g_opt_p8_sched;
-    const bool f32out = g.flags & (YV_EPI_RES_F32 | YV_EPI_OUT_F32);
-    const bool even_nk = ((g.K / (mx ? 128 : BK)) & 1) == 0;         // odd-P instances (160 / 192 rows) walk K tiles in pairs
-    const int ext = (g.flags & YV_EPI_SAVE_PRE) ? 1 : (g.flags & YV_EPI_GELU_BWD) ? 2 : 0;
-    int best = rows ? rows : g_opt_p8_rows;
-    if (ext && best > 224) best = 224;
-    if (!best) {
-        long long best_cost = -1;
-        const int cand[6] = {256, 224, 192, 160, 128, 96};
-        const bool small_ok = !mx && !ext && g_opt_p9_small;       // 128 / 96-row tiles: instances exist for the plain epilogues
-        for (int c = 0; c < (small_ok ? 6 : 4); ++c) {
-            if (cand[c] <= 192 && cand[c] >= 160 && !even_nk) continue;
-            if (cand[c] > 192 && f32out && even_nk) continue;      // f32 outputs: the residual prefetch next to the accumulators spills above 192 rows
-            if (cand[c] > 224 && ext) continue;                     // trainer epilogues: up to 224 rows
-            if (cand[c] > 160 && mx && f32out) continue;            // MX with f32 output: 160 rows (registers)
-            const long long tiles = (long long)((g.M + cand[c] - 1) / cand[c]) * (g.N / 256);
-            const long long rounds = (tiles + n_cu - 1) / n_cu;
-            // a K tile of a tile costs its rows + a fixed part (weight pieces, sync point); the short tiles pay the weight fetch
-            // over fewer rows and are worth it only where the taller ones leave CUs idle (tools/gemm_lab.hip, LAB_M=6304)
-            const long long cost = rounds * (cand[c] + (cand[c] < 160 ? g_opt_p9_small_fixed : 16));
-            if (best_cost < 0 || cost < best_cost) { best_cost = cost; best = cand[c]; }
-        }
-    }
-    if (best <= 192 && best >= 160 && !even_nk) best = 224;
-    // MX trainer epilogues.  Reached by tests/test_gpu_mx_train.py::test_mx_linear_ex_epilogues: 160 rows by the ViT-B/16 shapes
-    // (M = 6,304, N = 3,072, K = 768), 224 by the ViT-L/16 shapes (N = 4,096, K = 1,024) and by an odd K / 128 (K = 640);
-    // each height (160 / 192 / 224) also forced through "linear_p8_rows" by test_mx_linear_ex_persistent_tile_heights
-    if (mx && ext == 1) switch (best) {           // MX trainer: fc1 forward (GELU + saved pre-activation)
-        case 192: return launch_p9_inst<6, false, 1, true>(g, st, n_cu);
-        case 160: return launch_p9_inst<5, false, 1, true>(g, st, n_cu);
-        default: return launch_p9_inst<7, false, 1, true>(g, st, n_cu);
-    }
-    if (mx && ext == 2) switch (best) {           // MX trainer: fc2 data gradient (GELU backward)
-        case 192: return launch_p9_inst<6, false, 2, true>(g, st, n_cu);
-        case 160: return launch_p9_inst<5, false, 2, true>(g, st, n_cu);
-        default: return launch_p9_inst<7, false, 2, true>(g, st, n_cu);
-    }
-    if (mx) switch (best) {
-        case 224: return f32out ? launch_p9_inst<7, true, 0, true>(g, st, n_cu) : launch_p9_inst<7, false, 0, true>(g, st, n_cu);
-        case 192: return f32out ? launch_p9_inst<6, true, 0, true>(g, st, n_cu) : launch_p9_inst<6, false, 0, true>(g, st, n_cu);
-        case 160: return f32out ? launch_p9_inst<5, true, 0, true>(g, st, n_cu) : launch_p9_inst<5, false, 0, true>(g, st, n_cu);
-        default: return f32out ? launch_p9_inst<8, true, 0, true>(g, st, n_cu) : launch_p9_inst<8, false, 0, true>(g, st, n_cu);
-    }
-    if (ext == 1) switch (best) {
-        case 192: return launch_p9_inst<6, false, 1>(g, st, n_cu);
-        case 160: return launch_p9_inst<5, false, 1>(g, st, n_cu);
-        default: return launch_p9_inst<7, false, 1>(g, st, n_cu);
-    }
-    if (ext == 2) switch (best) {
-        case 192: return launch_p9_inst<6, false, 2>(g, st, n_cu);
-        case 160: return launch_p9_inst<5, false, 2>(g, st, n_cu);
-        default: return launch_p9_inst<7, false, 2>(g, st, n_cu);
-    }
-    switch (best) {
-        case 128: return f32out ? launch_p9_inst<4, true>(g, st, n_cu) : launch_p9_inst<4, false>(g, st, n_cu);
-        case 96: return f32out ? launch_p9_inst<3, true>(g, st, n_cu) : launch_p9_inst<3, false>(g, st, n_cu);
-        case 224: return f32out ? launch_p9_inst<7, true>(g, st, n_cu) : launch_p9_inst<7, false>(g, st, n_cu);
-        case 192: return f32out ? launch_p9_inst<6, true>(g, st, n_cu) : launch_p9_inst<6, false>(g, st, n_cu);
-        case 160: return f32out ? launch_p9_inst<5, true>(g, st, n_cu) : launch_p9_inst<5, false>(g, st, n_cu);
-        default: return f32out ? launch_p9_inst<8, true>(g, st, n_cu) : launch_p9_inst<8, false>(g, st, n_cu);
-    }
-}
-
-
-// ---------------------------------------------------------------------------------------------
 // Weight-gradient GEMM ("TN"): dW[n][k] = sum_t dY[t][n] * X[t][k], t = token (the reduction index).
 // Both operands are stored token-major, i.e. the reduction index is the ROW of the LDS tiles, so the MFMA
 // fragments (8 consecutive reduction elements per lane) are COLUMNS of those tiles: they are read with the
@@ -2919,12 +1747,7 @@ __global__ __launch_bounds__(512) void gemm_skinny_kernel(GemmArgs g) {
 int launch_skinny(GemmArgs& g, hipStream_t st) {
     g.tiles_m = (g.M + 63) / 64;
     g.tiles_n = g.N >> 4;
-    if (t_time_start || t_time_stop) {
-        hipExtLaunchKernelGGL(gemm_skinny_kernel, dim3(g.tiles_m * g.tiles_n), dim3(512), 0, st, t_time_start, t_time_stop, 0, g);
-        t_time_start = t_time_stop = nullptr;
-    } else {
-        hipLaunchKernelGGL(gemm_skinny_kernel, dim3(g.tiles_m * g.tiles_n), dim3(512), 0, st, g);
-    }
+    launch_timed(gemm_skinny_kernel, g.tiles_m * g.tiles_n, 512, 0, st, g);
     return yv_launch_status();
 }
 
@@ -2934,24 +1757,10 @@ int launch_dma(GemmArgs& g, hipStream_t st) {
     g.tiles_n = (g.N + BN - 1) / BN;
     const size_t lds = 2 * (size_t)(BM + BN) * 128;
     auto kern = gemm_dma_kernel<BM, BN, WM, WN, ABL, WT>;
-    if (lds > 65536 &&
-        hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return YV_ERR_LAUNCH;
+    if (!yv_grant_lds((const void*)kern, lds)) return YV_ERR_LAUNCH;
     const int S = g.splitk > 1 ? g.splitk : 1;
-    if (t_time_start || t_time_stop) {
-        // timestamps taken from the kernel's own dispatch packet (no extra barrier packets in the queue, unlike a pair of
-        // hipEventRecord calls around the launch)
-        hipExtLaunchKernelGGL(kern, dim3(g.tiles_m * g.tiles_n * S), dim3(WM * WN * 64), (uint32_t)lds, st, t_time_start,
-                              t_time_stop, 0, g);
-        t_time_start = t_time_stop = nullptr;
-    } else {
-        hipLaunchKernelGGL(kern, dim3(g.tiles_m * g.tiles_n * S), dim3(WM * WN * 64), lds, st, g);
-    }
-    if (S > 1) {
-        const long long items = (long long)g.M * (g.N >> 2);
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, g);
-    }
-    return yv_launch_status();
+    launch_timed(kern, g.tiles_m * g.tiles_n * S, WM * WN * 64, lds, st, g);
+    return launch_splitk_reduce(g, st);
 }
 
 template <int MODE, int BM, int BN, int WM, int WN>
@@ -2962,17 +1771,10 @@ int launch(GemmArgs& g, hipStream_t st) {
     if (lds < (size_t)THREADS / 64 * (BM / WM) * 128) lds = (size_t)THREADS / 64 * (BM / WM) * 128;   // the staged epilogue's slabs
     void (*kern)(GemmArgs) = igemm_kernel<MODE, BM, BN, WM, WN, false>;
     if constexpr (MODE == 1) { if (g.c1 > 0) kern = igemm_kernel<MODE, BM, BN, WM, WN, true>; }
-    if (lds > 65536) {
-        if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return YV_ERR_LAUNCH;
-    }
+    if (!yv_grant_lds((const void*)kern, lds)) return YV_ERR_LAUNCH;
     const int S = g.splitk > 1 ? g.splitk : 1;
     hipLaunchKernelGGL(kern, dim3(g.tiles_m * g.tiles_n * S), dim3(THREADS), lds, st, g);
-    if (S > 1) {
-        const long long items = (long long)g.M * (g.N >> 2);
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, g);
-    }
-    return yv_launch_status();
+    return launch_splitk_reduce(g, st);
 }
 
 
@@ -2994,16 +1796,7 @@ int launch_cdma(GemmArgs& g, hipStream_t st) {
     g.tiles_n = (g.N + BN - 1) / BN;
     const size_t lds = ST * (size_t)(128 + BN) * 128;
     auto kern = cgemm_dma_kernel<BN, WM, WN, ST>;
-    if (lds > 65536) {
-        static std::atomic<unsigned> granted[2] = {{0u}, {0u}};
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return YV_ERR_LAUNCH;
-        if (!((granted[dev >> 5].load(std::memory_order_acquire) >> (dev & 31)) & 1u)) {
-            if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-                return YV_ERR_LAUNCH;
-            granted[dev >> 5].fetch_or(1u << (dev & 31), std::memory_order_release);
-        }
-    }
+    if (!yv_grant_lds((const void*)kern, lds)) return YV_ERR_LAUNCH;
     hipLaunchKernelGGL(kern, dim3(g.tiles_m * g.tiles_n), dim3(256), lds, st, g);
     return yv_launch_status();
 }
@@ -3098,6 +1891,15 @@ int conv_instance_code(const GemmArgs& g, int kern) {
     return kern | (staged ? 16 : 0) | (split ? 32 : 0) | (two ? 64 : 0);
 }
 
+// Images per sub-batch of a convolution (32-bit byte offsets: each source below 2 GB): s0 / s1 bytes per image of the sources
+// (s1 = 0: one source), `lead` bytes addressed in front of source 0.  < 1: a single image is too large.
+long long conv_sub_batch(long long s0, long long s1, long long lead) {
+    const long long cap = 0x7ffffff0LL;
+    long long nb = s0 > 0 ? (cap - lead) / s0 : 0x7fffffffLL;
+    if (s1 > 0 && cap / s1 < nb) nb = cap / s1;
+    return nb;
+}
+
 }  // namespace
 
 extern "C" int yv_set_workspace(void* stream, void* ws, size_t bytes) {
@@ -3179,20 +1981,9 @@ static int launch_mx128(MxArgs& a, hipStream_t stream) {
     const int threads = 256;
     const size_t lds = 2 * (size_t)(128 * 128 * 2 + 1024);
     auto kern = gemm_mx_kernel<128, 128, 2, 2>;
-    if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return YV_ERR_LAUNCH;
-    const unsigned grid = (unsigned)(g.tiles_m * g.tiles_n * S);
-    if (t_time_start || t_time_stop) {
-        hipExtLaunchKernelGGL(kern, dim3(grid), dim3(threads), (uint32_t)lds, stream, t_time_start, t_time_stop, 0, a);
-        t_time_start = t_time_stop = nullptr;
-    } else {
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, stream, a);
-    }
-    if (S > 1) {
-        const long long items = (long long)g.M * (g.N >> 2);
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, stream, g);
-    }
-    return yv_launch_status();
+    if (!yv_grant_lds((const void*)kern, lds)) return YV_ERR_LAUNCH;
+    launch_timed(kern, (unsigned)(g.tiles_m * g.tiles_n * S), threads, lds, stream, a);
+    return launch_splitk_reduce(g, stream);
 }
 
 // flags of the MX linears' epilogues: yv_linear_mxfp8 (+ YV_EPI_OUT_MXFP8 from yv_linear_mxfp8_q) and, with a separate f32
@@ -3320,46 +2111,43 @@ extern "C" int yv_set_launch_timing(void* start_event, void* stop_event) {
     return YV_OK;
 }
 
+// key -> the option's storage (an accessor, not an address: linear_p8_cus is thread_local, so its address depends on the caller)
+static const struct { const char* key; int* (*at)(); } k_options[] = {
+    {"linear_variant", [] { return &g_opt_variant; }},
+    {"wgrad_split_cap", [] { return &g_opt_wgrad_cap; }},
+    {"wgrad_split", [] { return &g_opt_wgrad_split; }},
+    {"linear_p9_small", [] { return &g_opt_p9_small; }},
+    {"linear_p9_small_fixed", [] { return &g_opt_p9_small_fixed; }},
+    {"linear_group_m", [] { return &g_opt_group_m; }},
+    {"staged_epilogue", [] { return &g_opt_staged; }},
+    {"linear_p8", [] { return &g_opt_p8; }},
+    {"linear_p8_rows", [] { return &g_opt_p8_rows; }},
+    {"linear_p8_cus", [] { return &g_opt_p8_cus; }},
+    {"linear_p8_sched", [] { return &g_opt_p8_sched; }},
+    {"conv_splitk", [] { return &g_opt_splitk; }},
+    {"linear_splitk", [] { return &g_opt_linear_splitk; }},
+    {"linear_skinny", [] { return &g_opt_skinny; }},
+    {"wgrad_mx_split", [] { return &g_opt_wgrad_mx_split; }},
+    {"conv_dma", [] { return &g_opt_conv_dma; }},
+};
+static int* option_at(const char* key) {
+    for (const auto& o : k_options)
+        if (key && !strcmp(key, o.key)) return o.at();
+    return nullptr;
+}
+
 extern "C" int yv_set_option(const char* key, int value) {
-    if (!key) return YV_ERR_ARG;
-    if (!strcmp(key, "linear_variant")) { g_opt_variant = value; return YV_OK; }
-    if (!strcmp(key, "wgrad_split_cap")) { g_opt_wgrad_cap = value; return YV_OK; }
-    if (!strcmp(key, "wgrad_split")) { g_opt_wgrad_split = value; return YV_OK; }
-    if (!strcmp(key, "linear_p9_small")) { g_opt_p9_small = value; return YV_OK; }
-    if (!strcmp(key, "linear_p9_small_fixed")) { g_opt_p9_small_fixed = value; return YV_OK; }
-    if (!strcmp(key, "linear_group_m")) { g_opt_group_m = value; return YV_OK; }
-    if (!strcmp(key, "staged_epilogue")) { g_opt_staged = value; return YV_OK; }
-    if (!strcmp(key, "linear_p8")) { g_opt_p8 = value; return YV_OK; }
-    if (!strcmp(key, "linear_p8_rows")) { g_opt_p8_rows = value; return YV_OK; }
-    if (!strcmp(key, "linear_p8_cus")) { g_opt_p8_cus = value; return YV_OK; }
-    if (!strcmp(key, "linear_p8_sched")) { g_opt_p8_sched = value; return YV_OK; }
-    if (!strcmp(key, "conv_splitk")) { g_opt_splitk = value; return YV_OK; }
-    if (!strcmp(key, "linear_splitk")) { g_opt_linear_splitk = value; return YV_OK; }
-    if (!strcmp(key, "linear_skinny")) { g_opt_skinny = value; return YV_OK; }
-    if (!strcmp(key, "wgrad_mx_split")) { g_opt_wgrad_mx_split = value; return YV_OK; }
-    if (!strcmp(key, "conv_dma")) { g_opt_conv_dma = value; return YV_OK; }
-    return YV_ERR_ARG;
+    int* const opt = option_at(key);
+    if (!opt) return YV_ERR_ARG;
+    *opt = value;
+    return YV_OK;
 }
 
 extern "C" int yv_get_option(const char* key, int* value) {
-    if (!key || !value) return YV_ERR_ARG;
-    if (!strcmp(key, "linear_variant")) { *value = g_opt_variant; return YV_OK; }
-    if (!strcmp(key, "wgrad_split_cap")) { *value = g_opt_wgrad_cap; return YV_OK; }
-    if (!strcmp(key, "wgrad_split")) { *value = g_opt_wgrad_split; return YV_OK; }
-    if (!strcmp(key, "linear_p9_small")) { *value = g_opt_p9_small; return YV_OK; }
-    if (!strcmp(key, "linear_p9_small_fixed")) { *value = g_opt_p9_small_fixed; return YV_OK; }
-    if (!strcmp(key, "linear_group_m")) { *value = g_opt_group_m; return YV_OK; }
-    if (!strcmp(key, "staged_epilogue")) { *value = g_opt_staged; return YV_OK; }
-    if (!strcmp(key, "linear_p8")) { *value = g_opt_p8; return YV_OK; }
-    if (!strcmp(key, "linear_p8_rows")) { *value = g_opt_p8_rows; return YV_OK; }
-    if (!strcmp(key, "linear_p8_cus")) { *value = g_opt_p8_cus; return YV_OK; }
-    if (!strcmp(key, "linear_p8_sched")) { *value = g_opt_p8_sched; return YV_OK; }
-    if (!strcmp(key, "conv_splitk")) { *value = g_opt_splitk; return YV_OK; }
-    if (!strcmp(key, "linear_splitk")) { *value = g_opt_linear_splitk; return YV_OK; }
-    if (!strcmp(key, "linear_skinny")) { *value = g_opt_skinny; return YV_OK; }
-    if (!strcmp(key, "wgrad_mx_split")) { *value = g_opt_wgrad_mx_split; return YV_OK; }
-    if (!strcmp(key, "conv_dma")) { *value = g_opt_conv_dma; return YV_OK; }
-    return YV_ERR_ARG;
+    const int* const opt = option_at(key);
+    if (!opt || !value) return YV_ERR_ARG;
+    *value = *opt;
+    return YV_OK;
 }
 
 static int linear_impl(const void* A, int lda, const void* W, const float* bias, int M, int N, int K, void* out, int ldo,
@@ -3518,10 +2306,7 @@ static int conv_impl(const yv_view* in0, const yv_view* in1, int B, int Hout, in
     const bool two = in1 && in1->ptr;
     const long long s0 = (Hin >> in0->up) * (Win >> in0->up) * in0->ld * 2;
     const long long s1 = two ? (Hin >> in1->up) * (Win >> in1->up) * in1->ld * 2 : 0;
-    const long long lead = (Win + 1) * in0->ld * 2;
-    const long long cap = 0x7ffffff0LL;
-    long long nb = s0 > 0 ? (cap - lead) / s0 : B;
-    if (two && s1 > 0 && cap / s1 < nb) nb = cap / s1;
+    const long long nb = conv_sub_batch(s0, s1, (Win + 1) * in0->ld * 2);
     if (nb >= B)
         return conv_impl_one(in0, in1, B, Hout, Wout, ksize, stride, weight, bias, Cout, out, out_ld, res, res_ld, flags, ws, ws_bytes,
                              stream, query);
@@ -3594,11 +2379,7 @@ static int wgrad_impl(const void* dY, int ldy, const void* X, int ldx, int T, in
     const int S = g.splitk;
     const size_t lds = 2 * 2 * 64 * 256;
     hipLaunchKernelGGL(gemm_tn_kernel, dim3(g.tiles_m * g.tiles_n * S), dim3(256), lds, (hipStream_t)stream, g);
-    if (S > 1) {
-        const long long items = (long long)g.M * (g.N >> 2);
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, (hipStream_t)stream, g);
-    }
-    return yv_launch_status();
+    return launch_splitk_reduce(g, (hipStream_t)stream);
 }
 
 extern "C" int yv_wgrad(const void* dY, int ldy, const void* X, int ldx, int T, int N, int K, float* dW, int ldw,
@@ -3731,9 +2512,7 @@ extern "C" int yv_conv2d_mxfp8(const yv_mx_view* in0, const yv_mx_view* in1, int
     const bool two = in1 && in1->q;
     const long long s0 = (Hin >> in0->up) * (Win >> in0->up) * in0->ld;
     const long long s1 = two ? (Hin >> in1->up) * (Win >> in1->up) * in1->ld : 0;
-    const long long cap = 0x7ffffff0LL;
-    long long nb = (cap - (Win + 1) * in0->ld) / s0;
-    if (two && cap / s1 < nb) nb = cap / s1;
+    long long nb = conv_sub_batch(s0, s1, (Win + 1) * in0->ld);
     if (nb < 1) return YV_ERR_LIMIT;                              // a single image beyond 2 GB
     if (nb > B) nb = B;
     const long long opix = (long long)Hout * Wout;
@@ -3762,7 +2541,7 @@ extern "C" int yv_conv2d_mxfp8_instance(int B, int Hout, int Wout, int ksize, in
     if (rc != YV_OK) return rc;
     // first sub-batch of a dense source (pixel stride = Cin), as yv_conv2d_mxfp8 would take it
     const long long Win = (long long)Wout * stride, s0 = (long long)Hout * stride * Win * Cin;
-    long long nb = (0x7ffffff0LL - (Win + 1) * Cin) / s0;
+    long long nb = conv_sub_batch(s0, 0, (Win + 1) * Cin);
     if (nb < 1) return YV_ERR_LIMIT;
     if (nb > B) nb = B;
     return conv_mx_pick(nb * Hout * Wout, Cout);

@@ -13,7 +13,6 @@
 // intrinsics: no FMA contraction, IEEE divide) in torchvision's operation
 // order, which is what makes the keep list bit-exact against the reference.
 #include "yv_common.h"
-#include <atomic>
 
 namespace {
 
@@ -1356,9 +1355,7 @@ extern "C" int yv_custom_nms(const float* boxes, const float* scores, const int3
     if (need && (!ws || ws_bytes < need)) return YV_ERR_WORKSPACE;
     size_t lds = (size_t)np * 8 + (size_t)(((np >> 6) + 2) & ~1) * 8 + (np <= CN_LDS_BOX_MAX ? (size_t)np * 16 : 0);
     int threads = np < 1024 ? np : 1024;
-    if (hipFuncSetAttribute((const void*)custom_nms_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
-        hipSuccess)
-        return YV_ERR_LAUNCH;
+    if (!yv_grant_lds((const void*)custom_nms_kernel, lds)) return YV_ERR_LAUNCH;
     hipLaunchKernelGGL(custom_nms_kernel, dim3(n_sets), dim3(threads), lds, (hipStream_t)stream, boxes, scores, counts,
                        n_max, np, iou_threshold, keep, num_keep, (float4*)ws);
     return yv_launch_status();
@@ -1373,9 +1370,7 @@ extern "C" int yv_efficient_nms(const float* boxes, const float* scores, int B, 
     if (B == 0) return YV_OK;
     if (pre_topk <= 0 || pre_topk > EN_MAXK || nc > 32767 || (long long)A * nc > 0x7fffffffLL) return YV_ERR_LIMIT;
     size_t lds = (size_t)EN_MAXK * (8 + 16 + 2) + (EN_MAXK / 64) * 8 + sizeof(EnShared) + 16;
-    if (hipFuncSetAttribute((const void*)efficient_nms_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)lds) != hipSuccess)
-        return YV_ERR_LAUNCH;
+    if (!yv_grant_lds((const void*)efficient_nms_kernel, lds)) return YV_ERR_LAUNCH;
     hipLaunchKernelGGL(efficient_nms_kernel, dim3(B), dim3(EN_THREADS), lds, (hipStream_t)stream, boxes, scores, A, nc,
                        score_threshold, iou_threshold, max_out, pre_topk, num_dets, out_boxes, out_scores, out_labels);
     return yv_launch_status();
@@ -1438,21 +1433,8 @@ extern "C" int yv_efficient_nms_ws(const float* boxes, const float* scores, int 
     auto lds_of = [&](int cap, int nw) { return (size_t)cap * (8 + 16) + (size_t)max_out * 16 + 128 * 8 + (size_t)nw * 8 + 16; };
     const size_t head_dyn = (size_t)max_out * (16 + 8 + 2) + 16;
     const size_t lds1 = lds_of(EN_MAXK, 16) > head_dyn ? lds_of(EN_MAXK, 16) : head_dyn, lds0 = lds_of(1024, 4);
-    // dynamic-LDS limits already granted, PER DEVICE (the attribute belongs to the device's copy of the kernel; they only ever grow;
-    // atomics: request threads of different streams may race here - the worst case is a repeated, idempotent grant)
-    static std::atomic<size_t> attr_front[64], attr_classes[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return YV_ERR_LAUNCH;
-    if (lds1 > attr_front[dev].load(std::memory_order_acquire)) {
-        if (hipFuncSetAttribute((const void*)en2_front_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1) != hipSuccess)
-            return YV_ERR_LAUNCH;
-        attr_front[dev].store(lds1, std::memory_order_release);
-    }
-    if (lds0 > 32768 && lds0 > attr_classes[dev].load(std::memory_order_acquire)) {
-        if (hipFuncSetAttribute((const void*)en2_classes_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds0) != hipSuccess)
-            return YV_ERR_LAUNCH;
-        attr_classes[dev].store(lds0, std::memory_order_release);
-    }
+    // (the sizes depend on max_out: the grants grow with the largest request seen, see yv_grant_lds)
+    if (!yv_grant_lds((const void*)en2_front_kernel, lds1) || !yv_grant_lds((const void*)en2_classes_kernel, lds0)) return YV_ERR_LAUNCH;
     hipLaunchKernelGGL(en2_front_kernel, dim3(B), dim3(EN_THREADS), lds1, st, boxes, scores, A, nc, score_threshold, iou_threshold,
                        max_out, pre_topk, w, num_dets, out_boxes, out_scores, out_labels);
     if (nc <= EN2_TAIL_NC) {

@@ -187,7 +187,8 @@ def check(code: int, what: str = ""):
 
 
 def _apply_env_options():
-    """YV_OPTIONS="key=value,key=value": tuning knobs of yv_set_option for A/B runs (tools/, bench.py)."""
+    """YV_OPTIONS="key=value,key=value": yv_set_option pairs applied at import (A/B runs of bench.py / tools without editing
+    them); unknown keys fail loudly."""
     spec = os.environ.get("YV_OPTIONS", "")
     for item in filter(None, (x.strip() for x in spec.split(","))):
         k, _, v = item.partition("=")
@@ -1177,9 +1178,3 @@ def attention_mxfp8(qkv: torch.Tensor, R: int, N: int, H: int, out_q: torch.Tens
     check(lib.yv_attention_mxfp8(_p(qkv), R, N, H, float(64 ** -0.5 if scale is None else scale), _p(out_q), out_q.stride(0),
                                  _p(out_scale), out_scale.shape[1], _p(r_dev), _st()), "yv_attention_mxfp8")
 
-
-# development knob: YV_OPTIONS="key=value,key=value" applies yv_set_option pairs at import (A/B runs of bench.py / tools without
-# editing them); unknown keys fail loudly
-for _kv in filter(None, os.environ.get("YV_OPTIONS", "").split(",")):
-    _k, _v = _kv.split("=")
-    set_option(_k.strip(), int(_v))
