@@ -381,6 +381,19 @@ int yv_linear_ex(const void* A, int lda, const void* W, const float* bias, int M
 int yv_layernorm(const float* x, size_t ldx, const float* gamma, const float* beta, int rows, int D, float eps,
                  void* y, size_t ldy, const int32_t* count_dev, int rows_per_count, void* stream);
 
+/* Residual Linear + LayerNorm in one launch (timm Block: x = x + proj(attn) followed by norm2, x = x + fc2(mlp) followed
+ * by the next block's norm1; README.md:21-29):
+ *   x[M,N] (f32, row stride ldx, read-modify-write) = x + a[M,K] (bf16, row stride lda) @ w[N,K]^T (bf16) + bias[N] (f32)
+ *   h[M,N] (bf16, row stride ldh)                   = LayerNorm(x; gamma[N], beta[N], eps), statistics in f32, two-pass
+ * One kernel for every M (64-row tiles that span the output row; persistent, grid = "linear_p8_cus" budget of the calling thread).
+ * N in {128, 768, 1024}, K % 64 == 0, K >= 128, strides multiples of 8 elements, every pointer 16-byte aligned (YV_ERR_ARG,
+ * checked on the host before any HIP call); a, w, x, h are addressed with 32-bit byte offsets (YV_ERR_LIMIT past 2 GB).
+ * m_dev / m_mul as in yv_linear: rows >= min(M, m_dev[0]*m_mul) are neither read-modify-written in x nor written in h.
+ * A row's two outputs depend on that row's inputs only: bit-identical whatever M, the device count and the grid size. */
+int yv_linear_res_ln(const void* a, int lda, const void* w, const float* bias, int M, int N, int K, float* x, int ldx,
+                     const float* gamma, const float* beta, float eps, void* h, int ldh, const int32_t* m_dev, int m_mul,
+                     void* stream);
+
 /* Fused attention forward, non-causal: softmax(Q K^T * scale) V (timm Attention; README.md:21-23).
  * qkv (R*N, 3*H*64) bf16 as produced by the qkv Linear ([q|k|v], head-major);
  * out (R*N, H*64) bf16.  head dim 64; N <= 256 is one K/V tile (ViT-x/16: 197), longer sequences

@@ -1,4 +1,4 @@
-// Shared by the GEMM translation units (gemm.hip, gemm_persistent.hip): the argument block of every GEMM / convolution kernel,
+// Shared by the GEMM translation units (gemm.hip, gemm_persistent.hip, gemm_res_ln.hip): the argument block of every GEMM / convolution kernel,
 // the GELU of the epilogues, the timed launch, and the declarations of what one unit defines and the other uses.  Tiling and
 // layout conventions: the comment at the top of gemm.hip.  Kernels stay in the anonymous namespace of their unit; what crosses
 // a unit lives in namespace yvgemm.
@@ -64,6 +64,7 @@ extern thread_local int g_opt_p8_cus;
 extern thread_local hipEvent_t t_time_start, t_time_stop;   // yv_set_launch_timing (gemm.hip): the next timed launch of this thread
 int launch_p8(GemmArgs& g, hipStream_t st);
 int launch_p9(GemmArgs& g, hipStream_t st, int rows = 0, bool mx = false);
+int persistent_cus();                 // grid of a persistent launch made by this thread (gemm_persistent.hip)
 
 // Launches kern(arg).  Events armed by yv_set_launch_timing on this thread get the timestamps of the kernel's own dispatch packet
 // (no extra barrier packets in the queue, unlike a pair of hipEventRecord calls around the launch) and are cleared: one launch.

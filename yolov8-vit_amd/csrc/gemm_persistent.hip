@@ -444,18 +444,6 @@ int launch_p8_inst(GemmArgs& g, hipStream_t st, int n_cu) {
     return launch_p8_inst2<MF0, MF1, false>(g, st, n_cu);
 }
 
-// grid of a persistent launch: the CU count of the current device (looked up once: the same value from every thread), clipped
-// by the calling thread's "linear_p8_cus"; 0: the device query failed
-int persistent_cus() {
-    static int n_cu_dev = 0;
-    if (!n_cu_dev) {
-        int dev = 0; hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 0;
-        n_cu_dev = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    }
-    return (g_opt_p8_cus > 0 && g_opt_p8_cus < n_cu_dev) ? g_opt_p8_cus : n_cu_dev;
-}
-
 // ---------------------------------------------------------------------------------------------
 // gemm_p9_kernel (round 3): the persistent tile walk, LDS map and LDS-DMA addressing of gemm_p8_kernel with a FREE-RUNNING main
 // loop.  What the per-segment stamps of the DIAG build showed for gemm_p8_kernel (tools/gemm_lab.hip): a phase costs
@@ -1005,6 +993,18 @@ int launch_p9_rows(GemmArgs& g, hipStream_t st, int n_cu, int rows) {
 }
 
 }  // namespace
+
+// grid of a persistent launch: the CU count of the current device (looked up once: the same value from every thread), clipped
+// by the calling thread's "linear_p8_cus"; 0: the device query failed
+int yvgemm::persistent_cus() {
+    static int n_cu_dev = 0;
+    if (!n_cu_dev) {
+        int dev = 0; hipDeviceProp_t prop;
+        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 0;
+        n_cu_dev = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    }
+    return (g_opt_p8_cus > 0 && g_opt_p8_cus < n_cu_dev) ? g_opt_p8_cus : n_cu_dev;
+}
 
 int yvgemm::launch_p8(GemmArgs& g, hipStream_t st) {
     const int n_cu = persistent_cus();

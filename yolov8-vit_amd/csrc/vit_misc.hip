@@ -5,6 +5,9 @@
 //                    (utils/utils.py:64-72, utils/trainClass.py:112)
 // LayerNorm is HBM-bound (4 B read + 2 B written per element): one wave per row, the
 // row lives in registers (two-pass mean / variance in f32), 16-byte loads, 8-byte stores.
+// layernorm_kernel's summation order (lane l adds float4 chunks l, l + 64, ... as (x + y) + (z + w), then wave_sum's xor butterfly)
+// is a contract: gemm_res_ln_kernel (gemm_res_ln.hip) reproduces it so that the fused and the unfused classifier agree bit for bit
+// (tests/test_gpu_fused_ln.py::test_linear_res_ln_random).  Change the two together.
 #include "yv_common.h"
 
 namespace {

@@ -119,6 +119,7 @@ _SIGS = {
                           _i, _vp, _sz, _vp]),
     "yv_linear": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _i, _vp, _i, _vp]),
     "yv_layernorm": (_i, [_vp, _sz, _vp, _vp, _i, _i, _f, _vp, _sz, _vp, _i, _vp]),
+    "yv_linear_res_ln": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _f, _vp, _i, _vp, _i, _vp]),
     "yv_attention": (_i, [_vp, _i, _i, _i, _f, _vp, _vp, _vp]),
     "yv_attention_cls": (_i, [_vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp]),
     "yv_attention_debug": (_i, [_i]),
@@ -588,6 +589,35 @@ def linear(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], out: 
         lib.yv_set_launch_timing(None, None)             # not consumed when the call took a non-DMA kernel path
         hook(Mr, N, K, e0, e1)
     return out
+
+
+RES_LN_WIDTHS = (128, 768, 1024)          # output widths yv_linear_res_ln has an instance for (a tile spans the row)
+
+
+def linear_res_ln(a: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, x: torch.Tensor, gamma: torch.Tensor,
+                  beta: torch.Tensor, h: torch.Tensor, eps: float = 1e-6, m_dev: Optional[torch.Tensor] = None, m_mul: int = 1,
+                  M: Optional[int] = None):
+    """x[M,N] (f32) += a[M,K] @ w[N,K]^T + bias and h[M,N] (bf16) = LayerNorm(x; gamma, beta, eps) in one launch."""
+    _chk_dev(w, bias, gamma, beta, m_dev)
+    for t in (a, x, h):                      # row-strided 2-D views are operands as they are
+        if not t.is_cuda or t.dim() != 2 or t.stride(1) != 1:
+            raise YvError("expected a device matrix with unit column stride")
+    Mr = a.shape[0] if M is None else M
+    K = a.shape[1]
+    N = w.shape[0]
+    assert w.shape[1] == K and a.dtype == torch.bfloat16 and w.dtype == torch.bfloat16
+    assert x.dtype == torch.float32 and h.dtype == torch.bfloat16 and x.shape[1] == N and h.shape[1] == N
+    assert bias.dtype == gamma.dtype == beta.dtype == torch.float32 and bias.numel() == gamma.numel() == beta.numel() == N
+    hook = LINEAR_HOOK
+    if hook is not None:                     # bench.py: HIP events attached to the launch itself (hipExtLaunchKernel)
+        e0, e1 = _timing_event(), _timing_event()
+        check(lib.yv_set_launch_timing(e0.handle, e1.handle), "yv_set_launch_timing")
+    check(lib.yv_linear_res_ln(_p(a), a.stride(0), _p(w), _p(bias), Mr, N, K, _p(x), x.stride(0), _p(gamma), _p(beta),
+                               float(eps), _p(h), h.stride(0), _p(m_dev), m_mul, _st()), "yv_linear_res_ln")
+    if hook is not None:
+        lib.yv_set_launch_timing(None, None)
+        hook(Mr, N, K, e0, e1)
+    return x, h
 
 
 _CONV_WS = {}

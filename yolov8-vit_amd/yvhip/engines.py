@@ -21,7 +21,7 @@ import torch
 from .guard import StepGuard
 from . import (set_option, get_option, EPI_GELU, EPI_OUT_F32, EPI_POSEMB, EPI_RES_BF16, EPI_RES_F32, EPI_SILU, YvError, attention, attention_cls, attention_mxfp8,
                cls_rows,
-               c2f_fused, conv2d, conv2d_mxfp8, detect_decode, mx_map, mx_view, quant_conv_weight_mxfp8, quant_mxfp8_map, detect_tail, layernorm, layernorm_mxfp8, linear, linear_mxfp8, linear_mxfp8_q, quant_mxfp8, require_gpu, sppf_pool, stem_conv, view,
+               c2f_fused, conv2d, conv2d_mxfp8, detect_decode, mx_map, mx_view, quant_conv_weight_mxfp8, quant_mxfp8_map, detect_tail, layernorm, layernorm_mxfp8, linear, linear_mxfp8, linear_res_ln, RES_LN_WIDTHS, linear_mxfp8_q, quant_mxfp8, require_gpu, sppf_pool, stem_conv, view,
                wrapper_head)
 
 # --------------------------------------------------------------------------------------- YOLOv8
@@ -548,22 +548,33 @@ class VitEngine:
     through the Network_Wrapper head, class logits (cap, nc) + labels (cap)."""
 
     def __init__(self, state: Dict[str, torch.Tensor], name: str, num_classes: int = 5, img: int = 224,
-                 device: str = "cuda:0", dtype: str = "bf16", cls_tail: bool = True):
+                 device: str = "cuda:0", dtype: str = "bf16", cls_tail: bool = True, fused_ln: Optional[bool] = None):
         """cls_tail (bf16 path): the last block runs on the cls rows only - nothing reads its other rows (see _last_block_cls);
         False gives the full last block.
         dtype "bf16" (default) or "mxfp8": the four block linears (qkv, proj, fc1, fc2) then run on OCP e4m3 operands
         with one E8M0 scale per 32 K elements through the block-scaled MFMA (BASELINE.json configs[4]); weights are
         quantised once here, activations by yv_quant_mxfp8 in front of each GEMM; everything else (patch-embed, LayerNorm,
-        attention, residual stream, heads) keeps its bf16 / f32 form."""
+        attention, residual stream, heads) keeps its bf16 / f32 form.
+        fused_ln (bf16 path, opt-in): proj and fc2 run as linear_res_ln, which also writes the LayerNorm their result feeds (the
+        block's norm2 / the next block's norm1), so the separate LayerNorm passes over the residual stream go away - see
+        _backbone_pass.  None reads the environment variable YV_VIT_FUSED_LN ("1" = on, unset = off; a bf16 engine only, the
+        mxfp8 engine ignores the variable).  True with dtype "mxfp8" or an embedding width yv_linear_res_ln lacks: YvError."""
         require_gpu()
         if dtype not in ("bf16", "mxfp8"):
             raise YvError("dtype must be 'bf16' or 'mxfp8'")
         self.dtype = dtype
         self.cls_tail = bool(cls_tail)
+        if fused_ln is None:
+            fused_ln = dtype == "bf16" and os.environ.get("YV_VIT_FUSED_LN", "0") == "1"
+        self.fused_ln = bool(fused_ln)
+        if self.fused_ln and dtype != "bf16":
+            raise YvError("fused_ln is a property of the bf16 path (dtype='mxfp8' hands LayerNorm outputs over in MXFP8)")
         self.fuse_attention_quant = os.environ.get("YV_MX_ATTN_FUSED", "1") == "1"     # A/B switch of the mxfp8 path
         self.P, self.D, self.L, self.H = vit_cfg(name)
         if self.D // self.H != 64:
             raise YvError("attention kernel is specialised for head dim 64")
+        if self.fused_ln and self.D not in RES_LN_WIDTHS:
+            raise YvError(f"fused_ln: yv_linear_res_ln has no instance for width {self.D} (has {RES_LN_WIDTHS})")
         self.name, self.nc, self.img, self.dev = name, num_classes, img, torch.device(device)
         self.tok = (img // self.P) ** 2
         self.N = self.tok + 1
@@ -672,33 +683,46 @@ class VitEngine:
         rows = cap * N
         if self.dtype == "mxfp8":
             return self._backbone_mxfp8(b, cap, count)
+        # fused_ln: every proj also writes its block's norm2 output and every fc2 (but the last block's) the NEXT block's norm1 output
+        # (linear_res_ln), so of the 2L block LayerNorms only block 0's norm1 - its input comes from patch-embed + cls_rows - remains
+        fused = self.fused_ln
         for i, blk in enumerate(self.blocks):
             if self.full_cus_from is not None and i == self.full_cus_from:
                 set_option("linear_p8_cus", 0)          # the caller (PipelinedRunner) restores its own setting after the pass
             if self.cls_tail and i == self.L - 1:
-                self._last_block_cls(b, blk, cap, count)
+                self._last_block_cls(b, blk, cap, count, norm1_done=fused and i > 0)
                 break
-            layernorm(x, blk["n1w"], blk["n1b"], h, rows, D, D, D, count_dev=count, rows_per_count=N)
+            if not (fused and i > 0):
+                layernorm(x, blk["n1w"], blk["n1b"], h, rows, D, D, D, count_dev=count, rows_per_count=N)
             linear(h, blk["wqkv"], blk["bqkv"], qkv, m_dev=count, m_mul=N)
             attention(qkv, cap, N, H, o, r_dev=count)
-            linear(o, blk["wproj"], blk["bproj"], x, flags=EPI_RES_F32, m_dev=count, m_mul=N)
-            layernorm(x, blk["n2w"], blk["n2b"], h, rows, D, D, D, count_dev=count, rows_per_count=N)
+            if fused:
+                linear_res_ln(o, blk["wproj"], blk["bproj"], x, blk["n2w"], blk["n2b"], h, m_dev=count, m_mul=N)
+            else:
+                linear(o, blk["wproj"], blk["bproj"], x, flags=EPI_RES_F32, m_dev=count, m_mul=N)
+                layernorm(x, blk["n2w"], blk["n2b"], h, rows, D, D, D, count_dev=count, rows_per_count=N)
             linear(h, blk["wfc1"], blk["bfc1"], gbuf, flags=EPI_GELU, m_dev=count, m_mul=N)
-            linear(gbuf, blk["wfc2"], blk["bfc2"], x, flags=EPI_RES_F32, m_dev=count, m_mul=N)
+            if fused and i + 1 < self.L:
+                nxt = self.blocks[i + 1]
+                linear_res_ln(gbuf, blk["wfc2"], blk["bfc2"], x, nxt["n1w"], nxt["n1b"], h, m_dev=count, m_mul=N)
+            else:
+                linear(gbuf, blk["wfc2"], blk["bfc2"], x, flags=EPI_RES_F32, m_dev=count, m_mul=N)
         layernorm(x, self.nw, self.nb, b["c"], cap, D, N * D, D, count_dev=count, rows_per_count=1)
         linear(b["c"], self.w_head, self.b_head, b["feats"], flags=EPI_OUT_F32, m_dev=count, m_mul=1)
         return b["feats"]
 
-    def _last_block_cls(self, b: dict, blk: dict, cap: int, count: Optional[torch.Tensor]):
+    def _last_block_cls(self, b: dict, blk: dict, cap: int, count: Optional[torch.Tensor], norm1_done: bool = False):
         """The last block on the cls rows.  The final LayerNorm and the head read row 0 of each crop only, and inside a block token
         rows meet only in attention, through K and V: so K | V are computed for every row, and the query, the attention, proj, LN2,
-        fc1 and fc2 for the `cap` cls rows.  Only the cls rows of x are updated; the operands in between are compact (cap, *)."""
+        fc1 and fc2 for the `cap` cls rows.  Only the cls rows of x are updated; the operands in between are compact (cap, *).
+        norm1_done (fused_ln): the previous block's fc2 launch already wrote this block's norm1 output into h."""
         D, N, H = self.D, self.N, self.H
         x, h, qkv = b["x"], b["h"], b["qkv"]
         if "xc" not in b:                                                   # views, made once per buffer set
             b["xc"], b["hc"], b["kv"] = x[::N], h[::N], qkv[:, D:]          # cls rows (row stride N * D); the K | V columns
         xc = b["xc"]
-        layernorm(x, blk["n1w"], blk["n1b"], h, cap * N, D, D, D, count_dev=count, rows_per_count=N)
+        if not norm1_done:
+            layernorm(x, blk["n1w"], blk["n1b"], h, cap * N, D, D, D, count_dev=count, rows_per_count=N)
         linear(h, blk["wkv"], blk["bkv"], b["kv"], m_dev=count, m_mul=N)
         linear(b["hc"], blk["wq"], blk["bq"], b["tq"], m_dev=count, m_mul=1)
         attention_cls(b["tq"], qkv, cap, N, H, b["to"], r_dev=count)
