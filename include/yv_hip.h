@@ -407,6 +407,22 @@ int yv_attention(const void* qkv, int R, int N, int H, float scale, void* out, c
 int yv_attention_cls(const void* q, const void* qkv, int R, int N, int H, float scale, void* out, const int32_t* r_dev,
                      void* stream);
 
+/* Attention forward for sequences longer than one K/V tile (ViT-B/8 at 224: 785 tokens; ViT-x/16 at 384: 577); the same product
+ * as yv_attention from another kernel: 128-row query blocks whose last one has only its live 32-row waves, 64-key K/V tiles
+ * double-buffered in LDS with the next tile's fetch under the current tile's work, an online softmax per 32-key group, key groups
+ * wholly past N skipped.  Any N >= 1 is accepted; the engines use it for N > 224 (VitEngine / VitTrainer long_attn).
+ * qkv (R*N, 3*H*64) bf16.  Outputs, any combination with at least one of out / out_q:
+ *   out (R*N, H*64) bf16, or NULL;
+ *   lse (R, H, N) f32, log2 domain (m * scale * log2 e + log2 l: the input of yv_attention_bwd), or NULL;
+ *   out_q / out_scales: the MXFP8 operand image of yv_attention_mxfp8 (same numbers as out followed by yv_quant_mxfp8), both or
+ *   neither (NULL, 0, NULL, 0): H even, ldq % 16 == 0, ldq >= 64 H, rows_pad % 128 == 0, rows_pad >= R*N;
+ *   r_dev: device-side crop count, or NULL; crops >= min(r_dev[0], R) are not touched.
+ * qkv, out, out_q 16-byte aligned; breaking a rule is YV_ERR_ARG, a grid past 2^31 - 1 workgroups YV_ERR_LIMIT; R = 0 is YV_OK
+ * without a launch.  Addresses are 64-bit: no 2 GB limit.  A crop's outputs depend on that crop's inputs only: bit-identical
+ * whatever R, the crop's index and the grid. */
+int yv_attention_long(const void* qkv, int R, int N, int H, float scale, void* out, const int32_t* r_dev, float* lse,
+                      void* out_q, long long ldq, void* out_scales, long long rows_pad, void* stream);
+
 /* Diagnostic builds of the attention kernel (0 = normal; 1 no K/V loads, 2 no compute, 3 no V^T writes). */
 int yv_attention_debug(int ablate);
 

@@ -122,6 +122,7 @@ _SIGS = {
     "yv_linear_res_ln": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _f, _vp, _i, _vp, _i, _vp]),
     "yv_attention": (_i, [_vp, _i, _i, _i, _f, _vp, _vp, _vp]),
     "yv_attention_cls": (_i, [_vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp]),
+    "yv_attention_long": (_i, [_vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp, C.c_longlong, _vp, C.c_longlong, _vp]),
     "yv_attention_debug": (_i, [_i]),
     "yv_cls_rows": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
     "yv_wrapper_head": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _f, _i, _vp, _vp, _vp, _vp]),
@@ -678,6 +679,21 @@ def attention(qkv: torch.Tensor, R: int, N: int, H: int, out: torch.Tensor, scal
     _chk_dev(qkv, out, r_dev)
     check(lib.yv_attention(_p(qkv), R, N, H, float(64 ** -0.5 if scale is None else scale), _p(out), _p(r_dev),
                            _st()), "yv_attention")
+    return out
+
+
+def attention_long(qkv: torch.Tensor, R: int, N: int, H: int, out: Optional[torch.Tensor] = None, scale: Optional[float] = None,
+                   r_dev: Optional[torch.Tensor] = None, lse: Optional[torch.Tensor] = None,
+                   out_q: Optional[torch.Tensor] = None, out_scale: Optional[torch.Tensor] = None):
+    """The attention forward for sequences longer than one K/V tile (yv_attention_long; any N >= 1 is accepted).  Outputs, any
+    combination with at least one of out / out_q: out (R*N, H*64) bf16; lse (R, H, N) f32 for attention_bwd; out_q / out_scale,
+    the MXFP8 operand image of attention_mxfp8 (bytes (rows, >= H*64) + scales (H*64 // 128, rows_pad, 4)); r_dev: crop count."""
+    _chk_dev(qkv, out, r_dev, lse, out_q, out_scale)
+    if (out_q is None) != (out_scale is None):
+        raise YvError("attention_long: out_q and out_scale come together")
+    check(lib.yv_attention_long(_p(qkv), R, N, H, float(64 ** -0.5 if scale is None else scale), _p(out), _p(r_dev), _p(lse),
+                                _p(out_q), 0 if out_q is None else out_q.stride(0), _p(out_scale),
+                                0 if out_scale is None else out_scale.shape[1], _st()), "yv_attention_long")
     return out
 
 

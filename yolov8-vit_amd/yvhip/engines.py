@@ -19,7 +19,7 @@ from typing import Dict, List, Optional, Tuple
 import torch
 
 from .guard import StepGuard
-from . import (set_option, get_option, EPI_GELU, EPI_OUT_F32, EPI_POSEMB, EPI_RES_BF16, EPI_RES_F32, EPI_SILU, YvError, attention, attention_cls, attention_mxfp8,
+from . import (set_option, get_option, EPI_GELU, EPI_OUT_F32, EPI_POSEMB, EPI_RES_BF16, EPI_RES_F32, EPI_SILU, YvError, attention, attention_cls, attention_long, attention_mxfp8,
                cls_rows,
                c2f_fused, conv2d, conv2d_mxfp8, detect_decode, mx_map, mx_view, quant_conv_weight_mxfp8, quant_mxfp8_map, detect_tail, layernorm, layernorm_mxfp8, linear, linear_mxfp8, linear_res_ln, RES_LN_WIDTHS, linear_mxfp8_q, quant_mxfp8, require_gpu, sppf_pool, stem_conv, view,
                wrapper_head)
@@ -547,8 +547,11 @@ class VitEngine:
     """Patch-major bf16 crops (cap*tok, 3*P*P) -> backbone logits (cap, 1024-padded) f32 and,
     through the Network_Wrapper head, class logits (cap, nc) + labels (cap)."""
 
+    long_attn = False                                   # opt-in (see __init__)
+
     def __init__(self, state: Dict[str, torch.Tensor], name: str, num_classes: int = 5, img: int = 224,
-                 device: str = "cuda:0", dtype: str = "bf16", cls_tail: bool = True, fused_ln: Optional[bool] = None):
+                 device: str = "cuda:0", dtype: str = "bf16", cls_tail: bool = True, fused_ln: Optional[bool] = None,
+                 long_attn: Optional[bool] = None):
         """cls_tail (bf16 path): the last block runs on the cls rows only - nothing reads its other rows (see _last_block_cls);
         False gives the full last block.
         dtype "bf16" (default) or "mxfp8": the four block linears (qkv, proj, fc1, fc2) then run on OCP e4m3 operands
@@ -558,7 +561,12 @@ class VitEngine:
         fused_ln (bf16 path, opt-in): proj and fc2 run as linear_res_ln, which also writes the LayerNorm their result feeds (the
         block's norm2 / the next block's norm1), so the separate LayerNorm passes over the residual stream go away - see
         _backbone_pass.  None reads the environment variable YV_VIT_FUSED_LN ("1" = on, unset = off; a bf16 engine only, the
-        mxfp8 engine ignores the variable).  True with dtype "mxfp8" or an embedding width yv_linear_res_ln lacks: YvError."""
+        mxfp8 engine ignores the variable).  True with dtype "mxfp8" or an embedding width yv_linear_res_ln lacks: YvError.
+        long_attn (both dtypes, opt-in): the full blocks' attention runs as attention_long (128-row query blocks, pipelined 64-key
+        tiles; dtype "mxfp8": writing the proj operand directly) in place of attention / attention_mxfp8.  Effective only where the
+        engine's token count exceeds 224 (/8 models at 224, /16 models at 384): a shorter-sequence engine accepts the flag and
+        keeps calling attention, whose single-tile kernel is the tuned one there.  attention_cls of the cls tail is unchanged.
+        None reads the environment variable YV_VIT_LONG_ATTN ("1" = on, unset = off).  Works together with fused_ln and cls_tail."""
         require_gpu()
         if dtype not in ("bf16", "mxfp8"):
             raise YvError("dtype must be 'bf16' or 'mxfp8'")
@@ -569,6 +577,9 @@ class VitEngine:
         self.fused_ln = bool(fused_ln)
         if self.fused_ln and dtype != "bf16":
             raise YvError("fused_ln is a property of the bf16 path (dtype='mxfp8' hands LayerNorm outputs over in MXFP8)")
+        if long_attn is None:
+            long_attn = os.environ.get("YV_VIT_LONG_ATTN", "0") == "1"
+        self.long_attn = bool(long_attn)
         self.fuse_attention_quant = os.environ.get("YV_MX_ATTN_FUSED", "1") == "1"     # A/B switch of the mxfp8 path
         self.P, self.D, self.L, self.H = vit_cfg(name)
         if self.D // self.H != 64:
@@ -695,7 +706,10 @@ class VitEngine:
             if not (fused and i > 0):
                 layernorm(x, blk["n1w"], blk["n1b"], h, rows, D, D, D, count_dev=count, rows_per_count=N)
             linear(h, blk["wqkv"], blk["bqkv"], qkv, m_dev=count, m_mul=N)
-            attention(qkv, cap, N, H, o, r_dev=count)
+            if self.long_attn and N > 224:
+                attention_long(qkv, cap, N, H, o, r_dev=count)
+            else:
+                attention(qkv, cap, N, H, o, r_dev=count)
             if fused:
                 linear_res_ln(o, blk["wproj"], blk["bproj"], x, blk["n2w"], blk["n2b"], h, m_dev=count, m_mul=N)
             else:
@@ -742,10 +756,12 @@ class VitEngine:
         for blk in self.blocks:
             layernorm_mxfp8(x, blk["n1w"], blk["n1b"], hq, hs, rows, D, D, count_dev=count, rows_per_count=N)
             linear_mxfp8(hq, hs, blk["wqkv_q"], blk["wqkv_s"], blk["bqkv"], qkv, m_dev=count, m_mul=N)
-            if H % 2 == 0 and self.fuse_attention_quant:
+            if self.long_attn and N > 224 and H % 2 == 0:
+                attention_long(qkv, cap, N, H, r_dev=count, out_q=hq, out_scale=hs)      # the proj operand, as attention_mxfp8
+            elif H % 2 == 0 and self.fuse_attention_quant:
                 attention_mxfp8(qkv, cap, N, H, hq, hs, r_dev=count)          # attention writes the proj operand directly
             else:
-                attention(qkv, cap, N, H, o, r_dev=count)
+                (attention_long if self.long_attn and N > 224 else attention)(qkv, cap, N, H, o, r_dev=count)
                 quant_mxfp8(o, hq, hs)
             linear_mxfp8(hq, hs, blk["wproj_q"], blk["wproj_s"], blk["bproj"], x, flags=EPI_RES_F32, m_dev=count, m_mul=N)
             layernorm_mxfp8(x, blk["n2w"], blk["n2b"], hq, hs, rows, D, D, count_dev=count, rows_per_count=N)

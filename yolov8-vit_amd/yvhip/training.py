@@ -24,12 +24,13 @@ the all-reduce keep their bf16 / f32 form; the structure of forward, backward an
 """
 from __future__ import annotations
 
+import os
 from typing import Dict, List, Optional
 
 import torch
 
 from . import (EPI_GELU, EPI_GELU_BWD, EPI_OUT_F32, EPI_POSEMB, EPI_RES_F32, EPI_SAVE_PRE, YvError, attention_bwd,
-               attention_train, cast_colsum, cls_rows, colsum_bf16, head_bwd, layernorm, layernorm_bwd, lib,
+               attention_long, attention_train, cast_colsum, cls_rows, colsum_bf16, head_bwd, layernorm, layernorm_bwd, lib,
                linear, linear_ex, linear_mxfp8_ex, linear_nn, loss_fwd_bwd, quant_mxfp8_2d, r128, require_gpu, sgd_step,
                token_reduce, transpose_bf16_batched, wgrad, wgrad_mxfp8, wrapper_head)
 from .engines import vit_cfg
@@ -54,7 +55,13 @@ def check_train_dtype(dtype: str, D: int):
 class VitTrainer:
     def __init__(self, state: Dict[str, torch.Tensor], name: str, num_classes: int = 5, img: int = 224,
                  device: str = "cuda:0", momentum: float = 0.9, weight_decay: float = 1e-3,
-                 bucket_mb: float = 32.0, dtype: str = "bf16"):
+                 bucket_mb: float = 32.0, dtype: str = "bf16", long_attn: Optional[bool] = None):
+        """long_attn (opt-in, both dtypes): the forward attention runs as attention_long(..., lse=...) in place of attention_train
+        where the token count exceeds 224 (a shorter-sequence trainer accepts the flag and keeps attention_train); attention_bwd
+        is the same and consumes that lse.  None reads the environment variable YV_VIT_LONG_ATTN ("1" = on, unset = off)."""
+        if long_attn is None:
+            long_attn = os.environ.get("YV_VIT_LONG_ATTN", "0") == "1"
+        self.long_attn = bool(long_attn)
         self.P_, self.D, self.L, self.H = vit_cfg(name)
         check_train_dtype(dtype, self.D)
         require_gpu()
@@ -237,7 +244,7 @@ class VitTrainer:
                 continue
             layernorm(xin, self.p(k + "norm1.weight"), self.p(k + "norm1.bias"), b["h1"][i], M, D, D, D)
             linear(b["h1"][i], W(k + "attn.qkv.weight"), self.p(k + "attn.qkv.bias"), b["qkv"][i])
-            attention_train(b["qkv"][i], R, N, H, b["o"][i], b["lse"][i])
+            self._attention_fwd(b, i, R)
             linear_ex(b["o"][i], W(k + "attn.proj.weight"), self.p(k + "attn.proj.bias"), xmid, flags=EPI_RES_F32, res_f32=xin)
             layernorm(xmid, self.p(k + "norm2.weight"), self.p(k + "norm2.bias"), b["h2"][i], M, D, D, D)
             linear_ex(b["h2"][i], W(k + "mlp.fc1.weight"), self.p(k + "mlp.fc1.bias"), b["g"][i],
@@ -251,6 +258,13 @@ class VitTrainer:
         wrapper_head(b["feats"], w1t, self.p("fc.1.bias"), self.p("fc.3.weight"), self.p("fc.3.bias"), R, self.nc,
                      b["logits"], b["labels"])
         return b["logits"]
+
+    def _attention_fwd(self, b: dict, i: int, R: int):
+        """Block i's attention forward with the log2-sum-exp the backward needs."""
+        if self.long_attn and self.N > 224:
+            attention_long(b["qkv"][i], R, self.N, self.H, b["o"][i], lse=b["lse"][i])
+        else:
+            attention_train(b["qkv"][i], R, self.N, self.H, b["o"][i], b["lse"][i])
 
     # ---- MXFP8 block linears (dtype="mxfp8") -------------------------------------------------------------
     def _quant(self, b: dict, x: torch.Tensor, col: Optional[tuple]):
@@ -271,7 +285,7 @@ class VitTrainer:
         X = b["xc"][i]                                       # column forms kept for the block's weight gradients
         layernorm(xin, self.p(k + "norm1.weight"), self.p(k + "norm1.bias"), b["h1"][i], M, D, D, D)
         self._mx_linear(k + "attn.qkv.weight", self._quant(b, b["h1"][i], X["h1"]), self.p(k + "attn.qkv.bias"), b["qkv"][i])
-        attention_train(b["qkv"][i], R, N, H, b["o"][i], b["lse"][i])
+        self._attention_fwd(b, i, R)
         self._mx_linear(k + "attn.proj.weight", self._quant(b, b["o"][i], X["o"]), self.p(k + "attn.proj.bias"), xmid,
                         flags=EPI_RES_F32, res_f32=xin)
         layernorm(xmid, self.p(k + "norm2.weight"), self.p(k + "norm2.bias"), b["h2"][i], M, D, D, D)
