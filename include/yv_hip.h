@@ -457,6 +457,20 @@ int yv_attention_train(const void* qkv, int R, int N, int H, float scale, void* 
 int yv_attention_bwd(const void* qkv, const void* out, const void* dout, const float* lse, int R, int N, int H,
                      float scale, void* dqkv, float* delta_ws, void* stream);
 
+/* Attention backward for sequences longer than one tile (785 / 577 tokens); the same two kernels and the same arithmetic as
+ * yv_attention_bwd with the blocking and staging of yv_attention_long: 128-row owner blocks whose last one has only its live
+ * 32-row waves, the other axis walked in 64-row tiles double-buffered in LDS with the next tile's fetch under the current tile's
+ * work, groups wholly past N skipped, K^T / Q^T / dO^T read with transposing LDS reads from the row-major tile image.  Any
+ * N >= 1 is accepted; VitTrainer(long_attn_bwd=True) uses it for N > 224.
+ * Operands as yv_attention_bwd: qkv, dqkv (R*N, 3*H*64) bf16; out, dout (R*N, H*64) bf16; lse (R, H, N) f32, log2 domain, from
+ * yv_attention_train or yv_attention_long; delta_ws: R*H*N floats of scratch.  dqkv and delta_ws are bit-identical to
+ * yv_attention_bwd on finite inputs, for every N; rows of dqkv past R*N and floats of delta_ws past R*H*N are never written.
+ * qkv, out, dout, dqkv 16-byte aligned; a NULL pointer (but stream), R < 0, N <= 0, H <= 0 or a misaligned pointer is
+ * YV_ERR_ARG, a grid past 2^31 - 1 workgroups YV_ERR_LIMIT; R = 0 is YV_OK without a launch.  Addresses are 64-bit: no 2 GB
+ * limit.  A crop's gradients depend on that crop's inputs only: bit-identical whatever R, the crop's index and the grid. */
+int yv_attention_bwd_long(const void* qkv, const void* out, const void* dout, const float* lse, int R, int N, int H,
+                          float scale, void* dqkv, float* delta_ws, void* stream);
+
 /* out[M,N] (bf16) = A[M,K] . Wkn[K,N] with the weight in reduction-major layout (row stride ldw): the data
  * gradient dX = dY . W reads the (N_w, K_w) weight as it is stored, through transposing LDS reads (no W^T copy).
  * flags: YV_EPI_BIAS, YV_EPI_GELU_BWD (aux = saved pre-activation). */

@@ -131,6 +131,7 @@ _SIGS = {
     "yv_linear_ex": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _i, _vp]),
     "yv_attention_train": (_i, [_vp, _i, _i, _i, _f, _vp, _vp, _vp]),
     "yv_attention_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp]),
+    "yv_attention_bwd_long": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp]),
     "yv_linear_nn": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _i, _i, _vp, _i, _vp]),
     "yv_wgrad": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp]),
     "yv_wgrad_conv3": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp]),
@@ -752,6 +753,13 @@ def attention_train(qkv, R, N, H, out, lse, scale=None):
 def attention_bwd(qkv, out, dout, lse, R, N, H, dqkv, delta_ws, scale=None):
     check(lib.yv_attention_bwd(_p(qkv), _p(out), _p(dout), _p(lse), R, N, H, float(64 ** -0.5 if scale is None else scale),
                                _p(dqkv), _p(delta_ws), _st()), "yv_attention_bwd")
+
+
+def attention_bwd_long(qkv, out, dout, lse, R, N, H, dqkv, delta_ws, scale=None):
+    """attention_bwd for sequences longer than one tile (yv_attention_bwd_long; any N >= 1 is accepted): the same operands and,
+    on finite inputs, the same bits in dqkv and delta_ws."""
+    check(lib.yv_attention_bwd_long(_p(qkv), _p(out), _p(dout), _p(lse), R, N, H, float(64 ** -0.5 if scale is None else scale),
+                                    _p(dqkv), _p(delta_ws), _st()), "yv_attention_bwd_long")
 
 
 def transpose_bf16(x: torch.Tensor, out_t: torch.Tensor, rows: Optional[int] = None):

@@ -30,8 +30,8 @@ from typing import Dict, List, Optional
 import torch
 
 from . import (EPI_GELU, EPI_GELU_BWD, EPI_OUT_F32, EPI_POSEMB, EPI_RES_F32, EPI_SAVE_PRE, YvError, attention_bwd,
-               attention_long, attention_train, cast_colsum, cls_rows, colsum_bf16, head_bwd, layernorm, layernorm_bwd, lib,
-               linear, linear_ex, linear_mxfp8_ex, linear_nn, loss_fwd_bwd, quant_mxfp8_2d, r128, require_gpu, sgd_step,
+               attention_bwd_long, attention_long, attention_train, cast_colsum, cls_rows, colsum_bf16, head_bwd, layernorm,
+               layernorm_bwd, lib, linear, linear_ex, linear_mxfp8_ex, linear_nn, loss_fwd_bwd, quant_mxfp8_2d, r128, require_gpu, sgd_step,
                token_reduce, transpose_bf16_batched, wgrad, wgrad_mxfp8, wrapper_head)
 from .engines import vit_cfg
 
@@ -55,13 +55,21 @@ def check_train_dtype(dtype: str, D: int):
 class VitTrainer:
     def __init__(self, state: Dict[str, torch.Tensor], name: str, num_classes: int = 5, img: int = 224,
                  device: str = "cuda:0", momentum: float = 0.9, weight_decay: float = 1e-3,
-                 bucket_mb: float = 32.0, dtype: str = "bf16", long_attn: Optional[bool] = None):
+                 bucket_mb: float = 32.0, dtype: str = "bf16", long_attn: Optional[bool] = None,
+                 long_attn_bwd: Optional[bool] = None):
         """long_attn (opt-in, both dtypes): the forward attention runs as attention_long(..., lse=...) in place of attention_train
         where the token count exceeds 224 (a shorter-sequence trainer accepts the flag and keeps attention_train); attention_bwd
-        is the same and consumes that lse.  None reads the environment variable YV_VIT_LONG_ATTN ("1" = on, unset = off)."""
+        is the same and consumes that lse.  None reads the environment variable YV_VIT_LONG_ATTN ("1" = on, unset = off).
+
+        long_attn_bwd (opt-in, both dtypes, independent of long_attn): the attention backward runs as attention_bwd_long in place
+        of attention_bwd where the token count exceeds 224 (a shorter-sequence trainer accepts the flag and keeps attention_bwd).
+        Same operands, same bits in every gradient.  None reads YV_VIT_LONG_ATTN_BWD ("1" = on, unset = off)."""
         if long_attn is None:
             long_attn = os.environ.get("YV_VIT_LONG_ATTN", "0") == "1"
         self.long_attn = bool(long_attn)
+        if long_attn_bwd is None:
+            long_attn_bwd = os.environ.get("YV_VIT_LONG_ATTN_BWD", "0") == "1"
+        self.long_attn_bwd = bool(long_attn_bwd)
         self.P_, self.D, self.L, self.H = vit_cfg(name)
         check_train_dtype(dtype, self.D)
         require_gpu()
@@ -266,6 +274,10 @@ class VitTrainer:
         else:
             attention_train(b["qkv"][i], R, self.N, self.H, b["o"][i], b["lse"][i])
 
+    def _attention_bwd(self, *args):
+        """A block's attention backward (operands of attention_bwd): both kernels write the same bits."""
+        (attention_bwd_long if self.long_attn_bwd and self.N > 224 else attention_bwd)(*args)
+
     # ---- MXFP8 block linears (dtype="mxfp8") -------------------------------------------------------------
     def _quant(self, b: dict, x: torch.Tensor, col: Optional[tuple]):
         """bf16 (M, C) operand -> its row form (the shared A operand of width C) and, if `col`, its column form: one read."""
@@ -312,7 +324,7 @@ class VitTrainer:
         # attention branch
         cast_colsum(dx, dxb_proj, self.g(k + "attn.proj.bias"), b["ws"])
         self._mx_linear(k + "attn.proj.weight", self._quant(b, dxb_proj, S["c_proj"]), None, b["dnar"], transposed=True)
-        attention_bwd(b["qkv"][i], b["o"][i], b["dnar"], b["lse"][i], R, N, H, dqkv, b["delta"])
+        self._attention_bwd(b["qkv"][i], b["o"][i], b["dnar"], b["lse"][i], R, N, H, dqkv, b["delta"])
         self._mx_linear(k + "attn.qkv.weight", self._quant(b, dqkv, S["c_qkv"]), None, b["dnar"], transposed=True)
         layernorm_bwd(xin, D, self.p(k + "norm1.weight"), b["dnar"], D, M, D, dx, D,
                       self.g(k + "norm1.weight"), self.g(k + "norm1.bias"), b["ws"])
@@ -384,7 +396,7 @@ class VitTrainer:
             # attention branch
             cast_colsum(dx, dxb_proj, self.g(k + "attn.proj.bias"), b["ws"])
             linear(dxb_proj, self.wt(k + "attn.proj.weight"), None, b["dnar"])
-            attention_bwd(b["qkv"][i], b["o"][i], b["dnar"], b["lse"][i], R, N, H, dqkv, b["delta"])
+            self._attention_bwd(b["qkv"][i], b["o"][i], b["dnar"], b["lse"][i], R, N, H, dqkv, b["delta"])
             linear(dqkv, self.wt(k + "attn.qkv.weight"), None, b["dnar"])
             layernorm_bwd(xin, D, self.p(k + "norm1.weight"), b["dnar"], D, M, D, dx, D,
                           self.g(k + "norm1.weight"), self.g(k + "norm1.bias"), b["ws"])
