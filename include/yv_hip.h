@@ -471,6 +471,29 @@ int yv_attention_bwd(const void* qkv, const void* out, const void* dout, const f
 int yv_attention_bwd_long(const void* qkv, const void* out, const void* dout, const float* lse, int R, int N, int H,
                           float scale, void* dqkv, float* delta_ws, void* stream);
 
+/* yv_attention_cls for the trainer (VitTrainer(cls_tail=True)): attention of the cls query of each crop, with the log2-sum-exp
+ * its backward needs.  One workgroup per (crop, head), a streaming pass over K and V, every reduction in a fixed order.
+ * q: bf16, row r at q + r*ldq elements, H*64 wide (ldq = N*3*H*64 reads the cls rows of the qkv buffer itself, ldq = H*64 a
+ * compact copy); K and V from qkv (R*N, 3*H*64) bf16; out (R, H*64) bf16 compact, bit-identical to yv_attention_cls on the same
+ * operands; lse[r*H + h] = max + log2(sum) f32 in the scaled log2 domain of yv_attention_train, so that
+ * p_n = exp2(q.k_n * scale * log2 e - lse).  There is no device-side row count.
+ * q, qkv, out 16-byte aligned, ldq a multiple of 8 and >= H*64; a NULL pointer (but stream), R < 0, N <= 0, H <= 0 or a broken
+ * alignment rule is YV_ERR_ARG; N > 8192 or a grid past 2^31 - 1 workgroups YV_ERR_LIMIT; R = 0 is YV_OK without a launch.
+ * Addresses are 64-bit. */
+int yv_attention_cls_train(const void* q, long long ldq, const void* qkv, int R, int N, int H, float scale, void* out, float* lse,
+                           void* stream);
+
+/* Backward of yv_attention_cls_train.  q, ldq, qkv as there; dout (R, H*64) bf16 compact; lse from the forward.  In f32, per
+ * (crop r, head h): s_n = q.k_n * scale * log2 e, p_n = exp2(s_n - lse), dp_n = dO.v_n, delta = sum_n p_n dp_n,
+ * ds_n = p_n (dp_n - delta) * scale; dq = sum_n ds_n k_n, dk_n = ds_n q, dv_n = p_n dO.
+ * Writes EVERY element of rows [0, R*N) of dqkv (R*N, 3*H*64) bf16, each rounded once: dk_n and dv_n in the K and V thirds of
+ * row r*N + n, dq in the Q third of row r*N and zeros in the Q third of rows r*N + 1 .. r*N + N - 1.  Nothing past row R*N is
+ * written.  K is read twice and V once (delta is summed from p and dp, not taken from the forward's output).
+ * One workgroup per (crop, head), no atomics, every reduction in a fixed order: a crop's gradients are bit-identical whatever R
+ * and the crop's index.  Argument rules, limits and return codes as yv_attention_cls_train (dout and dqkv 16-byte aligned). */
+int yv_attention_cls_bwd(const void* q, long long ldq, const void* qkv, const void* dout, const float* lse, int R, int N, int H,
+                         float scale, void* dqkv, void* stream);
+
 /* out[M,N] (bf16) = A[M,K] . Wkn[K,N] with the weight in reduction-major layout (row stride ldw): the data
  * gradient dX = dY . W reads the (N_w, K_w) weight as it is stored, through transposing LDS reads (no W^T copy).
  * flags: YV_EPI_BIAS, YV_EPI_GELU_BWD (aux = saved pre-activation). */

@@ -132,6 +132,8 @@ _SIGS = {
     "yv_attention_train": (_i, [_vp, _i, _i, _i, _f, _vp, _vp, _vp]),
     "yv_attention_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp]),
     "yv_attention_bwd_long": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp]),
+    "yv_attention_cls_train": (_i, [_vp, C.c_longlong, _vp, _i, _i, _i, _f, _vp, _vp, _vp]),
+    "yv_attention_cls_bwd": (_i, [_vp, C.c_longlong, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp]),
     "yv_linear_nn": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _i, _i, _vp, _i, _vp]),
     "yv_wgrad": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp]),
     "yv_wgrad_conv3": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp]),
@@ -231,6 +233,14 @@ def _chk_dev(*ts):
                 raise YvError("expected a device tensor")
             if not t.is_contiguous():
                 raise YvError("expected a contiguous tensor")
+
+
+def _chk_rows(t):
+    """A 2-D device operand read with a row stride (t.stride(0)): only its rows must be contiguous."""
+    if not t.is_cuda:
+        raise YvError("expected a device tensor")
+    if t.dim() != 2 or t.stride(1) != 1:
+        raise YvError("expected a 2-D tensor with contiguous rows")
 
 
 # ------------------------------------------------------------------ boxes
@@ -760,6 +770,26 @@ def attention_bwd_long(qkv, out, dout, lse, R, N, H, dqkv, delta_ws, scale=None)
     on finite inputs, the same bits in dqkv and delta_ws."""
     check(lib.yv_attention_bwd_long(_p(qkv), _p(out), _p(dout), _p(lse), R, N, H, float(64 ** -0.5 if scale is None else scale),
                                     _p(dqkv), _p(delta_ws), _st()), "yv_attention_bwd_long")
+
+
+def attention_cls_train(q, qkv, R, N, H, out, lse, scale=None):
+    """attention_cls for the trainer (yv_attention_cls_train): q (R, H*64) bf16 with any row stride (a view of the qkv buffer's
+    cls rows needs no copy), out (R, H*64) bf16 compact with the bits of attention_cls, lse (R*H) f32 in the log2 domain."""
+    _chk_dev(qkv, out, lse)
+    _chk_rows(q)
+    check(lib.yv_attention_cls_train(_p(q), q.stride(0), _p(qkv), R, N, H, float(64 ** -0.5 if scale is None else scale),
+                                     _p(out), _p(lse), _st()), "yv_attention_cls_train")
+    return out
+
+
+def attention_cls_bwd(q, qkv, dout, lse, R, N, H, dqkv, scale=None):
+    """Backward of attention_cls_train (yv_attention_cls_bwd): dout (R, H*64) bf16 compact, lse from the forward; writes every
+    element of rows [0, R*N) of dqkv (R*N, 3*H*64) bf16: dK and dV of every key, dQ in the cls rows and zeros in the others."""
+    _chk_dev(qkv, dout, lse, dqkv)
+    _chk_rows(q)
+    check(lib.yv_attention_cls_bwd(_p(q), q.stride(0), _p(qkv), _p(dout), _p(lse), R, N, H,
+                                   float(64 ** -0.5 if scale is None else scale), _p(dqkv), _st()), "yv_attention_cls_bwd")
+    return dqkv
 
 
 def transpose_bf16(x: torch.Tensor, out_t: torch.Tensor, rows: Optional[int] = None):

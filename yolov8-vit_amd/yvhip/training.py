@@ -30,7 +30,7 @@ from typing import Dict, List, Optional
 import torch
 
 from . import (EPI_GELU, EPI_GELU_BWD, EPI_OUT_F32, EPI_POSEMB, EPI_RES_F32, EPI_SAVE_PRE, YvError, attention_bwd,
-               attention_bwd_long, attention_long, attention_train, cast_colsum, cls_rows, colsum_bf16, head_bwd, layernorm,
+               attention_bwd_long, attention_cls_bwd, attention_cls_train, attention_long, attention_train, cast_colsum, cls_rows, colsum_bf16, head_bwd, layernorm,
                layernorm_bwd, lib, linear, linear_ex, linear_mxfp8_ex, linear_nn, loss_fwd_bwd, quant_mxfp8_2d, r128, require_gpu, sgd_step,
                token_reduce, transpose_bf16_batched, wgrad, wgrad_mxfp8, wrapper_head)
 from .engines import vit_cfg
@@ -56,20 +56,33 @@ class VitTrainer:
     def __init__(self, state: Dict[str, torch.Tensor], name: str, num_classes: int = 5, img: int = 224,
                  device: str = "cuda:0", momentum: float = 0.9, weight_decay: float = 1e-3,
                  bucket_mb: float = 32.0, dtype: str = "bf16", long_attn: Optional[bool] = None,
-                 long_attn_bwd: Optional[bool] = None):
+                 long_attn_bwd: Optional[bool] = None, cls_tail: Optional[bool] = None):
         """long_attn (opt-in, both dtypes): the forward attention runs as attention_long(..., lse=...) in place of attention_train
         where the token count exceeds 224 (a shorter-sequence trainer accepts the flag and keeps attention_train); attention_bwd
         is the same and consumes that lse.  None reads the environment variable YV_VIT_LONG_ATTN ("1" = on, unset = off).
 
         long_attn_bwd (opt-in, both dtypes, independent of long_attn): the attention backward runs as attention_bwd_long in place
         of attention_bwd where the token count exceeds 224 (a shorter-sequence trainer accepts the flag and keeps attention_bwd).
-        Same operands, same bits in every gradient.  None reads YV_VIT_LONG_ATTN_BWD ("1" = on, unset = off)."""
+        Same operands, same bits in every gradient.  None reads YV_VIT_LONG_ATTN_BWD ("1" = on, unset = off).
+
+        cls_tail (opt-in, both dtypes, independent of the two flags above): the last block runs on the cls
+        rows.  Nothing after it reads tokens 1..N-1, so the gradient that enters it is zero on every other row and stays zero down
+        to its attention: LN1 and the qkv product (forward, data gradient, weight gradient) keep every row, the attention is
+        attention_cls_train / attention_cls_bwd (one query per crop; dK and dV for every key), and proj, LN2, fc1, GELU and fc2 with
+        their gradients run on compact (R, *) operands.  Blocks 0..L-2 are untouched.  With dtype="mxfp8" the cls-row products run
+        in bf16 on the bf16 mirror (forward `linear`, data gradients `linear_nn` on the master layout, weight gradients `wgrad`):
+        quantising a 32-row operand buys nothing, so the last block's small products are more precise than the MX ones; its
+        full-row qkv product and that product's two gradients stay MX.  A model of more than 8192 tokens accepts the flag and runs
+        the full block.  None reads YV_VIT_TRAIN_CLS_TAIL ("1" = on, unset = off)."""
         if long_attn is None:
             long_attn = os.environ.get("YV_VIT_LONG_ATTN", "0") == "1"
         self.long_attn = bool(long_attn)
         if long_attn_bwd is None:
             long_attn_bwd = os.environ.get("YV_VIT_LONG_ATTN_BWD", "0") == "1"
         self.long_attn_bwd = bool(long_attn_bwd)
+        if cls_tail is None:
+            cls_tail = os.environ.get("YV_VIT_TRAIN_CLS_TAIL", "0") == "1"
+        self.cls_tail = bool(cls_tail)
         self.P_, self.D, self.L, self.H = vit_cfg(name)
         check_train_dtype(dtype, self.D)
         require_gpu()
@@ -77,6 +90,7 @@ class VitTrainer:
         self.name, self.nc, self.img, self.dev = name, num_classes, img, torch.device(device)
         self.tok = (img // self.P_) ** 2
         self.N = self.tok + 1
+        self._tail = self.cls_tail and self.N <= 8192          # the cls kernels keep one query's scores in LDS
         self.momentum, self.wd = momentum, weight_decay
         self.steps = 0
         # ---- flat fp32 parameter / gradient / momentum buffers --------------------------------
@@ -229,6 +243,12 @@ class VitTrainer:
                      xc=[dict(h1=col(D), o=col(D), h2=col(D), g=col(4 * D)) for _ in range(L)])
             for S in b["dy"]:
                 S.update(c_fc2=col(D), c_wide=col(4 * D), c_proj=col(D), c_qkv=col(3 * D))
+        if self._tail:
+            # the last block's compact cls-row operands; those that feed a weight gradient have Rp rows and a zero tail that nothing
+            # writes.  The three gradient operands are this block's own (only one block uses them): no parity protocol
+            b["tail"] = dict(o=b16(Rp, D), h2=b16(Rp, D), g=b16(Rp, 4 * D), u=b16(R, 4 * D), xmid=f32(R, D), xout=f32(R, D),
+                             lse=f32(R * self.H), q=b["qkv"][L - 1][::N, :D], dxc=f32(R, D), dxb_fc2=b16(Rp, D),
+                             dxb_proj=b16(Rp, D), dwide=b16(Rp, 4 * D), dnar=b16(R, D), do=b16(R, D))
         self._bufs[R] = b
         return b
 
@@ -247,6 +267,9 @@ class VitTrainer:
         for i in range(L):
             k = f"model.blocks.{i}."
             xin, xmid, xout = b["x"][2 * i], b["x"][2 * i + 1], b["x"][2 * i + 2]
+            if i == L - 1 and self._tail:
+                self._tail_forward(b, R, xin)
+                continue
             if self.dtype == "mxfp8":
                 self._block_forward_mx(b, i, xin, xmid, xout)
                 continue
@@ -258,8 +281,10 @@ class VitTrainer:
             linear_ex(b["h2"][i], W(k + "mlp.fc1.weight"), self.p(k + "mlp.fc1.bias"), b["g"][i],
                       flags=EPI_GELU | EPI_SAVE_PRE, aux=b["u"][i])
             linear_ex(b["g"][i], W(k + "mlp.fc2.weight"), self.p(k + "mlp.fc2.bias"), xout, flags=EPI_RES_F32, res_f32=xmid)
-        xf = b["x"][2 * L]
-        layernorm(xf, self.p("model.norm.weight"), self.p("model.norm.bias"), b["c"], R, D, N * D, D)
+        if self._tail:
+            layernorm(b["tail"]["xout"], self.p("model.norm.weight"), self.p("model.norm.bias"), b["c"], R, D, D, D)
+        else:
+            layernorm(b["x"][2 * L], self.p("model.norm.weight"), self.p("model.norm.bias"), b["c"], R, D, N * D, D)
         linear(b["c"], self.w_head_pad, self.b_head_pad, b["feats"], flags=EPI_OUT_F32)
         w1t = self.p("fc.1.weight").t().contiguous()
         b["w1t"] = w1t
@@ -277,6 +302,84 @@ class VitTrainer:
     def _attention_bwd(self, *args):
         """A block's attention backward (operands of attention_bwd): both kernels write the same bits."""
         (attention_bwd_long if self.long_attn_bwd and self.N > 224 else attention_bwd)(*args)
+
+    # ---- the last block on the cls rows (cls_tail=True, both recipes) ---------------------------------------
+    def _tail_forward(self, b: dict, R: int, xin: torch.Tensor):
+        """Block L-1 forward: LN1 and the qkv product over every row (K and V of every token are needed), the rest on the R cls
+        rows.  The residual rows are copied into the f32 output first, so that proj and fc2 use the in-place EPI_RES_F32 form."""
+        D, N, H, L, M = self.D, self.N, self.H, self.L, b["M"]
+        i, T = L - 1, b["tail"]
+        k = f"model.blocks.{i}."
+        W = lambda n: self.gemm_w[k + n][2]
+        layernorm(xin, self.p(k + "norm1.weight"), self.p(k + "norm1.bias"), b["h1"][i], M, D, D, D)
+        if self.dtype == "mxfp8":
+            self._mx_linear(k + "attn.qkv.weight", self._quant(b, b["h1"][i], b["xc"][i]["h1"]), self.p(k + "attn.qkv.bias"),
+                            b["qkv"][i])
+        else:
+            linear(b["h1"][i], W("attn.qkv.weight"), self.p(k + "attn.qkv.bias"), b["qkv"][i])
+        attention_cls_train(T["q"], b["qkv"][i], R, N, H, T["o"][:R], T["lse"])
+        T["xmid"].copy_(xin[::N])
+        linear(T["o"][:R], W("attn.proj.weight"), self.p(k + "attn.proj.bias"), T["xmid"], flags=EPI_RES_F32)
+        layernorm(T["xmid"], self.p(k + "norm2.weight"), self.p(k + "norm2.bias"), T["h2"], R, D, D, D)
+        linear_ex(T["h2"][:R], W("mlp.fc1.weight"), self.p(k + "mlp.fc1.bias"), T["g"][:R], flags=EPI_GELU | EPI_SAVE_PRE,
+                  aux=T["u"])
+        T["xout"].copy_(T["xmid"])
+        linear(T["g"][:R], W("mlp.fc2.weight"), self.p(k + "mlp.fc2.bias"), T["xout"], flags=EPI_RES_F32)
+
+    def _tail_dgrad(self, key: str, dy: torch.Tensor, out: torch.Tensor, flags: int = 0, aux: Optional[torch.Tensor] = None):
+        """out = dy . W on cls rows: bf16 recipe on the transposed mirror, MX recipe (no such mirror) on the master layout."""
+        if self.dtype == "mxfp8":
+            linear_nn(dy, self.gemm_w[key][2], out, flags=flags, aux=aux)
+        elif aux is not None:
+            linear_ex(dy, self.wt(key), None, out, flags=flags, aux=aux)
+        else:
+            linear(dy, self.wt(key), None, out, flags=flags)
+
+    def _tail_backward(self, b: dict, S: dict, main, R: int):
+        """Block L-1 backward.  b["tail"]["dxc"] holds the cls rows of the incoming gradient (every other row is zero): MLP branch,
+        LN2 and proj on the R cls rows, attention_cls_bwd into the block's ordinary dqkv set, then today's full-row tail of the
+        block (qkv data gradient, LN1 backward) and, on the side stream, the bias column sums and the four weight gradients."""
+        D, N, H, L, M = self.D, self.N, self.H, self.L, b["M"]
+        i, T, Rp = L - 1, b["tail"], b["Rp"]
+        k = f"model.blocks.{i}."
+        xin, dx, dxc, dqkv = b["x"][2 * i], b["dx"], T["dxc"], S["dqkv"][:M]
+        dxb_fc2, dxb_proj, dwide = T["dxb_fc2"][:R], T["dxb_proj"][:R], T["dwide"][:R]
+        # MLP branch
+        cast_colsum(dxc, dxb_fc2, self.g(k + "mlp.fc2.bias"), b["ws"])
+        self._tail_dgrad(k + "mlp.fc2.weight", dxb_fc2, dwide, flags=EPI_GELU_BWD, aux=T["u"])
+        self._tail_dgrad(k + "mlp.fc1.weight", dwide, T["dnar"])
+        layernorm_bwd(T["xmid"], D, self.p(k + "norm2.weight"), T["dnar"], D, R, D, dxc, D,
+                      self.g(k + "norm2.weight"), self.g(k + "norm2.bias"), b["ws"])
+        # attention branch: one query per crop; dK and dV for every key, zeros in the other rows' dQ
+        cast_colsum(dxc, dxb_proj, self.g(k + "attn.proj.bias"), b["ws"])
+        self._tail_dgrad(k + "attn.proj.weight", dxb_proj, T["do"])
+        attention_cls_bwd(T["q"], b["qkv"][i], T["do"], T["lse"], R, N, H, dqkv)
+        dx[::N].copy_(dxc)                                     # dx is zero elsewhere (backward zeroes it)
+        if self.dtype == "mxfp8":
+            self._mx_linear(k + "attn.qkv.weight", self._quant(b, dqkv, S["c_qkv"]), None, b["dnar"], transposed=True)
+        else:
+            linear(dqkv, self.wt(k + "attn.qkv.weight"), None, b["dnar"])
+        layernorm_bwd(xin, D, self.p(k + "norm1.weight"), b["dnar"], D, M, D, dx, D,
+                      self.g(k + "norm1.weight"), self.g(k + "norm1.bias"), b["ws"])
+        ev = torch.cuda.Event()
+        ev.record(main)
+        with torch.cuda.stream(self.s_w):
+            self.s_w.wait_event(ev)
+            colsum_bf16(dwide, self.g(k + "mlp.fc1.bias"), b["ws_w"])
+            colsum_bf16(dqkv, self.g(k + "attn.qkv.bias"), b["ws_w"])
+            for w, dy, x in (("mlp.fc2.weight", "dxb_fc2", "g"), ("mlp.fc1.weight", "dwide", "h2"),
+                             ("attn.proj.weight", "dxb_proj", "o")):
+                N_, K_ = self.gemm_w[k + w][0], self.gemm_w[k + w][1]
+                wgrad(T[dy], T[x], self.g(k + w).reshape(N_, K_), T=Rp)
+            if self.dtype == "mxfp8":
+                N_, K_ = self.gemm_w[k + "attn.qkv.weight"][0], self.gemm_w[k + "attn.qkv.weight"][1]
+                X = b["xc"][i]["h1"]
+                wgrad_mxfp8(S["c_qkv"][0], S["c_qkv"][1], X[0], X[1], self.g(k + "attn.qkv.weight").reshape(N_, K_))
+            else:
+                self._wgrad(k + "attn.qkv.weight", S["dqkv"], b["full"]["h1"][i])
+            self._launch_ready_buckets(self.off[k + "norm1.weight"])
+            S["done"] = torch.cuda.Event()
+            S["done"].record(self.s_w)
 
     # ---- MXFP8 block linears (dtype="mxfp8") -------------------------------------------------------------
     def _quant(self, b: dict, x: torch.Tensor, col: Optional[tuple]):
@@ -369,8 +472,13 @@ class VitTrainer:
         self._wgrad("model.head.weight", b["full"]["dfeats"][:, :1000], b["full"]["c"])
         linear_nn(b["dfeats"], self.w_head_pad, b["dc"])
         b["dx"].zero_()
-        layernorm_bwd(b["x"][2 * L], N * D, self.p("model.norm.weight"), b["dc"], D, R, D, b["dx"], N * D,
-                      self.g("model.norm.weight"), self.g("model.norm.bias"), b["ws"])
+        if self._tail:
+            b["tail"]["dxc"].zero_()
+            layernorm_bwd(b["tail"]["xout"], D, self.p("model.norm.weight"), b["dc"], D, R, D, b["tail"]["dxc"], D,
+                          self.g("model.norm.weight"), self.g("model.norm.bias"), b["ws"])
+        else:
+            layernorm_bwd(b["x"][2 * L], N * D, self.p("model.norm.weight"), b["dc"], D, R, D, b["dx"], N * D,
+                          self.g("model.norm.weight"), self.g("model.norm.bias"), b["ws"])
         self._launch_ready_buckets(self.off["model.norm.weight"])
         # ---- transformer blocks, last to first -------------------------------------------------------------
         main = torch.cuda.current_stream()
@@ -383,6 +491,9 @@ class VitTrainer:
             S = b["dy"][i & 1]
             if S["done"] is not None:
                 main.wait_event(S["done"])                     # block i+2's weight gradients have read this set
+            if i == L - 1 and self._tail:
+                self._tail_backward(b, S, main, R)
+                continue
             if self.dtype == "mxfp8":
                 self._block_backward_mx(b, i, S, main, xin, xmid)
                 continue
