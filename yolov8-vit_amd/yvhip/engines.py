@@ -513,6 +513,11 @@ VIT_CFGS = {
 }
 
 
+def _env_flag(value: Optional[bool], var: str) -> bool:
+    """An opt-in constructor flag: the argument where one is given, else the environment variable `var` ("1" = on, unset = off)."""
+    return os.environ.get(var, "0") == "1" if value is None else bool(value)
+
+
 def vit_cfg(name: str):
     base = name.split(".")[0]
     if base not in VIT_CFGS:
@@ -572,14 +577,10 @@ class VitEngine:
             raise YvError("dtype must be 'bf16' or 'mxfp8'")
         self.dtype = dtype
         self.cls_tail = bool(cls_tail)
-        if fused_ln is None:
-            fused_ln = dtype == "bf16" and os.environ.get("YV_VIT_FUSED_LN", "0") == "1"
-        self.fused_ln = bool(fused_ln)
+        self.fused_ln = _env_flag(fused_ln, "YV_VIT_FUSED_LN") and (fused_ln is not None or dtype == "bf16")
         if self.fused_ln and dtype != "bf16":
             raise YvError("fused_ln is a property of the bf16 path (dtype='mxfp8' hands LayerNorm outputs over in MXFP8)")
-        if long_attn is None:
-            long_attn = os.environ.get("YV_VIT_LONG_ATTN", "0") == "1"
-        self.long_attn = bool(long_attn)
+        self.long_attn = _env_flag(long_attn, "YV_VIT_LONG_ATTN")
         self.fuse_attention_quant = os.environ.get("YV_MX_ATTN_FUSED", "1") == "1"     # A/B switch of the mxfp8 path
         self.P, self.D, self.L, self.H = vit_cfg(name)
         if self.D // self.H != 64:

@@ -21,10 +21,16 @@ ONE pass of yv_quant_mxfp8_2d that writes the row form (for the forward / data-g
 weight gradient); the weights are re-quantised from the bf16 mirror after every optimizer step (W row-wise and, from the same
 read, W^T row-wise).  Patch-embed, heads, attention, LayerNorm, GELU, the residual stream, master weights, gradients, SGD and
 the all-reduce keep their bf16 / f32 form; the structure of forward, backward and optimizer step is that of dtype="bf16".
+
+Where the block is written: its op order (LN1, qkv, attention, proj + residual, LN2, fc1 + GELU, fc2 + residual, and the reverse
+chain) stands once per direction in _block_forward / _block_backward and once per direction for the cls-row last block in
+_tail_forward / _tail_backward.  None of the four tests the recipe: _product, _dgrad and _wgrad pick the bf16 or MX form of a
+product, and _side_stream_epilogue is the one copy of the side-stream section (bias column sums, weight gradients, ready buckets,
+the "done" event of the parity protocol).  tests/test_trainer_trace_cpu.py pins the launch order.
 """
 from __future__ import annotations
 
-import os
+import math
 from typing import Dict, List, Optional
 
 import torch
@@ -33,7 +39,7 @@ from . import (EPI_GELU, EPI_GELU_BWD, EPI_OUT_F32, EPI_POSEMB, EPI_RES_F32, EPI
                attention_bwd_long, attention_cls_bwd, attention_cls_train, attention_long, attention_train, cast_colsum, cls_rows, colsum_bf16, head_bwd, layernorm,
                layernorm_bwd, lib, linear, linear_ex, linear_mxfp8_ex, linear_nn, loss_fwd_bwd, quant_mxfp8_2d, r128, require_gpu, sgd_step,
                token_reduce, transpose_bf16_batched, wgrad, wgrad_mxfp8, wrapper_head)
-from .engines import vit_cfg
+from .engines import _env_flag, vit_cfg
 
 
 def _r64(n: int) -> int:
@@ -41,6 +47,9 @@ def _r64(n: int) -> int:
 
 
 BLOCK_LINEARS = ("attn.qkv.weight", "attn.proj.weight", "mlp.fc1.weight", "mlp.fc2.weight")
+# a block's weight gradients in launch order: (weight, gradient operand in the parity set, its MX column form, activation)
+BLOCK_WGRADS = (("mlp.fc2.weight", "dxb_fc2", "c_fc2", "g"), ("mlp.fc1.weight", "dwide", "c_wide", "h2"),
+                ("attn.proj.weight", "dxb_proj", "c_proj", "o"), ("attn.qkv.weight", "dqkv", "c_qkv", "h1"))
 
 
 def check_train_dtype(dtype: str, D: int):
@@ -74,15 +83,9 @@ class VitTrainer:
         quantising a 32-row operand buys nothing, so the last block's small products are more precise than the MX ones; its
         full-row qkv product and that product's two gradients stay MX.  A model of more than 8192 tokens accepts the flag and runs
         the full block.  None reads YV_VIT_TRAIN_CLS_TAIL ("1" = on, unset = off)."""
-        if long_attn is None:
-            long_attn = os.environ.get("YV_VIT_LONG_ATTN", "0") == "1"
-        self.long_attn = bool(long_attn)
-        if long_attn_bwd is None:
-            long_attn_bwd = os.environ.get("YV_VIT_LONG_ATTN_BWD", "0") == "1"
-        self.long_attn_bwd = bool(long_attn_bwd)
-        if cls_tail is None:
-            cls_tail = os.environ.get("YV_VIT_TRAIN_CLS_TAIL", "0") == "1"
-        self.cls_tail = bool(cls_tail)
+        self.long_attn = _env_flag(long_attn, "YV_VIT_LONG_ATTN")
+        self.long_attn_bwd = _env_flag(long_attn_bwd, "YV_VIT_LONG_ATTN_BWD")
+        self.cls_tail = _env_flag(cls_tail, "YV_VIT_TRAIN_CLS_TAIL")
         self.P_, self.D, self.L, self.H = vit_cfg(name)
         check_train_dtype(dtype, self.D)
         require_gpu()
@@ -130,7 +133,7 @@ class VitTrainer:
         self.P16T = torch.zeros(o, dtype=torch.bfloat16, device=self.dev) if dtype == "bf16" else None
         self.blk_stride = (self.off["model.blocks.1.attn.qkv.weight"] - self.off["model.blocks.0.attn.qkv.weight"]) if self.L > 1 else 0
         for i in range(1, self.L):
-            for w in ("attn.qkv.weight", "attn.proj.weight", "mlp.fc1.weight", "mlp.fc2.weight"):
+            for w in BLOCK_LINEARS:
                 if self.off[f"model.blocks.{i}.{w}"] - self.off[f"model.blocks.0.{w}"] != i * self.blk_stride:
                     raise YvError("state dict: blocks are not laid out with one stride")
         # ---- MXFP8 weight operands (dtype="mxfp8"): per block linear W (N, K) row-wise and W^T (K, N) row-wise, both quantised
@@ -141,7 +144,7 @@ class VitTrainer:
             for i in range(self.L):
                 for w in BLOCK_LINEARS:
                     key = f"model.blocks.{i}.{w}"
-                    N_, K_ = self.gemm_w[key][0], self.gemm_w[key][1]
+                    N_, K_ = self._nk(key)
                     self.wmx[key] = (u8(N_, K_), u8(K_ // 128, r128(N_), 4), u8(K_, N_), u8(N_ // 128, r128(K_), 4))
         self.P16.copy_(self.P)                               # initial cast (plumbing); afterwards the SGD kernel mirrors
         self.refresh_working_copies()
@@ -151,19 +154,23 @@ class VitTrainer:
         self.reducer = BucketReducer(self.G, int(bucket_mb * 1024 * 1024 / 4))
 
     # ---- views ----------------------------------------------------------------------------------
+    def _span(self, k) -> slice:
+        """Parameter k's elements in a flat buffer."""
+        return slice(self.off[k], self.off[k] + math.prod(self.shapes[k]))
+
     def _view(self, flat, k):
-        o = self.off[k]
-        n = 1
-        for d in self.shapes[k]:
-            n *= d
-        return flat[o:o + n].view(self.shapes[k])
+        return flat[self._span(k)].view(self.shapes[k])
 
     def _view16(self, k):
-        o = self.off[k]
-        n = 1
-        for d in self.shapes[k]:
-            n *= d
-        return self.P16[o:o + n]
+        return self.P16[self._span(k)]
+
+    def _nk(self, key: str):
+        """(N, K) of a GEMM weight."""
+        return self.gemm_w[key][:2]
+
+    def _g2d(self, key: str) -> torch.Tensor:
+        """The gradient of a GEMM weight as the (N, K) matrix a weight-gradient product writes."""
+        return self.g(key).reshape(self._nk(key))
 
     def p(self, k):
         return self._view(self.P, k)
@@ -186,15 +193,15 @@ class VitTrainer:
             for key, (wq, ws, wtq, wts) in self.wmx.items():
                 quant_mxfp8_2d(self.gemm_w[key][2], wq, ws, wtq, wts)
             return
-        for w in ("attn.qkv.weight", "attn.proj.weight", "mlp.fc1.weight", "mlp.fc2.weight"):
+        for w in BLOCK_LINEARS:
             key = "model.blocks.0." + w
-            N, K = self.gemm_w[key][0], self.gemm_w[key][1]
+            N, K = self._nk(key)
             o = self.off[key]
             transpose_bf16_batched(self.P16[o:], self.P16T[o:], N, K, self.L, self.blk_stride, self.blk_stride)
 
     def wt(self, key: str) -> torch.Tensor:
         """W^T of a block linear, (K, N) row-major bf16 (view of the transposed mirror)."""
-        N, K = self.gemm_w[key][0], self.gemm_w[key][1]
+        N, K = self._nk(key)
         o = self.off[key]
         return self.P16T[o:o + N * K].view(K, N)
 
@@ -252,45 +259,71 @@ class VitTrainer:
         self._bufs[R] = b
         return b
 
-    # ---- forward (activations kept) -------------------------------------------------------------------
-    def forward(self, patches: torch.Tensor, R: int) -> torch.Tensor:
-        b = self._buffers(R)
-        D, N, tok, H, L = self.D, self.N, self.tok, self.H, self.L
-        M = R * N
-        W = lambda k: self.gemm_w[k][2]
-        b["patches"].copy_(patches)                            # token-padded copy (operand of the patch-embed wgrad)
-        patches = b["patches"]
-        x0 = b["x"][0]
-        cls_rows(self.p("model.cls_token").reshape(D), self.p("model.pos_embed").reshape(N, D), R, tok, D, x0)
-        linear(patches, W("model.patch_embed.proj.weight"), self.p("model.patch_embed.proj.bias"), x0,
-               flags=EPI_OUT_F32 | EPI_POSEMB, pos=self.p("model.pos_embed").reshape(N, D), tok=tok)
-        for i in range(L):
-            k = f"model.blocks.{i}."
-            xin, xmid, xout = b["x"][2 * i], b["x"][2 * i + 1], b["x"][2 * i + 2]
-            if i == L - 1 and self._tail:
-                self._tail_forward(b, R, xin)
-                continue
-            if self.dtype == "mxfp8":
-                self._block_forward_mx(b, i, xin, xmid, xout)
-                continue
-            layernorm(xin, self.p(k + "norm1.weight"), self.p(k + "norm1.bias"), b["h1"][i], M, D, D, D)
-            linear(b["h1"][i], W(k + "attn.qkv.weight"), self.p(k + "attn.qkv.bias"), b["qkv"][i])
-            self._attention_fwd(b, i, R)
-            linear_ex(b["o"][i], W(k + "attn.proj.weight"), self.p(k + "attn.proj.bias"), xmid, flags=EPI_RES_F32, res_f32=xin)
-            layernorm(xmid, self.p(k + "norm2.weight"), self.p(k + "norm2.bias"), b["h2"][i], M, D, D, D)
-            linear_ex(b["h2"][i], W(k + "mlp.fc1.weight"), self.p(k + "mlp.fc1.bias"), b["g"][i],
-                      flags=EPI_GELU | EPI_SAVE_PRE, aux=b["u"][i])
-            linear_ex(b["g"][i], W(k + "mlp.fc2.weight"), self.p(k + "mlp.fc2.bias"), xout, flags=EPI_RES_F32, res_f32=xmid)
-        if self._tail:
-            layernorm(b["tail"]["xout"], self.p("model.norm.weight"), self.p("model.norm.bias"), b["c"], R, D, D, D)
+    # ---- the three products of a block linear: the recipe (self.dtype) is chosen here and nowhere in the block bodies -----------
+    # `lin` names the linear inside block i ("attn.qkv", ...).  `col` names the buffer that takes the column form of the quantised
+    # operand, which the weight gradient reads (mxfp8 only; bf16 has no such form).  `cls` marks a compact cls-row operand: the
+    # mxfp8 recipe runs those products in bf16 on the bf16 mirror.  `epi` is the epilogue: flags, res_f32, aux.
+    def _quant(self, b: dict, x: torch.Tensor, col: Optional[tuple]):
+        """bf16 (M, C) operand -> its row form (the shared A operand of width C) and, if `col`, its column form: one read."""
+        q, s = b["rq"][x.shape[1]]
+        quant_mxfp8_2d(x, q, s, *(col if col is not None else (None, None)), col_form=col is not None)
+        return q, s
+
+    def _product(self, b: dict, i: int, lin: str, x: torch.Tensor, out: torch.Tensor, col: Optional[str] = None,
+                 cls: bool = False, **epi):
+        """Forward product out = x . W^T + bias.  bf16: linear, or linear_ex where the epilogue has a residual source or an aux
+        tensor.  mxfp8: x quantised (column form into b["xc"][i][col]), then linear_mxfp8_ex on the row-wise MX weight."""
+        key = f"model.blocks.{i}.{lin}.weight"
+        bias = self.p(f"model.blocks.{i}.{lin}.bias")
+        if self.dtype == "mxfp8" and not cls:
+            wq, ws = self.wmx[key][:2]
+            linear_mxfp8_ex(*self._quant(b, x, b["xc"][i][col]), wq, ws, bias, out, **epi)
         else:
-            layernorm(b["x"][2 * L], self.p("model.norm.weight"), self.p("model.norm.bias"), b["c"], R, D, N * D, D)
-        linear(b["c"], self.w_head_pad, self.b_head_pad, b["feats"], flags=EPI_OUT_F32)
-        w1t = self.p("fc.1.weight").t().contiguous()
-        b["w1t"] = w1t
-        wrapper_head(b["feats"], w1t, self.p("fc.1.bias"), self.p("fc.3.weight"), self.p("fc.3.bias"), R, self.nc,
-                     b["logits"], b["labels"])
-        return b["logits"]
+            (linear_ex if "res_f32" in epi or "aux" in epi else linear)(x, self.gemm_w[key][2], bias, out, **epi)
+
+    def _dgrad(self, b: dict, S: dict, i: int, lin: str, dy: torch.Tensor, out: torch.Tensor, col: Optional[str] = None,
+               cls: bool = False, **epi):
+        """Data gradient out = dy . W.  bf16: linear / linear_ex on the transposed mirror.  mxfp8: dy quantised (column form into
+        S[col]), then linear_mxfp8_ex on the MX W^T; cls rows: linear_nn on the master layout (the recipe has no transposed mirror)."""
+        key = f"model.blocks.{i}.{lin}.weight"
+        if self.dtype == "bf16":
+            (linear_ex if "aux" in epi else linear)(dy, self.wt(key), None, out, **epi)
+        elif cls:
+            linear_nn(dy, self.gemm_w[key][2], out, **epi)
+        else:
+            wtq, wts = self.wmx[key][2:]
+            linear_mxfp8_ex(*self._quant(b, dy, S[col]), wtq, wts, None, out, **epi)
+
+    def _wgrad(self, b: dict, S: dict, i: int, w: str, dy: str, col: str, x: str, tail: Optional[dict] = None):
+        """Weight gradient G[w] = dy^T . x of block i.  `dy` names the gradient operand in the parity set S (`col`: its column form),
+        `x` the activation.  bf16: wgrad on the 64-row padded, zero-tailed operands.  mxfp8: wgrad_mxfp8 on the column forms.
+        Operands that `tail` holds are compact cls rows: wgrad over their Rp rows, in both recipes."""
+        dw = self._g2d(f"model.blocks.{i}.{w}")
+        if tail is not None and dy in tail:
+            wgrad(tail[dy], tail[x], dw, T=b["Rp"])
+        elif self.dtype == "mxfp8":
+            wgrad_mxfp8(*S[col], *b["xc"][i][x], dw)
+        else:
+            wgrad(S[dy], b["full"][x][i], dw)
+
+    def _side_stream_epilogue(self, b: dict, S: dict, i: int, main, dwide: torch.Tensor, dqkv: torch.Tensor,
+                              tail: Optional[dict] = None):
+        """The end of every block's backward: its four weight gradients and the two bias gradients that are pure column sums (fc1,
+        qkv).  Nothing on the data-gradient chain needs them, so they run on the side stream (own split-K workspace and column-sum
+        scratch) under the next block's chain; the gradient buckets that become final with them are launched from that stream,
+        i.e. after them.  S["done"] lets block i-2, which writes the same parity set, wait for these reads."""
+        k = f"model.blocks.{i}."
+        ev = torch.cuda.Event()
+        ev.record(main)
+        with torch.cuda.stream(self.s_w):
+            self.s_w.wait_event(ev)
+            colsum_bf16(dwide, self.g(k + "mlp.fc1.bias"), b["ws_w"])
+            colsum_bf16(dqkv, self.g(k + "attn.qkv.bias"), b["ws_w"])
+            for w, dy, col, x in BLOCK_WGRADS:
+                self._wgrad(b, S, i, w, dy, col, x, tail)
+            self.reducer.ready(self.off[k + "norm1.weight"])
+            S["done"] = torch.cuda.Event()
+            S["done"].record(self.s_w)
 
     def _attention_fwd(self, b: dict, i: int, R: int):
         """Block i's attention forward with the log2-sum-exp the backward needs."""
@@ -303,173 +336,115 @@ class VitTrainer:
         """A block's attention backward (operands of attention_bwd): both kernels write the same bits."""
         (attention_bwd_long if self.long_attn_bwd and self.N > 224 else attention_bwd)(*args)
 
+    # ---- the full block (both recipes) ---------------------------------------------------------------------
+    def _block_forward(self, b: dict, i: int, R: int):
+        D, M = self.D, b["M"]
+        p = lambda n: self.p(f"model.blocks.{i}.{n}")
+        xin, xmid, xout = b["x"][2 * i:2 * i + 3]
+        layernorm(xin, p("norm1.weight"), p("norm1.bias"), b["h1"][i], M, D, D, D)
+        self._product(b, i, "attn.qkv", b["h1"][i], b["qkv"][i], col="h1")
+        self._attention_fwd(b, i, R)
+        self._product(b, i, "attn.proj", b["o"][i], xmid, col="o", flags=EPI_RES_F32, res_f32=xin)
+        layernorm(xmid, p("norm2.weight"), p("norm2.bias"), b["h2"][i], M, D, D, D)
+        self._product(b, i, "mlp.fc1", b["h2"][i], b["g"][i], col="h2", flags=EPI_GELU | EPI_SAVE_PRE, aux=b["u"][i])
+        self._product(b, i, "mlp.fc2", b["g"][i], xout, col="g", flags=EPI_RES_F32, res_f32=xmid)
+
+    def _block_backward(self, b: dict, S: dict, i: int, main, R: int):
+        """The block's data-gradient chain on the main stream (b["dx"]: the gradient of its output, then of its input), then its
+        weight gradients on the side stream.  The gradient operands live in the parity set S."""
+        D, N, H, M = self.D, self.N, self.H, b["M"]
+        p, g = (lambda n: self.p(f"model.blocks.{i}.{n}")), (lambda n: self.g(f"model.blocks.{i}.{n}"))
+        xin, xmid, dx = b["x"][2 * i], b["x"][2 * i + 1], b["dx"]
+        dxb_fc2, dxb_proj, dwide, dqkv = S["dxb_fc2"][:M], S["dxb_proj"][:M], S["dwide"][:M], S["dqkv"][:M]
+        # MLP branch
+        cast_colsum(dx, dxb_fc2, g("mlp.fc2.bias"), b["ws"])
+        self._dgrad(b, S, i, "mlp.fc2", dxb_fc2, dwide, col="c_fc2", flags=EPI_GELU_BWD, aux=b["u"][i])
+        self._dgrad(b, S, i, "mlp.fc1", dwide, b["dnar"], col="c_wide")
+        layernorm_bwd(xmid, D, p("norm2.weight"), b["dnar"], D, M, D, dx, D, g("norm2.weight"), g("norm2.bias"), b["ws"])
+        # attention branch
+        cast_colsum(dx, dxb_proj, g("attn.proj.bias"), b["ws"])
+        self._dgrad(b, S, i, "attn.proj", dxb_proj, b["dnar"], col="c_proj")
+        self._attention_bwd(b["qkv"][i], b["o"][i], b["dnar"], b["lse"][i], R, N, H, dqkv, b["delta"])
+        self._dgrad(b, S, i, "attn.qkv", dqkv, b["dnar"], col="c_qkv")
+        layernorm_bwd(xin, D, p("norm1.weight"), b["dnar"], D, M, D, dx, D, g("norm1.weight"), g("norm1.bias"), b["ws"])
+        self._side_stream_epilogue(b, S, i, main, dwide, dqkv)
+
     # ---- the last block on the cls rows (cls_tail=True, both recipes) ---------------------------------------
-    def _tail_forward(self, b: dict, R: int, xin: torch.Tensor):
+    def _tail_forward(self, b: dict, i: int, R: int):
         """Block L-1 forward: LN1 and the qkv product over every row (K and V of every token are needed), the rest on the R cls
         rows.  The residual rows are copied into the f32 output first, so that proj and fc2 use the in-place EPI_RES_F32 form."""
-        D, N, H, L, M = self.D, self.N, self.H, self.L, b["M"]
-        i, T = L - 1, b["tail"]
-        k = f"model.blocks.{i}."
-        W = lambda n: self.gemm_w[k + n][2]
-        layernorm(xin, self.p(k + "norm1.weight"), self.p(k + "norm1.bias"), b["h1"][i], M, D, D, D)
-        if self.dtype == "mxfp8":
-            self._mx_linear(k + "attn.qkv.weight", self._quant(b, b["h1"][i], b["xc"][i]["h1"]), self.p(k + "attn.qkv.bias"),
-                            b["qkv"][i])
-        else:
-            linear(b["h1"][i], W("attn.qkv.weight"), self.p(k + "attn.qkv.bias"), b["qkv"][i])
+        D, N, H, M, T = self.D, self.N, self.H, b["M"], b["tail"]
+        p = lambda n: self.p(f"model.blocks.{i}.{n}")
+        xin = b["x"][2 * i]
+        layernorm(xin, p("norm1.weight"), p("norm1.bias"), b["h1"][i], M, D, D, D)
+        self._product(b, i, "attn.qkv", b["h1"][i], b["qkv"][i], col="h1")
         attention_cls_train(T["q"], b["qkv"][i], R, N, H, T["o"][:R], T["lse"])
         T["xmid"].copy_(xin[::N])
-        linear(T["o"][:R], W("attn.proj.weight"), self.p(k + "attn.proj.bias"), T["xmid"], flags=EPI_RES_F32)
-        layernorm(T["xmid"], self.p(k + "norm2.weight"), self.p(k + "norm2.bias"), T["h2"], R, D, D, D)
-        linear_ex(T["h2"][:R], W("mlp.fc1.weight"), self.p(k + "mlp.fc1.bias"), T["g"][:R], flags=EPI_GELU | EPI_SAVE_PRE,
-                  aux=T["u"])
+        self._product(b, i, "attn.proj", T["o"][:R], T["xmid"], cls=True, flags=EPI_RES_F32)
+        layernorm(T["xmid"], p("norm2.weight"), p("norm2.bias"), T["h2"], R, D, D, D)
+        self._product(b, i, "mlp.fc1", T["h2"][:R], T["g"][:R], cls=True, flags=EPI_GELU | EPI_SAVE_PRE, aux=T["u"])
         T["xout"].copy_(T["xmid"])
-        linear(T["g"][:R], W("mlp.fc2.weight"), self.p(k + "mlp.fc2.bias"), T["xout"], flags=EPI_RES_F32)
+        self._product(b, i, "mlp.fc2", T["g"][:R], T["xout"], cls=True, flags=EPI_RES_F32)
 
-    def _tail_dgrad(self, key: str, dy: torch.Tensor, out: torch.Tensor, flags: int = 0, aux: Optional[torch.Tensor] = None):
-        """out = dy . W on cls rows: bf16 recipe on the transposed mirror, MX recipe (no such mirror) on the master layout."""
-        if self.dtype == "mxfp8":
-            linear_nn(dy, self.gemm_w[key][2], out, flags=flags, aux=aux)
-        elif aux is not None:
-            linear_ex(dy, self.wt(key), None, out, flags=flags, aux=aux)
-        else:
-            linear(dy, self.wt(key), None, out, flags=flags)
-
-    def _tail_backward(self, b: dict, S: dict, main, R: int):
+    def _tail_backward(self, b: dict, S: dict, i: int, main, R: int):
         """Block L-1 backward.  b["tail"]["dxc"] holds the cls rows of the incoming gradient (every other row is zero): MLP branch,
-        LN2 and proj on the R cls rows, attention_cls_bwd into the block's ordinary dqkv set, then today's full-row tail of the
-        block (qkv data gradient, LN1 backward) and, on the side stream, the bias column sums and the four weight gradients."""
-        D, N, H, L, M = self.D, self.N, self.H, self.L, b["M"]
-        i, T, Rp = L - 1, b["tail"], b["Rp"]
-        k = f"model.blocks.{i}."
+        LN2 and proj on the R cls rows, attention_cls_bwd into the block's ordinary dqkv set, then the full-row end of the block
+        (qkv data gradient, LN1 backward) and the side-stream epilogue with three of the four weight gradients on compact rows."""
+        D, N, H, M, T = self.D, self.N, self.H, b["M"], b["tail"]
+        p, g = (lambda n: self.p(f"model.blocks.{i}.{n}")), (lambda n: self.g(f"model.blocks.{i}.{n}"))
         xin, dx, dxc, dqkv = b["x"][2 * i], b["dx"], T["dxc"], S["dqkv"][:M]
         dxb_fc2, dxb_proj, dwide = T["dxb_fc2"][:R], T["dxb_proj"][:R], T["dwide"][:R]
         # MLP branch
-        cast_colsum(dxc, dxb_fc2, self.g(k + "mlp.fc2.bias"), b["ws"])
-        self._tail_dgrad(k + "mlp.fc2.weight", dxb_fc2, dwide, flags=EPI_GELU_BWD, aux=T["u"])
-        self._tail_dgrad(k + "mlp.fc1.weight", dwide, T["dnar"])
-        layernorm_bwd(T["xmid"], D, self.p(k + "norm2.weight"), T["dnar"], D, R, D, dxc, D,
-                      self.g(k + "norm2.weight"), self.g(k + "norm2.bias"), b["ws"])
+        cast_colsum(dxc, dxb_fc2, g("mlp.fc2.bias"), b["ws"])
+        self._dgrad(b, S, i, "mlp.fc2", dxb_fc2, dwide, cls=True, flags=EPI_GELU_BWD, aux=T["u"])
+        self._dgrad(b, S, i, "mlp.fc1", dwide, T["dnar"], cls=True)
+        layernorm_bwd(T["xmid"], D, p("norm2.weight"), T["dnar"], D, R, D, dxc, D, g("norm2.weight"), g("norm2.bias"), b["ws"])
         # attention branch: one query per crop; dK and dV for every key, zeros in the other rows' dQ
-        cast_colsum(dxc, dxb_proj, self.g(k + "attn.proj.bias"), b["ws"])
-        self._tail_dgrad(k + "attn.proj.weight", dxb_proj, T["do"])
+        cast_colsum(dxc, dxb_proj, g("attn.proj.bias"), b["ws"])
+        self._dgrad(b, S, i, "attn.proj", dxb_proj, T["do"], cls=True)
         attention_cls_bwd(T["q"], b["qkv"][i], T["do"], T["lse"], R, N, H, dqkv)
         dx[::N].copy_(dxc)                                     # dx is zero elsewhere (backward zeroes it)
-        if self.dtype == "mxfp8":
-            self._mx_linear(k + "attn.qkv.weight", self._quant(b, dqkv, S["c_qkv"]), None, b["dnar"], transposed=True)
+        self._dgrad(b, S, i, "attn.qkv", dqkv, b["dnar"], col="c_qkv")
+        layernorm_bwd(xin, D, p("norm1.weight"), b["dnar"], D, M, D, dx, D, g("norm1.weight"), g("norm1.bias"), b["ws"])
+        self._side_stream_epilogue(b, S, i, main, dwide, dqkv, tail=T)
+
+    # ---- forward (activations kept) -------------------------------------------------------------------
+    def forward(self, patches: torch.Tensor, R: int) -> torch.Tensor:
+        b = self._buffers(R)
+        D, N, tok, L = self.D, self.N, self.tok, self.L
+        b["patches"].copy_(patches)                            # token-padded copy (operand of the patch-embed wgrad)
+        patches = b["patches"]
+        x0 = b["x"][0]
+        cls_rows(self.p("model.cls_token").reshape(D), self.p("model.pos_embed").reshape(N, D), R, tok, D, x0)
+        linear(patches, self.gemm_w["model.patch_embed.proj.weight"][2], self.p("model.patch_embed.proj.bias"), x0,
+               flags=EPI_OUT_F32 | EPI_POSEMB, pos=self.p("model.pos_embed").reshape(N, D), tok=tok)
+        for i in range(L):
+            (self._tail_forward if i == L - 1 and self._tail else self._block_forward)(b, i, R)
+        if self._tail:
+            layernorm(b["tail"]["xout"], self.p("model.norm.weight"), self.p("model.norm.bias"), b["c"], R, D, D, D)
         else:
-            linear(dqkv, self.wt(k + "attn.qkv.weight"), None, b["dnar"])
-        layernorm_bwd(xin, D, self.p(k + "norm1.weight"), b["dnar"], D, M, D, dx, D,
-                      self.g(k + "norm1.weight"), self.g(k + "norm1.bias"), b["ws"])
-        ev = torch.cuda.Event()
-        ev.record(main)
-        with torch.cuda.stream(self.s_w):
-            self.s_w.wait_event(ev)
-            colsum_bf16(dwide, self.g(k + "mlp.fc1.bias"), b["ws_w"])
-            colsum_bf16(dqkv, self.g(k + "attn.qkv.bias"), b["ws_w"])
-            for w, dy, x in (("mlp.fc2.weight", "dxb_fc2", "g"), ("mlp.fc1.weight", "dwide", "h2"),
-                             ("attn.proj.weight", "dxb_proj", "o")):
-                N_, K_ = self.gemm_w[k + w][0], self.gemm_w[k + w][1]
-                wgrad(T[dy], T[x], self.g(k + w).reshape(N_, K_), T=Rp)
-            if self.dtype == "mxfp8":
-                N_, K_ = self.gemm_w[k + "attn.qkv.weight"][0], self.gemm_w[k + "attn.qkv.weight"][1]
-                X = b["xc"][i]["h1"]
-                wgrad_mxfp8(S["c_qkv"][0], S["c_qkv"][1], X[0], X[1], self.g(k + "attn.qkv.weight").reshape(N_, K_))
-            else:
-                self._wgrad(k + "attn.qkv.weight", S["dqkv"], b["full"]["h1"][i])
-            self._launch_ready_buckets(self.off[k + "norm1.weight"])
-            S["done"] = torch.cuda.Event()
-            S["done"].record(self.s_w)
-
-    # ---- MXFP8 block linears (dtype="mxfp8") -------------------------------------------------------------
-    def _quant(self, b: dict, x: torch.Tensor, col: Optional[tuple]):
-        """bf16 (M, C) operand -> its row form (the shared A operand of width C) and, if `col`, its column form: one read."""
-        q, s = b["rq"][x.shape[1]]
-        quant_mxfp8_2d(x, q, s, *(col if col is not None else (None, None)), col_form=col is not None)
-        return q, s
-
-    def _mx_linear(self, key: str, a: tuple, bias, out, transposed: bool = False, **kw):
-        """out = a . W^T (forward) or a . W (transposed: the data gradient, on the W^T operand) with the MX trainer epilogues."""
-        wq, ws, wtq, wts = self.wmx[key]
-        linear_mxfp8_ex(a[0], a[1], wtq if transposed else wq, wts if transposed else ws, bias, out, **kw)
-
-    def _block_forward_mx(self, b: dict, i: int, xin, xmid, xout):
-        k = f"model.blocks.{i}."
-        D, N, H, M = self.D, self.N, self.H, b["M"]
-        R = M // N
-        X = b["xc"][i]                                       # column forms kept for the block's weight gradients
-        layernorm(xin, self.p(k + "norm1.weight"), self.p(k + "norm1.bias"), b["h1"][i], M, D, D, D)
-        self._mx_linear(k + "attn.qkv.weight", self._quant(b, b["h1"][i], X["h1"]), self.p(k + "attn.qkv.bias"), b["qkv"][i])
-        self._attention_fwd(b, i, R)
-        self._mx_linear(k + "attn.proj.weight", self._quant(b, b["o"][i], X["o"]), self.p(k + "attn.proj.bias"), xmid,
-                        flags=EPI_RES_F32, res_f32=xin)
-        layernorm(xmid, self.p(k + "norm2.weight"), self.p(k + "norm2.bias"), b["h2"][i], M, D, D, D)
-        self._mx_linear(k + "mlp.fc1.weight", self._quant(b, b["h2"][i], X["h2"]), self.p(k + "mlp.fc1.bias"), b["g"][i],
-                        flags=EPI_GELU | EPI_SAVE_PRE, aux=b["u"][i])
-        self._mx_linear(k + "mlp.fc2.weight", self._quant(b, b["g"][i], X["g"]), self.p(k + "mlp.fc2.bias"), xout,
-                        flags=EPI_RES_F32, res_f32=xmid)
-
-    def _block_backward_mx(self, b: dict, i: int, S: dict, main, xin, xmid):
-        """The block's data-gradient chain on the main stream (every incoming gradient quantised once: row form for the
-        data gradient, column form for the weight gradient), then its weight gradients on the side stream."""
-        k = f"model.blocks.{i}."
-        D, N, H, M = self.D, self.N, self.H, b["M"]
-        R = M // N
-        dx = b["dx"]
-        dxb_fc2, dxb_proj, dwide, dqkv = S["dxb_fc2"][:M], S["dxb_proj"][:M], S["dwide"][:M], S["dqkv"][:M]
-        # MLP branch
-        cast_colsum(dx, dxb_fc2, self.g(k + "mlp.fc2.bias"), b["ws"])
-        self._mx_linear(k + "mlp.fc2.weight", self._quant(b, dxb_fc2, S["c_fc2"]), None, dwide, transposed=True,
-                        flags=EPI_GELU_BWD, aux=b["u"][i])
-        self._mx_linear(k + "mlp.fc1.weight", self._quant(b, dwide, S["c_wide"]), None, b["dnar"], transposed=True)
-        layernorm_bwd(xmid, D, self.p(k + "norm2.weight"), b["dnar"], D, M, D, dx, D,
-                      self.g(k + "norm2.weight"), self.g(k + "norm2.bias"), b["ws"])
-        # attention branch
-        cast_colsum(dx, dxb_proj, self.g(k + "attn.proj.bias"), b["ws"])
-        self._mx_linear(k + "attn.proj.weight", self._quant(b, dxb_proj, S["c_proj"]), None, b["dnar"], transposed=True)
-        self._attention_bwd(b["qkv"][i], b["o"][i], b["dnar"], b["lse"][i], R, N, H, dqkv, b["delta"])
-        self._mx_linear(k + "attn.qkv.weight", self._quant(b, dqkv, S["c_qkv"]), None, b["dnar"], transposed=True)
-        layernorm_bwd(xin, D, self.p(k + "norm1.weight"), b["dnar"], D, M, D, dx, D,
-                      self.g(k + "norm1.weight"), self.g(k + "norm1.bias"), b["ws"])
-        ev = torch.cuda.Event()
-        ev.record(main)
-        X = b["xc"][i]
-        with torch.cuda.stream(self.s_w):
-            self.s_w.wait_event(ev)
-            colsum_bf16(dwide, self.g(k + "mlp.fc1.bias"), b["ws_w"])
-            colsum_bf16(dqkv, self.g(k + "attn.qkv.bias"), b["ws_w"])
-            for w, dy, x in (("mlp.fc2.weight", "c_fc2", "g"), ("mlp.fc1.weight", "c_wide", "h2"),
-                             ("attn.proj.weight", "c_proj", "o"), ("attn.qkv.weight", "c_qkv", "h1")):
-                N_, K_ = self.gemm_w[k + w][0], self.gemm_w[k + w][1]
-                wgrad_mxfp8(S[dy][0], S[dy][1], X[x][0], X[x][1], self.g(k + w).reshape(N_, K_))
-            self._launch_ready_buckets(self.off[k + "norm1.weight"])
-            S["done"] = torch.cuda.Event()
-            S["done"].record(self.s_w)
+            layernorm(b["x"][2 * L], self.p("model.norm.weight"), self.p("model.norm.bias"), b["c"], R, D, N * D, D)
+        linear(b["c"], self.w_head_pad, self.b_head_pad, b["feats"], flags=EPI_OUT_F32)
+        w1t = self.p("fc.1.weight").t().contiguous()
+        b["w1t"] = w1t
+        wrapper_head(b["feats"], w1t, self.p("fc.1.bias"), self.p("fc.3.weight"), self.p("fc.3.bias"), R, self.nc,
+                     b["logits"], b["labels"])
+        return b["logits"]
 
     # ---- backward ---------------------------------------------------------------------------------------
-    def _wgrad(self, key: str, dy_full: torch.Tensor, x_full: torch.Tensor):
-        """G[key] (N,K) = dy^T . x over the (64-padded, zero-tailed) token rows: transposing-read MFMA GEMM."""
-        N, K = self.gemm_w[key][0], self.gemm_w[key][1]
-        wgrad(dy_full, x_full, self.g(key).reshape(N, K))
-
-    def _launch_ready_buckets(self, low_offset: int):
-        """Gradients at offsets >= low_offset are final: start their all-reduce while backward continues."""
-        self.reducer.ready(low_offset)
-
     def backward(self, patches: torch.Tensor, labels: torch.Tensor, R: int) -> torch.Tensor:
         b = self._buffers(R)
-        D, N, tok, H, L = self.D, self.N, self.tok, self.H, self.L
-        M = R * N
-        Wm = lambda k: self.gemm_w[k][2]                    # master-layout bf16 weight (N_w, K_w)
+        D, N, tok, L = self.D, self.N, self.tok, self.L
         self.reducer.reset()
         loss, dlogits = loss_fwd_bwd(b["logits"], labels)
         # ---- Network_Wrapper.fc + backbone head -----------------------------------------------------------
+        # reducer.ready(offset): gradients at offsets >= offset are final; their all-reduce starts while backward continues
         head_bwd(b["feats"], b["w1t"], self.p("fc.1.bias"), self.p("fc.3.weight"), dlogits, R, self.nc,
                  self.g("fc.1.weight"), self.g("fc.1.bias"), self.g("fc.3.weight"), self.g("fc.3.bias"), b["dfeats"], b["ws"])
-        self._launch_ready_buckets(self.off["fc.1.weight"])
+        self.reducer.ready(self.off["fc.1.weight"])
         colsum_bf16(b["dfeats"], b["ws"][:1024], b["ws"][1024:], rows=R)
         self.g("model.head.bias").copy_(b["ws"][:1000])
-        self._wgrad("model.head.weight", b["full"]["dfeats"][:, :1000], b["full"]["c"])
+        wgrad(b["full"]["dfeats"][:, :1000], b["full"]["c"], self._g2d("model.head.weight"))
         linear_nn(b["dfeats"], self.w_head_pad, b["dc"])
         b["dx"].zero_()
         if self._tail:
@@ -479,54 +454,16 @@ class VitTrainer:
         else:
             layernorm_bwd(b["x"][2 * L], N * D, self.p("model.norm.weight"), b["dc"], D, R, D, b["dx"], N * D,
                           self.g("model.norm.weight"), self.g("model.norm.bias"), b["ws"])
-        self._launch_ready_buckets(self.off["model.norm.weight"])
+        self.reducer.ready(self.off["model.norm.weight"])
         # ---- transformer blocks, last to first -------------------------------------------------------------
         main = torch.cuda.current_stream()
         if self.s_w is None:
             self.s_w = torch.cuda.Stream()
         for i in reversed(range(L)):
-            k = f"model.blocks.{i}."
-            xin, xmid = b["x"][2 * i], b["x"][2 * i + 1]
-            dx = b["dx"]
-            S = b["dy"][i & 1]
+            S = b["dy"][i & 1]                                 # gradient operands, double-buffered by block parity
             if S["done"] is not None:
                 main.wait_event(S["done"])                     # block i+2's weight gradients have read this set
-            if i == L - 1 and self._tail:
-                self._tail_backward(b, S, main, R)
-                continue
-            if self.dtype == "mxfp8":
-                self._block_backward_mx(b, i, S, main, xin, xmid)
-                continue
-            dxb_fc2, dxb_proj, dwide, dqkv = S["dxb_fc2"][:M], S["dxb_proj"][:M], S["dwide"][:M], S["dqkv"][:M]
-            # MLP branch
-            cast_colsum(dx, dxb_fc2, self.g(k + "mlp.fc2.bias"), b["ws"])
-            linear_ex(dxb_fc2, self.wt(k + "mlp.fc2.weight"), None, dwide, flags=EPI_GELU_BWD, aux=b["u"][i])
-            linear(dwide, self.wt(k + "mlp.fc1.weight"), None, b["dnar"])
-            layernorm_bwd(xmid, D, self.p(k + "norm2.weight"), b["dnar"], D, M, D, dx, D,
-                          self.g(k + "norm2.weight"), self.g(k + "norm2.bias"), b["ws"])
-            # attention branch
-            cast_colsum(dx, dxb_proj, self.g(k + "attn.proj.bias"), b["ws"])
-            linear(dxb_proj, self.wt(k + "attn.proj.weight"), None, b["dnar"])
-            self._attention_bwd(b["qkv"][i], b["o"][i], b["dnar"], b["lse"][i], R, N, H, dqkv, b["delta"])
-            linear(dqkv, self.wt(k + "attn.qkv.weight"), None, b["dnar"])
-            layernorm_bwd(xin, D, self.p(k + "norm1.weight"), b["dnar"], D, M, D, dx, D,
-                          self.g(k + "norm1.weight"), self.g(k + "norm1.bias"), b["ws"])
-            # the block's four weight gradients and the two bias gradients that are pure column sums (fc1, qkv): nothing on the
-            # data-gradient chain needs them, so they run on the side stream (own split-K workspace and column-sum scratch) under
-            # the next block's chain; the gradient buckets that become final with them are launched from that stream, i.e. after them
-            ev = torch.cuda.Event()
-            ev.record(main)
-            with torch.cuda.stream(self.s_w):
-                self.s_w.wait_event(ev)
-                colsum_bf16(dwide, self.g(k + "mlp.fc1.bias"), b["ws_w"])
-                colsum_bf16(dqkv, self.g(k + "attn.qkv.bias"), b["ws_w"])
-                self._wgrad(k + "mlp.fc2.weight", S["dxb_fc2"], b["full"]["g"][i])
-                self._wgrad(k + "mlp.fc1.weight", S["dwide"], b["full"]["h2"][i])
-                self._wgrad(k + "attn.proj.weight", S["dxb_proj"], b["full"]["o"][i])
-                self._wgrad(k + "attn.qkv.weight", S["dqkv"], b["full"]["h1"][i])
-                self._launch_ready_buckets(self.off[k + "norm1.weight"])
-                S["done"] = torch.cuda.Event()
-                S["done"].record(self.s_w)
+            (self._tail_backward if i == L - 1 and self._tail else self._block_backward)(b, S, i, main, R)
         main.wait_stream(self.s_w)
         # ---- embeddings -----------------------------------------------------------------------------------
         token_reduce(b["dx"], R, N, D, b["dpos"])
@@ -534,7 +471,7 @@ class VitTrainer:
         self.g("model.cls_token").copy_(b["dpos"][0].view(1, 1, D))
         b["dtok32"].copy_(b["dx"].view(R, N, D)[:, 1:, :].reshape(R * tok, D))          # drop the cls rows (copy only)
         cast_colsum(b["dtok32"], b["dtok"], self.g("model.patch_embed.proj.bias"), b["ws"])
-        self._wgrad("model.patch_embed.proj.weight", b["full"]["dtok"], b["full"]["patches"])
+        wgrad(b["full"]["dtok"], b["full"]["patches"], self._g2d("model.patch_embed.proj.weight"))
         return loss
 
     # ---- optimizer ----------------------------------------------------------------------------------------
