@@ -230,6 +230,20 @@ int yv_train_crops(const uint8_t* pool, size_t pool_bytes, const int64_t* table,
 int yv_mosaic_augment(const uint8_t* tiles, int n_tiles, int B, int S, const float* rec_f, const int32_t* rec_i,
                       const uint8_t* lut, uint8_t* out, void* stream);
 
+/* The same pass for the non-default knobs of the detector trainer (degrees, shear, perspective, flipud, mixup).
+ * `layers` is 1 or 2; per image b and layer L:
+ *   rec_h (B,layers,9) f32: inverse homography, output pixel -> canvas: w = (h6*xs + h7*ys) + h8,
+ *                           u = ((h0*xs + h1*ys) + h2) / w, v = ((h3*xs + h4*ys) + h5) / w; where !(w > 0) the layer
+ *                           shows the fill value 114;
+ *   rec_i (B,layers,34) i32: per layer as above; the flip word rec_i[b,0,1] (bit 0 mirrors x, bit 1 mirrors y) applies to
+ *                           both layers;
+ *   mix (B) f32: weight m = clamp(mix, 0, 1) of layer 0 (NaN -> 0); the layers, each a whole 8-bit value, blend to
+ *                           floor(m*c0 + (1-m)*c1) before the HSV tables.  May be null when layers == 1.
+ * With layers == 1 and the last row (0, 0, 1) the output equals yv_mosaic_augment on the same record bit for bit.
+ * A null pointer, layers outside {1, 2} or a null mix with layers == 2: YV_ERR_ARG. */
+int yv_mosaic_augment_ex(const uint8_t* tiles, int n_tiles, int B, int S, int layers, const float* rec_h,
+                         const int32_t* rec_i, const float* mix, const uint8_t* lut, uint8_t* out, void* stream);
+
 /* DFL decode + anchors + sigmoid (docs/YOLO_TensorRT_Technical.md:14-30,72-77).
  * Per scale s (3 scales, strides 8/16/32): box logits (B,Hs,Ws,64) f32 and class
  * logits (B,Hs,Ws,cls_ld) f32, NHWC.  Outputs boxes (B,A,4) f32 xyxy input pixels,

@@ -128,6 +128,10 @@ extern "C" int yv_augment_patchify(const float* x, int B, int S, int P, const fl
 //   lut   (B,3,256) u8: hue / saturation / value tables applied in 8-bit HSV (H in [0,180))
 // Bilinear taps outside every rectangle read the fill value 114.  f32 arithmetic, one rounding per operation, in the
 // order oracle/yolo_augment.py states.
+// `yv_mosaic_augment_ex` (mosaic_ex_kernel below) is the same pass for the non-default knobs - degrees, shear, perspective,
+// flipud, mixup: a 3 x 3 inverse homography with the projective divide, a flip word of two bits and an optional second
+// gathered layer blended in before the HSV tables.  Both kernels call the same sampling step (mos_sample) and the same
+// HSV tail (mos_hsv_store); tests/yolo_augment_emulation.py states the arithmetic of the second one.
 namespace {
 
 constexpr int MOS_THREADS = 256;
@@ -150,20 +154,9 @@ __device__ __forceinline__ void mos_tap(const uint8_t* __restrict__ tiles, const
 
 __device__ __forceinline__ float round_half_up(float v) { return floorf(__fadd_rn(v, 0.5f)); }
 
-__global__ __launch_bounds__(MOS_THREADS) void mosaic_kernel(const uint8_t* __restrict__ tiles, int n_tiles_total, int S,
-                                                             const float* __restrict__ rec_f, const int32_t* __restrict__ rec_i,
-                                                             const uint8_t* __restrict__ lut, uint8_t* __restrict__ out) {
-    const int b = blockIdx.y;
-    const int p = blockIdx.x * MOS_THREADS + threadIdx.x;
-    if (p >= S * S) return;
-    const int y = p / S, x = p - y * S;
-    const float* a = rec_f + (size_t)b * 6;
-    const int32_t* ri = rec_i + (size_t)b * 34;
-    int nt = ri[0];
-    nt = nt < 0 ? 0 : (nt > 4 ? 4 : nt);
-    const float xs = (float)(ri[1] ? S - 1 - x : x), ys = (float)y;
-    float u = __fadd_rn(__fadd_rn(__fmul_rn(a[0], xs), __fmul_rn(a[1], ys)), a[2]);
-    float v = __fadd_rn(__fadd_rn(__fmul_rn(a[3], xs), __fmul_rn(a[4], ys)), a[5]);
+// one layer at canvas coordinate (u, v): clamp to +-8S (NaN -> -8S), four taps, bilinear, one whole 8-bit value per channel
+__device__ __forceinline__ void mos_sample(const uint8_t* __restrict__ tiles, const int32_t* __restrict__ ri, int nt,
+                                           int n_tiles_total, int S, float u, float v, float (&rgb)[3]) {
     const float lim = (float)(8 * S);
     u = fminf(fmaxf(u, -lim), lim);
     v = fminf(fmaxf(v, -lim), lim);
@@ -171,7 +164,7 @@ __global__ __launch_bounds__(MOS_THREADS) void mosaic_kernel(const uint8_t* __re
     const float fx = __fsub_rn(u, uf), fy = __fsub_rn(v, vf);
     const float gx = __fsub_rn(1.0f, fx), gy = __fsub_rn(1.0f, fy);
     const int i0 = (int)uf, j0 = (int)vf;
-    float rgb[3], t00[3], t01[3], t10[3], t11[3];
+    float t00[3], t01[3], t10[3], t11[3];
     mos_tap(tiles, ri, nt, n_tiles_total, S, i0, j0, t00);
     mos_tap(tiles, ri, nt, n_tiles_total, S, i0 + 1, j0, t01);
     mos_tap(tiles, ri, nt, n_tiles_total, S, i0, j0 + 1, t10);
@@ -182,6 +175,10 @@ __global__ __launch_bounds__(MOS_THREADS) void mosaic_kernel(const uint8_t* __re
         const float bot = __fadd_rn(__fmul_rn(t10[c], gx), __fmul_rn(t11[c], fx));
         rgb[c] = fminf(fmaxf(round_half_up(__fadd_rn(__fmul_rn(top, gy), __fmul_rn(bot, fy))), 0.0f), 255.0f);
     }
+}
+
+// HSV tables of one image on a whole-valued rgb in [0,255], then the store of the output pixel
+__device__ __forceinline__ void mos_hsv_store(const float (&rgb)[3], const uint8_t* __restrict__ l, uint8_t* __restrict__ o) {
     // 8-bit HSV: V = max, S = 255 * (V - min) / V, H = half degrees in [0,180)
     const float R = rgb[0], G = rgb[1], Bc = rgb[2];
     const float vmax = fmaxf(R, fmaxf(G, Bc)), vmin = fminf(R, fminf(G, Bc));
@@ -196,7 +193,6 @@ __global__ __launch_bounds__(MOS_THREADS) void mosaic_kernel(const uint8_t* __re
     }
     int h8 = (int)round_half_up(__fmul_rn(h, 0.5f));
     if (h8 >= 180) h8 -= 180;
-    const uint8_t* l = lut + (size_t)b * 768;
     const float H2 = (float)l[h8], S2 = (float)l[256 + (int)s], V2 = (float)l[512 + (int)vmax];
     // back: sector = H / 30 (half degrees), f = fractional part
     const float hs = __fdiv_rn(H2, 30.0f);
@@ -216,10 +212,71 @@ __global__ __launch_bounds__(MOS_THREADS) void mosaic_kernel(const uint8_t* __re
         case 4: r2 = tt; g2 = pp; b2 = V2; break;
         default: r2 = V2; g2 = pp; b2 = qq; break;
     }
-    uint8_t* o = out + (((size_t)b * S + y) * S + x) * 3;
     o[0] = (uint8_t)fminf(fmaxf(round_half_up(r2), 0.0f), 255.0f);
     o[1] = (uint8_t)fminf(fmaxf(round_half_up(g2), 0.0f), 255.0f);
     o[2] = (uint8_t)fminf(fmaxf(round_half_up(b2), 0.0f), 255.0f);
+}
+
+__global__ __launch_bounds__(MOS_THREADS) void mosaic_kernel(const uint8_t* __restrict__ tiles, int n_tiles_total, int S,
+                                                             const float* __restrict__ rec_f, const int32_t* __restrict__ rec_i,
+                                                             const uint8_t* __restrict__ lut, uint8_t* __restrict__ out) {
+    const int b = blockIdx.y;
+    const int p = blockIdx.x * MOS_THREADS + threadIdx.x;
+    if (p >= S * S) return;
+    const int y = p / S, x = p - y * S;
+    const float* a = rec_f + (size_t)b * 6;
+    const int32_t* ri = rec_i + (size_t)b * 34;
+    int nt = ri[0];
+    nt = nt < 0 ? 0 : (nt > 4 ? 4 : nt);
+    const float xs = (float)(ri[1] ? S - 1 - x : x), ys = (float)y;
+    const float u = __fadd_rn(__fadd_rn(__fmul_rn(a[0], xs), __fmul_rn(a[1], ys)), a[2]);
+    const float v = __fadd_rn(__fadd_rn(__fmul_rn(a[3], xs), __fmul_rn(a[4], ys)), a[5]);
+    float rgb[3];
+    mos_sample(tiles, ri, nt, n_tiles_total, S, u, v, rgb);
+    mos_hsv_store(rgb, lut + (size_t)b * 768, out + (((size_t)b * S + y) * S + x) * 3);
+}
+
+// The same pass through an inverse HOMOGRAPHY (rotation, shear, perspective of RandomPerspective), with a vertical flip and,
+// for LAYERS == 2, a second gathered layer blended in before the HSV tables (MixUp).  Per layer L of image b:
+//   rec_h (B,LAYERS,9)  f32: w = (h6*xs + h7*ys) + h8, u = ((h0*xs + h1*ys) + h2) / w, v = ((h3*xs + h4*ys) + h5) / w;
+//                            !(w > 0) (zero, negative, NaN): the layer's pixel is the fill value
+//   rec_i (B,LAYERS,34) i32: as above; the flip word (bit 0: x, bit 1: y) is layer 0's and applies to both layers
+//   mix   (B)           f32: m = clamp(mix, 0, 1) (NaN -> 0), c = floor(m*c0 + (1-m)*c1) on the layers' 8-bit values
+// A template on LAYERS: the one-layer instance carries no second record, no blend and no read of `mix`.
+template <int LAYERS>
+__global__ __launch_bounds__(MOS_THREADS) void mosaic_ex_kernel(const uint8_t* __restrict__ tiles, int n_tiles_total, int S,
+                                                                const float* __restrict__ rec_h, const int32_t* __restrict__ rec_i,
+                                                                const float* __restrict__ mix, const uint8_t* __restrict__ lut,
+                                                                uint8_t* __restrict__ out) {
+    const int b = blockIdx.y;
+    const int p = blockIdx.x * MOS_THREADS + threadIdx.x;
+    if (p >= S * S) return;
+    const int y = p / S, x = p - y * S;
+    const int flip = rec_i[(size_t)b * LAYERS * 34 + 1];
+    const float xs = (float)((flip & 1) ? S - 1 - x : x), ys = (float)((flip & 2) ? S - 1 - y : y);
+    float lay[LAYERS][3];
+#pragma unroll
+    for (int L = 0; L < LAYERS; ++L) {
+        const float* h = rec_h + ((size_t)b * LAYERS + L) * 9;
+        const int32_t* ri = rec_i + ((size_t)b * LAYERS + L) * 34;
+        int nt = ri[0];
+        nt = nt < 0 ? 0 : (nt > 4 ? 4 : nt);
+        const float w = __fadd_rn(__fadd_rn(__fmul_rn(h[6], xs), __fmul_rn(h[7], ys)), h[8]);
+        if (w > 0.0f) {
+            const float un = __fadd_rn(__fadd_rn(__fmul_rn(h[0], xs), __fmul_rn(h[1], ys)), h[2]);
+            const float vn = __fadd_rn(__fadd_rn(__fmul_rn(h[3], xs), __fmul_rn(h[4], ys)), h[5]);
+            mos_sample(tiles, ri, nt, n_tiles_total, S, __fdiv_rn(un, w), __fdiv_rn(vn, w), lay[L]);
+        } else {
+            lay[L][0] = lay[L][1] = lay[L][2] = 114.0f;
+        }
+    }
+    if constexpr (LAYERS == 2) {
+        const float m = fminf(fmaxf(mix[b], 0.0f), 1.0f), m1 = __fsub_rn(1.0f, m);
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+            lay[0][c] = fminf(fmaxf(floorf(__fadd_rn(__fmul_rn(m, lay[0][c]), __fmul_rn(m1, lay[1][c]))), 0.0f), 255.0f);
+    }
+    mos_hsv_store(lay[0], lut + (size_t)b * 768, out + (((size_t)b * S + y) * S + x) * 3);
 }
 
 }  // namespace
@@ -231,5 +288,18 @@ extern "C" int yv_mosaic_augment(const uint8_t* tiles, int n_tiles, int B, int S
     if (B == 0) return YV_OK;
     mosaic_kernel<<<dim3((unsigned)((S * S + MOS_THREADS - 1) / MOS_THREADS), (unsigned)B), dim3(MOS_THREADS), 0,
                     (hipStream_t)stream>>>(tiles, n_tiles, S, rec_f, rec_i, lut, out);
+    return yv_launch_status();
+}
+
+extern "C" int yv_mosaic_augment_ex(const uint8_t* tiles, int n_tiles, int B, int S, int layers, const float* rec_h,
+                                    const int32_t* rec_i, const float* mix, const uint8_t* lut, uint8_t* out, void* stream) {
+    if (!tiles || !rec_h || !rec_i || !lut || !out) return YV_ERR_ARG;
+    if (layers != 1 && layers != 2) return YV_ERR_ARG;
+    if (layers == 2 && !mix) return YV_ERR_ARG;
+    if (n_tiles <= 0 || B < 0 || S <= 0) return YV_ERR_ARG;
+    if (B == 0) return YV_OK;
+    const dim3 grid((unsigned)((S * S + MOS_THREADS - 1) / MOS_THREADS), (unsigned)B), block(MOS_THREADS);
+    if (layers == 1) mosaic_ex_kernel<1><<<grid, block, 0, (hipStream_t)stream>>>(tiles, n_tiles, S, rec_h, rec_i, mix, lut, out);
+    else mosaic_ex_kernel<2><<<grid, block, 0, (hipStream_t)stream>>>(tiles, n_tiles, S, rec_h, rec_i, mix, lut, out);
     return yv_launch_status();
 }

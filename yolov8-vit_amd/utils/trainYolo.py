@@ -3,8 +3,8 @@
 `train(epochs, batch, data)` keeps the reference's signature and runs the MI355X detector training step
 (yvhip.yolo_training.YoloTrainer: un-fused YOLOv8 forward with BatchNorm batch statistics, v8 detection loss,
 backward, SGD) over the YOLO-format dataset the `data` yaml names.  Around that step the published trainer's defaults
-are followed: Mosaic -> RandomPerspective(scale, translate) -> HSV -> flip augmentation composed on the device
-(yvhip/yolo_augment.py, mosaic closed for the last 10 epochs), `optimizer='auto'` (AdamW / Nesterov SGD), warm-up,
+are followed: Mosaic -> RandomPerspective -> MixUp -> HSV -> flips composed on the device under the trainer's own
+hyper-parameter names (yvhip/yolo_augment.py, mosaic and mixup closed for the last 10 epochs), `optimizer='auto'` (AdamW / Nesterov SGD), warm-up,
 nominal-batch accumulation, ModelEMA, validation after every epoch with best-fitness checkpoint selection, `val()` before
 and after.  The pickled `/app/utils/weight/best.pt` cannot be read with a safe loader, so initial weights come from `weights=` (a state dict written by this trainer) or from a
 seeded random initialisation.  Parity unpinned: every piece lives in `ultralytics`, absent from the reference tree.
@@ -21,7 +21,8 @@ from .class_config import xml2txt          # noqa: F401  (same import as the ref
 
 WEIGHTS_IN = "/app/utils/weight/best.pth"
 WEIGHTS_OUT = "/app/utils/new_weight/yolo_best.pth"
-NOT_BUILT = ["rotation / shear / perspective / mixup / copy-paste augmentation (all 0 in the default configuration)"]
+NOT_BUILT = ["copy-paste augmentation (0 in the default configuration; needs instance masks, which the box-only dataset "
+             "format does not carry)"]
 NBS = 64                                   # ultralytics nominal batch size
 
 
@@ -47,19 +48,30 @@ def val(state, data, scale="n", imgsz=640, batch=16, conf=0.25, iou=0.6, device=
 
 def train(epochs, batch, data, weights=None, scale="n", size=640, save=None, device="cuda:0", seed=42, log=print,
           optimizer="auto", lr0=1e-4, lrf=1e-4, momentum=0.937, weight_decay=5e-4, warmup_epochs=3.0, augment=True,
-          close_mosaic=10):
+          close_mosaic=10, hsv_h=0.015, hsv_s=0.7, hsv_v=0.4, degrees=0.0, translate=0.1, aug_scale=0.5, shear=0.0,
+          perspective=0.0, flipud=0.0, fliplr=0.5, mosaic=1.0, mixup=0.0, copy_paste=0.0):
     """utils/trainYolo.py:6-35: `model.train(epochs=, batch=, data=, lr0=1e-4, lrf=1e-4)` with the ultralytics defaults
     around it: optimizer 'auto' (see _auto_optimizer), linear lr0 -> lr0*lrf schedule, warm-up over
     max(3 epochs, 100 iterations) (lr from 0 - biases from 0.1, 0.0 under AdamW - and momentum from 0.8), gradient
     accumulation to the nominal batch 64 with weight decay scaled by batch*accumulate/64, ModelEMA(0.9999, tau 2000)
     whose weights are validated after every epoch (conf 0.001, IoU 0.7); the epoch with the best fitness
     (0.1 mAP50 + 0.9 mAP50-95) is saved to `save` (best) next to `<save>_last` (last).
+    The augmentation hyper-parameters carry the trainer's names and defaults (hsv_h .. mixup, see
+    yvhip.yolo_augment.DetAugment for the ranges), except the trainer's `scale` gain, which is `aug_scale` here: `scale` has
+    been this function's model scale ('n', 's', ...) from the start.  mixup, like the mosaic, stops at `close_mosaic`.  `copy_paste` must be 0:
+    it pastes instance masks and the dataset format here holds boxes only.
     Returns {"epochs": [...per-epoch mean (total, box, cls, dfl)...], "weights": path or None, "not_built": [...]}."""
     import numpy as np
     from yvhip.yolo_data import list_samples, load_batch, max_boxes_per_image, read_data_yaml
     from yvhip.yolo_val import validate
     from yvhip.yolo_augment import DetAugment, augment_batch
     from yvhip.yolo_training import YoloTrainer, init_yolo_train_state
+    if copy_paste != 0:
+        raise yvhip.YvError("trainYolo.train: copy_paste is not built: it pastes instance masks, and the dataset format "
+                            "(generate_annotation XML, YOLO txt boxes) carries none")
+    det_aug = DetAugment(size, seed=seed, mosaic=mosaic, hsv=(hsv_h, hsv_s, hsv_v), fliplr=fliplr, translate=translate,
+                         scale=aug_scale, degrees=degrees, shear=shear, perspective=perspective, flipud=flipud,
+                         mixup=mixup) if augment else None
     yvhip.require_gpu()
     cfg = read_data_yaml(data)
     nc = cfg["nc"]
@@ -94,7 +106,7 @@ def train(epochs, batch, data, weights=None, scale="n", size=640, save=None, dev
     val_samples = list_samples(cfg["val"]) if cfg["val"] and os.path.isdir(cfg["val"]) else []
     best_fit, best_state, best_epoch = None, None, -1
     order_rng = random.Random(seed)
-    det_aug, mosaic_on, G_aug = (DetAugment(size, seed=seed) if augment else None), True, 4 * G
+    mosaic_on, G_aug = True, (8 if mixup > 0 else 4) * G   # a mosaic shows the boxes of four images, a mix of two mosaics
     for ep in range(int(epochs)):
         lr = lr0 * lf(ep)
         acc, steps = torch.zeros(4), 0
@@ -109,7 +121,7 @@ def train(epochs, batch, data, weights=None, scale="n", size=640, save=None, dev
                 acc_now = max(1, int(np.interp(ni, xi, [1, NBS / B]).round()))
                 lrs = {g: float(np.interp(ni, xi, [warmup_bias_lr if g == "bias" else 0.0, lr])) for g in ("w", "bnw", "bias")}
                 mom = float(np.interp(ni, xi, [0.8, momentum]))
-            if det_aug is not None:                            # Mosaic -> affine -> HSV -> flip, composed on the device
+            if det_aug is not None:                            # Mosaic -> perspective -> mixup -> HSV -> flips, on the device
                 img, gtb, gtl, gtn = augment_batch(order, range(i, i + B), det_aug, G_aug, device, use_mosaic=mosaic_on)
             else:
                 img, gtb, gtl, gtn = load_batch(order[i:i + B], size, G)

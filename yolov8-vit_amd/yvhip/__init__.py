@@ -91,6 +91,7 @@ _SIGS = {
     "yv_augment_patchify": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "yv_train_crops": (_i, [_vp, _sz, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp]),
     "yv_mosaic_augment": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "yv_mosaic_augment_ex": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "yv_detect_decode": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "yv_detect_tail": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "yv_c2f_debug": (_i, [_vp]),
@@ -438,6 +439,34 @@ def mosaic_augment(tiles: torch.Tensor, rec_f: torch.Tensor, rec_i: torch.Tensor
         raise YvError("mosaic_augment: lut must be (B,3,256) u8")
     out = torch.empty((B, S, S, 3), dtype=torch.uint8, device=tiles.device)
     check(lib.yv_mosaic_augment(_p(tiles), N, B, S, _p(rec_f), _p(rec_i), _p(lut), _p(out), _st()), "yv_mosaic_augment")
+    return out
+
+
+def mosaic_augment_ex(tiles: torch.Tensor, rec_h: torch.Tensor, rec_i: torch.Tensor, mix: Optional[torch.Tensor],
+                      lut: torch.Tensor) -> torch.Tensor:
+    """tiles (N,S,S,3) u8 + per output image `layers` (1 or 2) records: rec_h (B,layers,9) f32 inverse homographies,
+    rec_i (B,layers,34) i32, mix (B) f32 weight of layer 0 (None allowed with one layer), lut (B,3,256) u8
+    -> (B,S,S,3) u8: rotation / shear / perspective / flipud / mixup of the detector trainer (yvhip.yolo_augment)."""
+    _chk_dev(tiles, rec_h, rec_i, mix, lut)
+    if tiles.dim() != 4 or tiles.shape[3] != 3 or tiles.shape[1] != tiles.shape[2] or tiles.shape[0] < 1 \
+            or tiles.dtype != torch.uint8:
+        raise YvError("mosaic_augment_ex: tiles must be a contiguous (N,S,S,3) u8 tensor")
+    N, S = tiles.shape[0], tiles.shape[1]
+    if rec_h.dim() != 3 or rec_h.shape[1] not in (1, 2) or rec_h.shape[2] != 9 or rec_h.dtype != torch.float32:
+        raise YvError("mosaic_augment_ex: rec_h must be (B,layers,9) f32 with layers 1 or 2")
+    B, layers = rec_h.shape[0], rec_h.shape[1]
+    if tuple(rec_i.shape) != (B, layers, 34) or rec_i.dtype != torch.int32:
+        raise YvError("mosaic_augment_ex: rec_i must be (B,layers,34) i32")
+    if mix is None:
+        if layers == 2:
+            raise YvError("mosaic_augment_ex: mix is required with two layers")
+    elif tuple(mix.shape) != (B,) or mix.dtype != torch.float32:
+        raise YvError("mosaic_augment_ex: mix must be (B) f32")
+    if tuple(lut.shape) != (B, 3, 256) or lut.dtype != torch.uint8:
+        raise YvError("mosaic_augment_ex: lut must be (B,3,256) u8")
+    out = torch.empty((B, S, S, 3), dtype=torch.uint8, device=tiles.device)
+    check(lib.yv_mosaic_augment_ex(_p(tiles), N, B, S, layers, _p(rec_h), _p(rec_i), _p(mix), _p(lut), _p(out), _st()),
+          "yv_mosaic_augment_ex")
     return out
 
 
