@@ -73,15 +73,11 @@ def test_mx_conv_plan_reads_only_32_aligned_views():
     """Every MX convolution of every scale reads channel counts / offsets that are multiples of 32 (the engine's own
     launch list, without a device)."""
     for scale in "nsm":
-        eng = engines.YoloEngine.__new__(engines.YoloEngine)
-        eng.layers, eng.fused_c2f = engines.yolo_layers(scale), True
-        ch = engines._c(256, scale)
-        eng.c2, eng.c3 = max(16, ch // 4, engines.REG_MAX * 4), max(ch, 5)
         plan = set(engines.mx_conv_plan(scale, 5, speed_filter=False, min_width=0))
-        specs = {sp[0]: sp for sp in eng._conv_specs()}
-        assert plan <= set(specs)
+        convs = {e.key: e for e in engines.detect_launches(scale, 5) if isinstance(e, engines.Conv)}
+        assert plan <= set(convs)
         for key in plan:
-            for _, off, c, _ in specs[key][1]:
+            for _, off, c, _ in convs[key].srcs:
                 assert off % 32 == 0 and c % 32 == 0, (scale, key)
 
 

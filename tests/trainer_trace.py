@@ -174,29 +174,31 @@ def _differs(value, default) -> bool:
     return type(value) is not type(default) or value != default
 
 
+def native_stub(rec, name, real, result=lambda given: None):
+    """Recording stand-in for the native wrapper `real`.  It appends what the wrapper receives, however the call spells it: the
+    parameters without a default in the signature's order, the others by name where the value is not the default.  It returns
+    result(arguments by name)."""
+    sig = inspect.signature(real)
+
+    def call(*a, **k):
+        given = sig.bind(*a, **k).arguments
+        pos = [given[p.name] for p in sig.parameters.values() if p.default is p.empty]
+        kw = {p.name: given[p.name] for p in sig.parameters.values()
+              if p.default is not p.empty and p.name in given and _differs(given[p.name], p.default)}
+        rec.add(name, pos, kw)
+        return result(given)
+    return call
+
+
 def _patch(mp, rec):
     from yvhip import dist, training
-
-    def stub(name, real):
-        sig = inspect.signature(real)
-
-        def call(*a, **k):
-            # what the wrapper receives, however the call spells it: parameters without a default in the signature's order, the
-            # others by name where the value is not the default
-            given = sig.bind(*a, **k).arguments
-            pos = [given[p.name] for p in sig.parameters.values() if p.default is p.empty]
-            kw = {p.name: given[p.name] for p in sig.parameters.values()
-                  if p.default is not p.empty and p.name in given and _differs(given[p.name], p.default)}
-            rec.add(name, pos, kw)
-            if name == "loss_fwd_bwd":
-                return torch.zeros(1, dtype=torch.float32), torch.zeros_like(a[0])
-        return call
+    loss = lambda given: (torch.zeros(1, dtype=torch.float32), torch.zeros_like(given["logits"]))
 
     natives = {n: v for n, v in vars(training).items()
                if inspect.isfunction(v) and v.__module__ == "yvhip" and n not in HOST_ONLY}
     assert {"linear", "linear_ex", "wgrad", "wgrad_mxfp8", "attention_bwd_long", "sgd_step"} <= set(natives), sorted(natives)
     for n, real in natives.items():
-        mp.setattr(training, n, stub(n, real))
+        mp.setattr(training, n, native_stub(rec, n, real, loss) if n == "loss_fwd_bwd" else native_stub(rec, n, real))
     mp.setattr(training, "require_gpu", lambda: None)
     mp.setattr(torch.cuda, "current_stream", lambda device=None: rec.stack[-1])
     mp.setattr(torch.cuda, "Stream", lambda *a, **k: _Stream(rec))

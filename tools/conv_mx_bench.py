@@ -23,21 +23,13 @@ from yvhip import engines
 REPS, WARM = int(os.environ.get("REPS", 20)), 3
 dev = "cuda:0"
 CONV_KERNELS = ("igemm_kernel", "cgemm_dma_kernel", "splitk_reduce_kernel", "cgemm_mx_kernel")
+
+
 def layer_shapes(scale, nc=5):
-    eng = engines.YoloEngine.__new__(engines.YoloEngine)
-    eng.layers, eng.fused_c2f = engines.yolo_layers(scale), True
-    ch = engines._c(256, scale)
-    eng.c2, eng.c3 = max(16, ch // 4, engines.REG_MAX * 4), max(ch, min(nc, 100))
-    couts = {k: co for k, _, co, _ in engines.yolo_conv_keys(scale, nc)}
-    for s in range(3):
-        couts[f"det{s}.0"] = eng.c2 + eng.c3
     plan = set(engines.mx_conv_plan(scale, nc, speed_filter=False, min_width=0))
-    for key, srcs, k, st, oname, _, _ in eng._conv_specs():
-        if key not in plan:
-            continue
-        idx = int(oname[3:]) if oname[:3] in ("out",) else (int(oname[1:]) if oname[0] in "yt" else None)
-        stride = engines.LAYER_STRIDE[idx] if idx is not None else (8, 16, 32)[int(oname[3])]
-        yield key, [(c, up) for _, _, c, up in srcs], k, st, couts[key], 640 // stride
+    for e in engines.detect_launches(scale, nc):
+        if isinstance(e, engines.Conv) and e.key in plan:
+            yield e.key, [(c, up) for _, _, c, up in e.srcs], e.k, e.stride, e.cout, 640 // e.down
 
 
 def time_it(fn):

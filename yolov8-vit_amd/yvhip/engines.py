@@ -12,17 +12,19 @@ device buffers.  Activations are NHWC bf16; concat / split / upsample never mate
 """
 from __future__ import annotations
 
+import functools
 import math
 import os
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import torch
 
 from .guard import StepGuard
-from . import (set_option, get_option, EPI_GELU, EPI_OUT_F32, EPI_POSEMB, EPI_RES_BF16, EPI_RES_F32, EPI_SILU, YvError, attention, attention_cls, attention_long, attention_mxfp8,
-               cls_rows,
-               c2f_fused, conv2d, conv2d_mxfp8, detect_decode, mx_map, mx_view, quant_conv_weight_mxfp8, quant_mxfp8_map, detect_tail, layernorm, layernorm_mxfp8, linear, linear_mxfp8, linear_res_ln, RES_LN_WIDTHS, linear_mxfp8_q, quant_mxfp8, require_gpu, sppf_pool, stem_conv, view,
-               wrapper_head)
+from . import (EPI_GELU, EPI_OUT_F32, EPI_POSEMB, EPI_RES_BF16, EPI_RES_F32, EPI_SILU, RES_LN_WIDTHS, YvError, attention,
+               attention_cls, attention_long, attention_mxfp8, c2f_fused, cls_rows, conv2d, conv2d_mxfp8, detect_decode,
+               detect_tail, get_option, layernorm, layernorm_mxfp8, linear, linear_mxfp8, linear_mxfp8_q, linear_res_ln, mx_map,
+               mx_view, quant_conv_weight_mxfp8, quant_mxfp8, quant_mxfp8_map, require_gpu, set_option, sppf_pool, stem_conv,
+               view, wrapper_head)
 
 # --------------------------------------------------------------------------------------- YOLOv8
 YOLO_SCALES = {"n": (0.33, 0.25, 1024), "s": (0.33, 0.50, 1024), "m": (0.67, 0.75, 768)}
@@ -64,6 +66,12 @@ def yolo_layers(scale: str):
     ]
 
 
+def detect_widths(scale: str, nc: int) -> Tuple[Tuple[int, int, int], int, int, int]:
+    """Detect head: (input channels per scale, width of the box branch, width of the class branch, nc padded to a multiple of 8)."""
+    ch = (_c(256, scale), _c(512, scale), _c(1024, scale))
+    return ch, max(16, ch[0] // 4, REG_MAX * 4), max(ch[0], min(nc, 100)), (nc + 7) // 8 * 8
+
+
 def yolo_conv_keys(scale: str, nc: int) -> List[Tuple[str, int, int, int]]:
     """(state-dict prefix, cin, cout, k) of every conv in the fused model."""
     out = []
@@ -83,9 +91,7 @@ def yolo_conv_keys(scale: str, nc: int) -> List[Tuple[str, int, int, int]]:
         elif kind == "sppf":
             out.append((pre + "cv1.conv", p["cin"], p["cin"] // 2, 1))
             out.append((pre + "cv2.conv", p["cin"] * 2, p["cout"], 1))
-    ch = (_c(256, scale), _c(512, scale), _c(1024, scale))
-    c2 = max(16, ch[0] // 4, REG_MAX * 4)
-    c3 = max(ch[0], min(nc, 100))
+    ch, c2, c3, _ = detect_widths(scale, nc)
     for s, ci in enumerate(ch):
         out += [(f"model.22.cv2.{s}.0.conv", ci, c2, 3), (f"model.22.cv2.{s}.1.conv", c2, c2, 3),
                 (f"model.22.cv2.{s}.2", c2, 4 * REG_MAX, 1), (f"model.22.cv3.{s}.0.conv", ci, c3, 3),
@@ -116,6 +122,93 @@ def _fused_c2f_block(p: dict) -> bool:
     return "a" not in p and p["add"] and p["cin"] == p["cout"] and c in (16, 32) and p["n"] in (1, 2)
 
 
+# ---- the detector's launch list: entries of four kinds.  Buffers go by name: out{idx} (a layer's output), y{idx} (the concat
+# buffer of a C2f / SPPF block), t{idx} (a bottleneck's hidden map), det{s}.hb / .hc (the head's feature maps), det{s}.box / .cls
+class Stem(NamedTuple):
+    key: str
+    out: str
+
+
+class Conv(NamedTuple):
+    key: str                    # of the weight and bias tables (a state-dict prefix, det{s}.0 or a padded 1 x 1 of the head)
+    srcs: tuple                 # one or two (buffer, channel offset, channels, up): the input views, concatenated
+    k: int
+    stride: int
+    out: str
+    out_off: int                # channel offset in `out`
+    res_off: Optional[int]      # channel offset in `out` of the bf16 residual, None = no residual
+    flags: int                  # epilogue
+    cout: int
+    down: int                   # the output grid is (size // down) x (size // down)
+    block: Optional[int]        # index of the C2f block the convolution is part of
+
+
+class C2fFused(NamedTuple):
+    src: str
+    out: str
+    c: int
+    n: int
+    cv1: str
+    m: tuple                    # keys of m.0.cv1, m.0.cv2, m.1.cv1, ...
+    cv2: str
+
+
+class Pool(NamedTuple):
+    buf: str                    # SPPF: three chained 5 x 5 max-pools of channels [0, c) into the three chunks behind them
+    c: int
+
+
+@functools.lru_cache(maxsize=None)
+def detect_launches(scale: str, nc: int = 5, fused_c2f: bool = True, tail: bool = True) -> tuple:
+    """What YoloEngine launches in front of the decode, in order: Stem, Conv, C2fFused and Pool entries.  fused_c2f: the blocks of
+    _fused_c2f_block as one entry each, else layer by layer.  tail=False: without the last 1 x 1 convolutions of the head (the
+    fused Detect tail runs them)."""
+    layers = yolo_layers(scale)
+    width = {idx: p["cout"] for idx, _, p in layers}
+    out: list = []
+
+    def conv(key, srcs, k, stride, obuf, cout, down, out_off=0, res_off=None, flags=EPI_SILU, block=None):
+        flags |= EPI_RES_BF16 if res_off is not None else 0
+        out.append(Conv(key, tuple(srcs), k, stride, obuf, out_off, res_off, flags, cout, down, block))
+
+    for idx, kind, p in layers:
+        pre, d, o = f"model.{idx}.", LAYER_STRIDE[idx], f"out{idx}"
+        src = [(f"out{idx - 1}", 0, p.get("cin"), 0)]
+        if kind == "stem":
+            out.append(Stem(pre + "conv", o))
+        elif kind == "conv":
+            conv(pre + "conv", src, 3, 2, o, p["cout"], d)
+        elif kind == "c2f":
+            c, n, y, t = p["cout"] // 2, p["n"], f"y{idx}", f"t{idx}"
+            m = [pre + f"m.{j}.cv{i}.conv" for j in range(n) for i in (1, 2)]
+            if fused_c2f and _fused_c2f_block(p):       # one launch, intermediates in LDS (YOLOv8n: model.2, model.4)
+                out.append(C2fFused(src[0][0], o, c, n, pre + "cv1.conv", tuple(m), pre + "cv2.conv"))
+                continue
+            if "a" in p:                                # the neck: concat of two layers' outputs, one of them upsampled
+                src = [(f"out{i}", 0, width[i], up) for i, up in (p["a"], p["b"])]
+            conv(pre + "cv1.conv", src, 1, 1, y, 2 * c, d, block=idx)
+            for j in range(n):
+                at = (1 + j) * c
+                conv(m[2 * j], [(y, at, c, 0)], 3, 1, t, c, d, block=idx)
+                conv(m[2 * j + 1], [(t, 0, c, 0)], 3, 1, y, c, d, at + c, at if p["add"] else None, block=idx)
+            conv(pre + "cv2.conv", [(y, 0, (2 + n) * c, 0)], 1, 1, o, p["cout"], d, block=idx)
+        elif kind == "sppf":
+            c_, y = p["cin"] // 2, f"y{idx}"
+            conv(pre + "cv1.conv", src, 1, 1, y, c_, d)
+            out.append(Pool(y, c_))
+            conv(pre + "cv2.conv", [(y, 0, 4 * c_, 0)], 1, 1, o, p["cout"], d)
+    ch, c2, c3, ncp = detect_widths(scale, nc)
+    for s, fidx in enumerate((15, 18, 21)):
+        d, hb, hc = LAYER_STRIDE[fidx], f"det{s}.hb", f"det{s}.hc"
+        conv(f"det{s}.0", [(f"out{fidx}", 0, ch[s], 0)], 3, 1, hb, c2 + c3, d)
+        conv(f"model.22.cv2.{s}.1.conv", [(hb, 0, c2, 0)], 3, 1, hc, c2, d)
+        conv(f"model.22.cv3.{s}.1.conv", [(hb, c2, c3, 0)], 3, 1, hc, c3, d, c2)
+        if tail:
+            conv(f"model.22.cv2.{s}.2", [(hc, 0, c2, 0)], 1, 1, f"det{s}.box", 4 * REG_MAX, d, flags=EPI_OUT_F32)
+            conv(f"model.22.cv3.{s}.2.pad", [(hc, c2, c3, 0)], 1, 1, f"det{s}.cls", ncp, d, flags=EPI_OUT_F32)
+    return tuple(out)
+
+
 # layer kinds (kernel size, stride, whether Cin % 128 == 0) whose MXFP8 launches measured slower than the bf16 ones on the
 # MI355X (tools/conv_mx_bench.py under rocprofv3, YOLOv8m at 64 images, profiles/conv_mx_layers.txt; DESIGN.md section 10):
 # the 1 x 1 layers, +19 % / +21 %.  They stay bf16.
@@ -135,43 +228,22 @@ def mx_conv_plan(scale: str, nc: int = 5, speed_filter: bool = True, min_width: 
     blocks (one yv_c2f_fused launch), SPPF's cv2 (reads the bf16 max-pool chunks) and the last 1 x 1 convolutions of the
     head (read by yv_detect_tail / the decode); then the layer kinds of MX_SLOW_KINDS (speed_filter) and the layers
     narrower than MX_MIN_WIDTH channels (min_width overrides it)."""
-    a32 = lambda *v: all(x % 32 == 0 for x in v)
-    cand: List[Tuple[str, int, int, List[int], int]] = []        # (key, k, stride, source widths, cout)
-    width = {}
-    for idx, kind, p in yolo_layers(scale):
-        pre = f"model.{idx}."
-        width[idx] = p["cout"]
-        if kind == "conv" and a32(p["cin"], p["cout"], width[idx - 1]):
-            cand.append((pre + "conv", 3, 2, [p["cin"]], p["cout"]))
-        elif kind == "c2f" and not _fused_c2f_block(p):
-            c = p["cout"] // 2
-            srcs = [width[p["a"][0]], width[p["b"][0]]] if "a" in p else [p["cin"]]
-            if not a32(c, *srcs):
-                continue
-            cand.append((pre + "cv1.conv", 1, 1, srcs, 2 * c))
-            for j in range(p["n"]):
-                cand += [(pre + f"m.{j}.cv1.conv", 3, 1, [c], c), (pre + f"m.{j}.cv2.conv", 3, 1, [c], c)]
-            cand.append((pre + "cv2.conv", 1, 1, [(2 + p["n"]) * c], p["cout"]))
-        elif kind == "sppf" and a32(p["cin"], p["cin"] // 2):
-            cand.append((pre + "cv1.conv", 1, 1, [p["cin"]], p["cin"] // 2))
-    ch = (_c(256, scale), _c(512, scale), _c(1024, scale))
-    c2 = max(16, ch[0] // 4, REG_MAX * 4)
-    c3 = max(ch[0], min(nc, 100))
-    for s in range(3):
-        if a32(ch[s], c2 + c3):
-            cand.append((f"det{s}.0", 3, 1, [ch[s]], c2 + c3))
-        if a32(c2):
-            cand.append((f"model.22.cv2.{s}.1.conv", 3, 1, [c2], c2))
-        if a32(c2, c3):
-            cand.append((f"model.22.cv3.{s}.1.conv", 3, 1, [c3], c3))
+    launches = detect_launches(scale, nc)
+    pooled = {e.buf for e in launches if isinstance(e, Pool)}
+    a32 = lambda e: all(x % 32 == 0 for x in (e.cout, e.out_off, *(x for _, off, c, _ in e.srcs for x in (off, c))))
+    convs = [e for e in launches if isinstance(e, Conv) and not e.flags & EPI_OUT_F32 and e.srcs[0][0] not in pooled]
+    straddling = {e.block for e in convs if e.block is not None and not a32(e)}
     mw = MX_MIN_WIDTH if min_width is None else min_width
     out: List[str] = []
-    for key, k, st, srcs, co in cand:
-        if speed_filter and (k, st, sum(srcs) % 128 == 0) in MX_SLOW_KINDS:
+    for e in convs:
+        widths = [c for _, _, c, _ in e.srcs]
+        if not a32(e) or e.block in straddling:
             continue
-        if min(*srcs, co) < mw:
+        if speed_filter and (e.k, e.stride, sum(widths) % 128 == 0) in MX_SLOW_KINDS:
             continue
-        out.append(key)
+        if min(*widths, e.cout) < mw:
+            continue
+        out.append(e.key)
     return out
 
 
@@ -209,10 +281,7 @@ class YoloEngine:
             else:
                 self.w[key] = _khwc(wt.float()).to(self.dev)
             self.b[key] = bs.float().contiguous().to(self.dev)
-        ch = (_c(256, scale), _c(512, scale), _c(1024, scale))
-        self.c2 = max(16, ch[0] // 4, REG_MAX * 4)
-        self.c3 = max(ch[0], min(nc, 100))
-        self.ncp = (nc + 7) // 8 * 8
+        _, self.c2, self.c3, self.ncp = detect_widths(scale, nc)
         for s in range(3):
             # horizontal fusion of the two 3x3 convs that share the scale's feature map (test.ipynb:1285)
             k0, k1 = f"model.22.cv2.{s}.0.conv", f"model.22.cv3.{s}.0.conv"
@@ -234,190 +303,69 @@ class YoloEngine:
         self.fused_tail = self.c2 == 64 and nc <= 16 and self.c3 in (64, 128, 192)
         self.fused_c2f = True                    # backbone C2f blocks with c <= 32 in one launch each (yv_c2f_fused)
         self.mx_layers: List[str] = mx_conv_plan(scale, nc) if dtype == "mxfp8" else []
-        self.wq: Dict[str, tuple] = {}
-        self._specs: Dict[str, tuple] = {}
-        if self.mx_layers:
-            for key in self.mx_layers:           # (e4m3 (Cout, Kpad), K-step-major scales)
-                self.wq[key] = quant_conv_weight_mxfp8(self.w[key])
-            self._specs = {sp[0]: sp for sp in self._conv_specs()}
+        # (e4m3 (Cout, Kpad), K-step-major scales) of the MX convolutions
+        self.wq: Dict[str, tuple] = {key: quant_conv_weight_mxfp8(self.w[key]) for key in self.mx_layers}
+        if self.wq:
             torch.cuda.synchronize(self.dev)
+        heads = [(f"model.22.cv2.{s}.2", f"model.22.cv3.{s}.2.pad16") for s in range(3)]
+        self._tail_operands = ([self.w[k] for k, _ in heads], [self.b[k] for k, _ in heads],
+                               [self.w[k] for _, k in heads], [self.b[k] for _, k in heads])
         self._bufs: Dict[int, dict] = {}
         self.guard = StepGuard()                 # one replay of the launch list at a time (callers may be threads)
         self.A = sum((size // s) ** 2 for s in (8, 16, 32))
 
     # -- buffers are allocated once per batch size and reused (no allocation in the step)
     def _buffers(self, B: int) -> dict:
+        """"flat": the launch list's buffers by name; "out": the layers' outputs by index; "mx": the MX maps by buffer name."""
         if B in self._bufs:
             return self._bufs[B]
         S = self.size
         bf = lambda h, c: torch.zeros((B, h, h, c), dtype=torch.bfloat16, device=self.dev)
         f32 = lambda h, c: torch.zeros((B, h, h, c), dtype=torch.float32, device=self.dev)
-        bufs: dict = {"out": {}, "y": {}, "t": {}}
-        bufs["h"] = {}
+        flat: Dict[str, torch.Tensor] = {}
         for idx, kind, p in self.layers:
             h = S // LAYER_STRIDE[idx]
-            bufs["out"][idx] = bf(h, p["cout"])
-            bufs["h"][idx] = h
+            flat[f"out{idx}"] = bf(h, p["cout"])
             if kind == "c2f":
                 c = p["cout"] // 2
-                bufs["y"][idx] = bf(h, (2 + p["n"]) * c)
-                bufs["t"][idx] = bf(h, c)
+                flat[f"y{idx}"] = bf(h, (2 + p["n"]) * c)
+                flat[f"t{idx}"] = bf(h, c)
             elif kind == "sppf":
-                bufs["y"][idx] = bf(h, p["cin"] * 2)
+                flat[f"y{idx}"] = bf(h, p["cin"] * 2)
         for s, st in enumerate((8, 16, 32)):
             hs = S // st
-            bufs[f"det{s}.hb"] = bf(hs, self.c2 + self.c3)
-            bufs[f"det{s}.hc"] = bf(hs, self.c2 + self.c3)
-            bufs[f"det{s}.box"] = f32(hs, 4 * REG_MAX)
-            bufs[f"det{s}.cls"] = f32(hs, self.ncp)
-        if self.mx_layers:
-            # every bf16 activation an MX convolution reads gets an MX map next to it, written by its producers
-            flat = {f"{k}{i}": t for k in ("out", "y", "t") for i, t in bufs[k].items()}
-            flat.update({f"det{s}.{x}": bufs[f"det{s}.{x}"] for s in range(3) for x in ("hb", "hc")})
-            bufs["flat"] = flat
-            bufs["mx"] = {n: mx_map(B, flat[n].shape[1], flat[n].shape[2], flat[n].shape[3], self.dev)
-                          for n in self._mx_sources()}
-        self._bufs[B] = bufs
+            flat[f"det{s}.hb"] = bf(hs, self.c2 + self.c3)
+            flat[f"det{s}.hc"] = bf(hs, self.c2 + self.c3)
+            flat[f"det{s}.box"] = f32(hs, 4 * REG_MAX)
+            flat[f"det{s}.cls"] = f32(hs, self.ncp)
+        # every bf16 activation an MX convolution reads gets an MX map next to it, written by its producers (bf16 engine: none)
+        mx_convs = [e for e in detect_launches(self.scale, self.nc) if type(e) is Conv and e.key in self.wq]
+        read = sorted({b for e in mx_convs for b, *_ in e.srcs})
+        bufs = self._bufs[B] = dict(
+            flat=flat, out={idx: flat[f"out{idx}"] for idx, _, _ in self.layers},
+            mx={n: mx_map(B, flat[n].shape[1], flat[n].shape[2], flat[n].shape[3], self.dev) for n in read},
+            **{x: [flat[f"det{s}.{x}"] for s in range(3)] for x in ("hc", "box", "cls")})
         return bufs
 
-    def _c2f(self, idx: int, p: dict, in0, in1, B: int, bufs: dict):
-        pre = f"model.{idx}."
-        h = bufs["h"][idx]
-        c = p["cout"] // 2
-        y, t, out = bufs["y"][idx], bufs["t"][idx], bufs["out"][idx]
-        if (self.fused_c2f and in1 is None and p["add"] and p["cin"] == p["cout"] and c in (16, 32) and p["n"] in (1, 2)):
-            # the whole block in one launch, intermediates in LDS (yv_c2f_fused; YOLOv8n: model.2 and model.4)
-            keys = [pre + f"m.{j}.cv{k}.conv" for j in range(p["n"]) for k in (1, 2)]
-            c2f_fused(bufs["out"][idx - 1], c, p["n"], self.w[pre + "cv1.conv"], self.b[pre + "cv1.conv"],
-                      [self.w[k] for k in keys], [self.b[k] for k in keys], self.w[pre + "cv2.conv"], self.b[pre + "cv2.conv"], out)
-            return
-        conv2d(in0, in1, B, h, h, 1, 1, self.w[pre + "cv1.conv"], self.b[pre + "cv1.conv"], y, 0, EPI_SILU)
-        for j in range(p["n"]):
-            src = (1 + j) * c
-            conv2d(view(y, src, c), None, B, h, h, 3, 1, self.w[pre + f"m.{j}.cv1.conv"], self.b[pre + f"m.{j}.cv1.conv"],
-                   t, 0, EPI_SILU)
-            if p["add"]:
-                conv2d(view(t, 0, c), None, B, h, h, 3, 1, self.w[pre + f"m.{j}.cv2.conv"],
-                       self.b[pre + f"m.{j}.cv2.conv"], y, src + c, EPI_SILU | EPI_RES_BF16, res=y, res_c_off=src)
-            else:
-                conv2d(view(t, 0, c), None, B, h, h, 3, 1, self.w[pre + f"m.{j}.cv2.conv"],
-                       self.b[pre + f"m.{j}.cv2.conv"], y, src + c, EPI_SILU)
-        conv2d(view(y, 0, (2 + p["n"]) * c), None, B, h, h, 1, 1, self.w[pre + "cv2.conv"], self.b[pre + "cv2.conv"],
-               out, 0, EPI_SILU)
-
-    # -- MXFP8 detector (dtype="mxfp8")
-    def _conv_specs(self):
-        """Every convolution of the step in order: (key, sources [(buffer, c_off, c, up)], k, stride, out buffer, out c_off,
-        residual c_off or None).  Buffers: out{idx}, y{idx}, t{idx}, det{s}.hb / .hc."""
-        specs = []
-        for idx, kind, p in self.layers:
-            pre = f"model.{idx}."
-            if kind == "conv":
-                specs.append((pre + "conv", [(f"out{idx - 1}", 0, p["cin"], 0)], 3, 2, f"out{idx}", 0, None))
-            elif kind == "c2f":
-                if "a" not in p and self.fused_c2f and _fused_c2f_block(p):
-                    continue
-                c = p["cout"] // 2
-                if "a" in p:
-                    (ia, ua), (ib, ub) = p["a"], p["b"]
-                    wa, wb = self.layers_by_idx[ia]["cout"], self.layers_by_idx[ib]["cout"]
-                    srcs = [(f"out{ia}", 0, wa, ua), (f"out{ib}", 0, wb, ub)]
-                else:
-                    srcs = [(f"out{idx - 1}", 0, p["cin"], 0)]
-                specs.append((pre + "cv1.conv", srcs, 1, 1, f"y{idx}", 0, None))
-                for j in range(p["n"]):
-                    src = (1 + j) * c
-                    specs.append((pre + f"m.{j}.cv1.conv", [(f"y{idx}", src, c, 0)], 3, 1, f"t{idx}", 0, None))
-                    specs.append((pre + f"m.{j}.cv2.conv", [(f"t{idx}", 0, c, 0)], 3, 1, f"y{idx}", src + c,
-                                  src if p["add"] else None))
-                specs.append((pre + "cv2.conv", [(f"y{idx}", 0, (2 + p["n"]) * c, 0)], 1, 1, f"out{idx}", 0, None))
-            elif kind == "sppf":
-                specs.append((pre + "cv1.conv", [(f"out{idx - 1}", 0, p["cin"], 0)], 1, 1, f"y{idx}", 0, None))
-        c2, c3 = self.c2, self.c3
-        for s, fidx in enumerate((15, 18, 21)):
-            w = self.layers_by_idx[fidx]["cout"]
-            specs.append((f"det{s}.0", [(f"out{fidx}", 0, w, 0)], 3, 1, f"det{s}.hb", 0, None))
-            specs.append((f"model.22.cv2.{s}.1.conv", [(f"det{s}.hb", 0, c2, 0)], 3, 1, f"det{s}.hc", 0, None))
-            specs.append((f"model.22.cv3.{s}.1.conv", [(f"det{s}.hb", c2, c3, 0)], 3, 1, f"det{s}.hc", c2, None))
-        return specs
-
-    @property
-    def layers_by_idx(self):
-        return {idx: p for idx, _, p in self.layers}
-
-    def _mx_sources(self):
-        mx = set(self.mx_layers)
-        return sorted({b for key, srcs, *_ in self._specs.values() if key in mx for b, *_ in srcs})
-
     def _produced(self, bufs, name: str, c_off: int, c: int):
-        """A bf16 producer wrote channels [c_off, c_off+c) of `name`: bring its MX map up to date."""
+        """A bf16 producer wrote channels [c_off, c_off+c) of `name`: bring its MX map, if it has one, up to date."""
         if name in bufs["mx"]:
             quant_mxfp8_map(bufs["flat"][name], bufs["mx"][name], c_off, c, c_off)
 
-    def _conv(self, bufs, B: int, h: int, spec):
-        key, srcs, k, st, oname, ooff, roff = spec
-        out = bufs["flat"][oname]
-        flags = EPI_SILU | (EPI_RES_BF16 if roff is not None else 0)
-        res = out if roff is not None else None
-        cout = self.b[key].shape[0]
-        if key in self.wq:
-            wq, ws = self.wq[key]
-            v = [mx_view(bufs["mx"][b], off, c, up) for b, off, c, up in srcs]
-            conv2d_mxfp8(v[0], v[1] if len(v) > 1 else None, B, h, h, k, st, wq, ws, self.b[key], out, ooff, flags,
-                         res=res, res_c_off=roff or 0, out_mx=bufs["mx"].get(oname), outq_c_off=ooff)
+    def _conv(self, bufs, B: int, e: Conv):
+        flat, mx = bufs["flat"], bufs["mx"]
+        h, out = self.size // e.down, flat[e.out]
+        res = out if e.res_off is not None else None
+        if e.key in self.wq:
+            wq, ws = self.wq[e.key]
+            v = [mx_view(mx[b], off, c, up) for b, off, c, up in e.srcs]
+            conv2d_mxfp8(v[0], v[1] if len(v) > 1 else None, B, h, h, e.k, e.stride, wq, ws, self.b[e.key], out, e.out_off,
+                         e.flags, res=res, res_c_off=e.res_off or 0, out_mx=mx.get(e.out), outq_c_off=e.out_off)
         else:
-            v = [view(bufs["flat"][b], off, c, up) for b, off, c, up in srcs]
-            conv2d(v[0], v[1] if len(v) > 1 else None, B, h, h, k, st, self.w[key], self.b[key], out, ooff, flags,
-                   res=res, res_c_off=roff or 0)
-            self._produced(bufs, oname, ooff, cout)
-
-    def _forward_raw_mx(self, images: torch.Tensor, B: int, bufs: dict, tail: bool):
-        """_forward_raw with the convolutions of self.mx_layers on MX operands (same launch order otherwise)."""
-        o = bufs["out"]
-        specs = self._specs
-        for idx, kind, p in self.layers:
-            pre = f"model.{idx}."
-            h = bufs["h"][idx]
-            if kind == "stem":
-                stem_conv(images, self.w[pre + "conv"], self.b[pre + "conv"], o[0])
-                self._produced(bufs, "out0", 0, p["cout"])
-            elif kind == "conv":
-                self._conv(bufs, B, h, specs[pre + "conv"])
-            elif kind == "c2f":
-                if "a" not in p and self.fused_c2f and _fused_c2f_block(p):
-                    self._c2f(idx, p, view(o[idx - 1], 0, p["cin"]), None, B, bufs)
-                    self._produced(bufs, f"out{idx}", 0, p["cout"])
-                    continue
-                self._conv(bufs, B, h, specs[pre + "cv1.conv"])
-                for j in range(p["n"]):
-                    self._conv(bufs, B, h, specs[pre + f"m.{j}.cv1.conv"])
-                    self._conv(bufs, B, h, specs[pre + f"m.{j}.cv2.conv"])
-                self._conv(bufs, B, h, specs[pre + "cv2.conv"])
-            elif kind == "sppf":
-                y = bufs["y"][idx]
-                c_ = p["cin"] // 2
-                self._conv(bufs, B, h, specs[pre + "cv1.conv"])
-                sppf_pool(y, c_)
-                conv2d(view(y, 0, 4 * c_), None, B, h, h, 1, 1, self.w[pre + "cv2.conv"], self.b[pre + "cv2.conv"],
-                       o[idx], 0, EPI_SILU)
-                self._produced(bufs, f"out{idx}", 0, p["cout"])
-        box_l, cls_l = [], []
-        c2, c3 = self.c2, self.c3
-        for s, fidx in enumerate((15, 18, 21)):
-            hs = bufs["h"][fidx]
-            hc = bufs[f"det{s}.hc"]
-            for key in (f"det{s}.0", f"model.22.cv2.{s}.1.conv", f"model.22.cv3.{s}.1.conv"):
-                self._conv(bufs, B, hs, specs[key])
-            if not tail:
-                box_l.append(hc)
-                continue
-            k = f"model.22.cv2.{s}.2"
-            conv2d(view(hc, 0, c2), None, B, hs, hs, 1, 1, self.w[k], self.b[k], bufs[f"det{s}.box"], 0, EPI_OUT_F32)
-            k = f"model.22.cv3.{s}.2.pad"
-            conv2d(view(hc, c2, c3), None, B, hs, hs, 1, 1, self.w[k], self.b[k], bufs[f"det{s}.cls"], 0, EPI_OUT_F32)
-            box_l.append(bufs[f"det{s}.box"])
-            cls_l.append(bufs[f"det{s}.cls"])
-        return box_l, cls_l
+            v = [view(flat[b], off, c, up) for b, off, c, up in e.srcs]
+            conv2d(v[0], v[1] if len(v) > 1 else None, B, h, h, e.k, e.stride, self.w[e.key], self.b[e.key], out, e.out_off,
+                   e.flags, res=res, res_c_off=e.res_off or 0)
+            self._produced(bufs, e.out, e.out_off, e.cout)
 
     def forward_raw(self, images: torch.Tensor):
         """Runs backbone+neck+head; returns per-scale (box logits f32, class logits f32) NHWC tensors.  Called with `self.guard`
@@ -432,72 +380,34 @@ class YoloEngine:
             return tuple([t.clone() for t in part] for part in res)
 
     def _forward_raw(self, images: torch.Tensor, tail: bool = True):
-        """tail=False: stop in front of the last 1 x 1 convolutions and return the per-scale feature buffers (B,Hs,Ws,c2+c3)."""
+        """Walks detect_launches (self.fused_c2f is read here, so it may be flipped between calls).  tail=False: stop in front of
+        the last 1 x 1 convolutions and return the per-scale feature buffers (B,Hs,Ws,c2+c3)."""
         if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[-1] != 3:
             raise YvError("images must be (B,S,S,3) uint8")
         B, S = images.shape[0], images.shape[1]
         if S != self.size or images.shape[2] != self.size:
             raise YvError(f"engine built for {self.size}x{self.size}")
         bufs = self._buffers(B)
-        if self.mx_layers:
-            return self._forward_raw_mx(images, B, bufs, tail)
-        o = bufs["out"]
-        for idx, kind, p in self.layers:
-            pre = f"model.{idx}."
-            h = bufs["h"][idx]
-            if kind == "stem":
-                stem_conv(images, self.w[pre + "conv"], self.b[pre + "conv"], o[0])
-            elif kind == "conv":
-                src = o[idx - 1]
-                conv2d(view(src, 0, p["cin"]), None, B, h, h, 3, 2, self.w[pre + "conv"], self.b[pre + "conv"], o[idx],
-                       0, EPI_SILU)
-            elif kind == "c2f":
-                if "a" in p:
-                    (ia, ua), (ib, ub) = p["a"], p["b"]
-                    in0 = view(o[ia], 0, o[ia].shape[-1], up=ua)
-                    in1 = view(o[ib], 0, o[ib].shape[-1], up=ub)
+        flat, w, b = bufs["flat"], self.w, self.b
+        for e in detect_launches(self.scale, self.nc, bool(self.fused_c2f), tail):
+            if type(e) is Conv:
+                self._conv(bufs, B, e)
+            elif type(e) is Pool:
+                sppf_pool(flat[e.buf], e.c)
+            else:
+                if type(e) is Stem:
+                    stem_conv(images, w[e.key], b[e.key], flat[e.out])
                 else:
-                    in0, in1 = view(o[idx - 1], 0, p["cin"]), None
-                self._c2f(idx, p, in0, in1, B, bufs)
-            elif kind == "sppf":
-                y = bufs["y"][idx]
-                c_ = p["cin"] // 2
-                conv2d(view(o[idx - 1], 0, p["cin"]), None, B, h, h, 1, 1, self.w[pre + "cv1.conv"],
-                       self.b[pre + "cv1.conv"], y, 0, EPI_SILU)
-                sppf_pool(y, c_)
-                conv2d(view(y, 0, 4 * c_), None, B, h, h, 1, 1, self.w[pre + "cv2.conv"], self.b[pre + "cv2.conv"],
-                       o[idx], 0, EPI_SILU)
-        box_l, cls_l = [], []
-        c2, c3 = self.c2, self.c3
-        for s, fidx in enumerate((15, 18, 21)):
-            f = o[fidx]
-            hs = bufs["h"][fidx]
-            hb, hc = bufs[f"det{s}.hb"], bufs[f"det{s}.hc"]
-            conv2d(view(f, 0, f.shape[-1]), None, B, hs, hs, 3, 1, self.w[f"det{s}.0"], self.b[f"det{s}.0"], hb, 0,
-                   EPI_SILU)
-            k = f"model.22.cv2.{s}.1.conv"
-            conv2d(view(hb, 0, c2), None, B, hs, hs, 3, 1, self.w[k], self.b[k], hc, 0, EPI_SILU)
-            k = f"model.22.cv3.{s}.1.conv"
-            conv2d(view(hb, c2, c3), None, B, hs, hs, 3, 1, self.w[k], self.b[k], hc, c2, EPI_SILU)
-            if not tail:
-                box_l.append(hc)
-                continue
-            k = f"model.22.cv2.{s}.2"
-            conv2d(view(hc, 0, c2), None, B, hs, hs, 1, 1, self.w[k], self.b[k], bufs[f"det{s}.box"], 0, EPI_OUT_F32)
-            k = f"model.22.cv3.{s}.2.pad"
-            conv2d(view(hc, c2, c3), None, B, hs, hs, 1, 1, self.w[k], self.b[k], bufs[f"det{s}.cls"], 0, EPI_OUT_F32)
-            box_l.append(bufs[f"det{s}.box"])
-            cls_l.append(bufs[f"det{s}.cls"])
-        return box_l, cls_l
+                    c2f_fused(flat[e.src], e.c, e.n, w[e.cv1], b[e.cv1], [w[k] for k in e.m], [b[k] for k in e.m], w[e.cv2],
+                              b[e.cv2], flat[e.out])
+                self._produced(bufs, e.out, 0, flat[e.out].shape[-1])
+        return (list(bufs["box"]), list(bufs["cls"])) if tail else (list(bufs["hc"]), [])
 
     def __call__(self, images: torch.Tensor):
         with self.guard:                         # the decode reads the engine-owned head buffers
             if self.fused_tail:
                 feats, _ = self._forward_raw(images, tail=False)
-                return detect_tail(feats, self.c3,
-                                   [self.w[f"model.22.cv2.{s}.2"] for s in range(3)], [self.b[f"model.22.cv2.{s}.2"] for s in range(3)],
-                                   [self.w[f"model.22.cv3.{s}.2.pad16"] for s in range(3)],
-                                   [self.b[f"model.22.cv3.{s}.2.pad16"] for s in range(3)], self.size, self.nc)
+                return detect_tail(feats, self.c3, *self._tail_operands, self.size, self.nc)
             box_l, cls_l = self._forward_raw(images)
             return detect_decode(box_l, cls_l, self.size, self.nc)
 
@@ -507,7 +417,6 @@ VIT_CFGS = {
     "vit_base_patch16_224": (16, 768, 12, 12),
     "vit_base_patch8_224": (8, 768, 12, 12),            # the reference's configured model (utils/class_config.py:21)
     "vit_large_patch16_224": (16, 1024, 24, 16),        # BASELINE.json configs[4]
-    "vit_large_patch16_224": (16, 1024, 24, 16),
     "vit_tiny_test": (16, 128, 2, 2),
     "vit_tiny8_test": (8, 128, 2, 2),
 }
@@ -558,14 +467,15 @@ class VitEngine:
                  device: str = "cuda:0", dtype: str = "bf16", cls_tail: bool = True, fused_ln: Optional[bool] = None,
                  long_attn: Optional[bool] = None):
         """cls_tail (bf16 path): the last block runs on the cls rows only - nothing reads its other rows (see _last_block_cls);
-        False gives the full last block.
+        False gives the full last block.  The mxfp8 pass runs every block in full whatever cls_tail says, and it ignores
+        full_cus_from (the attribute PipelinedRunner sets): both are properties of the bf16 block loop.
         dtype "bf16" (default) or "mxfp8": the four block linears (qkv, proj, fc1, fc2) then run on OCP e4m3 operands
         with one E8M0 scale per 32 K elements through the block-scaled MFMA (BASELINE.json configs[4]); weights are
         quantised once here, activations by yv_quant_mxfp8 in front of each GEMM; everything else (patch-embed, LayerNorm,
         attention, residual stream, heads) keeps its bf16 / f32 form.
         fused_ln (bf16 path, opt-in): proj and fc2 run as linear_res_ln, which also writes the LayerNorm their result feeds (the
         block's norm2 / the next block's norm1), so the separate LayerNorm passes over the residual stream go away - see
-        _backbone_pass.  None reads the environment variable YV_VIT_FUSED_LN ("1" = on, unset = off; a bf16 engine only, the
+        _blocks_bf16.  None reads the environment variable YV_VIT_FUSED_LN ("1" = on, unset = off; a bf16 engine only, the
         mxfp8 engine ignores the variable).  True with dtype "mxfp8" or an embedding width yv_linear_res_ln lacks: YvError.
         long_attn (both dtypes, opt-in): the full blocks' attention runs as attention_long (128-row query blocks, pipelined 64-key
         tiles; dtype "mxfp8": writing the proj operand directly) in place of attention / attention_mxfp8.  Effective only where the
@@ -687,14 +597,36 @@ class VitEngine:
 
     def _backbone_pass(self, patches: torch.Tensor, cap: int, count: Optional[torch.Tensor], slot: int) -> torch.Tensor:
         b = self._buffers(cap, slot)
-        D, N, tok, H = self.D, self.N, self.tok, self.H
-        x, h, qkv, o, gbuf = b["x"], b["h"], b["qkv"], b["o"], b["g"]
+        D, N, tok = self.D, self.N, self.tok
+        x = b["x"]
         cls_rows(self.cls, self.pos, cap, tok, D, x)
         linear(patches, self.w_pe, self.b_pe, x, flags=EPI_OUT_F32 | EPI_POSEMB, pos=self.pos, tok=tok, m_dev=count,
                m_mul=tok)
+        (self._blocks_mxfp8 if self.dtype == "mxfp8" else self._blocks_bf16)(b, cap, count)
+        layernorm(x, self.nw, self.nb, b["c"], cap, D, N * D, D, count_dev=count, rows_per_count=1)
+        linear(b["c"], self.w_head, self.b_head, b["feats"], flags=EPI_OUT_F32, m_dev=count, m_mul=1)
+        return b["feats"]
+
+    def _attention(self, b: dict, cap: int, count: Optional[torch.Tensor], mx: bool = False):
+        """Attention of a full block, qkv -> o: attention_long where the flag is on and the sequence long enough, else attention.
+        mx: the result is the proj operand (q, qs) instead - written by the kernel itself (attention_long, or attention_mxfp8 unless
+        YV_MX_ATTN_FUSED=0), else by a quantisation pass over o.  Both MX kernels take an even head count, which an mxfp8 engine
+        always has: H = D / 64 and D is a multiple of 128."""
+        N, H, qkv, o = self.N, self.H, b["qkv"], b["o"]
+        long = self.long_attn and N > 224
+        if mx and long:
+            attention_long(qkv, cap, N, H, r_dev=count, out_q=b["q"], out_scale=b["qs"])
+        elif mx and self.fuse_attention_quant:
+            attention_mxfp8(qkv, cap, N, H, b["q"], b["qs"], r_dev=count)
+        else:
+            (attention_long if long else attention)(qkv, cap, N, H, o, r_dev=count)
+            if mx:
+                quant_mxfp8(o, b["q"], b["qs"])
+
+    def _blocks_bf16(self, b: dict, cap: int, count: Optional[torch.Tensor]):
+        D, N = self.D, self.N
+        x, h, qkv, o, gbuf = b["x"], b["h"], b["qkv"], b["o"], b["g"]
         rows = cap * N
-        if self.dtype == "mxfp8":
-            return self._backbone_mxfp8(b, cap, count)
         # fused_ln: every proj also writes its block's norm2 output and every fc2 (but the last block's) the NEXT block's norm1 output
         # (linear_res_ln), so of the 2L block LayerNorms only block 0's norm1 - its input comes from patch-embed + cls_rows - remains
         fused = self.fused_ln
@@ -707,10 +639,7 @@ class VitEngine:
             if not (fused and i > 0):
                 layernorm(x, blk["n1w"], blk["n1b"], h, rows, D, D, D, count_dev=count, rows_per_count=N)
             linear(h, blk["wqkv"], blk["bqkv"], qkv, m_dev=count, m_mul=N)
-            if self.long_attn and N > 224:
-                attention_long(qkv, cap, N, H, o, r_dev=count)
-            else:
-                attention(qkv, cap, N, H, o, r_dev=count)
+            self._attention(b, cap, count)
             if fused:
                 linear_res_ln(o, blk["wproj"], blk["bproj"], x, blk["n2w"], blk["n2b"], h, m_dev=count, m_mul=N)
             else:
@@ -722,9 +651,6 @@ class VitEngine:
                 linear_res_ln(gbuf, blk["wfc2"], blk["bfc2"], x, nxt["n1w"], nxt["n1b"], h, m_dev=count, m_mul=N)
             else:
                 linear(gbuf, blk["wfc2"], blk["bfc2"], x, flags=EPI_RES_F32, m_dev=count, m_mul=N)
-        layernorm(x, self.nw, self.nb, b["c"], cap, D, N * D, D, count_dev=count, rows_per_count=1)
-        linear(b["c"], self.w_head, self.b_head, b["feats"], flags=EPI_OUT_F32, m_dev=count, m_mul=1)
-        return b["feats"]
 
     def _last_block_cls(self, b: dict, blk: dict, cap: int, count: Optional[torch.Tensor], norm1_done: bool = False):
         """The last block on the cls rows.  The final LayerNorm and the head read row 0 of each crop only, and inside a block token
@@ -746,31 +672,22 @@ class VitEngine:
         linear(b["th"], blk["wfc1"], blk["bfc1"], b["tg"], flags=EPI_GELU, m_dev=count, m_mul=1)
         linear(b["tg"], blk["wfc2"], blk["bfc2"], xc, flags=EPI_RES_F32, m_dev=count, m_mul=1)
 
-    def _backbone_mxfp8(self, b: dict, cap: int, count: Optional[torch.Tensor]) -> torch.Tensor:
+    def _blocks_mxfp8(self, b: dict, cap: int, count: Optional[torch.Tensor]):
         """Block linears in MXFP8.  Operand hand-offs: LayerNorm writes the qkv / fc1 operand directly, the fc1 epilogue
         writes the fc2 operand directly (GELU output never exists in bf16 in HBM), attention writes the proj operand
         directly: no separate quantisation pass is left."""
-        D, N, H = self.D, self.N, self.H
-        x, qkv, o = b["x"], b["qkv"], b["o"]
+        D, N = self.D, self.N
+        x, qkv = b["x"], b["qkv"]
         hq, hs, gq, gs = b["q"], b["qs"], b["gq"], b["gs"]
         rows = cap * N
         for blk in self.blocks:
             layernorm_mxfp8(x, blk["n1w"], blk["n1b"], hq, hs, rows, D, D, count_dev=count, rows_per_count=N)
             linear_mxfp8(hq, hs, blk["wqkv_q"], blk["wqkv_s"], blk["bqkv"], qkv, m_dev=count, m_mul=N)
-            if self.long_attn and N > 224 and H % 2 == 0:
-                attention_long(qkv, cap, N, H, r_dev=count, out_q=hq, out_scale=hs)      # the proj operand, as attention_mxfp8
-            elif H % 2 == 0 and self.fuse_attention_quant:
-                attention_mxfp8(qkv, cap, N, H, hq, hs, r_dev=count)          # attention writes the proj operand directly
-            else:
-                (attention_long if self.long_attn and N > 224 else attention)(qkv, cap, N, H, o, r_dev=count)
-                quant_mxfp8(o, hq, hs)
+            self._attention(b, cap, count, mx=True)
             linear_mxfp8(hq, hs, blk["wproj_q"], blk["wproj_s"], blk["bproj"], x, flags=EPI_RES_F32, m_dev=count, m_mul=N)
             layernorm_mxfp8(x, blk["n2w"], blk["n2b"], hq, hs, rows, D, D, count_dev=count, rows_per_count=N)
             linear_mxfp8_q(hq, hs, blk["wfc1_q"], blk["wfc1_s"], blk["bfc1"], gq, gs, flags=EPI_GELU, m_dev=count, m_mul=N)
             linear_mxfp8(gq, gs, blk["wfc2_q"], blk["wfc2_s"], blk["bfc2"], x, flags=EPI_RES_F32, m_dev=count, m_mul=N)
-        layernorm(x, self.nw, self.nb, b["c"], cap, D, N * D, D, count_dev=count, rows_per_count=1)
-        linear(b["c"], self.w_head, self.b_head, b["feats"], flags=EPI_OUT_F32, m_dev=count, m_mul=1)
-        return b["feats"]
 
     def head(self, feats: torch.Tensor, cap: int, logits: torch.Tensor, labels: torch.Tensor, scale: float = 1.0,
              accumulate: bool = False, count: Optional[torch.Tensor] = None):

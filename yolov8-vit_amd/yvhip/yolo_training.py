@@ -23,7 +23,7 @@ from . import (OPT_ADAMW, OPT_SGD_NESTEROV, VIEW_ADD, VIEW_COPY, VIEW_PAD, VIEW_
                blob_nhwc8, bn_act_bwd, bn_act_fwd, ema_update, optim_step,
                bn_stats, bn_ws_floats, cast_colsum, colsum_ws_floats, conv_view, conv_weight_dgrad, detect_loss,
                detect_loss_ws_bytes, im2col3, maxpool5_bwd, mview, require_gpu, sgd_step, sppf_pool, view_op, wgrad, wgrad_conv3)
-from .engines import LAYER_STRIDE, REG_MAX, _c, yolo_conv_keys, yolo_layers
+from .engines import LAYER_STRIDE, REG_MAX, detect_widths, yolo_conv_keys, yolo_layers
 
 BN_EPS, BN_MOMENTUM = 1e-3, 0.03
 
@@ -256,9 +256,7 @@ class YoloTrainer:
             elif kind == "sppf":
                 self.mod[idx] = dict(kind="sppf", c_=p["cin"] // 2, cv1=_Block(self, pre + ".cv1", p["cin"], p["cin"] // 2, 1, 1),
                                      cv2=_Block(self, pre + ".cv2", p["cin"] * 2, p["cout"], 1, 1))
-        ch = (_c(256, sc), _c(512, sc), _c(1024, sc))
-        self.c2 = max(16, ch[0] // 4, REG_MAX * 4)
-        self.c3 = max(ch[0], min(nc, 100))
+        ch, self.c2, self.c3, _ = detect_widths(sc, nc)
         self.det = []
         for s, ci in enumerate(ch):
             pre = f"model.22"
