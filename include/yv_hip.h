@@ -38,8 +38,18 @@ int yv_version(void);
 const char* yv_error_string(int code);
 /* 1 if the current HIP device is gfx950, 0 otherwise, <0 on HIP error. */
 int yv_device_is_gfx950(void);
-/* Tuning knobs (process-wide, not part of the reference surface): "linear_variant" (0 register-staged
- * 128x128, 1 LDS-DMA 128x128, 2 256x128, 3 256x256, 4 128x256), "linear_group_m" (M tiles per L2 group). */
+/* Tuning knobs (process-wide, not part of the reference surface): "linear_group_m" (M tiles per L2 group) and "linear_variant",
+ * the kernel of yv_linear / yv_linear_ex (yv_linear_route reports what a value selects for a shape):
+ *   1          the shipped rule: skinny, register-staged, split-K, persistent or 128 x 128 LDS-DMA tiles by shape and flags;
+ *   0          igemm_kernel, register-staged 128 x 16 / 32 / 64 / 128 tiles, for every shape;
+ *   2, 3, 4    gemm_dma_kernel with 256 x 128, 256 x 256, 128 x 256 tiles;
+ *   9, 11      the persistent gemm_p8_kernel / gemm_p9_kernel where the shape and flags allow them, at any M (else 128 x 128);
+ *   101 .. 104 gemm_dma_kernel 128 x 128 with one stage of its main loop taken out (ablations 1 .. 4, tools/gemm_bench.py);
+ *   201 .. 204 the same ablations on 256 x 256 tiles;
+ *   any other  128 x 128 LDS-DMA tiles.
+ * Every value but 1 switches the skinny kernel off; N <= 64 or K % 64 != 0 always runs igemm_kernel; a split-K launch (a
+ * registered workspace, few tiles, a long K) takes 128 x 128 tiles whatever the value says.  The forced instances check less
+ * than the shipped rule does: they are for benchmarks at shapes known to suit them. */
 int yv_set_option(const char* key, int value);
 /* Current value of a knob.  "linear_p8_cus" (workgroups of the persistent classifier GEMMs; 0 = every CU) is PER THREAD: it
  * applies to the launches the calling thread makes (a pipelined runner lowers it around its own classifier submissions so that
@@ -98,6 +108,35 @@ int yv_linear_mxfp8_ex(const void* Aq, long long lda, const void* Ascale, long l
 /* Diagnostic: the kernel instance an MX linear of this shape and flags launches with dense operands (0: 128 x 128 tiles,
  * gemm_mx_kernel; 1: the persistent kernel), or a negative YV_ERR_* code if the arguments are not accepted. */
 int yv_linear_mxfp8_instance(int M, int N, int K, int flags);
+/* The route of a linear: the kernel yv_linear / yv_linear_ex (mx = 0) or yv_linear_mxfp8 / yv_linear_mxfp8_ex (mx = 1) launches
+ * for this shape, flags and strides under the current options, decided by the function the launch path itself calls.  Host
+ * only: nothing is dereferenced or launched, bases count as 16-byte aligned, MX operands as dense (scale rows rounded up to 128).
+ *   flags        as the launch takes them, plus YV_ROUTE_M_DEV where the launch would pass a device row count (m_dev);
+ *   has_res_f32  a separate f32 residual source (yv_linear_ex / yv_linear_mxfp8_ex);  ldaux > 0: an aux tensor of that row stride;
+ *   lda          in elements (mx: bytes);  ws_bytes: the split-K workspace registered for the stream (0: none);
+ *   n_cu         workgroups of a persistent launch before "linear_p8_cus" clips them; 0 = the CU count of the current device
+ *                (YV_ERR_LAUNCH where there is none).
+ * Returns YV_OK and fills *out, or the YV_ERR_* code with which the launch would reject the arguments. */
+#define YV_LIN_SKINNY 0 /* gemm_skinny_kernel, 64 x 16 tiles, K split over its eight waves                                  */
+#define YV_LIN_IGEMM 1  /* igemm_kernel<0, 128, tile_cols, ..>: register-staged                                             */
+#define YV_LIN_DMA 2    /* gemm_dma_kernel<tile_rows, tile_cols, .., abl>: LDS-DMA, with splitk > 1 + splitk_reduce_kernel  */
+#define YV_LIN_P8 3     /* gemm_p8_kernel<.., f32out>: persistent, 8-phase, tile_rows x 256                                 */
+#define YV_LIN_P9 4     /* gemm_p9_kernel<tile_rows / 32, f32out, 0, ext, mx>: persistent, free-running, tile_rows x 256    */
+#define YV_LIN_MX 5     /* gemm_mx_kernel<128, 128, 2, 2> (mx = 1 only)                                                     */
+#define YV_ROUTE_M_DEV 0x40000000 /* yv_linear_route's `flags` only */
+typedef struct {
+    int kernel;               /* YV_LIN_* */
+    int tile_rows, tile_cols; /* output tile of a workgroup */
+    int f32out;               /* persistent kernels: the f32 epilogue instance (f32 output or f32 residual) */
+    int ext;                  /* gemm_p9_kernel: trainer epilogue instance, 1 YV_EPI_SAVE_PRE, 2 YV_EPI_GELU_BWD */
+    int abl;                  /* gemm_dma_kernel: ablation 1 .. 4 ("linear_variant" 10x / 20x), else 0 */
+    int mx;                   /* MXFP8 operands */
+    int splitk;               /* K slices per tile (1: none) */
+    int staged;               /* GemmArgs::staged: the LDS-staged epilogue is usable */
+    int grid;                 /* workgroups launched (persistent kernels: min(tiles, CUs)) */
+} yv_linear_route_t;
+int yv_linear_route(int M, int N, int K, int lda, int ldo, int flags, int has_res_f32, int ldaux, int mx, size_t ws_bytes,
+                    int n_cu, yv_linear_route_t* out);
 /* MX weight gradient: dW (N, K) f32 (row stride ldw) = dY^T . X over T_pad tokens, from the column forms of
  * yv_quant_mxfp8_2d: dYt (N, T_pad) bytes (row stride ldy) + scales (T_pad/128, dy_rows_pad, 4), Xt (K, T_pad) bytes (row
  * stride ldx) + scales (T_pad/128, x_rows_pad, 4).  Split over tokens through the stream's workspace (yv_set_workspace);

@@ -46,6 +46,9 @@ def test_skinny_linear_exact_integer(yv, M, N, K, kind):
     x = torch.randint(-64, 65, (M, N), generator=g).float()
     flags = {"plain": 0, "gelu": yv.EPI_GELU, "res": yv.EPI_RES_F32, "f32": yv.EPI_OUT_F32}[kind]
     f32 = kind in ("res", "f32")
+    for m_dev in (False, True):
+        r = yv.linear_route(M, N, K, flags | yv.EPI_BIAS, m_dev=m_dev)
+        assert (r.kernel, r.tile_rows, r.tile_cols, r.splitk) == (yv.LIN_SKINNY, 64, 16, 1)
     wd, bd = bf(w).to(DEV), bias.to(DEV)
     fill = 3.0
 
@@ -115,9 +118,12 @@ def test_skinny_route_agrees_with_tiled_route(yv):
     w = bf(torch.randint(-2, 3, (N, K), generator=g).float()).to(DEV)
     bias = torch.randint(-8, 9, (N,), generator=g).float().to(DEV)
     o1 = torch.zeros(M, N, device=DEV); o2 = torch.zeros(M, N, device=DEV)
+    assert yv.linear_route(M, N, K, yv.EPI_BIAS | yv.EPI_OUT_F32).kernel == yv.LIN_SKINNY
     yv.linear(a, w, bias, o1, flags=yv.EPI_OUT_F32)
     yv.set_option("linear_skinny", 0)
     try:
+        r = yv.linear_route(M, N, K, yv.EPI_BIAS | yv.EPI_OUT_F32)
+        assert (r.kernel, r.tile_rows, r.tile_cols) == (yv.LIN_DMA, 128, 128)
         yv.linear(a, w, bias, o2, flags=yv.EPI_OUT_F32)
     finally:
         yv.set_option("linear_skinny", 256)

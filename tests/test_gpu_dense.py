@@ -74,6 +74,14 @@ def test_linear_epilogues(yv):
     assert torch.allclose(o2.cpu()[:150], lin[:150], atol=1e-3, rtol=1e-4) and float(o2[150:].abs().sum()) == 0
 
 
+# test_linear_exact_integer: the route of each shape under the shipped options, (family, tile rows) - the free-running persistent
+# kernel at three tile heights (96 rows where 160-row tiles would leave more than half the CUs idle), 128 x 128 LDS-DMA tiles
+# (M < 2,048, N % 256 != 0) and the skinny kernel (M <= 256)
+EXACT_ROUTES = {(6304, 768, 768): ("LIN_P9", 96), (6304, 2304, 768): ("LIN_P9", 256), (6304, 3072, 768): ("LIN_P9", 160),
+                (6304, 768, 3072): ("LIN_P9", 96), (1000, 768, 768): ("LIN_DMA", 128), (1000, 1000, 768): ("LIN_DMA", 128),
+                (130, 256, 1024): ("LIN_SKINNY", 64), (128 * 70 + 5, 640, 768): ("LIN_DMA", 128), (70000, 384, 768): ("LIN_DMA", 128)}
+
+
 @pytest.mark.parametrize("M,N,K,kind", [
     (25216 // 4, 768, 768, "res"), (6304, 2304, 768, "plain"), (6304, 3072, 768, "gelu"), (6304, 768, 3072, "res"),
     (1000, 768, 768, "res"), (1000, 1000, 768, "gelu"), (130, 256, 1024, "plain"), (128 * 70 + 5, 640, 768, "gelu"),
@@ -90,6 +98,9 @@ def test_linear_exact_integer(yv, M, N, K, kind):
     ad, wd, bd = bf(a).to(DEV), bf(w).to(DEV), bias.to(DEV)
     flags = {"plain": 0, "gelu": yv.EPI_GELU, "res": yv.EPI_RES_F32}[kind]
     x = torch.randint(-64, 65, (M, N), generator=g).float()
+    for m_dev in (False, True):
+        r = yv.linear_route(M, N, K, flags | yv.EPI_BIAS, m_dev=m_dev)
+        assert (r.kernel, r.tile_rows, r.splitk) == (getattr(yv, EXACT_ROUTES[M, N, K][0]), EXACT_ROUTES[M, N, K][1], 1), r
 
     def run(m_dev=None, m_mul=1):
         o = x.clone().to(DEV) if kind == "res" else torch.full((M, N), 3.0, dtype=torch.bfloat16, device=DEV)
@@ -143,6 +154,21 @@ def test_linear_persistent_8phase_exact_integer(yv, M, N, K, kind, rows, variant
     yv.set_option("linear_variant", variant)
     yv.set_option("linear_p8_rows", rows)
     try:
+        # the route: variant 9 the 8-phase kernel (from 128 rows; f32 epilogue up to 192), variant 11 the free-running one, but
+        # the 8-phase kernel for an f32 output with an odd K / 64 (K = 192).  The bf16-output 6,304 x 768 shapes with K = 2,304 /
+        # 3,072 are split-K material (300 tiles, 36 / 48 K steps: two slices) and a split comes before a forced variant: only their
+        # launch with a device row count reaches the persistent kernel.
+        p8 = variant == 9 or (f32 and (K // 64) % 2 == 1)
+        for m_dev in (False, True):
+            for fl in (flags, flags | yv.EPI_BIAS):
+                r = yv.linear_route(M, N, K, fl, m_dev=m_dev)
+                if kind == "plain" and (M, N, K) in ((6304, 768, 2304), (6304, 768, 3072)) and not m_dev:
+                    assert (r.kernel, r.tile_rows, r.tile_cols, r.splitk) == (yv.LIN_DMA, 128, 128, 2), r
+                    continue
+                assert (r.kernel, r.f32out, r.splitk) == (yv.LIN_P8 if p8 else yv.LIN_P9, int(f32), 1), r
+                if rows:
+                    assert r.tile_rows == (min(max(rows, 128), 192 if f32 else 256) if p8 else rows), r
+
         def run(m_dev=None, m_mul=1, with_bias=True):
             o = x.clone().to(DEV) if f32 else torch.full((M, N), 3.0, dtype=torch.bfloat16, device=DEV)
             yv.linear(ad, wd, bd if with_bias else None, o, flags=flags, m_dev=m_dev, m_mul=m_mul)
@@ -184,6 +210,7 @@ def test_linear_persistent_8phase_race_screen(yv):
     g = torch.Generator().manual_seed(0)
     side = torch.cuda.Stream()
     noise = torch.randn(4096, 4096, device=DEV, dtype=torch.bfloat16)
+    n_dev = torch.cuda.get_device_properties(0).multi_processor_count
     try:
         for (m, n, k) in ((12608, 768, 768), (6304, 2304, 768), (2048 + 37, 1536, 128)):
             a = bf(torch.randn(m, k, generator=g)).to(DEV); w = bf(torch.randn(n, k, generator=g) * 0.05).to(DEV)
@@ -191,6 +218,16 @@ def test_linear_persistent_8phase_race_screen(yv):
             for flags, dt in ((yv.EPI_GELU, torch.bfloat16), (yv.EPI_RES_F32, torch.float32)):
                 def run(variant, cus=0, rows=0):
                     yv.set_option("linear_variant", variant); yv.set_option("linear_p8_cus", cus); yv.set_option("linear_p8_rows", rows)
+                    # the route: variant 3 the 256 x 256 LDS-DMA kernel, variant 9 the 8-phase kernel at the forced height (f32
+                    # epilogue: up to 192 rows) on one workgroup per tile, at most "linear_p8_cus" / the device's CUs
+                    f32 = bool(flags & yv.EPI_RES_F32)
+                    rt = yv.linear_route(m, n, k, flags | yv.EPI_BIAS)
+                    if variant == 3:
+                        assert (rt.kernel, rt.tile_rows, rt.tile_cols, rt.splitk) == (yv.LIN_DMA, 256, 256, 1), rt
+                    else:
+                        assert (rt.kernel, rt.f32out, rt.splitk) == (yv.LIN_P8, int(f32), 1), rt
+                        assert rt.tile_rows == (min(rows, 192 if f32 else 256) if rows else rt.tile_rows) and rt.tile_rows in (128, 160, 192, 224, 256), rt
+                        assert rt.grid == min(-(-m // rt.tile_rows) * (n // 256), cus or n_dev), rt
                     out = res0.clone() if flags & yv.EPI_RES_F32 else torch.full((m, n), 3.0, dtype=dt, device=DEV)
                     yv.linear(a, w, bias, out, flags=flags)
                     return out
@@ -205,6 +242,14 @@ def test_linear_persistent_8phase_race_screen(yv):
         torch.cuda.synchronize()
     finally:
         yv.set_option("linear_variant", 1); yv.set_option("linear_p8_cus", 0); yv.set_option("linear_p8_rows", 0)
+
+
+# test_linear_free_running_trainer_epilogues: the forms that reach gemm_p9_kernel under "linear_p8" = 3, with the tile height it
+# picks when none is forced.  N = 3,072 is wide enough for every form; below 192 tiles of 160 rows only the f32-residual form
+# goes on (96 / 128-row tiles have no trainer epilogue), and 2,085 x 768 has too few tiles of any height: there both runs of the
+# comparison are the 128 x 128 kernel.
+TRAINER_P9 = {(6304, 3072, 768): {"resf": 160, "save_pre": 160, "gelu_bwd": 160}, (6304, 768, 3072): {"resf": 96},
+              (2048 + 37, 768, 256): {}, (6304, 768, 768): {"resf": 96}, (9999, 512, 128): {"resf": 96}}
 
 
 @pytest.mark.parametrize("M,N,K,rows", [(6304, 3072, 768, 0), (6304, 768, 3072, 0), (2048 + 37, 768, 256, 160), (6304, 768, 768, 192),
@@ -222,6 +267,13 @@ def test_linear_free_running_trainer_epilogues(yv, M, N, K, rows):
 
     def run(p8, form):
         yv.set_option("linear_p8", p8); yv.set_option("linear_p8_rows", rows if p8 else 0)
+        fl = {"resf": yv.EPI_BIAS | yv.EPI_RES_F32, "save_pre": yv.EPI_BIAS | yv.EPI_GELU | yv.EPI_SAVE_PRE, "gelu_bwd": yv.EPI_GELU_BWD}[form]
+        r = yv.linear_route(M, N, K, fl, res_f32=form == "resf", ldaux=0 if form == "resf" else N)
+        if p8 and form in TRAINER_P9[M, N, K]:
+            want = rows if rows else TRAINER_P9[M, N, K][form]
+            assert (r.kernel, r.tile_rows, r.ext, r.f32out) == (yv.LIN_P9, want, ("resf", "save_pre", "gelu_bwd").index(form), int(form == "resf")), r
+        else:
+            assert (r.kernel, r.tile_rows, r.tile_cols) == (yv.LIN_DMA, 128, 128), r
         if form == "resf":
             out = torch.full((M, N), 7.0, device=DEV)
             yv.linear_ex(a, w, bias, out, flags=yv.EPI_RES_F32, res_f32=xin)
@@ -272,6 +324,8 @@ def test_gelu_fast_form_accuracy(yv):
     o = torch.zeros(M, N, dtype=torch.bfloat16, device=DEV)
     yv.set_option("linear_variant", 9)
     try:
+        r = yv.linear_route(M, N, K, yv.EPI_GELU)
+        assert (r.kernel, r.tile_cols, r.f32out, r.splitk) == (yv.LIN_P8, 256, 0, 1), r
         yv.linear(a.to(DEV), bf(w).to(DEV), None, o, flags=yv.EPI_GELU)
     finally:
         yv.set_option("linear_variant", 1)

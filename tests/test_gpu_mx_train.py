@@ -116,7 +116,16 @@ def _epilogue_case(yv, kind, M, N, K, seed):
     ("save_pre", 6304, 3072, 640, 1), ("gelu_bwd", 6304, 3072, 640, 1)])          # odd K / 128: 224-row tiles
 def test_mx_linear_ex_epilogues(yv, kind, M, N, K, inst):
     bias_on = kind != "gelu_bwd"
-    assert yv.linear_mxfp8_instance(M, N, K, _FLAGS(yv)[kind] | (yv.EPI_BIAS if bias_on else 0)) == inst
+    flags = _FLAGS(yv)[kind] | (yv.EPI_BIAS if bias_on else 0)
+    assert yv.linear_mxfp8_instance(M, N, K, flags) == inst
+    # the persistent kernel's tile height: 160 rows by the ViT-B/16 shapes, 224 by the ViT-L/16 shapes and by an odd K / 128
+    r = yv.linear_route(M, N, K, flags, mx=True, res_f32=kind == "res_src", ldaux=0 if kind == "res_src" else N)
+    rows = {(6304, 3072, 768): 160, (12608, 768, 768): 160, (6304, 4096, 1024): 224, (6304, 3072, 640): 224}
+    if inst:
+        assert (r.kernel, r.tile_rows, r.mx, r.ext, r.f32out) == (yv.LIN_P9, rows[M, N, K], 1, ["res_src", "save_pre", "gelu_bwd"].index(kind),
+                                                                  int(kind == "res_src")), r
+    else:
+        assert (r.kernel, r.tile_rows, r.tile_cols, r.splitk) == (yv.LIN_MX, 128, 128, 1), r
     _epilogue_case(yv, kind, M, N, K, M + N + K + inst)
 
 
@@ -131,6 +140,8 @@ def test_mx_linear_ex_persistent_tile_heights(yv, kind):
         outs = {}
         for rows in (0, 160, 192, 224):
             yv.set_option("linear_p8_rows", rows)
+            r = yv.linear_route(M, N, K, _FLAGS(yv)[kind] | (yv.EPI_BIAS if kind == "save_pre" else 0), mx=True, ldaux=N)
+            assert (r.kernel, r.tile_rows, r.ext) == (yv.LIN_P9, rows if rows else 160, 1 if kind == "save_pre" else 2), r
             outs[rows] = _epilogue_case(yv, kind, M, N, K, 77)
     finally:
         yv.set_option("linear_p8_rows", prev)

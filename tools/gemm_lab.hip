@@ -193,15 +193,21 @@ int main(int argc, char** argv) {
         ps.push_back(make_problem("dproj", M, 768, 768, 0));
     }
     std::vector<Variant> vs;
-    vs.push_back({"p8 (shipped)", [](GemmArgs& g, hipStream_t st) { return launch_p8(g, st); }});
+    // the launch path's two steps: the pure tile-height rule, then the instance of that height (n: the persistent grid)
+    const auto p8 = [](GemmArgs& g, hipStream_t st) {
+        const int n = persistent_cus();
+        return launch_p8(g, st, p8_tile_rows(g.M, g.N, g.flags, n), n);
+    };
+    const auto p9 = [](int rows) {
+        return [rows](GemmArgs& g, hipStream_t st) {
+            const int n = persistent_cus();
+            return launch_p9(g, st, p9_tile_rows(g.M, g.N, g.K, g.flags, false, n, rows), n, false);
+        };
+    };
+    vs.push_back({"p8 (shipped)", p8});
     if (getenv("LAB_R1")) vs.push_back({"dma128 (round 1)", [](GemmArgs& g, hipStream_t st) { return launch_dma<128, 128, 2, 2>(g, st); }});
-    vs.push_back({"p9 auto", [](GemmArgs& g, hipStream_t st) { return launch_p9(g, st, 0); }});
-    vs.push_back({"p9 256", [](GemmArgs& g, hipStream_t st) { return launch_p9(g, st, 256); }});
-    vs.push_back({"p9 224", [](GemmArgs& g, hipStream_t st) { return launch_p9(g, st, 224); }});
-    vs.push_back({"p9 192", [](GemmArgs& g, hipStream_t st) { return launch_p9(g, st, 192); }});
-    vs.push_back({"p9 160", [](GemmArgs& g, hipStream_t st) { return launch_p9(g, st, 160); }});
-    vs.push_back({"p9 128", [](GemmArgs& g, hipStream_t st) { return launch_p9(g, st, 128); }});
-    vs.push_back({"p9 96", [](GemmArgs& g, hipStream_t st) { return launch_p9(g, st, 96); }});
+    vs.push_back({"p9 auto", p9(0)});
+    for (int rows : {256, 224, 192, 160, 128, 96}) vs.push_back({"p9 " + std::to_string(rows), p9(rows)});
     double tot_fl = 0; std::vector<double> tot_us(vs.size(), 0.0);
     for (auto& p : ps) {
         // reference = shipped kernel

@@ -1891,6 +1891,122 @@ int conv_instance_code(const GemmArgs& g, int kern) {
     return kern | (staged ? 16 : 0) | (split ? 32 : 0) | (two ? 64 : 0);
 }
 
+// The route of a linear: ONE rule per operand type (linear_route: bf16, mx_linear_route: MXFP8) for the launch path and for
+// yv_linear_route, which reports it without a device.  Pure: shape, flags, strides, null-ness of the pointers and options in, a
+// LinearRoute out.  Pinned by tests/test_linear_routes_cpu.py; order, reasons and measurements: DESIGN.md section 19.
+using LinearRoute = yv_linear_route_t;
+struct LinearQuery { LinearRoute* out; size_t ws_bytes; int n_cu; };     // yv_linear_route: report the route, launch nothing
+long long tiles_of(int M, int N, int rows) { return (long long)((M + rows - 1) / rows) * (N >> 8); }     // rows x 256 tiles
+
+LinearRoute route_of(const GemmArgs& g, int kernel, int bm, int bn, int splitk = 1, int abl = 0) {
+    LinearRoute r = {};
+    r.kernel = kernel; r.tile_rows = bm; r.tile_cols = bn; r.abl = abl; r.splitk = splitk; r.staged = g.staged;
+    r.grid = ((g.M + bm - 1) / bm) * ((g.N + bn - 1) / bn) * splitk;
+    return r;
+}
+
+LinearRoute persistent_route(const GemmArgs& g, int kernel, int rows, bool mx, int n_cu) {
+    LinearRoute r = route_of(g, kernel, rows, 256);
+    if (r.grid > n_cu) r.grid = n_cu;
+    const bool f32o = g.flags & (YV_EPI_RES_F32 | YV_EPI_OUT_F32);
+    r.mx = mx;
+    r.ext = kernel != YV_LIN_P9 ? 0 : (g.flags & YV_EPI_SAVE_PRE) ? 1 : (g.flags & YV_EPI_GELU_BWD) ? 2 : 0;
+    r.f32out = f32o && !r.ext && (kernel == YV_LIN_P9 || rows <= 192);      // (gemm_p8_kernel: launch_p8_inst)
+    return r;
+}
+
+// What the persistent kernels ask of a linear's shape (kstep: 64 bf16 / 128 MXFP8 elements): 256-column tiles up to 4,096 columns,
+// two K steps, output rows of 8-element stride ...
+bool persistent_shape(int N, int K, int ldo, int kstep) { return !(N & 255) && N <= 4096 && K >= 2 * kstep && !(ldo & 7); }
+// ... and of the launch (esz: bytes per operand element): no GELU before an f32 output, 32-bit byte offsets everywhere
+bool persistent_ok(int M, int N, int K, long long lda, int ldo, int flags, bool aux, int ldaux, int esz) {
+    const long long lim = 0x7fffffffLL;
+    return persistent_shape(N, K, ldo, 128 / esz) && !((flags & YV_EPI_GELU) && (flags & (YV_EPI_RES_F32 | YV_EPI_OUT_F32))) &&
+           ((long long)(M - 1) * lda + K) * esz < lim && (long long)N * K * esz < lim &&
+           ((long long)(M - 1) * ldo + N) * 4 < lim && (!aux || ((long long)(M - 1) * ldaux + N) * 2 < lim);
+}
+
+// the forms split-K takes (linear_impl looks the stream's workspace up for these only: a lock the classifier's linears never take)
+bool splitk_form(const GemmArgs& g) { return g_opt_linear_splitk && !(g.flags & ~(YV_EPI_BIAS | YV_EPI_OUT_F32)) && !g.m_dev; }
+
+LinearRoute linear_route(const GemmArgs& g, bool have_ws, size_t ws_bytes, int n_cu) {
+    const int M = g.M, N = g.N, K = g.K, flags = g.flags, v = g_opt_variant;
+    const bool f32o = flags & (YV_EPI_RES_F32 | YV_EPI_OUT_F32), ext = flags & (YV_EPI_SAVE_PRE | YV_EPI_GELU_BWD);
+    // (plain: the forms every family takes - no pos_embed, nothing of yv_linear_ex)
+    const bool plain = !(flags & ~(YV_EPI_BIAS | YV_EPI_GELU | YV_EPI_RES_F32 | YV_EPI_OUT_F32)) && !g.resf && !g.aux;
+    // 1. one row per crop (the classifier's cls-row tail, the head): gemm_skinny_kernel; 2. register-staged tiles
+    if (v == 1 && M <= g_opt_skinny && !(N & 15) && !(K & 31) && plain) return route_of(g, YV_LIN_SKINNY, 64, 16);
+    if ((K % BK) || N <= 64 || v == 0) return route_of(g, YV_LIN_IGEMM, 128, 16 << igemm_pick(N));
+    // 3. split-K for wgrad-shaped problems (few 128 x 128 tiles, a long reduction), partial sums in the stream's workspace, added in
+    // slice order by splitk_reduce_kernel; not where the free-running kernel's 96-row tiles fill the chip (the 6,304 x 768 x 768
+    // data gradients).  It comes before a forced variant, which it overrides.
+    const bool small_fills = g_opt_p9_small && tiles_of(M, N, 96) >= 128;
+    const bool p9_small_shape = v == 1 && g_opt_p8 >= 3 && M >= 2048 && persistent_shape(N, K, g.ldo, BK) && small_fills;
+    if (have_ws && splitk_form(g) && !p9_small_shape) {
+        const long long tiles = (long long)((M + 127) / 128) * ((N + 127) / 128);
+        const int nk = K / BK;
+        int S = (int)(768 / tiles);
+        if (S > nk / 4) S = nk / 4;
+        if (S > 8) S = 8;
+        if (S >= 2 && (size_t)S * M * N * sizeof(float) <= ws_bytes) return route_of(g, YV_LIN_DMA, 128, 128, S);
+    }
+    // 4. a forced LDS-DMA instance (101 .. 104 / 201 .. 204: the ablations ABL of gemm_dma_kernel)
+    switch (v) {
+        case 2: return route_of(g, YV_LIN_DMA, 256, 128);
+        case 3: return route_of(g, YV_LIN_DMA, 256, 256);
+        case 4: return route_of(g, YV_LIN_DMA, 128, 256);
+        case 101: case 102: case 103: case 104: return route_of(g, YV_LIN_DMA, 128, 128, 1, v - 100);
+        case 201: case 202: case 203: case 204: return route_of(g, YV_LIN_DMA, 256, 256, 1, v - 200);
+    }
+    // 5. the persistent kernels, by the shape under "linear_p8" or forced ("linear_variant" 9 / 11).  train: the forms of
+    // yv_linear_ex, which only the free-running kernel has (K / 64 even)
+    const bool train = g_opt_p8 >= 3 && !(flags & ~(YV_EPI_BIAS | YV_EPI_GELU | YV_EPI_RES_F32 | YV_EPI_SAVE_PRE | YV_EPI_GELU_BWD)) &&
+                       (!g.resf || (flags & YV_EPI_RES_F32)) && (!(flags & YV_EPI_SAVE_PRE) || (flags & YV_EPI_GELU)) &&
+                       !((flags & YV_EPI_GELU_BWD) && (flags & (YV_EPI_GELU | YV_EPI_SAVE_PRE))) && (g.resf || g.aux) && !((K / BK) & 1);
+    const bool asked = v == 1 ? g_opt_p8 && M >= 2048 && (N >= 1536 || g_opt_p8 >= 2) : (v == 9 || v == 11);
+    if (asked && (train || plain) && g.staged && persistent_ok(M, N, K, g.lda0, g.ldo, flags, g.aux != nullptr, g.ldaux, 2)) {
+        const bool free_running = v == 1 ? g_opt_p8 >= 3 : v == 11;
+        // enough tiles for the chip: 192 of 160 rows or, without a trainer epilogue, 128 of 96 rows
+        const bool fills = v != 1 || tiles_of(M, N, 160) >= 192 || (small_fills && !ext);
+        // (f32 outputs: 160-row tiles, whose K tiles are walked in pairs; the 8-phase kernel takes an odd K / 64)
+        if (free_running && fills && !(f32o && ((K / BK) & 1)))
+            return persistent_route(g, YV_LIN_P9, p9_tile_rows(M, N, K, flags, false, n_cu, 0), false, n_cu);
+        if (free_running ? fills : !train) return persistent_route(g, YV_LIN_P8, p8_tile_rows(M, N, flags, n_cu), false, n_cu);
+    }
+    // 6. 128 x 128 tiles, two workgroups per CU
+    return route_of(g, YV_LIN_DMA, 128, 128);
+}
+
+// MXFP8 operands: the free-running persistent kernel (tests/test_gpu_mx_train.py::test_mx_linear_ex_epilogues reaches each
+// epilogue family on it and on the other), else gemm_mx_kernel<128, 128, 2, 2>
+LinearRoute mx_linear_route(const GemmArgs& g, long long lda, long long a_rows, long long w_rows, int n_cu) {
+    const int M = g.M, N = g.N, K = g.K, flags = g.flags, nkm = K >> 7;
+    const bool f32o = flags & (YV_EPI_RES_F32 | YV_EPI_OUT_F32), ext = flags & (YV_EPI_SAVE_PRE | YV_EPI_GELU_BWD);
+    if (g_opt_p8 >= 3 && g_opt_variant == 1 && M >= 2048 && tiles_of(M, N, 160) >= 192 &&
+        persistent_ok(M, N, K, lda, g.ldo, flags, ext, g.ldaux, 1) && !((flags & YV_EPI_OUT_MXFP8) && f32o) && !(f32o && (nkm & 1)) &&
+        (long long)nkm * a_rows * 4 < 0x7fffffffLL && (long long)nkm * w_rows * 4 < 0x7fffffffLL)
+        return persistent_route(g, YV_LIN_P9, p9_tile_rows(M, N, K, flags, true, n_cu, 0), true, n_cu);
+    LinearRoute r = route_of(g, YV_LIN_MX, 128, 128);
+    return r.mx = 1, r;
+}
+
+// Token slices of a weight gradient of `tiles` 128 x 128 output tiles (out_bytes together) over T tokens (1: no split).  Conv
+// shapes (1-16 tiles over 10^5+ output pixels): up to "wgrad_split_cap" slices of >= 512 rows.  Matrix shapes: ONE round of the
+// 512 workgroup slots - a second, partly filled round costs more than the longer slices of the first save (tools/wgrad_bench.py:
+// dW 2304 x 768 over 6,336 tokens 43 us at S = 4, 65 us at S = 5)
+int wgrad_slices(long long tiles, int T, size_t out_bytes, size_t ws_bytes) {
+    int S = (int)((tiles <= 16 ? 1024 : 512) / tiles);
+    if (S < 1) S = 1;
+    const int cap = tiles <= 16 ? g_opt_wgrad_cap : 16;
+    const int min_rows = tiles <= 16 ? 512 : 128;
+    if (S > T / min_rows) S = T / min_rows;
+    if (S > cap) S = cap;
+    if (tiles > 16 && g_opt_wgrad_split > 0) S = g_opt_wgrad_split;
+    const size_t fit = ws_bytes / out_bytes;
+    if ((size_t)S > fit) S = (int)fit;
+    return S >= 2 ? S : 1;
+}
+
 // Images per sub-batch of a convolution (32-bit byte offsets: each source below 2 GB): s0 / s1 bytes per image of the sources
 // (s1 = 0: one source), `lead` bytes addressed in front of source 0.  < 1: a single image is too large.
 long long conv_sub_batch(long long s0, long long s1, long long lead) {
@@ -1931,7 +2047,7 @@ static int linear_mx_impl(const void* Aq, long long lda, const void* Ascale, lon
                           const void* Wscale, long long w_rows_pad, const float* bias, int M, int N, int K, void* out,
                           int ldo, int flags, const int32_t* m_dev, int m_mul, void* out_q, long long ldq, void* out_scales,
                           long long out_rows_pad, void* stream, const float* res_f32 = nullptr, void* aux = nullptr,
-                          int ldaux = 0);
+                          int ldaux = 0, const LinearQuery* q = nullptr);
 
 extern "C" int yv_linear_mxfp8(const void* Aq, long long lda, const void* Ascale, long long a_rows_pad, const void* Wq,
                                const void* Wscale, long long w_rows_pad, const float* bias, int M, int N, int K, void* out,
@@ -1949,26 +2065,6 @@ extern "C" int yv_linear_mxfp8_q(const void* Aq, long long lda, const void* Asca
     if (flags & ~(YV_EPI_BIAS | YV_EPI_GELU)) return YV_ERR_ARG;
     return linear_mx_impl(Aq, lda, Ascale, a_rows_pad, Wq, Wscale, w_rows_pad, bias, M, N, K, out_q, (int)ldq,
                           flags | YV_EPI_OUT_MXFP8, m_dev, m_mul, out_q, ldq, out_scales, out_rows_pad, stream);
-}
-
-// Instance of an MX linear (0: gemm_mx_kernel 128 x 128, 1: persistent gemm_p9_kernel<..., MX>).  One rule for
-// linear_mx_impl and the diagnostic yv_linear_mxfp8_instance.  Instances reached by tests/test_gpu_mx_train.py:
-//   1 with SAVE_PRE / GELU_BWD / RES_F32 epilogues: test_mx_linear_ex_epilogues (M = 6,304 / 12,608 shapes; the tile height inside
-//     the persistent kernel is launch_p9's choice: see the tests named at its MX switch arms);
-//   0 with the same epilogues: test_mx_linear_ex_epilogues (N = 768 at M = 6,304, M < 2,048) and every split-K weight gradient
-//     (test_wgrad_mxfp8_exact).
-static int mx_linear_pick(int M, int N, int K, long long lda, int ldo, long long a_rows, long long w_rows, int flags, int ldaux) {
-    const int nkm = K >> 7;
-    const bool f32o = flags & (YV_EPI_RES_F32 | YV_EPI_OUT_F32);
-    const bool ext = flags & (YV_EPI_SAVE_PRE | YV_EPI_GELU_BWD);
-    if (g_opt_p8 >= 3 && g_opt_variant == 1 && !(N & 255) && N <= 4096 && nkm >= 2 && M >= 2048 &&
-        !((flags & YV_EPI_GELU) && f32o) && !((flags & YV_EPI_OUT_MXFP8) && f32o) && !(f32o && (nkm & 1)) &&
-        (long long)((M + 159) / 160) * (N >> 8) >= 192 &&
-        (long long)(M - 1) * lda + K < 0x7fffffffLL && (long long)N * K < 0x7fffffffLL &&
-        ((long long)(M - 1) * ldo + N) * 4 < 0x7fffffffLL && (long long)(K >> 7) * a_rows * 4 < 0x7fffffffLL &&
-        (long long)(K >> 7) * w_rows * 4 < 0x7fffffffLL && (!ext || ((long long)(M - 1) * ldaux + N) * 2 < 0x7fffffffLL))
-        return 1;
-    return 0;
 }
 
 // gemm_mx_kernel<128, 128, 2, 2> (split-K when g.splitk > 1: partials into g.partial, then splitk_reduce_kernel)
@@ -2004,7 +2100,7 @@ static bool mx_flags_ok(int flags, const float* res_f32, const void* aux, int ld
 static int linear_mx_impl(const void* Aq, long long lda, const void* Ascale, long long a_rows_pad, const void* Wq,
                           const void* Wscale, long long w_rows_pad, const float* bias, int M, int N, int K, void* out,
                           int ldo, int flags, const int32_t* m_dev, int m_mul, void* out_q, long long ldq, void* out_scales,
-                          long long out_rows_pad, void* stream, const float* res_f32, void* aux, int ldaux) {
+                          long long out_rows_pad, void* stream, const float* res_f32, void* aux, int ldaux, const LinearQuery* q) {
     if (!Aq || !Ascale || !Wq || !Wscale || !out || M < 0 || N <= 0 || K <= 0) return YV_ERR_ARG;
     if ((K & 127) || (lda & 15) || (N & 7) || (ldo & 7)) return YV_ERR_ARG;             // whole 128-element K steps
     if (a_rows_pad < M || (a_rows_pad & 127) || w_rows_pad < N || (w_rows_pad & 127)) return YV_ERR_ARG;
@@ -2024,12 +2120,13 @@ static int linear_mx_impl(const void* Aq, long long lda, const void* Ascale, lon
     g.group_m = g_opt_group_m > 0 ? g_opt_group_m : 8;
     a.sa = (const uint8_t*)Ascale; a.sw = (const uint8_t*)Wscale; a.rows_a = a_rows_pad; a.rows_w = w_rows_pad;
     g.mxq = (uint8_t*)out_q; g.ldmxq = ldq; g.mxs = (uint8_t*)out_scales; g.mx_rows = out_rows_pad;
-    // persistent free-running kernel (round 3): the bf16 schedule with one block-scaled MFMA per fragment pair and K tile
+    // (persistent kernel: the bf16 schedule with one block-scaled MFMA per fragment pair and K tile)
     g.mx_sa = a.sa; g.mx_sw = a.sw; g.mx_rows_a = a.rows_a; g.mx_rows_w = a.rows_w;
-    if (mx_linear_pick(M, N, K, lda, ldo, a_rows_pad, w_rows_pad, flags, ldaux) == 1)
-        return launch_p9(g, (hipStream_t)stream, 0, true);
-    // (a 256 x 128 / 8-wave instance of the same template was measured on the ViT-L shapes: 4-15 % slower than two
-    // 128 x 128 workgroups per CU, like its bf16 counterpart, and is not dispatched)
+    const int n_cu = q ? q->n_cu : persistent_cus();
+    if (!n_cu) return YV_ERR_LAUNCH;
+    const LinearRoute r = mx_linear_route(g, lda, a_rows_pad, w_rows_pad, n_cu);
+    if (q) { *q->out = r; return YV_OK; }
+    if (r.kernel == YV_LIN_P9) return launch_p9(g, (hipStream_t)stream, r.tile_rows, n_cu, true);
     return launch_mx128(a, (hipStream_t)stream);
 }
 
@@ -2042,12 +2139,10 @@ extern "C" int yv_linear_mxfp8_ex(const void* Aq, long long lda, const void* Asc
 }
 
 extern "C" int yv_linear_mxfp8_instance(int M, int N, int K, int flags) {
-    if (M <= 0 || N <= 0 || K <= 0 || (K & 127) || (N & 7) || (flags & YV_EPI_OUT_MXFP8)) return YV_ERR_ARG;
-    // dense operands (lda = K, ldo = ldaux = N) and scale rows rounded up to 128, as the trainer allocates them
-    const bool ext = flags & (YV_EPI_SAVE_PRE | YV_EPI_GELU_BWD);
-    static unsigned char dummy[16] __attribute__((aligned(16)));
-    if (!mx_flags_ok(flags, nullptr, ext ? (const void*)dummy : nullptr, ext ? N : 0)) return YV_ERR_ARG;
-    return mx_linear_pick(M, N, K, K, N, (M + 127) / 128 * 128LL, (N + 127) / 128 * 128LL, flags, N);
+    // dense operands (lda = K, ldo = ldaux = N); the kernel family does not depend on the CU count
+    LinearRoute r;
+    const int rc = yv_linear_route(M, N, K, K, N, flags, 0, (flags & (YV_EPI_SAVE_PRE | YV_EPI_GELU_BWD)) ? N : 0, 1, 0, 256, &r);
+    return rc != YV_OK ? rc : r.kernel == YV_LIN_P9;
 }
 
 int g_opt_wgrad_mx_split = 0;      // > 0: forced number of token slices of the MX weight gradient ("wgrad_mx_split"; 1 = off)
@@ -2150,9 +2245,37 @@ extern "C" int yv_get_option(const char* key, int* value) {
     return YV_OK;
 }
 
+// Launches the route: no decisions.  ws: the workspace the route was told of.
+static int launch_linear(GemmArgs& g, const LinearRoute& r, void* ws, int n_cu, hipStream_t st) {
+    g.splitk = r.splitk;
+    if (r.splitk > 1) g.partial = (float*)ws;
+    switch (r.kernel) {
+        case YV_LIN_SKINNY: return launch_skinny(g, st);
+        case YV_LIN_P8: return launch_p8(g, st, r.tile_rows, n_cu);
+        case YV_LIN_P9: return launch_p9(g, st, r.tile_rows, n_cu, r.mx);
+    }
+    if (r.kernel == YV_LIN_DMA)
+        switch ((r.tile_rows >> 7) * 100 + (r.tile_cols >> 7) * 10 + r.abl) {      // gemm_dma_kernel<rows, columns, waves, ABL>
+            case 210: return launch_dma<256, 128, 4, 2>(g, st);
+            case 220: return launch_dma<256, 256, 2, 4>(g, st);
+            case 120: return launch_dma<128, 256, 2, 4>(g, st);
+            case 221: return launch_dma<256, 256, 2, 4, 1>(g, st);
+            case 222: return launch_dma<256, 256, 2, 4, 2>(g, st);
+            case 223: return launch_dma<256, 256, 2, 4, 3>(g, st);
+            case 224: return launch_dma<256, 256, 2, 4, 4>(g, st);
+            case 111: return launch_dma<128, 128, 2, 2, 1>(g, st);
+            case 112: return launch_dma<128, 128, 2, 2, 2>(g, st);
+            case 113: return launch_dma<128, 128, 2, 2, 3>(g, st);
+            case 114: return launch_dma<128, 128, 2, 2, 4>(g, st);
+            default: return launch_dma<128, 128, 2, 2>(g, st);
+        }
+    // (named last, as before: kernels are emitted in the order they are named, and igemm_kernel addresses g_zero_page pc-relative)
+    return launch_igemm<0>(g, igemm_pick(r.tile_cols), st);
+}
+
 static int linear_impl(const void* A, int lda, const void* W, const float* bias, int M, int N, int K, void* out, int ldo,
                        const float* pos, int tok, int flags, const int32_t* m_dev, int m_mul, const float* res_f32,
-                       void* aux, int ldaux, hipStream_t stream) {
+                       void* aux, int ldaux, hipStream_t stream, const LinearQuery* q = nullptr) {
     if (!A || !W || !out || M < 0 || N <= 0 || K <= 0) return YV_ERR_ARG;
     if ((K & 7) || (lda & 7) || (N & 3) || (ldo & 3)) return YV_ERR_ARG;            // 16-byte operand chunks, 4-wide stores
     if ((flags & YV_EPI_BIAS) && !bias) return YV_ERR_ARG;
@@ -2171,77 +2294,14 @@ static int linear_impl(const void* A, int lda, const void* W, const float* bias,
     if ((flags & (YV_EPI_SAVE_PRE | YV_EPI_GELU_BWD)) && (!g.staged || (K % BK) || N <= 64)) return YV_ERR_ARG;
     if (res_f32 && (!g.staged || (K % BK) || N <= 64)) return YV_ERR_ARG;
     g.group_m = g_opt_group_m > 0 ? g_opt_group_m : 8;
-    g.splitk = 1;
-    // one row per crop (the cls-row tail of the classifier's last block, the head): a weight-streaming pass, see gemm_skinny_kernel
-    if (g_opt_variant == 1 && M <= g_opt_skinny && !(N & 15) && !(K & 31) && !res_f32 && !aux &&
-        !(flags & ~(YV_EPI_BIAS | YV_EPI_GELU | YV_EPI_RES_F32 | YV_EPI_OUT_F32)))
-        return launch_skinny(g, stream);
-    if ((K % BK) == 0 && N > 64 && g_opt_variant != 0) {
-        // split-K for wgrad-shaped problems (few 128x128 output tiles, long reduction): a 2304x768 weight gradient
-        // over 6336 tokens is 108 tiles for 256 CUs; slicing K fills the chip.  Deterministic: partial sums go to
-        // the stream's workspace and are added in slice order by splitk_reduce_kernel.
-        void* ws = nullptr; size_t wsb = 0;
-        // (not where the free-running kernel's 96-row tiles fill the chip in one round: the trainer's 6,304 x 768 data gradients were
-        // two K slices of 300 tiles + a reduce pass; as 198 tiles of 96 x 256 the fine-tune step is 9.20 -> 9.00 ms)
-        const bool p9_small_route = g_opt_variant == 1 && g_opt_p8 >= 3 && g_opt_p9_small && !(N & 255) && N <= 4096 && M >= 2048 &&
-                                    K >= 128 && (long long)((M + 95) / 96) * (N >> 8) >= 128 && !(ldo & 7);
-        if (g_opt_linear_splitk && !p9_small_route && !(flags & ~(YV_EPI_BIAS | YV_EPI_OUT_F32)) && !m_dev && ws_lookup((void*)stream, &ws, &wsb)) {
-            const long long tiles = (long long)((M + 127) / 128) * ((N + 127) / 128);
-            const int nk = K / BK;
-            int S = (int)(768 / tiles);
-            if (S > nk / 4) S = nk / 4;
-            if (S > 8) S = 8;
-            if (S >= 2 && (size_t)S * M * N * sizeof(float) <= wsb) { g.splitk = S; g.partial = (float*)ws; }
-        }
-        int variant = g_opt_variant;
-        if (g.splitk > 1) variant = 10;
-        // auto: 128x128 tiles, two workgroups per CU (one workgroup's epilogue overlaps the other's main loop).
-        // Isolated, the 8-phase 256x256 kernel is 3-13 % faster on N >= 1536, but inside the pipeline (operands
-        // cold in L2, GELU / residual epilogues) the interleaved end-to-end A/B measures it 1-2 % slower.
-        // persistent 8-phase kernel: wide bf16-output linears (the qkv / fc1 shapes), see gemm_p8_kernel for its restrictions
-        // (the free-running kernel also takes the trainer's forms: a separate f32 residual source, YV_EPI_SAVE_PRE, YV_EPI_GELU_BWD)
-        const bool p9_train = g_opt_p8 >= 3 && !(flags & ~(YV_EPI_BIAS | YV_EPI_GELU | YV_EPI_RES_F32 | YV_EPI_SAVE_PRE | YV_EPI_GELU_BWD)) &&
-                              (!res_f32 || (flags & YV_EPI_RES_F32)) &&
-                              (!(flags & YV_EPI_SAVE_PRE) || (flags & YV_EPI_GELU)) && !((flags & YV_EPI_GELU_BWD) && (flags & (YV_EPI_GELU | YV_EPI_SAVE_PRE))) &&
-                              (!aux || ((long long)(M - 1) * ldaux + N) * 2 < 0x7fffffffLL) && (res_f32 || aux) && !((K / BK) & 1);
-        const bool p8_ok = !(N & 255) && N <= 4096 && K >= 128 &&
-                           (p9_train || (!(flags & ~(YV_EPI_BIAS | YV_EPI_GELU | YV_EPI_RES_F32 | YV_EPI_OUT_F32)) && !res_f32 && !aux)) &&
-                           !((flags & YV_EPI_GELU) && (flags & (YV_EPI_RES_F32 | YV_EPI_OUT_F32))) && g.staged &&
-                           ((long long)(M - 1) * lda + K) * 2 < 0x7fffffffLL && (long long)N * K * 2 < 0x7fffffffLL &&
-                           ((long long)(M - 1) * ldo + N) * 4 < 0x7fffffffLL && !(ldo & 7) && !(lda & 7);
-        if (variant == 1 && g_opt_p8 && p8_ok && M >= 2048 && (N >= 1536 || g_opt_p8 >= 2)) variant = g_opt_p8 >= 3 ? 11 : 9;
-        if ((variant == 9 || variant == 11) && !p8_ok) variant = 1;
-        if (variant == 9 && p9_train) variant = 1;                  // (those forms exist in the free-running kernel only)
-        // a persistent grid of 256-column tiles needs enough tiles for the chip: the trainer's 6,304 x 768 products are 120 tiles of
-        // 160 rows - fewer than half the CUs - and run faster as 300 tiles of 128 x 128 at two workgroups per CU (measured: the
-        // fine-tune step 9.65 -> 9.9 ms with them on the persistent kernel)
-        // (round 3, later: 96 / 128-row tiles of the free-running kernel - 198 tiles of 96 x 256 for those products - take them back
-        // where no trainer epilogue is involved)
-        if (variant == 11 && g_opt_variant == 1 && (long long)((M + 159) / 160) * (N >> 8) < 192) {
-            const bool small_ok = g_opt_p9_small && !(flags & (YV_EPI_SAVE_PRE | YV_EPI_GELU_BWD));
-            if (!small_ok || (long long)((M + 95) / 96) * (N >> 8) < 128) variant = 1;
-        }
-        // free-running form (round 3): f32 outputs have the registers for 160-row tiles only, whose three-phase K tiles are walked
-        // in pairs (K / 64 even); the 8-phase kernel takes the rest
-        if (variant == 11 && (flags & (YV_EPI_RES_F32 | YV_EPI_OUT_F32)) && ((K / BK) & 1)) variant = 9;
-        switch (variant) {
-            case 2: return launch_dma<256, 128, 4, 2>(g, stream);
-            case 3: return launch_dma<256, 256, 2, 4>(g, stream);
-            case 4: return launch_dma<128, 256, 2, 4>(g, stream);
-            case 9: return launch_p8(g, stream);
-            case 11: return launch_p9(g, stream);
-            case 201: return launch_dma<256, 256, 2, 4, 1>(g, stream);
-            case 202: return launch_dma<256, 256, 2, 4, 2>(g, stream);
-            case 203: return launch_dma<256, 256, 2, 4, 3>(g, stream);
-            case 204: return launch_dma<256, 256, 2, 4, 4>(g, stream);
-            case 101: return launch_dma<128, 128, 2, 2, 1>(g, stream);
-            case 102: return launch_dma<128, 128, 2, 2, 2>(g, stream);
-            case 103: return launch_dma<128, 128, 2, 2, 3>(g, stream);
-            case 104: return launch_dma<128, 128, 2, 2, 4>(g, stream);
-            default: return launch_dma<128, 128, 2, 2>(g, stream);
-        }
-    }
-    return launch_igemm<0>(g, igemm_pick(g.N), stream);
+    void* ws = nullptr; size_t wsb = 0;
+    if (q) { ws = q->ws_bytes ? out : nullptr; wsb = q->ws_bytes; }
+    else if (splitk_form(g)) ws_lookup((void*)stream, &ws, &wsb);
+    const int n_cu = q ? q->n_cu : persistent_cus();
+    if (!n_cu) return YV_ERR_LAUNCH;
+    const LinearRoute r = linear_route(g, ws != nullptr, wsb, n_cu);
+    if (q) { *q->out = r; return YV_OK; }
+    return launch_linear(g, r, ws, n_cu, stream);
 }
 
 extern "C" int yv_linear(const void* A, int lda, const void* W, const float* bias, int M, int N, int K, void* out,
@@ -2254,6 +2314,25 @@ extern "C" int yv_linear_ex(const void* A, int lda, const void* W, const float* 
                             int ldo, int flags, const float* res_f32, void* aux, int ldaux, void* stream) {
     return linear_impl(A, lda, W, bias, M, N, K, out, ldo, nullptr, 0, flags, nullptr, 1, res_f32, aux, ldaux,
                        (hipStream_t)stream);
+}
+
+// The launch path on dummy 16-byte-aligned bases with a LinearQuery, i.e. its argument checks and its route; nothing is
+// dereferenced or launched.  MX: scale rows rounded up to 128, as the trainer allocates them.
+extern "C" int yv_linear_route(int M, int N, int K, int lda, int ldo, int flags, int has_res_f32, int ldaux, int mx, size_t ws_bytes,
+                               int n_cu, yv_linear_route_t* out) {
+    static unsigned char dummy[16] __attribute__((aligned(16)));
+    if (!out || M <= 0 || n_cu < 0) return YV_ERR_ARG;
+    const LinearQuery q = {out, ws_bytes, persistent_cus(n_cu)};
+    const float* f = (const float*)dummy;
+    const int32_t* m_dev = (flags & YV_ROUTE_M_DEV) ? (const int32_t*)dummy : nullptr;
+    flags &= ~YV_ROUTE_M_DEV;
+    if (!mx)
+        return linear_impl(dummy, lda, dummy, f, M, N, K, dummy, ldo, f, 1, flags, m_dev, 1, has_res_f32 ? f : nullptr,
+                           ldaux > 0 ? dummy : nullptr, ldaux, nullptr, &q);
+    if (flags & YV_EPI_OUT_MXFP8) return YV_ERR_ARG;               // as yv_linear_mxfp8 / yv_linear_mxfp8_ex
+    return linear_mx_impl(dummy, lda, dummy, (M + 127) / 128 * 128LL, dummy, dummy, (N + 127) / 128 * 128LL, f, M, N, K, dummy, ldo,
+                          flags, m_dev, 1, nullptr, 0, nullptr, 0, nullptr, has_res_f32 ? f : nullptr, ldaux > 0 ? dummy : nullptr,
+                          ldaux, &q);
 }
 
 static int conv_impl_one(const yv_view* in0, const yv_view* in1, int B, int Hout, int Wout, int ksize, int stride,
@@ -2357,25 +2436,8 @@ static int wgrad_impl(const void* dY, int ldy, const void* X, int ldx, int T, in
     g.M = N; g.N = K; g.K = T; g.out = dW; g.ldo = ldw; g.flags = YV_EPI_OUT_F32;
     g.tiles_m = (N + 127) / 128; g.tiles_n = (K + 127) / 128;
     void* ws = nullptr; size_t wsb = 0;
-    g.splitk = 1;
-    if (ws_lookup(stream, &ws, &wsb)) {
-        const long long tiles = (long long)g.tiles_m * g.tiles_n;
-        // ViT weight gradients: 100+ tiles over 6k tokens -> S <= 9.  Conv weight gradients: 1-4 tiles over 10^5..10^6
-        // output pixels -> up to 512 slices of >= 512 rows each (the partials stay tiny: S * Cout * 9*Cin floats)
-        // matrix-shaped gradients: ONE round of the 512 workgroup slots (2 per CU) - a second, partly filled round costs more than
-        // the longer slices of the first save (tools/wgrad_bench.py: dW 2304 x 768 over 6,336 tokens 43 us at S = 4 = 432
-        // workgroups, 65 us at S = 5 = 540; round 2 took 1024 / tiles = 9: 63 us)
-        int S = (int)((tiles <= 16 ? 1024 : 512) / tiles);
-        if (S < 1) S = 1;
-        const int cap = tiles <= 16 ? g_opt_wgrad_cap : 16;
-        const int min_rows = tiles <= 16 ? 512 : 128;
-        if (S > T / min_rows) S = T / min_rows;
-        if (S > cap) S = cap;
-        if (tiles > 16 && g_opt_wgrad_split > 0) S = g_opt_wgrad_split;
-        const size_t fit = wsb / ((size_t)N * K * sizeof(float));
-        if ((size_t)S > fit) S = (int)fit;
-        if (S >= 2) { g.splitk = S; g.partial = (float*)ws; }
-    }
+    g.splitk = ws_lookup(stream, &ws, &wsb) ? wgrad_slices((long long)g.tiles_m * g.tiles_n, T, (size_t)N * K * sizeof(float), wsb) : 1;
+    if (g.splitk > 1) g.partial = (float*)ws;
     const int S = g.splitk;
     const size_t lds = 2 * 2 * 64 * 256;
     hipLaunchKernelGGL(gemm_tn_kernel, dim3(g.tiles_m * g.tiles_n * S), dim3(256), lds, (hipStream_t)stream, g);

@@ -62,9 +62,13 @@ struct GemmArgs {
 extern int g_opt_p8_sched, g_opt_p8_rows, g_opt_p9_small, g_opt_p9_small_fixed;
 extern thread_local int g_opt_p8_cus;
 extern thread_local hipEvent_t t_time_start, t_time_stop;   // yv_set_launch_timing (gemm.hip): the next timed launch of this thread
-int launch_p8(GemmArgs& g, hipStream_t st);
-int launch_p9(GemmArgs& g, hipStream_t st, int rows = 0, bool mx = false);
-int persistent_cus();                 // grid of a persistent launch made by this thread (gemm_persistent.hip)
+int persistent_cus(int n_cu = 0);      // grid of a persistent launch made by this thread (gemm_persistent.hip)
+// tile height of a persistent launch on n_cu workgroups (pure: shape, flags and options in, rows out) ...
+int p8_tile_rows(int M, int N, int flags, int n_cu);
+int p9_tile_rows(int M, int N, int K, int flags, bool mx, int n_cu, int forced_rows);
+// ... and the launch of the instance with that height
+int launch_p8(GemmArgs& g, hipStream_t st, int rows, int n_cu);
+int launch_p9(GemmArgs& g, hipStream_t st, int rows, int n_cu, bool mx);
 
 // Launches kern(arg).  Events armed by yv_set_launch_timing on this thread get the timestamps of the kernel's own dispatch packet
 // (no extra barrier packets in the queue, unlike a pair of hipEventRecord calls around the launch) and are cleared: one launch.

@@ -976,8 +976,7 @@ int launch_p9_inst(GemmArgs& g, hipStream_t st, int n_cu) {
     return launch_persistent(gemm_p9_kernel<MF, F32OUT, 0, EXT, MX>, 32 * MF, 2 * 65536 + 16384 + (MX ? 4096 : 0), g, st, n_cu);
 }
 
-// The tile heights of one epilogue family (F32OUT, EXT, MX).  Instances exist for 160 / 192 / 224 rows in every family, 256 rows
-// (the default) for the plain epilogues and - the trainer epilogues EXT stop at 224 - 128 / 96 rows for the plain bf16-operand ones.
+// The tile heights of one epilogue family (F32OUT, EXT, MX): what p9_tile_rows returns for it.
 template <bool F32OUT, int EXT, bool MX>
 int launch_p9_rows(GemmArgs& g, hipStream_t st, int n_cu, int rows) {
     if constexpr (!EXT && !MX) {
@@ -994,10 +993,11 @@ int launch_p9_rows(GemmArgs& g, hipStream_t st, int n_cu, int rows) {
 
 }  // namespace
 
-// grid of a persistent launch: the CU count of the current device (looked up once: the same value from every thread), clipped
-// by the calling thread's "linear_p8_cus"; 0: the device query failed
-int yvgemm::persistent_cus() {
+// grid of a persistent launch: the CU count of the current device (looked up once: the same value from every thread; n_cu != 0:
+// that count instead, yv_linear_route), clipped by the calling thread's "linear_p8_cus"; 0: the device query failed
+int yvgemm::persistent_cus(int n_cu) {
     static int n_cu_dev = 0;
+    if (n_cu) return (g_opt_p8_cus > 0 && g_opt_p8_cus < n_cu) ? g_opt_p8_cus : n_cu;
     if (!n_cu_dev) {
         int dev = 0; hipDeviceProp_t prop;
         if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 0;
@@ -1006,45 +1006,33 @@ int yvgemm::persistent_cus() {
     return (g_opt_p8_cus > 0 && g_opt_p8_cus < n_cu_dev) ? g_opt_p8_cus : n_cu_dev;
 }
 
-int yvgemm::launch_p8(GemmArgs& g, hipStream_t st) {
-    const int n_cu = persistent_cus();
-    if (!n_cu) return YV_ERR_LAUNCH;
-    g.sched = g_opt_p8_sched;
-    // tile height: minimise rounds x (rows + a fixed per-tile cost worth ~24 rows: epilogue, pipeline turn-around)
-    int best = 256;
+// Tile height of gemm_p8_kernel: "linear_p8_rows", else minimise rounds x (rows + ~24 rows of epilogue and pipeline turn-around)
+int yvgemm::p8_tile_rows(int M, int N, int flags, int n_cu) {
+    const bool f32out = flags & (YV_EPI_RES_F32 | YV_EPI_OUT_F32);
+    int best = f32out ? 192 : 256;
     if (g_opt_p8_rows) {
         best = g_opt_p8_rows < 128 ? 128 : g_opt_p8_rows;          // (96: a tile height of the free-running kernel only)
-        if ((g.flags & (YV_EPI_RES_F32 | YV_EPI_OUT_F32)) && best > 192) best = 192;
+        if (f32out && best > 192) best = 192;
     } else {
         long long best_cost = -1;
         const int cand[5] = {256, 224, 192, 160, 128};
-        const bool f32out = g.flags & (YV_EPI_RES_F32 | YV_EPI_OUT_F32);
-        best = f32out ? 192 : 256;
         for (int c = f32out ? 2 : 0; c < 5; ++c) {
-            const long long tiles = (long long)((g.M + cand[c] - 1) / cand[c]) * (g.N / 256);
+            const long long tiles = (long long)((M + cand[c] - 1) / cand[c]) * (N / 256);
             const long long rounds = (tiles + n_cu - 1) / n_cu;
             const long long cost = rounds * (cand[c] + 24);
             if (best_cost < 0 || cost < best_cost) { best_cost = cost; best = cand[c]; }
         }
     }
-    switch (best) {
-        case 224: return launch_p8_inst<4, 3>(g, st, n_cu);
-        case 192: return launch_p8_inst<3, 3>(g, st, n_cu);
-        case 160: return launch_p8_inst<3, 2>(g, st, n_cu);
-        case 128: return launch_p8_inst<2, 2>(g, st, n_cu);
-        default: return launch_p8_inst<4, 4>(g, st, n_cu);
-    }
+    return (best == 224 || best == 192 || best == 160 || best == 128) ? best : 256;    // a height without an instance: 256 rows
 }
 
-// rows: 0 = choose (minimise rounds x (rows + per-tile cost)), else 160 / 192 / 224 / 256
-int yvgemm::launch_p9(GemmArgs& g, hipStream_t st, int rows, bool mx) {
-    const int n_cu = persistent_cus();
-    if (!n_cu) return YV_ERR_LAUNCH;
-    g.sched = g_opt_p8_sched;
-    const bool f32out = g.flags & (YV_EPI_RES_F32 | YV_EPI_OUT_F32);
-    const bool even_nk = ((g.K / (mx ? 128 : BK)) & 1) == 0;         // odd-P instances (160 / 192 rows) walk K tiles in pairs
-    const int ext = (g.flags & YV_EPI_SAVE_PRE) ? 1 : (g.flags & YV_EPI_GELU_BWD) ? 2 : 0;
-    int best = rows ? rows : g_opt_p8_rows;
+// Tile height of gemm_p9_kernel: forced_rows, else "linear_p8_rows", else minimise rounds x (rows + per-tile cost).  Instances:
+// 160 / 192 / 224 rows in every epilogue family, 256 for the plain epilogues, 128 / 96 for the plain bf16-operand ones.
+int yvgemm::p9_tile_rows(int M, int N, int K, int flags, bool mx, int n_cu, int forced_rows) {
+    const bool f32out = flags & (YV_EPI_RES_F32 | YV_EPI_OUT_F32);
+    const bool even_nk = ((K / (mx ? 128 : BK)) & 1) == 0;           // odd-P instances (160 / 192 rows) walk K tiles in pairs
+    const bool ext = flags & (YV_EPI_SAVE_PRE | YV_EPI_GELU_BWD);
+    int best = forced_rows ? forced_rows : g_opt_p8_rows;
     if (ext && best > 224) best = 224;
     if (!best) {
         long long best_cost = -1;
@@ -1055,7 +1043,7 @@ int yvgemm::launch_p9(GemmArgs& g, hipStream_t st, int rows, bool mx) {
             if (cand[c] > 192 && f32out && even_nk) continue;      // f32 outputs: the residual prefetch next to the accumulators spills above 192 rows
             if (cand[c] > 224 && ext) continue;                     // trainer epilogues: up to 224 rows
             if (cand[c] > 160 && mx && f32out) continue;            // MX with f32 output: 160 rows (registers)
-            const long long tiles = (long long)((g.M + cand[c] - 1) / cand[c]) * (g.N / 256);
+            const long long tiles = (long long)((M + cand[c] - 1) / cand[c]) * (N / 256);
             const long long rounds = (tiles + n_cu - 1) / n_cu;
             // a K tile of a tile costs its rows + a fixed part (weight pieces, sync point); the short tiles pay the weight fetch
             // over fewer rows and are worth it only where the taller ones leave CUs idle (tools/gemm_lab.hip, LAB_M=6304)
@@ -1064,17 +1052,34 @@ int yvgemm::launch_p9(GemmArgs& g, hipStream_t st, int rows, bool mx) {
         }
     }
     if (best <= 192 && best >= 160 && !even_nk) best = 224;
-    // MX trainer epilogues.  Reached by tests/test_gpu_mx_train.py::test_mx_linear_ex_epilogues: 160 rows by the ViT-B/16 shapes
-    // (M = 6,304, N = 3,072, K = 768), 224 by the ViT-L/16 shapes (N = 4,096, K = 1,024) and by an odd K / 128 (K = 640);
-    // each height (160 / 192 / 224) also forced through "linear_p8_rows" by test_mx_linear_ex_persistent_tile_heights
+    if (best == 224 || best == 192 || best == 160 || ((best == 128 || best == 96) && !ext && !mx)) return best;
+    return ext ? 224 : 256;                                         // a height without an instance in this family
+}
+
+int yvgemm::launch_p8(GemmArgs& g, hipStream_t st, int rows, int n_cu) {
+    g.sched = g_opt_p8_sched;
+    switch (rows) {
+        case 224: return launch_p8_inst<4, 3>(g, st, n_cu);
+        case 192: return launch_p8_inst<3, 3>(g, st, n_cu);
+        case 160: return launch_p8_inst<3, 2>(g, st, n_cu);
+        case 128: return launch_p8_inst<2, 2>(g, st, n_cu);
+        default: return launch_p8_inst<4, 4>(g, st, n_cu);
+    }
+}
+
+// (the families and heights are reached by tests/test_gpu_dense.py and tests/test_gpu_mx_train.py, which assert their routes)
+int yvgemm::launch_p9(GemmArgs& g, hipStream_t st, int rows, int n_cu, bool mx) {
+    g.sched = g_opt_p8_sched;
+    const bool f32out = g.flags & (YV_EPI_RES_F32 | YV_EPI_OUT_F32);
+    const int ext = (g.flags & YV_EPI_SAVE_PRE) ? 1 : (g.flags & YV_EPI_GELU_BWD) ? 2 : 0;
     switch ((mx ? 4 : 0) + (ext ? ext : f32out ? 3 : 0)) {      // the family: a trainer epilogue (1 SAVE_PRE, 2 GELU_BWD) before f32out
-        case 0: return launch_p9_rows<false, 0, false>(g, st, n_cu, best);
-        case 1: return launch_p9_rows<false, 1, false>(g, st, n_cu, best);
-        case 2: return launch_p9_rows<false, 2, false>(g, st, n_cu, best);
-        case 3: return launch_p9_rows<true, 0, false>(g, st, n_cu, best);
-        case 4: return launch_p9_rows<false, 0, true>(g, st, n_cu, best);
-        case 5: return launch_p9_rows<false, 1, true>(g, st, n_cu, best);     // MX trainer: fc1 forward (GELU + saved pre-activation)
-        case 6: return launch_p9_rows<false, 2, true>(g, st, n_cu, best);     // MX trainer: fc2 data gradient (GELU backward)
-        default: return launch_p9_rows<true, 0, true>(g, st, n_cu, best);
+        case 0: return launch_p9_rows<false, 0, false>(g, st, n_cu, rows);
+        case 1: return launch_p9_rows<false, 1, false>(g, st, n_cu, rows);
+        case 2: return launch_p9_rows<false, 2, false>(g, st, n_cu, rows);
+        case 3: return launch_p9_rows<true, 0, false>(g, st, n_cu, rows);
+        case 4: return launch_p9_rows<false, 0, true>(g, st, n_cu, rows);
+        case 5: return launch_p9_rows<false, 1, true>(g, st, n_cu, rows);     // MX trainer: fc1 forward (GELU + saved pre-activation)
+        case 6: return launch_p9_rows<false, 2, true>(g, st, n_cu, rows);     // MX trainer: fc2 data gradient (GELU backward)
+        default: return launch_p9_rows<true, 0, true>(g, st, n_cu, rows);
     }
 }

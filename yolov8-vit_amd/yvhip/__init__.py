@@ -7,6 +7,7 @@ library is missing or a call fails, a `YvError` is raised.
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import os
 
@@ -76,6 +77,7 @@ _SIGS = {
     "yv_linear_mxfp8_ex": (_i, [_vp, C.c_longlong, _vp, C.c_longlong, _vp, _vp, C.c_longlong, _vp, _i, _i, _i, _vp, _i, _i, _vp,
                                 _vp, _i, _vp]),
     "yv_linear_mxfp8_instance": (_i, [_i, _i, _i, _i]),
+    "yv_linear_route": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _sz, _i, _vp]),
     "yv_wgrad_mxfp8": (_i, [_vp, C.c_longlong, _vp, C.c_longlong, _vp, C.c_longlong, _vp, C.c_longlong, _i, _i, _i, _vp, _i, _vp]),
     "yv_custom_nms_ws_bytes": (_sz, [_i, _i]),
     "yv_custom_nms": (_i, [_vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _sz, _vp]),
@@ -1162,6 +1164,26 @@ def linear_mxfp8_instance(M: int, N: int, K: int, flags: int = 0) -> int:
     r = lib.yv_linear_mxfp8_instance(M, N, K, flags)
     check(min(r, 0), "yv_linear_mxfp8_instance")
     return r
+
+
+STREAM_WS_BYTES = 16 * 1024 * 1024 * 4      # the split-K workspace _st() registers per stream (what linear_route assumes by default)
+# linear_route: kernel families (yv_linear_route_t.kernel, include/yv_hip.h)
+LIN_SKINNY, LIN_IGEMM, LIN_DMA, LIN_P8, LIN_P9, LIN_MX = 0, 1, 2, 3, 4, 5
+ROUTE_M_DEV = 0x40000000                     # linear_route flag: the launch passes a device row count
+LinearRoute = collections.namedtuple("LinearRoute", "kernel tile_rows tile_cols f32out ext abl mx splitk staged grid")
+
+
+def linear_route(M: int, N: int, K: int, flags: int = 0, lda: Optional[int] = None, ldo: Optional[int] = None,
+                 res_f32: bool = False, ldaux: int = 0, mx: bool = False, ws_bytes: int = STREAM_WS_BYTES,
+                 n_cu: int = 0, m_dev: bool = False) -> LinearRoute:
+    """Route linear / linear_ex (mx: linear_mxfp8 / linear_mxfp8_ex) take for this shape under the current options (host only):
+    see yv_linear_route in include/yv_hip.h.  `flags` as the C entry takes them (EPI_BIAS is NOT added); dense rows by
+    default; m_dev: the launch passes a device row count; n_cu = 0: the current device's CU count (needs a GPU)."""
+    out = (C.c_int * len(LinearRoute._fields))()
+    check(lib.yv_linear_route(M, N, K, K if lda is None else lda, N if ldo is None else ldo, flags | (ROUTE_M_DEV if m_dev else 0),
+                              int(res_f32), ldaux, int(mx),
+                              ws_bytes, n_cu, out), "yv_linear_route")
+    return LinearRoute(*out)
 
 
 def wgrad_mxfp8(dyt: torch.Tensor, dy_scale: torch.Tensor, xt: torch.Tensor, x_scale: torch.Tensor, dw: torch.Tensor):
