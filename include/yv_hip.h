@@ -557,6 +557,26 @@ int yv_linear_nn(const void* A, int lda, const void* Wkn, int ldw, const float* 
  * whose tail rows are ZERO): the fragments are columns of the LDS tiles, read with ds_read_b64_tr_b16; no transposed
  * copies.  Split over T when a workspace is registered for the stream (deterministic). */
 int yv_wgrad(const void* dY, int ldy, const void* X, int ldx, int T, int N, int K, float* dW, int ldw, void* stream);
+/* yv_wgrad with the output tile chosen by the caller: tile_n = 128 is yv_wgrad (gemm_tn_kernel, 128 (n) x 128 (k) tiles);
+ * 64 / 32 run gemm_tn_narrow_kernel, 64 / 32 (n) x 256 (k) tiles that issue no load, LDS read or MFMA for 16-column fragments
+ * past N or K (few output channels: the detector's early layers); 0 lets yv_wgrad_route choose.  Any other value:
+ * YV_ERR_ARG.  For an equal number of token slices every tile gives the same bits. */
+int yv_wgrad_tiled(const void* dY, int ldy, const void* X, int ldx, int T, int N, int K, float* dW, int ldw, int tile_n,
+                   void* stream);
+/* The route of a weight gradient (yv_wgrad, yv_wgrad_tiled, and yv_wgrad_conv3* with K = 9 * Cin), decided by the function the
+ * launch path itself calls.  Host only: nothing is dereferenced, launched or queried.  tile_n as yv_wgrad_tiled takes it.
+ * tile_n = 0 chooses: the tile from {32, 64, 128} with the fewest padded columns ceil(N / tile) * tile, ties to the wider one;
+ * then a 64-wide tile goes back to 128 when it would launch fewer workgroups than the 128 x 128 tiles and those fit one round of
+ * the 2 * n_cu workgroup slots (measured slower there).  ws_bytes: the workspace registered for the stream (0: none, no token
+ * split); n_cu: CUs of the device, 0 = 256 (what the launch path passes: the slice rule's slot constants are that part's).
+ * Returns YV_OK and fills *out, or YV_ERR_ARG where the launch would reject T, N, K or tile_n. */
+typedef struct {
+    int tile_n, tile_k; /* output tile of a workgroup: 128 x 128, 64 x 256 or 32 x 256 */
+    int tiles;          /* ceil(N / tile_n) * ceil(K / tile_k) */
+    int slices;         /* token slices S (1: no split, no reduce pass) */
+    int workgroups;     /* tiles * slices */
+} yv_wgrad_route_t;
+int yv_wgrad_route(int T, int N, int K, int tile_n, size_t ws_bytes, int n_cu, yv_wgrad_route_t* out);
 
 /* Weight gradient of a 3x3 / stride 1 / pad 1 convolution with no im2col buffer: dW (N, 9*Cin) f32, column
  * ((dy+1)*3 + dx+1)*Cin + ci.  Operands over the zero-padded pixel grid (B, H+2, W+2), T = that pixel count rounded up to
@@ -565,6 +585,9 @@ int yv_wgrad(const void* dY, int ldy, const void* X, int ldx, int T, int N, int 
  * reach there, always multiplied by a zero row of dYp).  yv_view_op mode 6 writes both layouts. */
 int yv_wgrad_conv3(const void* dYp, int ldy, const void* Xp, int Cin, int pitch, int T, int N, float* dW, int ldw,
                    void* stream);
+/* yv_wgrad_conv3 with the output tile of yv_wgrad_tiled (tile_n = 128: yv_wgrad_conv3). */
+int yv_wgrad_conv3_tiled(const void* dYp, int ldy, const void* Xp, int Cin, int pitch, int T, int N, float* dW, int ldw,
+                         int tile_n, void* stream);
 
 /* out_t[c][r] = in[r][c] (bf16), rows of out_t zero padded up to the next multiple of 64 (ld_out >= that). */
 int yv_transpose_bf16(const void* in, int rows, int cols, long long ld_in, void* out_t, long long ld_out, void* stream);

@@ -587,13 +587,28 @@ typedef __attribute__((address_space(3))) s16x4* lds_s16x4_t;
 // reduction-major tiles ([64 reduction rows][128 columns] bf16, 256-byte LDS rows): chunk swizzle and the
 // hardware-transposing fragment read (8 consecutive reduction elements 32*ks + 8*(lane>>4) + 0..7 of column
 // col0 + (lane&15)): two ds_read_b64_tr_b16, lane 4q+p of a 16-lane group addressing row q, columns 4p..4p+3
-__device__ __forceinline__ int tn_swz(int row) { return ((row & 3) << 1) | (((row >> 3) & 1) << 3); }
+// COLS = 64 / 32 (the dY tile of gemm_tn_narrow_kernel: 128- / 64-byte rows, dense): the same read from a swizzle derived for
+// that pitch.  A 32-lane half reads rows r + {0..3, 8..11}, 32 bytes (8 banks) of each; bank = (addr / 4) % 64, so the eight rows
+// must land in eight different 32-byte groups of a 256-byte span.  group = (addr / 32) % 8:
+//   128: ch >> 1 - the pitch contributes nothing, row bits 0, 1 and 3 are XORed into chunk bits 1, 2 and 3;
+//    64: (row & 1) << 2 | ch >> 1 - row bit 0 comes from the pitch, row bits 1 and 3 are XORed into chunk bits 1 and 2;
+//    32: (row & 3) << 1 | ch >> 1 - row bits 0 and 1 come from the pitch, row bit 3 is XORed into chunk bit 1.
+// Chunk bit 0 is never touched: the two chunks (32 bytes) a 16-lane group reads of a row stay adjacent.
+template <int COLS = 128>
+__device__ __forceinline__ int tn_swz(int row) {
+    if constexpr (COLS == 128) return ((row & 3) << 1) | (((row >> 3) & 1) << 3);
+    else if constexpr (COLS == 64) return (((row >> 1) & 1) << 1) | (((row >> 3) & 1) << 2);
+    else return ((row >> 3) & 1) << 1;
+}
+template <int COLS = 128>
 __device__ __forceinline__ bf16x8 tr_frag(const unsigned char* tile, int ks, int lane, int col0) {
+    static_assert(COLS == 128 || COLS == 64 || COLS == 32, "row pitch of a reduction-major tile");
+    constexpr int P = COLS * 2;
     const int fi = lane & 15, mg = lane >> 4, q = fi >> 2, p = fi & 3;
     const int row = ks * 32 + mg * 8 + q;
     const int ch = (col0 + 4 * p) >> 3, off = ((col0 + 4 * p) & 7) * 2;
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t)(tile + row * 256 + ((ch ^ tn_swz(row)) << 4) + off));
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t)(tile + (row + 4) * 256 + ((ch ^ tn_swz(row + 4)) << 4) + off));
+    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t)(tile + row * P + ((ch ^ tn_swz<COLS>(row)) << 4) + off));
+    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t)(tile + (row + 4) * P + ((ch ^ tn_swz<COLS>(row + 4)) << 4) + off));
     const u32x4 pk = {__builtin_bit_cast(u32x2, lo)[0], __builtin_bit_cast(u32x2, lo)[1],
                       __builtin_bit_cast(u32x2, hi)[0], __builtin_bit_cast(u32x2, hi)[1]};
     return __builtin_bit_cast(bf16x8, pk);
@@ -1654,6 +1669,145 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(GemmArgs g) {
     }
 }
 
+// The same product for few output channels (wgrad_route picks it; opt-in): TN (n) x 256 (k) output tiles,
+// TN = 64 or 32, so a workgroup keeps the 128 x 128 tile's 64 accumulators per lane only where dW has columns.
+//   X tile: [64 tokens][256 columns] as TWO [64][128] sub-tiles in gemm_tn_kernel's layout (256-byte rows, tn_swz<128>); wave w
+//   owns k columns 64 w .. 64 w + 63 (sub-tile w / 2) against all TN n columns.
+//   dY tile: [64][TN] dense (128- / 64-byte rows), swizzle tn_swz<TN>: 2 x 32 KB + 8 / 4 KB per buffer, two buffers = 80 / 72 KB.
+//   A 16-column fragment that lies wholly past N (or K) gets no DMA (its lanes are masked off the load: the LDS destination is
+//   base + 16 * lane whatever the mask), no LDS read and no MFMA: a wave picks the loop instance for its count of live k and
+//   n fragments once (wave-uniform), so the transposing reads run with every lane on and the loop bodies have no branches.
+//   Chunks past N / K inside a live fragment are clamped to N - 8 / K - 8 as above.
+// Summation: the MFMA, the ascending token walk, the slices and tr_frag's token-to-slot mapping are gemm_tn_kernel's, so for
+// an equal slice count every dW element is the same chain of operations on the same values - bit-identical results.
+template <int TN>
+__global__ __launch_bounds__(256, 2) void gemm_tn_narrow_kernel(GemmArgs g) {
+    static_assert(TN == 64 || TN == 32, "dY tile width");
+    constexpr int TB = 64, XSUB = TB * 256, BUF = 2 * XSUB + TB * TN * 2;   // bytes: an X sub-tile, one buffer
+    constexpr int NF = TN / 16;                               // n fragments of a wave
+    constexpr int YCH = TN / 8, YROWS = 64 / YCH, YI = YCH / 4;   // dY: chunks per row, rows per DMA instruction, instructions per wave
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int Nw = g.M, Kw = g.N, T = g.K;
+    int bid = blockIdx.x;
+    const int S = g.splitk > 1 ? g.splitk : 1;
+    const int slice = bid % S;
+    bid /= S;
+    const int tn_ = bid / g.tiles_n, tk_ = bid - tn_ * g.tiles_n;
+    const int n0 = tn_ * TN, k0 = tk_ * 256;
+    const int n_live = Nw - n0 < TN ? Nw - n0 : TN, k_live = Kw - k0 < 256 ? Kw - k0 : 256;   // columns inside dW: > 0, multiples of 8
+    const int nnf = (n_live + 15) >> 4;                       // live n fragments
+    int nkf = (k_live - wave * 64 + 15) >> 4;                 // live k fragments of this wave
+    nkf = nkf < 0 ? 0 : nkf > 4 ? 4 : nkf;
+
+    // DMA.  dY: lane -> (row = YROWS * instr + lane / YCH, chunk' = lane % YCH); X: as gemm_tn_kernel per sub-tile;
+    // source chunk = chunk' ^ swz(row).  A lane whose source chunk lies in a dead fragment issues nothing.
+    const uint16_t* ysrc[YI];
+    const uint16_t* xsrc[8];
+    unsigned ylive = 0, xlive = 0;
+#pragma unroll
+    for (int j = 0; j < YI; ++j) {
+        const int row = (j * 4 + wave) * YROWS + lane / YCH;
+        const int c = ((lane % YCH) ^ tn_swz<TN>(row)) * 8;
+        ylive |= (unsigned)((c & ~15) < n_live) << j;
+        ysrc[j] = g.a0 + (long long)row * g.lda0 + n0 + (c < n_live ? c : n_live - 8);
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const int row = ((j & 3) * 4 + wave) * 4 + (lane >> 4);
+        const int c = (j >> 2) * 128 + (((lane & 15) ^ tn_swz(row)) << 3);
+        xlive |= (unsigned)((c & ~15) < k_live) << j;
+        const int ck = k0 + (c < k_live ? c : k_live - 8);
+        long long xoff = ck;
+        if (g.seg_len) { const int sg = ck / g.seg_len; xoff = (long long)sg * g.seg_stride + (ck - sg * g.seg_len); }
+        xsrc[j] = g.w + (long long)row * g.lda1 + xoff;
+    }
+    auto issue = [&](int tt, int buf) {
+        unsigned char* Xt = smem + buf * BUF;
+        unsigned char* Yt = Xt + 2 * XSUB;
+#pragma unroll
+        for (int j = 0; j < YI; ++j)
+            if (ylive >> j & 1)
+                __builtin_amdgcn_global_load_lds((gptr_t)(ysrc[j] + (long long)tt * TB * g.lda0), (lptr_t)(Yt + (j * 4 + wave) * 1024), 16, 0, 0);
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            if (xlive >> j & 1)
+                __builtin_amdgcn_global_load_lds((gptr_t)(xsrc[j] + (long long)tt * TB * g.lda1),
+                                                 (lptr_t)(Xt + (j >> 2) * XSUB + ((j & 3) * 4 + wave) * 1024), 16, 0, 0);
+    };
+    f32x4 acc[4][NF];                                         // [k fragment][n fragment]
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < NF; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    const int fi = lane & 15, mg = lane >> 4;
+    const int nt_all = T / TB;
+    const int t0 = (int)((long long)nt_all * slice / S), t1 = (int)((long long)nt_all * (slice + 1) / S);
+    if (t0 < t1) {
+        issue(t0, 0);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+    }
+    // the token walk of a wave with NK live k fragments and NN live n fragments, one branch-free loop per pair (a wave with
+    // runtime guards around each read and MFMA holds the whole workgroup back at the barrier: measured)
+    auto walk = [&](auto nk, auto nn) {
+        constexpr int NK = decltype(nk)::value, NN = decltype(nn)::value;
+        for (int tt = t0; tt < t1; ++tt) {
+            const int cur = (tt - t0) & 1;
+            if (tt + 1 < t1) issue(tt + 1, cur ^ 1);
+            const unsigned char* Xt = smem + cur * BUF + (wave >> 1) * XSUB;
+            const unsigned char* Yt = smem + cur * BUF + 2 * XSUB;
+            if constexpr (NK > 0) {
+#pragma unroll
+                for (int ks = 0; ks < 2; ++ks) {
+                    bf16x8 fx[NK], fy[NN];
+#pragma unroll
+                    for (int i = 0; i < NK; ++i) fx[i] = tr_frag(Xt, ks, lane, (wave & 1) * 64 + i * 16);
+#pragma unroll
+                    for (int j = 0; j < NN; ++j) fy[j] = tr_frag<TN>(Yt, ks, lane, j * 16);
+#pragma unroll
+                    for (int i = 0; i < NK; ++i)
+#pragma unroll
+                        for (int j = 0; j < NN; ++j)
+                            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fx[i], fy[j], acc[i][j], 0, 0, 0);
+                }
+            }
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __syncthreads();
+        }
+    };
+    auto by_n = [&](auto nk) {                                // nnf = 1 .. NF
+        if constexpr (decltype(nk)::value == 0) walk(nk, std::integral_constant<int, 1>{});
+        else if constexpr (NF == 2) { if (nnf == 2) walk(nk, std::integral_constant<int, 2>{}); else walk(nk, std::integral_constant<int, 1>{}); }
+        else switch (nnf) {
+            case 4: walk(nk, std::integral_constant<int, 4>{}); break;
+            case 3: walk(nk, std::integral_constant<int, 3>{}); break;
+            case 2: walk(nk, std::integral_constant<int, 2>{}); break;
+            default: walk(nk, std::integral_constant<int, 1>{});
+        }
+    };
+    switch (nkf) {                                            // 0 .. 4
+        case 4: by_n(std::integral_constant<int, 4>{}); break;
+        case 3: by_n(std::integral_constant<int, 3>{}); break;
+        case 2: by_n(std::integral_constant<int, 2>{}); break;
+        case 1: by_n(std::integral_constant<int, 1>{}); break;
+        default: by_n(std::integral_constant<int, 0>{});
+    }
+    // D[row = k (lane>>4)*4 + reg][col = n (lane&15)]  ->  dW[n][k..k+3]
+    float* out = S > 1 ? g.partial + (long long)slice * Nw * Kw : (float*)g.out;
+    const long long ldo = S > 1 ? Kw : g.ldo;
+#pragma unroll
+    for (int j = 0; j < NF; ++j) {
+        const int n = n0 + j * 16 + fi;
+        if (n >= Nw) continue;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int k = k0 + wave * 64 + i * 16 + mg * 4;
+            if (k < Kw) *(float4*)(out + (long long)n * ldo + k) = make_float4(acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]);
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // Skinny-M linear (M <= 256: one row per crop - the classifier's last-block tail on the cls rows, and its head).  Such a product
 // is a pass over the weight matrix (fc2 of ViT-B: 4.7 MB against 64 x 768 outputs); 128 x 128 tiles make 6 .. 24 workgroups of it,
@@ -2005,6 +2159,41 @@ int wgrad_slices(long long tiles, int T, size_t out_bytes, size_t ws_bytes) {
     const size_t fit = ws_bytes / out_bytes;
     if ((size_t)S > fit) S = (int)fit;
     return S >= 2 ? S : 1;
+}
+
+// The route of a weight gradient: ONE rule for wgrad_impl's launch and for yv_wgrad_route, which reports it without a device.
+// Pure: shape, the requested N tile (128: gemm_tn_kernel, the decision from before the narrow tiles; 64 / 32:
+// gemm_tn_narrow_kernel, x 256 k columns; 0: choose), the workspace size, the CU count and the options in, a WgradRoute out.
+// tile_n = 0, in this order (measurements: DESIGN.md section 20, profiles/wgrad_narrow_layers_column_rule.txt):
+//   1. the tile with the fewest padded columns ceil(N / tile) * tile, ties to the wider tile - so 128 stays wherever a narrow
+//      tile would compute as many columns (every N % 128 == 0, and e.g. N = 104);
+//   2. a 64-wide tile goes back to 128 when it would launch FEWER workgroups than the 128 x 128 tiles and those fit one round of
+//      the 2 * n_cu workgroup slots.  A 64 x 256 workgroup does the MFMA work of a 128 x 128 one per step over twice the useful
+//      k range: half the workgroups at the same pace each lose to a machine the 128 x 128 launch does not even fill (K = 192,
+//      288 at any T; every K >= 576 at <= 28 k tokens: x 1.03 - 1.14 measured), and win once that launch needs a second round
+//      (K >= 576 at 10^5 tokens: x 0.67 - 0.76) or where the count does not change (K <= 128: x 0.84 - 0.94).  A 32-wide tile
+//      stays: its workgroup carries half the accumulators and MFMAs, and it won at every measured shape (x 0.70 - 0.93).
+// n_cu = 0 stands for 256, the part wgrad_slices' slot constants are for.  Pinned by tests/test_wgrad_routes_cpu.py.
+using WgradRoute = yv_wgrad_route_t;
+static WgradRoute wgrad_tiled_route(int T, int N, int K, int tile_n, size_t ws_bytes) {
+    WgradRoute r = {};
+    r.tile_n = tile_n;
+    r.tile_k = tile_n == 128 ? 128 : 256;
+    r.tiles = ((N + r.tile_n - 1) / r.tile_n) * ((K + r.tile_k - 1) / r.tile_k);
+    r.slices = ws_bytes ? wgrad_slices(r.tiles, T, (size_t)N * K * sizeof(float), ws_bytes) : 1;
+    r.workgroups = r.tiles * r.slices;
+    return r;
+}
+WgradRoute wgrad_route(int T, int N, int K, int tile_n, size_t ws_bytes, int n_cu) {
+    if (tile_n) return wgrad_tiled_route(T, N, K, tile_n, ws_bytes);
+    const WgradRoute wide = wgrad_tiled_route(T, N, K, 128, ws_bytes);
+    tile_n = 128;
+    for (int t = 64; t >= 32; t >>= 1)
+        if ((N + t - 1) / t * t < (N + tile_n - 1) / tile_n * tile_n) tile_n = t;
+    if (tile_n == 128) return wide;
+    const WgradRoute r = wgrad_tiled_route(T, N, K, tile_n, ws_bytes);
+    if (tile_n == 64 && r.workgroups < wide.workgroups && wide.workgroups <= 2 * (n_cu > 0 ? n_cu : 256)) return wide;
+    return r;
 }
 
 // Images per sub-batch of a convolution (32-bit byte offsets: each source below 2 GB): s0 / s1 bytes per image of the sources
@@ -2426,27 +2615,44 @@ extern "C" int yv_linear_nn(const void* A, int lda, const void* Wkn, int ldw, co
 }
 
 static int wgrad_impl(const void* dY, int ldy, const void* X, int ldx, int T, int N, int K, float* dW, int ldw, int seg_len,
-                      long long seg_stride, void* stream) {
+                      long long seg_stride, int tile_n, void* stream) {
     if (!dY || !X || !dW || T <= 0 || N <= 0 || K <= 0) return YV_ERR_ARG;
     if ((T & 63) || (N & 7) || (K & 7) || (ldy & 7) || (ldx & 7) || (ldw & 3)) return YV_ERR_ARG;
     if (((uintptr_t)dY | (uintptr_t)X | (uintptr_t)dW) & 15) return YV_ERR_ARG;
+    if (tile_n != 0 && tile_n != 32 && tile_n != 64 && tile_n != 128) return YV_ERR_ARG;
     GemmArgs g = {};
     g.seg_len = seg_len; g.seg_stride = seg_stride;
     g.a0 = (const uint16_t*)dY; g.lda0 = ldy; g.w = (const uint16_t*)X; g.lda1 = ldx;
     g.M = N; g.N = K; g.K = T; g.out = dW; g.ldo = ldw; g.flags = YV_EPI_OUT_F32;
-    g.tiles_m = (N + 127) / 128; g.tiles_n = (K + 127) / 128;
     void* ws = nullptr; size_t wsb = 0;
-    g.splitk = ws_lookup(stream, &ws, &wsb) ? wgrad_slices((long long)g.tiles_m * g.tiles_n, T, (size_t)N * K * sizeof(float), wsb) : 1;
+    if (!ws_lookup(stream, &ws, &wsb)) wsb = 0;
+    const WgradRoute r = wgrad_route(T, N, K, tile_n, wsb, 0);
+    g.tiles_m = (N + r.tile_n - 1) / r.tile_n; g.tiles_n = (K + r.tile_k - 1) / r.tile_k;
+    g.splitk = r.slices;
     if (g.splitk > 1) g.partial = (float*)ws;
-    const int S = g.splitk;
-    const size_t lds = 2 * 2 * 64 * 256;
-    hipLaunchKernelGGL(gemm_tn_kernel, dim3(g.tiles_m * g.tiles_n * S), dim3(256), lds, (hipStream_t)stream, g);
+    void (*kern)(GemmArgs) = r.tile_n == 128 ? gemm_tn_kernel : r.tile_n == 64 ? gemm_tn_narrow_kernel<64> : gemm_tn_narrow_kernel<32>;
+    const size_t lds = r.tile_n == 128 ? 2 * 2 * 64 * 256 : 2 * (2 * 64 * 256 + 64 * r.tile_n * 2);
+    if (r.tile_n != 128 && !yv_grant_lds((const void*)kern, lds)) return YV_ERR_LAUNCH;
+    hipLaunchKernelGGL(kern, dim3(r.workgroups), dim3(256), lds, (hipStream_t)stream, g);
     return launch_splitk_reduce(g, (hipStream_t)stream);
 }
 
 extern "C" int yv_wgrad(const void* dY, int ldy, const void* X, int ldx, int T, int N, int K, float* dW, int ldw,
                         void* stream) {
-    return wgrad_impl(dY, ldy, X, ldx, T, N, K, dW, ldw, 0, 0, stream);
+    return wgrad_impl(dY, ldy, X, ldx, T, N, K, dW, ldw, 0, 0, 128, stream);
+}
+
+extern "C" int yv_wgrad_tiled(const void* dY, int ldy, const void* X, int ldx, int T, int N, int K, float* dW, int ldw,
+                              int tile_n, void* stream) {
+    return wgrad_impl(dY, ldy, X, ldx, T, N, K, dW, ldw, 0, 0, tile_n, stream);
+}
+
+extern "C" int yv_wgrad_route(int T, int N, int K, int tile_n, size_t ws_bytes, int n_cu, yv_wgrad_route_t* out) {
+    if (!out || T <= 0 || N <= 0 || K <= 0 || n_cu < 0) return YV_ERR_ARG;
+    if ((T & 63) || (N & 7) || (K & 7)) return YV_ERR_ARG;
+    if (tile_n != 0 && tile_n != 32 && tile_n != 64 && tile_n != 128) return YV_ERR_ARG;
+    *out = wgrad_route(T, N, K, tile_n, ws_bytes, n_cu);
+    return YV_OK;
 }
 
 // 3x3 / stride 1 / pad 1 weight gradient without an im2col buffer.  Both operands are laid out over the PADDED pixel grid
@@ -2458,9 +2664,14 @@ extern "C" int yv_wgrad(const void* dY, int ldy, const void* X, int ldx, int T, 
 // activation ring must be zero too, and pitch + 1 readable rows of finite values must surround the activation.
 extern "C" int yv_wgrad_conv3(const void* dYp, int ldy, const void* Xp, int Cin, int pitch, int T, int N, float* dW, int ldw,
                               void* stream) {
+    return yv_wgrad_conv3_tiled(dYp, ldy, Xp, Cin, pitch, T, N, dW, ldw, 128, stream);
+}
+
+extern "C" int yv_wgrad_conv3_tiled(const void* dYp, int ldy, const void* Xp, int Cin, int pitch, int T, int N, float* dW, int ldw,
+                                    int tile_n, void* stream) {
     if (!Xp || Cin < 8 || (Cin & 7) || pitch < 3) return YV_ERR_ARG;
     const uint16_t* base = (const uint16_t*)Xp - (long long)(pitch + 1) * Cin;
-    return wgrad_impl(dYp, ldy, base, Cin, T, N, 9 * Cin, dW, ldw, 3 * Cin, (long long)pitch * Cin, stream);
+    return wgrad_impl(dYp, ldy, base, Cin, T, N, 9 * Cin, dW, ldw, 3 * Cin, (long long)pitch * Cin, tile_n, stream);
 }
 
 extern "C" int yv_conv2d(const yv_view* in0, const yv_view* in1, int B, int Hout, int Wout, int ksize, int stride,

@@ -140,6 +140,9 @@ _SIGS = {
     "yv_linear_nn": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _i, _i, _vp, _i, _vp]),
     "yv_wgrad": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp]),
     "yv_wgrad_conv3": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp]),
+    "yv_wgrad_tiled": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp]),
+    "yv_wgrad_conv3_tiled": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp]),
+    "yv_wgrad_route": (_i, [_i, _i, _i, _i, _sz, _i, _vp]),
     "yv_transpose_bf16": (_i, [_vp, _i, _i, C.c_longlong, _vp, C.c_longlong, _vp]),
     "yv_cast_weights": (_i, [_vp, _i, _i, _vp, _vp, C.c_longlong, _vp]),
     "yv_colsum_ws_floats": (_sz, [_i, _i]),
@@ -867,29 +870,38 @@ def head_bwd(feats, w1t, b1, w2, dlogits, R, nc, dw1, db1, dw2, db2, dfeats, ws)
                           _p(dw2), _p(db2), _p(dfeats), dfeats.stride(0), _p(ws), _st()), "yv_head_bwd")
 
 
-def wgrad(dy: torch.Tensor, x: torch.Tensor, dw: torch.Tensor, T: Optional[int] = None):
-    """dw (N,K) f32 = dy[:T]^T @ x[:T]; dy (>=T,N), x (>=T,K) bf16, T a multiple of 64 with zero tail rows."""
+def wgrad(dy: torch.Tensor, x: torch.Tensor, dw: torch.Tensor, T: Optional[int] = None, tile_n: Optional[int] = None):
+    """dw (N,K) f32 = dy[:T]^T @ x[:T]; dy (>=T,N), x (>=T,K) bf16, T a multiple of 64 with zero tail rows.
+    tile_n: None = yv_wgrad (128 x 128 tiles); 128 / 64 / 32 = that N tile, 0 = the one wgrad_route picks (yv_wgrad_tiled)."""
     for t_ in (dy, x, dw):
         if not t_.is_cuda or t_.stride(-1) != 1:
             raise YvError("wgrad operands must be device tensors with unit column stride")
     t = dy.shape[0] if T is None else T
-    check(lib.yv_wgrad(_p(dy), dy.stride(0), _p(x), x.stride(0), t, dy.shape[1], x.shape[1], _p(dw), dw.stride(0), _st()),
-          "yv_wgrad")
+    if tile_n is None:
+        check(lib.yv_wgrad(_p(dy), dy.stride(0), _p(x), x.stride(0), t, dy.shape[1], x.shape[1], _p(dw), dw.stride(0), _st()),
+              "yv_wgrad")
+    else:
+        check(lib.yv_wgrad_tiled(_p(dy), dy.stride(0), _p(x), x.stride(0), t, dy.shape[1], x.shape[1], _p(dw), dw.stride(0),
+                                 int(tile_n), _st()), "yv_wgrad_tiled")
     return dw
 
 
-def wgrad_conv3(dyp: torch.Tensor, xp: torch.Tensor, dw: torch.Tensor, T: int, pitch: int):
+def wgrad_conv3(dyp: torch.Tensor, xp: torch.Tensor, dw: torch.Tensor, T: int, pitch: int, tile_n: Optional[int] = None):
     """dw (N, 9*Cin) f32 = 3x3 / stride 1 weight gradient from operands over the zero-padded pixel grid (view_op VIEW_PAD):
     dyp (>=T, N) bf16 with zero ring / tail, xp (T, Cin) bf16 DENSE view inside a buffer that has pitch + 1 rows of finite
-    values on both sides (see yv_wgrad_conv3)."""
+    values on both sides (see yv_wgrad_conv3).  tile_n as wgrad takes it (yv_wgrad_conv3_tiled)."""
     for t_ in (dyp, xp, dw):
         if not t_.is_cuda or t_.stride(-1) != 1:
             raise YvError("wgrad_conv3 operands must be device tensors with unit column stride")
     cin = xp.shape[1]
     if xp.stride(0) != cin or dw.shape[1] != 9 * cin:
         raise YvError("wgrad_conv3: xp must be dense (row stride Cin) and dw (N, 9*Cin)")
-    check(lib.yv_wgrad_conv3(_p(dyp), dyp.stride(0), _p(xp), cin, pitch, T, dyp.shape[1], _p(dw), dw.stride(0), _st()),
-          "yv_wgrad_conv3")
+    if tile_n is None:
+        check(lib.yv_wgrad_conv3(_p(dyp), dyp.stride(0), _p(xp), cin, pitch, T, dyp.shape[1], _p(dw), dw.stride(0), _st()),
+              "yv_wgrad_conv3")
+    else:
+        check(lib.yv_wgrad_conv3_tiled(_p(dyp), dyp.stride(0), _p(xp), cin, pitch, T, dyp.shape[1], _p(dw), dw.stride(0),
+                                       int(tile_n), _st()), "yv_wgrad_conv3_tiled")
     return dw
 
 
@@ -1184,6 +1196,17 @@ def linear_route(M: int, N: int, K: int, flags: int = 0, lda: Optional[int] = No
                               int(res_f32), ldaux, int(mx),
                               ws_bytes, n_cu, out), "yv_linear_route")
     return LinearRoute(*out)
+
+
+WgradRoute = collections.namedtuple("WgradRoute", "tile_n tile_k tiles slices workgroups")
+
+
+def wgrad_route(T: int, N: int, K: int, tile_n: int = 0, ws_bytes: int = STREAM_WS_BYTES, n_cu: int = 256) -> WgradRoute:
+    """Route wgrad / wgrad_conv3 (K = 9 * Cin) take for this shape and tile_n under the current options (host only): see
+    yv_wgrad_route in include/yv_hip.h.  tile_n = 128 is what tile_n=None launches."""
+    out = (C.c_int * len(WgradRoute._fields))()
+    check(lib.yv_wgrad_route(T, N, K, tile_n, ws_bytes, n_cu, out), "yv_wgrad_route")
+    return WgradRoute(*out)
 
 
 def wgrad_mxfp8(dyt: torch.Tensor, dy_scale: torch.Tensor, xt: torch.Tensor, x_scale: torch.Tensor, dw: torch.Tensor):

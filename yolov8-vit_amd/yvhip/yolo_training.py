@@ -23,7 +23,7 @@ from . import (OPT_ADAMW, OPT_SGD_NESTEROV, VIEW_ADD, VIEW_COPY, VIEW_PAD, VIEW_
                blob_nhwc8, bn_act_bwd, bn_act_fwd, ema_update, optim_step,
                bn_stats, bn_ws_floats, cast_colsum, colsum_ws_floats, conv_view, conv_weight_dgrad, detect_loss,
                detect_loss_ws_bytes, im2col3, maxpool5_bwd, mview, require_gpu, sgd_step, sppf_pool, view_op, wgrad, wgrad_conv3)
-from .engines import LAYER_STRIDE, REG_MAX, detect_widths, yolo_conv_keys, yolo_layers
+from .engines import LAYER_STRIDE, REG_MAX, _env_flag, detect_widths, yolo_conv_keys, yolo_layers
 
 BN_EPS, BN_MOMENTUM = 1e-3, 0.03
 
@@ -54,6 +54,22 @@ def init_yolo_train_state(scale: str = "n", nc: int = 5, seed: int = 42) -> Dict
             sd[key + ".bias"] = (torch.full((co,), 1.0) if ".cv2." in key else
                                  torch.full((co,), math.log(5 / nc / (640 / (8 << s_idx)) ** 2)))
     return sd
+
+
+def yolo_wgrad_shapes(scale: str, nc: int, size: int = 640, batch: int = 16,
+                      implicit: bool = True) -> List[Tuple[str, int, int, int, int]]:
+    """(key, T, N, K, pitch) of every weight-gradient product of a YoloTrainer step (host only): dW (N, K) over T tokens,
+    channels padded to 8, T to 64.  pitch > 0: a 3x3 / stride 1 layer on the zero-padded pixel grid of that row pitch
+    (wgrad_conv3; `implicit`), 0: wgrad on the activation (1x1) or on its im2col."""
+    out = []
+    for key, cin, cout, k in yolo_conv_keys(scale, nc):
+        parts = key.split(".")
+        idx = int(parts[1])
+        h = size // ((8, 16, 32)[int(parts[3])] if idx == 22 else LAYER_STRIDE[idx])
+        s1 = k == 3 and not (idx != 22 and len(parts) == 3)      # "model.<i>.conv": the stem and the stride-2 convolutions
+        pitch = h + 2 if s1 and implicit else 0
+        out.append((key, _r64(batch * pitch * pitch if pitch else batch * h * h), (cout + 7) // 8 * 8, k * k * ((cin + 7) // 8 * 8), pitch))
+    return out
 
 
 class _Act:
@@ -95,7 +111,7 @@ class YoloTrainer:
     def __init__(self, state: Dict[str, torch.Tensor], scale: str = "n", nc: int = 5, size: int = 640, batch: int = 16,
                  lr: float = 1e-4, momentum: float = 0.937, weight_decay: float = 5e-4, device: str = "cuda:0",
                  optimizer: str = "sgd", ema: bool = False, ema_decay: float = 0.9999, ema_tau: float = 2000.0,
-                 overlap_wgrad: bool = True, implicit_wgrad: bool = True):
+                 overlap_wgrad: bool = True, implicit_wgrad: bool = True, narrow_wgrad: Optional[bool] = None):
         require_gpu()
         if size % 32:
             raise YvError("input size must be a multiple of 32")
@@ -103,6 +119,9 @@ class YoloTrainer:
         self.lr, self.momentum, self.weight_decay = lr, momentum, weight_decay
         self.overlap_wgrad, self.s_w, self._pending = overlap_wgrad, None, []
         self.implicit_wgrad = implicit_wgrad               # 3x3 / stride 1 weight gradients without an im2col buffer
+        # opt-in: weight gradients on the N tile wgrad_route picks (32 / 64 x 256 for few output channels); off = yv_wgrad's 128 x 128
+        self.narrow_wgrad = _env_flag(narrow_wgrad, "YV_YOLO_NARROW_WGRAD")
+        self._wgrad_tile = 0 if self.narrow_wgrad else None
         if optimizer not in ("sgd", "sgd_nesterov", "adamw"):
             raise YvError("optimizer must be 'sgd', 'sgd_nesterov' or 'adamw'")
         self.optimizer, self.use_ema, self.ema_decay, self.ema_tau = optimizer, ema, ema_decay, ema_tau
@@ -399,7 +418,7 @@ class YoloTrainer:
         dz = self.dz[b.key]
         dw = self.gr(b.w).view(b.cout, b.taps * b.cin)
         if b.k == 1:
-            wgrad(dz, x_buf[:, x_off:x_off + b.cin], dw, T=Tp)
+            wgrad(dz, x_buf[:, x_off:x_off + b.cin], dw, T=Tp, tile_n=self._wgrad_tile)
         elif b.s == 1 and self.implicit_wgrad:
             # no im2col: both operands are copied once onto the zero-padded pixel grid, where every tap is a constant row
             # offset and the three taps of a kernel row are contiguous (yv_wgrad_conv3)
@@ -412,13 +431,13 @@ class YoloTrainer:
             view_op(VIEW_PAD, mview(dz), mview(dzp), self.B, hout, hout)
             if tpp != tpad:
                 dzp[tpad:].zero_()
-            wgrad_conv3(dzp, xp, dw, tpp, hp)
+            wgrad_conv3(dzp, xp, dw, tpp, hp, tile_n=self._wgrad_tile)
         else:
             col = self.col[:Tp * 9 * b.cin].view(Tp, 9 * b.cin)
             if Tp != T:
                 col[T:].zero_()
             im2col3(mview(x_buf, x_off, b.cin), self.B, hin, hin, b.s, col)
-            wgrad(dz, col, dw, T=Tp)
+            wgrad(dz, col, dw, T=Tp, tile_n=self._wgrad_tile)
 
     def _flush_wgrads(self):
         """The weight gradients of the blocks back-propagated since the last flush go to a second HIP stream: nothing on
