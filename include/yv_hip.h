@@ -571,12 +571,25 @@ int yv_wgrad_tiled(const void* dY, int ldy, const void* X, int ldx, int T, int N
  * split); n_cu: CUs of the device, 0 = 256 (what the launch path passes: the slice rule's slot constants are that part's).
  * Returns YV_OK and fills *out, or YV_ERR_ARG where the launch would reject T, N, K or tile_n. */
 typedef struct {
-    int tile_n, tile_k; /* output tile of a workgroup: 128 x 128, 64 x 256 or 32 x 256 */
+    int tile_n, tile_k; /* output tile of a workgroup: 128 x 128, 64 x 256 or 32 x 256 (yv_wgrad_wide_route: or 256 x 128) */
     int tiles;          /* ceil(N / tile_n) * ceil(K / tile_k) */
     int slices;         /* token slices S (1: no split, no reduce pass) */
     int workgroups;     /* tiles * slices */
 } yv_wgrad_route_t;
 int yv_wgrad_route(int T, int N, int K, int tile_n, size_t ws_bytes, int n_cu, yv_wgrad_route_t* out);
+
+/* yv_wgrad on 256 (n) x 128 (k) output tiles (gemm_tn_wide_kernel: three quarters of the LDS-DMA traffic of the 128 x 128 tiles
+ * per MFMA; matrix-shaped dW, e.g. the classifier's linears).  Operands and preconditions are yv_wgrad's.  mode 1: always the wide
+ * tile; mode 0: routed - the wide tile where yv_wgrad_wide_route picks it, otherwise exactly the launch of yv_wgrad; any other
+ * mode: YV_ERR_ARG.  For an equal number of token slices the wide tile gives the bits of yv_wgrad. */
+int yv_wgrad_wide(const void* dY, int ldy, const void* X, int ldx, int T, int N, int K, float* dW, int ldw, int mode,
+                  void* stream);
+/* The route of yv_wgrad_wide, decided by the function its launch calls; host only, as yv_wgrad_route.  Wide (tile_n = 256,
+ * tile_k = 128) under mode 1, and under mode 0 where N >= 256, K >= 128, the 128 x 128 launch has more than 16 tiles and those
+ * tiles times T / 64 are at least 25,000 (below that the wide tile measured slower); else the result of
+ * yv_wgrad_route(T, N, K, 128, ...).  Slices of the wide tile: one round of the 2 * n_cu workgroup slots, at least 128 token
+ * rows per slice, at most 16, even when more than two; option "wgrad_split" > 0 forces the count; never more than ws_bytes holds. */
+int yv_wgrad_wide_route(int T, int N, int K, int mode, size_t ws_bytes, int n_cu, yv_wgrad_route_t* out);
 
 /* Weight gradient of a 3x3 / stride 1 / pad 1 convolution with no im2col buffer: dW (N, 9*Cin) f32, column
  * ((dy+1)*3 + dx+1)*Cin + ci.  Operands over the zero-padded pixel grid (B, H+2, W+2), T = that pixel count rounded up to

@@ -1808,6 +1808,140 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_narrow_kernel(GemmArgs g) {
     }
 }
 
+// The same product for large dW (wgrad_wide_route picks it; opt-in): 256 (n) x 128 (k) output tiles, so a
+// workgroup moves 24 KB through the LDS-DMA path per 32 tokens where two 128 x 128 workgroups move 32 KB for the same MFMAs.
+//   Stage: 32 tokens = dY as TWO [32][128] sub-tiles + X as ONE, each in gemm_tn_kernel's layout (256-byte rows, tn_swz<128>;
+//   the swizzle and tr_frag's row mapping repeat every 32 rows, so a stage reads as step ks = 0 of a 64-token tile): 24 KB, two
+//   of them (48 KB), the DMA of stage s + 1 issued before the MFMAs of stage s and drained (vmcnt(0)) at the stage's only barrier,
+//   as gemm_tn_kernel does per 64 tokens (a ring of three with a counted wait measured equal or slower).  Wave w owns n columns 128 (w / 2) .. + 127 (dY sub-tile w / 2) x k columns 64 (w % 2) .. + 63:
+//   8 x 4 fragments, 32 accumulators, 32 MFMAs per stage as gemm_tn_kernel has per 32 tokens.
+//   Edges as gemm_tn_narrow_kernel: no DMA, LDS read or MFMA for a 16-column fragment wholly past N or K (one branch-free loop
+//   per wave-uniform pair of live counts); chunks past N / K inside a live fragment clamp to N - 8 / K - 8.
+// Summation: the MFMA, tr_frag's token-to-slot mapping per 32 tokens, the ascending token walk and the slice boundaries (whole
+// 64-token tiles, t0 = nt * slice / S) are gemm_tn_kernel's: for an equal slice count the results are bit-identical.
+__global__ __launch_bounds__(256, 2) void gemm_tn_wide_kernel(GemmArgs g) {
+    constexpr int TB = 32, SUB = TB * 256, STAGE = 3 * SUB;   // bytes: a [32][128] sub-tile; dY sub-tiles 0 and 1, then X
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int Nw = g.M, Kw = g.N, T = g.K;
+    int bid = blockIdx.x;
+    const int S = g.splitk > 1 ? g.splitk : 1;
+    const int slice = bid % S;
+    bid /= S;
+    const int tn_ = bid / g.tiles_n, tk_ = bid - tn_ * g.tiles_n;
+    const int n0 = tn_ * 256, k0 = tk_ * 128;
+    const int n_live = Nw - n0 < 256 ? Nw - n0 : 256, k_live = Kw - k0 < 128 ? Kw - k0 : 128;   // columns inside dW: > 0, multiples of 8
+    const int wn = wave >> 1, wk = wave & 1;
+    int nnf = (n_live - wn * 128 + 15) >> 4;                  // live n fragments of this wave
+    nnf = nnf < 0 ? 0 : nnf > 8 ? 8 : nnf;
+    int nkf = (k_live - wk * 64 + 15) >> 4;                   // live k fragments of this wave
+    nkf = nkf < 0 ? 0 : nkf > 4 ? 4 : nkf;
+    const int ysubs = n_live > 128 ? 2 : 1;                   // dY sub-tiles with a live column
+
+    // DMA.  lane -> (row = 4 * instr + lane / 16, chunk' = lane % 16) of a sub-tile, source chunk = chunk' ^ swz(row); two
+    // instructions per wave and sub-tile.  A lane whose source chunk lies in a dead fragment issues nothing.
+    const uint16_t* ysrc[4];
+    const uint16_t* xsrc[2];
+    unsigned ylive = 0, xlive = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int row = ((j & 1) * 4 + wave) * 4 + (lane >> 4);          // 0..31
+        const int c = (j >> 1) * 128 + (((lane & 15) ^ tn_swz(row)) << 3);
+        ylive |= (unsigned)((c & ~15) < n_live) << j;
+        ysrc[j] = g.a0 + (long long)row * g.lda0 + n0 + (c < n_live ? c : n_live - 8);
+    }
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int row = (j * 4 + wave) * 4 + (lane >> 4);
+        const int c = ((lane & 15) ^ tn_swz(row)) << 3;
+        xlive |= (unsigned)((c & ~15) < k_live) << j;
+        xsrc[j] = g.w + (long long)row * g.lda1 + k0 + (c < k_live ? c : k_live - 8);
+    }
+    auto issue = [&](int s, int buf) {
+        unsigned char* Yt = smem + buf * STAGE;
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if ((j >> 1) < ysubs)                             // wave-uniform: nothing is issued for a sub-tile past N
+                if (ylive >> j & 1)
+                    __builtin_amdgcn_global_load_lds((gptr_t)(ysrc[j] + (long long)s * TB * g.lda0),
+                                                     (lptr_t)(Yt + (j >> 1) * SUB + ((j & 1) * 4 + wave) * 1024), 16, 0, 0);
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+            if (xlive >> j & 1)
+                __builtin_amdgcn_global_load_lds((gptr_t)(xsrc[j] + (long long)s * TB * g.lda1),
+                                                 (lptr_t)(Yt + 2 * SUB + (j * 4 + wave) * 1024), 16, 0, 0);
+    };
+    f32x4 acc[4][8];                                          // [k fragment][n fragment]
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    const int fi = lane & 15, mg = lane >> 4;
+    const int nt_all = T / 64;
+    const int s0 = 2 * (int)((long long)nt_all * slice / S), s1 = 2 * (int)((long long)nt_all * (slice + 1) / S);   // 32-token stages
+    if (s0 < s1) {
+        issue(s0, 0);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+    }
+    auto walk = [&](auto nk, auto nn) {
+        constexpr int NK = decltype(nk)::value, NN = decltype(nn)::value;
+        for (int s = s0; s < s1; ++s) {
+            const int cur = (s - s0) & 1;
+            if (s + 1 < s1) issue(s + 1, cur ^ 1);
+            if constexpr (NK > 0) {
+                const unsigned char* Yt = smem + cur * STAGE + wn * SUB;
+                const unsigned char* Xt = smem + cur * STAGE + 2 * SUB;
+                bf16x8 fx[NK], fy[NN];
+#pragma unroll
+                for (int i = 0; i < NK; ++i) fx[i] = tr_frag(Xt, 0, lane, wk * 64 + i * 16);
+#pragma unroll
+                for (int j = 0; j < NN; ++j) fy[j] = tr_frag(Yt, 0, lane, j * 16);
+#pragma unroll
+                for (int i = 0; i < NK; ++i)
+#pragma unroll
+                    for (int j = 0; j < NN; ++j)
+                        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fx[i], fy[j], acc[i][j], 0, 0, 0);
+            }
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __syncthreads();
+        }
+    };
+    auto by_n = [&](auto nk) {                                // nnf = 1 .. 8
+        switch (nnf) {
+            case 8: walk(nk, std::integral_constant<int, 8>{}); break;
+            case 7: walk(nk, std::integral_constant<int, 7>{}); break;
+            case 6: walk(nk, std::integral_constant<int, 6>{}); break;
+            case 5: walk(nk, std::integral_constant<int, 5>{}); break;
+            case 4: walk(nk, std::integral_constant<int, 4>{}); break;
+            case 3: walk(nk, std::integral_constant<int, 3>{}); break;
+            case 2: walk(nk, std::integral_constant<int, 2>{}); break;
+            default: walk(nk, std::integral_constant<int, 1>{});
+        }
+    };
+    if (nnf == 0) nkf = 0;                                    // a wave with no live fragment only feeds the DMA
+    switch (nkf) {                                            // 0 .. 4
+        case 4: by_n(std::integral_constant<int, 4>{}); break;
+        case 3: by_n(std::integral_constant<int, 3>{}); break;
+        case 2: by_n(std::integral_constant<int, 2>{}); break;
+        case 1: by_n(std::integral_constant<int, 1>{}); break;
+        default: walk(std::integral_constant<int, 0>{}, std::integral_constant<int, 1>{});
+    }
+    // D[row = k (lane>>4)*4 + reg][col = n (lane&15)]  ->  dW[n][k..k+3]
+    float* out = S > 1 ? g.partial + (long long)slice * Nw * Kw : (float*)g.out;
+    const long long ldo = S > 1 ? Kw : g.ldo;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const int n = n0 + wn * 128 + j * 16 + fi;
+        if (n >= Nw) continue;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int k = k0 + wk * 64 + i * 16 + mg * 4;
+            if (k < Kw) *(float4*)(out + (long long)n * ldo + k) = make_float4(acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]);
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // Skinny-M linear (M <= 256: one row per crop - the classifier's last-block tail on the cls rows, and its head).  Such a product
 // is a pass over the weight matrix (fc2 of ViT-B: 4.7 MB against 64 x 768 outputs); 128 x 128 tiles make 6 .. 24 workgroups of it,
@@ -2193,6 +2327,39 @@ WgradRoute wgrad_route(int T, int N, int K, int tile_n, size_t ws_bytes, int n_c
     if (tile_n == 128) return wide;
     const WgradRoute r = wgrad_tiled_route(T, N, K, tile_n, ws_bytes);
     if (tile_n == 64 && r.workgroups < wide.workgroups && wide.workgroups <= 2 * (n_cu > 0 ? n_cu : 256)) return wide;
+    return r;
+}
+
+// The route of yv_wgrad_wide: ONE rule for its launch and for yv_wgrad_wide_route (measurements: DESIGN.md section 21,
+// profiles/wgrad_wide_layers.txt, profiles/wgrad_wide_slices.txt).  mode 1: the 256 (n) x 128 (k) tiles of gemm_tn_wide_kernel.
+// mode 0: those tiles where N >= 256, K >= 128, the 128 x 128 launch has more than 16 tiles (matrix shapes, not the conv regime)
+// AND those tiles times the 64-token tiles of T number at least 25,000; everywhere else exactly wgrad_route(T, N, K, 128).  The
+// wide tile's gain grows with the MFMA work, its price (half the workgroups, twice the slices to reduce) does not: every measured
+// shape below the bound was no faster wide (all of ViT-B/16 at 32 crops x 1.00 - 1.47, qkv at 64 crops x 1.04, every proj, head and
+// patch embedding x 1.15 - 1.49), every one above it faster (x 0.85 - 0.98).
+// Slices of the wide tile: one round of the 2 * n_cu workgroup slots, at least 128 token rows per slice, at most 16, and EVEN
+// when more than two: slice = workgroup % S and workgroups b, b + 8 share an XCD's L2, so under an odd S every XCD reads every
+// token slice (qkv of ViT-B/16: S = 8 48 us, S = 9 54 us at 32 crops, 114 against 136 us at 128).  "wgrad_split" > 0 forces the
+// count at any tile count; then what the workspace holds.
+static int wgrad_wide_slices(long long tiles, int T, size_t out_bytes, size_t ws_bytes, int n_cu) {
+    int S = (int)(2LL * n_cu / tiles);
+    if (S > T / 128) S = T / 128;
+    if (S > 16) S = 16;
+    if (S > 2) S &= ~1;
+    if (g_opt_wgrad_split > 0) S = g_opt_wgrad_split;
+    const size_t fit = ws_bytes / out_bytes;
+    if ((size_t)S > fit) S = (int)fit;
+    return S >= 2 ? S : 1;
+}
+WgradRoute wgrad_wide_route(int T, int N, int K, int mode, size_t ws_bytes, int n_cu) {
+    const WgradRoute base = wgrad_tiled_route(T, N, K, 128, ws_bytes);
+    if (mode == 0 && !(N >= 256 && K >= 128 && base.tiles > 16 && (long long)base.tiles * (T / 64) >= 25000)) return base;
+    WgradRoute r = {};
+    r.tile_n = 256;
+    r.tile_k = 128;
+    r.tiles = ((N + 255) / 256) * ((K + 127) / 128);
+    r.slices = ws_bytes ? wgrad_wide_slices(r.tiles, T, (size_t)N * K * sizeof(float), ws_bytes, n_cu > 0 ? n_cu : 256) : 1;
+    r.workgroups = r.tiles * r.slices;
     return r;
 }
 
@@ -2614,27 +2781,38 @@ extern "C" int yv_linear_nn(const void* A, int lda, const void* Wkn, int ldw, co
     return launch_dma<128, 128, 2, 2, 0, true>(g, (hipStream_t)stream);
 }
 
-static int wgrad_impl(const void* dY, int ldy, const void* X, int ldx, int T, int N, int K, float* dW, int ldw, int seg_len,
-                      long long seg_stride, int tile_n, void* stream) {
-    if (!dY || !X || !dW || T <= 0 || N <= 0 || K <= 0) return YV_ERR_ARG;
-    if ((T & 63) || (N & 7) || (K & 7) || (ldy & 7) || (ldx & 7) || (ldw & 3)) return YV_ERR_ARG;
-    if (((uintptr_t)dY | (uintptr_t)X | (uintptr_t)dW) & 15) return YV_ERR_ARG;
-    if (tile_n != 0 && tile_n != 32 && tile_n != 64 && tile_n != 128) return YV_ERR_ARG;
+static bool wgrad_args_ok(const void* dY, int ldy, const void* X, int ldx, int T, int N, int K, const float* dW, int ldw) {
+    if (!dY || !X || !dW || T <= 0 || N <= 0 || K <= 0) return false;
+    if ((T & 63) || (N & 7) || (K & 7) || (ldy & 7) || (ldx & 7) || (ldw & 3)) return false;
+    return !(((uintptr_t)dY | (uintptr_t)X | (uintptr_t)dW) & 15);
+}
+
+// Launches the route: no decisions.  ws: the workspace the route was told of.
+static int wgrad_launch(const void* dY, int ldy, const void* X, int ldx, int T, int N, int K, float* dW, int ldw, int seg_len,
+                        long long seg_stride, const WgradRoute& r, void* ws, void* stream) {
     GemmArgs g = {};
     g.seg_len = seg_len; g.seg_stride = seg_stride;
     g.a0 = (const uint16_t*)dY; g.lda0 = ldy; g.w = (const uint16_t*)X; g.lda1 = ldx;
     g.M = N; g.N = K; g.K = T; g.out = dW; g.ldo = ldw; g.flags = YV_EPI_OUT_F32;
-    void* ws = nullptr; size_t wsb = 0;
-    if (!ws_lookup(stream, &ws, &wsb)) wsb = 0;
-    const WgradRoute r = wgrad_route(T, N, K, tile_n, wsb, 0);
     g.tiles_m = (N + r.tile_n - 1) / r.tile_n; g.tiles_n = (K + r.tile_k - 1) / r.tile_k;
     g.splitk = r.slices;
     if (g.splitk > 1) g.partial = (float*)ws;
-    void (*kern)(GemmArgs) = r.tile_n == 128 ? gemm_tn_kernel : r.tile_n == 64 ? gemm_tn_narrow_kernel<64> : gemm_tn_narrow_kernel<32>;
-    const size_t lds = r.tile_n == 128 ? 2 * 2 * 64 * 256 : 2 * (2 * 64 * 256 + 64 * r.tile_n * 2);
+    void (*kern)(GemmArgs) = r.tile_n == 256 ? gemm_tn_wide_kernel
+                             : r.tile_n == 128 ? gemm_tn_kernel : r.tile_n == 64 ? gemm_tn_narrow_kernel<64> : gemm_tn_narrow_kernel<32>;
+    const size_t lds = r.tile_n == 256 ? 2 * 3 * 32 * 256
+                       : r.tile_n == 128 ? 2 * 2 * 64 * 256 : 2 * (2 * 64 * 256 + 64 * r.tile_n * 2);
     if (r.tile_n != 128 && !yv_grant_lds((const void*)kern, lds)) return YV_ERR_LAUNCH;
     hipLaunchKernelGGL(kern, dim3(r.workgroups), dim3(256), lds, (hipStream_t)stream, g);
     return launch_splitk_reduce(g, (hipStream_t)stream);
+}
+
+static int wgrad_impl(const void* dY, int ldy, const void* X, int ldx, int T, int N, int K, float* dW, int ldw, int seg_len,
+                      long long seg_stride, int tile_n, void* stream) {
+    if (!wgrad_args_ok(dY, ldy, X, ldx, T, N, K, dW, ldw)) return YV_ERR_ARG;
+    if (tile_n != 0 && tile_n != 32 && tile_n != 64 && tile_n != 128) return YV_ERR_ARG;
+    void* ws = nullptr; size_t wsb = 0;
+    if (!ws_lookup(stream, &ws, &wsb)) wsb = 0;
+    return wgrad_launch(dY, ldy, X, ldx, T, N, K, dW, ldw, seg_len, seg_stride, wgrad_route(T, N, K, tile_n, wsb, 0), ws, stream);
 }
 
 extern "C" int yv_wgrad(const void* dY, int ldy, const void* X, int ldx, int T, int N, int K, float* dW, int ldw,
@@ -2652,6 +2830,21 @@ extern "C" int yv_wgrad_route(int T, int N, int K, int tile_n, size_t ws_bytes, 
     if ((T & 63) || (N & 7) || (K & 7)) return YV_ERR_ARG;
     if (tile_n != 0 && tile_n != 32 && tile_n != 64 && tile_n != 128) return YV_ERR_ARG;
     *out = wgrad_route(T, N, K, tile_n, ws_bytes, n_cu);
+    return YV_OK;
+}
+
+extern "C" int yv_wgrad_wide(const void* dY, int ldy, const void* X, int ldx, int T, int N, int K, float* dW, int ldw, int mode,
+                             void* stream) {
+    if (!wgrad_args_ok(dY, ldy, X, ldx, T, N, K, dW, ldw) || (mode != 0 && mode != 1)) return YV_ERR_ARG;
+    void* ws = nullptr; size_t wsb = 0;
+    if (!ws_lookup(stream, &ws, &wsb)) wsb = 0;
+    return wgrad_launch(dY, ldy, X, ldx, T, N, K, dW, ldw, 0, 0, wgrad_wide_route(T, N, K, mode, wsb, 0), ws, stream);
+}
+
+extern "C" int yv_wgrad_wide_route(int T, int N, int K, int mode, size_t ws_bytes, int n_cu, yv_wgrad_route_t* out) {
+    if (!out || T <= 0 || N <= 0 || K <= 0 || n_cu < 0 || (mode != 0 && mode != 1)) return YV_ERR_ARG;
+    if ((T & 63) || (N & 7) || (K & 7)) return YV_ERR_ARG;
+    *out = wgrad_wide_route(T, N, K, mode, ws_bytes, n_cu);
     return YV_OK;
 }
 

@@ -220,14 +220,18 @@ def _trainer_for(net, optimizer):
     recipe is replaced by a new one built from the module's weights (train_one_epoch writes them back after every epoch),
     with fresh momentum.  The same holds for the module's `_yv_train_cls_tail` (CFG.train_cls_tail: the last block trained on the
     cls rows, VitTrainer(cls_tail=True)); when it is not set the trainer is built without the argument and follows
-    YV_VIT_TRAIN_CLS_TAIL."""
+    YV_VIT_TRAIN_CLS_TAIL.  Likewise `_yv_train_wide_wgrad` (CFG.train_wide_wgrad: 256 x 128 weight-gradient tiles,
+    VitTrainer(wide_wgrad=True)) and YV_VIT_WIDE_WGRAD."""
     from yvhip.training import VitTrainer
     tr = getattr(net, "_yv_trainer", None)
     dtype = getattr(net, "_yv_train_dtype", "bf16")
     cls_tail = bool(getattr(net, "_yv_train_cls_tail", False))
+    wide_wgrad = bool(getattr(net, "_yv_train_wide_wgrad", False))
     if tr is not None and getattr(tr, "dtype", "bf16") != dtype:
         tr = None
     if tr is not None and getattr(tr, "cls_tail", False) != (cls_tail or os.environ.get("YV_VIT_TRAIN_CLS_TAIL", "0") == "1"):
+        tr = None
+    if tr is not None and getattr(tr, "wide_wgrad", False) != (wide_wgrad or os.environ.get("YV_VIT_WIDE_WGRAD", "0") == "1"):
         tr = None
     if tr is None:
         mom, wd = 0.9, 1e-3                                   # utils/trainClass.py:442-443
@@ -239,7 +243,8 @@ def _trainer_for(net, optimizer):
             dev = torch.device("cuda", torch.cuda.current_device())
         sd = {k: v.detach() for k, v in net.state_dict().items()}
         tr = VitTrainer(sd, net.model.arch, net.num_class, net.model.img, device=str(dev), momentum=mom, weight_decay=wd,
-                        **({} if dtype == "bf16" else {"dtype": dtype}), **({"cls_tail": True} if cls_tail else {}))
+                        **({} if dtype == "bf16" else {"dtype": dtype}), **({"cls_tail": True} if cls_tail else {}),
+                        **({"wide_wgrad": True} if wide_wgrad else {}))
         net._yv_trainer = tr
     return tr
 
@@ -461,12 +466,15 @@ def fit(net, train_loader, valid_loader, CFG, log=False, save_path=None):
     """Epoch loop of utils/trainClass.py:459-508 for caller-provided loaders: train, validate, keep the best
     state dict (optionally saved), write result.json when `log` (same shape as :475-490).  An optional CFG.train_dtype
     ("bf16" when absent, or "mxfp8": MXFP8 block linears, yvhip.training.VitTrainer) selects the fine-tune recipe; an optional
-    CFG.train_cls_tail (absent or False: as before) trains the last block on the cls rows (VitTrainer(cls_tail=True))."""
+    CFG.train_cls_tail (absent or False: as before) trains the last block on the cls rows (VitTrainer(cls_tail=True)); an optional
+    CFG.train_wide_wgrad (absent or False: as before) launches the bf16 weight gradients on 256 x 128 tiles
+    (VitTrainer(wide_wgrad=True))."""
     from yvhip.training import check_train_dtype
     dtype = getattr(CFG, "train_dtype", None) or "bf16"
     check_train_dtype(dtype, 128)                         # the width rule is checked when the trainer is built
     net._yv_train_dtype = dtype
     net._yv_train_cls_tail = bool(getattr(CFG, "train_cls_tail", False))
+    net._yv_train_wide_wgrad = bool(getattr(CFG, "train_wide_wgrad", False))
     optimizer = torch.optim.SGD(net.parameters(), CFG.lr, momentum=0.9, weight_decay=1e-3)   # hyper-parameter carrier
     best, results = 0.0, {}
     for epoch_num in range(1, CFG.epoch + 1):

@@ -143,6 +143,8 @@ _SIGS = {
     "yv_wgrad_tiled": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp]),
     "yv_wgrad_conv3_tiled": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp]),
     "yv_wgrad_route": (_i, [_i, _i, _i, _i, _sz, _i, _vp]),
+    "yv_wgrad_wide": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp]),
+    "yv_wgrad_wide_route": (_i, [_i, _i, _i, _i, _sz, _i, _vp]),
     "yv_transpose_bf16": (_i, [_vp, _i, _i, C.c_longlong, _vp, C.c_longlong, _vp]),
     "yv_cast_weights": (_i, [_vp, _i, _i, _vp, _vp, C.c_longlong, _vp]),
     "yv_colsum_ws_floats": (_sz, [_i, _i]),
@@ -886,6 +888,18 @@ def wgrad(dy: torch.Tensor, x: torch.Tensor, dw: torch.Tensor, T: Optional[int] 
     return dw
 
 
+def wgrad_wide(dy: torch.Tensor, x: torch.Tensor, dw: torch.Tensor, T: Optional[int] = None, routed: bool = False):
+    """wgrad on 256 (n) x 128 (k) output tiles (yv_wgrad_wide); operands as wgrad takes them.  routed=False: always the wide tile;
+    routed=True: the wide tile where wgrad_wide_route picks it, otherwise exactly what wgrad launches."""
+    for t_ in (dy, x, dw):
+        if not t_.is_cuda or t_.stride(-1) != 1:
+            raise YvError("wgrad operands must be device tensors with unit column stride")
+    t = dy.shape[0] if T is None else T
+    check(lib.yv_wgrad_wide(_p(dy), dy.stride(0), _p(x), x.stride(0), t, dy.shape[1], x.shape[1], _p(dw), dw.stride(0),
+                            0 if routed else 1, _st()), "yv_wgrad_wide")
+    return dw
+
+
 def wgrad_conv3(dyp: torch.Tensor, xp: torch.Tensor, dw: torch.Tensor, T: int, pitch: int, tile_n: Optional[int] = None):
     """dw (N, 9*Cin) f32 = 3x3 / stride 1 weight gradient from operands over the zero-padded pixel grid (view_op VIEW_PAD):
     dyp (>=T, N) bf16 with zero ring / tail, xp (T, Cin) bf16 DENSE view inside a buffer that has pitch + 1 rows of finite
@@ -1206,6 +1220,14 @@ def wgrad_route(T: int, N: int, K: int, tile_n: int = 0, ws_bytes: int = STREAM_
     yv_wgrad_route in include/yv_hip.h.  tile_n = 128 is what tile_n=None launches."""
     out = (C.c_int * len(WgradRoute._fields))()
     check(lib.yv_wgrad_route(T, N, K, tile_n, ws_bytes, n_cu, out), "yv_wgrad_route")
+    return WgradRoute(*out)
+
+
+def wgrad_wide_route(T: int, N: int, K: int, routed: bool = False, ws_bytes: int = STREAM_WS_BYTES, n_cu: int = 256) -> WgradRoute:
+    """Route wgrad_wide takes for this shape under the current options (host only): see yv_wgrad_wide_route in
+    include/yv_hip.h.  tile_n = 256 is the wide tile; routed=True may answer wgrad_route(T, N, K, 128)."""
+    out = (C.c_int * len(WgradRoute._fields))()
+    check(lib.yv_wgrad_wide_route(T, N, K, 0 if routed else 1, ws_bytes, n_cu, out), "yv_wgrad_wide_route")
     return WgradRoute(*out)
 
 

@@ -38,7 +38,7 @@ import torch
 from . import (EPI_GELU, EPI_GELU_BWD, EPI_OUT_F32, EPI_POSEMB, EPI_RES_F32, EPI_SAVE_PRE, YvError, attention_bwd,
                attention_bwd_long, attention_cls_bwd, attention_cls_train, attention_long, attention_train, cast_colsum, cls_rows, colsum_bf16, head_bwd, layernorm,
                layernorm_bwd, lib, linear, linear_ex, linear_mxfp8_ex, linear_nn, loss_fwd_bwd, quant_mxfp8_2d, r128, require_gpu, sgd_step,
-               token_reduce, transpose_bf16_batched, wgrad, wgrad_mxfp8, wrapper_head)
+               token_reduce, transpose_bf16_batched, wgrad, wgrad_mxfp8, wgrad_wide, wrapper_head)
 from .engines import _env_flag, vit_cfg
 
 
@@ -65,7 +65,7 @@ class VitTrainer:
     def __init__(self, state: Dict[str, torch.Tensor], name: str, num_classes: int = 5, img: int = 224,
                  device: str = "cuda:0", momentum: float = 0.9, weight_decay: float = 1e-3,
                  bucket_mb: float = 32.0, dtype: str = "bf16", long_attn: Optional[bool] = None,
-                 long_attn_bwd: Optional[bool] = None, cls_tail: Optional[bool] = None):
+                 long_attn_bwd: Optional[bool] = None, cls_tail: Optional[bool] = None, wide_wgrad: Optional[bool] = None):
         """long_attn (opt-in, both dtypes): the forward attention runs as attention_long(..., lse=...) in place of attention_train
         where the token count exceeds 224 (a shorter-sequence trainer accepts the flag and keeps attention_train); attention_bwd
         is the same and consumes that lse.  None reads the environment variable YV_VIT_LONG_ATTN ("1" = on, unset = off).
@@ -82,10 +82,16 @@ class VitTrainer:
         in bf16 on the bf16 mirror (forward `linear`, data gradients `linear_nn` on the master layout, weight gradients `wgrad`):
         quantising a 32-row operand buys nothing, so the last block's small products are more precise than the MX ones; its
         full-row qkv product and that product's two gradients stay MX.  A model of more than 8192 tokens accepts the flag and runs
-        the full block.  None reads YV_VIT_TRAIN_CLS_TAIL ("1" = on, unset = off)."""
+        the full block.  None reads YV_VIT_TRAIN_CLS_TAIL ("1" = on, unset = off).
+
+        wide_wgrad (opt-in, both dtypes, independent of the flags above): every bf16 weight gradient - the
+        block linears, the compact cls-row form, the head and the patch embedding - is launched as wgrad_wide(..., routed=True) in
+        place of wgrad on the same operands: 256 x 128 output tiles where wgrad_wide_route picks them, wgrad's own launch elsewhere.
+        The MX column-form launches are not touched.  None reads YV_VIT_WIDE_WGRAD ("1" = on, unset = off)."""
         self.long_attn = _env_flag(long_attn, "YV_VIT_LONG_ATTN")
         self.long_attn_bwd = _env_flag(long_attn_bwd, "YV_VIT_LONG_ATTN_BWD")
         self.cls_tail = _env_flag(cls_tail, "YV_VIT_TRAIN_CLS_TAIL")
+        self.wide_wgrad = _env_flag(wide_wgrad, "YV_VIT_WIDE_WGRAD")
         self.P_, self.D, self.L, self.H = vit_cfg(name)
         check_train_dtype(dtype, self.D)
         require_gpu()
@@ -294,17 +300,24 @@ class VitTrainer:
             wtq, wts = self.wmx[key][2:]
             linear_mxfp8_ex(*self._quant(b, dy, S[col]), wtq, wts, None, out, **epi)
 
+    def _wgrad_bf16(self, dy: torch.Tensor, x: torch.Tensor, dw: torch.Tensor, **kw):
+        """The bf16 weight-gradient launch: wgrad, or with wide_wgrad the routed wgrad_wide on the same operands."""
+        if self.wide_wgrad:
+            wgrad_wide(dy, x, dw, routed=True, **kw)
+        else:
+            wgrad(dy, x, dw, **kw)
+
     def _wgrad(self, b: dict, S: dict, i: int, w: str, dy: str, col: str, x: str, tail: Optional[dict] = None):
         """Weight gradient G[w] = dy^T . x of block i.  `dy` names the gradient operand in the parity set S (`col`: its column form),
         `x` the activation.  bf16: wgrad on the 64-row padded, zero-tailed operands.  mxfp8: wgrad_mxfp8 on the column forms.
         Operands that `tail` holds are compact cls rows: wgrad over their Rp rows, in both recipes."""
         dw = self._g2d(f"model.blocks.{i}.{w}")
         if tail is not None and dy in tail:
-            wgrad(tail[dy], tail[x], dw, T=b["Rp"])
+            self._wgrad_bf16(tail[dy], tail[x], dw, T=b["Rp"])
         elif self.dtype == "mxfp8":
             wgrad_mxfp8(*S[col], *b["xc"][i][x], dw)
         else:
-            wgrad(S[dy], b["full"][x][i], dw)
+            self._wgrad_bf16(S[dy], b["full"][x][i], dw)
 
     def _side_stream_epilogue(self, b: dict, S: dict, i: int, main, dwide: torch.Tensor, dqkv: torch.Tensor,
                               tail: Optional[dict] = None):
@@ -444,7 +457,7 @@ class VitTrainer:
         self.reducer.ready(self.off["fc.1.weight"])
         colsum_bf16(b["dfeats"], b["ws"][:1024], b["ws"][1024:], rows=R)
         self.g("model.head.bias").copy_(b["ws"][:1000])
-        wgrad(b["full"]["dfeats"][:, :1000], b["full"]["c"], self._g2d("model.head.weight"))
+        self._wgrad_bf16(b["full"]["dfeats"][:, :1000], b["full"]["c"], self._g2d("model.head.weight"))
         linear_nn(b["dfeats"], self.w_head_pad, b["dc"])
         b["dx"].zero_()
         if self._tail:
@@ -471,7 +484,7 @@ class VitTrainer:
         self.g("model.cls_token").copy_(b["dpos"][0].view(1, 1, D))
         b["dtok32"].copy_(b["dx"].view(R, N, D)[:, 1:, :].reshape(R * tok, D))          # drop the cls rows (copy only)
         cast_colsum(b["dtok32"], b["dtok"], self.g("model.patch_embed.proj.bias"), b["ws"])
-        wgrad(b["full"]["dtok"], b["full"]["patches"], self._g2d("model.patch_embed.proj.weight"))
+        self._wgrad_bf16(b["full"]["dtok"], b["full"]["patches"], self._g2d("model.patch_embed.proj.weight"))
         return loss
 
     # ---- optimizer ----------------------------------------------------------------------------------------
