@@ -413,6 +413,25 @@ int yv_conv2d_ws(const yv_view* in0, const yv_view* in1, int B, int Hout, int Wo
                  const void* weight, const float* bias, int Cout, void* out, int out_ld, const void* res, int res_ld,
                  int flags, void* ws, size_t ws_bytes, void* stream);
 
+/* yv_conv2d_ws with the BatchNorm batch statistics of its output taken in the epilogue (opt-in: YoloTrainer(fused_bn_stats=True)).
+ * out (bf16) receives the same bits yv_conv2d_ws writes for the same arguments.  Every workgroup also writes, for its tile of
+ * 128 rows (tm = first row / 128) and each of its columns n < Cout,
+ *   stats_ws[(tm * 2 + 0) * Cout + n] = sum over the tile's rows m < B*Hout*Wout of v,   stats_ws[(tm * 2 + 1) * Cout + n] = sum of v * v,
+ * v = the bf16-rounded value stored to out, back in f32; f32 sums in an order the code fixes (bitwise reproducible), each float
+ * written by one plain store (nothing is zeroed or accumulated in memory).  This is the (chunks, 2, C) layout of yv_bn_stats'
+ * first stage with chunks = ceil(T / 128); yv_bn_stats_finish turns it into mean / rstd.
+ * Accepted: one source, bf16 output, flags = 0 or YV_EPI_BIAS (anything else YV_ERR_ARG), Cout % 8 == 0, the other argument
+ * rules of yv_conv2d.  A batch yv_conv2d_ws would take in sub-batches (a source beyond 2 GB) is YV_ERR_LIMIT: the tiles are one
+ * sequence.  stats_ws_floats < yv_conv_stats_ws_floats(B*Hout*Wout, Cout): YV_ERR_WORKSPACE.  All of these are decided on the
+ * host before any HIP call.  The call never splits K (ws / ws_bytes are accepted for symmetry with yv_conv2d_ws); otherwise its
+ * route is yv_conv2d_ws's: yv_conv2d_instance under "conv_splitk" = 0 reports it. */
+int yv_conv2d_stats(const yv_view* in0, int B, int Hout, int Wout, int ksize, int stride, const void* weight,
+                    const float* bias, int Cout, void* out, int out_ld, int flags, float* stats_ws, size_t stats_ws_floats,
+                    void* ws, size_t ws_bytes, void* stream);
+/* Floats of yv_conv2d_stats' workspace for T output rows: ceil(T / 128) * 2 * Cout tile partials and, where there are more
+ * than 2048 tiles, the chunk partials yv_bn_stats_finish folds them into (at most 2048 * 2 * Cout).  0 for T or Cout <= 0. */
+size_t yv_conv_stats_ws_floats(long long T, int Cout);
+
 /* Linear: out[M,N] = A[M,K] @ W[N,K]^T (+bias)(+GELU)(+residual) on MFMA
  * (timm Attention.qkv/proj, Mlp.fc1/fc2, head; README.md:21-35).
  * A (M,K) bf16 row stride lda; W (N,K) bf16; bias (N) f32.
@@ -674,6 +693,13 @@ int yv_blob_nhwc8(const void* images_u8, long long pixels, void* out_bf16, void*
 size_t yv_bn_ws_floats(long long T, int C);
 int yv_bn_stats(const void* z, long long ldz, long long T, int C, float eps, float momentum, float* mean, float* rstd,
                 float* run_mean, float* run_var, float* ws, size_t ws_floats, void* stream);
+
+/* Second half of yv_bn_stats for tile partials written by yv_conv2d_stats (stats_ws as that call left it, T = B*Hout*Wout rows,
+ * C = Cout): more than 2048 tiles are first folded, groups of ceil(tiles / 2048) consecutive tiles in ascending order in
+ * double, into chunk partials behind the tile partials; then yv_bn_stats' finaliser (same double-precision formulas, same
+ * running-estimate rule: both of run_mean / run_var or neither). */
+int yv_bn_stats_finish(float* stats_ws, long long T, int C, float eps, float momentum, float* mean, float* rstd,
+                       float* run_mean, float* run_var, void* stream);
 
 /* a = act(gamma*(z-mean)*rstd + beta) [+ res]   (act 1 = SiLU, 0 = identity); a, res bf16 views. */
 int yv_bn_act_fwd(const void* z, long long ldz, long long T, int C, const float* mean, const float* rstd,

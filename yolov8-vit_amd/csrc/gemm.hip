@@ -56,9 +56,11 @@ __device__ __forceinline__ float silu_f(float x) { return x * __builtin_amdgcn_r
 // 256 bytes of zeros: where a staged chunk is padding (outside the image, past K, past the last row) the conv / linear gather
 // reads THIS instead of branching around the load or masking the data afterwards
 __device__ __attribute__((aligned(256))) uint32_t g_zero_page[64];
-template <int MF, int NF>
+// STATS (yv_conv2d_stats): cs / cq (NF * 4 floats each, zeroed by the caller) receive this lane's column sums of the bf16-rounded
+// values it stores and of their squares, rows in ascending fragment order; rows >= M and columns >= N add nothing.
+template <int MF, int NF, bool STATS = false>
 __device__ __forceinline__ void epilogue(const GemmArgs& g, f32x4 (&acc)[NF][MF], int M, int m0, int n0, int wrow_m,
-                                         int wrow_n, int fr, int fq) {
+                                         int wrow_n, int fr, int fq, float* cs = nullptr, float* cq = nullptr) {
     // ---- epilogue: lane owns channels n..n+3 of row m --------------------------------------
     const int flags = g.flags;
 #pragma unroll
@@ -108,6 +110,14 @@ __device__ __forceinline__ void epilogue(const GemmArgs& g, f32x4 (&acc)[NF][MF]
             } else {
                 uint16_t* o = (uint16_t*)g.out + orow * g.ldo + n;
                 *(uint2*)o = make_uint2(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]));
+                if constexpr (STATS) {
+                    const uint32_t pk[2] = {pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])};
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        const float f = bf16_to_f32((uint16_t)(q & 1 ? pk[q >> 1] >> 16 : pk[q >> 1] & 0xffff));
+                        cs[i * 4 + q] += f; cq[i * 4 + q] += f * f;
+                    }
+                }
             }
         }
     }
@@ -119,9 +129,12 @@ __device__ __forceinline__ void epilogue(const GemmArgs& g, f32x4 (&acc)[NF][MF]
 // output left at ~2 TB/s.  Here each wave transposes its tile through a private, XOR-swizzled LDS
 // slab (reusing the main-loop buffers after the loop's last barrier) and writes whole 128-byte
 // (bf16) / 256-byte (f32) row segments with 16-byte stores; residual reads are coalesced the same way.
-template <int MF>
+// STATS (yv_conv2d_stats, bf16 output): cs / cq (8 floats each, zeroed by the caller) receive the column sums of the 8 channels
+// this lane stores (n = n0 + wrow_n + (lane & 7) * 8 ..) and of their squares, its rows (lane >> 3) + 8 * it in ascending order.
+template <int MF, bool STATS = false>
 __device__ __forceinline__ void epilogue_staged(const GemmArgs& g, f32x4 (&acc)[4][MF], int M, int m0, int n0,
-                                                int wrow_m, int wrow_n, int lane, unsigned char* stage) {
+                                                int wrow_m, int wrow_n, int lane, unsigned char* stage, float* cs = nullptr,
+                                                float* cq = nullptr) {
     const int flags = g.flags;
     const int fr = lane & 15, fq = lane >> 4;
     const int nb = n0 + wrow_n;
@@ -234,6 +247,14 @@ __device__ __forceinline__ void epilogue_staged(const GemmArgs& g, f32x4 (&acc)[
                     pk = make_uint4(o[0], o[1], o[2], o[3]);
                 }
                 *(uint4*)((uint16_t*)g.out + (long long)m * g.ldo + n) = pk;
+                if constexpr (STATS) {
+                    const uint32_t a[4] = {pk.x, pk.y, pk.z, pk.w};
+#pragma unroll
+                    for (int q = 0; q < 8; ++q) {
+                        const float f = bf16_to_f32((uint16_t)(q & 1 ? a[q >> 1] >> 16 : a[q >> 1] & 0xffff));
+                        cs[q] += f; cq[q] += f * f;
+                    }
+                }
             }
         }
     } else {
@@ -274,9 +295,66 @@ __device__ __forceinline__ void epilogue_staged(const GemmArgs& g, f32x4 (&acc)[
     }
 }
 
-template <int MF, int NF>
+// STATS (yv_conv2d_stats; WM row-group waves, BN tile columns, tm the tile's row index): the workgroup also writes the column sums
+// of what it stored to g.stats[(tm * 2 + which) * N + n] (which 0: sum, 1: sum of squares), each float by one plain store.
+// Summation order: a lane's rows in ascending order (the epilogues), then the lanes that hold the same columns by an xor
+// butterfly (both partners compute the same sum), then the WM waves in wave order through LDS.  The scratch (WM x 2 x BN floats)
+// lies at the start of the tile buffers, i.e. inside the staged epilogue's slabs: a barrier that every wave reaches (its rows
+// may all lie past M - it then adds zeros) separates the two uses.  g.staged is the same for the whole launch.
+template <int MF, int NF, bool STATS = false, int WM = 1, int BN = 16>
 __device__ __forceinline__ void finish_tile(const GemmArgs& g, f32x4 (&acc)[NF][MF], int M, int m0, int n0, int wrow_m,
-                                            int wrow_n, int lane, int wave, unsigned char* smem) {
+                                            int wrow_n, int lane, int wave, unsigned char* smem, int tm = 0) {
+    if constexpr (STATS) {
+        float* const sc = (float*)smem + (wrow_m / (MF * 16)) * 2 * BN + wrow_n;      // this wave's [which][column] rows
+        bool staged = false;
+        if constexpr (NF == 4 && (MF % 2) == 0) staged = g.staged;
+        if constexpr (NF == 4 && (MF % 2) == 0) {
+            if (staged) {
+                float cs[8], cq[8];
+#pragma unroll
+                for (int q = 0; q < 8; ++q) cs[q] = cq[q] = 0.f;
+                epilogue_staged<MF, true>(g, acc, M, m0, n0, wrow_m, wrow_n, lane, smem + wave * (MF * 16 * 128), cs, cq);
+#pragma unroll
+                for (int q = 0; q < 8; ++q)
+#pragma unroll
+                    for (int d = 8; d < 64; d <<= 1) { cs[q] += __shfl_xor(cs[q], d, 64); cq[q] += __shfl_xor(cq[q], d, 64); }
+                __syncthreads();                              // every wave is done with its slab
+                if (lane < 8) {
+#pragma unroll
+                    for (int q = 0; q < 8; ++q) { sc[lane * 8 + q] = cs[q]; sc[BN + lane * 8 + q] = cq[q]; }
+                }
+            }
+        }
+        if (!staged) {
+            // one 16-column fragment at a time (8 sums live); the direct epilogue leaves the tile buffers idle: no barrier before
+#pragma unroll
+            for (int i = 0; i < NF; ++i) {
+                float cs[4] = {0.f, 0.f, 0.f, 0.f}, cq[4] = {0.f, 0.f, 0.f, 0.f};
+                epilogue<MF, 1, true>(g, reinterpret_cast<f32x4 (&)[1][MF]>(acc[i]), M, m0, n0, wrow_m, wrow_n + i * 16, lane & 15,
+                                      lane >> 4, cs, cq);
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+#pragma unroll
+                    for (int d = 1; d < 16; d <<= 1) { cs[q] += __shfl_xor(cs[q], d, 64); cq[q] += __shfl_xor(cq[q], d, 64); }
+                if ((lane & 15) == 0) {
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        sc[i * 16 + (lane >> 4) * 4 + q] = cs[q];
+                        sc[BN + i * 16 + (lane >> 4) * 4 + q] = cq[q];
+                    }
+                }
+            }
+        }
+        __syncthreads();
+        for (int idx = threadIdx.x; idx < 2 * BN; idx += THREADS) {
+            const int which = idx / BN, col = idx - which * BN;
+            float t = 0.f;
+#pragma unroll
+            for (int w = 0; w < WM; ++w) t += ((const float*)smem)[(w * 2 + which) * BN + col];
+            if (n0 + col < g.N) g.stats[((long long)tm * 2 + which) * g.N + n0 + col] = t;
+        }
+        return;
+    }
     if constexpr (NF == 4 && (MF % 2) == 0) {
         if (g.staged) {          // wave-private slab of MF*16 rows x 128 B inside the (now idle) tile buffers
             epilogue_staged<MF>(g, acc, M, m0, n0, wrow_m, wrow_n, lane, smem + wave * (MF * 16 * 128));
@@ -286,7 +364,8 @@ __device__ __forceinline__ void finish_tile(const GemmArgs& g, f32x4 (&acc)[NF][
     epilogue<MF, NF>(g, acc, M, m0, n0, wrow_m, wrow_n, lane & 15, lane >> 4);
 }
 
-template <int MODE /*0 linear, 1 conv*/, int BM, int BN, int WM, int WN, bool TWO = false /*conv with two concatenated sources*/>
+template <int MODE /*0 linear, 1 conv*/, int BM, int BN, int WM, int WN, bool TWO = false /*conv with two concatenated sources*/,
+          bool STATS = false /*conv that also writes its tile's column sums (finish_tile)*/>
 __global__ __launch_bounds__(THREADS) void igemm_kernel(GemmArgs g) {
     constexpr int MF = BM / WM / 16;               // activation fragments per wave
     constexpr int NF = BN / WN / 16;               // weight fragments per wave
@@ -520,7 +599,7 @@ __global__ __launch_bounds__(THREADS) void igemm_kernel(GemmArgs g) {
         }
         return;
     }
-    finish_tile<MF, NF>(g, acc, M, m0, n0, wrow_m, wrow_n, lane, wave, smem);
+    finish_tile<MF, NF, STATS, WM, BN>(g, acc, M, m0, n0, wrow_m, wrow_n, lane, wave, smem, tm);
 }
 
 // second stage of a split-K conv: sum the K slices, then the usual epilogue (bias, SiLU, bf16 shortcut, store)
@@ -766,7 +845,7 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_dma_kernel(GemmArgs g) {
 // VALU issue of exactly that gather and staging.  Epilogues: finish_tile (bias, SiLU, bf16 shortcut, f32 output).
 // Eligibility (host): (c0 + c1) % 64 == 0, c1 == 0 or (1 x 1 and c0 % 64 == 0), Cout >= 64, staged epilogue usable.
 // ---------------------------------------------------------------------------------------------
-template <int BN, int WM, int WN, int ST = 2 /* LDS stages: ST - 1 K steps of DMA in flight */>
+template <int BN, int WM, int WN, int ST = 2 /* LDS stages: ST - 1 K steps of DMA in flight */, bool STATS = false /* as igemm_kernel */>
 __global__ __launch_bounds__(256) void cgemm_dma_kernel(GemmArgs g) {
     constexpr int BM = 128, NW = 4;
     static_assert(WM * WN == NW, "four waves");
@@ -913,7 +992,7 @@ __global__ __launch_bounds__(256) void cgemm_dma_kernel(GemmArgs g) {
         }
     }
     asm volatile("s_barrier" ::: "memory");                       // the staged epilogue reuses the tile buffers
-    finish_tile<MF, NF>(g, acc, M, m0, n0, wrow_m, wrow_n, lane, wave, smem);
+    finish_tile<MF, NF, STATS, WM, BN>(g, acc, M, m0, n0, wrow_m, wrow_n, lane, wave, smem, tm);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2059,6 +2138,7 @@ int launch(GemmArgs& g, hipStream_t st) {
     if (lds < (size_t)THREADS / 64 * (BM / WM) * 128) lds = (size_t)THREADS / 64 * (BM / WM) * 128;   // the staged epilogue's slabs
     void (*kern)(GemmArgs) = igemm_kernel<MODE, BM, BN, WM, WN, false>;
     if constexpr (MODE == 1) { if (g.c1 > 0) kern = igemm_kernel<MODE, BM, BN, WM, WN, true>; }
+    if constexpr (MODE == 1 && BM == 128) { if (g.stats) kern = igemm_kernel<MODE, BM, BN, WM, WN, false, true>; }
     if (!yv_grant_lds((const void*)kern, lds)) return YV_ERR_LAUNCH;
     const int S = g.splitk > 1 ? g.splitk : 1;
     hipLaunchKernelGGL(kern, dim3(g.tiles_m * g.tiles_n * S), dim3(THREADS), lds, st, g);
@@ -2083,7 +2163,8 @@ int launch_cdma(GemmArgs& g, hipStream_t st) {
     g.tiles_m = (g.M + 127) / 128;
     g.tiles_n = (g.N + BN - 1) / BN;
     const size_t lds = ST * (size_t)(128 + BN) * 128;
-    auto kern = cgemm_dma_kernel<BN, WM, WN, ST>;
+    void (*kern)(GemmArgs) = cgemm_dma_kernel<BN, WM, WN, ST>;
+    if (g.stats) kern = cgemm_dma_kernel<BN, WM, WN, ST, true>;
     if (!yv_grant_lds((const void*)kern, lds)) return YV_ERR_LAUNCH;
     hipLaunchKernelGGL(kern, dim3(g.tiles_m * g.tiles_n), dim3(256), lds, st, g);
     return yv_launch_status();
@@ -2693,7 +2774,8 @@ extern "C" int yv_linear_route(int M, int N, int K, int lda, int ldo, int flags,
 
 static int conv_impl_one(const yv_view* in0, const yv_view* in1, int B, int Hout, int Wout, int ksize, int stride,
                          const void* weight, const float* bias, int Cout, void* out, int out_ld, const void* res,
-                         int res_ld, int flags, void* ws, size_t ws_bytes, void* stream, bool query = false) {
+                         int res_ld, int flags, void* ws, size_t ws_bytes, void* stream, bool query = false,
+                         float* stats = nullptr /* yv_conv2d_stats: the tile partials; never split-K */) {
     if (!in0 || !in0->ptr || !weight || !out || B <= 0 || Hout <= 0 || Wout <= 0 || Cout <= 0) return YV_ERR_ARG;
     if (!(ksize == 1 || ksize == 3) || !(stride == 1 || stride == 2)) return YV_ERR_ARG;
     if (in1 && in1->ptr && ksize != 1) return YV_ERR_ARG;
@@ -2723,9 +2805,10 @@ static int conv_impl_one(const yv_view* in0, const yv_view* in1, int B, int Hout
     g.w = (const uint16_t*)weight; g.bias = bias;
     g.M = B * Hout * Wout; g.N = Cout; g.K = ksize * ksize * Cin;
     g.out = out; g.ldo = out_ld; g.res = (const uint16_t*)res; g.ldres = res_ld; g.flags = flags;
-    const int kern = conv_route(g, ws != nullptr, ws_bytes);
+    const int kern = conv_route(g, ws != nullptr && !stats, ws_bytes);
     if (query) return conv_instance_code(g, kern);                // yv_conv2d_instance: the route, no launch
     if (g.splitk > 1) g.partial = (float*)ws;
+    g.stats = stats;
     return launch_conv(g, kern, (hipStream_t)stream);
 }
 
@@ -2879,6 +2962,24 @@ extern "C" int yv_conv2d_ws(const yv_view* in0, const yv_view* in1, int B, int H
                             int res_ld, int flags, void* ws, size_t ws_bytes, void* stream) {
     return conv_impl(in0, in1, B, Hout, Wout, ksize, stride, weight, bias, Cout, out, out_ld, res, res_ld, flags, ws, ws_bytes,
                      stream);
+}
+
+extern "C" int yv_conv2d_stats(const yv_view* in0, int B, int Hout, int Wout, int ksize, int stride, const void* weight,
+                               const float* bias, int Cout, void* out, int out_ld, int flags, float* stats_ws, size_t stats_ws_floats,
+                               void* ws, size_t ws_bytes, void* stream) {
+    if (!stats_ws || (flags & ~YV_EPI_BIAS) || Cout <= 0 || (Cout & 7)) return YV_ERR_ARG;
+    // the argument checks of yv_conv2d_ws, by its route query: nothing is launched
+    const int code = conv_impl_one(in0, nullptr, B, Hout, Wout, ksize, stride, weight, bias, Cout, out, out_ld, nullptr, 0, flags, ws,
+                                   ws_bytes, stream, true, stats_ws);
+    if (code < 0) return code;
+    {   // one launch, one tile sequence: not what yv_conv2d_ws takes in sub-batches
+        const long long Hin = (long long)Hout * stride, Win = (long long)Wout * stride;
+        const long long s0 = (Hin >> in0->up) * (Win >> in0->up) * in0->ld * 2;
+        if (conv_sub_batch(s0, 0, (Win + 1) * in0->ld * 2) < B) return YV_ERR_LIMIT;
+    }
+    if (stats_ws_floats < yv_conv_stats_ws_floats((long long)B * Hout * Wout, Cout)) return YV_ERR_WORKSPACE;
+    return conv_impl_one(in0, nullptr, B, Hout, Wout, ksize, stride, weight, bias, Cout, out, out_ld, nullptr, 0, flags, ws, ws_bytes,
+                         stream, false, stats_ws);
 }
 
 extern "C" int yv_conv2d_instance(int B, int Hout, int Wout, int ksize, int stride, int c0, int c1, int Cout, int out_ld,

@@ -56,6 +56,7 @@ struct GemmArgs {
     const uint8_t* mx_sa;
     const uint8_t* mx_sw;
     long long mx_rows_a, mx_rows_w;
+    float* stats;                // STATS convolutions (yv_conv2d_stats): per-tile column sums (tiles_m, 2, N), see finish_tile
 };
 
 // tuning options read in both units (defined and described in gemm_persistent.hip) and the persistent launchers

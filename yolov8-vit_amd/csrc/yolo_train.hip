@@ -163,6 +163,18 @@ __global__ __launch_bounds__(256) void bn_stats_final_kernel(const float* __rest
     }
 }
 
+// yv_bn_stats_finish, more than 2048 tile partials (tiles, 2, C): chunk k = the sum of tiles [k * group, (k + 1) * group) in
+// ascending order, in double; written behind the tile partials as (chunks, 2, C).  One thread per (chunk, which, channel).
+__global__ __launch_bounds__(256) void bn_stats_fold_kernel(float* __restrict__ partial, int tiles, int group, int chunks, int C) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)chunks * 2 * C) return;
+    const int k = (int)(i / (2 * C)), wc = (int)(i - (long long)k * 2 * C);        // wc = which * C + channel
+    const int t0 = k * group, t1 = t0 + group < tiles ? t0 + group : tiles;
+    double a = 0.0;
+    for (int t = t0; t < t1; ++t) a += partial[(long long)t * 2 * C + wc];
+    partial[(long long)tiles * 2 * C + i] = (float)a;
+}
+
 __global__ __launch_bounds__(256) void bn_bwd_final_kernel(const float* __restrict__ partial, int chunks, int C, long long T,
                                                            int batch_stats, float* __restrict__ dgamma, float* __restrict__ dbeta,
                                                            float* __restrict__ coef /* (2, C): mean(g), mean(g*xhat) */) {
@@ -442,6 +454,40 @@ extern "C" int yv_bn_stats(const void* z, long long ldz, long long T, int C, flo
     const int rp = 256 / (C >> 3);
     hipLaunchKernelGGL(chan_reduce_kernel<0>, dim3(chunks), dim3(256), (size_t)rp * 2 * C * sizeof(float), (hipStream_t)stream, a);
     hipLaunchKernelGGL(bn_stats_final_kernel, dim3((C + 7) / 8), dim3(256), 0, (hipStream_t)stream, ws, chunks, C, T, eps,
+                       mean, rstd, run_mean, run_var, momentum);
+    return yv_launch_status();
+}
+
+// chunks the finaliser walks for `tiles` tile partials (at most 2048, as yv_bn_stats), *group tiles each
+static int stats_chunks(long long tiles, int* group) {
+    *group = (int)((tiles + 2047) / 2048);
+    return (int)((tiles + *group - 1) / *group);
+}
+
+extern "C" size_t yv_conv_stats_ws_floats(long long T, int Cout) {
+    if (T <= 0 || Cout <= 0) return 0;
+    const long long tiles = (T + 127) / 128;
+    int group;
+    const int chunks = stats_chunks(tiles, &group);
+    return (size_t)tiles * 2 * Cout + (tiles > 2048 ? (size_t)chunks * 2 * Cout : 0);
+}
+
+extern "C" int yv_bn_stats_finish(float* stats_ws, long long T, int C, float eps, float momentum, float* mean, float* rstd,
+                                  float* run_mean, float* run_var, void* stream) {
+    if (!stats_ws || !mean || !rstd || !bn_shape_ok(T, C, C) || T > 0x7fffffffLL) return YV_ERR_ARG;
+    if ((run_mean == nullptr) != (run_var == nullptr)) return YV_ERR_ARG;
+    const int tiles = (int)((T + 127) / 128);
+    int group;
+    int chunks = stats_chunks(tiles, &group);
+    const float* partial = stats_ws;
+    if (tiles > 2048) {
+        hipLaunchKernelGGL(bn_stats_fold_kernel, dim3(blocks_for((long long)chunks * 2 * C)), dim3(256), 0, (hipStream_t)stream,
+                           stats_ws, tiles, group, chunks, C);
+        partial = stats_ws + (size_t)tiles * 2 * C;
+    } else {
+        chunks = tiles;
+    }
+    hipLaunchKernelGGL(bn_stats_final_kernel, dim3((C + 7) / 8), dim3(256), 0, (hipStream_t)stream, partial, chunks, C, T, eps,
                        mean, rstd, run_mean, run_var, momentum);
     return yv_launch_status();
 }

@@ -107,6 +107,9 @@ _SIGS = {
     "yv_blob_nhwc8": (_i, [_vp, C.c_longlong, _vp, _vp]),
     "yv_bn_ws_floats": (_sz, [C.c_longlong, _i]),
     "yv_bn_stats": (_i, [_vp, C.c_longlong, C.c_longlong, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "yv_bn_stats_finish": (_i, [_vp, C.c_longlong, _i, _f, _f, _vp, _vp, _vp, _vp, _vp]),
+    "yv_conv_stats_ws_floats": (_sz, [C.c_longlong, _i]),
+    "yv_conv2d_stats": (_i, [C.POINTER(yv_view), _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _i, _i, _vp, _sz, _vp, _sz, _vp]),
     "yv_bn_act_fwd": (_i, [_vp, C.c_longlong, C.c_longlong, _i, _vp, _vp, _vp, _vp, _vp, C.c_longlong, _vp, C.c_longlong,
                            _i, _vp]),
     "yv_bn_act_bwd": (_i, [_vp, C.c_longlong, _vp, C.c_longlong, C.c_longlong, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp,
@@ -949,6 +952,17 @@ def bn_stats(z: "yv_view", T: int, mean, rstd, run_mean, run_var, ws, eps: float
                           ws.numel(), _st()), "yv_bn_stats")
 
 
+def conv_stats_ws_floats(T: int, Cout: int) -> int:
+    """Floats of conv_view_stats' `stats_ws` for T output rows (tile partials + what bn_stats_finish folds them into)."""
+    return int(lib.yv_conv_stats_ws_floats(T, Cout))
+
+
+def bn_stats_finish(stats_ws, T: int, mean, rstd, run_mean, run_var, eps: float = 1e-3, momentum: float = 0.03):
+    """bn_stats' second half on the tile partials conv_view_stats left in `stats_ws` (C = mean.numel())."""
+    check(lib.yv_bn_stats_finish(_p(stats_ws), T, mean.numel(), eps, momentum, _p(mean), _p(rstd), _p(run_mean), _p(run_var),
+                                 _st()), "yv_bn_stats_finish")
+
+
 def bn_act_fwd(z: "yv_view", T: int, mean, rstd, gamma, beta, out: "yv_view", res: Optional["yv_view"] = None, act: int = 1):
     check(lib.yv_bn_act_fwd(z.ptr, z.ld, T, z.c, _p(mean), _p(rstd), _p(gamma), _p(beta), res.ptr if res else None,
                             res.ld if res else 0, out.ptr, out.ld, act, _st()), "yv_bn_act_fwd")
@@ -1004,6 +1018,17 @@ def conv_view(in0: "yv_view", B: int, Hout: int, Wout: int, ksize: int, stride: 
     check(lib.yv_conv2d_ws(C.byref(in0), None, B, Hout, Wout, ksize, stride, _p(weight), _p(bias), Cout, out.ptr, out.ld,
                            res.ptr if res is not None else None, res.ld if res is not None else 0, flags, _p(ws),
                            ws.numel() * 4, _st()), "yv_conv2d_ws")
+
+
+def conv_view_stats(in0: "yv_view", B: int, Hout: int, Wout: int, ksize: int, stride: int, weight: torch.Tensor, Cout: int,
+                    out: "yv_view", stats_ws: torch.Tensor, bias: Optional[torch.Tensor] = None, flags: int = 0):
+    """conv_view (bf16 out, optional bias, nothing else) that also leaves the per-tile column sums of what it stored in
+    `stats_ws` (f32, >= conv_stats_ws_floats(B*Hout*Wout, Cout) floats) for bn_stats_finish: yv_conv2d_stats."""
+    if bias is not None:
+        flags |= EPI_BIAS
+    ws = _conv_workspace(weight.device)
+    check(lib.yv_conv2d_stats(C.byref(in0), B, Hout, Wout, ksize, stride, _p(weight), _p(bias), Cout, out.ptr, out.ld, flags,
+                              _p(stats_ws), stats_ws.numel(), _p(ws), ws.numel() * 4, _st()), "yv_conv2d_stats")
 
 
 def mview(t: torch.Tensor, c_off: int = 0, c: Optional[int] = None) -> "yv_view":

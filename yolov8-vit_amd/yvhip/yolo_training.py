@@ -21,7 +21,8 @@ import math
 
 from . import (OPT_ADAMW, OPT_SGD_NESTEROV, VIEW_ADD, VIEW_COPY, VIEW_PAD, VIEW_UP2, VIEW_UP2_BWD, VIEW_ZERO_INSERT, YvError, axpby,
                blob_nhwc8, bn_act_bwd, bn_act_fwd, ema_update, optim_step,
-               bn_stats, bn_ws_floats, cast_colsum, colsum_ws_floats, conv_view, conv_weight_dgrad, detect_loss,
+               bn_stats, bn_stats_finish, bn_ws_floats, cast_colsum, colsum_ws_floats, conv_stats_ws_floats, conv_view,
+               conv_view_stats, conv_weight_dgrad, detect_loss,
                detect_loss_ws_bytes, im2col3, maxpool5_bwd, mview, require_gpu, sgd_step, sppf_pool, view_op, wgrad, wgrad_conv3)
 from .engines import LAYER_STRIDE, REG_MAX, _env_flag, detect_widths, yolo_conv_keys, yolo_layers
 
@@ -111,7 +112,8 @@ class YoloTrainer:
     def __init__(self, state: Dict[str, torch.Tensor], scale: str = "n", nc: int = 5, size: int = 640, batch: int = 16,
                  lr: float = 1e-4, momentum: float = 0.937, weight_decay: float = 5e-4, device: str = "cuda:0",
                  optimizer: str = "sgd", ema: bool = False, ema_decay: float = 0.9999, ema_tau: float = 2000.0,
-                 overlap_wgrad: bool = True, implicit_wgrad: bool = True, narrow_wgrad: Optional[bool] = None):
+                 overlap_wgrad: bool = True, implicit_wgrad: bool = True, narrow_wgrad: Optional[bool] = None,
+                 fused_bn_stats: Optional[bool] = None):
         require_gpu()
         if size % 32:
             raise YvError("input size must be a multiple of 32")
@@ -122,6 +124,9 @@ class YoloTrainer:
         # opt-in: weight gradients on the N tile wgrad_route picks (32 / 64 x 256 for few output channels); off = yv_wgrad's 128 x 128
         self.narrow_wgrad = _env_flag(narrow_wgrad, "YV_YOLO_NARROW_WGRAD")
         self._wgrad_tile = 0 if self.narrow_wgrad else None
+        # opt-in: the forward's BatchNorm batch statistics from the convolution's epilogue (yv_conv2d_stats + yv_bn_stats_finish)
+        # in place of a pass over z (yv_bn_stats); DESIGN.md section 22
+        self.fused_bn_stats = _env_flag(fused_bn_stats, "YV_YOLO_FUSED_BN_STATS")
         if optimizer not in ("sgd", "sgd_nesterov", "adamw"):
             raise YvError("optimizer must be 'sgd', 'sgd_nesterov' or 'adamw'")
         self.optimizer, self.use_ema, self.ema_decay, self.ema_tau = optimizer, ema, ema_decay, ema_tau
@@ -333,6 +338,8 @@ class YoloTrainer:
                 self.mean[b.key] = torch.zeros(b.cout, device=dev)
                 self.rstd[b.key] = torch.zeros(b.cout, device=dev)
                 ws_f = max(ws_f, bn_ws_floats(T, b.cout))
+                if self.fused_bn_stats:
+                    ws_f = max(ws_f, conv_stats_ws_floats(T, b.cout))
             else:
                 ws_f = max(ws_f, colsum_ws_floats(T, b.cout))
             self.dz[b.key] = torch.zeros((_r64(T), b.cout), dtype=torch.bfloat16, device=dev)
@@ -380,8 +387,13 @@ class YoloTrainer:
         hin, hout = self.geom[b.key]
         T = self.B * hout * hout
         z = mview(self.z[b.key])
-        conv_view(x, self.B, hout, hout, b.k, b.s, self.w16(b), b.cout, z)
-        bn_stats(z, T, self.mean[b.key], self.rstd[b.key], self.run_mean[b.key], self.run_var[b.key], self.ws, BN_EPS, BN_MOMENTUM)
+        if self.fused_bn_stats:
+            conv_view_stats(x, self.B, hout, hout, b.k, b.s, self.w16(b), b.cout, z, self.ws)
+            bn_stats_finish(self.ws, T, self.mean[b.key], self.rstd[b.key], self.run_mean[b.key], self.run_var[b.key], BN_EPS,
+                            BN_MOMENTUM)
+        else:
+            conv_view(x, self.B, hout, hout, b.k, b.s, self.w16(b), b.cout, z)
+            bn_stats(z, T, self.mean[b.key], self.rstd[b.key], self.run_mean[b.key], self.run_var[b.key], self.ws, BN_EPS, BN_MOMENTUM)
         bn_act_fwd(z, T, self.mean[b.key], self.rstd[b.key], self.p(b.gamma), self.p(b.beta), out, res=res)
 
     def _bwd(self, b: _Block, da, x_buf: torch.Tensor, x_off: int, dx=None):
