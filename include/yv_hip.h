@@ -543,6 +543,21 @@ int yv_attention_bwd(const void* qkv, const void* out, const void* dout, const f
 int yv_attention_bwd_long(const void* qkv, const void* out, const void* dout, const float* lse, int R, int N, int H,
                           float scale, void* dqkv, float* delta_ws, void* stream);
 
+/* Attention backward for sequences of up to 224 tokens (197) in ONE launch; the same arithmetic as yv_attention_bwd with its two
+ * kernels as two phases of one workgroup per (crop, head): Q, K, V and dO are fetched once into LDS images of ceil(N / 32) * 32
+ * rows (the swizzled row-major layout of yv_attention_bwd_long, read row-wise and with transposing LDS reads), phase 1 owns the
+ * queries (dQ, delta), phase 2 the keys (dK, dV) and takes lse / delta from LDS; the fetch of Q and dO lands under phase 1.
+ * VitTrainer(short_attn_bwd=True) uses it for N <= 224.
+ * Operands as yv_attention_bwd: qkv, dqkv (R*N, 3*H*64) bf16; out, dout (R*N, H*64) bf16; lse (R, H, N) f32, log2 domain, from
+ * yv_attention_train or yv_attention_long; delta_ws: R*H*N floats, written as yv_attention_bwd writes them.  dqkv and delta_ws
+ * are bit-identical to yv_attention_bwd on finite inputs, for every 1 <= N <= 224; rows of dqkv past R*N and floats of delta_ws
+ * past R*H*N are never written.
+ * qkv, out, dout, dqkv 16-byte aligned; a NULL pointer (but stream), R < 0, N <= 0, H <= 0 or a misaligned pointer is
+ * YV_ERR_ARG, N > 224 or a grid past 2^31 - 1 workgroups YV_ERR_LIMIT; R = 0 is YV_OK without a launch.  Addresses are 64-bit:
+ * no 2 GB limit.  A crop's gradients depend on that crop's inputs only: bit-identical whatever R, the crop's index and the grid. */
+int yv_attention_bwd_short(const void* qkv, const void* out, const void* dout, const float* lse, int R, int N, int H,
+                           float scale, void* dqkv, float* delta_ws, void* stream);
+
 /* yv_attention_cls for the trainer (VitTrainer(cls_tail=True)): attention of the cls query of each crop, with the log2-sum-exp
  * its backward needs.  One workgroup per (crop, head), a streaming pass over K and V, every reduction in a fixed order.
  * q: bf16, row r at q + r*ldq elements, H*64 wide (ldq = N*3*H*64 reads the cls rows of the qkv buffer itself, ldq = H*64 a

@@ -221,17 +221,22 @@ def _trainer_for(net, optimizer):
     with fresh momentum.  The same holds for the module's `_yv_train_cls_tail` (CFG.train_cls_tail: the last block trained on the
     cls rows, VitTrainer(cls_tail=True)); when it is not set the trainer is built without the argument and follows
     YV_VIT_TRAIN_CLS_TAIL.  Likewise `_yv_train_wide_wgrad` (CFG.train_wide_wgrad: 256 x 128 weight-gradient tiles,
-    VitTrainer(wide_wgrad=True)) and YV_VIT_WIDE_WGRAD."""
+    VitTrainer(wide_wgrad=True)) and YV_VIT_WIDE_WGRAD, and `_yv_train_short_attn_bwd` (CFG.train_short_attn_bwd: the one-launch
+    attention backward, VitTrainer(short_attn_bwd=True)) and YV_VIT_SHORT_ATTN_BWD."""
     from yvhip.training import VitTrainer
     tr = getattr(net, "_yv_trainer", None)
     dtype = getattr(net, "_yv_train_dtype", "bf16")
     cls_tail = bool(getattr(net, "_yv_train_cls_tail", False))
     wide_wgrad = bool(getattr(net, "_yv_train_wide_wgrad", False))
+    short_attn_bwd = bool(getattr(net, "_yv_train_short_attn_bwd", False))
     if tr is not None and getattr(tr, "dtype", "bf16") != dtype:
         tr = None
     if tr is not None and getattr(tr, "cls_tail", False) != (cls_tail or os.environ.get("YV_VIT_TRAIN_CLS_TAIL", "0") == "1"):
         tr = None
     if tr is not None and getattr(tr, "wide_wgrad", False) != (wide_wgrad or os.environ.get("YV_VIT_WIDE_WGRAD", "0") == "1"):
+        tr = None
+    if tr is not None and getattr(tr, "short_attn_bwd", False) != (
+            short_attn_bwd or os.environ.get("YV_VIT_SHORT_ATTN_BWD", "0") == "1"):
         tr = None
     if tr is None:
         mom, wd = 0.9, 1e-3                                   # utils/trainClass.py:442-443
@@ -244,7 +249,8 @@ def _trainer_for(net, optimizer):
         sd = {k: v.detach() for k, v in net.state_dict().items()}
         tr = VitTrainer(sd, net.model.arch, net.num_class, net.model.img, device=str(dev), momentum=mom, weight_decay=wd,
                         **({} if dtype == "bf16" else {"dtype": dtype}), **({"cls_tail": True} if cls_tail else {}),
-                        **({"wide_wgrad": True} if wide_wgrad else {}))
+                        **({"wide_wgrad": True} if wide_wgrad else {}),
+                        **({"short_attn_bwd": True} if short_attn_bwd else {}))
         net._yv_trainer = tr
     return tr
 
@@ -468,13 +474,15 @@ def fit(net, train_loader, valid_loader, CFG, log=False, save_path=None):
     ("bf16" when absent, or "mxfp8": MXFP8 block linears, yvhip.training.VitTrainer) selects the fine-tune recipe; an optional
     CFG.train_cls_tail (absent or False: as before) trains the last block on the cls rows (VitTrainer(cls_tail=True)); an optional
     CFG.train_wide_wgrad (absent or False: as before) launches the bf16 weight gradients on 256 x 128 tiles
-    (VitTrainer(wide_wgrad=True))."""
+    (VitTrainer(wide_wgrad=True)); an optional CFG.train_short_attn_bwd (absent or False: as before) runs the attention backward
+    of a model of up to 224 tokens in one launch (VitTrainer(short_attn_bwd=True))."""
     from yvhip.training import check_train_dtype
     dtype = getattr(CFG, "train_dtype", None) or "bf16"
     check_train_dtype(dtype, 128)                         # the width rule is checked when the trainer is built
     net._yv_train_dtype = dtype
     net._yv_train_cls_tail = bool(getattr(CFG, "train_cls_tail", False))
     net._yv_train_wide_wgrad = bool(getattr(CFG, "train_wide_wgrad", False))
+    net._yv_train_short_attn_bwd = bool(getattr(CFG, "train_short_attn_bwd", False))
     optimizer = torch.optim.SGD(net.parameters(), CFG.lr, momentum=0.9, weight_decay=1e-3)   # hyper-parameter carrier
     best, results = 0.0, {}
     for epoch_num in range(1, CFG.epoch + 1):

@@ -138,6 +138,7 @@ _SIGS = {
     "yv_attention_train": (_i, [_vp, _i, _i, _i, _f, _vp, _vp, _vp]),
     "yv_attention_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp]),
     "yv_attention_bwd_long": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp]),
+    "yv_attention_bwd_short": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp]),
     "yv_attention_cls_train": (_i, [_vp, C.c_longlong, _vp, _i, _i, _i, _f, _vp, _vp, _vp]),
     "yv_attention_cls_bwd": (_i, [_vp, C.c_longlong, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp]),
     "yv_linear_nn": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _i, _i, _vp, _i, _vp]),
@@ -809,6 +810,13 @@ def attention_bwd_long(qkv, out, dout, lse, R, N, H, dqkv, delta_ws, scale=None)
     on finite inputs, the same bits in dqkv and delta_ws."""
     check(lib.yv_attention_bwd_long(_p(qkv), _p(out), _p(dout), _p(lse), R, N, H, float(64 ** -0.5 if scale is None else scale),
                                     _p(dqkv), _p(delta_ws), _st()), "yv_attention_bwd_long")
+
+
+def attention_bwd_short(qkv, out, dout, lse, R, N, H, dqkv, delta_ws, scale=None):
+    """attention_bwd in one launch for sequences of up to 224 tokens (yv_attention_bwd_short; N > 224 is refused): the same
+    operands and, on finite inputs, the same bits in dqkv and delta_ws."""
+    check(lib.yv_attention_bwd_short(_p(qkv), _p(out), _p(dout), _p(lse), R, N, H, float(64 ** -0.5 if scale is None else scale),
+                                     _p(dqkv), _p(delta_ws), _st()), "yv_attention_bwd_short")
 
 
 def attention_cls_train(q, qkv, R, N, H, out, lse, scale=None):

@@ -36,7 +36,7 @@ from typing import Dict, List, Optional
 import torch
 
 from . import (EPI_GELU, EPI_GELU_BWD, EPI_OUT_F32, EPI_POSEMB, EPI_RES_F32, EPI_SAVE_PRE, YvError, attention_bwd,
-               attention_bwd_long, attention_cls_bwd, attention_cls_train, attention_long, attention_train, cast_colsum, cls_rows, colsum_bf16, head_bwd, layernorm,
+               attention_bwd_long, attention_bwd_short, attention_cls_bwd, attention_cls_train, attention_long, attention_train, cast_colsum, cls_rows, colsum_bf16, head_bwd, layernorm,
                layernorm_bwd, lib, linear, linear_ex, linear_mxfp8_ex, linear_nn, loss_fwd_bwd, quant_mxfp8_2d, r128, require_gpu, sgd_step,
                token_reduce, transpose_bf16_batched, wgrad, wgrad_mxfp8, wgrad_wide, wrapper_head)
 from .engines import _env_flag, vit_cfg
@@ -65,7 +65,8 @@ class VitTrainer:
     def __init__(self, state: Dict[str, torch.Tensor], name: str, num_classes: int = 5, img: int = 224,
                  device: str = "cuda:0", momentum: float = 0.9, weight_decay: float = 1e-3,
                  bucket_mb: float = 32.0, dtype: str = "bf16", long_attn: Optional[bool] = None,
-                 long_attn_bwd: Optional[bool] = None, cls_tail: Optional[bool] = None, wide_wgrad: Optional[bool] = None):
+                 long_attn_bwd: Optional[bool] = None, cls_tail: Optional[bool] = None, wide_wgrad: Optional[bool] = None,
+                 short_attn_bwd: Optional[bool] = None):
         """long_attn (opt-in, both dtypes): the forward attention runs as attention_long(..., lse=...) in place of attention_train
         where the token count exceeds 224 (a shorter-sequence trainer accepts the flag and keeps attention_train); attention_bwd
         is the same and consumes that lse.  None reads the environment variable YV_VIT_LONG_ATTN ("1" = on, unset = off).
@@ -87,11 +88,17 @@ class VitTrainer:
         wide_wgrad (opt-in, both dtypes, independent of the flags above): every bf16 weight gradient - the
         block linears, the compact cls-row form, the head and the patch embedding - is launched as wgrad_wide(..., routed=True) in
         place of wgrad on the same operands: 256 x 128 output tiles where wgrad_wide_route picks them, wgrad's own launch elsewhere.
-        The MX column-form launches are not touched.  None reads YV_VIT_WIDE_WGRAD ("1" = on, unset = off)."""
+        The MX column-form launches are not touched.  None reads YV_VIT_WIDE_WGRAD ("1" = on, unset = off).
+
+        short_attn_bwd (opt-in, both dtypes, independent of the flags above): the attention backward runs as
+        the one-launch attention_bwd_short in place of attention_bwd where the token count is at most 224 (a longer-sequence
+        trainer accepts the flag and is unaffected; with cls_tail the last block keeps attention_cls_bwd).  Same operands, same
+        bits in every gradient.  None reads YV_VIT_SHORT_ATTN_BWD ("1" = on, unset = off)."""
         self.long_attn = _env_flag(long_attn, "YV_VIT_LONG_ATTN")
         self.long_attn_bwd = _env_flag(long_attn_bwd, "YV_VIT_LONG_ATTN_BWD")
         self.cls_tail = _env_flag(cls_tail, "YV_VIT_TRAIN_CLS_TAIL")
         self.wide_wgrad = _env_flag(wide_wgrad, "YV_VIT_WIDE_WGRAD")
+        self.short_attn_bwd = _env_flag(short_attn_bwd, "YV_VIT_SHORT_ATTN_BWD")
         self.P_, self.D, self.L, self.H = vit_cfg(name)
         check_train_dtype(dtype, self.D)
         require_gpu()
@@ -346,8 +353,13 @@ class VitTrainer:
             attention_train(b["qkv"][i], R, self.N, self.H, b["o"][i], b["lse"][i])
 
     def _attention_bwd(self, *args):
-        """A block's attention backward (operands of attention_bwd): both kernels write the same bits."""
-        (attention_bwd_long if self.long_attn_bwd and self.N > 224 else attention_bwd)(*args)
+        """A block's attention backward (operands of attention_bwd): all three kernels write the same bits."""
+        if self.short_attn_bwd and self.N <= 224:
+            attention_bwd_short(*args)
+        elif self.long_attn_bwd and self.N > 224:
+            attention_bwd_long(*args)
+        else:
+            attention_bwd(*args)
 
     # ---- the full block (both recipes) ---------------------------------------------------------------------
     def _block_forward(self, b: dict, i: int, R: int):
