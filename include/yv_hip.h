@@ -743,8 +743,46 @@ int yv_maxpool5_bwd(const void* x, long long ldx, const void* dout, long long ld
 int yv_im2col3(const void* x, long long ldx, int B, int Hin, int Win, int C, int stride, void* col, void* stream);
 
 /* wd (Cin, taps, Cout) = 180-degree tap flip + in/out transpose of w (Cout, taps, Cin) bf16: the data gradient of a
- * stride-1 conv is yv_conv2d(dz, wd); of a stride-2 conv the same over the zero-inserted dz (yv_view_op mode 4). */
+ * stride-1 conv is yv_conv2d(dz, wd); of a stride-2 conv the same over the zero-inserted dz (yv_view_op mode 4), or - 3 x 3,
+ * without the zero-inserted copy and its products with zeros - yv_conv2d_dgrad_s2(dz, wd), which reads the same wd. */
 int yv_conv_weight_dgrad(const void* w, int Cout, int taps, int Cin, void* wd, void* stream);
+
+/* Data gradient of a 3 x 3 / stride 2 / pad 1 convolution without zero insertion: dx (B, 2*Hout, 2*Wout, Cin) = [res +] the
+ * gradient of z = conv(x, w) at dz (B, Hout, Wout, Cout), wd = yv_conv_weight_dgrad(w) (Cin, 9, Cout).  The output pixel
+ * (2i + py, 2j + px) belongs to parity phase (py, px); per axis parity 0 takes wd slot row 1 at dz row i, parity 1 takes slot
+ * row 0 at dz row i and slot row 2 at dz row i + 1 (zero past the last row); the 2-D slot is 3 * row + col.  The phases have
+ * 1 / 2 / 2 / 4 taps - 9 tap products per 2 x 2 output block where the zero-inserted convolution spends 36 - and each is an
+ * implicit GEMM (B*Hout*Wout rows, Cin columns, K = taps * Cout, taps in ascending slot order) on the phase form of the
+ * convolution kernels; the four run in ONE launch, heaviest first.  bf16 in and out, f32 accumulation, no bias, no activation.
+ * Eligibility (else YV_ERR_ARG, nothing is written): Cout a multiple of 64, Cin a multiple of 8, dz->c == Cout, no upsample,
+ * strides that are multiples of 8 and cover the channels, every base 16-byte aligned.  res (same grid and type as dx, may be dx
+ * itself) is optional.  32-bit byte offsets address dz: a batch whose dz passes 2 GB is taken in sub-batches, one image and wd
+ * must stay below 2 GB (YV_ERR_LIMIT).  ws / ws_bytes: reserved, no route splits K.
+ * With res the number of roundings depends on the route (yv_conv2d_dgrad_s2_route reports it):
+ *   direct epilogue (staged 0: 16- / 32-wide tiles, "staged_epilogue" = 0):  dx = bf16(y + r), ONE rounding;
+ *   staged epilogue (staged 1: every LDS-DMA route, the 64- / 128-wide tiles otherwise):  dx = bf16(bf16(y) + r), the
+ *   gradient is rounded to bf16 BEFORE the residual is added, TWO roundings.
+ * Without a residual both forms give the same bits.  Where yv_conv2d over the zero-inserted dz takes the same epilogue form and
+ * does not split K, its result has the same bits: its other K steps add products with zeros. */
+int yv_conv2d_dgrad_s2(const yv_view* dz, int B, int Hout, int Wout, const void* wd, int Cin, int Cout, void* dx, int dx_ld,
+                       const void* res, int res_ld, void* ws, size_t ws_bytes, void* stream);
+
+/* The route of yv_conv2d_dgrad_s2 for the data gradient of a ksize x ksize / stride 2 layer with input (B, Hin, Win, Cin) and
+ * Cout output channels, decided by the function the launch path itself calls.  Host only: nothing is dereferenced, launched or
+ * queried; dense 16-byte aligned bases are assumed, dz_ld / dx_ld / res_ld are the pixel strides (res_ld = 0: no residual).
+ * Returns a negative YV_ERR_* code where yv_conv2d_dgrad_s2 rejects the arguments or cannot express the layer (ksize != 3, odd
+ * Hin or Win), else YV_OK and *out; for a batch taken in sub-batches, the route of the first one. */
+typedef struct {
+    int kernel;     /* instance, numbered as yv_conv2d_instance bits 0-3: 0 .. 3 igemm_kernel 128 x 16 / 32 / 64 / 128 tiles,
+                       5 cgemm_dma_kernel<64,4,1,3>, 7 <128,2,2,2>; each in its phase form */
+    int ksteps[4];  /* 64-deep K steps per tile of the phases in launch order (1,1), (1,0), (0,1), (0,0): 4, 2, 2, 1 x Cout / 64 */
+    int staged;     /* 1: the staged epilogue runs (two roundings with a residual, see yv_conv2d_dgrad_s2) */
+    int tiles;      /* tiles of ONE phase */
+    int workgroups; /* 4 * tiles: the launch */
+    int use;        /* 1: measured no slower than zero insertion + yv_conv2d for this shape; 0: keep that path */
+} yv_dgrad_s2_route_t;
+int yv_conv2d_dgrad_s2_route(int B, int Hin, int Win, int ksize, int Cin, int Cout, int dz_ld, int dx_ld, int res_ld,
+                             yv_dgrad_s2_route_t* out);
 
 /* v8 detection loss and its gradient (the objective of `YOLO(pt).train(...)`, utils/trainYolo.py:33; published
  * ultralytics v8DetectionLoss restated in oracle/yolo_train.py - parity unpinned): DFL decode, TaskAlignedAssigner

@@ -58,9 +58,20 @@ __device__ __forceinline__ float silu_f(float x) { return x * __builtin_amdgcn_r
 __device__ __attribute__((aligned(256))) uint32_t g_zero_page[64];
 // STATS (yv_conv2d_stats): cs / cq (NF * 4 floats each, zeroed by the caller) receive this lane's column sums of the bf16-rounded
 // values it stores and of their squares, rows in ascending fragment order; rows >= M and columns >= N add nothing.
-template <int MF, int NF, bool STATS = false>
+// PHASE (yv_conv2d_dgrad_s2): row m = (b, i, j) of the Hout x Wout gradient grid is pixel (b, 2i + py, 2j + px) of the output and of
+// the residual, ph = py * 2 + px being the workgroup's phase.
+template <bool PHASE>
+__device__ __forceinline__ long long phase_row(const GemmArgs& g, int m, int ph) {
+    if constexpr (!PHASE) return m;
+    const int hw = g.Hout * g.Wout;
+    const int b = m / hw, rem = m - b * hw;
+    const int i = rem / g.Wout, j = rem - i * g.Wout;
+    return ((long long)b * (2 * g.Hout) + 2 * i + (ph >> 1)) * (2 * g.Wout) + 2 * j + (ph & 1);
+}
+
+template <int MF, int NF, bool STATS = false, bool PHASE = false>
 __device__ __forceinline__ void epilogue(const GemmArgs& g, f32x4 (&acc)[NF][MF], int M, int m0, int n0, int wrow_m,
-                                         int wrow_n, int fr, int fq, float* cs = nullptr, float* cq = nullptr) {
+                                         int wrow_n, int fr, int fq, float* cs = nullptr, float* cq = nullptr, int ph = 0) {
     // ---- epilogue: lane owns channels n..n+3 of row m --------------------------------------
     const int flags = g.flags;
 #pragma unroll
@@ -68,6 +79,7 @@ __device__ __forceinline__ void epilogue(const GemmArgs& g, f32x4 (&acc)[NF][MF]
         const int m = m0 + wrow_m + j * 16 + fr;
         if (m >= M) continue;
         long long orow = m;
+        if constexpr (PHASE) orow = phase_row<true>(g, m, ph);
         const float* posrow = nullptr;
         if (flags & YV_EPI_POSEMB) {
             const int r = m / g.tok, t = m - r * g.tok;
@@ -131,10 +143,10 @@ __device__ __forceinline__ void epilogue(const GemmArgs& g, f32x4 (&acc)[NF][MF]
 // (bf16) / 256-byte (f32) row segments with 16-byte stores; residual reads are coalesced the same way.
 // STATS (yv_conv2d_stats, bf16 output): cs / cq (8 floats each, zeroed by the caller) receive the column sums of the 8 channels
 // this lane stores (n = n0 + wrow_n + (lane & 7) * 8 ..) and of their squares, its rows (lane >> 3) + 8 * it in ascending order.
-template <int MF, bool STATS = false>
+template <int MF, bool STATS = false, bool PHASE = false /* bf16 output only: the row map of phase_row */>
 __device__ __forceinline__ void epilogue_staged(const GemmArgs& g, f32x4 (&acc)[4][MF], int M, int m0, int n0,
                                                 int wrow_m, int wrow_n, int lane, unsigned char* stage, float* cs = nullptr,
-                                                float* cq = nullptr) {
+                                                float* cq = nullptr, int ph = 0) {
     const int flags = g.flags;
     const int fr = lane & 15, fq = lane >> 4;
     const int nb = n0 + wrow_n;
@@ -194,8 +206,10 @@ __device__ __forceinline__ void epilogue_staged(const GemmArgs& g, f32x4 (&acc)[
             const int m = m0 + wrow_m + row, n = nb + ch * 8;
             uint4 pk = *(const uint4*)(stage + row * 128 + ((ch ^ (row & 7)) << 4));
             if (m < M && n < g.N) {
+                [[maybe_unused]] long long om = 0;
+                if constexpr (PHASE) om = phase_row<true>(g, m, ph);
                 if (flags & YV_EPI_RES_BF16) {
-                    const uint4 rr = *(const uint4*)(g.res + (long long)m * g.ldres + n);
+                    const uint4 rr = *(const uint4*)(g.res + (PHASE ? om : (long long)m) * g.ldres + n);
                     const uint32_t a[4] = {pk.x, pk.y, pk.z, pk.w}, b[4] = {rr.x, rr.y, rr.z, rr.w};
                     uint32_t o[4];
 #pragma unroll
@@ -246,7 +260,7 @@ __device__ __forceinline__ void epilogue_staged(const GemmArgs& g, f32x4 (&acc)[
                                            bf16_to_f32((uint16_t)(a[q] >> 16)) * gelu_grad_f(bf16_to_f32((uint16_t)(b[q] >> 16))));
                     pk = make_uint4(o[0], o[1], o[2], o[3]);
                 }
-                *(uint4*)((uint16_t*)g.out + (long long)m * g.ldo + n) = pk;
+                *(uint4*)((uint16_t*)g.out + (PHASE ? om : (long long)m) * g.ldo + n) = pk;
                 if constexpr (STATS) {
                     const uint32_t a[4] = {pk.x, pk.y, pk.z, pk.w};
 #pragma unroll
@@ -301,9 +315,10 @@ __device__ __forceinline__ void epilogue_staged(const GemmArgs& g, f32x4 (&acc)[
 // butterfly (both partners compute the same sum), then the WM waves in wave order through LDS.  The scratch (WM x 2 x BN floats)
 // lies at the start of the tile buffers, i.e. inside the staged epilogue's slabs: a barrier that every wave reaches (its rows
 // may all lie past M - it then adds zeros) separates the two uses.  g.staged is the same for the whole launch.
-template <int MF, int NF, bool STATS = false, int WM = 1, int BN = 16>
+template <int MF, int NF, bool STATS = false, int WM = 1, int BN = 16, bool PHASE = false>
 __device__ __forceinline__ void finish_tile(const GemmArgs& g, f32x4 (&acc)[NF][MF], int M, int m0, int n0, int wrow_m,
-                                            int wrow_n, int lane, int wave, unsigned char* smem, int tm = 0) {
+                                            int wrow_n, int lane, int wave, unsigned char* smem, int tm = 0, int ph = 0) {
+    static_assert(!(STATS && PHASE), "no column sums of a data gradient");
     if constexpr (STATS) {
         float* const sc = (float*)smem + (wrow_m / (MF * 16)) * 2 * BN + wrow_n;      // this wave's [which][column] rows
         bool staged = false;
@@ -357,16 +372,52 @@ __device__ __forceinline__ void finish_tile(const GemmArgs& g, f32x4 (&acc)[NF][
     }
     if constexpr (NF == 4 && (MF % 2) == 0) {
         if (g.staged) {          // wave-private slab of MF*16 rows x 128 B inside the (now idle) tile buffers
-            epilogue_staged<MF>(g, acc, M, m0, n0, wrow_m, wrow_n, lane, smem + wave * (MF * 16 * 128));
+            epilogue_staged<MF, false, PHASE>(g, acc, M, m0, n0, wrow_m, wrow_n, lane, smem + wave * (MF * 16 * 128), nullptr, nullptr,
+                                              ph);
             return;
         }
     }
-    epilogue<MF, NF>(g, acc, M, m0, n0, wrow_m, wrow_n, lane & 15, lane >> 4);
+    epilogue<MF, NF, false, PHASE>(g, acc, M, m0, n0, wrow_m, wrow_n, lane & 15, lane >> 4, nullptr, nullptr, ph);
+}
+
+// ---- PHASE form of the convolution kernels (yv_conv2d_dgrad_s2): the data gradient of a 3 x 3 / stride 2 convolution --------------
+// One launch holds the four parity phases (py, px) of the output pixel (2i + py, 2j + px), heaviest first: the workgroup id picks the
+// phase (ph = py * 2 + px), then the tile inside it.  Per axis parity 0 takes wd slot row 1 at displacement 0, parity 1 takes slot
+// row 0 at displacement 0 and slot row 2 at displacement + 1; the phase's taps are walked in ascending slot (3 * row + col) order,
+// which is the order the stride-1 convolution over the zero-inserted gradient meets its non-zero terms.  The source grid is the
+// Hout x Wout gradient itself (g.Hin = g.Hout, g.stride = 1), g.c0 its channels (a multiple of 64: a K step lies inside one tap),
+// g.K = 9 * g.c0 the row stride of wd (Cin, 9, Cout); no tap lies before the pixel, so the descriptor needs no negative bias.
+__device__ __forceinline__ int phase_of_block(const GemmArgs& g, int& bid) {
+    const int per = g.tiles_m * g.tiles_n;
+    const int q = bid / per;                      // launch order 0 .. 3: (1,1) four taps, (1,0) and (0,1) two, (0,0) one
+    bid -= q * per;
+    return 3 - (g.group_m + q);
+}
+__device__ __forceinline__ int phase_ksteps(const GemmArgs& g, int ph) { return ((ph >> 1) + 1) * ((ph & 1) + 1) * (g.c0 / BK); }
+// validity of the nine wd slots for the pixel (oy, ox): slot row / column 2 reads the next gradient row / column
+__device__ __forceinline__ uint32_t phase_taps(const GemmArgs& g, int oy, int ox) {
+    const uint32_t rows = oy + 1 < g.Hout ? 0x1ffu : 0x03fu, cols = ox + 1 < g.Wout ? 0x1ffu : 0x0dbu;
+    return rows & cols;
+}
+// K step at element kb of phase ph -> wd slot, byte displacement of its source pixel (+ channel), byte column in a wd row
+struct PhaseStep { int slot; uint32_t src, wcol; };
+__device__ __forceinline__ PhaseStep phase_step(const GemmArgs& g, int ph, int kb) {
+    const int t = g.cin_shift >= 0 ? (kb >> g.cin_shift) : kb / g.c0;
+    const int c = kb - t * g.c0;
+    const int px = ph & 1, py = ph >> 1;
+    const int row = py ? 2 * (px ? t >> 1 : t) : 1, col = px ? 2 * (t & 1) : 1;
+    PhaseStep s;
+    s.slot = 3 * row + col;
+    s.src = (uint32_t)((((row >> 1) * g.Win + (col >> 1)) * g.lda0 + c) * 2);
+    s.wcol = (uint32_t)((s.slot * g.c0 + c) * 2);
+    return s;
 }
 
 template <int MODE /*0 linear, 1 conv*/, int BM, int BN, int WM, int WN, bool TWO = false /*conv with two concatenated sources*/,
-          bool STATS = false /*conv that also writes its tile's column sums (finish_tile)*/>
+          bool STATS = false /*conv that also writes its tile's column sums (finish_tile)*/,
+          bool PHASE = false /*stride-2 data gradient by parity phase (above)*/>
 __global__ __launch_bounds__(THREADS) void igemm_kernel(GemmArgs g) {
+    static_assert(!PHASE || (MODE == 1 && !TWO && !STATS), "the phase form is a one-source convolution");
     constexpr int MF = BM / WM / 16;               // activation fragments per wave
     constexpr int NF = BN / WN / 16;               // weight fragments per wave
     constexpr int A_CH = BM * 8 / THREADS;         // 16-byte chunks per thread per K step (activations)
@@ -381,8 +432,10 @@ __global__ __launch_bounds__(THREADS) void igemm_kernel(GemmArgs g) {
 
     // XCD-aware bijective remap of the 1-D grid
     int bid = blockIdx.x;
+    int nwg = gridDim.x, ph = 0;
+    if constexpr (PHASE) { ph = phase_of_block(g, bid); nwg = g.tiles_m * g.tiles_n; }
     {
-        const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, x = bid & 7;
+        const int q = nwg >> 3, r = nwg & 7, x = bid & 7;
         bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
     }
     const int S = g.splitk > 1 ? g.splitk : 1;
@@ -423,7 +476,9 @@ __global__ __launch_bounds__(THREADS) void igemm_kernel(GemmArgs g) {
             a_off1[p] = g.c1 ? (uint32_t)((((long long)b * (g.Hin >> g.up1) + (cy >> g.up1)) * (g.Win >> g.up1) + (cx >> g.up1)) * g.lda1 * 2) + ch * 16 - a_off0[p] : 0u;
             uint32_t taps = 0;
             if (a_valid[p]) {
-                if (g.ksize == 3) {
+                if constexpr (PHASE) {
+                    taps = phase_taps(g, cy, cx);
+                } else if (g.ksize == 3) {
 #pragma unroll
                     for (int t = 0; t < 9; ++t) {
                         const int iy = cy + t / 3 - 1, ix = cx + t % 3 - 1;
@@ -462,7 +517,7 @@ __global__ __launch_bounds__(THREADS) void igemm_kernel(GemmArgs g) {
         return make_uint4(v[0], v[1], v[2], v[3]);
     };
     constexpr uint32_t OOB = 0x80000000u;
-    const uint32_t bias0 = MODE == 1 && g.ksize == 3 ? (uint32_t)((g.Win + 1) * g.lda0 * 2) : 0u;
+    const uint32_t bias0 = MODE == 1 && !PHASE && g.ksize == 3 ? (uint32_t)((g.Win + 1) * g.lda0 * 2) : 0u;
     // (copies first: a ternary between two FIELDS of the by-value kernel argument selects between their addresses; and the
     //  descriptors are built inside the lambda - captured by reference they are objects hipcc cannot keep out of memory, and the
     //  whole closure, kernel argument included, lands in scratch)
@@ -496,8 +551,13 @@ __global__ __launch_bounds__(THREADS) void igemm_kernel(GemmArgs g) {
                 rw[p] = ld16(w_ok[p] && k_ok, wp + (uint32_t)(w_off[p] + (uint32_t)kb * 2));
         } else {
             int tap = 0;                                       // (per lane only when a K step spans several taps: Cin < 64)
-            uint32_t soff = bias0, dl = 0;
-            if (g.ksize == 3) {
+            uint32_t soff = bias0, dl = 0, wcol = 0;            // (wcol: PHASE only)
+            if constexpr (PHASE) {
+                const PhaseStep ps = phase_step(g, ph, kb);
+                tap = ps.slot;
+                soff = (uint32_t)__builtin_amdgcn_readfirstlane((int)ps.src);
+                wcol = (uint32_t)__builtin_amdgcn_readfirstlane((int)ps.wcol);
+            } else if (g.ksize == 3) {
                 const int kk = g.tap_uniform ? kb : k;
                 tap = g.cin_shift >= 0 ? (kk >> g.cin_shift) : kk / Cin;
                 const int cin = kk - tap * Cin;
@@ -517,7 +577,7 @@ __global__ __launch_bounds__(THREADS) void igemm_kernel(GemmArgs g) {
             const auto rsW = __builtin_amdgcn_make_buffer_rsrc((void*)wp, 0, 0x7fffffff, 0x00020000);
 #pragma unroll
             for (int p = 0; p < W_CH; ++p) {
-                const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsW, (w_ok[p] && k_ok) ? w_off[p] : OOB, (uint32_t)kb * 2, 0);
+                const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsW, (w_ok[p] && k_ok) ? w_off[p] : OOB, PHASE ? wcol : (uint32_t)kb * 2, 0);
                 rw[p] = make_uint4(v[0], v[1], v[2], v[3]);
             }
         }
@@ -547,7 +607,7 @@ __global__ __launch_bounds__(THREADS) void igemm_kernel(GemmArgs g) {
     const int wrow_m = wm * (BM / WM), wrow_n = wn * (BN / WN);
     const int fr = lane & 15, fq = lane >> 4;
 
-    const int nk_all = (g.K + BK - 1) / BK;
+    const int nk_all = PHASE ? phase_ksteps(g, ph) : (g.K + BK - 1) / BK;
     const int kt0 = (int)((long long)nk_all * slice / S), nk = (int)((long long)nk_all * (slice + 1) / S);
     // ONE LDS buffer: the next step's operands wait in registers while this step's MFMAs read the tile, and go to LDS between
     // two barriers.  The launches are latency-bound (a gather per step, ~0.2 us of MFMAs), so what counts is how many workgroups
@@ -599,7 +659,7 @@ __global__ __launch_bounds__(THREADS) void igemm_kernel(GemmArgs g) {
         }
         return;
     }
-    finish_tile<MF, NF, STATS, WM, BN>(g, acc, M, m0, n0, wrow_m, wrow_n, lane, wave, smem, tm);
+    finish_tile<MF, NF, STATS, WM, BN, PHASE>(g, acc, M, m0, n0, wrow_m, wrow_n, lane, wave, smem, tm, ph);
 }
 
 // second stage of a split-K conv: sum the K slices, then the usual epilogue (bias, SiLU, bf16 shortcut, store)
@@ -845,8 +905,10 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_dma_kernel(GemmArgs g) {
 // VALU issue of exactly that gather and staging.  Epilogues: finish_tile (bias, SiLU, bf16 shortcut, f32 output).
 // Eligibility (host): (c0 + c1) % 64 == 0, c1 == 0 or (1 x 1 and c0 % 64 == 0), Cout >= 64, staged epilogue usable.
 // ---------------------------------------------------------------------------------------------
-template <int BN, int WM, int WN, int ST = 2 /* LDS stages: ST - 1 K steps of DMA in flight */, bool STATS = false /* as igemm_kernel */>
+template <int BN, int WM, int WN, int ST = 2 /* LDS stages: ST - 1 K steps of DMA in flight */, bool STATS = false /* as igemm_kernel */,
+          bool PHASE = false /* as igemm_kernel */>
 __global__ __launch_bounds__(256) void cgemm_dma_kernel(GemmArgs g) {
+    static_assert(!(PHASE && STATS), "the phase form is a plain convolution");
     constexpr int BM = 128, NW = 4;
     static_assert(WM * WN == NW, "four waves");
     constexpr int MF = BM / WM / 16, NF = BN / WN / 16;
@@ -856,8 +918,10 @@ __global__ __launch_bounds__(256) void cgemm_dma_kernel(GemmArgs g) {
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int M = g.M;
     int bid = blockIdx.x;
+    int nwg = gridDim.x, ph = 0;
+    if constexpr (PHASE) { ph = phase_of_block(g, bid); nwg = g.tiles_m * g.tiles_n; }
     {
-        const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, x = bid & 7;
+        const int q = nwg >> 3, r = nwg & 7, x = bid & 7;
         bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
     }
     const int tm = bid / g.tiles_n, tn = bid - tm * g.tiles_n;
@@ -881,7 +945,9 @@ __global__ __launch_bounds__(256) void cgemm_dma_kernel(GemmArgs g) {
         a_off1[j] = g.c1 ? (uint32_t)((((long long)b * (g.Hin >> g.up1) + (cy >> g.up1)) * (g.Win >> g.up1) + (cx >> g.up1)) * g.lda1 * 2) + sw : 0u;
         uint32_t taps = 0;
         if (m < M) {
-            if (g.ksize == 3) {
+            if constexpr (PHASE) {
+                taps = phase_taps(g, cy, cx);
+            } else if (g.ksize == 3) {
 #pragma unroll
                 for (int t = 0; t < 9; ++t) {
                     const int iy = cy + t / 3 - 1, ix = cx + t % 3 - 1;
@@ -901,7 +967,7 @@ __global__ __launch_bounds__(256) void cgemm_dma_kernel(GemmArgs g) {
         w_off[j] = (uint32_t)(((long long)n * g.K + ((lch ^ (r & 7)) << 3)) * 2);
     }
     // the scalar offset is unsigned: source 0's descriptor starts one row + one pixel before the tensor (3 x 3 only)
-    const uint32_t bias0 = g.ksize == 3 ? (uint32_t)((g.Win + 1) * g.lda0 * 2) : 0u;
+    const uint32_t bias0 = !PHASE && g.ksize == 3 ? (uint32_t)((g.Win + 1) * g.lda0 * 2) : 0u;
     const auto rs0 = __builtin_amdgcn_make_buffer_rsrc((void*)((const unsigned char*)g.a0 - bias0), 0, 0x7fffffff, 0x00020000);
     const auto rs1 = __builtin_amdgcn_make_buffer_rsrc((void*)(g.c1 ? g.a1 : g.a0), 0, 0x7fffffff, 0x00020000);
     const auto rsW = __builtin_amdgcn_make_buffer_rsrc((void*)g.w, 0, 0x7fffffff, 0x00020000);
@@ -911,6 +977,17 @@ __global__ __launch_bounds__(256) void cgemm_dma_kernel(GemmArgs g) {
         unsigned char* A = smem + buf * (A_BYTES + W_BYTES);
         unsigned char* W = A + A_BYTES;
         const int kb = kt * BK;                                  // (uniform)
+        if constexpr (PHASE) {
+            const PhaseStep ps = phase_step(g, ph, kb);
+#pragma unroll
+            for (int j = 0; j < A_INS; ++j)
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rs0, (lptr_t)(A + (j * NW + wave) * 1024), 16,
+                                                         (int)(((a_taps[j] >> ps.slot) & 1u) ? a_off0[j] : OOB), (int)ps.src, 0, 0);
+#pragma unroll
+            for (int j = 0; j < W_INS; ++j)
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsW, (lptr_t)(W + (j * NW + wave) * 1024), 16, (int)w_off[j], (int)ps.wcol, 0, 0);
+            return;
+        }
         if (g.c1 && kb >= g.c0) {                                // second source of a two-source 1 x 1
             const int so = (kb - g.c0) * 2;
 #pragma unroll
@@ -944,7 +1021,7 @@ __global__ __launch_bounds__(256) void cgemm_dma_kernel(GemmArgs g) {
     const int wm = wave / WN, wn = wave - wm * WN;
     const int wrow_m = wm * (BM / WM), wrow_n = wn * (BN / WN);
     const int fr = lane & 15, fq = lane >> 4;
-    const int nk = g.K / BK;
+    const int nk = PHASE ? phase_ksteps(g, ph) : g.K / BK;
     // ring of ST stages, ST - 1 K steps in flight: the launches are latency-bound (9 .. 36 K steps per tile, one L2 / HBM round trip
     // each when only the next step is in flight), and inside the pipeline the detector runs on the few CUs the classifier leaves
     // free, where a tile's latency is all that counts.  Step kt: counted wait (the ST - 2 younger steps stay in flight), ONE raw
@@ -992,7 +1069,7 @@ __global__ __launch_bounds__(256) void cgemm_dma_kernel(GemmArgs g) {
         }
     }
     asm volatile("s_barrier" ::: "memory");                       // the staged epilogue reuses the tile buffers
-    finish_tile<MF, NF, STATS, WM, BN>(g, acc, M, m0, n0, wrow_m, wrow_n, lane, wave, smem, tm);
+    finish_tile<MF, NF, STATS, WM, BN, PHASE>(g, acc, M, m0, n0, wrow_m, wrow_n, lane, wave, smem, tm, ph);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2156,6 +2233,7 @@ bool epi_can_stage(const GemmArgs& g) {
     return true;
 }
 
+int g_opt_dgrad_s2_split = 0;       // yv_conv2d_dgrad_s2: 1 = one launch per phase ("dgrad_s2_split"; measured slower)
 int g_opt_conv_dma = 8;             // convolutions with 64-aligned input channels on the LDS-DMA structure ("conv_dma": 0 off, 1..8 see dispatch)
 
 template <int BN, int WM, int WN, int ST>
@@ -2248,6 +2326,65 @@ int launch_conv(GemmArgs& g, int kern, hipStream_t st) {
     case CK_CDMA_128_2: return launch_cdma<128, 2, 2, 2>(g, st);
     case CK_CDMA_128_3: return launch_cdma<128, 2, 2, 3>(g, st);
     default: return launch_igemm<1>(g, kern, st);
+    }
+}
+
+// ---- yv_conv2d_dgrad_s2: the phase form of the two kernel families, the four phases in ONE launch (4 x tiles workgroups) ----------
+int launch_phases(void (*kern)(GemmArgs), GemmArgs& g, int threads, size_t lds, hipStream_t st) {
+    const int per = g.tiles_m * g.tiles_n;
+    if (!g_opt_dgrad_s2_split) {
+        g.group_m = 0;
+        hipLaunchKernelGGL(kern, dim3(4 * per), dim3(threads), lds, st, g);
+        return yv_launch_status();
+    }
+    for (int q = 0; q < 4; ++q) {                // (tools/dgrad_s2_bench.py --split: the comparison DESIGN 24 reports)
+        g.group_m = q;
+        hipLaunchKernelGGL(kern, dim3(per), dim3(threads), lds, st, g);
+        const int rc = yv_launch_status();
+        if (rc != YV_OK) return rc;
+    }
+    return YV_OK;
+}
+
+template <int BN, int WM, int WN>
+int launch_phase_igemm(GemmArgs& g, hipStream_t st) {
+    g.tiles_m = (g.M + 127) / 128;
+    g.tiles_n = (g.N + BN - 1) / BN;
+    size_t lds = (size_t)(128 + BN) * 128;
+    if (lds < (size_t)THREADS / 64 * (128 / WM) * 128) lds = (size_t)THREADS / 64 * (128 / WM) * 128;   // the staged epilogue's slabs
+    void (*kern)(GemmArgs) = igemm_kernel<1, 128, BN, WM, WN, false, false, true>;
+    if (!yv_grant_lds((const void*)kern, lds)) return YV_ERR_LAUNCH;
+    return launch_phases(kern, g, THREADS, lds, st);
+}
+
+template <int BN, int WM, int WN, int ST>
+int launch_phase_cdma(GemmArgs& g, hipStream_t st) {
+    g.tiles_m = (g.M + 127) / 128;
+    g.tiles_n = (g.N + BN - 1) / BN;
+    const size_t lds = ST * (size_t)(128 + BN) * 128;
+    void (*kern)(GemmArgs) = cgemm_dma_kernel<BN, WM, WN, ST, false, true>;
+    if (!yv_grant_lds((const void*)kern, lds)) return YV_ERR_LAUNCH;
+    return launch_phases(kern, g, 256, lds, st);
+}
+
+// The route of one phase launch: ONE rule for dgrad_s2_one (which launches it) and yv_conv2d_dgrad_s2_route (which reports it).
+// The LDS-DMA form from 64 output columns (= input channels of the layer) where the staged epilogue is usable, 64-wide three-stage
+// tiles except the 128-wide two-stage ones of conv_route's large-map rule; igemm_kernel's tiles below that.  Never split-K.
+int dgrad_s2_route(GemmArgs& g) {
+    g.staged = g_opt_staged && epi_can_stage(g);
+    g.splitk = 1;
+    if (g_opt_conv_dma && g.N >= 64 && g.staged) return (g.M >= 100000 && g.N > 64) ? CK_CDMA_128_2 : CK_CDMA_64_3;
+    return igemm_pick(g.N);
+}
+
+int launch_dgrad_s2(GemmArgs& g, int kern, hipStream_t st) {
+    switch (kern) {
+    case CK_CDMA_64_3: return launch_phase_cdma<64, 4, 1, 3>(g, st);
+    case CK_CDMA_128_2: return launch_phase_cdma<128, 2, 2, 2>(g, st);
+    case CK_IGEMM_128: return launch_phase_igemm<128, 2, 2>(g, st);
+    case CK_IGEMM_64: return launch_phase_igemm<64, 4, 1>(g, st);
+    case CK_IGEMM_32: return launch_phase_igemm<32, 4, 1>(g, st);
+    default: return launch_phase_igemm<16, 4, 1>(g, st);
     }
 }
 
@@ -2661,6 +2798,7 @@ static const struct { const char* key; int* (*at)(); } k_options[] = {
     {"linear_skinny", [] { return &g_opt_skinny; }},
     {"wgrad_mx_split", [] { return &g_opt_wgrad_mx_split; }},
     {"conv_dma", [] { return &g_opt_conv_dma; }},
+    {"dgrad_s2_split", [] { return &g_opt_dgrad_s2_split; }},
 };
 static int* option_at(const char* key) {
     for (const auto& o : k_options)
@@ -2990,6 +3128,72 @@ extern "C" int yv_conv2d_instance(int B, int Hout, int Wout, int ksize, int stri
     const yv_view v0 = {dummy, c0, c0, 0}, v1 = {dummy, c1, c1, 0};
     return conv_impl(&v0, c1 ? &v1 : nullptr, B, Hout, Wout, ksize, stride, dummy, (const float*)dummy, Cout, dummy, out_ld,
                      (flags & YV_EPI_RES_BF16) ? dummy : nullptr, res_ld, flags, ws_bytes ? dummy : nullptr, ws_bytes, nullptr, true);
+}
+
+// ---------------------------------------------------------------------------------------------------- stride-2 data gradient by phase
+// One sub-batch (sources below 2 GB).  route != nullptr: report, launch nothing.
+static int dgrad_s2_one(const yv_view* dz, int B, int Hout, int Wout, const void* wd, int Cin, int Cout, void* dx, int dx_ld,
+                        const void* res, int res_ld, void* stream, yv_dgrad_s2_route_t* route) {
+    GemmArgs g = {};
+    g.cin_shift = (Cout & (Cout - 1)) == 0 ? __builtin_ctz((unsigned)Cout) : -1;
+    g.tap_uniform = 1;
+    g.a0 = (const uint16_t*)dz->ptr; g.lda0 = dz->ld; g.c0 = Cout;
+    g.Hin = Hout; g.Win = Wout; g.Hout = Hout; g.Wout = Wout; g.ksize = 3; g.stride = 1;       // the source grid (see phase_step)
+    g.w = (const uint16_t*)wd;
+    g.M = B * Hout * Wout; g.N = Cin; g.K = 9 * Cout;
+    g.out = dx; g.ldo = dx_ld; g.res = (const uint16_t*)res; g.ldres = res_ld; g.flags = res ? YV_EPI_RES_BF16 : 0;
+    const int kern = dgrad_s2_route(g);
+    if (route) {
+        const int bn = kern == CK_CDMA_128_2 || kern == CK_IGEMM_128 ? 128 : (kern == CK_IGEMM_32 ? 32 : (kern == CK_IGEMM_16 ? 16 : 64));
+        route->kernel = kern;
+        route->staged = g.staged && kern >= CK_IGEMM_64;
+        for (int q = 0; q < 4; ++q) route->ksteps[q] = (q == 0 ? 4 : (q == 3 ? 1 : 2)) * (Cout / BK);
+        route->tiles = ((g.M + 127) / 128) * ((g.N + bn - 1) / bn);
+        route->workgroups = 4 * route->tiles;
+        route->use = 1;
+        return YV_OK;
+    }
+    return launch_dgrad_s2(g, kern, (hipStream_t)stream);
+}
+
+static int dgrad_s2_impl(const yv_view* dz, int B, int Hout, int Wout, const void* wd, int Cin, int Cout, void* dx, int dx_ld,
+                         const void* res, int res_ld, void* stream, yv_dgrad_s2_route_t* route) {
+    if (!dz || !dz->ptr || !wd || !dx || B <= 0 || Hout <= 0 || Wout <= 0 || Cin <= 0 || Cout <= 0) return YV_ERR_ARG;
+    if ((Cout % 64) || (Cin & 7) || dz->c != Cout || dz->up || dz->ld < Cout || (dz->ld & 7) || dx_ld < Cin || (dx_ld & 7) ||
+        (res && (res_ld < Cin || (res_ld & 7))))
+        return YV_ERR_ARG;
+    if (((uintptr_t)dz->ptr | (uintptr_t)wd | (uintptr_t)dx | (uintptr_t)res) & 15) return YV_ERR_ARG;
+    if (4LL * B * Hout * Wout > 0x7fffffffLL || 9LL * Cin * Cout * 2 >= 0x7fffffffLL) return YV_ERR_LIMIT;
+    // 32-bit byte offsets into the gradient: sub-batches as conv_impl takes them (lead: the + 1 row / + 1 pixel displacement)
+    const long long s0 = (long long)Hout * Wout * dz->ld * 2;
+    const long long nb = conv_sub_batch(s0, 0, (long long)(Wout + 1) * dz->ld * 2);
+    if (nb < 1) return YV_ERR_LIMIT;
+    if (nb >= B || route) return dgrad_s2_one(dz, (int)(nb < B ? nb : B), Hout, Wout, wd, Cin, Cout, dx, dx_ld, res, res_ld, stream, route);
+    for (long long b0 = 0; b0 < B; b0 += nb) {
+        const int n = (int)(B - b0 < nb ? B - b0 : nb);
+        yv_view v = *dz;
+        v.ptr = (unsigned char*)dz->ptr + b0 * s0;
+        const long long opix = b0 * 4 * Hout * Wout;
+        const int rc = dgrad_s2_one(&v, n, Hout, Wout, wd, Cin, Cout, (unsigned char*)dx + opix * dx_ld * 2, dx_ld,
+                                    res ? (const unsigned char*)res + opix * res_ld * 2 : nullptr, res_ld, stream, nullptr);
+        if (rc != YV_OK) return rc;
+    }
+    return YV_OK;
+}
+
+extern "C" int yv_conv2d_dgrad_s2(const yv_view* dz, int B, int Hout, int Wout, const void* wd, int Cin, int Cout, void* dx, int dx_ld,
+                                  const void* res, int res_ld, void* ws, size_t ws_bytes, void* stream) {
+    (void)ws; (void)ws_bytes;                                     // no route splits K
+    return dgrad_s2_impl(dz, B, Hout, Wout, wd, Cin, Cout, dx, dx_ld, res, res_ld, stream, nullptr);
+}
+
+extern "C" int yv_conv2d_dgrad_s2_route(int B, int Hin, int Win, int ksize, int Cin, int Cout, int dz_ld, int dx_ld, int res_ld,
+                                        yv_dgrad_s2_route_t* out) {
+    // 16-byte aligned bases; nothing is dereferenced or launched
+    static unsigned char dummy[16] __attribute__((aligned(16)));
+    if (!out || ksize != 3 || Hin <= 0 || Win <= 0 || (Hin & 1) || (Win & 1)) return YV_ERR_ARG;
+    const yv_view v = {dummy, dz_ld, Cout, 0};
+    return dgrad_s2_impl(&v, B, Hin / 2, Win / 2, dummy, Cin, Cout, dummy, dx_ld, res_ld > 0 ? dummy : nullptr, res_ld, nullptr, out);
 }
 
 // ---------------------------------------------------------------------------------------------------- MXFP8 convolutions

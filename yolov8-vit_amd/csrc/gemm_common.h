@@ -36,7 +36,8 @@ struct GemmArgs {
     const int32_t* m_dev;
     int m_mul;
     int tiles_m, tiles_n;
-    int group_m;
+    int group_m;                 // linear kernels; PHASE convolutions (yv_conv2d_dgrad_s2) keep the launch-order index of the grid's
+                                 // first phase here: a field of its own would move the hidden arguments of every GemmArgs kernel
     int ldw;                     // WT kernels: row stride of the reduction-major weight (K, N)
     const float* resf;           // f32 residual source (null: read-modify-write `out`)
     uint16_t* aux;               // bf16 side buffer: SAVE_PRE target / GELU_BWD pre-activation

@@ -16,7 +16,7 @@ import os
 _HWQ_PRESET = os.environ.get("GPU_MAX_HW_QUEUES")
 os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import re
-from typing import List, Optional
+from typing import List, Optional, Tuple
 
 import torch
 
@@ -121,6 +121,8 @@ _SIGS = {
     "yv_conv2d": (_i, [C.POINTER(yv_view), C.POINTER(yv_view), _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _i, _vp, _i,
                        _i, _vp]),
     "yv_conv2d_instance": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _sz]),
+    "yv_conv2d_dgrad_s2": (_i, [C.POINTER(yv_view), _i, _i, _i, _vp, _i, _i, _vp, _i, _vp, _i, _vp, _sz, _vp]),
+    "yv_conv2d_dgrad_s2_route": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "yv_conv2d_ws": (_i, [C.POINTER(yv_view), C.POINTER(yv_view), _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _i, _vp, _i,
                           _i, _vp, _sz, _vp]),
     "yv_linear": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _i, _vp, _i, _vp]),
@@ -1026,6 +1028,42 @@ def conv_view(in0: "yv_view", B: int, Hout: int, Wout: int, ksize: int, stride: 
     check(lib.yv_conv2d_ws(C.byref(in0), None, B, Hout, Wout, ksize, stride, _p(weight), _p(bias), Cout, out.ptr, out.ld,
                            res.ptr if res is not None else None, res.ld if res is not None else 0, flags, _p(ws),
                            ws.numel() * 4, _st()), "yv_conv2d_ws")
+
+
+def dgrad_s2_taps(py: int, px: int) -> List[Tuple[int, int, int]]:
+    """The taps of parity phase (py, px) of a 3 x 3 / stride 2 / pad 1 data gradient, as (wd slot, dy, dx) in ascending slot
+    order: dx[b, 2i + py, 2j + px, :] = sum over the list of wd[:, slot, :] @ dz[b, i + dy, j + dx, :] (zero past the last row /
+    column), wd (Cin, 9, Cout) being conv_weight_dgrad's flipped weight.  Per axis parity 0 takes slot row 1 at displacement
+    0; parity 1 takes slot row 0 at displacement 0 and slot row 2 at displacement + 1.  1 / 2 / 2 / 4 taps: yv_conv2d_dgrad_s2
+    walks exactly this list."""
+    axis = lambda p: ((0, 0), (2, 1)) if p else ((1, 0),)
+    return [(3 * r + c, dy, dx) for r, dy in axis(py) for c, dx in axis(px)]
+
+
+DgradS2Route = collections.namedtuple("DgradS2Route", "kernel ksteps staged tiles workgroups use")
+
+
+def conv_dgrad_s2_route(B: int, Hin: int, Win: int, ksize: int, Cin: int, Cout: int, dz_ld: Optional[int] = None,
+                        dx_ld: Optional[int] = None, res_ld: Optional[int] = None) -> DgradS2Route:
+    """Route conv_dgrad_s2 takes for the data gradient of a ksize x ksize / stride 2 layer (B, Hin, Win, Cin) -> Cout under the
+    current options (host only): see yv_conv2d_dgrad_s2_route in include/yv_hip.h.  kernel is a CONV_IGEMM_* / CONV_DMA_* code;
+    dense rows and a residual of dx's stride by default (res_ld = 0: none); raises YvError where the entry rejects the layer;
+    use = False: the route keeps this shape on zero insertion."""
+    out = (C.c_int * 9)()
+    dx_ld = Cin if dx_ld is None else dx_ld
+    check(lib.yv_conv2d_dgrad_s2_route(B, Hin, Win, ksize, Cin, Cout, Cout if dz_ld is None else dz_ld, dx_ld,
+                                       dx_ld if res_ld is None else res_ld, out), "yv_conv2d_dgrad_s2_route")
+    return DgradS2Route(out[0], tuple(out[1:5]), bool(out[5]), out[6], out[7], bool(out[8]))
+
+
+def conv_dgrad_s2(dz: "yv_view", B: int, Hout: int, Wout: int, wd: torch.Tensor, Cin: int, Cout: int, dx: "yv_view",
+                  res: Optional["yv_view"] = None):
+    """dx (B, 2*Hout, 2*Wout) view = [res +] data gradient of a 3 x 3 / stride 2 convolution at dz (B, Hout, Wout) with
+    wd = conv_weight_dgrad(w), no zero-inserted copy: yv_conv2d_dgrad_s2.  res may be dx (accumulate into a slice)."""
+    _chk_dev(wd)
+    check(lib.yv_conv2d_dgrad_s2(C.byref(dz), B, Hout, Wout, _p(wd), Cin, Cout, dx.ptr, dx.ld,
+                                 res.ptr if res is not None else None, res.ld if res is not None else 0, None, 0, _st()),
+          "yv_conv2d_dgrad_s2")
 
 
 def conv_view_stats(in0: "yv_view", B: int, Hout: int, Wout: int, ksize: int, stride: int, weight: torch.Tensor, Cout: int,

@@ -22,7 +22,7 @@ import math
 from . import (OPT_ADAMW, OPT_SGD_NESTEROV, VIEW_ADD, VIEW_COPY, VIEW_PAD, VIEW_UP2, VIEW_UP2_BWD, VIEW_ZERO_INSERT, YvError, axpby,
                blob_nhwc8, bn_act_bwd, bn_act_fwd, ema_update, optim_step,
                bn_stats, bn_stats_finish, bn_ws_floats, cast_colsum, colsum_ws_floats, conv_stats_ws_floats, conv_view,
-               conv_view_stats, conv_weight_dgrad, detect_loss,
+               conv_dgrad_s2, conv_dgrad_s2_route, conv_view_stats, conv_weight_dgrad, detect_loss,
                detect_loss_ws_bytes, im2col3, maxpool5_bwd, mview, require_gpu, sgd_step, sppf_pool, view_op, wgrad, wgrad_conv3)
 from .engines import LAYER_STRIDE, REG_MAX, _env_flag, detect_widths, yolo_conv_keys, yolo_layers
 
@@ -73,6 +73,13 @@ def yolo_wgrad_shapes(scale: str, nc: int, size: int = 640, batch: int = 16,
     return out
 
 
+def yolo_s2_dgrad_shapes(scale: str, size: int = 640) -> List[Tuple[str, int, int, int]]:
+    """(key, Hin, Cin, Cout) of every stride-2 convolution of a YoloTrainer step that has a data gradient (host only): model.1, 3,
+    5, 7, 16, 19 - the stem's input is the image."""
+    return [(f"model.{idx}", 2 * (size // LAYER_STRIDE[idx]), p["cin"], p["cout"])
+            for idx, kind, p in yolo_layers(scale) if kind == "conv"]
+
+
 class _Act:
     """(B,H,W,C) bf16 activation + its gradient, stored as (rows padded to 64, C)."""
 
@@ -113,7 +120,7 @@ class YoloTrainer:
                  lr: float = 1e-4, momentum: float = 0.937, weight_decay: float = 5e-4, device: str = "cuda:0",
                  optimizer: str = "sgd", ema: bool = False, ema_decay: float = 0.9999, ema_tau: float = 2000.0,
                  overlap_wgrad: bool = True, implicit_wgrad: bool = True, narrow_wgrad: Optional[bool] = None,
-                 fused_bn_stats: Optional[bool] = None):
+                 fused_bn_stats: Optional[bool] = None, phase_dgrad: Optional[bool] = None):
         require_gpu()
         if size % 32:
             raise YvError("input size must be a multiple of 32")
@@ -127,6 +134,10 @@ class YoloTrainer:
         # opt-in: the forward's BatchNorm batch statistics from the convolution's epilogue (yv_conv2d_stats + yv_bn_stats_finish)
         # in place of a pass over z (yv_bn_stats); DESIGN.md section 22
         self.fused_bn_stats = _env_flag(fused_bn_stats, "YV_YOLO_FUSED_BN_STATS")
+        # opt-in: the data gradient of the stride-2 convolutions by parity phase (yv_conv2d_dgrad_s2) in place of zero insertion +
+        # a stride-1 convolution, for the blocks whose route says so (_alloc_buffers); DESIGN.md section 24
+        self.phase_dgrad = _env_flag(phase_dgrad, "YV_YOLO_PHASE_DGRAD")
+        self._phase_blocks: set = set()
         if optimizer not in ("sgd", "sgd_nesterov", "adamw"):
             raise YvError("optimizer must be 'sgd', 'sgd_nesterov' or 'adamw'")
         self.optimizer, self.use_ema, self.ema_decay, self.ema_tau = optimizer, ema, ema_decay, ema_tau
@@ -351,7 +362,9 @@ class YoloTrainer:
                 dzp_n = max(dzp_n, tpp * b.cout)
             elif b.k == 3:
                 col_n = max(col_n, _r64(T) * 9 * b.cin)
-            if b.s == 2:
+            if b.s == 2 and self.phase_dgrad and self._phase_eligible(b, hin):
+                self._phase_blocks.add(b.key)
+            elif b.s == 2:
                 zi_n = max(zi_n, B * hin * hin * b.cout)
         self.ws = torch.zeros(max(ws_f, 16), device=dev)
         self.wd_buf = torch.zeros(max(wd_n, 8), dtype=torch.bfloat16, device=dev)
@@ -359,6 +372,13 @@ class YoloTrainer:
         self.zi = torch.zeros(max(zi_n, 8), dtype=torch.bfloat16, device=dev)
         self.xp = torch.zeros(max(xp_n, 8), dtype=torch.bfloat16, device=dev)       # zero-initialised: its margins are read
         self.dzp = torch.zeros(max(dzp_n, 8), dtype=torch.bfloat16, device=dev)
+
+    def _phase_eligible(self, b: _Block, hin: int) -> bool:
+        """The route's answer for this block's data gradient (asked once, at construction): eligible and not measured slower."""
+        try:
+            return conv_dgrad_s2_route(self.B, hin, hin, b.k, b.cin, b.cout).use
+        except YvError:
+            return False
 
     def _block_geometry(self):
         S = self.size
@@ -415,6 +435,9 @@ class YoloTrainer:
         if dx is not None:
             wd = self.wd_buf[:b.cin * b.taps * b.cout]
             conv_weight_dgrad(self.w16(b), b.cout, b.taps, b.cin, wd)
+            if b.key in self._phase_blocks:
+                conv_dgrad_s2(mview(dz), self.B, hout, hout, wd, b.cin, b.cout, dx, res=dx)
+                return
             if b.s == 1:
                 src = mview(dz)
             else:
