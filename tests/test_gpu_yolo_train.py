@@ -257,12 +257,11 @@ def test_trainer_local_consistency(yv, scale, nc, S, B):
     x0 = _act_nchw(tr.x0, tr.x0.buf)[:, :3]
     topo = {i: (k, a) for i, k, a in topology(scale)}
     for idx, kind, p in tr.layers:
-        m = tr.mod[idx]
         if idx == 0:
             xin = x0.clone().requires_grad_(True)
         elif "a" in p:                                               # neck: input = concat buffer (checked below)
             (ia, ua), (ib, _) = p["a"], p["b"]
-            cat = tr.aux[idx]["cat"]
+            cat = tr.act[f"cat{idx}"]
             xa = _act_nchw(tr.out[ia], tr.out[ia].buf)
             xb = _act_nchw(tr.out[ib], tr.out[ib].buf)
             exp = torch.cat([torch.nn.functional.interpolate(xa, scale_factor=2, mode="nearest") if ua else xa, xb], 1)

@@ -63,6 +63,23 @@ def test_shape_list_holds_the_layers_the_narrow_tiles_are_for():
     assert p["model.2.m.0.cv1.conv"] == (16 * 162 * 162 + 63) // 64 * 64 and p["model.1.conv"] == 16 * 160 * 160
 
 
+@pytest.mark.parametrize("nc", [5, 80])
+@pytest.mark.parametrize("scale", ["n", "s", "m", "l", "x"])
+def test_launch_list_holds_the_convolutions_of_the_state_dict(scale, nc):
+    """The blocks of train_launches are the convolutions of yolo_conv_keys, key for key with the state dict's channel counts.  The
+    package defines the scales n, s and m (engines.YOLO_SCALES); for l and x both functions must refuse alike."""
+    from yvhip.engines import YOLO_SCALES, yolo_conv_keys
+    from yvhip.yolo_training import Block, train_launches
+    if scale not in YOLO_SCALES:
+        for fn in (yolo_conv_keys, train_launches):
+            with pytest.raises(KeyError):
+                fn(scale, nc)
+        return
+    blocks = [e for e in train_launches(scale, nc) if isinstance(e, Block)]
+    got = {(e.key + (".conv" if e.bn else ""), e.cin_real, e.cout_real, e.k) for e in blocks}
+    assert got == set(yolo_conv_keys(scale, nc)) and len(blocks) == len(got)
+
+
 def test_tile_128_is_the_present_rule():
     shapes = all_shapes()
     assert len(shapes) > 60

@@ -1,5 +1,5 @@
 """BatchNorm batch statistics of the detector trainer's forward, two launch sequences per BatchNorm convolution of YOLOv8s (nc 80)
-at 16 x 640 x 640 (the shapes of YoloTrainer._block_geometry, i.e. what bench.py --mode train-yolo runs):
+at 16 x 640 x 640 (the shapes of YoloTrainer.blocks / .geom, i.e. what bench.py --mode train-yolo runs):
 
   A  yv_conv2d_ws, then yv_bn_stats (a pass over z + the finaliser)                  - YoloTrainer's default
   B  yv_conv2d_stats (the statistics from the convolution's epilogue), then yv_bn_stats_finish   - YoloTrainer(fused_bn_stats=True)
@@ -28,7 +28,8 @@ def trainer_shapes():
     """[(first key, count, cin, cout, k, s, hin, hout)] of the BatchNorm blocks, in the trainer's order of first appearance."""
     tr = YoloTrainer(init_yolo_train_state(SCALE, NC, seed=0), scale=SCALE, nc=NC, size=SIZE, batch=BATCH)
     count, first = collections.Counter(), {}
-    for b, (hin, hout) in tr._block_geometry():
+    for b in tr.blocks:
+        hin, hout = tr.geom[b.key]
         if b.bn:
             sh = (b.cin, b.cout, b.k, b.s, hin, hout)
             count[sh] += 1

@@ -10,14 +10,21 @@ launches for forward and backward.  torch only owns device memory.  Layout rules
     zeroed once per step), which is what makes multi-consumer tensors (C2f splits, P3/P4/P5 features) correct;
   * a conv's data gradient is a conv of dz with the flipped / transposed weight (zero-inserted dz for stride 2), its
     weight gradient dz^T . im2col(x) runs on the transposing-read GEMM of the ViT trainer (yv_wgrad).
+
+The network's wiring - which block reads which view and writes which - is stated once, in `train_launches`: Block, Concat and Pool
+entries that name their buffers.  The trainer derives its parameters, activations and scratch sizes from that list, `forward`
+walks it, `backward` walks `train_backward_order` of it, and `yolo_wgrad_shapes` / `yolo_s2_dgrad_shapes` read it.  The order of the
+launches is pinned by tests/test_yolo_trainer_trace_cpu.py.
 """
 from __future__ import annotations
 
-from typing import Dict, List, Optional, Tuple
+import functools
+import itertools
+import math
+import re
+from typing import Dict, List, NamedTuple, Optional, Tuple, Union
 
 import torch
-
-import math
 
 from . import (OPT_ADAMW, OPT_SGD_NESTEROV, VIEW_ADD, VIEW_COPY, VIEW_PAD, VIEW_UP2, VIEW_UP2_BWD, VIEW_ZERO_INSERT, YvError, axpby,
                blob_nhwc8, bn_act_bwd, bn_act_fwd, ema_update, optim_step,
@@ -31,6 +38,128 @@ BN_EPS, BN_MOMENTUM = 1e-3, 0.03
 
 def _r64(n: int) -> int:
     return (n + 63) // 64 * 64
+
+
+# ---- the training network's launch list: entries of three kinds.  Buffers go by name: x0 (the image, 8 channels), out{idx} (a layer's
+# output), y{idx} (the concat buffer of a C2f / SPPF block), t{idx}.{j} (a bottleneck's hidden map), cat{idx} (the neck's concat),
+# det{s}.{b0,b1,c0,c1} (the head's feature maps) and det{s}.{box,cls} (its f32 logits).  A view is (buffer, channel offset, channels).
+class Block(NamedTuple):
+    unit: Union[int, Tuple[int, str]]   # what the block is part of: a layer index, or (head scale, "box" / "cls")
+    key: str                    # state-dict prefix
+    k: int
+    stride: int
+    bn: bool                    # True: conv -> BatchNorm -> SiLU, bf16 output; False: plain biased conv, f32 output (Detect's last layers)
+    src: tuple                  # the input view
+    out: tuple                  # the output view
+    res_off: Optional[int]      # channel offset in out's buffer of the residual added to the output, None = no residual
+    down_in: int                # the input grid is (size // down_in) x (size // down_in)
+    down: int                   # the output grid likewise
+    cin: int                    # channels as stored (padded to a multiple of 8) ...
+    cout: int
+    cin_real: int               # ... and as the state dict has them
+    cout_real: int
+    dgrad: bool                 # the input has a gradient (the stem's, the image, has none)
+
+
+class Concat(NamedTuple):
+    unit: int
+    out: str                    # the neck's concat: both sources copied side by side into `out`
+    srcs: tuple                 # two (buffer, channel offset in `out`, channels, up); up = 1: nearest-neighbour 2 x upsample of a grid half the size
+    down: int
+
+
+class Pool(NamedTuple):
+    unit: int
+    buf: str                    # SPPF: three chained 5 x 5 max-pools of channels [0, c) into the three chunks behind them
+    c: int
+    down: int
+
+
+@functools.lru_cache(maxsize=None)
+def train_launches(scale: str, nc: int = 5) -> tuple:
+    """The un-fused training network in forward order (host only): layers in yaml order, a neck C2f as concat, cv1, the bottleneck
+    pairs, cv2, SPPF as cv1, pool, cv2, then the head per scale, box branch before class branch."""
+    layers = yolo_layers(scale)
+    width = {idx: p["cout"] for idx, _, p in layers}
+    out: list = []
+
+    def block(unit, key, src, dst, k, stride, down, bn=True, res_off=None, cin_real=None, cout_real=None, dgrad=True):
+        out.append(Block(unit, key, k, stride, bn, src, dst, res_off, down // stride, down, src[2], dst[2],
+                         src[2] if cin_real is None else cin_real, dst[2] if cout_real is None else cout_real, dgrad))
+
+    for idx, kind, p in layers:
+        pre, d, o = f"model.{idx}", LAYER_STRIDE[idx], (f"out{idx}", 0, p["cout"])
+        src = (f"out{idx - 1}", 0, p.get("cin"))
+        if kind == "stem":
+            block(idx, pre, ("x0", 0, 8), o, 3, 2, d, cin_real=3, dgrad=False)
+        elif kind == "conv":
+            block(idx, pre, src, o, 3, 2, d)
+        elif kind == "c2f":
+            c, n, y = p["cout"] // 2, p["n"], f"y{idx}"
+            if "a" in p:                                # the neck: concat of two layers' outputs, one of them upsampled
+                (ia, ua), (ib, ub) = p["a"], p["b"]
+                out.append(Concat(idx, f"cat{idx}", ((f"out{ia}", 0, width[ia], ua), (f"out{ib}", width[ia], width[ib], ub)), d))
+                src = (f"cat{idx}", 0, p["cin"])
+            block(idx, pre + ".cv1", src, (y, 0, 2 * c), 1, 1, d)
+            for j in range(n):
+                at, t = (1 + j) * c, f"t{idx}.{j}"
+                block(idx, pre + f".m.{j}.cv1", (y, at, c), (t, 0, c), 3, 1, d)
+                block(idx, pre + f".m.{j}.cv2", (t, 0, c), (y, at + c, c), 3, 1, d, res_off=at if p["add"] else None)
+            block(idx, pre + ".cv2", (y, 0, (2 + n) * c), o, 1, 1, d)
+        elif kind == "sppf":
+            c_, y = p["cin"] // 2, f"y{idx}"
+            block(idx, pre + ".cv1", src, (y, 0, c_), 1, 1, d)
+            out.append(Pool(idx, y, c_, d))
+            block(idx, pre + ".cv2", (y, 0, 4 * c_), o, 1, 1, d)
+    ch, c2, c3, ncp = detect_widths(scale, nc)
+    for s, fidx in enumerate((15, 18, 21)):
+        d, f = LAYER_STRIDE[fidx], (f"out{fidx}", 0, ch[s])
+        for branch, cv, w, co, co_real in (("box", "cv2", c2, 4 * REG_MAX, 4 * REG_MAX), ("cls", "cv3", c3, ncp, nc)):
+            unit, pre, a = (s, branch), f"model.22.{cv}.{s}", f"det{s}.{branch[0]}"
+            block(unit, pre + ".0", f, (a + "0", 0, w), 3, 1, d)
+            block(unit, pre + ".1", (a + "0", 0, w), (a + "1", 0, w), 3, 1, d)
+            block(unit, pre + ".2", (a + "1", 0, w), (f"det{s}.{branch}", 0, co), 1, 1, d, bn=False, cout_real=co_real)
+    return tuple(out)
+
+
+@functools.lru_cache(maxsize=None)
+def train_backward_order(scale: str, nc: int = 5) -> tuple:
+    """The entries of train_launches in the order backward() walks them, as groups: the weight gradients of a group's blocks are
+    flushed to the side stream behind it.  A unit's entries run back to front (a block's residual gradient is added right behind
+    the block, _bwd), and so do the layers, one group each.  The head is the one place that is NOT a plain reversal: it comes
+    first, scale 0, 1, 2, one group per scale, in it the box branch back to front, then the class branch.
+    The order is part of the result, not a matter of taste: activation gradients accumulate in bf16 into shared slices, so the
+    order of the accumulations decides the bits, and the flush points decide what the weight gradients overlap."""
+    units = [tuple(g)[::-1] for _, g in itertools.groupby(train_launches(scale, nc), key=lambda e: e.unit)]
+    head = [u for u in units if isinstance(u[0].unit, tuple)]
+    scales = [sum(g, ()) for _, g in itertools.groupby(head, key=lambda u: u[0].unit[0])]
+    return tuple(scales + [u for u in reversed(units) if not isinstance(u[0].unit, tuple)])
+
+
+def _state_dict_order(launches) -> List[Block]:
+    """The blocks in the order ultralytics registers them (which the flat parameter buffer follows): forward order, except that a
+    C2f's cv2 sits in front of its bottlenecks."""
+    blocks = [e for e in launches if isinstance(e, Block)]
+    return [e for _, unit in itertools.groupby(blocks, key=lambda e: e.unit) for e in sorted(unit, key=lambda e: ".m." in e.key)]
+
+
+def _activations(launches) -> List[Tuple[str, int, int]]:
+    """(name, grid divisor, channels) of every bf16 activation of the list, in the order the trainer allocates them (which the
+    offsets of the gradients in their one allocation follow): unit by unit, in a layer x0, out, y, t.j, cat, in the head as used."""
+    dims: Dict[str, list] = {}                          # buffer: [unit that uses it first, grid divisor, channels]
+    for e in launches:
+        if isinstance(e, Block):
+            uses = [(e.src[0], e.src[1] + e.src[2], e.down_in)] + [(e.out[0], e.out[1] + e.out[2], e.down)] * e.bn
+        elif isinstance(e, Concat):
+            uses = [(e.out, sum(c for _, _, c, _ in e.srcs), e.down)]
+        else:
+            uses = [(e.buf, 4 * e.c, e.down)]
+        for buf, c, down in uses:
+            d = dims.setdefault(buf, [e.unit, down, 0])
+            d[2] = max(d[2], c)
+    rank = lambda name: ("x", "out", "y", "t", "cat", "det").index(re.match("[a-z]+", name).group())
+    return [(name, d, c) for _, unit in itertools.groupby(dims.items(), key=lambda kv: kv[1][0])
+            for name, (_, d, c) in sorted(unit, key=lambda kv: rank(kv[0]))]
 
 
 def init_yolo_train_state(scale: str = "n", nc: int = 5, seed: int = 42) -> Dict[str, torch.Tensor]:
@@ -63,32 +192,29 @@ def yolo_wgrad_shapes(scale: str, nc: int, size: int = 640, batch: int = 16,
     channels padded to 8, T to 64.  pitch > 0: a 3x3 / stride 1 layer on the zero-padded pixel grid of that row pitch
     (wgrad_conv3; `implicit`), 0: wgrad on the activation (1x1) or on its im2col."""
     out = []
-    for key, cin, cout, k in yolo_conv_keys(scale, nc):
-        parts = key.split(".")
-        idx = int(parts[1])
-        h = size // ((8, 16, 32)[int(parts[3])] if idx == 22 else LAYER_STRIDE[idx])
-        s1 = k == 3 and not (idx != 22 and len(parts) == 3)      # "model.<i>.conv": the stem and the stride-2 convolutions
-        pitch = h + 2 if s1 and implicit else 0
-        out.append((key, _r64(batch * pitch * pitch if pitch else batch * h * h), (cout + 7) // 8 * 8, k * k * ((cin + 7) // 8 * 8), pitch))
+    for e in _state_dict_order(train_launches(scale, nc)):
+        h = size // e.down
+        pitch = h + 2 if e.k == 3 and e.stride == 1 and implicit else 0
+        out.append((e.key + (".conv" if e.bn else ""), _r64(batch * pitch * pitch if pitch else batch * h * h), e.cout,
+                    e.k * e.k * e.cin, pitch))
     return out
 
 
 def yolo_s2_dgrad_shapes(scale: str, size: int = 640) -> List[Tuple[str, int, int, int]]:
     """(key, Hin, Cin, Cout) of every stride-2 convolution of a YoloTrainer step that has a data gradient (host only): model.1, 3,
     5, 7, 16, 19 - the stem's input is the image."""
-    return [(f"model.{idx}", 2 * (size // LAYER_STRIDE[idx]), p["cin"], p["cout"])
-            for idx, kind, p in yolo_layers(scale) if kind == "conv"]
+    return [(e.key, 2 * (size // e.down), e.cin, e.cout)
+            for e in train_launches(scale) if isinstance(e, Block) and e.stride == 2 and e.dgrad]
 
 
 class _Act:
     """(B,H,W,C) bf16 activation + its gradient, stored as (rows padded to 64, C)."""
 
-    def __init__(self, tr: "YoloTrainer", B: int, H: int, W: int, Cn: int):
+    def __init__(self, dev: torch.device, B: int, H: int, W: int, Cn: int):
         self.B, self.H, self.W, self.C = B, H, W, Cn
         self.T = B * H * W
-        self.buf = torch.zeros((_r64(self.T), Cn), dtype=torch.bfloat16, device=tr.dev)
-        tr._grad_specs.append(self)
-        self.grad: Optional[torch.Tensor] = None
+        self.buf = torch.zeros((_r64(self.T), Cn), dtype=torch.bfloat16, device=dev)
+        self.grad: Optional[torch.Tensor] = None            # a slice of the trainer's one gradient allocation
 
     def v(self, off: int = 0, c: Optional[int] = None):
         return mview(self.buf, off, self.C - off if c is None else c)
@@ -100,19 +226,37 @@ class _Act:
 class _Block:
     """One Conv(+BN+SiLU) (bn=True) or plain biased conv (Detect's last layers)."""
 
-    def __init__(self, tr: "YoloTrainer", key: str, cin: int, cout: int, k: int, s: int, bn: bool = True,
-                 cin_real: Optional[int] = None, cout_real: Optional[int] = None):
-        self.key, self.cin, self.cout, self.k, self.s, self.bn = key, cin, cout, k, s, bn
-        self.cin_real = cin if cin_real is None else cin_real
-        self.cout_real = cout if cout_real is None else cout_real
-        self.taps = k * k
-        self.w = tr._param(key + (".conv.weight" if bn else ".weight"), cout * self.taps * cin, "w")
-        if bn:                                   # ultralytics groups: conv weights (decay) / BatchNorm weights / all biases
-            self.gamma = tr._param(key + ".bn.weight", cout, "bnw")
-            self.beta = tr._param(key + ".bn.bias", cout, "bias")
+    def __init__(self, tr: "YoloTrainer", e: Block):
+        self.e, self.key, self.cin, self.cout, self.k, self.s, self.bn = e, e.key, e.cin, e.cout, e.k, e.stride, e.bn
+        self.cin_real, self.cout_real, self.taps = e.cin_real, e.cout_real, e.k * e.k
+        self.w = tr._param(e.key + (".conv.weight" if e.bn else ".weight"), e.cout * self.taps * e.cin, "w")
+        if e.bn:                                 # ultralytics groups: conv weights (decay) / BatchNorm weights / all biases
+            self.gamma = tr._param(e.key + ".bn.weight", e.cout, "bnw")
+            self.beta = tr._param(e.key + ".bn.bias", e.cout, "bias")
         else:
-            self.bias = tr._param(key + ".bias", cout, "bias")
-        tr.blocks.append(self)
+            self.bias = tr._param(e.key + ".bias", e.cout, "bias")
+
+    def bind(self, tr: "YoloTrainer"):
+        """The operands the entry names, resolved once: x / dx the input view and its gradient (None: no data gradient), x_buf,
+        x_off the input rows as the weight gradient takes them, y / dy the output view and its gradient (a plain block: the f32
+        logits and the loss kernel's gradient of them), res / dres the residual view and its gradient; and the block's own slices
+        of the flat buffers (every allocation lives as long as the trainer), so that a step slices nothing again."""
+        e, key, src = self.e, self.key, tr.act[self.e.src[0]]
+        self.w16, self.dw, self.dzv = tr.w16(self), tr.gr(self.w).view(self.cout, self.taps * self.cin), mview(tr.dz[key])
+        self.x_buf, self.x_off = src.buf, e.src[1]
+        self.x, self.dx = src.v(*e.src[1:]), src.g(*e.src[1:]) if e.dgrad else None
+        self.res = self.dres = None
+        if e.bn:
+            dst, self.zv = tr.act[e.out[0]], mview(tr.z[key])
+            self.stat, self.run = (tr.mean[key], tr.rstd[key]), (tr.run_mean[key], tr.run_var[key])
+            self.affine, self.daffine = (tr.p(self.gamma), tr.p(self.beta)), (tr.gr(self.gamma), tr.gr(self.beta))
+            self.y, self.dy = dst.v(*e.out[1:]), dst.g(*e.out[1:])
+            if e.res_off is not None:
+                self.res, self.dres = dst.v(e.res_off, e.out[2]), dst.g(e.res_off, e.out[2])
+        else:
+            s, branch = e.unit
+            self.bias_p, self.dbias = tr.p(self.bias), tr.gr(self.bias)
+            self.y, self.dy = mview(tr.det_out[e.out[0]]), tr.det_out[f"det{s}.d{branch}"]
 
 
 class YoloTrainer:
@@ -142,10 +286,11 @@ class YoloTrainer:
             raise YvError("optimizer must be 'sgd', 'sgd_nesterov' or 'adamw'")
         self.optimizer, self.use_ema, self.ema_decay, self.ema_tau = optimizer, ema, ema_decay, ema_tau
         self.ncp = (nc + 7) // 8 * 8
-        self.blocks: List[_Block] = []
         self._pspecs: List[Tuple[str, int, str]] = []
-        self._grad_specs: List[_Act] = []
-        self._build_graph()
+        self.layers = yolo_layers(scale)
+        self.launches, self._backward_order = train_launches(scale, nc), train_backward_order(scale, nc)
+        self.blocks: List[_Block] = [_Block(self, e) for e in _state_dict_order(self.launches)]
+        self.block: Dict[str, _Block] = {b.key: b for b in self.blocks}
         self._alloc_params(state)
         self._alloc_buffers()
         self.step_count = 0
@@ -229,121 +374,55 @@ class YoloTrainer:
 
     def state_dict(self, ema: bool = False) -> Dict[str, torch.Tensor]:
         """Un-fused ultralytics key layout, fp32, on the host; ema=True returns the ModelEMA copy (what ultralytics saves)."""
-        sd: Dict[str, torch.Tensor] = {}
         if ema and not self.use_ema:
             raise YvError("trainer was built without ema=True")
-        P = (self.P_ema if ema else self.P).cpu()
-        RS = (self.RS_ema if ema else self.RS).cpu()
-        for b in self.blocks:
-            o, n = self.off[b.w]
-            w = P[o:o + n].view(b.cout, b.k, b.k, b.cin)[:b.cout_real, :, :, :b.cin_real].permute(0, 3, 1, 2).contiguous()
-            if b.bn:
-                sd[b.key + ".conv.weight"] = w
-                for pid, suffix in ((b.gamma, ".bn.weight"), (b.beta, ".bn.bias")):
-                    o2, n2 = self.off[pid]
-                    sd[b.key + suffix] = P[o2:o2 + n2].clone()
-                ro = self._rs_off[b.key]
-                sd[b.key + ".bn.running_mean"] = RS[ro:ro + b.cout].clone()
-                sd[b.key + ".bn.running_var"] = RS[ro + b.cout:ro + 2 * b.cout].clone()
-            else:
-                sd[b.key + ".weight"] = w
-                o2, _ = self.off[b.bias]
-                sd[b.key + ".bias"] = P[o2:o2 + b.cout_real].clone()
-        return sd
+        return self._unpack((self.P_ema if ema else self.P).cpu(), (self.RS_ema if ema else self.RS).cpu())
 
     def grads(self) -> Dict[str, torch.Tensor]:
         """Gradients in the layout of state_dict() (tests)."""
+        return self._unpack(self.G.cpu())
+
+    def _unpack(self, flat: torch.Tensor, rs: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+        """A host copy of a flat buffer in P's layout (and of the running statistics) under the un-fused ultralytics keys."""
         sd: Dict[str, torch.Tensor] = {}
-        G = self.G.cpu()
         for b in self.blocks:
             o, n = self.off[b.w]
-            w = G[o:o + n].view(b.cout, b.k, b.k, b.cin)[:b.cout_real, :, :, :b.cin_real].permute(0, 3, 1, 2).contiguous()
+            w = flat[o:o + n].view(b.cout, b.k, b.k, b.cin)[:b.cout_real, :, :, :b.cin_real].permute(0, 3, 1, 2).contiguous()
             if b.bn:
                 sd[b.key + ".conv.weight"] = w
                 for pid, suffix in ((b.gamma, ".bn.weight"), (b.beta, ".bn.bias")):
                     o2, n2 = self.off[pid]
-                    sd[b.key + suffix] = G[o2:o2 + n2].clone()
+                    sd[b.key + suffix] = flat[o2:o2 + n2].clone()
+                if rs is not None:
+                    ro = self._rs_off[b.key]
+                    sd[b.key + ".bn.running_mean"] = rs[ro:ro + b.cout].clone()
+                    sd[b.key + ".bn.running_var"] = rs[ro + b.cout:ro + 2 * b.cout].clone()
             else:
                 sd[b.key + ".weight"] = w
                 o2, _ = self.off[b.bias]
-                sd[b.key + ".bias"] = G[o2:o2 + b.cout_real].clone()
+                sd[b.key + ".bias"] = flat[o2:o2 + b.cout_real].clone()
         return sd
 
-    # ------------------------------------------------------------------ graph
-    def _build_graph(self):
-        sc, nc = self.scale, self.nc
-        self.layers = yolo_layers(sc)
-        self.mod: Dict[int, dict] = {}
-        for idx, kind, p in self.layers:
-            pre = f"model.{idx}"
-            if kind == "stem":
-                self.mod[idx] = dict(kind="conv", blk=_Block(self, pre, 8, p["cout"], 3, 2, cin_real=3))
-            elif kind == "conv":
-                self.mod[idx] = dict(kind="conv", blk=_Block(self, pre, p["cin"], p["cout"], 3, 2))
-            elif kind == "c2f":
-                c = p["cout"] // 2
-                m = dict(kind="c2f", c=c, n=p["n"], add=p["add"], p=p,
-                         cv1=_Block(self, pre + ".cv1", p["cin"], 2 * c, 1, 1),
-                         cv2=_Block(self, pre + ".cv2", (2 + p["n"]) * c, p["cout"], 1, 1), m=[])
-                for j in range(p["n"]):
-                    m["m"].append((_Block(self, pre + f".m.{j}.cv1", c, c, 3, 1), _Block(self, pre + f".m.{j}.cv2", c, c, 3, 1)))
-                self.mod[idx] = m
-            elif kind == "sppf":
-                self.mod[idx] = dict(kind="sppf", c_=p["cin"] // 2, cv1=_Block(self, pre + ".cv1", p["cin"], p["cin"] // 2, 1, 1),
-                                     cv2=_Block(self, pre + ".cv2", p["cin"] * 2, p["cout"], 1, 1))
-        ch, self.c2, self.c3, _ = detect_widths(sc, nc)
-        self.det = []
-        for s, ci in enumerate(ch):
-            pre = f"model.22"
-            self.det.append(dict(
-                b0=_Block(self, f"{pre}.cv2.{s}.0", ci, self.c2, 3, 1), b1=_Block(self, f"{pre}.cv2.{s}.1", self.c2, self.c2, 3, 1),
-                b2=_Block(self, f"{pre}.cv2.{s}.2", self.c2, 4 * REG_MAX, 1, 1, bn=False),
-                c0=_Block(self, f"{pre}.cv3.{s}.0", ci, self.c3, 3, 1), c1=_Block(self, f"{pre}.cv3.{s}.1", self.c3, self.c3, 3, 1),
-                c2=_Block(self, f"{pre}.cv3.{s}.2", self.c3, self.ncp, 1, 1, bn=False, cout_real=nc)))
-
+    # ------------------------------------------------------------------ buffers
     def _alloc_buffers(self):
         B, S, dev = self.B, self.size, self.dev
-        A = lambda h, c: _Act(self, B, h, h, c)
-        self.x0 = A(S, 8)
-        self.out: Dict[int, _Act] = {}
-        self.aux: Dict[int, dict] = {}
-        for idx, kind, p in self.layers:
-            h = S // LAYER_STRIDE[idx]
-            self.out[idx] = A(h, p["cout"])
-            if kind == "c2f":
-                c, n = p["cout"] // 2, p["n"]
-                a = dict(y=A(h, (2 + n) * c), t=[A(h, c) for _ in range(n)])
-                if "a" in p:
-                    a["cat"] = A(h, p["cin"])
-                self.aux[idx] = a
-            elif kind == "sppf":
-                self.aux[idx] = dict(y=A(h, p["cin"] * 2))
-        self.det_act = []
-        self.det_out = []
-        for s, st in enumerate((8, 16, 32)):
-            h = S // st
-            self.det_act.append(dict(b0=A(h, self.c2), b1=A(h, self.c2), c0=A(h, self.c3), c1=A(h, self.c3)))
-            T = B * h * h
-            self.det_out.append(dict(box=torch.zeros((T, 4 * REG_MAX), device=dev), cls=torch.zeros((T, self.ncp), device=dev),
-                                     dbox=torch.zeros((T, 4 * REG_MAX), device=dev), dcls=torch.zeros((T, self.ncp), device=dev)))
+        self.act: Dict[str, _Act] = {name: _Act(dev, B, S // down, S // down, c) for name, down, c in _activations(self.launches)}
+        self.x0, self.out = self.act["x0"], {idx: self.act[f"out{idx}"] for idx, _, _ in self.layers}
         # one allocation for every activation gradient (zeroed once per step)
-        total = sum(a.buf.numel() for a in self._grad_specs)
+        total = sum(a.buf.numel() for a in self.act.values())
         self.grad_flat = torch.zeros(total, dtype=torch.bfloat16, device=dev)
         pos = 0
-        for a in self._grad_specs:
+        for a in self.act.values():
             n = a.buf.numel()
             a.grad = self.grad_flat[pos:pos + n].view(a.buf.shape)
             pos += n
-        # per-block pre-activation, its gradient and the batch statistics
-        self.z: Dict[str, torch.Tensor] = {}
-        self.dz: Dict[str, torch.Tensor] = {}
-        self.mean: Dict[str, torch.Tensor] = {}
-        self.rstd: Dict[str, torch.Tensor] = {}
-        self.geom: Dict[str, Tuple[int, int]] = {}
+        self.det_out: Dict[str, torch.Tensor] = {}                # the head's f32 logits and the loss kernel's gradient of them
+        self.z, self.dz, self.mean, self.rstd = {}, {}, {}, {}   # by block key: pre-activation, its gradient, the batch statistics
+        self.geom: Dict[str, Tuple[int, int]] = {}                # by block key: (input grid, output grid)
         ws_f, wd_n, col_n, zi_n, xp_n, dzp_n = 0, 0, 0, 0, 0, 0
-        for b, (hin, hout) in self._block_geometry():
+        for b in self.blocks:
+            hin, hout = self.geom[b.key] = S // b.e.down_in, S // b.e.down
             T = B * hout * hout
-            self.geom[b.key] = (hin, hout)
             if b.bn:
                 self.z[b.key] = torch.zeros((_r64(T), b.cout), dtype=torch.bfloat16, device=dev)
                 self.mean[b.key] = torch.zeros(b.cout, device=dev)
@@ -352,6 +431,9 @@ class YoloTrainer:
                 if self.fused_bn_stats:
                     ws_f = max(ws_f, conv_stats_ws_floats(T, b.cout))
             else:
+                s, branch = b.e.unit
+                for name in (branch, "d" + branch):                # det{s}.box / .cls, det{s}.dbox / .dcls
+                    self.det_out[f"det{s}.{name}"] = torch.zeros((T, b.cout), device=dev)
                 ws_f = max(ws_f, colsum_ws_floats(T, b.cout))
             self.dz[b.key] = torch.zeros((_r64(T), b.cout), dtype=torch.bfloat16, device=dev)
             wd_n = max(wd_n, b.cout * b.taps * b.cin)
@@ -372,6 +454,8 @@ class YoloTrainer:
         self.zi = torch.zeros(max(zi_n, 8), dtype=torch.bfloat16, device=dev)
         self.xp = torch.zeros(max(xp_n, 8), dtype=torch.bfloat16, device=dev)       # zero-initialised: its margins are read
         self.dzp = torch.zeros(max(dzp_n, 8), dtype=torch.bfloat16, device=dev)
+        for b in self.blocks:
+            b.bind(self)
 
     def _phase_eligible(self, b: _Block, hin: int) -> bool:
         """The route's answer for this block's data gradient (asked once, at construction): eligible and not measured slower."""
@@ -380,78 +464,55 @@ class YoloTrainer:
         except YvError:
             return False
 
-    def _block_geometry(self):
-        S = self.size
-        for idx, kind, p in self.layers:
-            h = S // LAYER_STRIDE[idx]
-            m = self.mod[idx]
-            if m["kind"] == "conv":
-                yield m["blk"], (h * 2, h)
-            elif m["kind"] == "c2f":
-                yield m["cv1"], (h, h)
-                yield m["cv2"], (h, h)
-                for b1, b2 in m["m"]:
-                    yield b1, (h, h)
-                    yield b2, (h, h)
-            else:
-                yield m["cv1"], (h, h)
-                yield m["cv2"], (h, h)
-        for s, st in enumerate((8, 16, 32)):
-            h = S // st
-            for b in self.det[s].values():
-                yield b, (h, h)
-
     # ------------------------------------------------------------------ one block, forward / backward
-    def _fwd(self, b: _Block, x, out, res=None):
-        """x: input view (B,Hin,Hin,cin); out / res: views on the output grid."""
-        hin, hout = self.geom[b.key]
+    def _fwd(self, b: _Block):
+        hout = self.geom[b.key][1]
+        if not b.bn:                                            # Detect's last 1 x 1: biased, f32 logits
+            conv_view(b.x, self.B, hout, hout, b.k, b.s, b.w16, b.cout, b.y, bias=b.bias_p, out_f32=True)
+            return
         T = self.B * hout * hout
-        z = mview(self.z[b.key])
         if self.fused_bn_stats:
-            conv_view_stats(x, self.B, hout, hout, b.k, b.s, self.w16(b), b.cout, z, self.ws)
-            bn_stats_finish(self.ws, T, self.mean[b.key], self.rstd[b.key], self.run_mean[b.key], self.run_var[b.key], BN_EPS,
-                            BN_MOMENTUM)
+            conv_view_stats(b.x, self.B, hout, hout, b.k, b.s, b.w16, b.cout, b.zv, self.ws)
+            bn_stats_finish(self.ws, T, *b.stat, *b.run, BN_EPS, BN_MOMENTUM)
         else:
-            conv_view(x, self.B, hout, hout, b.k, b.s, self.w16(b), b.cout, z)
-            bn_stats(z, T, self.mean[b.key], self.rstd[b.key], self.run_mean[b.key], self.run_var[b.key], self.ws, BN_EPS, BN_MOMENTUM)
-        bn_act_fwd(z, T, self.mean[b.key], self.rstd[b.key], self.p(b.gamma), self.p(b.beta), out, res=res)
+            conv_view(b.x, self.B, hout, hout, b.k, b.s, b.w16, b.cout, b.zv)
+            bn_stats(b.zv, T, *b.stat, *b.run, self.ws, BN_EPS, BN_MOMENTUM)
+        bn_act_fwd(b.zv, T, *b.stat, *b.affine, b.y, res=b.res)
 
-    def _bwd(self, b: _Block, da, x_buf: torch.Tensor, x_off: int, dx=None):
-        """da: gradient view of the block's output; x_buf[:, x_off:x_off+cin]: its input rows; dx: gradient view of
-        the input (accumulated) or None."""
+    def _bwd(self, b: _Block, da=None):
+        """From the gradient of the block's output (b.dy; da: a caller's gradient of a plain block's logits in its place) to the
+        block's parameter gradients and, accumulated, the gradients of its input (b.dx) and of its residual (b.dres)."""
         hin, hout = self.geom[b.key]
         T = self.B * hout * hout
-        Tp = _r64(T)
-        dz = self.dz[b.key]
         if b.bn:
-            bn_act_bwd(da, mview(self.z[b.key]), T, self.mean[b.key], self.rstd[b.key], self.p(b.gamma), self.p(b.beta),
-                       self.gr(b.gamma), self.gr(b.beta), mview(dz), self.ws)
-        else:                                                   # da is the f32 loss gradient (T, cout): cast + bias gradient
-            cast_colsum(da, dz, self.gr(b.bias), self.ws)
+            bn_act_bwd(b.dy, b.zv, T, *b.stat, *b.affine, *b.daffine, b.dzv, self.ws)
+        else:                                                   # the f32 loss gradient (T, cout): cast + bias gradient
+            cast_colsum(b.dy if da is None else da, self.dz[b.key], b.dbias, self.ws)
         if self.overlap_wgrad:
-            self._pending.append((b, x_buf, x_off))             # weight gradients run on the side stream (_flush_wgrads)
+            self._pending.append((b, b.x_buf, b.x_off))         # weight gradients run on the side stream (_flush_wgrads)
         else:
-            self._wgrad_block(b, x_buf, x_off)
-        if dx is not None:
+            self._wgrad_block(b, b.x_buf, b.x_off)
+        if b.dx is not None:
             wd = self.wd_buf[:b.cin * b.taps * b.cout]
-            conv_weight_dgrad(self.w16(b), b.cout, b.taps, b.cin, wd)
+            conv_weight_dgrad(b.w16, b.cout, b.taps, b.cin, wd)
             if b.key in self._phase_blocks:
-                conv_dgrad_s2(mview(dz), self.B, hout, hout, wd, b.cin, b.cout, dx, res=dx)
-                return
-            if b.s == 1:
-                src = mview(dz)
+                conv_dgrad_s2(b.dzv, self.B, hout, hout, wd, b.cin, b.cout, b.dx, res=b.dx)
             else:
-                zi = self.zi[:self.B * hin * hin * b.cout].view(self.B * hin * hin, b.cout)
-                view_op(VIEW_ZERO_INSERT, mview(dz), mview(zi), self.B, hout, hout)
-                src = mview(zi)
-            conv_view(src, self.B, hin, hin, b.k, 1, wd.view(b.cin, b.taps * b.cout), b.cin, dx, res=dx)
+                if b.s == 1:
+                    src = b.dzv
+                else:
+                    zi = self.zi[:self.B * hin * hin * b.cout].view(self.B * hin * hin, b.cout)
+                    view_op(VIEW_ZERO_INSERT, b.dzv, mview(zi), self.B, hout, hout)
+                    src = mview(zi)
+                conv_view(src, self.B, hin, hin, b.k, 1, wd.view(b.cin, b.taps * b.cout), b.cin, b.dx, res=b.dx)
+        if b.dres is not None:                                  # behind the block, in front of the one that wrote the residual
+            view_op(VIEW_ADD, b.dy, b.dres, self.B, hout, hout)
 
     def _wgrad_block(self, b: _Block, x_buf: torch.Tensor, x_off: int):
         hin, hout = self.geom[b.key]
         T = self.B * hout * hout
         Tp = _r64(T)
-        dz = self.dz[b.key]
-        dw = self.gr(b.w).view(b.cout, b.taps * b.cin)
+        dz, dw = self.dz[b.key], b.dw
         if b.k == 1:
             wgrad(dz, x_buf[:, x_off:x_off + b.cin], dw, T=Tp, tile_n=self._wgrad_tile)
         elif b.s == 1 and self.implicit_wgrad:
@@ -463,7 +524,7 @@ class YoloTrainer:
             xp = self.xp[mg * b.cin:(mg + tpp) * b.cin].view(tpp, b.cin)
             view_op(VIEW_PAD, mview(x_buf, x_off, b.cin), mview(xp), self.B, hin, hin)
             dzp = self.dzp[:tpp * b.cout].view(tpp, b.cout)
-            view_op(VIEW_PAD, mview(dz), mview(dzp), self.B, hout, hout)
+            view_op(VIEW_PAD, b.dzv, mview(dzp), self.B, hout, hout)
             if tpp != tpad:
                 dzp[tpad:].zero_()
             wgrad_conv3(dzp, xp, dw, tpp, hp, tile_n=self._wgrad_tile)
@@ -498,101 +559,36 @@ class YoloTrainer:
         if images.dtype != torch.uint8 or tuple(images.shape) != (B, S, S, 3) or not images.is_cuda:
             raise YvError(f"images must be ({B},{S},{S},3) uint8 on the device")
         blob_nhwc8(images.contiguous(), self.x0.buf)
-        o = self.out
-        for idx, kind, p in self.layers:
-            m = self.mod[idx]
-            if m["kind"] == "conv":
-                src = self.x0 if idx == 0 else o[idx - 1]
-                self._fwd(m["blk"], src.v(), o[idx].v())
-            elif m["kind"] == "c2f":
-                a = self.aux[idx]
-                if "a" in p:
-                    (ia, ua), (ib, _) = p["a"], p["b"]
-                    cat, ca = a["cat"], o[ia].C
-                    if ua:
-                        view_op(VIEW_UP2, o[ia].v(), cat.v(0, ca), B, o[ia].H, o[ia].W)
-                    else:
-                        view_op(VIEW_COPY, o[ia].v(), cat.v(0, ca), B, cat.H, cat.W)
-                    view_op(VIEW_COPY, o[ib].v(), cat.v(ca, o[ib].C), B, cat.H, cat.W)
-                    xin = cat
-                else:
-                    xin = o[idx - 1]
-                y, c = a["y"], m["c"]
-                self._fwd(m["cv1"], xin.v(), y.v(0, 2 * c))
-                for j, (b1, b2) in enumerate(m["m"]):
-                    src = (1 + j) * c
-                    self._fwd(b1, y.v(src, c), a["t"][j].v())
-                    self._fwd(b2, a["t"][j].v(), y.v(src + c, c), res=y.v(src, c) if m["add"] else None)
-                self._fwd(m["cv2"], y.v(), o[idx].v())
+        for e in self.launches:
+            if isinstance(e, Block):
+                self._fwd(self.block[e.key])
+            elif isinstance(e, Concat):
+                for name, at, c, up in e.srcs:
+                    src = self.act[name]
+                    view_op(VIEW_UP2 if up else VIEW_COPY, src.v(), self.act[e.out].v(at, c), B, src.H, src.W)
             else:
-                y, c_ = self.aux[idx]["y"], m["c_"]
-                self._fwd(m["cv1"], o[idx - 1].v(), y.v(0, c_))
-                sppf_pool(y.buf[:y.T].view(B, y.H, y.W, y.C), c_)
-                self._fwd(m["cv2"], y.v(), o[idx].v())
-        res = []
-        for s, fidx in enumerate((15, 18, 21)):
-            f, d, act, do = o[fidx], self.det[s], self.det_act[s], self.det_out[s]
-            h = f.H
-            self._fwd(d["b0"], f.v(), act["b0"].v())
-            self._fwd(d["b1"], act["b0"].v(), act["b1"].v())
-            conv_view(act["b1"].v(), B, h, h, 1, 1, self.w16(d["b2"]), 4 * REG_MAX, mview(do["box"]), bias=self.p(d["b2"].bias),
-                      out_f32=True)
-            self._fwd(d["c0"], f.v(), act["c0"].v())
-            self._fwd(d["c1"], act["c0"].v(), act["c1"].v())
-            conv_view(act["c1"].v(), B, h, h, 1, 1, self.w16(d["c2"]), self.ncp, mview(do["cls"]), bias=self.p(d["c2"].bias),
-                      out_f32=True)
-            res.append((do["box"], do["cls"]))
-        return res
+                y = self.act[e.buf]
+                sppf_pool(y.buf[:y.T].view(B, y.H, y.W, y.C), e.c)
+        return [(self.det_out[f"det{s}.box"], self.det_out[f"det{s}.cls"]) for s in range(3)]
 
     # ------------------------------------------------------------------ backward
     def backward(self, dlogits=None):
         """dlogits: per scale (d box (T,64) f32, d cls (T,ncp) f32); default: the buffers the loss kernel filled."""
         B = self.B
+        da = {} if dlogits is None else {f"det{s}.{name}": t for s, pair in enumerate(dlogits) for name, t in zip(("box", "cls"), pair)}
         self.grad_flat.zero_()
-        o = self.out
-        for s, fidx in enumerate((15, 18, 21)):
-            f, d, act, do = o[fidx], self.det[s], self.det_act[s], self.det_out[s]
-            dbox, dcls = (do["dbox"], do["dcls"]) if dlogits is None else dlogits[s]
-            self._bwd(d["b2"], dbox, act["b1"].buf, 0, act["b1"].g())
-            self._bwd(d["b1"], act["b1"].g(), act["b0"].buf, 0, act["b0"].g())
-            self._bwd(d["b0"], act["b0"].g(), f.buf, 0, f.g())
-            self._bwd(d["c2"], dcls, act["c1"].buf, 0, act["c1"].g())
-            self._bwd(d["c1"], act["c1"].g(), act["c0"].buf, 0, act["c0"].g())
-            self._bwd(d["c0"], act["c0"].g(), f.buf, 0, f.g())
-            self._flush_wgrads()
-        for idx, kind, p in reversed(self.layers):
-            m = self.mod[idx]
-            if m["kind"] == "conv":
-                src = self.x0 if idx == 0 else o[idx - 1]
-                self._bwd(m["blk"], o[idx].g(), src.buf, 0, None if idx == 0 else src.g())
-            elif m["kind"] == "c2f":
-                a = self.aux[idx]
-                y, c = a["y"], m["c"]
-                xin = a["cat"] if "a" in p else o[idx - 1]
-                self._bwd(m["cv2"], o[idx].g(), y.buf, 0, y.g())
-                for j in range(m["n"] - 1, -1, -1):
-                    b1, b2 = m["m"][j]
-                    src = (1 + j) * c
-                    t = a["t"][j]
-                    self._bwd(b2, y.g(src + c, c), t.buf, 0, t.g())
-                    if m["add"]:
-                        view_op(VIEW_ADD, y.g(src + c, c), y.g(src, c), B, y.H, y.W)
-                    self._bwd(b1, t.g(), y.buf, src, y.g(src, c))
-                self._bwd(m["cv1"], y.g(0, 2 * c), xin.buf, 0, xin.g())
-                if "a" in p:
-                    (ia, ua), (ib, _) = p["a"], p["b"]
-                    cat, ca = a["cat"], o[ia].C
-                    if ua:
-                        view_op(VIEW_UP2_BWD, cat.g(0, ca), o[ia].g(), B, o[ia].H, o[ia].W)
-                    else:
-                        view_op(VIEW_ADD, cat.g(0, ca), o[ia].g(), B, cat.H, cat.W)
-                    view_op(VIEW_ADD, cat.g(ca, o[ib].C), o[ib].g(), B, cat.H, cat.W)
-            else:
-                y, c_ = self.aux[idx]["y"], m["c_"]
-                self._bwd(m["cv2"], o[idx].g(), y.buf, 0, y.g())
-                for q in (2, 1, 0):                       # p_{q+1} = maxpool(p_q)
-                    maxpool5_bwd(y.v(q * c_, c_), y.g((q + 1) * c_, c_), y.g(q * c_, c_), B, y.H, y.W)
-                self._bwd(m["cv1"], y.g(0, c_), o[idx - 1].buf, 0, o[idx - 1].g())
+        for group in self._backward_order:
+            for e in group:
+                if isinstance(e, Block):
+                    self._bwd(self.block[e.key], da.get(e.out[0]))
+                elif isinstance(e, Concat):
+                    for name, at, c, up in e.srcs:
+                        src = self.act[name]
+                        view_op(VIEW_UP2_BWD if up else VIEW_ADD, self.act[e.out].g(at, c), src.g(), B, src.H, src.W)
+                else:
+                    y, c = self.act[e.buf], e.c
+                    for q in (2, 1, 0):                       # p_{q+1} = maxpool(p_q)
+                        maxpool5_bwd(y.v(q * c, c), y.g((q + 1) * c, c), y.g(q * c, c), B, y.H, y.W)
             self._flush_wgrads()
         if self.s_w is not None:
             torch.cuda.current_stream().wait_stream(self.s_w)      # every weight gradient is in G before the caller goes on
@@ -608,9 +604,9 @@ class YoloTrainer:
         A = sum((self.size // st) ** 2 for st in (8, 16, 32))
         if G not in self._loss_ws:
             self._loss_ws[G] = torch.zeros(detect_loss_ws_bytes(B, A, G), dtype=torch.uint8, device=self.dev)
-        do = self.det_out
-        detect_loss([d["box"] for d in do], [d["cls"] for d in do], [d["dbox"] for d in do], [d["dcls"] for d in do], B,
-                    self.size, self.nc, self.ncp, gt_boxes, gt_labels, gt_counts, self.loss_out, self._loss_ws[G], gains)
+        box, cls, dbox, dcls = ([self.det_out[f"det{s}.{name}"] for s in range(3)] for name in ("box", "cls", "dbox", "dcls"))
+        detect_loss(box, cls, dbox, dcls, B, self.size, self.nc, self.ncp, gt_boxes, gt_labels, gt_counts, self.loss_out,
+                    self._loss_ws[G], gains)
         return self.loss_out
 
     def step(self, images: torch.Tensor, gt_boxes: torch.Tensor, gt_labels: torch.Tensor, gt_counts: torch.Tensor,
