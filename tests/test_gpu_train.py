@@ -83,6 +83,7 @@ def test_layernorm_bwd(yv):
 
 @pytest.mark.parametrize("R,N,H", [(2, 197, 3), (1, 50, 2), (2, 33, 1), (1, 256, 2), (1, 785, 2), (1, 257, 1), (1, 600, 1)])
 def test_attention_bwd(yv, R, N, H):
+    """Whole-tensor rel-L2 against fp32 autograd; the per-element check against fp64 is tests/test_gpu_attn_bwd_bound.py."""
     g = torch.Generator().manual_seed(R + N)
     D = H * 64
     qkv = bf(torch.randn(R * N, 3 * D, generator=g))
