@@ -11,16 +11,17 @@ The gate is |got - ref| <= GATE * B for EVERY element, GATE = 1.01, with B a fir
 only: U = 2^-8, the unit roundoff of round-to-nearest bf16 (8 significant bits), and G64 = 64 * 2^-24, an f32 dot product of 64 terms
 in any order (EPS = 2^-24 is one f32 rounding).  The 1 % is for the second-order terms (U^2 = 1.5e-5 relative).  Nothing is fitted.
 
-yv_attention_bwd (csrc/attention_bwd.hip; yv_attention_bwd_long and yv_attention_bwd_short hold the same element-wise expressions and
-casts - attention_bwd_long.hip:168-198, 306-344, attention_bwd_short.hip:165-192, 237-272 - and are bit-equal by their own tests):
-  * score argument (lines 106, 113 / 193, 200: MFMA f32 accumulation of S, the f32 lse, one multiply, one subtract, exp2f):
+yv_attention_bwd, yv_attention_bwd_long and yv_attention_bwd_short compile ONE text of the element-wise expressions, casts and MFMA
+order, csrc/attention_bwd_core.h (owner_query, to_ds, to_p_ds, dq_group, dkv_group, store_head_row; the three .hip files hold blocking
+and staging only), and are bit-equal by their own tests and tests/golden/attn_bwd_bits.json.  Lines of that header:
+  * score argument (lines 163, 136 / 191, 147: MFMA f32 accumulation of S, the f32 lse, one multiply, one subtract, exp2f):
         delta_arg = c G64 (|Q| |K|^T) + 2^-23 (|c S| + |lse| + 1)
-  * P:   E_P = U P + P delta_arg ln2.  The U term is the cast of P to bf16 before P^T dO (line 208, `fp[j] = (__bf16)sv[..]`).
-  * dS:  E_S = U |dS| + |dS| (delta_arg ln2 + 4 EPS) + P scale G64 (|dO| |V|^T + sum_d |dO O|).  U: the cast of dS to bf16 (lines 120
-         and 208, `fp[j] = (__bf16)s[..]`, `fs[j] = (__bf16)dp[..]`); 4 EPS: the subtract and the two multiplies of lines 114 / 202; the
-         last term is the f32 cancellation in dP - delta (dP: MFMA, line 107 / 194; delta: lines 80-82) and dominates where the softmax
+  * P:   E_P = U P + P delta_arg ln2.  The U term is the cast of P to bf16 before P^T dO (line 201, `fp[j] = (__bf16)sv[..]`).
+  * dS:  E_S = U |dS| + |dS| (delta_arg ln2 + 4 EPS) + P scale G64 (|dO| |V|^T + sum_d |dO O|).  U: the cast of dS to bf16 (lines 173
+         and 201, `fp[j] = (__bf16)s[..]`, `fs[j] = (__bf16)dp[..]`); 4 EPS: the subtract and the two multiplies of lines 137 / 149; the
+         last term is the f32 cancellation in dP - delta (dP: MFMA, line 164 / 192; delta: lines 112-114) and dominates where the softmax
          is peaked - without it the bound is not a bound.
-  * outputs (f32 MFMA accumulation over N keys / queries, lines 124, 212, 213, then pack_bf16x2, RNE, lines 134, 225, 227):
+  * outputs (f32 MFMA accumulation over N keys / queries, lines 176, 204, 205, then pack_bf16x2, RNE, line 217):
         B_dQ = E_S |K| + N EPS (|dS| |K|) + U |dQ|     B_dK = E_S^T |Q| + N EPS (|dS|^T |Q|) + U |dK|
         B_dV = E_P^T |dO| + N EPS (P^T |dO|) + U |dV|  B_delta = G64 sum_d |dO O|   (64 exact bf16 x bf16 products summed in f32)
 

@@ -1,5 +1,5 @@
 """The gate of attn_bwd_reference.py is neither vacuous nor too tight, shown without a GPU: a torch emulation of the arithmetic of
-csrc/attention_bwd.hip (f32, P and dS rounded to bf16 where the kernel casts them, bf16 outputs) passes it on every case of
+csrc/attention_bwd_core.h (f32, P and dS rounded to bf16 where the kernel casts them, bf16 outputs) passes it on every case of
 test_gpu_attn_bwd_bound.py, every mutant of that emulation fails it on the outputs named here, and the whole-tensor rel-L2 2e-2 gate
 of tests/test_gpu_train.py::test_attention_bwd lets the 1 % scale mutant through, and the dropped query in the dV third."""
 import pytest
@@ -14,7 +14,7 @@ def rel_l2(a, b):
 
 
 def emulate_bwd(qkv, out, dout, lse, R, N, H, mutant=None, scale=SCALE):
-    """attention_bwd.hip in torch f32: S and dP with f32 accumulation, P = exp2f(S c - lse), dS = P (dP - delta) scale, P and dS cast
+    """attention_bwd_core.h in torch f32: S and dP with f32 accumulation, P = exp2f(S c - lse), dS = P (dP - delta) scale, P and dS cast
     to bf16 before the second products (`fp[j] = (__bf16)...`), dqkv rounded to bf16.  -> (dqkv (R*N, 3D) bf16, delta (R*H*N) f32).
     mutant: one wrong line of that arithmetic (MUTANTS)."""
     q, k, v = split_qkv(qkv, R, N, H, torch.float32)
@@ -185,7 +185,7 @@ def emulate_cls_bwd(case, R, N, H, mutant=None, scale=SCALE):
     P = torch.exp2((q0 @ k.mT) * c - case["lse"].view(R, H, 1, 1))
     dP = do @ v.mT
     dS = P * (dP - (P * dP).sum(-1, keepdim=True)) * (scale * 1.01 if mutant == "scale_1pc" else scale)
-    if mutant == "p_cast_to_bf16":                                   # the operand cast of attention_bwd.hip, which this kernel does not have
+    if mutant == "p_cast_to_bf16":                                   # the operand cast of attention_bwd_core.h, which this kernel does not have
         P = bf(P).float()
     dq = torch.zeros(R, H, N, 64)
     dq[:, :, :1] = dS @ k
