@@ -449,7 +449,9 @@ int yv_linear_ex(const void* A, int lda, const void* W, const float* bias, int M
 
 /* LayerNorm over the last dim (timm blocks.*.norm1/2, norm; eps 1e-6; README.md:21-29).
  * x (rows, D) f32 with row stride ldx -> y (rows, D) bf16 row stride ldy.
- * count_dev: optional device i32; rows at run time = min(rows, count_dev[0]*rows_per_count). */
+ * count_dev: optional device i32; rows at run time = min(rows, count_dev[0]*rows_per_count).
+ * D, ldx, ldy multiples of 4; x, gamma, beta 16-byte aligned and y 8-byte aligned (YV_ERR_ARG, checked on the host before any
+ * HIP call: the kernel reads float4 and writes uint2); D <= 1024 (YV_ERR_LIMIT). */
 int yv_layernorm(const float* x, size_t ldx, const float* gamma, const float* beta, int rows, int D, float eps,
                  void* y, size_t ldy, const int32_t* count_dev, int rows_per_count, void* stream);
 
@@ -650,7 +652,10 @@ int yv_cast_colsum(const float* x, int rows, int cols, void* y_bf16, float* cols
 int yv_colsum_bf16(const void* x, int rows, int cols, long long ld, float* colsum, int accumulate, float* ws,
                    void* stream);
 
-/* LayerNorm backward: dx += dLN(dy) (f32 stream), dgamma / dbeta (D) f32; statistics recomputed from x. */
+/* LayerNorm backward: dx += dLN(dy) (f32 stream), dgamma / dbeta (D) f32; statistics recomputed from x.
+ * D, ldx, lddy, lddx multiples of 4; x, gamma, dx 16-byte aligned and dy 8-byte aligned (YV_ERR_ARG, checked on the host before
+ * any HIP call: the kernel reads float4 / uint2); D <= 1024 (YV_ERR_LIMIT).  ws: yv_layernorm_bwd_ws_floats(rows, D) floats, any
+ * 4-byte alignment (a workspace that is not 16-byte aligned takes the scalar second stage: the same sums in another order). */
 size_t yv_layernorm_bwd_ws_floats(int rows, int D);
 int yv_layernorm_bwd(const float* x, long long ldx, const float* gamma, const void* dy, long long lddy, int rows, int D,
                      float eps, float* dx, long long lddx, float* dgamma, float* dbeta, float* ws, void* stream);

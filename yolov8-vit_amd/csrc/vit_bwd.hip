@@ -187,9 +187,11 @@ __global__ __launch_bounds__(256) void reduce_rows_kernel(const float* __restric
     }
 }
 
-// columns not a multiple of 4 (small heads): one column per thread, 8 row groups
+// columns not a multiple of 4 (small heads) or a workspace that is not 16-byte aligned: one column per thread, 8 row groups;
+// out2 / split as in reduce_rows_kernel
 __global__ __launch_bounds__(256) void reduce_rows_scalar_kernel(const float* __restrict__ partial, int parts, int cols,
-                                                                 float* __restrict__ out, int accumulate) {
+                                                                 float* __restrict__ out, int accumulate,
+                                                                 float* __restrict__ out2 = nullptr, int split = 0) {
     __shared__ float red[8][32];
     const int cl = threadIdx.x & 31, grp = threadIdx.x >> 5;
     const int c = blockIdx.x * 32 + cl;
@@ -202,7 +204,8 @@ __global__ __launch_bounds__(256) void reduce_rows_scalar_kernel(const float* __
         float t = red[0][cl];
 #pragma unroll
         for (int q = 1; q < 8; ++q) t += red[q][cl];
-        out[c] = accumulate ? out[c] + t : t;
+        float* o = (out2 && c >= split) ? out2 + (c - split) : out + c;             // [0, split) -> out, [split, cols) -> out2
+        *o = accumulate ? *o + t : t;
     }
 }
 
@@ -213,7 +216,7 @@ void launch_reduce_rows(hipStream_t st, const float* partial, int parts, int col
                            split);
     else
         hipLaunchKernelGGL(reduce_rows_scalar_kernel, dim3((cols + 31) / 32), dim3(256), 0, st, partial, parts, cols, out,
-                           accumulate);
+                           accumulate, out2, split);
 }
 
 // ---------------------------------------------------------------------------------------- LayerNorm backward
@@ -451,6 +454,7 @@ extern "C" int yv_layernorm_bwd(const float* x, long long ldx, const float* gamm
                                 float* ws, void* stream) {
     if (!x || !gamma || !dy || !dx || !dgamma || !dbeta || !ws || rows <= 0 || D <= 0) return YV_ERR_ARG;
     if ((D & 3) || (ldx & 3) || (lddy & 3) || (lddx & 3)) return YV_ERR_ARG;
+    if ((((uintptr_t)x | (uintptr_t)gamma | (uintptr_t)dx) & 15) || ((uintptr_t)dy & 7)) return YV_ERR_ARG;   // float4 / uint2 accesses
     if (D > LNB_MAXC * 256) return YV_ERR_LIMIT;
     const int blocks = (rows + LNB_ROWS - 1) / LNB_ROWS;
     hipStream_t st = (hipStream_t)stream;

@@ -217,6 +217,7 @@ extern "C" int yv_layernorm(const float* x, size_t ldx, const float* gamma, cons
                             void* stream) {
     if (!x || !gamma || !beta || !y || rows < 0 || D <= 0) return YV_ERR_ARG;
     if ((D & 3) || (ldx & 3) || (ldy & 3)) return YV_ERR_ARG;
+    if ((((uintptr_t)x | (uintptr_t)gamma | (uintptr_t)beta) & 15) || ((uintptr_t)y & 7)) return YV_ERR_ARG;  // float4 / uint2 accesses
     if (D > LN_MAXC * 256) return YV_ERR_LIMIT;
     if (rows == 0) return YV_OK;
     hipLaunchKernelGGL(layernorm_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, x, ldx, gamma, beta,
