@@ -703,7 +703,8 @@ int yv_ema_update(float* ema, const float* src, size_t n, float decay, void* str
 
 /* ---- detector training (the ultralytics trainer behind utils/trainYolo.py:13-35) --------
  * Conv = conv(no bias) -> BatchNorm2d(eps 1e-3, momentum 0.03) -> SiLU, un-folded; activations are NHWC bf16 views:
- * (rows = B*H*W, C) with a row stride `ld` (elements), C a multiple of 8, pointers 16-byte aligned. */
+ * (rows = B*H*W, C) with a row stride `ld` (elements, a multiple of 8, at least C), C a multiple of 8, pointers 16-byte
+ * aligned; anything else is YV_ERR_ARG. */
 
 /* u8 RGB pixels -> bf16 value/255, channels padded 3 -> 8 with zeros (`blob`, YOLOTensorRT_yolodet_py_解读.md:70-74). */
 int yv_blob_nhwc8(const void* images_u8, long long pixels, void* out_bf16, void* stream);

@@ -496,7 +496,7 @@ extern "C" int yv_bn_act_fwd(const void* z, long long ldz, long long T, int C, c
                              const float* gamma, const float* beta, const void* res, long long ldres, void* out,
                              long long ldo, int act, void* stream) {
     if (!z || !out || !mean || !rstd || !gamma || !beta || !bn_shape_ok(T, C, ldz) || (ldo & 7) || ldo < C) return YV_ERR_ARG;
-    if (res && ((ldres & 7) || ((uintptr_t)res & 15))) return YV_ERR_ARG;
+    if (res && ((ldres & 7) || ldres < C || ((uintptr_t)res & 15))) return YV_ERR_ARG;
     if (((uintptr_t)z | (uintptr_t)out) & 15) return YV_ERR_ARG;
     ActArgs a = {};
     a.z = (const uint16_t*)z; a.ldz = ldz; a.res = (const uint16_t*)res; a.ldres = ldres; a.out = (uint16_t*)out; a.ldo = ldo;
@@ -549,6 +549,7 @@ extern "C" int yv_maxpool5_bwd(const void* x, long long ldx, const void* dout, l
                                int H, int W, int C, void* ws, size_t ws_bytes, void* stream) {
     if (!x || !dout || !din || !ws || B <= 0 || H <= 0 || W <= 0 || C < 8 || (C & 7)) return YV_ERR_ARG;
     if ((ldx & 7) || (lddo & 7) || (lddi & 7) || (((uintptr_t)x | (uintptr_t)dout | (uintptr_t)din | (uintptr_t)ws) & 15)) return YV_ERR_ARG;
+    if (ldx < C || lddo < C || lddi < C) return YV_ERR_ARG;
     if (ws_bytes < (size_t)B * H * W * C) return YV_ERR_WORKSPACE;
     const unsigned blocks = blocks_for((long long)B * H * W * (C >> 3));
     hipLaunchKernelGGL(maxpool5_argmax_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)x, ldx, B, H, W, C,
@@ -559,7 +560,7 @@ extern "C" int yv_maxpool5_bwd(const void* x, long long ldx, const void* dout, l
 }
 
 extern "C" int yv_im2col3(const void* x, long long ldx, int B, int Hin, int Win, int C, int stride, void* col, void* stream) {
-    if (!x || !col || B <= 0 || Hin <= 0 || Win <= 0 || C < 8 || (C & 7) || (ldx & 7) || !(stride == 1 || stride == 2))
+    if (!x || !col || B <= 0 || Hin <= 0 || Win <= 0 || C < 8 || (C & 7) || (ldx & 7) || ldx < C || !(stride == 1 || stride == 2))
         return YV_ERR_ARG;
     if (((uintptr_t)x | (uintptr_t)col) & 15) return YV_ERR_ARG;
     const int Hout = (Hin - 1) / stride + 1, Wout = (Win - 1) / stride + 1;       // k 3, pad 1
