@@ -638,6 +638,26 @@ int yv_wgrad_conv3(const void* dYp, int ldy, const void* Xp, int Cin, int pitch,
 int yv_wgrad_conv3_tiled(const void* dYp, int ldy, const void* Xp, int Cin, int pitch, int T, int N, float* dW, int ldw,
                          int tile_n, void* stream);
 
+/* Weight gradient of a 3x3 / pad 1 convolution of stride 1 or 2 with no operand copy: dW (N, 9*Cin) f32, column
+ * (ky*3 + kx)*Cin + ci, equal bit for bit to yv_im2col3 + yv_wgrad_tiled on the same operands (the same route, hence the same
+ * token slices).  X is the convolution's input (B, Hin, Win, Cin) bf16 as any view with row stride ldx >= Cin (a multiple of 8),
+ * read in place: the kernel computes each tap's source pixel itself, and a tap in the padding reads a zero chunk the library
+ * owns.  The output grid is Hout = (Hin - 1) / stride + 1, Wout likewise (odd grids allowed), as in yv_im2col3.  dY (r64(T), N)
+ * bf16, T = B * Hout * Wout, r64 = rounded up to a multiple of 64, its tail rows ZERO, row stride ldy >= N (a multiple of 8).
+ * Cin and N multiples of 8, ldw >= 9*Cin a multiple of 4, bases 16-byte aligned, T <= 2^31 - 64, tile_n as yv_wgrad_tiled takes
+ * it; anything else: YV_ERR_ARG, nothing launched. */
+int yv_wgrad_conv3_gather(const void* dY, int ldy, const void* X, long long ldx, int B, int Hin, int Win, int stride, int Cin, int N,
+                          float* dW, int ldw, int tile_n, void* stream);
+/* The route of yv_wgrad_conv3_gather; host only, as yv_wgrad_route.  *gemm is yv_wgrad_route(r64(T), N, 9*Cin, tile_n, ws_bytes,
+ * n_cu).  *use: 0 where the per-layer measurement had the gather form slower than yv_im2col3 + yv_wgrad_tiled (a trainer then
+ * keeps that layer on im2col); no measured layer was slower, so 1 everywhere today. */
+int yv_wgrad_conv3_gather_route(int B, int Hin, int Win, int stride, int Cin, int N, int tile_n, size_t ws_bytes, int n_cu,
+                                yv_wgrad_route_t* gemm, int* use);
+/* The index function of yv_wgrad_conv3_gather's kernels, run on the host with the multiply-shift constants the launch computes:
+ * *pixel = (b*Hin + iy)*Win + ix, the input pixel that tap (0..8, ky*3 + kx) of output pixel m reads, or -1 where it reads
+ * zero (padding, or m >= B*Hout*Wout).  Host only. */
+int yv_wgrad_conv3_gather_src(int B, int Hin, int Win, int stride, int m, int tap, long long* pixel);
+
 /* out_t[c][r] = in[r][c] (bf16), rows of out_t zero padded up to the next multiple of 64 (ld_out >= that). */
 int yv_transpose_bf16(const void* in, int rows, int cols, long long ld_in, void* out_t, long long ld_out, void* stream);
 

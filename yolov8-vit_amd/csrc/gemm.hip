@@ -1735,7 +1735,57 @@ __global__ __launch_bounds__(256) void quant_mx_2d_kernel(const uint16_t* __rest
 // Few output tiles, long reduction -> always split over the token dimension (deterministic slice-order reduce).
 // ---------------------------------------------------------------------------------------------
 
-__global__ __launch_bounds__(256, 2) void gemm_tn_kernel(GemmArgs g) {
+// The gather form (yv_wgrad_conv3_gather): X is not a (T, K) matrix but the virtual im2col of a 3 x 3 / pad 1
+// convolution's input x (B, Hin, Win, Cin), row stride ldx: row m = output pixel (b, oy, ox), column k = (ky * 3 + kx) * Cin + ci,
+// the K order of yv_im2col3.  A lane's 16-byte chunk lies inside one tap (Cin % 8 == 0), so its source is x's own pixel
+// (b, oy * stride + ky - 1, ox * stride + kx - 1) or, for a tap in the padding or a row past T, a zero chunk of the library's.
+// The LDS then holds what the im2col path puts there, and everything behind the DMA is unchanged.
+// m -> (b, oy, ox) without a division: q = (m * mul) >> sh with mul = ceil(2^sh / d), sh = 31 + ceil(log2 d), exact for every
+// 0 <= m < 2^31 (Granlund & Montgomery 1994, theorem 4.2 with N = 31; mul < 2^32).  ONE function computes the index, for the
+// kernels and, through yv_wgrad_conv3_gather_src, for the host.
+struct ConvGather {
+    const uint16_t* x;
+    long long ldx;
+    int T, Hin, Win, Hout, Wout, stride, Cin;
+    uint32_t mul_w, mul_h;          // m / Wout, (m / Wout) / Hout
+    int sh_w, sh_h;
+};
+__device__ uint4 g_zero_chunk = {0u, 0u, 0u, 0u};            // what a tap in the padding reads
+
+inline void gather_magic(int d, uint32_t* mul, int* sh) {
+    int l = 0;
+    while ((1LL << l) < d) ++l;
+    *sh = 31 + l;
+    *mul = (uint32_t)(((1ULL << *sh) + (unsigned long long)d - 1) / (unsigned long long)d);
+}
+inline ConvGather conv_gather_of(const void* x, long long ldx, int B, int Hin, int Win, int stride, int Cin) {
+    ConvGather q = {};
+    q.x = (const uint16_t*)x; q.ldx = ldx; q.Hin = Hin; q.Win = Win; q.stride = stride; q.Cin = Cin;
+    q.Hout = (Hin - 1) / stride + 1; q.Wout = (Win - 1) / stride + 1;
+    q.T = B * q.Hout * q.Wout;
+    gather_magic(q.Wout, &q.mul_w, &q.sh_w);
+    gather_magic(q.Hout, &q.mul_h, &q.sh_h);
+    return q;
+}
+// input pixel index (b * Hin + iy) * Win + ix that tap (ky, kx) of output pixel m reads, -1: zero (padding, or m >= T)
+__host__ __device__ __forceinline__ long long conv_gather_pixel(const ConvGather& q, int m, int ky, int kx) {
+    if (m >= q.T) return -1;
+    const uint32_t r = (uint32_t)(((unsigned long long)(uint32_t)m * q.mul_w) >> q.sh_w);
+    const int ox = m - (int)r * q.Wout;
+    const int b = (int)(((unsigned long long)r * q.mul_h) >> q.sh_h);
+    const int oy = (int)r - b * q.Hout;
+    const int iy = oy * q.stride + ky - 1, ix = ox * q.stride + kx - 1;
+    if ((unsigned)iy >= (unsigned)q.Hin || (unsigned)ix >= (unsigned)q.Win) return -1;
+    return ((long long)b * q.Hin + iy) * q.Win + ix;
+}
+// the source of a lane's chunk of token m: tap (ky, kx), channel ci (fixed per lane in the prologue)
+__device__ __forceinline__ const uint16_t* conv_gather_src(const ConvGather& q, int m, int ky, int kx, int ci) {
+    const long long p = conv_gather_pixel(q, m, ky, kx);
+    return p < 0 ? (const uint16_t*)&g_zero_chunk : q.x + p * q.ldx + ci;
+}
+
+template <bool GATHER>
+__device__ __forceinline__ void gemm_tn_body(const GemmArgs& g, const ConvGather& q) {
     // g.a0 = dY (T, N) ld lda0 ; g.w = X (T, K) ld lda1 ; T = g.K (multiple of 64) ; out (N, K) f32 ld ldo
     constexpr int TB = 64, TILE = TB * 256;                   // bytes per operand tile
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -1752,6 +1802,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(GemmArgs g) {
     const int lr = lane >> 4, lc = lane & 15;
     const uint16_t* ysrc[4];
     const uint16_t* xsrc[4];
+    int xtap[4], xrow[4];                                     // GATHER: in place of xsrc
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int row = (j * 4 + wave) * 4 + lr;              // 0..63
@@ -1759,9 +1810,15 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(GemmArgs g) {
         int cn = n0 + ch * 8; cn = cn < Nw ? cn : Nw - 8;      // column clamp (results of clamped columns are not stored)
         int ck = k0 + ch * 8; ck = ck < Kw ? ck : Kw - 8;
         ysrc[j] = g.a0 + (long long)row * g.lda0 + cn;
-        long long xoff = ck;
-        if (g.seg_len) { const int sg = ck / g.seg_len; xoff = (long long)sg * g.seg_stride + (ck - sg * g.seg_len); }
-        xsrc[j] = g.w + (long long)row * g.lda1 + xoff;
+        if constexpr (GATHER) {                               // the chunk's tap and channel: ky | kx << 2 | ci << 4
+            const int tap = ck / q.Cin;
+            xtap[j] = tap / 3 | (tap % 3) << 2 | (ck - tap * q.Cin) << 4;
+            xrow[j] = row;
+        } else {
+            long long xoff = ck;
+            if (g.seg_len) { const int sg = ck / g.seg_len; xoff = (long long)sg * g.seg_stride + (ck - sg * g.seg_len); }
+            xsrc[j] = g.w + (long long)row * g.lda1 + xoff;
+        }
     }
     auto issue = [&](int tt, int buf) {
         unsigned char* Yt = smem + buf * (2 * TILE);
@@ -1769,7 +1826,10 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(GemmArgs g) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             __builtin_amdgcn_global_load_lds((gptr_t)(ysrc[j] + (long long)tt * TB * g.lda0), (lptr_t)(Yt + (j * 4 + wave) * 1024), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((gptr_t)(xsrc[j] + (long long)tt * TB * g.lda1), (lptr_t)(Xt + (j * 4 + wave) * 1024), 16, 0, 0);
+            const uint16_t* xs;
+            if constexpr (GATHER) xs = conv_gather_src(q, tt * TB + xrow[j], xtap[j] & 3, xtap[j] >> 2 & 3, xtap[j] >> 4);
+            else xs = xsrc[j] + (long long)tt * TB * g.lda1;
+            __builtin_amdgcn_global_load_lds((gptr_t)xs, (lptr_t)(Xt + (j * 4 + wave) * 1024), 16, 0, 0);
         }
     };
     f32x4 acc[4][4];                                          // [k fragment][n fragment]
@@ -1824,6 +1884,8 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(GemmArgs g) {
         }
     }
 }
+__global__ __launch_bounds__(256, 2) void gemm_tn_kernel(GemmArgs g) { gemm_tn_body<false>(g, ConvGather{}); }
+__global__ __launch_bounds__(256, 2) void gemm_tn_gather_kernel(GemmArgs g, ConvGather q) { gemm_tn_body<true>(g, q); }
 
 // The same product for few output channels (wgrad_route picks it; opt-in): TN (n) x 256 (k) output tiles,
 // TN = 64 or 32, so a workgroup keeps the 128 x 128 tile's 64 accumulators per lane only where dW has columns.
@@ -1836,9 +1898,15 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(GemmArgs g) {
 //   Chunks past N / K inside a live fragment are clamped to N - 8 / K - 8 as above.
 // Summation: the MFMA, the ascending token walk, the slices and tr_frag's token-to-slot mapping are gemm_tn_kernel's, so for
 // an equal slice count every dW element is the same chain of operations on the same values - bit-identical results.
-template <int TN>
-__global__ __launch_bounds__(256, 2) void gemm_tn_narrow_kernel(GemmArgs g) {
+// GATHER: the X side of issue() as in gemm_tn_body; the ConvGather block is then the kernel's second argument (a parameter pack,
+// empty otherwise: the plain instances keep their argument block, and their code).
+__device__ __forceinline__ int gather_args() { return 0; }
+__device__ __forceinline__ const ConvGather& gather_args(const ConvGather& q) { return q; }
+template <int TN, bool GATHER = false, typename... Q>
+__global__ __launch_bounds__(256, 2) void gemm_tn_narrow_kernel(GemmArgs g, Q... gather) {
     static_assert(TN == 64 || TN == 32, "dY tile width");
+    static_assert(sizeof...(Q) == (GATHER ? 1 : 0), "the gather form takes one ConvGather");
+    [[maybe_unused]] const auto& q = gather_args(gather...);
     constexpr int TB = 64, XSUB = TB * 256, BUF = 2 * XSUB + TB * TN * 2;   // bytes: an X sub-tile, one buffer
     constexpr int NF = TN / 16;                               // n fragments of a wave
     constexpr int YCH = TN / 8, YROWS = 64 / YCH, YI = YCH / 4;   // dY: chunks per row, rows per DMA instruction, instructions per wave
@@ -1860,6 +1928,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_narrow_kernel(GemmArgs g) {
     // source chunk = chunk' ^ swz(row).  A lane whose source chunk lies in a dead fragment issues nothing.
     const uint16_t* ysrc[YI];
     const uint16_t* xsrc[8];
+    int xtap[8], xrow[8];                                     // GATHER: in place of xsrc
     unsigned ylive = 0, xlive = 0;
 #pragma unroll
     for (int j = 0; j < YI; ++j) {
@@ -1874,9 +1943,15 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_narrow_kernel(GemmArgs g) {
         const int c = (j >> 2) * 128 + (((lane & 15) ^ tn_swz(row)) << 3);
         xlive |= (unsigned)((c & ~15) < k_live) << j;
         const int ck = k0 + (c < k_live ? c : k_live - 8);
-        long long xoff = ck;
-        if (g.seg_len) { const int sg = ck / g.seg_len; xoff = (long long)sg * g.seg_stride + (ck - sg * g.seg_len); }
-        xsrc[j] = g.w + (long long)row * g.lda1 + xoff;
+        if constexpr (GATHER) {                               // the chunk's tap and channel: ky | kx << 2 | ci << 4
+            const int tap = ck / q.Cin;
+            xtap[j] = tap / 3 | (tap % 3) << 2 | (ck - tap * q.Cin) << 4;
+            xrow[j] = row;
+        } else {
+            long long xoff = ck;
+            if (g.seg_len) { const int sg = ck / g.seg_len; xoff = (long long)sg * g.seg_stride + (ck - sg * g.seg_len); }
+            xsrc[j] = g.w + (long long)row * g.lda1 + xoff;
+        }
     }
     auto issue = [&](int tt, int buf) {
         unsigned char* Xt = smem + buf * BUF;
@@ -1887,9 +1962,12 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_narrow_kernel(GemmArgs g) {
                 __builtin_amdgcn_global_load_lds((gptr_t)(ysrc[j] + (long long)tt * TB * g.lda0), (lptr_t)(Yt + (j * 4 + wave) * 1024), 16, 0, 0);
 #pragma unroll
         for (int j = 0; j < 8; ++j)
-            if (xlive >> j & 1)
-                __builtin_amdgcn_global_load_lds((gptr_t)(xsrc[j] + (long long)tt * TB * g.lda1),
-                                                 (lptr_t)(Xt + (j >> 2) * XSUB + ((j & 3) * 4 + wave) * 1024), 16, 0, 0);
+            if (xlive >> j & 1) {
+                const uint16_t* xs;
+                if constexpr (GATHER) xs = conv_gather_src(q, tt * TB + xrow[j], xtap[j] & 3, xtap[j] >> 2 & 3, xtap[j] >> 4);
+                else xs = xsrc[j] + (long long)tt * TB * g.lda1;
+                __builtin_amdgcn_global_load_lds((gptr_t)xs, (lptr_t)(Xt + (j >> 2) * XSUB + ((j & 3) * 4 + wave) * 1024), 16, 0, 0);
+            }
     };
     f32x4 acc[4][NF];                                         // [k fragment][n fragment]
 #pragma unroll
@@ -3018,8 +3096,9 @@ static int wgrad_launch(const void* dY, int ldy, const void* X, int ldx, int T, 
     g.tiles_m = (N + r.tile_n - 1) / r.tile_n; g.tiles_n = (K + r.tile_k - 1) / r.tile_k;
     g.splitk = r.slices;
     if (g.splitk > 1) g.partial = (float*)ws;
-    void (*kern)(GemmArgs) = r.tile_n == 256 ? gemm_tn_wide_kernel
-                             : r.tile_n == 128 ? gemm_tn_kernel : r.tile_n == 64 ? gemm_tn_narrow_kernel<64> : gemm_tn_narrow_kernel<32>;
+    using Kern = void (*)(GemmArgs);
+    Kern kern = r.tile_n == 256 ? gemm_tn_wide_kernel
+                : r.tile_n == 128 ? gemm_tn_kernel : r.tile_n == 64 ? (Kern)gemm_tn_narrow_kernel<64> : (Kern)gemm_tn_narrow_kernel<32>;
     const size_t lds = r.tile_n == 256 ? 2 * 3 * 32 * 256
                        : r.tile_n == 128 ? 2 * 2 * 64 * 256 : 2 * (2 * 64 * 256 + 64 * r.tile_n * 2);
     if (r.tile_n != 128 && !yv_grant_lds((const void*)kern, lds)) return YV_ERR_LAUNCH;
@@ -3086,6 +3165,58 @@ extern "C" int yv_wgrad_conv3_tiled(const void* dYp, int ldy, const void* Xp, in
     if (!Xp || Cin < 8 || (Cin & 7) || pitch < 3) return YV_ERR_ARG;
     const uint16_t* base = (const uint16_t*)Xp - (long long)(pitch + 1) * Cin;
     return wgrad_impl(dYp, ldy, base, Cin, T, N, 9 * Cin, dW, ldw, 3 * Cin, (long long)pitch * Cin, tile_n, stream);
+}
+
+// 3x3 / pad 1 / stride 1 or 2 weight gradient with no operand copy at all: the gather form of the kernels above reads dY and x in
+// place.  The route is wgrad_route's for (r64(T), N, 9 * Cin): the same tiles and slices as yv_im2col3 + yv_wgrad_tiled, hence the
+// same bits.  `use`: 0 where the per-layer measurement had the gather form slower; it was faster on all seven stride-2 layers of
+// YOLOv8s and YOLOv8n at 16 x 640^2 with either tile (x 0.53 - 0.94, profiles/wgrad_gather_layers.txt), so 1 everywhere
+// (DESIGN.md section 26).
+static bool gather_grid_ok(int B, int Hin, int Win, int stride, int Cin, int N, int tile_n) {
+    if (B <= 0 || Hin <= 0 || Win <= 0 || !(stride == 1 || stride == 2) || Cin < 8 || (Cin & 7) || N <= 0 || (N & 7)) return false;
+    if (tile_n != 0 && tile_n != 32 && tile_n != 64 && tile_n != 128) return false;
+    const long long T = (long long)B * ((Hin - 1) / stride + 1) * ((Win - 1) / stride + 1);
+    return T <= (1LL << 31) - 64 && 9LL * Cin < (1LL << 31);
+}
+
+extern "C" int yv_wgrad_conv3_gather_route(int B, int Hin, int Win, int stride, int Cin, int N, int tile_n, size_t ws_bytes, int n_cu,
+                                           yv_wgrad_route_t* gemm, int* use) {
+    if (!gemm || !use || n_cu < 0 || !gather_grid_ok(B, Hin, Win, stride, Cin, N, tile_n)) return YV_ERR_ARG;
+    const ConvGather q = conv_gather_of(nullptr, Cin, B, Hin, Win, stride, Cin);
+    *gemm = wgrad_route((q.T + 63) & ~63, N, 9 * Cin, tile_n, ws_bytes, n_cu);
+    *use = 1;
+    return YV_OK;
+}
+
+extern "C" int yv_wgrad_conv3_gather_src(int B, int Hin, int Win, int stride, int m, int tap, long long* pixel) {
+    if (!pixel || m < 0 || tap < 0 || tap > 8 || !gather_grid_ok(B, Hin, Win, stride, 8, 8, 0)) return YV_ERR_ARG;
+    *pixel = conv_gather_pixel(conv_gather_of(nullptr, 8, B, Hin, Win, stride, 8), m, tap / 3, tap % 3);
+    return YV_OK;
+}
+
+extern "C" int yv_wgrad_conv3_gather(const void* dY, int ldy, const void* X, long long ldx, int B, int Hin, int Win, int stride,
+                                     int Cin, int N, float* dW, int ldw, int tile_n, void* stream) {
+    if (!dY || !X || !dW || !gather_grid_ok(B, Hin, Win, stride, Cin, N, tile_n)) return YV_ERR_ARG;
+    if ((ldy & 7) || ldy < N || (ldx & 7) || ldx < Cin || (ldw & 3) || ldw < 9 * Cin) return YV_ERR_ARG;
+    if (((uintptr_t)dY | (uintptr_t)X | (uintptr_t)dW) & 15) return YV_ERR_ARG;
+    const ConvGather q = conv_gather_of(X, ldx, B, Hin, Win, stride, Cin);
+    const int T = (q.T + 63) & ~63, K = 9 * Cin;
+    void* ws = nullptr; size_t wsb = 0;
+    if (!ws_lookup(stream, &ws, &wsb)) wsb = 0;
+    const WgradRoute r = wgrad_route(T, N, K, tile_n, wsb, 0);
+    GemmArgs g = {};
+    g.a0 = (const uint16_t*)dY; g.lda0 = ldy;
+    g.M = N; g.N = K; g.K = T; g.out = dW; g.ldo = ldw; g.flags = YV_EPI_OUT_F32;
+    g.tiles_m = (N + r.tile_n - 1) / r.tile_n; g.tiles_n = (K + r.tile_k - 1) / r.tile_k;
+    g.splitk = r.slices;
+    if (g.splitk > 1) g.partial = (float*)ws;
+    using Kern = void (*)(GemmArgs, ConvGather);
+    Kern kern = r.tile_n == 128 ? gemm_tn_gather_kernel
+                : r.tile_n == 64 ? (Kern)gemm_tn_narrow_kernel<64, true> : (Kern)gemm_tn_narrow_kernel<32, true>;
+    const size_t lds = r.tile_n == 128 ? 2 * 2 * 64 * 256 : 2 * (2 * 64 * 256 + 64 * r.tile_n * 2);
+    if (!yv_grant_lds((const void*)kern, lds)) return YV_ERR_LAUNCH;
+    hipLaunchKernelGGL(kern, dim3(r.workgroups), dim3(256), lds, (hipStream_t)stream, g, q);
+    return launch_splitk_reduce(g, (hipStream_t)stream);
 }
 
 extern "C" int yv_conv2d(const yv_view* in0, const yv_view* in1, int B, int Hout, int Wout, int ksize, int stride,

@@ -148,6 +148,9 @@ _SIGS = {
     "yv_wgrad_conv3": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp]),
     "yv_wgrad_tiled": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp]),
     "yv_wgrad_conv3_tiled": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp]),
+    "yv_wgrad_conv3_gather": (_i, [_vp, _i, _vp, C.c_longlong, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp]),
+    "yv_wgrad_conv3_gather_route": (_i, [_i, _i, _i, _i, _i, _i, _i, _sz, _i, _vp, _vp]),
+    "yv_wgrad_conv3_gather_src": (_i, [_i, _i, _i, _i, _i, _i, _vp]),
     "yv_wgrad_route": (_i, [_i, _i, _i, _i, _sz, _i, _vp]),
     "yv_wgrad_wide": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp]),
     "yv_wgrad_wide_route": (_i, [_i, _i, _i, _i, _sz, _i, _vp]),
@@ -932,6 +935,22 @@ def wgrad_conv3(dyp: torch.Tensor, xp: torch.Tensor, dw: torch.Tensor, T: int, p
     return dw
 
 
+def wgrad_conv3_gather(dy: torch.Tensor, x: "yv_view", dw: torch.Tensor, B: int, Hin: int, Win: int, stride: int,
+                       tile_n: Optional[int] = None):
+    """dw (N, 9*Cin) f32 = 3x3 / pad 1 / stride 1 or 2 weight gradient with no operand copy (yv_wgrad_conv3_gather): dy
+    (r64(B*Hout*Wout), N) bf16 with a zero tail, x the convolution's input (B, Hin, Win, Cin) as a view (mview), read in place.
+    tile_n as wgrad takes it; the bits are those of im2col3 + wgrad(tile_n=...) on the same operands."""
+    for t_ in (dy, dw):
+        if not t_.is_cuda or t_.stride(-1) != 1:
+            raise YvError("wgrad_conv3_gather operands must be device tensors with unit column stride")
+    hout, wout = (Hin - 1) // stride + 1, (Win - 1) // stride + 1
+    if dy.shape[0] < (B * hout * wout + 63) // 64 * 64 or dw.shape != (dy.shape[1], 9 * x.c) or x.up:
+        raise YvError("wgrad_conv3_gather: dy must have r64(B*Hout*Wout) rows, dw be (N, 9*Cin) and x a plain view")
+    check(lib.yv_wgrad_conv3_gather(_p(dy), dy.stride(0), x.ptr, x.ld, B, Hin, Win, stride, x.c, dy.shape[1], _p(dw), dw.stride(0),
+                                    128 if tile_n is None else int(tile_n), _st()), "yv_wgrad_conv3_gather")
+    return dw
+
+
 def linear_nn(a: torch.Tensor, w_kn: torch.Tensor, out: torch.Tensor, flags: int = 0, aux: Optional[torch.Tensor] = None,
               M: Optional[int] = None):
     """out[M,N] = a[M,K] @ w_kn[K,N] (weight read reduction-major: dgrad on the master layout)."""
@@ -1300,6 +1319,25 @@ def wgrad_wide_route(T: int, N: int, K: int, routed: bool = False, ws_bytes: int
     out = (C.c_int * len(WgradRoute._fields))()
     check(lib.yv_wgrad_wide_route(T, N, K, 0 if routed else 1, ws_bytes, n_cu, out), "yv_wgrad_wide_route")
     return WgradRoute(*out)
+
+
+def wgrad_conv3_gather_route(B: int, Hin: int, Win: int, stride: int, Cin: int, N: int, tile_n: int = 0,
+                             ws_bytes: int = STREAM_WS_BYTES, n_cu: int = 256) -> Tuple[WgradRoute, bool]:
+    """(route, use) of wgrad_conv3_gather for this layer (host only): see yv_wgrad_conv3_gather_route in include/yv_hip.h.  The
+    route is wgrad_route(r64(B*Hout*Wout), N, 9*Cin, tile_n); use is False where the gather form was measured slower than
+    im2col3 + wgrad."""
+    out, use = (C.c_int * len(WgradRoute._fields))(), C.c_int(0)
+    check(lib.yv_wgrad_conv3_gather_route(B, Hin, Win, stride, Cin, N, tile_n, ws_bytes, n_cu, out, C.byref(use)),
+          "yv_wgrad_conv3_gather_route")
+    return WgradRoute(*out), bool(use.value)
+
+
+def wgrad_conv3_gather_src(B: int, Hin: int, Win: int, stride: int, m: int, tap: int) -> int:
+    """Input pixel index (b*Hin + iy)*Win + ix that tap (0..8) of output pixel m reads in wgrad_conv3_gather's kernels, -1 for
+    zero (host only: the kernels' own index function, yv_wgrad_conv3_gather_src)."""
+    pixel = C.c_longlong(0)
+    check(lib.yv_wgrad_conv3_gather_src(B, Hin, Win, stride, m, tap, C.byref(pixel)), "yv_wgrad_conv3_gather_src")
+    return int(pixel.value)
 
 
 def wgrad_mxfp8(dyt: torch.Tensor, dy_scale: torch.Tensor, xt: torch.Tensor, x_scale: torch.Tensor, dw: torch.Tensor):

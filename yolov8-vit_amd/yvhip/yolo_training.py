@@ -26,11 +26,13 @@ from typing import Dict, List, NamedTuple, Optional, Tuple, Union
 
 import torch
 
+import yvhip as _yv
 from . import (OPT_ADAMW, OPT_SGD_NESTEROV, VIEW_ADD, VIEW_COPY, VIEW_PAD, VIEW_UP2, VIEW_UP2_BWD, VIEW_ZERO_INSERT, YvError, axpby,
                blob_nhwc8, bn_act_bwd, bn_act_fwd, ema_update, optim_step,
                bn_stats, bn_stats_finish, bn_ws_floats, cast_colsum, colsum_ws_floats, conv_stats_ws_floats, conv_view,
                conv_dgrad_s2, conv_dgrad_s2_route, conv_view_stats, conv_weight_dgrad, detect_loss,
-               detect_loss_ws_bytes, im2col3, maxpool5_bwd, mview, require_gpu, sgd_step, sppf_pool, view_op, wgrad, wgrad_conv3)
+               detect_loss_ws_bytes, im2col3, maxpool5_bwd, mview, require_gpu, sgd_step, sppf_pool, view_op, wgrad, wgrad_conv3,
+               wgrad_conv3_gather)
 from .engines import LAYER_STRIDE, REG_MAX, _env_flag, detect_widths, yolo_conv_keys, yolo_layers
 
 BN_EPS, BN_MOMENTUM = 1e-3, 0.03
@@ -264,7 +266,7 @@ class YoloTrainer:
                  lr: float = 1e-4, momentum: float = 0.937, weight_decay: float = 5e-4, device: str = "cuda:0",
                  optimizer: str = "sgd", ema: bool = False, ema_decay: float = 0.9999, ema_tau: float = 2000.0,
                  overlap_wgrad: bool = True, implicit_wgrad: bool = True, narrow_wgrad: Optional[bool] = None,
-                 fused_bn_stats: Optional[bool] = None, phase_dgrad: Optional[bool] = None):
+                 fused_bn_stats: Optional[bool] = None, phase_dgrad: Optional[bool] = None, gather_wgrad: Optional[bool] = None):
         require_gpu()
         if size % 32:
             raise YvError("input size must be a multiple of 32")
@@ -282,6 +284,11 @@ class YoloTrainer:
         # a stride-1 convolution, for the blocks whose route says so (_alloc_buffers); DESIGN.md section 24
         self.phase_dgrad = _env_flag(phase_dgrad, "YV_YOLO_PHASE_DGRAD")
         self._phase_blocks: set = set()
+        # opt-in: the weight gradient of the 3 x 3 / stride-2 convolutions with gathered source addresses (yv_wgrad_conv3_gather)
+        # in place of im2col + wgrad, for the blocks whose route says so (_alloc_buffers); needs implicit_wgrad (without it the
+        # trainer is the im2col statement); DESIGN.md section 26
+        self.gather_wgrad = _env_flag(gather_wgrad, "YV_YOLO_GATHER_WGRAD")
+        self._gather_blocks: set = set()
         if optimizer not in ("sgd", "sgd_nesterov", "adamw"):
             raise YvError("optimizer must be 'sgd', 'sgd_nesterov' or 'adamw'")
         self.optimizer, self.use_ema, self.ema_decay, self.ema_tau = optimizer, ema, ema_decay, ema_tau
@@ -442,6 +449,8 @@ class YoloTrainer:
                 tpp = _r64(B * hp * hp)
                 xp_n = max(xp_n, (tpp + 2 * (hp + 1)) * b.cin)
                 dzp_n = max(dzp_n, tpp * b.cout)
+            elif b.k == 3 and self.gather_wgrad and self.implicit_wgrad and self._gather_eligible(b, hin):
+                self._gather_blocks.add(b.key)
             elif b.k == 3:
                 col_n = max(col_n, _r64(T) * 9 * b.cin)
             if b.s == 2 and self.phase_dgrad and self._phase_eligible(b, hin):
@@ -461,6 +470,16 @@ class YoloTrainer:
         """The route's answer for this block's data gradient (asked once, at construction): eligible and not measured slower."""
         try:
             return conv_dgrad_s2_route(self.B, hin, hin, b.k, b.cin, b.cout).use
+        except YvError:
+            return False
+
+    def _gather_eligible(self, b: _Block, hin: int) -> bool:
+        """The route's answer for this block's weight gradient (asked once, at construction, and only with the flag on).  The
+        route is reached through the package so that a launch trace, which stubs the wrappers this module imports, gets the real
+        answer."""
+        try:
+            return _yv.wgrad_conv3_gather_route(self.B, hin, hin, b.s, b.cin, b.cout,
+                                                128 if self._wgrad_tile is None else self._wgrad_tile)[1]
         except YvError:
             return False
 
@@ -528,6 +547,9 @@ class YoloTrainer:
             if tpp != tpad:
                 dzp[tpad:].zero_()
             wgrad_conv3(dzp, xp, dw, tpp, hp, tile_n=self._wgrad_tile)
+        elif b.key in self._gather_blocks:
+            # no im2col either: the kernel computes each tap's source pixel and reads dz and x in place (yv_wgrad_conv3_gather)
+            wgrad_conv3_gather(dz, mview(x_buf, x_off, b.cin), dw, self.B, hin, hin, b.s, tile_n=self._wgrad_tile)
         else:
             col = self.col[:Tp * 9 * b.cin].view(Tp, 9 * b.cin)
             if Tp != T:
