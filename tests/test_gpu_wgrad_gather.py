@@ -1,5 +1,5 @@
-"""The im2col-free weight gradient by gathered source addresses (yv_wgrad_conv3_gather: the gather form of gemm_tn_kernel and
-gemm_tn_narrow_kernel<64 / 32>) on the GPU.  Every comparison is exact, so there is no tolerance.
+"""The im2col-free weight gradient by gathered source addresses (yv_wgrad_conv3_gather: gemm_tn_gather_kernel and
+gemm_tn_narrow_gather_kernel<64 / 32>) on the GPU.  Every comparison is exact, so there is no tolerance.
 
 Integer operands (x in [-2, 2], dz in {-1, 0, 1}): every product and every f32 partial sum is an integer below 2^24 (asserted
 from the shape before the launch), so the result must EQUAL float64 autograd whatever the tile and the slices.  Both operands

@@ -1784,163 +1784,100 @@ __device__ __forceinline__ const uint16_t* conv_gather_src(const ConvGather& q, 
     return p < 0 ? (const uint16_t*)&g_zero_chunk : q.x + p * q.ldx + ci;
 }
 
-template <bool GATHER>
+// ONE text (gemm_tn_body) for every tile shape.  A workgroup owns TN (n) x TK (k) of dW and walks the tokens in stages of TB; a
+// stage holds each operand as images [TB][COLS] in the layout above (COLS * 2-byte rows, tn_swz<COLS>, tr_frag<COLS>).  Its four
+// waves are WK along k (64 k columns = 4 fragments each) by WN along n (NF fragments each).
+//   tile          | TN x TK      | TB | dY images      | X images       | in a buffer | (wk, wn) of wave w | NF      | edges | LDS
+//   Tn128         | 128 x 128    | 64 | 1 x [64][128]  | 1 x [64][128]  | dY, X       | w >> 1, w & 1      | 4       | clamp | 64 KB
+//   TnNarrow<TN>  | 64, 32 x 256 | 64 | 1 x [64][TN]   | 2 x [64][128]  | X, dY       | w, 0               | TN / 16 | live  | 80, 72 KB
+//   TnWide        | 256 x 128    | 32 | 2 x [32][128]  | 1 x [32][128]  | dY, X       | w & 1, w >> 1      | 8       | live  | 48 KB
+// Tn128: gemm_tn_kernel, every weight gradient unless a route says otherwise.
+// TnNarrow (wgrad_route picks it; opt-in): few output channels - a workgroup keeps the 128 x 128 tile's 64
+//   accumulators per lane only where dW has columns.
+// TnWide (wgrad_wide_route picks it; opt-in): large dW - a workgroup moves 24 KB through the LDS-DMA path per
+//   32 tokens where two 128 x 128 workgroups move 32 KB for the same MFMAs.  The swizzle and tr_frag's row mapping repeat every 32
+//   rows, so a 32-token stage reads as step ks = 0 of a 64-token tile; a 64-token double buffer would be 96 KB (a ring of three
+//   stages with a counted wait measured equal or slower).
+// Edges.  Chunks past N / K are clamped to N - 8 / K - 8 (results of clamped columns are not stored).  "live" tiles besides give a
+//   16-column fragment that lies wholly past N (or K) no DMA (its lanes are masked off the load: the LDS destination is
+//   base + 16 * lane whatever the mask; nothing at all is issued for an image past the edge), no LDS read and no MFMA: a wave picks
+//   the loop instance for its count of live k and n fragments once (wave-uniform), so the transposing reads run with every lane on
+//   and the loop bodies have no branches (a wave with runtime guards around each read and MFMA holds the whole workgroup back at
+//   the barrier: measured).  Tn128 always runs 4 x 4.
+// Pipeline: two buffers; the DMA of stage s + 1 is issued before the MFMAs of stage s and drained (vmcnt(0)) at the stage's only
+//   barrier.  ALTERNATE: the dY and X instructions of a stage are issued in turns (Tn128), otherwise dY first.
+// Summation: the MFMA, tr_frag's token-to-slot mapping per 32 tokens, the ascending token walk and the slice boundaries (whole
+//   64-token tiles, t0 = nt * slice / S) do not depend on the tile, so for an equal slice count every dW element is the same chain
+//   of operations on the same values whatever the tile: bit-identical results (tests/golden/wgrad_bits.json pins them).
+// GATHER: only the X side of the DMA changes; the ConvGather block is then the kernel's second argument.
+template <int TN_, int TK_, int TB_>
+struct TnShape {
+    static constexpr int TN = TN_, TK = TK_, TB = TB_;
+    static constexpr int YC = TN < 128 ? TN : 128, YS = TN / YC, XS = TK / 128;       // columns of a dY image; images of dY, of X
+    static constexpr int YSUB = TB * YC * 2, XSUB = TB * 256;                        // bytes of an image
+    static constexpr int YPI = YSUB / 4096, XPI = XSUB / 4096;                       // DMA instructions (1 KB) per wave and image
+    static constexpr int BUF = YS * YSUB + XS * XSUB, LDS = 2 * BUF;                 // bytes of a buffer; dynamic LDS of the launch
+    static constexpr int WK = TK / 64, WN = 4 / WK, NF = TN / WN / 16;
+    static_assert(YS * YC == TN && XS * 128 == TK && (TB == 64 || TB == 32) && YPI >= 1 && WK * WN == 4 && NF * WN * 16 == TN, "tile");
+};
+struct Tn128 : TnShape<128, 128, 64> { static constexpr bool LIVE = false, K_OUTER = true, Y_FIRST = true, ALTERNATE = true; };
+template <int TN>
+struct TnNarrow : TnShape<TN, 256, 64> { static constexpr bool LIVE = true, K_OUTER = true, Y_FIRST = false, ALTERNATE = false; };
+struct TnWide : TnShape<256, 128, 32> { static constexpr bool LIVE = true, K_OUTER = false, Y_FIRST = true, ALTERNATE = false; };
+
+// DMA instruction j of an operand with images [TB][COLS], PI instructions per wave and image: lane -> row of the image
+// (64 / CH rows per instruction, CH = COLS / 8 chunks per row) and first column of the operand tile; source chunk = chunk' ^ swz(row)
+template <int COLS, int PI>
+__device__ __forceinline__ void tn_dma_lane(int j, int wave, int lane, int& row, int& col) {
+    constexpr int CH = COLS / 8;
+    row = ((j % PI) * 4 + wave) * (64 / CH) + lane / CH;
+    col = (j / PI) * COLS + (((lane % CH) ^ tn_swz<COLS>(row)) << 3);
+}
+// f(std::integral_constant<int, n>) for a runtime LO <= n <= HI
+template <int LO, int HI, class F>
+__device__ __forceinline__ void tn_dispatch(int n, F& f) {
+    if constexpr (LO == HI) f(std::integral_constant<int, LO>{});
+    else if (n >= HI) f(std::integral_constant<int, HI>{});
+    else tn_dispatch<LO, HI - 1>(n, f);
+}
+
+template <class D, bool GATHER>
 __device__ __forceinline__ void gemm_tn_body(const GemmArgs& g, const ConvGather& q) {
     // g.a0 = dY (T, N) ld lda0 ; g.w = X (T, K) ld lda1 ; T = g.K (multiple of 64) ; out (N, K) f32 ld ldo
-    constexpr int TB = 64, TILE = TB * 256;                   // bytes per operand tile
+    constexpr int TB = D::TB, NF = D::NF, YI = D::YS * D::YPI, XI = D::XS * D::XPI;   // YI, XI: DMA instructions of a wave per stage
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = D::LIVE ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6;   // the dispatch below wants provably uniform counts
     const int Nw = g.M, Kw = g.N, T = g.K;
     int bid = blockIdx.x;
     const int S = g.splitk > 1 ? g.splitk : 1;
     const int slice = bid % S;
     bid /= S;
     const int tn_ = bid / g.tiles_n, tk_ = bid - tn_ * g.tiles_n;
-    const int n0 = tn_ * 128, k0 = tk_ * 128;
+    const int n0 = tn_ * D::TN, k0 = tk_ * D::TK;
+    const int n_live = Nw - n0 < D::TN ? Nw - n0 : D::TN, k_live = Kw - k0 < D::TK ? Kw - k0 : D::TK;   // columns inside dW: > 0, multiples of 8
+    const int wk = D::K_OUTER ? wave / D::WN : wave % D::WK, wn = D::K_OUTER ? wave % D::WN : wave / D::WK;
+    int nnf = (n_live - wn * NF * 16 + 15) >> 4;              // live n fragments of this wave
+    nnf = nnf < 0 ? 0 : nnf > NF ? NF : nnf;
+    int nkf = (k_live - wk * 64 + 15) >> 4;                   // live k fragments of this wave
+    nkf = nkf < 0 || nnf == 0 ? 0 : nkf > 4 ? 4 : nkf;        // a wave with no live fragment only feeds the DMA
 
-    // DMA: lane -> (row = 4*instr + lane/16, chunk' = lane%16); source chunk = chunk' ^ swz(row)
-    const int lr = lane >> 4, lc = lane & 15;
-    const uint16_t* ysrc[4];
-    const uint16_t* xsrc[4];
-    int xtap[4], xrow[4];                                     // GATHER: in place of xsrc
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int row = (j * 4 + wave) * 4 + lr;              // 0..63
-        const int ch = lc ^ tn_swz(row);
-        int cn = n0 + ch * 8; cn = cn < Nw ? cn : Nw - 8;      // column clamp (results of clamped columns are not stored)
-        int ck = k0 + ch * 8; ck = ck < Kw ? ck : Kw - 8;
-        ysrc[j] = g.a0 + (long long)row * g.lda0 + cn;
-        if constexpr (GATHER) {                               // the chunk's tap and channel: ky | kx << 2 | ci << 4
-            const int tap = ck / q.Cin;
-            xtap[j] = tap / 3 | (tap % 3) << 2 | (ck - tap * q.Cin) << 4;
-            xrow[j] = row;
-        } else {
-            long long xoff = ck;
-            if (g.seg_len) { const int sg = ck / g.seg_len; xoff = (long long)sg * g.seg_stride + (ck - sg * g.seg_len); }
-            xsrc[j] = g.w + (long long)row * g.lda1 + xoff;
-        }
-    }
-    auto issue = [&](int tt, int buf) {
-        unsigned char* Yt = smem + buf * (2 * TILE);
-        unsigned char* Xt = Yt + TILE;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            __builtin_amdgcn_global_load_lds((gptr_t)(ysrc[j] + (long long)tt * TB * g.lda0), (lptr_t)(Yt + (j * 4 + wave) * 1024), 16, 0, 0);
-            const uint16_t* xs;
-            if constexpr (GATHER) xs = conv_gather_src(q, tt * TB + xrow[j], xtap[j] & 3, xtap[j] >> 2 & 3, xtap[j] >> 4);
-            else xs = xsrc[j] + (long long)tt * TB * g.lda1;
-            __builtin_amdgcn_global_load_lds((gptr_t)xs, (lptr_t)(Xt + (j * 4 + wave) * 1024), 16, 0, 0);
-        }
-    };
-    f32x4 acc[4][4];                                          // [k fragment][n fragment]
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    const int wk = wave >> 1, wn = wave & 1;                  // 2 x 2 waves, 64 (k) x 64 (n) each
-    const int fi = lane & 15, mg = lane >> 4;
-
-    auto frag = [&](const unsigned char* tile, int ks, int col0) -> bf16x8 { return tr_frag(tile, ks, lane, col0); };
-
-    const int nt_all = T / TB;
-    const int t0 = (int)((long long)nt_all * slice / S), t1 = (int)((long long)nt_all * (slice + 1) / S);
-    if (t0 < t1) {
-        issue(t0, 0);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-    }
-    for (int tt = t0; tt < t1; ++tt) {
-        const int cur = (tt - t0) & 1;
-        if (tt + 1 < t1) issue(tt + 1, cur ^ 1);
-        const unsigned char* Yt = smem + cur * (2 * TILE);
-        const unsigned char* Xt = Yt + TILE;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            bf16x8 fx[4], fy[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) fx[i] = frag(Xt, ks, wk * 64 + i * 16);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) fy[j] = frag(Yt, ks, wn * 64 + j * 16);
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fx[i], fy[j], acc[i][j], 0, 0, 0);
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-    }
-    // D[row = k (lane>>4)*4 + reg][col = n (lane&15)]  ->  dW[n][k..k+3]
-    float* out = S > 1 ? g.partial + (long long)slice * Nw * Kw : (float*)g.out;
-    const long long ldo = S > 1 ? Kw : g.ldo;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int n = n0 + wn * 64 + j * 16 + fi;
-        if (n >= Nw) continue;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int k = k0 + wk * 64 + i * 16 + mg * 4;
-            if (k < Kw) *(float4*)(out + (long long)n * ldo + k) = make_float4(acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]);
-        }
-    }
-}
-__global__ __launch_bounds__(256, 2) void gemm_tn_kernel(GemmArgs g) { gemm_tn_body<false>(g, ConvGather{}); }
-__global__ __launch_bounds__(256, 2) void gemm_tn_gather_kernel(GemmArgs g, ConvGather q) { gemm_tn_body<true>(g, q); }
-
-// The same product for few output channels (wgrad_route picks it; opt-in): TN (n) x 256 (k) output tiles,
-// TN = 64 or 32, so a workgroup keeps the 128 x 128 tile's 64 accumulators per lane only where dW has columns.
-//   X tile: [64 tokens][256 columns] as TWO [64][128] sub-tiles in gemm_tn_kernel's layout (256-byte rows, tn_swz<128>); wave w
-//   owns k columns 64 w .. 64 w + 63 (sub-tile w / 2) against all TN n columns.
-//   dY tile: [64][TN] dense (128- / 64-byte rows), swizzle tn_swz<TN>: 2 x 32 KB + 8 / 4 KB per buffer, two buffers = 80 / 72 KB.
-//   A 16-column fragment that lies wholly past N (or K) gets no DMA (its lanes are masked off the load: the LDS destination is
-//   base + 16 * lane whatever the mask), no LDS read and no MFMA: a wave picks the loop instance for its count of live k and
-//   n fragments once (wave-uniform), so the transposing reads run with every lane on and the loop bodies have no branches.
-//   Chunks past N / K inside a live fragment are clamped to N - 8 / K - 8 as above.
-// Summation: the MFMA, the ascending token walk, the slices and tr_frag's token-to-slot mapping are gemm_tn_kernel's, so for
-// an equal slice count every dW element is the same chain of operations on the same values - bit-identical results.
-// GATHER: the X side of issue() as in gemm_tn_body; the ConvGather block is then the kernel's second argument (a parameter pack,
-// empty otherwise: the plain instances keep their argument block, and their code).
-__device__ __forceinline__ int gather_args() { return 0; }
-__device__ __forceinline__ const ConvGather& gather_args(const ConvGather& q) { return q; }
-template <int TN, bool GATHER = false, typename... Q>
-__global__ __launch_bounds__(256, 2) void gemm_tn_narrow_kernel(GemmArgs g, Q... gather) {
-    static_assert(TN == 64 || TN == 32, "dY tile width");
-    static_assert(sizeof...(Q) == (GATHER ? 1 : 0), "the gather form takes one ConvGather");
-    [[maybe_unused]] const auto& q = gather_args(gather...);
-    constexpr int TB = 64, XSUB = TB * 256, BUF = 2 * XSUB + TB * TN * 2;   // bytes: an X sub-tile, one buffer
-    constexpr int NF = TN / 16;                               // n fragments of a wave
-    constexpr int YCH = TN / 8, YROWS = 64 / YCH, YI = YCH / 4;   // dY: chunks per row, rows per DMA instruction, instructions per wave
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int Nw = g.M, Kw = g.N, T = g.K;
-    int bid = blockIdx.x;
-    const int S = g.splitk > 1 ? g.splitk : 1;
-    const int slice = bid % S;
-    bid /= S;
-    const int tn_ = bid / g.tiles_n, tk_ = bid - tn_ * g.tiles_n;
-    const int n0 = tn_ * TN, k0 = tk_ * 256;
-    const int n_live = Nw - n0 < TN ? Nw - n0 : TN, k_live = Kw - k0 < 256 ? Kw - k0 : 256;   // columns inside dW: > 0, multiples of 8
-    const int nnf = (n_live + 15) >> 4;                       // live n fragments
-    int nkf = (k_live - wave * 64 + 15) >> 4;                 // live k fragments of this wave
-    nkf = nkf < 0 ? 0 : nkf > 4 ? 4 : nkf;
-
-    // DMA.  dY: lane -> (row = YROWS * instr + lane / YCH, chunk' = lane % YCH); X: as gemm_tn_kernel per sub-tile;
-    // source chunk = chunk' ^ swz(row).  A lane whose source chunk lies in a dead fragment issues nothing.
+    // DMA sources.  A lane whose source chunk lies in a dead fragment issues nothing (LIVE).
     const uint16_t* ysrc[YI];
-    const uint16_t* xsrc[8];
-    int xtap[8], xrow[8];                                     // GATHER: in place of xsrc
+    const uint16_t* xsrc[XI];
+    int xtap[XI], xrow[XI];                                   // GATHER: in place of xsrc
     unsigned ylive = 0, xlive = 0;
 #pragma unroll
     for (int j = 0; j < YI; ++j) {
-        const int row = (j * 4 + wave) * YROWS + lane / YCH;
-        const int c = ((lane % YCH) ^ tn_swz<TN>(row)) * 8;
+        int row, c;
+        tn_dma_lane<D::YC, D::YPI>(j, wave, lane, row, c);
         ylive |= (unsigned)((c & ~15) < n_live) << j;
         ysrc[j] = g.a0 + (long long)row * g.lda0 + n0 + (c < n_live ? c : n_live - 8);
     }
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const int row = ((j & 3) * 4 + wave) * 4 + (lane >> 4);
-        const int c = (j >> 2) * 128 + (((lane & 15) ^ tn_swz(row)) << 3);
+    for (int j = 0; j < XI; ++j) {
+        int row, c;
+        tn_dma_lane<128, D::XPI>(j, wave, lane, row, c);
         xlive |= (unsigned)((c & ~15) < k_live) << j;
         const int ck = k0 + (c < k_live ? c : k_live - 8);
         if constexpr (GATHER) {                               // the chunk's tap and channel: ky | kx << 2 | ci << 4
@@ -1953,21 +1890,32 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_narrow_kernel(GemmArgs g, Q...
             xsrc[j] = g.w + (long long)row * g.lda1 + xoff;
         }
     }
-    auto issue = [&](int tt, int buf) {
-        unsigned char* Xt = smem + buf * BUF;
-        unsigned char* Yt = Xt + 2 * XSUB;
+    auto ydma = [&](int s, unsigned char* Yt, int j) {
+        if (D::LIVE && ((j / D::YPI) * D::YC >= n_live || !(ylive >> j & 1))) return;     // the first test is wave-uniform
+        __builtin_amdgcn_global_load_lds((gptr_t)(ysrc[j] + (long long)s * TB * g.lda0),
+                                         (lptr_t)(Yt + (j / D::YPI) * D::YSUB + ((j % D::YPI) * 4 + wave) * 1024), 16, 0, 0);
+    };
+    auto xdma = [&](int s, unsigned char* Xt, int j) {
+        if (D::LIVE && ((j / D::XPI) * 128 >= k_live || !(xlive >> j & 1))) return;
+        const uint16_t* xs;
+        if constexpr (GATHER) xs = conv_gather_src(q, s * TB + xrow[j], xtap[j] & 3, xtap[j] >> 2 & 3, xtap[j] >> 4);
+        else xs = xsrc[j] + (long long)s * TB * g.lda1;
+        __builtin_amdgcn_global_load_lds((gptr_t)xs, (lptr_t)(Xt + (j / D::XPI) * D::XSUB + ((j % D::XPI) * 4 + wave) * 1024), 16, 0, 0);
+    };
+    constexpr int Y_AT = D::Y_FIRST ? 0 : D::XS * D::XSUB, X_AT = D::Y_FIRST ? D::YS * D::YSUB : 0;   // the operands inside a buffer
+    auto issue = [&](int s, int buf) {
+        unsigned char* Yt = smem + buf * D::BUF + Y_AT;
+        unsigned char* Xt = smem + buf * D::BUF + X_AT;
+        if constexpr (D::ALTERNATE) {
+            static_assert(!D::ALTERNATE || YI == XI, "instructions in turns");
 #pragma unroll
-        for (int j = 0; j < YI; ++j)
-            if (ylive >> j & 1)
-                __builtin_amdgcn_global_load_lds((gptr_t)(ysrc[j] + (long long)tt * TB * g.lda0), (lptr_t)(Yt + (j * 4 + wave) * 1024), 16, 0, 0);
+            for (int j = 0; j < YI; ++j) { ydma(s, Yt, j); xdma(s, Xt, j); }
+        } else {
 #pragma unroll
-        for (int j = 0; j < 8; ++j)
-            if (xlive >> j & 1) {
-                const uint16_t* xs;
-                if constexpr (GATHER) xs = conv_gather_src(q, tt * TB + xrow[j], xtap[j] & 3, xtap[j] >> 2 & 3, xtap[j] >> 4);
-                else xs = xsrc[j] + (long long)tt * TB * g.lda1;
-                __builtin_amdgcn_global_load_lds((gptr_t)xs, (lptr_t)(Xt + (j >> 2) * XSUB + ((j & 3) * 4 + wave) * 1024), 16, 0, 0);
-            }
+            for (int j = 0; j < YI; ++j) ydma(s, Yt, j);
+#pragma unroll
+            for (int j = 0; j < XI; ++j) xdma(s, Xt, j);
+        }
     };
     f32x4 acc[4][NF];                                         // [k fragment][n fragment]
 #pragma unroll
@@ -1975,30 +1923,29 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_narrow_kernel(GemmArgs g, Q...
 #pragma unroll
         for (int j = 0; j < NF; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
     const int fi = lane & 15, mg = lane >> 4;
-    const int nt_all = T / TB;
-    const int t0 = (int)((long long)nt_all * slice / S), t1 = (int)((long long)nt_all * (slice + 1) / S);
-    if (t0 < t1) {
-        issue(t0, 0);
+    const int nt_all = T / 64;                                // slices are whole 64-token tiles; stages of TB tokens
+    const int s0 = 64 / TB * (int)((long long)nt_all * slice / S), s1 = 64 / TB * (int)((long long)nt_all * (slice + 1) / S);
+    if (s0 < s1) {
+        issue(s0, 0);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
     }
-    // the token walk of a wave with NK live k fragments and NN live n fragments, one branch-free loop per pair (a wave with
-    // runtime guards around each read and MFMA holds the whole workgroup back at the barrier: measured)
+    // the token walk of a wave with NK live k fragments and NN live n fragments
     auto walk = [&](auto nk, auto nn) {
         constexpr int NK = decltype(nk)::value, NN = decltype(nn)::value;
-        for (int tt = t0; tt < t1; ++tt) {
-            const int cur = (tt - t0) & 1;
-            if (tt + 1 < t1) issue(tt + 1, cur ^ 1);
-            const unsigned char* Xt = smem + cur * BUF + (wave >> 1) * XSUB;
-            const unsigned char* Yt = smem + cur * BUF + 2 * XSUB;
+        for (int s = s0; s < s1; ++s) {
+            const int cur = (s - s0) & 1;
+            if (s + 1 < s1) issue(s + 1, cur ^ 1);
             if constexpr (NK > 0) {
+                const unsigned char* Yt = smem + cur * D::BUF + Y_AT + wn * NF * 16 / D::YC * D::YSUB;   // the wave's images
+                const unsigned char* Xt = smem + cur * D::BUF + X_AT + wk * 64 / 128 * D::XSUB;
 #pragma unroll
-                for (int ks = 0; ks < 2; ++ks) {
+                for (int ks = 0; ks < TB / 32; ++ks) {
                     bf16x8 fx[NK], fy[NN];
 #pragma unroll
-                    for (int i = 0; i < NK; ++i) fx[i] = tr_frag(Xt, ks, lane, (wave & 1) * 64 + i * 16);
+                    for (int i = 0; i < NK; ++i) fx[i] = tr_frag(Xt, ks, lane, wk * 64 % 128 + i * 16);
 #pragma unroll
-                    for (int j = 0; j < NN; ++j) fy[j] = tr_frag<TN>(Yt, ks, lane, j * 16);
+                    for (int j = 0; j < NN; ++j) fy[j] = tr_frag<D::YC>(Yt, ks, lane, wn * NF * 16 % D::YC + j * 16);
 #pragma unroll
                     for (int i = 0; i < NK; ++i)
 #pragma unroll
@@ -2010,163 +1957,24 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_narrow_kernel(GemmArgs g, Q...
             __syncthreads();
         }
     };
-    auto by_n = [&](auto nk) {                                // nnf = 1 .. NF
-        if constexpr (decltype(nk)::value == 0) walk(nk, std::integral_constant<int, 1>{});
-        else if constexpr (NF == 2) { if (nnf == 2) walk(nk, std::integral_constant<int, 2>{}); else walk(nk, std::integral_constant<int, 1>{}); }
-        else switch (nnf) {
-            case 4: walk(nk, std::integral_constant<int, 4>{}); break;
-            case 3: walk(nk, std::integral_constant<int, 3>{}); break;
-            case 2: walk(nk, std::integral_constant<int, 2>{}); break;
-            default: walk(nk, std::integral_constant<int, 1>{});
-        }
-    };
-    switch (nkf) {                                            // 0 .. 4
-        case 4: by_n(std::integral_constant<int, 4>{}); break;
-        case 3: by_n(std::integral_constant<int, 3>{}); break;
-        case 2: by_n(std::integral_constant<int, 2>{}); break;
-        case 1: by_n(std::integral_constant<int, 1>{}); break;
-        default: by_n(std::integral_constant<int, 0>{});
+    if constexpr (D::LIVE) {
+        auto by_n = [&](auto nk) {
+            if constexpr (decltype(nk)::value == 0) walk(nk, std::integral_constant<int, 1>{});
+            else {
+                auto with_n = [&](auto nn) { walk(nk, nn); };
+                tn_dispatch<1, NF>(nnf, with_n);
+            }
+        };
+        tn_dispatch<0, 4>(nkf, by_n);
+    } else {
+        walk(std::integral_constant<int, 4>{}, std::integral_constant<int, NF>{});
     }
     // D[row = k (lane>>4)*4 + reg][col = n (lane&15)]  ->  dW[n][k..k+3]
     float* out = S > 1 ? g.partial + (long long)slice * Nw * Kw : (float*)g.out;
     const long long ldo = S > 1 ? Kw : g.ldo;
 #pragma unroll
     for (int j = 0; j < NF; ++j) {
-        const int n = n0 + j * 16 + fi;
-        if (n >= Nw) continue;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int k = k0 + wave * 64 + i * 16 + mg * 4;
-            if (k < Kw) *(float4*)(out + (long long)n * ldo + k) = make_float4(acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]);
-        }
-    }
-}
-
-// The same product for large dW (wgrad_wide_route picks it; opt-in): 256 (n) x 128 (k) output tiles, so a
-// workgroup moves 24 KB through the LDS-DMA path per 32 tokens where two 128 x 128 workgroups move 32 KB for the same MFMAs.
-//   Stage: 32 tokens = dY as TWO [32][128] sub-tiles + X as ONE, each in gemm_tn_kernel's layout (256-byte rows, tn_swz<128>;
-//   the swizzle and tr_frag's row mapping repeat every 32 rows, so a stage reads as step ks = 0 of a 64-token tile): 24 KB, two
-//   of them (48 KB), the DMA of stage s + 1 issued before the MFMAs of stage s and drained (vmcnt(0)) at the stage's only barrier,
-//   as gemm_tn_kernel does per 64 tokens (a ring of three with a counted wait measured equal or slower).  Wave w owns n columns 128 (w / 2) .. + 127 (dY sub-tile w / 2) x k columns 64 (w % 2) .. + 63:
-//   8 x 4 fragments, 32 accumulators, 32 MFMAs per stage as gemm_tn_kernel has per 32 tokens.
-//   Edges as gemm_tn_narrow_kernel: no DMA, LDS read or MFMA for a 16-column fragment wholly past N or K (one branch-free loop
-//   per wave-uniform pair of live counts); chunks past N / K inside a live fragment clamp to N - 8 / K - 8.
-// Summation: the MFMA, tr_frag's token-to-slot mapping per 32 tokens, the ascending token walk and the slice boundaries (whole
-// 64-token tiles, t0 = nt * slice / S) are gemm_tn_kernel's: for an equal slice count the results are bit-identical.
-__global__ __launch_bounds__(256, 2) void gemm_tn_wide_kernel(GemmArgs g) {
-    constexpr int TB = 32, SUB = TB * 256, STAGE = 3 * SUB;   // bytes: a [32][128] sub-tile; dY sub-tiles 0 and 1, then X
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int Nw = g.M, Kw = g.N, T = g.K;
-    int bid = blockIdx.x;
-    const int S = g.splitk > 1 ? g.splitk : 1;
-    const int slice = bid % S;
-    bid /= S;
-    const int tn_ = bid / g.tiles_n, tk_ = bid - tn_ * g.tiles_n;
-    const int n0 = tn_ * 256, k0 = tk_ * 128;
-    const int n_live = Nw - n0 < 256 ? Nw - n0 : 256, k_live = Kw - k0 < 128 ? Kw - k0 : 128;   // columns inside dW: > 0, multiples of 8
-    const int wn = wave >> 1, wk = wave & 1;
-    int nnf = (n_live - wn * 128 + 15) >> 4;                  // live n fragments of this wave
-    nnf = nnf < 0 ? 0 : nnf > 8 ? 8 : nnf;
-    int nkf = (k_live - wk * 64 + 15) >> 4;                   // live k fragments of this wave
-    nkf = nkf < 0 ? 0 : nkf > 4 ? 4 : nkf;
-    const int ysubs = n_live > 128 ? 2 : 1;                   // dY sub-tiles with a live column
-
-    // DMA.  lane -> (row = 4 * instr + lane / 16, chunk' = lane % 16) of a sub-tile, source chunk = chunk' ^ swz(row); two
-    // instructions per wave and sub-tile.  A lane whose source chunk lies in a dead fragment issues nothing.
-    const uint16_t* ysrc[4];
-    const uint16_t* xsrc[2];
-    unsigned ylive = 0, xlive = 0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int row = ((j & 1) * 4 + wave) * 4 + (lane >> 4);          // 0..31
-        const int c = (j >> 1) * 128 + (((lane & 15) ^ tn_swz(row)) << 3);
-        ylive |= (unsigned)((c & ~15) < n_live) << j;
-        ysrc[j] = g.a0 + (long long)row * g.lda0 + n0 + (c < n_live ? c : n_live - 8);
-    }
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int row = (j * 4 + wave) * 4 + (lane >> 4);
-        const int c = ((lane & 15) ^ tn_swz(row)) << 3;
-        xlive |= (unsigned)((c & ~15) < k_live) << j;
-        xsrc[j] = g.w + (long long)row * g.lda1 + k0 + (c < k_live ? c : k_live - 8);
-    }
-    auto issue = [&](int s, int buf) {
-        unsigned char* Yt = smem + buf * STAGE;
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if ((j >> 1) < ysubs)                             // wave-uniform: nothing is issued for a sub-tile past N
-                if (ylive >> j & 1)
-                    __builtin_amdgcn_global_load_lds((gptr_t)(ysrc[j] + (long long)s * TB * g.lda0),
-                                                     (lptr_t)(Yt + (j >> 1) * SUB + ((j & 1) * 4 + wave) * 1024), 16, 0, 0);
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-            if (xlive >> j & 1)
-                __builtin_amdgcn_global_load_lds((gptr_t)(xsrc[j] + (long long)s * TB * g.lda1),
-                                                 (lptr_t)(Yt + 2 * SUB + (j * 4 + wave) * 1024), 16, 0, 0);
-    };
-    f32x4 acc[4][8];                                          // [k fragment][n fragment]
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    const int fi = lane & 15, mg = lane >> 4;
-    const int nt_all = T / 64;
-    const int s0 = 2 * (int)((long long)nt_all * slice / S), s1 = 2 * (int)((long long)nt_all * (slice + 1) / S);   // 32-token stages
-    if (s0 < s1) {
-        issue(s0, 0);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-    }
-    auto walk = [&](auto nk, auto nn) {
-        constexpr int NK = decltype(nk)::value, NN = decltype(nn)::value;
-        for (int s = s0; s < s1; ++s) {
-            const int cur = (s - s0) & 1;
-            if (s + 1 < s1) issue(s + 1, cur ^ 1);
-            if constexpr (NK > 0) {
-                const unsigned char* Yt = smem + cur * STAGE + wn * SUB;
-                const unsigned char* Xt = smem + cur * STAGE + 2 * SUB;
-                bf16x8 fx[NK], fy[NN];
-#pragma unroll
-                for (int i = 0; i < NK; ++i) fx[i] = tr_frag(Xt, 0, lane, wk * 64 + i * 16);
-#pragma unroll
-                for (int j = 0; j < NN; ++j) fy[j] = tr_frag(Yt, 0, lane, j * 16);
-#pragma unroll
-                for (int i = 0; i < NK; ++i)
-#pragma unroll
-                    for (int j = 0; j < NN; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fx[i], fy[j], acc[i][j], 0, 0, 0);
-            }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-        }
-    };
-    auto by_n = [&](auto nk) {                                // nnf = 1 .. 8
-        switch (nnf) {
-            case 8: walk(nk, std::integral_constant<int, 8>{}); break;
-            case 7: walk(nk, std::integral_constant<int, 7>{}); break;
-            case 6: walk(nk, std::integral_constant<int, 6>{}); break;
-            case 5: walk(nk, std::integral_constant<int, 5>{}); break;
-            case 4: walk(nk, std::integral_constant<int, 4>{}); break;
-            case 3: walk(nk, std::integral_constant<int, 3>{}); break;
-            case 2: walk(nk, std::integral_constant<int, 2>{}); break;
-            default: walk(nk, std::integral_constant<int, 1>{});
-        }
-    };
-    if (nnf == 0) nkf = 0;                                    // a wave with no live fragment only feeds the DMA
-    switch (nkf) {                                            // 0 .. 4
-        case 4: by_n(std::integral_constant<int, 4>{}); break;
-        case 3: by_n(std::integral_constant<int, 3>{}); break;
-        case 2: by_n(std::integral_constant<int, 2>{}); break;
-        case 1: by_n(std::integral_constant<int, 1>{}); break;
-        default: walk(std::integral_constant<int, 0>{}, std::integral_constant<int, 1>{});
-    }
-    // D[row = k (lane>>4)*4 + reg][col = n (lane&15)]  ->  dW[n][k..k+3]
-    float* out = S > 1 ? g.partial + (long long)slice * Nw * Kw : (float*)g.out;
-    const long long ldo = S > 1 ? Kw : g.ldo;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const int n = n0 + wn * 128 + j * 16 + fi;
+        const int n = n0 + wn * NF * 16 + j * 16 + fi;
         if (n >= Nw) continue;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -2175,6 +1983,13 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_wide_kernel(GemmArgs g) {
         }
     }
 }
+__global__ __launch_bounds__(256, 2) void gemm_tn_kernel(GemmArgs g) { gemm_tn_body<Tn128, false>(g, ConvGather{}); }
+__global__ __launch_bounds__(256, 2) void gemm_tn_gather_kernel(GemmArgs g, ConvGather q) { gemm_tn_body<Tn128, true>(g, q); }
+template <int TN>
+__global__ __launch_bounds__(256, 2) void gemm_tn_narrow_kernel(GemmArgs g) { gemm_tn_body<TnNarrow<TN>, false>(g, ConvGather{}); }
+template <int TN>
+__global__ __launch_bounds__(256, 2) void gemm_tn_narrow_gather_kernel(GemmArgs g, ConvGather q) { gemm_tn_body<TnNarrow<TN>, true>(g, q); }
+__global__ __launch_bounds__(256, 2) void gemm_tn_wide_kernel(GemmArgs g) { gemm_tn_body<TnWide, false>(g, ConvGather{}); }
 
 // ---------------------------------------------------------------------------------------------
 // Skinny-M linear (M <= 256: one row per crop - the classifier's last-block tail on the cls rows, and its head).  Such a product
@@ -3080,15 +2895,30 @@ extern "C" int yv_linear_nn(const void* A, int lda, const void* Wkn, int ldw, co
     return launch_dma<128, 128, 2, 2, 0, true>(g, (hipStream_t)stream);
 }
 
+static bool wgrad_tile_ok(int tile_n) { return tile_n == 0 || tile_n == 32 || tile_n == 64 || tile_n == 128; }
+static bool wgrad_shape_ok(int T, int N, int K) { return T > 0 && N > 0 && K > 0 && !((T & 63) || (N & 7) || (K & 7)); }
 static bool wgrad_args_ok(const void* dY, int ldy, const void* X, int ldx, int T, int N, int K, const float* dW, int ldw) {
-    if (!dY || !X || !dW || T <= 0 || N <= 0 || K <= 0) return false;
-    if ((T & 63) || (N & 7) || (K & 7) || (ldy & 7) || (ldx & 7) || (ldw & 3)) return false;
+    if (!dY || !X || !dW || !wgrad_shape_ok(T, N, K) || (ldy & 7) || (ldx & 7) || (ldw & 3)) return false;
     return !(((uintptr_t)dY | (uintptr_t)X | (uintptr_t)dW) & 15);
 }
+// the split-K workspace registered for the stream (yv_set_workspace); none: no bytes
+struct StreamWs { void* ptr = nullptr; size_t bytes = 0; };
+static StreamWs stream_ws(void* stream) {
+    StreamWs w;
+    if (!ws_lookup(stream, &w.ptr, &w.bytes)) w.bytes = 0;
+    return w;
+}
 
-// Launches the route: no decisions.  ws: the workspace the route was told of.
+// The instances of gemm_tn_body: tile_n of the route -> dynamic LDS bytes and kernel, plain and gather form (no wide gather form)
+constexpr int TN_TILE[4] = {128, 64, 32, 256};
+constexpr size_t TN_LDS[4] = {Tn128::LDS, TnNarrow<64>::LDS, TnNarrow<32>::LDS, TnWide::LDS};
+static const void* const TN_KERNEL[2][4] = {
+    {(const void*)gemm_tn_kernel, (const void*)gemm_tn_narrow_kernel<64>, (const void*)gemm_tn_narrow_kernel<32>, (const void*)gemm_tn_wide_kernel},
+    {(const void*)gemm_tn_gather_kernel, (const void*)gemm_tn_narrow_gather_kernel<64>, (const void*)gemm_tn_narrow_gather_kernel<32>, nullptr}};
+
+// Launches the route: no decisions.  ws: the workspace the route was told of.  q: the gather form (X lies behind q->x; seg_len = 0).
 static int wgrad_launch(const void* dY, int ldy, const void* X, int ldx, int T, int N, int K, float* dW, int ldw, int seg_len,
-                        long long seg_stride, const WgradRoute& r, void* ws, void* stream) {
+                        long long seg_stride, const WgradRoute& r, void* ws, void* stream, const ConvGather* q = nullptr) {
     GemmArgs g = {};
     g.seg_len = seg_len; g.seg_stride = seg_stride;
     g.a0 = (const uint16_t*)dY; g.lda0 = ldy; g.w = (const uint16_t*)X; g.lda1 = ldx;
@@ -3096,23 +2926,21 @@ static int wgrad_launch(const void* dY, int ldy, const void* X, int ldx, int T, 
     g.tiles_m = (N + r.tile_n - 1) / r.tile_n; g.tiles_n = (K + r.tile_k - 1) / r.tile_k;
     g.splitk = r.slices;
     if (g.splitk > 1) g.partial = (float*)ws;
-    using Kern = void (*)(GemmArgs);
-    Kern kern = r.tile_n == 256 ? gemm_tn_wide_kernel
-                : r.tile_n == 128 ? gemm_tn_kernel : r.tile_n == 64 ? (Kern)gemm_tn_narrow_kernel<64> : (Kern)gemm_tn_narrow_kernel<32>;
-    const size_t lds = r.tile_n == 256 ? 2 * 3 * 32 * 256
-                       : r.tile_n == 128 ? 2 * 2 * 64 * 256 : 2 * (2 * 64 * 256 + 64 * r.tile_n * 2);
-    if (r.tile_n != 128 && !yv_grant_lds((const void*)kern, lds)) return YV_ERR_LAUNCH;
-    hipLaunchKernelGGL(kern, dim3(r.workgroups), dim3(256), lds, (hipStream_t)stream, g);
+    int t = 0;
+    while (t < 4 && TN_TILE[t] != r.tile_n) ++t;
+    const void* kern = t < 4 ? TN_KERNEL[q != nullptr][t] : nullptr;
+    if (!kern) return YV_ERR_ARG;                                 // no route names such a tile
+    if (!yv_grant_lds(kern, TN_LDS[t])) return YV_ERR_LAUNCH;
+    void* args[2] = {&g, (void*)q};
+    hipLaunchKernel(kern, dim3(r.workgroups), dim3(256), args, TN_LDS[t], (hipStream_t)stream);
     return launch_splitk_reduce(g, (hipStream_t)stream);
 }
 
 static int wgrad_impl(const void* dY, int ldy, const void* X, int ldx, int T, int N, int K, float* dW, int ldw, int seg_len,
                       long long seg_stride, int tile_n, void* stream) {
-    if (!wgrad_args_ok(dY, ldy, X, ldx, T, N, K, dW, ldw)) return YV_ERR_ARG;
-    if (tile_n != 0 && tile_n != 32 && tile_n != 64 && tile_n != 128) return YV_ERR_ARG;
-    void* ws = nullptr; size_t wsb = 0;
-    if (!ws_lookup(stream, &ws, &wsb)) wsb = 0;
-    return wgrad_launch(dY, ldy, X, ldx, T, N, K, dW, ldw, seg_len, seg_stride, wgrad_route(T, N, K, tile_n, wsb, 0), ws, stream);
+    if (!wgrad_args_ok(dY, ldy, X, ldx, T, N, K, dW, ldw) || !wgrad_tile_ok(tile_n)) return YV_ERR_ARG;
+    const StreamWs ws = stream_ws(stream);
+    return wgrad_launch(dY, ldy, X, ldx, T, N, K, dW, ldw, seg_len, seg_stride, wgrad_route(T, N, K, tile_n, ws.bytes, 0), ws.ptr, stream);
 }
 
 extern "C" int yv_wgrad(const void* dY, int ldy, const void* X, int ldx, int T, int N, int K, float* dW, int ldw,
@@ -3126,9 +2954,7 @@ extern "C" int yv_wgrad_tiled(const void* dY, int ldy, const void* X, int ldx, i
 }
 
 extern "C" int yv_wgrad_route(int T, int N, int K, int tile_n, size_t ws_bytes, int n_cu, yv_wgrad_route_t* out) {
-    if (!out || T <= 0 || N <= 0 || K <= 0 || n_cu < 0) return YV_ERR_ARG;
-    if ((T & 63) || (N & 7) || (K & 7)) return YV_ERR_ARG;
-    if (tile_n != 0 && tile_n != 32 && tile_n != 64 && tile_n != 128) return YV_ERR_ARG;
+    if (!out || n_cu < 0 || !wgrad_shape_ok(T, N, K) || !wgrad_tile_ok(tile_n)) return YV_ERR_ARG;
     *out = wgrad_route(T, N, K, tile_n, ws_bytes, n_cu);
     return YV_OK;
 }
@@ -3136,14 +2962,12 @@ extern "C" int yv_wgrad_route(int T, int N, int K, int tile_n, size_t ws_bytes, 
 extern "C" int yv_wgrad_wide(const void* dY, int ldy, const void* X, int ldx, int T, int N, int K, float* dW, int ldw, int mode,
                              void* stream) {
     if (!wgrad_args_ok(dY, ldy, X, ldx, T, N, K, dW, ldw) || (mode != 0 && mode != 1)) return YV_ERR_ARG;
-    void* ws = nullptr; size_t wsb = 0;
-    if (!ws_lookup(stream, &ws, &wsb)) wsb = 0;
-    return wgrad_launch(dY, ldy, X, ldx, T, N, K, dW, ldw, 0, 0, wgrad_wide_route(T, N, K, mode, wsb, 0), ws, stream);
+    const StreamWs ws = stream_ws(stream);
+    return wgrad_launch(dY, ldy, X, ldx, T, N, K, dW, ldw, 0, 0, wgrad_wide_route(T, N, K, mode, ws.bytes, 0), ws.ptr, stream);
 }
 
 extern "C" int yv_wgrad_wide_route(int T, int N, int K, int mode, size_t ws_bytes, int n_cu, yv_wgrad_route_t* out) {
-    if (!out || T <= 0 || N <= 0 || K <= 0 || n_cu < 0 || (mode != 0 && mode != 1)) return YV_ERR_ARG;
-    if ((T & 63) || (N & 7) || (K & 7)) return YV_ERR_ARG;
+    if (!out || n_cu < 0 || (mode != 0 && mode != 1) || !wgrad_shape_ok(T, N, K)) return YV_ERR_ARG;
     *out = wgrad_wide_route(T, N, K, mode, ws_bytes, n_cu);
     return YV_OK;
 }
@@ -3173,10 +2997,10 @@ extern "C" int yv_wgrad_conv3_tiled(const void* dYp, int ldy, const void* Xp, in
 // YOLOv8s and YOLOv8n at 16 x 640^2 with either tile (x 0.53 - 0.94, profiles/wgrad_gather_layers.txt), so 1 everywhere
 // (DESIGN.md section 26).
 static bool gather_grid_ok(int B, int Hin, int Win, int stride, int Cin, int N, int tile_n) {
-    if (B <= 0 || Hin <= 0 || Win <= 0 || !(stride == 1 || stride == 2) || Cin < 8 || (Cin & 7) || N <= 0 || (N & 7)) return false;
-    if (tile_n != 0 && tile_n != 32 && tile_n != 64 && tile_n != 128) return false;
+    if (B <= 0 || Hin <= 0 || Win <= 0 || !(stride == 1 || stride == 2) || Cin < 8 || !wgrad_tile_ok(tile_n)) return false;
     const long long T = (long long)B * ((Hin - 1) / stride + 1) * ((Win - 1) / stride + 1);
-    return T <= (1LL << 31) - 64 && 9LL * Cin < (1LL << 31);
+    if (T > (1LL << 31) - 64 || 9LL * Cin >= (1LL << 31)) return false;
+    return wgrad_shape_ok((int)((T + 63) & ~63LL), N, 9 * Cin);      // 9 * Cin % 8 == 0: Cin % 8 == 0
 }
 
 extern "C" int yv_wgrad_conv3_gather_route(int B, int Hin, int Win, int stride, int Cin, int N, int tile_n, size_t ws_bytes, int n_cu,
@@ -3201,22 +3025,8 @@ extern "C" int yv_wgrad_conv3_gather(const void* dY, int ldy, const void* X, lon
     if (((uintptr_t)dY | (uintptr_t)X | (uintptr_t)dW) & 15) return YV_ERR_ARG;
     const ConvGather q = conv_gather_of(X, ldx, B, Hin, Win, stride, Cin);
     const int T = (q.T + 63) & ~63, K = 9 * Cin;
-    void* ws = nullptr; size_t wsb = 0;
-    if (!ws_lookup(stream, &ws, &wsb)) wsb = 0;
-    const WgradRoute r = wgrad_route(T, N, K, tile_n, wsb, 0);
-    GemmArgs g = {};
-    g.a0 = (const uint16_t*)dY; g.lda0 = ldy;
-    g.M = N; g.N = K; g.K = T; g.out = dW; g.ldo = ldw; g.flags = YV_EPI_OUT_F32;
-    g.tiles_m = (N + r.tile_n - 1) / r.tile_n; g.tiles_n = (K + r.tile_k - 1) / r.tile_k;
-    g.splitk = r.slices;
-    if (g.splitk > 1) g.partial = (float*)ws;
-    using Kern = void (*)(GemmArgs, ConvGather);
-    Kern kern = r.tile_n == 128 ? gemm_tn_gather_kernel
-                : r.tile_n == 64 ? (Kern)gemm_tn_narrow_kernel<64, true> : (Kern)gemm_tn_narrow_kernel<32, true>;
-    const size_t lds = r.tile_n == 128 ? 2 * 2 * 64 * 256 : 2 * (2 * 64 * 256 + 64 * r.tile_n * 2);
-    if (!yv_grant_lds((const void*)kern, lds)) return YV_ERR_LAUNCH;
-    hipLaunchKernelGGL(kern, dim3(r.workgroups), dim3(256), lds, (hipStream_t)stream, g, q);
-    return launch_splitk_reduce(g, (hipStream_t)stream);
+    const StreamWs ws = stream_ws(stream);
+    return wgrad_launch(dY, ldy, nullptr, 0, T, N, K, dW, ldw, 0, 0, wgrad_route(T, N, K, tile_n, ws.bytes, 0), ws.ptr, stream, &q);
 }
 
 extern "C" int yv_conv2d(const yv_view* in0, const yv_view* in1, int B, int Hout, int Wout, int ksize, int stride,
