@@ -1,7 +1,7 @@
 """CPU emulation of the MXFP8 fine-tune recipe (VitTrainer(dtype="mxfp8")) and the synthetic task of its convergence test.
 
 The four block linears of every transformer block run all three GEMMs on dequantised MX operands (the rule of
-yv_quant_mxfp8, pinned by test_gpu_fp8.py::emulate_quant), each quantised along its reduction axis:
+yv_quant_mxfp8, pinned to mx_reference.py::emulate_quant by test_gpu_fp8.py), each quantised along its reduction axis:
     forward         Y  = q(X) . q(W)^T            X, W quantised along in-features
     data gradient   dX = q(dY) . q(W^T)^T         dY, W^T quantised along out-features
     weight gradient dW = q(dY^T) . q(X^T)^T       dY^T, X^T quantised along tokens (zero-padded to a multiple of 32)
@@ -11,7 +11,7 @@ from __future__ import annotations
 import torch
 import torch.nn.functional as F
 
-from test_gpu_fp8 import emulate_quant
+from mx_reference import emulate_quant
 
 
 def mx_deq(x: torch.Tensor) -> torch.Tensor:

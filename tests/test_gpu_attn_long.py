@@ -229,6 +229,28 @@ def test_attention_long_mxfp8_equals_out_then_quant(yv, R, N, H):
     assert bool((q[live:] == 0xA5).all()) and bool((s[:, live:] == 0x5B).all())
 
 
+def test_attention_long_mxfp8_zero_head(yv):
+    """V of one head is zero: that head's two blocks of every row are all-zero blocks - scale byte 0, zero bytes (the -127 branch of
+    the block exponent, csrc/mx_quant.h); the other heads equal the bf16 output followed by yv_quant_mxfp8."""
+    R, N, H, zh = 1, 785, 4, 1
+    D = H * 64
+    g = torch.Generator().manual_seed(R * 1000 + N + H + 1)
+    qkv = (torch.randn(R * N, 3 * D, generator=g) * 0.7).to(torch.bfloat16)
+    qkv[:, 2 * D + zh * 64:2 * D + (zh + 1) * 64] = 0
+    qkv = qkv.to(DEV)
+    o = torch.zeros(R * N, D, dtype=torch.bfloat16, device=DEV)
+    yv.attention_long(qkv, R, N, H, o)
+    q_ref, s_ref = yv.quant_mxfp8(o)
+    q = torch.full((R * N, D), 0xA5, dtype=torch.uint8, device=DEV)
+    s = torch.full_like(s_ref, 0x5B)
+    yv.attention_long(qkv, R, N, H, out_q=q, out_scale=s)
+    torch.cuda.synchronize()
+    assert bool((q[:, zh * 64:(zh + 1) * 64] == 0).all())
+    s_rows = s[:, :R * N].permute(1, 0, 2).reshape(R * N, D // 32)
+    assert bool((s_rows[:, 2 * zh:2 * zh + 2] == 0).all())
+    assert torch.equal(q, q_ref) and torch.equal(s[:, :R * N], s_ref[:, :R * N])
+
+
 # ------------------------------------------------------------------------------------------------ 8. engine
 @functools.lru_cache(maxsize=None)
 def _engine_case(name, R):

@@ -7,6 +7,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from mx_reference import assert_edge_blocks, dequant as dequant_map, edge_rows, emulate_quant_rows
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 
@@ -16,24 +18,6 @@ def yv():
     import yvhip
     yvhip.require_gpu()
     return yvhip
-
-
-def emulate_quant_rows(x: torch.Tensor):
-    """x (..., C) bf16-representable -> (bytes (..., C) uint8, scale bytes (..., C/32) uint8)."""
-    shp = x.shape
-    b = x.reshape(-1, shp[-1] // 32, 32).double()
-    amax = b.abs().amax(-1)
-    e = torch.where(amax > 0, torch.ceil(torch.log2((amax / 448.0).clamp_min(1e-300))), torch.full_like(amax, -127.0))
-    e = torch.where((amax > 0) & (torch.pow(2.0, e - 1) * 448.0 >= amax), e - 1, e).clamp(-127, 127)
-    q = (b * torch.pow(2.0, -e)[..., None]).float().to(torch.float8_e4m3fn)
-    return q.view(torch.uint8).reshape(shp), (e + 127).to(torch.uint8).reshape(*shp[:-1], shp[-1] // 32)
-
-
-def dequant_map(q: torch.Tensor, s: torch.Tensor) -> torch.Tensor:
-    """MX map (q (..., C), s (..., C/32)) -> f64 values."""
-    v = q.view(torch.float8_e4m3fn).double()
-    sc = torch.pow(2.0, s.double() - 127.0).repeat_interleave(32, -1)
-    return v * sc
 
 
 def dequant_weight(wq: torch.Tensor, ws: torch.Tensor) -> torch.Tensor:
@@ -196,6 +180,27 @@ def test_conv2d_mxfp8_mx_output_is_quantised_bf16_output(yv, ci):
     # the MX map alone (no bf16 store): the same bytes
     _, _, _, only_mx, _, _ = _run_case(yv, case, seed=ci, mx_out=True, bf16_out=False)
     assert torch.equal(only_mx[0], q) and torch.equal(only_mx[1], s)
+
+
+@pytest.mark.parametrize("bf16_out", [True, False])
+def test_conv2d_mxfp8_mx_output_edge_blocks(yv, bf16_out):
+    """1 x 1, stride 1, identity weight, zero bias, no SiLU on the dequantised image of a planted tensor (mx_reference.edge_rows: the
+    blocks where the exponent rule's branches decide the byte): every output is one exact product, so the MX-map output is the CPU
+    reference of the input, with and without the bf16 store.  Ragged M (169 pixels), three blocks per pixel."""
+    B, H, C = 1, 13, 96
+    x = edge_rows(B * H * H, C, seed=13, exact=True)
+    assert_edge_blocks(x)
+    qb, sb = emulate_quant_rows(x)
+    m = yv.mx_map(B, H, H, C, DEV)
+    yv.quant_mxfp8_map(x.view(B, H, H, C).to(torch.bfloat16).to(DEV), m)
+    wq, ws = yv.quant_conv_weight_mxfp8(torch.eye(C, dtype=torch.bfloat16, device=DEV))
+    out = torch.zeros(B, H, H, C, dtype=torch.bfloat16, device=DEV) if bf16_out else None
+    out_mx = yv.mx_map(B, H, H, C, DEV)
+    yv.conv2d_mxfp8(yv.mx_view(m, 0, C), None, B, H, H, 1, 1, wq, ws, torch.zeros(C, device=DEV), out, 0, 0, out_mx=out_mx)
+    torch.cuda.synchronize()
+    assert torch.equal(out_mx[0].cpu().view(-1, C), qb) and torch.equal(out_mx[1].cpu().view(-1, C // 32), sb)
+    if bf16_out:
+        assert torch.equal(out.cpu().float().view(-1, C), x)
 
 
 def test_yolo_engine_rejects_unknown_dtype(yv):

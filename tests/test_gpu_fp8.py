@@ -7,6 +7,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from mx_reference import assert_edge_blocks, edge_rows, emulate_quant, scale_rows
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 
@@ -47,21 +49,6 @@ def test_mx_mfma_layout(yv):
     unit = torch.from_numpy(np.full((64,), 0x7f7f7f7f, dtype=np.uint32).view(np.int32)).to(DEV)     # 2^0 in every byte
     for op in range(4):                                      # the probe uses the same opsel for both scale operands
         assert run(ones(), ones(), packed, unit, op).unique().tolist() == [128.0 * 2 ** op]
-
-
-def emulate_quant(x: torch.Tensor):
-    """x (rows, K) bf16-representable f32 -> (bytes (rows, K) uint8, scale bytes (rows, K/32) uint8, dequantised f64)."""
-    rows, K = x.shape
-    b = x.view(rows, K // 32, 32).double()
-    amax = b.abs().amax(-1)
-    r = (amax / 448.0)
-    e = torch.where(amax > 0, torch.ceil(torch.log2(r.clamp_min(1e-300))), torch.full_like(amax, -127.0))
-    # log2 of an exact power of two is exact in f64; guard the rounding of ceil() anyway
-    e = torch.where((amax > 0) & (torch.pow(2.0, e - 1) * 448.0 >= amax), e - 1, e).clamp(-127, 127)
-    scaled = (b * torch.pow(2.0, -e)[..., None]).float()
-    q = scaled.to(torch.float8_e4m3fn)
-    deq = q.double() * torch.pow(2.0, e)[..., None]
-    return q.view(torch.uint8).view(rows, K), (e + 127).to(torch.uint8), deq.view(rows, K)
 
 
 @pytest.mark.parametrize("rows,K", [(64, 128), (197, 1024), (1000, 768), (130, 384)])
@@ -261,3 +248,89 @@ def test_attention_mxfp8_equals_attention_then_quant(yv, R, N, H):
     torch.cuda.synchronize()
     assert torch.equal(q[:live], q_ref[:live]) and torch.equal(s[:, :live], s_ref[:, :live])
     assert float(q[live:].float().abs().sum()) == 0
+
+
+# ---- edge blocks at the fused producers -------------------------------------------------------------------------------------
+# Every fused producer is run on operands for which its bf16 operation is exactly the identity, so the expected bytes are the
+# CPU reference (mx_reference) of a planted tensor that holds the blocks where the exponent rule's branches decide the byte: all
+# zero, amax +-448 * 2^k (k = -3, 0, 5), amax 2^-20, amax 8 among smaller values (mx_reference.edge_rows).
+
+@pytest.mark.parametrize("M,N,inst", [(130, 128, 0), (7880, 1024, 1)])
+def test_linear_mxfp8_q_edge_blocks(yv, M, N, inst):
+    """Linear -> MXFP8 with W = identity, zero bias, no activation and A the dequantised image of the planted tensor: every output is
+    one exact product of a value that is exact in e4m3 and in bf16, so the image is mx_reference of A.  Once on the 128 x 128
+    kernel's epilogue, once on the persistent kernel's (N = K = 1024 reaches it from 7521 rows on; the 7880 rows repeat 394 planted ones)."""
+    assert yv.linear_mxfp8_instance(M, N, N) == inst
+    base = edge_rows(min(M, 394), N, seed=M, exact=True)
+    assert_edge_blocks(base)
+    qb, sb, _ = emulate_quant(base)
+    rep = M // base.shape[0]
+    assert rep * base.shape[0] == M
+    a = base.repeat(rep, 1).to(torch.bfloat16).to(DEV)
+    aq, asc = yv.quant_mxfp8(a)
+    wq, wsc = yv.quant_mxfp8(torch.eye(N, dtype=torch.bfloat16, device=DEV))
+    q = torch.full((M, N), 0xA5, dtype=torch.uint8, device=DEV)
+    s = torch.full_like(asc, 0x5B)
+    yv.linear_mxfp8_q(aq, asc, wq, wsc, torch.zeros(N, device=DEV), q, s)
+    torch.cuda.synchronize()
+    assert torch.equal(q.cpu(), qb.repeat(rep, 1))
+    assert torch.equal(scale_rows(s.cpu(), M), sb.repeat(rep, 1))
+
+
+@pytest.mark.parametrize("D", [128, 1024])
+def test_layernorm_mxfp8_edge_blocks(yv, D):
+    """LayerNorm -> MXFP8 with gamma = 0 and beta = one planted row: every live row is beta exactly.  The device-side row count
+    cuts inside the last workgroup's four rows."""
+    rows, per, live = 302, 99, 297                               # 297 = 74 * 4 + 1
+    g = torch.Generator().manual_seed(D)
+    x = (torch.randn(rows, D, generator=g) * 3 + 0.5).to(DEV)
+    cnt = torch.tensor([3], dtype=torch.int32, device=DEV)
+    planted = edge_rows(-(-7 * 32 // D), D, seed=D)               # as many rows as hold the edge blocks once
+    assert_edge_blocks(planted)
+    qb, sb = emulate_quant(planted)[:2]
+    for i in range(planted.shape[0]):
+        q = torch.full((rows, D), 0xA5, dtype=torch.uint8, device=DEV)
+        s = torch.full((D // 128, 512, 4), 0x5B, dtype=torch.uint8, device=DEV)
+        yv.layernorm_mxfp8(x, torch.zeros(D, device=DEV), planted[i].to(DEV), q, s, rows, D, D, count_dev=cnt, rows_per_count=per)
+        torch.cuda.synchronize()
+        assert torch.equal(q[:live].cpu(), qb[i].expand(live, D))
+        assert torch.equal(scale_rows(s.cpu(), live), sb[i].expand(live, D // 32))
+        assert bool((q[live:] == 0xA5).all()) and bool((s[:, live:] == 0x5B).all())      # rows past the count stay untouched
+
+
+def test_attention_mxfp8_edge_blocks_one_token(yv):
+    """Attention -> MXFP8 at N = 1 (attention_pipe_kernel<1>): the softmax of one score is 1, the output is V exactly."""
+    R, H = 5, 4
+    D = H * 64
+    g = torch.Generator().manual_seed(7)
+    v = edge_rows(R, D, seed=3)
+    assert_edge_blocks(v)
+    qkv = (torch.randn(R, 3 * D, generator=g) * 0.7).to(torch.bfloat16)
+    qkv[:, 2 * D:] = v.to(torch.bfloat16)
+    qb, sb = emulate_quant(v)[:2]
+    q = torch.full((R, D), 0xA5, dtype=torch.uint8, device=DEV)
+    s = torch.full((D // 128, 128, 4), 0x5B, dtype=torch.uint8, device=DEV)
+    yv.attention_mxfp8(qkv.to(DEV), R, 1, H, q, s)
+    torch.cuda.synchronize()
+    assert torch.equal(q.cpu(), qb) and torch.equal(scale_rows(s.cpu(), R), sb)
+
+
+def test_attention_mxfp8_zero_head(yv):
+    """Attention -> MXFP8 at N = 785 (attention_kernel, online softmax): V of one head is zero, so that head's two blocks of every
+    row are all-zero blocks - scale byte 0, zero bytes; the other heads equal attention followed by yv_quant_mxfp8."""
+    R, N, H, zh = 1, 785, 4, 2
+    D = H * 64
+    g = torch.Generator().manual_seed(R * 1000 + N + H + 1)
+    qkv = (torch.randn(R * N, 3 * D, generator=g) * 0.7).to(torch.bfloat16)
+    qkv[:, 2 * D + zh * 64:2 * D + (zh + 1) * 64] = 0
+    qkv = qkv.to(DEV)
+    o = torch.zeros(R * N, D, dtype=torch.bfloat16, device=DEV)
+    yv.attention(qkv, R, N, H, o)
+    q_ref, s_ref = yv.quant_mxfp8(o)
+    q = torch.full((R * N, D), 0xA5, dtype=torch.uint8, device=DEV)
+    s = torch.full_like(s_ref, 0x5B)
+    yv.attention_mxfp8(qkv, R, N, H, q, s)
+    torch.cuda.synchronize()
+    assert bool((q[:, zh * 64:(zh + 1) * 64] == 0).all())
+    assert bool((scale_rows(s.cpu(), R * N)[:, 2 * zh:2 * zh + 2] == 0).all())
+    assert torch.equal(q, q_ref) and torch.equal(s[:, :R * N], s_ref[:, :R * N])

@@ -56,7 +56,7 @@ def test_quant_mxfp8_2d_is_byte_exact(yv, T, C, ld):
 
 # ------------------------------------------------------------------------------------------------ 2. epilogues
 def _operands(yv, M, N, K, seed):
-    from test_gpu_fp8 import emulate_quant
+    from mx_reference import emulate_quant
     g = torch.Generator().manual_seed(seed)
     a = (torch.randn(M, K, generator=g) * torch.exp(torch.randn(M, 1, generator=g))).to(torch.bfloat16)
     w = (torch.randn(N, K, generator=g) * 0.05).to(torch.bfloat16)

@@ -18,7 +18,7 @@
 //   LDS images: K rows are 128 B with the 16-byte chunk XOR-swizzled by ((row>>1)&7)
 //   (conflict-free ds_read_b128 for the 32-row A fragment); V^T rows are padded to
 //   2*NP+8 bytes (odd multiple of 8 B: conflict-free ds_read_b64 over 32 rows).
-#include "yv_common.h"
+#include "mx_quant.h"
 #include <type_traits>
 
 namespace {
@@ -255,29 +255,14 @@ __global__ __launch_bounds__(NT * 64, SINGLE ? 4 : 1) void attention_kernel(cons
             const long long row = (long long)r * N + q;
 #pragma unroll
             for (int mt = 0; mt < 2; ++mt) {
-                float f[16], amax = 0.f;
+                float f[16];
 #pragma unroll
-                for (int k = 0; k < 16; ++k) { f[k] = bf16_to_f32(f32_to_bf16(o[mt][k] * inv)); amax = fmaxf(amax, fabsf(f[k])); }
-                amax = fmaxf(amax, __shfl_xor(amax, 32, 64));
-                int e = -127;
-                if (amax > 0.f) {
-                    int ex;
-                    const float mant = frexpf(amax * (1.0f / 448.0f), &ex);
-                    e = mant == 0.5f ? ex - 1 : ex;
-                    e = e < -127 ? -127 : (e > 127 ? 127 : e);
-                }
-                const float is = ldexpf(1.0f, -e);
+                for (int k = 0; k < 16; ++k) f[k] = bf16_to_f32(f32_to_bf16(o[mt][k] * inv));
+                uint32_t p[4];
+                const int e = mx_quant_block<32>(f, p);
 #pragma unroll
-                for (int g4 = 0; g4 < 4; ++g4) {
-                    int p = 0;
-                    p = __builtin_amdgcn_cvt_pk_fp8_f32(f[4 * g4] * is, f[4 * g4 + 1] * is, p, false);
-                    p = __builtin_amdgcn_cvt_pk_fp8_f32(f[4 * g4 + 2] * is, f[4 * g4 + 3] * is, p, true);
-                    *(uint32_t*)(mx.q + row * mx.ldq + hd * HD + mt * 32 + 8 * g4 + 4 * hh) = (uint32_t)p;
-                }
-                if (hh == 0) {
-                    const int bk = hd * 2 + mt;
-                    mx.s[((long long)(bk >> 2) * mx.rows + row) * 4 + (bk & 3)] = (uint8_t)(e + 127);
-                }
+                for (int g4 = 0; g4 < 4; ++g4) *(uint32_t*)(mx.q + row * mx.ldq + hd * HD + mt * 32 + 8 * g4 + 4 * hh) = p[g4];
+                if (hh == 0) mx.s[mx_scale_kmajor(hd * 2 + mt, mx.rows, row)] = (uint8_t)(e + 127);
             }
             return;
         }
@@ -522,29 +507,14 @@ __global__ __launch_bounds__(NT * 64) void attention_pipe_kernel(const uint16_t*
                 const long long row = (long long)r * N + q;
 #pragma unroll
                 for (int mt = 0; mt < 2; ++mt) {
-                    float f[16], amax = 0.f;
+                    float f[16];
 #pragma unroll
-                    for (int k = 0; k < 16; ++k) { f[k] = bf16_to_f32(f32_to_bf16(o[mt][k] * inv)); amax = fmaxf(amax, fabsf(f[k])); }
-                    amax = fmaxf(amax, __shfl_xor(amax, 32, 64));
-                    int e = -127;
-                    if (amax > 0.f) {
-                        int ex;
-                        const float mant = frexpf(amax * (1.0f / 448.0f), &ex);
-                        e = mant == 0.5f ? ex - 1 : ex;
-                        e = e < -127 ? -127 : (e > 127 ? 127 : e);
-                    }
-                    const float is = ldexpf(1.0f, -e);
+                    for (int k = 0; k < 16; ++k) f[k] = bf16_to_f32(f32_to_bf16(o[mt][k] * inv));
+                    uint32_t p[4];
+                    const int e = mx_quant_block<32>(f, p);
 #pragma unroll
-                    for (int g4 = 0; g4 < 4; ++g4) {
-                        int pq = 0;
-                        pq = __builtin_amdgcn_cvt_pk_fp8_f32(f[4 * g4] * is, f[4 * g4 + 1] * is, pq, false);
-                        pq = __builtin_amdgcn_cvt_pk_fp8_f32(f[4 * g4 + 2] * is, f[4 * g4 + 3] * is, pq, true);
-                        *(uint32_t*)(mx.q + row * mx.ldq + hd * HD + mt * 32 + 8 * g4 + 4 * hh) = (uint32_t)pq;
-                    }
-                    if (hh == 0) {
-                        const int bk = hd * 2 + mt;
-                        mx.s[((long long)(bk >> 2) * mx.rows + row) * 4 + (bk & 3)] = (uint8_t)(e + 127);
-                    }
+                    for (int g4 = 0; g4 < 4; ++g4) *(uint32_t*)(mx.q + row * mx.ldq + hd * HD + mt * 32 + 8 * g4 + 4 * hh) = p[g4];
+                    if (hh == 0) mx.s[mx_scale_kmajor(hd * 2 + mt, mx.rows, row)] = (uint8_t)(e + 127);
                 }
             }
         } else {
@@ -609,14 +579,6 @@ int launch_attn(const uint16_t* qkv, int R, int N, int H, float scale, uint16_t*
 //   1. s[n] = q . K[n] * scale (log2 domain) into LDS, 2. block max / exp2 / sum, 3. o = sum_n p[n] V[n] / sum.
 // Every reduction has a fixed order: the result does not depend on the launch.
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ void unpack_bf16x8(const u32x4 v, float (&f)[8]) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        f[2 * i] = __uint_as_float(v[i] << 16);
-        f[2 * i + 1] = __uint_as_float(v[i] & 0xffff0000u);
-    }
-}
-
 __global__ __launch_bounds__(256) void attention_cls_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict__ qkv, int R,
                                                             int N, int H, float scale_log2, uint16_t* __restrict__ out,
                                                             const int32_t* __restrict__ r_dev) {

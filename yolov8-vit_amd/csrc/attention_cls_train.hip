@@ -20,14 +20,6 @@
 
 namespace {
 
-__device__ __forceinline__ void unpack_bf16x8(const u32x4 v, float (&f)[8]) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        f[2 * i] = __uint_as_float(v[i] << 16);
-        f[2 * i + 1] = __uint_as_float(v[i] & 0xffff0000u);
-    }
-}
-
 __device__ __forceinline__ u32x4 pack_bf16x8(const float (&f)[8]) {
     u32x4 v;
 #pragma unroll

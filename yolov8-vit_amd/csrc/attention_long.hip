@@ -17,7 +17,7 @@
 //   * a query's reduction runs over the key groups in index order whatever the grid: a crop's output does not depend on R, on the
 //     crop's index or on the launch.
 // 64-bit addressing throughout: no 2 GB limit on the tensors.
-#include "yv_common.h"
+#include "mx_quant.h"
 
 namespace {
 
@@ -185,29 +185,14 @@ __global__ __launch_bounds__(NW * 64, 2) void attention_long_kernel(const uint16
         const long long row = (long long)r * N + q;
 #pragma unroll
         for (int mt = 0; mt < 2; ++mt) {
-            float f[16], amax = 0.f;
+            float f[16];
 #pragma unroll
-            for (int k = 0; k < 16; ++k) { f[k] = bf16_to_f32(f32_to_bf16(o[mt][k] * inv)); amax = fmaxf(amax, fabsf(f[k])); }
-            amax = fmaxf(amax, __shfl_xor(amax, 32, 64));
-            int e = -127;
-            if (amax > 0.f) {
-                int ex;
-                const float mant = frexpf(amax * (1.0f / 448.0f), &ex);
-                e = mant == 0.5f ? ex - 1 : ex;
-                e = e < -127 ? -127 : (e > 127 ? 127 : e);
-            }
-            const float is = ldexpf(1.0f, -e);
+            for (int k = 0; k < 16; ++k) f[k] = bf16_to_f32(f32_to_bf16(o[mt][k] * inv));
+            uint32_t p[4];
+            const int e = mx_quant_block<32>(f, p);
 #pragma unroll
-            for (int g4 = 0; g4 < 4; ++g4) {
-                int p = 0;
-                p = __builtin_amdgcn_cvt_pk_fp8_f32(f[4 * g4] * is, f[4 * g4 + 1] * is, p, false);
-                p = __builtin_amdgcn_cvt_pk_fp8_f32(f[4 * g4 + 2] * is, f[4 * g4 + 3] * is, p, true);
-                *(uint32_t*)(mx.q + row * mx.ldq + hd * HD + mt * 32 + 8 * g4 + 4 * hh) = (uint32_t)p;
-            }
-            if (hh == 0) {
-                const int bk = hd * 2 + mt;
-                mx.s[((long long)(bk >> 2) * mx.rows + row) * 4 + (bk & 3)] = (uint8_t)(e + 127);
-            }
+            for (int g4 = 0; g4 < 4; ++g4) *(uint32_t*)(mx.q + row * mx.ldq + hd * HD + mt * 32 + 8 * g4 + 4 * hh) = p[g4];
+            if (hh == 0) mx.s[mx_scale_kmajor(hd * 2 + mt, mx.rows, row)] = (uint8_t)(e + 127);
         }
     }
     if (!out) return;

@@ -23,6 +23,7 @@
 #include <map>
 #include <mutex>
 #include "gemm_common.h"
+#include "mx_quant.h"
 
 using namespace yvgemm;
 
@@ -136,6 +137,35 @@ __device__ __forceinline__ void epilogue(const GemmArgs& g, f32x4 (&acc)[NF][MF]
 }
 
 
+// The bf16 slab of the staged epilogues: a wave's MF * 16 rows x 128 B, the 16-byte chunk index XOR-swizzled with row & 7.
+// slab_put: the four values of accumulator fragment (i, j) of lane (fr, fq); slab_row: the 8 consecutive columns ch * 8 .. of a row.
+__device__ __forceinline__ void slab_put(unsigned char* stage, int i, int j, int fr, int fq, const float* v) {
+    const int row = j * 16 + fr, c16 = i * 2 + (fq >> 1);
+    *(uint2*)(stage + row * 128 + ((c16 ^ (row & 7)) << 4) + (fq & 1) * 8) = make_uint2(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]));
+}
+__device__ __forceinline__ uint4 slab_row(const unsigned char* stage, int row, int ch) {
+    return *(const uint4*)(stage + row * 128 + ((ch ^ (row & 7)) << 4));
+}
+// a + b of 8 bf16 values each, in f32, rounded to bf16 (the bf16 shortcut / residual)
+__device__ __forceinline__ uint4 add_bf16x8(const uint4 pa, const uint4 pb) {
+    const uint32_t a[4] = {pa.x, pa.y, pa.z, pa.w}, b[4] = {pb.x, pb.y, pb.z, pb.w};
+    uint32_t o[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+        o[q] = pack_bf16x2(bf16_to_f32((uint16_t)(a[q] & 0xffff)) + bf16_to_f32((uint16_t)(b[q] & 0xffff)),
+                           bf16_to_f32((uint16_t)(a[q] >> 16)) + bf16_to_f32((uint16_t)(b[q] >> 16)));
+    return make_uint4(o[0], o[1], o[2], o[3]);
+}
+// 8 bf16 values of a lane, 32-column block shared with the lanes at xor 1 and 2 -> 8 e4m3 bytes; returns the block exponent
+__device__ __forceinline__ int mx_quant_bf16x8(const uint4 pk, uint2& q8) {
+    float f[8];
+    unpack_bf16x8((u32x4){pk.x, pk.y, pk.z, pk.w}, f);
+    uint32_t p[2];
+    const int e = mx_quant_block<1, 2>(f, p);
+    q8 = make_uint2(p[0], p[1]);
+    return e;
+}
+
 // Coalesced epilogue for 64-column wave tiles (NF == 4).  The ablation of the first version showed
 // the direct epilogue (8-byte stores, 32-byte row segments) costing 41 % of a K = 768 GEMM: the
 // output left at ~2 TB/s.  Here each wave transposes its tile through a private, XOR-swizzled LDS
@@ -178,15 +208,13 @@ __device__ __forceinline__ void epilogue_staged(const GemmArgs& g, f32x4 (&acc)[
                 for (int i = 0; i < 4; ++i) {
                     float v[4];
                     value(i, j, v, false);
-                    const int row = j * 16 + fr, c16 = i * 2 + (fq >> 1);
-                    *(uint2*)(stage + row * 128 + ((c16 ^ (row & 7)) << 4) + (fq & 1) * 8) =
-                        make_uint2(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]));
+                    slab_put(stage, i, j, fr, fq, v);
                 }
 #pragma unroll
             for (int it = 0; it < MF * 2; ++it) {
                 const int row = it * 8 + (lane >> 3), ch = lane & 7;
                 const int m = m0 + wrow_m + row, n = nb + ch * 8;
-                const uint4 pk = *(const uint4*)(stage + row * 128 + ((ch ^ (row & 7)) << 4));
+                const uint4 pk = slab_row(stage, row, ch);
                 if (m < M && n < g.N) *(uint4*)(g.aux + (long long)m * g.ldaux + n) = pk;
             }
         }
@@ -196,58 +224,24 @@ __device__ __forceinline__ void epilogue_staged(const GemmArgs& g, f32x4 (&acc)[
             for (int i = 0; i < 4; ++i) {
                 float v[4];
                 value(i, j, v);
-                const int row = j * 16 + fr, c16 = i * 2 + (fq >> 1);
-                *(uint2*)(stage + row * 128 + ((c16 ^ (row & 7)) << 4) + (fq & 1) * 8) =
-                    make_uint2(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]));
+                slab_put(stage, i, j, fr, fq, v);
             }
 #pragma unroll
         for (int it = 0; it < MF * 2; ++it) {
             const int row = it * 8 + (lane >> 3), ch = lane & 7;
             const int m = m0 + wrow_m + row, n = nb + ch * 8;
-            uint4 pk = *(const uint4*)(stage + row * 128 + ((ch ^ (row & 7)) << 4));
+            uint4 pk = slab_row(stage, row, ch);
             if (m < M && n < g.N) {
                 [[maybe_unused]] long long om = 0;
                 if constexpr (PHASE) om = phase_row<true>(g, m, ph);
-                if (flags & YV_EPI_RES_BF16) {
-                    const uint4 rr = *(const uint4*)(g.res + (PHASE ? om : (long long)m) * g.ldres + n);
-                    const uint32_t a[4] = {pk.x, pk.y, pk.z, pk.w}, b[4] = {rr.x, rr.y, rr.z, rr.w};
-                    uint32_t o[4];
-#pragma unroll
-                    for (int q = 0; q < 4; ++q)
-                        o[q] = pack_bf16x2(bf16_to_f32((uint16_t)(a[q] & 0xffff)) + bf16_to_f32((uint16_t)(b[q] & 0xffff)),
-                                           bf16_to_f32((uint16_t)(a[q] >> 16)) + bf16_to_f32((uint16_t)(b[q] >> 16)));
-                    pk = make_uint4(o[0], o[1], o[2], o[3]);
-                }
+                if (flags & YV_EPI_RES_BF16) pk = add_bf16x8(pk, *(const uint4*)(g.res + (PHASE ? om : (long long)m) * g.ldres + n));
                 if (flags & YV_EPI_OUT_MXFP8) {
                     // the consumer is another MXFP8 GEMM: quantise the 8 (bf16-rounded) values of this lane together with
                     // the 3 lanes that hold the rest of their 32-column block, skip the bf16 store
-                    const uint32_t a[4] = {pk.x, pk.y, pk.z, pk.w};
-                    float f[8];
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) { f[2 * q] = bf16_to_f32((uint16_t)(a[q] & 0xffff)); f[2 * q + 1] = bf16_to_f32((uint16_t)(a[q] >> 16)); }
-                    float amax = 0.f;
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) amax = fmaxf(amax, fabsf(f[q]));
-                    amax = fmaxf(amax, __shfl_xor(amax, 1, 64));
-                    amax = fmaxf(amax, __shfl_xor(amax, 2, 64));
-                    int e = -127;
-                    if (amax > 0.f) {
-                        int ex;
-                        const float mant = frexpf(amax * (1.0f / 448.0f), &ex);
-                        e = mant == 0.5f ? ex - 1 : ex;
-                        e = e < -127 ? -127 : (e > 127 ? 127 : e);
-                    }
-                    const float inv = ldexpf(1.0f, -e);
-                    int p0 = 0, p1 = 0;
-                    p0 = __builtin_amdgcn_cvt_pk_fp8_f32(f[0] * inv, f[1] * inv, p0, false);
-                    p0 = __builtin_amdgcn_cvt_pk_fp8_f32(f[2] * inv, f[3] * inv, p0, true);
-                    p1 = __builtin_amdgcn_cvt_pk_fp8_f32(f[4] * inv, f[5] * inv, p1, false);
-                    p1 = __builtin_amdgcn_cvt_pk_fp8_f32(f[6] * inv, f[7] * inv, p1, true);
-                    *(uint2*)(g.mxq + (long long)m * g.ldmxq + n) = make_uint2((uint32_t)p0, (uint32_t)p1);
-                    if ((ch & 3) == 0) {
-                        const int bk = n >> 5;
-                        g.mxs[((long long)(bk >> 2) * g.mx_rows + m) * 4 + (bk & 3)] = (uint8_t)(e + 127);
-                    }
+                    uint2 q8;
+                    const int e = mx_quant_bf16x8(pk, q8);
+                    *(uint2*)(g.mxq + (long long)m * g.ldmxq + n) = q8;
+                    if ((ch & 3) == 0) g.mxs[mx_scale_kmajor(n >> 5, g.mx_rows, m)] = (uint8_t)(e + 127);
                     continue;
                 }
                 if (flags & YV_EPI_GELU_BWD) {      // out = dg * gelu'(u), u = saved pre-activation (bf16)
@@ -1239,51 +1233,28 @@ __global__ __launch_bounds__(64) void mx_probe_kernel(const i32x8* __restrict__ 
     d[l] = acc;
 }
 
-// x (rows, K) bf16 -> q (rows, K) e4m3 bytes + scales (rows, K/32) E8M0: scale exponent e = ceil(log2(amax / 448)) of the
-// 32-element block (so that amax * 2^-e <= 448), all-zero blocks get e = -127; q = RNE_e4m3(x * 2^-e)
-__global__ __launch_bounds__(256) void quant_mx_kernel(const uint16_t* __restrict__ x, long long ldx, long long rows, int K,
-                                                       uint8_t* __restrict__ q, long long ldq, uint8_t* __restrict__ sc,
-                                                       long long rows_pad) {
+// x (rows, K) bf16 -> q (rows, K) e4m3 bytes + one E8M0 scale per 32-element block (the format: mx_quant.h), one thread per block.
+// yv_quant_mxfp8: scales K-step-major (K/128, rows_pad, 4).  yv_quant_mxfp8_map (MAP; a row is a pixel of a bf16 NHWC view, K its
+// channels): scales (pixel, C/32), ldq bytes per pixel.
+template <bool MAP>
+__device__ __forceinline__ void quant_mx_rows(const uint16_t* __restrict__ x, long long ldx, long long rows, int K,
+                                              uint8_t* __restrict__ q, long long ldq, uint8_t* __restrict__ sc, long long rows_pad) {
     const int kb = K >> 5;
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
     if (idx >= rows * kb) return;
     const long long r = idx / kb;
     const int b = (int)(idx - r * kb);
-    const uint16_t* src = x + r * ldx + b * 32;
-    float v[32];
-    float amax = 0.f;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        const uint4 u = *(const uint4*)(src + c * 8);
-        const uint32_t w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            v[c * 8 + 2 * i] = bf16_to_f32((uint16_t)(w[i] & 0xffff));
-            v[c * 8 + 2 * i + 1] = bf16_to_f32((uint16_t)(w[i] >> 16));
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 32; ++i) amax = fmaxf(amax, fabsf(v[i]));
-    int e = -127;
-    if (amax > 0.f) {
-        int ex;
-        const float mant = frexpf(amax * (1.0f / 448.0f), &ex);          // amax/448 = mant * 2^ex, mant in [0.5, 1)
-        e = mant == 0.5f ? ex - 1 : ex;                                   // ceil(log2(amax/448))
-        e = e < -127 ? -127 : (e > 127 ? 127 : e);
-    }
-    const float inv = ldexpf(1.0f, -e);
-    uint32_t out[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        int p = 0;
-        p = __builtin_amdgcn_cvt_pk_fp8_f32(v[4 * i] * inv, v[4 * i + 1] * inv, p, false);
-        p = __builtin_amdgcn_cvt_pk_fp8_f32(v[4 * i + 2] * inv, v[4 * i + 3] * inv, p, true);
-        out[i] = (uint32_t)p;
-    }
-    uint4* dst = (uint4*)(q + r * ldq + b * 32);
-    dst[0] = make_uint4(out[0], out[1], out[2], out[3]);
-    dst[1] = make_uint4(out[4], out[5], out[6], out[7]);
-    sc[((long long)(b >> 2) * rows_pad + r) * 4 + (b & 3)] = (uint8_t)(e + 127);      // (K/128, rows_pad, 4)
+    const uint8_t s = mx_quant_row32(x + r * ldx + b * 32, q + r * ldq + b * 32);
+    sc[MAP ? mx_scale_map(r, ldq, b) : mx_scale_kmajor(b, rows_pad, r)] = s;
+}
+__global__ __launch_bounds__(256) void quant_mx_kernel(const uint16_t* __restrict__ x, long long ldx, long long rows, int K,
+                                                       uint8_t* __restrict__ q, long long ldq, uint8_t* __restrict__ sc,
+                                                       long long rows_pad) {
+    quant_mx_rows<false>(x, ldx, rows, K, q, ldq, sc, rows_pad);
+}
+__global__ __launch_bounds__(256) void quant_mx_map_kernel(const uint16_t* __restrict__ x, long long ldx, long long pixels, int C,
+                                                           uint8_t* __restrict__ q, long long ldq, uint8_t* __restrict__ sc) {
+    quant_mx_rows<true>(x, ldx, pixels, C, q, ldq, sc, 0);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1304,7 +1275,7 @@ __global__ __launch_bounds__(256) void quant_mx_kernel(const uint16_t* __restric
 //   yv_quant_mxfp8 writes.  They are loaded into registers one K step ahead, behind the DMA of that step.
 //   K is zero-padded to a multiple of 128 (the weight's padding is zeros, the activation's padding blocks read zeros).
 //   Epilogue: finish_tile (bias, SiLU, bf16 shortcut, bf16 / f32 output), or - when an MX-map output is wanted - the bf16
-//   staged epilogue followed by the rule of yv_quant_mxfp8_map on the bf16-rounded values (byte-identical to the bf16
+//   staged epilogue followed by the block quantiser of mx_quant.h on the bf16-rounded values (byte-identical to the bf16
 //   output quantised afterwards), with or without the bf16 store.
 // ---------------------------------------------------------------------------------------------
 struct ConvMxArgs {
@@ -1319,18 +1290,8 @@ struct ConvMxArgs {
     int ldq;
 };
 
-// E8M0 exponent of a 32-element block: ceil(log2(amax / 448)) (all-zero blocks -127), as quant_mx_kernel
-__device__ __forceinline__ int mx_block_exp(float amax) {
-    int e = -127;
-    if (amax > 0.f) {
-        int ex;
-        const float mant = frexpf(amax * (1.0f / 448.0f), &ex);
-        e = mant == 0.5f ? ex - 1 : ex;
-        e = e < -127 ? -127 : (e > 127 ? 127 : e);
-    }
-    return e;
-}
-
+// The MX-map output of cgemm_mx_kernel: bias, SiLU and bf16 shortcut as the bf16 branch of epilogue_staged (its slab, its adds), then
+// the bf16 store (if wanted) and the block quantiser on the same bf16-rounded values.
 template <int MF>
 __device__ __forceinline__ void epilogue_conv_mx(const ConvMxArgs& a, f32x4 (&acc)[4][MF], int M, int m0, int n0,
                                                  int wrow_m, int wrow_n, int lane, unsigned char* stage) {
@@ -1350,45 +1311,20 @@ __device__ __forceinline__ void epilogue_conv_mx(const ConvMxArgs& a, f32x4 (&ac
 #pragma unroll
                 for (int q = 0; q < 4; ++q) v[q] = silu_f(v[q]);
             }
-            const int row = j * 16 + fr, c16 = i * 2 + (fq >> 1);
-            *(uint2*)(stage + row * 128 + ((c16 ^ (row & 7)) << 4) + (fq & 1) * 8) =
-                make_uint2(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]));
+            slab_put(stage, i, j, fr, fq, v);
         }
 #pragma unroll
     for (int it = 0; it < MF * 2; ++it) {
         const int row = it * 8 + (lane >> 3), ch = lane & 7;
         const int m = m0 + wrow_m + row, n = nb + ch * 8;
-        uint4 pk = *(const uint4*)(stage + row * 128 + ((ch ^ (row & 7)) << 4));
+        uint4 pk = slab_row(stage, row, ch);
         if (m < M && n < g.N) {           // (N % 32 == 0: the four lanes of a 32-channel block agree)
-            if (flags & YV_EPI_RES_BF16) {
-                const uint4 rr = *(const uint4*)(g.res + (long long)m * g.ldres + n);
-                const uint32_t x[4] = {pk.x, pk.y, pk.z, pk.w}, y[4] = {rr.x, rr.y, rr.z, rr.w};
-                uint32_t o[4];
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-                    o[q] = pack_bf16x2(bf16_to_f32((uint16_t)(x[q] & 0xffff)) + bf16_to_f32((uint16_t)(y[q] & 0xffff)),
-                                       bf16_to_f32((uint16_t)(x[q] >> 16)) + bf16_to_f32((uint16_t)(y[q] >> 16)));
-                pk = make_uint4(o[0], o[1], o[2], o[3]);
-            }
+            if (flags & YV_EPI_RES_BF16) pk = add_bf16x8(pk, *(const uint4*)(g.res + (long long)m * g.ldres + n));
             if (g.out) *(uint4*)((uint16_t*)g.out + (long long)m * g.ldo + n) = pk;
-            const uint32_t x[4] = {pk.x, pk.y, pk.z, pk.w};
-            float f[8];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) { f[2 * q] = bf16_to_f32((uint16_t)(x[q] & 0xffff)); f[2 * q + 1] = bf16_to_f32((uint16_t)(x[q] >> 16)); }
-            float amax = 0.f;
-#pragma unroll
-            for (int q = 0; q < 8; ++q) amax = fmaxf(amax, fabsf(f[q]));
-            amax = fmaxf(amax, __shfl_xor(amax, 1, 64));
-            amax = fmaxf(amax, __shfl_xor(amax, 2, 64));
-            const int e = mx_block_exp(amax);
-            const float inv = ldexpf(1.0f, -e);
-            int p0 = 0, p1 = 0;
-            p0 = __builtin_amdgcn_cvt_pk_fp8_f32(f[0] * inv, f[1] * inv, p0, false);
-            p0 = __builtin_amdgcn_cvt_pk_fp8_f32(f[2] * inv, f[3] * inv, p0, true);
-            p1 = __builtin_amdgcn_cvt_pk_fp8_f32(f[4] * inv, f[5] * inv, p1, false);
-            p1 = __builtin_amdgcn_cvt_pk_fp8_f32(f[6] * inv, f[7] * inv, p1, true);
-            *(uint2*)(a.oq + (long long)m * a.ldq + n) = make_uint2((uint32_t)p0, (uint32_t)p1);
-            if ((ch & 3) == 0) a.os[(long long)m * (a.ldq >> 5) + (n >> 5)] = (uint8_t)(e + 127);
+            uint2 q8;
+            const int e = mx_quant_bf16x8(pk, q8);
+            *(uint2*)(a.oq + (long long)m * a.ldq + n) = q8;
+            if ((ch & 3) == 0) a.os[mx_scale_map(m, a.ldq, n >> 5)] = (uint8_t)(e + 127);
         }
     }
 }
@@ -1600,68 +1536,12 @@ __global__ __launch_bounds__(256) void cgemm_mx_kernel(ConvMxArgs a) {
     else finish_tile<MF, NF>(a.g, acc, M, m0, n0, wrow_m, wrow_n, lane, wave, smem);
 }
 
-// bf16 NHWC view -> MX map (yv_quant_mxfp8_map): one thread per (pixel, 32-channel block), the arithmetic of quant_mx_kernel
-__global__ __launch_bounds__(256) void quant_mx_map_kernel(const uint16_t* __restrict__ x, long long ldx, long long pixels, int C,
-                                                           uint8_t* __restrict__ q, long long ldq, uint8_t* __restrict__ sc) {
-    const int kb = C >> 5;
-    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= pixels * kb) return;
-    const long long p = idx / kb;
-    const int b = (int)(idx - p * kb);
-    const uint16_t* src = x + p * ldx + b * 32;
-    float v[32];
-    float amax = 0.f;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        const uint4 u = *(const uint4*)(src + c * 8);
-        const uint32_t w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            v[c * 8 + 2 * i] = bf16_to_f32((uint16_t)(w[i] & 0xffff));
-            v[c * 8 + 2 * i + 1] = bf16_to_f32((uint16_t)(w[i] >> 16));
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 32; ++i) amax = fmaxf(amax, fabsf(v[i]));
-    const int e = mx_block_exp(amax);
-    const float inv = ldexpf(1.0f, -e);
-    uint32_t out[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        int pq = 0;
-        pq = __builtin_amdgcn_cvt_pk_fp8_f32(v[4 * i] * inv, v[4 * i + 1] * inv, pq, false);
-        pq = __builtin_amdgcn_cvt_pk_fp8_f32(v[4 * i + 2] * inv, v[4 * i + 3] * inv, pq, true);
-        out[i] = (uint32_t)pq;
-    }
-    uint4* dst = (uint4*)(q + p * ldq + b * 32);
-    dst[0] = make_uint4(out[0], out[1], out[2], out[3]);
-    dst[1] = make_uint4(out[4], out[5], out[6], out[7]);
-    sc[p * (ldq >> 5) + b] = (uint8_t)(e + 127);
-}
-
-// 32 bf16-representable values -> 8 dwords of e4m3 bytes; returns the block exponent (the arithmetic of quant_mx_kernel)
-__device__ __forceinline__ int mx_quant32(const float (&v)[32], uint32_t (&out)[8]) {
-    float amax = 0.f;
-#pragma unroll
-    for (int i = 0; i < 32; ++i) amax = fmaxf(amax, fabsf(v[i]));
-    const int e = mx_block_exp(amax);
-    const float inv = ldexpf(1.0f, -e);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        int pq = 0;
-        pq = __builtin_amdgcn_cvt_pk_fp8_f32(v[4 * i] * inv, v[4 * i + 1] * inv, pq, false);
-        pq = __builtin_amdgcn_cvt_pk_fp8_f32(v[4 * i + 2] * inv, v[4 * i + 3] * inv, pq, true);
-        out[i] = (uint32_t)pq;
-    }
-    return e;
-}
-
 // Two-form quantiser (yv_quant_mxfp8_2d; the MX trainer's operands).  A workgroup stages a tile of 64 rows (t) x 128 columns
 // (c) of the bf16 input in LDS (rows past T read as zeros) and writes, from the one read:
-//   row form:    thread (row tid / 4, block tid % 4): the 32-column block of quant_mx_kernel - bytes and scale identical;
+//   row form:    thread (row tid / 4, block tid % 4): one 32-column block through mx_quant_row32, the body of quant_mx_kernel;
 //   column form: thread (column tid % 128, half tid / 128): the 32 rows of that column as one MX block of the TRANSPOSE, i.e.
 //                bytes (C, T_pad) (row stride ldqt) and scales K-step-major along t, (T_pad/128, c_rows_pad, 4) - what
-//                quant_mx_kernel writes for x^T padded with zero rows up to T_pad (the weight-gradient operands).
+//                yv_quant_mxfp8 writes for x^T padded with zero rows up to T_pad (the weight-gradient operands).
 // LDS rows are 272 bytes (16-byte pad): the row-form reads of a wave (16 rows x 4 blocks) spread over the banks; the column-form
 // reads of a wave are 64 consecutive bf16 of one row.
 __global__ __launch_bounds__(256) void quant_mx_2d_kernel(const uint16_t* __restrict__ x, long long ldx, long long T, int C,
@@ -1685,23 +1565,8 @@ __global__ __launch_bounds__(256) void quant_mx_2d_kernel(const uint16_t* __rest
         const int r = tid >> 2, b = tid & 3;
         const long long t = t0 + r;
         if (t < T) {
-            float v[32];
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                const uint4 u = *(const uint4*)(tile + r * PITCH + b * 64 + c * 16);
-                const uint32_t w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    v[c * 8 + 2 * i] = bf16_to_f32((uint16_t)(w[i] & 0xffff));
-                    v[c * 8 + 2 * i + 1] = bf16_to_f32((uint16_t)(w[i] >> 16));
-                }
-            }
-            uint32_t out[8];
-            const int e = mx_quant32(v, out);
-            uint4* dst = (uint4*)(q + t * ldq + c0 + b * 32);
-            dst[0] = make_uint4(out[0], out[1], out[2], out[3]);
-            dst[1] = make_uint4(out[4], out[5], out[6], out[7]);
-            sc[((long long)(c0 >> 7) * rows_pad + t) * 4 + b] = (uint8_t)(e + 127);
+            const uint8_t s = mx_quant_row32((const uint16_t*)(tile + r * PITCH + b * 64), q + t * ldq + c0 + b * 32);
+            sc[mx_scale_kmajor((c0 >> 5) + b, rows_pad, t)] = s;
         }
     }
     if (qt) {
@@ -1710,12 +1575,12 @@ __global__ __launch_bounds__(256) void quant_mx_2d_kernel(const uint16_t* __rest
 #pragma unroll
         for (int i = 0; i < 32; ++i) v[i] = bf16_to_f32(*(const uint16_t*)(tile + (h * 32 + i) * PITCH + c * 2));
         uint32_t out[8];
-        const int e = mx_quant32(v, out);
+        const int e = mx_quant_block(v, out);
         const long long tb = (t0 >> 5) + h;                      // 32-row block of t
         uint4* dst = (uint4*)(qt + (long long)(c0 + c) * ldqt + tb * 32);
         dst[0] = make_uint4(out[0], out[1], out[2], out[3]);
         dst[1] = make_uint4(out[4], out[5], out[6], out[7]);
-        sct[((tb >> 2) * c_rows_pad + c0 + c) * 4 + (tb & 3)] = (uint8_t)(e + 127);
+        sct[mx_scale_kmajor((int)tb, c_rows_pad, c0 + c)] = (uint8_t)(e + 127);
     }
 }
 

@@ -2,6 +2,7 @@
 // launchers and tuning options.  GemmArgs and the conventions of the family: gemm_common.h, gemm.hip.
 #include <type_traits>
 #include "gemm_common.h"
+#include "mx_quant.h"
 
 using namespace yvgemm;
 
@@ -842,11 +843,11 @@ __global__ __launch_bounds__(512) void gemm_p9_kernel(GemmArgs g) {
                 }
             } else if (MX && (g.flags & YV_EPI_OUT_MXFP8)) {
                 // the consumer is another MXFP8 GEMM (fc1 -> fc2): the lane's 16 consecutive (bf16-rounded) outputs + the 16 of lane ^ 16
-                // are one 32-column MX block; same arithmetic as the 128 x 128 kernel's epilogue (byte-identical images)
+                // are one 32-column MX block; the quantiser of mx_quant.h, as the 128 x 128 kernel's epilogue (byte-identical images)
 #pragma unroll
                 for (int j = 0; j < MF; ++j) {
                     const int m = m0 + wrow_m + j * 16 + fr;
-                    float f[16], amax = 0.f;
+                    float f[16];
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
                         float v0 = acc[i][j][0] + bv[i].x, v1 = acc[i][j][1] + bv[i].y;
@@ -855,32 +856,12 @@ __global__ __launch_bounds__(512) void gemm_p9_kernel(GemmArgs g) {
                         f[4 * i] = bf16_to_f32(f32_to_bf16(v0)); f[4 * i + 1] = bf16_to_f32(f32_to_bf16(v1));
                         f[4 * i + 2] = bf16_to_f32(f32_to_bf16(v2)); f[4 * i + 3] = bf16_to_f32(f32_to_bf16(v3));
                     }
-#pragma unroll
-                    for (int q = 0; q < 16; ++q) amax = fmaxf(amax, fabsf(f[q]));
-                    amax = fmaxf(amax, __shfl_xor(amax, 16, 64));
-                    int e = -127;
-                    if (amax > 0.f) {
-                        int ex;
-                        const float mant = frexpf(amax * (1.0f / 448.0f), &ex);
-                        e = mant == 0.5f ? ex - 1 : ex;
-                        e = e < -127 ? -127 : (e > 127 ? 127 : e);
-                    }
-                    const float inv = ldexpf(1.0f, -e);
                     uint32_t q4[4];
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        int pq = 0;
-                        pq = __builtin_amdgcn_cvt_pk_fp8_f32(f[4 * i] * inv, f[4 * i + 1] * inv, pq, false);
-                        pq = __builtin_amdgcn_cvt_pk_fp8_f32(f[4 * i + 2] * inv, f[4 * i + 3] * inv, pq, true);
-                        q4[i] = (uint32_t)pq;
-                    }
+                    const int e = mx_quant_block<16>(f, q4);
                     if (m < M) {
                         const int n = n0 + wrow_n + fq * 16;
                         *(uint4*)(g.mxq + (long long)m * g.ldmxq + n) = make_uint4(q4[0], q4[1], q4[2], q4[3]);
-                        if (!(fq & 1)) {
-                            const int bk = n >> 5;
-                            g.mxs[((long long)(bk >> 2) * g.mx_rows + m) * 4 + (bk & 3)] = (uint8_t)(e + 127);
-                        }
+                        if (!(fq & 1)) g.mxs[mx_scale_kmajor(n >> 5, g.mx_rows, m)] = (uint8_t)(e + 127);
                     }
                 }
             } else {

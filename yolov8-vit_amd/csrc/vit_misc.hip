@@ -8,7 +8,7 @@
 // layernorm_kernel's summation order (lane l adds float4 chunks l, l + 64, ... as (x + y) + (z + w), then wave_sum's xor butterfly)
 // is a contract: gemm_res_ln_kernel (gemm_res_ln.hip) reproduces it so that the fused and the unfused classifier agree bit for bit
 // (tests/test_gpu_fused_ln.py::test_linear_res_ln_random).  Change the two together.
-#include "yv_common.h"
+#include "mx_quant.h"
 
 namespace {
 
@@ -106,30 +106,14 @@ __global__ __launch_bounds__(256) void layernorm_mx_kernel(const float* __restri
         if (c >= nch) continue;                                   // D is a multiple of 128: whole 8-lane groups drop out
         const float4 g = ((const float4*)gamma)[c], b = ((const float4*)beta)[c];
         // the bf16 rounding of the unfused path is kept, so both paths quantise the same numbers
-        const float o0 = bf16_to_f32(f32_to_bf16((v[i].x - mean) * rstd * g.x + b.x));
-        const float o1 = bf16_to_f32(f32_to_bf16((v[i].y - mean) * rstd * g.y + b.y));
-        const float o2 = bf16_to_f32(f32_to_bf16((v[i].z - mean) * rstd * g.z + b.z));
-        const float o3 = bf16_to_f32(f32_to_bf16((v[i].w - mean) * rstd * g.w + b.w));
-        float amax = fmaxf(fmaxf(fabsf(o0), fabsf(o1)), fmaxf(fabsf(o2), fabsf(o3)));
-        amax = fmaxf(amax, __shfl_xor(amax, 1, 64));
-        amax = fmaxf(amax, __shfl_xor(amax, 2, 64));
-        amax = fmaxf(amax, __shfl_xor(amax, 4, 64));
-        int e = -127;
-        if (amax > 0.f) {
-            int ex;
-            const float mant = frexpf(amax * (1.0f / 448.0f), &ex);
-            e = mant == 0.5f ? ex - 1 : ex;
-            e = e < -127 ? -127 : (e > 127 ? 127 : e);
-        }
-        const float inv = ldexpf(1.0f, -e);
-        int p = 0;
-        p = __builtin_amdgcn_cvt_pk_fp8_f32(o0 * inv, o1 * inv, p, false);
-        p = __builtin_amdgcn_cvt_pk_fp8_f32(o2 * inv, o3 * inv, p, true);
-        *(uint32_t*)(q + (size_t)row * ldq + 4 * c) = (uint32_t)p;
-        if ((lane & 7) == 0) {
-            const int bk = c >> 3;
-            sc[((long long)(bk >> 2) * rows_pad + row) * 4 + (bk & 3)] = (uint8_t)(e + 127);
-        }
+        const float o[4] = {bf16_to_f32(f32_to_bf16((v[i].x - mean) * rstd * g.x + b.x)),
+                            bf16_to_f32(f32_to_bf16((v[i].y - mean) * rstd * g.y + b.y)),
+                            bf16_to_f32(f32_to_bf16((v[i].z - mean) * rstd * g.z + b.z)),
+                            bf16_to_f32(f32_to_bf16((v[i].w - mean) * rstd * g.w + b.w))};
+        uint32_t p[1];
+        const int e = mx_quant_block<1, 2, 4>(o, p);
+        *(uint32_t*)(q + (size_t)row * ldq + 4 * c) = p[0];
+        if ((lane & 7) == 0) sc[mx_scale_kmajor(c >> 3, rows_pad, row)] = (uint8_t)(e + 127);
     }
 }
 
