@@ -3,7 +3,8 @@
 one K/V tile, alternating in one process.
 
   python3 tools/attn_long_bench.py            kernels: (R, N, H) in (32, 785, 12), (128, 785, 12), (64, 577, 12), (64, 577, 16)
-  python3 tools/attn_long_bench.py e2e        the classifier alone (VitEngine.backbone + head, vit_base_patch8_224, 32 and 128
+  python3 tools/attn_long_bench.py kernels RxNxH ...   the same on the shapes given, e.g. 64x197x12 (both entry points take any N)
+  python3 tools/attn_long_bench.py e2e       the classifier alone (VitEngine.backbone + head, vit_base_patch8_224, 32 and 128
                                               crops, bf16 and mxfp8) with long_attn off and on
 
 Each arm is warmed, then the arms take turns in batches of launches timed with device events until each has at least 0.5 s of
@@ -51,9 +52,9 @@ def rel_l2(a, b):
     return float((a.double() - b.double()).norm() / b.double().norm())
 
 
-def kernels():
+def kernels(shapes=SHAPES):
     print(f"# yv_attention (parent kernel) and yv_attention_long, alternating; >= {SECONDS} s of launches per arm")
-    for R, N, H in SHAPES:
+    for R, N, H in shapes:
         D = H * 64
         g = torch.Generator().manual_seed(N + H)
         qkv = (torch.randn(R * N, 3 * D, generator=g) * 1.5).to(torch.bfloat16).to(dev)
@@ -116,4 +117,9 @@ def e2e():
 
 
 if __name__ == "__main__":
-    e2e() if sys.argv[1:] == ["e2e"] else kernels()
+    if sys.argv[1:] == ["e2e"]:
+        e2e()
+    elif sys.argv[1:2] == ["kernels"] and sys.argv[2:]:
+        kernels([tuple(int(v) for v in a.split("x")) for a in sys.argv[2:]])
+    else:
+        kernels()

@@ -6,28 +6,14 @@
 // rescale and each wave computes its full 32 x N score block in registers; longer sequences (ViT-B/8:
 // 785 tokens) walk 256-row K/V tiles with running max / sum.
 //
-// MFMA plan (v_mfma_f32_32x32x16_bf16, accumulators in f32):
-//   S^T tile = K_tile (A: 32 keys x 64 d) . Q^T (B: 64 d x 32 queries)
-//     -> the accumulator has the KEY on the register axis and the QUERY on the lane,
-//        so the softmax row-reduction is in-lane + one lane^32 exchange, and
-//   O^T = V^T (A: 64 d x keys) . P^T (B: keys x 32 queries)
-//     takes the exponentiated accumulator registers directly as its B operand
-//     (registers 8s..8s+7 -> k-step s; k order inside a step is
-//      16s + 8(j>>2) + 4h + (j&3), matched by the V^T fragment addressing): P never
-//     touches LDS.
-//   LDS images: K rows are 128 B with the 16-byte chunk XOR-swizzled by ((row>>1)&7)
-//   (conflict-free ds_read_b128 for the 32-row A fragment); V^T rows are padded to
-//   2*NP+8 bytes (odd multiple of 8 B: conflict-free ds_read_b64 over 32 rows).
-#include "mx_quant.h"
+// The MFMA plan, the LDS images (swizzled K rows, padded V^T rows, row-major swizzled V for the transposing read), the softmax
+// group step and the output formats are csrc/attention_fwd_core.h, shared with attention_long.hip.
+#include "attention_fwd_core.h"
 #include <type_traits>
 
 namespace {
 
-constexpr int HD = 64;
 int g_attn_abl = 0;               // diagnostic builds (yv_attention_debug)
-
-// optional MXFP8 image of the output (operand of the proj GEMM of yv_linear_mxfp8): e4m3 bytes + E8M0 per 32 columns
-struct AttnMx { uint8_t* q; long long ldq; uint8_t* s; long long rows; };
 
 // SINGLE (N <= NP, the ViT-x/16 case: 197 tokens in one 224-row tile): the 32-key score groups are consumed one at a time with
 // an online softmax (running max / sum per query, O rescaled only when some row's maximum really grew - typically 2-3 of the
@@ -58,10 +44,8 @@ __global__ __launch_bounds__(NT * 64, SINGLE ? 4 : 1) void attention_kernel(cons
     // ---- Q fragments (B operand), straight from global --------------------------------------
     const int rl = lane & 31, hh = lane >> 5;
     const int q = qb * NP + wave * 32 + rl;
-    const int qc = q < N ? q : N - 1;
     bf16x8 fq[4];
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) fq[ks] = *(const bf16x8*)(base + (size_t)qc * ld + ks * 16 + hh * 8);
+    q_frags(base, q, N, ld, hh, fq);
 
     f32x16 o[2];
 #pragma unroll
@@ -82,7 +66,7 @@ __global__ __launch_bounds__(NT * 64, SINGLE ? 4 : 1) void attention_kernel(cons
 #pragma unroll
         for (int i = 0; i < TRIPS; ++i) {
             const int it = tid + i * T;
-            const int kl = (it < NP * 8 ? it : NP * 8 - 1) >> 3, c = it & 7;
+            const int kl = row_chunk(it < NP * 8 ? it : NP * 8 - 1).row, c = row_chunk(it).c;
             int key = kv0 + kl;
             key = key < N ? key : N - 1;
             kvr[i] = vvr[i] = make_uint4(0, 0, 0, 0);
@@ -95,8 +79,8 @@ __global__ __launch_bounds__(NT * 64, SINGLE ? 4 : 1) void attention_kernel(cons
         for (int i = 0; i < TRIPS; ++i) {
             const int it = tid + i * T;
             if (it >= NP * 8) break;
-            const int kl = it >> 3, c = it & 7;
-            *(uint4*)(Ks + kl * 128 + ((c ^ ((kl >> 1) & 7)) << 4)) = kvr[i];
+            const auto [kl, c] = row_chunk(it);
+            *(uint4*)(Ks + k_off(kl, c)) = kvr[i];
             const uint32_t w[4] = {vvr[i].x, vvr[i].y, vvr[i].z, vvr[i].w};
             if (ABL != 3) {
 #pragma unroll
@@ -113,58 +97,10 @@ __global__ __launch_bounds__(NT * 64, SINGLE ? 4 : 1) void attention_kernel(cons
             float l_lane = 0.f;                               // this lane's share of the row sum (lane ^ 32 holds the rest)
 #pragma unroll 1
             for (int kt = 0; kt < NT; ++kt) {                // rolled: unrolled, the scheduler hoists every group's MFMAs again
-                f32x16 sv;
-#pragma unroll
-                for (int e = 0; e < 16; ++e) sv[e] = 0.f;
-                const int row = kt * 32 + rl;
-#pragma unroll
-                for (int ks = 0; ks < 4; ++ks) {
-                    const int c = 2 * ks + hh;
-                    const bf16x8 fk = *(const bf16x8*)(Ks + row * 128 + ((c ^ ((row >> 1) & 7)) << 4));
-                    sv = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fk, fq[ks], sv, 0, 0, 0);
-                }
-                if (kt * 32 + 32 > N) {
-#pragma unroll
-                    for (int e = 0; e < 16; ++e) {
-                        const int key = kt * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh;
-                        sv[e] = key < N ? sv[e] : -INFINITY;
-                    }
-                }
-                float mx = sv[0];
-#pragma unroll
-                for (int e = 1; e < 16; ++e) mx = fmaxf(mx, sv[e]);
-                mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-                const float m_new = fmaxf(m_run, mx);        // group 0 holds valid keys for every row -> finite from then on
-                if (__any(m_new > m_run)) {                  // wave-uniform: some query's maximum grew
-                    const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * scale_log2e);   // 1 for unchanged rows, 0 at the start
-                    l_lane *= alpha;
-#pragma unroll
-                    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-                        for (int e = 0; e < 16; ++e) o[mt][e] *= alpha;
-                    m_run = m_new;
-                }
-                const float mb = m_run * scale_log2e;
-#pragma unroll
-                for (int e = 0; e < 16; ++e) {
-                    sv[e] = __builtin_amdgcn_exp2f(fmaf(sv[e], scale_log2e, -mb));
-                    l_lane += sv[e];
-                }
-#pragma unroll
-                for (int st = 0; st < 2; ++st) {
-                    bf16x8 fp;
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) fp[j] = (__bf16)sv[8 * st + j];
-                    const int key0 = kt * 32 + 16 * st + 4 * hh;
-#pragma unroll
-                    for (int mt = 0; mt < 2; ++mt) {
-                        const unsigned char* vr = Vt + (mt * 32 + rl) * VT_STRIDE + key0 * 2;
-                        const uint2 lo = *(const uint2*)vr;
-                        const uint2 hi = *(const uint2*)(vr + 16);
-                        const u32x4 pk = {lo.x, lo.y, hi.x, hi.y};
-                        o[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, pk), fp, o[mt], 0, 0, 0);
-                    }
-                }
+                f32x16 sv = score_group(Ks, kt * 32, fq, rl, hh);
+                if (kt * 32 + 32 > N) mask_group(sv, kt * 32, N, hh);
+                online_step(sv, m_run, l_lane, o, scale_log2e);
+                pv_product(sv, o, [&](int mt, int st) __attribute__((always_inline)) { return vt_frag_padded(Vt, VT_STRIDE, mt, kt * 32 + 16 * st, rl, hh); });
             }
             l_run = l_lane + __shfl_xor(l_lane, 32, 64);
             continue;
@@ -176,13 +112,8 @@ __global__ __launch_bounds__(NT * 64, SINGLE ? 4 : 1) void attention_kernel(cons
         for (int kt = 0; kt < NT; ++kt) {
 #pragma unroll
             for (int e = 0; e < 16; ++e) s[kt][e] = 0.f;
-            const int row = kt * 32 + rl;
 #pragma unroll
-            for (int ks = 0; ks < 4; ++ks) {
-                const int c = 2 * ks + hh;
-                const bf16x8 fk = *(const bf16x8*)(Ks + row * 128 + ((c ^ ((row >> 1) & 7)) << 4));
-                s[kt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fk, fq[ks], s[kt], 0, 0, 0);
-            }
+            for (int ks = 0; ks < 4; ++ks) s[kt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(k_frag(Ks, kt * 32 + rl, ks, hh), fq[ks], s[kt], 0, 0, 0);
         }
 
         // ---- online softmax over this tile's keys (register axis + lane^32) -----------------
@@ -190,13 +121,7 @@ __global__ __launch_bounds__(NT * 64, SINGLE ? 4 : 1) void attention_kernel(cons
         float mx = -INFINITY;
 #pragma unroll
         for (int kt = 0; kt < NT; ++kt) {
-            if (kv0 + kt * 32 + 32 > N) {
-#pragma unroll
-                for (int e = 0; e < 16; ++e) {
-                    const int key = kv0 + kt * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh;
-                    s[kt][e] = key < N ? s[kt][e] : -INFINITY;
-                }
-            }
+            if (kv0 + kt * 32 + 32 > N) mask_group(s[kt], kv0 + kt * 32, N, hh);
 #pragma unroll
             for (int e = 0; e < 16; ++e) mx = fmaxf(mx, s[kt][e]);
         }
@@ -228,53 +153,20 @@ __global__ __launch_bounds__(NT * 64, SINGLE ? 4 : 1) void attention_kernel(cons
         for (int kt = 0; kt < NT; ++kt) {
 #pragma unroll
             for (int st = 0; st < 2; ++st) {
-                bf16x8 fp;
+                const bf16x8 fp = p_frag(s[kt], st);
 #pragma unroll
-                for (int j = 0; j < 8; ++j) fp[j] = (__bf16)s[kt][8 * st + j];
-                const int key0 = kt * 32 + 16 * st + 4 * hh;
-#pragma unroll
-                for (int mt = 0; mt < 2; ++mt) {
-                    const unsigned char* vr = Vt + (mt * 32 + rl) * VT_STRIDE + key0 * 2;
-                    const uint2 lo = *(const uint2*)vr;
-                    const uint2 hi = *(const uint2*)(vr + 16);
-                    const u32x4 pk = {lo.x, lo.y, hi.x, hi.y};
-                    const bf16x8 fv = __builtin_bit_cast(bf16x8, pk);
-                    o[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fv, fp, o[mt], 0, 0, 0);
-                }
+                for (int mt = 0; mt < 2; ++mt)
+                    o[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vt_frag_padded(Vt, VT_STRIDE, mt, kt * 32 + 16 * st, rl, hh), fp, o[mt], 0, 0, 0);
             }
         }
     }
 
-    // ---- normalise and store: lane owns d = 32mt + 8g + 4hh .. +3 of its query -------------
+    // ---- normalise and store -----------------------------------------------------------------
     if (q < N) {
-        if (lse && hh == 0) lse[((size_t)r * H + hd) * N + q] = m_run * scale_log2e + log2f(l_run);   // log2 domain
+        store_lse(lse, r, H, hd, N, q, hh, m_run * scale_log2e, l_run);
         const float inv = 1.0f / l_run;
-        if (mx.q) {
-            // a head's 64 columns are two MX blocks (d 0..31 = mt 0, d 32..63 = mt 1); a query's values of one block sit
-            // in this lane and in lane ^ 32; the bf16 rounding of the ordinary output is kept
-            const long long row = (long long)r * N + q;
-#pragma unroll
-            for (int mt = 0; mt < 2; ++mt) {
-                float f[16];
-#pragma unroll
-                for (int k = 0; k < 16; ++k) f[k] = bf16_to_f32(f32_to_bf16(o[mt][k] * inv));
-                uint32_t p[4];
-                const int e = mx_quant_block<32>(f, p);
-#pragma unroll
-                for (int g4 = 0; g4 < 4; ++g4) *(uint32_t*)(mx.q + row * mx.ldq + hd * HD + mt * 32 + 8 * g4 + 4 * hh) = p[g4];
-                if (hh == 0) mx.s[mx_scale_kmajor(hd * 2 + mt, mx.rows, row)] = (uint8_t)(e + 127);
-            }
-            return;
-        }
-        uint16_t* orow = out + ((size_t)r * N + q) * D + hd * HD;
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-            for (int g4 = 0; g4 < 4; ++g4) {
-                const int d = mt * 32 + 8 * g4 + 4 * hh;
-                *(uint2*)(orow + d) = make_uint2(pack_bf16x2(o[mt][4 * g4] * inv, o[mt][4 * g4 + 1] * inv),
-                                                 pack_bf16x2(o[mt][4 * g4 + 2] * inv, o[mt][4 * g4 + 3] * inv));
-            }
+        if (mx.q) store_mx(o, inv, mx, r, N, hd, q, hh);
+        else store_direct(out + ((size_t)r * N + q) * D + hd * HD, o, inv, hh);
     }
 }
 
@@ -286,9 +178,7 @@ __global__ __launch_bounds__(NT * 64, SINGLE ? 4 : 1) void attention_kernel(cons
 //     8 rows per wave and tensor pair; no staging registers, no LDS stores, V is NOT transposed: the PV product's A operand
 //     (V^T: 32 d x 16 keys) is read from the row-major image with the transposing LDS read ds_read_b64_tr_b16 (two per fragment:
 //     keys kb + 4h + 0..3 and kb + 8 + 4h + 0..3 - the k order the exponentiated accumulator registers have);
-//   * images: K chunk ^ ((row >> 1) & 7) (conflict-free ds_read_b128 of the 32-row A fragment, as before); V chunk ^ 4 ((row >> 1) & 1):
-//     a 32-lane half of the transposing read takes rows q = 0..3 of a 4-key block, 64 bytes each; rows 0 / 2 (and 1 / 3) start
-//     on the same bank and the swizzle sends them to opposite halves of the 128-byte row.  Swizzles act on the DMA's SOURCE chunk;
+//   * images: k_chunk / v_chunk of attention_fwd_core.h; the swizzles act on the DMA's SOURCE chunk;
 //   * one workgroup per CU (140 KB of LDS at NT = 7), so a wave may hold all NT score groups (16 NT registers): one softmax pass,
 //     no running maximum, no rescale;
 //   * one barrier per item: behind it item i has landed for every wave AND every wave is done with item i-1, whose buffer the
@@ -296,10 +186,7 @@ __global__ __launch_bounds__(NT * 64, SINGLE ? 4 : 1) void attention_kernel(cons
 //   * output rows leave as 16-byte stores (v_permlane32_swap pairs the two half-waves' 8-byte pieces of a query row).
 // Rows past N are fetched from row N-1 (finite; their scores are masked to -inf, their probabilities are exactly 0).
 // ---------------------------------------------------------------------------------------------
-typedef const __attribute__((address_space(1))) void* at_gptr_t;
 typedef __attribute__((address_space(3))) void* at_lptr_t;
-typedef __attribute__((ext_vector_type(4))) short at_s16x4;
-typedef __attribute__((address_space(3))) at_s16x4* at_lds_s16x4_t;
 typedef float at_f32x2 __attribute__((ext_vector_type(2)));
 
 // transposing reads of PV step n (inline asm: see the kernel) and the counted wait for them
@@ -346,9 +233,9 @@ __global__ __launch_bounds__(NT * 64) void attention_pipe_kernel(const uint16_t*
             const int pid = wave * 8 + j;                       // wave-uniform
             const int tensor = pid >= NT * 4 ? 1 : 0;
             const int prow = (pid - tensor * NT * 4) * 8;
-            const int row = prow + (lane >> 3), c = lane & 7;
+            const int row = prow + row_chunk(lane).row, c = row_chunk(lane).c;
             const int key = row < N ? row : N - 1;
-            const int cs = tensor ? (c ^ (((row >> 1) & 1) << 2)) : (c ^ ((row >> 1) & 7));
+            const int cs = tensor ? v_chunk(row, c) : k_chunk(row, c);
             const uint32_t voff = (uint32_t)((key * ld + (tensor + 1) * D + cs * 8) * 2);
             if (ABL != 1) __builtin_amdgcn_raw_ptr_buffer_load_lds(rsQ, (at_lptr_t)(B + tensor * TILE + prow * 128), 16, (int)voff, (int)base, 0, 0);
         }
@@ -363,20 +250,13 @@ __global__ __launch_bounds__(NT * 64) void attention_pipe_kernel(const uint16_t*
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int prow = wave * 32 + j * 8;
-            const int row = prow + (lane >> 3), c = lane & 7;
+            const int row = prow + row_chunk(lane).row, c = row_chunk(lane).c;
             const int qr = row < N ? row : N - 1;
-            const uint32_t voff = (uint32_t)((qr * ld + ((c ^ ((row >> 1) & 7)) << 3)) * 2);
+            const uint32_t voff = (uint32_t)((qr * ld + k_chunk(row, c) * 8) * 2);
             if (ABL != 1) __builtin_amdgcn_raw_ptr_buffer_load_lds(rsQ, (at_lptr_t)(smem + 2 * BUF + prow * 128), 16, (int)voff, (int)base, 0, 0);
         }
     };
-    // V^T fragment addressing of the transposing read (see above): 16-lane group G = lane >> 4 takes d columns (G & 1) * 16 .. + 15
-    // of the key rows kb + 4 (G >> 1) + q; lane 4 q + p of the group addresses row q, columns 4 p .. 4 p + 3
-    const int tG = lane >> 4, tq = (lane >> 2) & 3, tp = lane & 3;
-    const int tkq = 4 * (tG >> 1) + tq;
-    const int tsw = ((tkq >> 1) & 1) << 2;
-    const int tc = (tG & 1) * 2 + (tp >> 1);
-    const int voff0 = tkq * 128 + (((0 ^ tsw) + tc) << 4) + (tp & 1) * 8;      // mt = 0: chunks 0..3
-    const int voff1 = tkq * 128 + (((4 ^ tsw) + tc) << 4) + (tp & 1) * 8;      // mt = 1: chunks 4..7
+    const VtOff vto = vt_offsets(lane);                                    // V^T fragment addressing of the transposing read
 
     const bool plain = !lse && !mx.q && ABL == 0;                          // exactly 4 output stores per wave and item (the counted wait below)
     issue(it0, 0);
@@ -395,12 +275,8 @@ __global__ __launch_bounds__(NT * 64) void attention_pipe_kernel(const uint16_t*
         const unsigned char* Vs = Ks + TILE;
         if (ABL == 2) { if (more) issue_q(item + 1); continue; }
         bf16x8 fq[4];
-        {
-            const int row = wave * 32 + rl;
 #pragma unroll
-            for (int ks = 0; ks < 4; ++ks)
-                fq[ks] = *(const bf16x8*)(smem + 2 * BUF + row * 128 + (((2 * ks + hh) ^ ((row >> 1) & 7)) << 4));
-        }
+        for (int ks = 0; ks < 4; ++ks) fq[ks] = k_frag(smem + 2 * BUF, wave * 32 + rl, ks, hh);
 
         // ---- S^T = K . Q^T: all NT groups ----------------------------------------------------
         // (the four K fragments of group kt+1 are read before group kt's MFMAs: left to itself hipcc reads every fragment into the same
@@ -408,9 +284,8 @@ __global__ __launch_bounds__(NT * 64) void attention_pipe_kernel(const uint16_t*
         f32x16 s[NT];
         bf16x8 kf[2][4];
         auto read_k = [&](int kt, bf16x8 (&f)[4]) __attribute__((always_inline)) {
-            const int row = kt * 32 + rl;
 #pragma unroll
-            for (int ks = 0; ks < 4; ++ks) f[ks] = *(const bf16x8*)(Ks + row * 128 + (((2 * ks + hh) ^ ((row >> 1) & 7)) << 4));
+            for (int ks = 0; ks < 4; ++ks) f[ks] = k_frag(Ks, kt * 32 + rl, ks, hh);
         };
         read_k(0, kf[0]);
 #pragma unroll
@@ -430,13 +305,7 @@ __global__ __launch_bounds__(NT * 64) void attention_pipe_kernel(const uint16_t*
         float mxv = -INFINITY;
 #pragma unroll
         for (int kt = 0; kt < NT; ++kt) {
-            if (kt == NT - 1) {                                   // only the last group can straddle N (N > 32 (NT - 1)); branch-free
-#pragma unroll
-                for (int e = 0; e < 16; ++e) {
-                    const int key = kt * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh;
-                    s[kt][e] = key < N ? s[kt][e] : -INFINITY;
-                }
-            }
+            if (kt == NT - 1) mask_group(s[kt], kt * 32, N, hh);  // only the last group can straddle N (N > 32 (NT - 1)); branch-free
 #pragma unroll
             for (int e = 0; e < 16; ++e) mxv = fmaxf(mxv, s[kt][e]);
         }
@@ -451,7 +320,7 @@ __global__ __launch_bounds__(NT * 64) void attention_pipe_kernel(const uint16_t*
 #pragma unroll
             for (int e = 0; e < 16; e += 2) {
                 // elements e .. e + 3 of every lane are keys >= 32 kt + 8 (e >> 2): past N (last group only) they are exactly 0
-                if (kt == NT - 1 && kt * 32 + 8 * (e >> 2) >= N) {
+                if (kt == NT - 1 && kt * 32 + key_of(e & ~3, 0) >= N) {
                     fp[kt][e >> 3][e & 7] = (__bf16)0.f; fp[kt][e >> 3][(e & 7) + 1] = (__bf16)0.f;
                     continue;
                 }
@@ -472,7 +341,7 @@ __global__ __launch_bounds__(NT * 64) void attention_pipe_kernel(const uint16_t*
         // only make the wait stricter).  Step n = (key group kt, 16-key half st); a step's reads: (mt 0, mt 1) x (keys +0..3, +8..11).
         u32x2 vr[2][4];
         const uint32_t vbase = (uint32_t)(uintptr_t)(at_lptr_t)(const_cast<unsigned char*>(Vs));
-        const uint32_t va0 = vbase + voff0, va1 = vbase + voff1;
+        const uint32_t va0 = vbase + vto.o[0], va1 = vbase + vto.o[1];
         auto pv_step = [&](auto n_c) __attribute__((always_inline)) {
             constexpr int n = decltype(n_c)::value, kt = n >> 1, st = n & 1;
             if constexpr (n + 1 < 2 * NT) at_vread<n + 1>(vr, va0, va1);
@@ -501,39 +370,18 @@ __global__ __launch_bounds__(NT * 64) void attention_pipe_kernel(const uint16_t*
         const int r = item / H, hd = item - r * H;
         const int q = wave * 32 + rl;
         const float inv = 1.0f / l;
-        if (lse && hh == 0 && q < N) lse[((size_t)r * H + hd) * N + q] = mb + log2f(l);              // log2 domain
+        store_lse(lse, r, H, hd, N, q, hh, mb, l);
         if (mx.q) {
-            if (q < N) {
-                const long long row = (long long)r * N + q;
-#pragma unroll
-                for (int mt = 0; mt < 2; ++mt) {
-                    float f[16];
-#pragma unroll
-                    for (int k = 0; k < 16; ++k) f[k] = bf16_to_f32(f32_to_bf16(o[mt][k] * inv));
-                    uint32_t p[4];
-                    const int e = mx_quant_block<32>(f, p);
-#pragma unroll
-                    for (int g4 = 0; g4 < 4; ++g4) *(uint32_t*)(mx.q + row * mx.ldq + hd * HD + mt * 32 + 8 * g4 + 4 * hh) = p[g4];
-                    if (hh == 0) mx.s[mx_scale_kmajor(hd * 2 + mt, mx.rows, row)] = (uint8_t)(e + 127);
-                }
-            }
+            if (q < N) store_mx(o, inv, mx, r, N, hd, q, hh);
         } else {
-            // a lane holds d = 32 mt + 8 g + 4 hh .. + 3 of its query; pairs of groups (g, g + 1) are exchanged between the half-waves
-            // so that lane hh = 0 owns d = 8 g .. 8 g + 7 and lane hh = 1 owns d = 8 (g + 1) .. + 7: 8 stores of 16 bytes
             const auto rsO = __builtin_amdgcn_make_buffer_rsrc((void*)out, 0, 0x7fffffff, 0x00020000);   // (offsets checked by the host: < 2 GB)
             const uint32_t ob = q < N ? (uint32_t)((((size_t)r * N + q) * D + hd * HD) * 2) : 0x80000000u;
 #pragma unroll
             for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
                 for (int g4 = 0; g4 < 4; g4 += 2) {
-                    uint32_t a0 = pack_bf16x2(o[mt][4 * g4] * inv, o[mt][4 * g4 + 1] * inv);
-                    uint32_t a1 = pack_bf16x2(o[mt][4 * g4 + 2] * inv, o[mt][4 * g4 + 3] * inv);
-                    uint32_t b0 = pack_bf16x2(o[mt][4 * g4 + 4] * inv, o[mt][4 * g4 + 5] * inv);
-                    uint32_t b1 = pack_bf16x2(o[mt][4 * g4 + 6] * inv, o[mt][4 * g4 + 7] * inv);
-                    const auto x0 = __builtin_amdgcn_permlane32_swap(a0, b0, false, false);
-                    const auto x1 = __builtin_amdgcn_permlane32_swap(a1, b1, false, false);
-                    const u32x4 pkv = {x0[0], x1[0], x0[1], x1[1]};
-                    if (ABL != 3) __builtin_amdgcn_raw_buffer_store_b128(pkv, rsO, ob + (uint32_t)((mt * 32 + 8 * (g4 + hh)) * 2), 0, 0);
+                    const u32x4 pkv = swapped_rows(o, inv, mt, g4);
+                    if (ABL != 3) __builtin_amdgcn_raw_buffer_store_b128(pkv, rsO, ob + (uint32_t)(swapped_col(mt, g4, hh) * 2), 0, 0);
                     else asm volatile("" :: "v"(pkv));
                 }
         }
@@ -553,7 +401,7 @@ int launch_attn_pipe(const uint16_t* qkv, int R, int N, int H, float scale, uint
     int per = items / 256;
     per = per < 1 ? 1 : (per > 6 ? 6 : per);
     const int grid = (items + per - 1) / per;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(NT * 64), lds, st, qkv, N, H, R, per, scale * 1.4426950408889634f, out, r_dev, lse, mx);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(NT * 64), lds, st, qkv, N, H, R, per, scale * LOG2E, out, r_dev, lse, mx);
     return yv_launch_status();
 }
 
@@ -567,7 +415,7 @@ int launch_attn(const uint16_t* qkv, int R, int N, int H, float scale, uint16_t*
                 single ? attention_kernel<NT, 0, true> : attention_kernel<NT, 0, false>;
     if (!yv_grant_lds((const void*)kern, lds)) return YV_ERR_LAUNCH;
     const int QB = (N + NP - 1) / NP;
-    hipLaunchKernelGGL(kern, dim3(R * H * QB), dim3(NT * 64), lds, st, qkv, N, H, QB, scale * 1.4426950408889634f, out,
+    hipLaunchKernelGGL(kern, dim3(R * H * QB), dim3(NT * 64), lds, st, qkv, N, H, QB, scale * LOG2E, out,
                        r_dev, lse, mx);
     return yv_launch_status();
 }

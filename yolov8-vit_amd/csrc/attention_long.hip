@@ -1,8 +1,8 @@
 // Attention forward for sequences that do not fit one K/V tile (ViT-B/8 at 224: 785 tokens; ViT-x/16 at 384: 577), head dim 64,
 // non-causal, bf16 in, f32 accumulate: yv_attention_long.  DESIGN.md section 15.
 //
-// Same MFMA plan as attention.hip (v_mfma_f32_32x32x16_bf16; S^T = K . Q^T has the key on the register axis and the query on the
-// lane; the exponentiated accumulator registers are the B operand of O^T = V^T . P^T, so P never touches LDS), other blocking:
+// The MFMA plan, the LDS images, the online-softmax group step and the output formats are csrc/attention_fwd_core.h, shared with
+// attention.hip; the blocking is this file's:
 //   * a workgroup is 4 waves x 32 query rows = 128 queries of one (crop, head).  The N % 128 rows left over go to a second launch
 //     whose workgroups have ceil((N % 128) / 32) waves: no wave exists for a 32-row group that lies wholly past N;
 //   * keys are walked in tiles of 64 (two 32-key groups; 32 in the one-wave workgroup) up to ceil(N / 32) groups: a group wholly past N is skipped, only the
@@ -12,20 +12,13 @@
 //   * K and V tiles are double-buffered in LDS by register staging with the issue-early / write-late split: the global loads of
 //     tile t + 1 are issued in front of tile t's MFMA / exp work and written to the other buffer behind it, one barrier per tile.
 //     Plain loads and 16-byte LDS stores: every wait is the compiler's;
-//   * images as in attention_pipe_kernel: K chunk ^ ((row >> 1) & 7) (conflict-free ds_read_b128 of the 32-row A fragment); V stays
-//     row-major, chunk ^ 4 ((row >> 1) & 1), and is read with the transposing ds_read_b64_tr_b16;
+//   * images as in attention_pipe_kernel: swizzled K rows; V stays row-major and is read with the transposing ds_read_b64_tr_b16;
 //   * a query's reduction runs over the key groups in index order whatever the grid: a crop's output does not depend on R, on the
 //     crop's index or on the launch.
 // 64-bit addressing throughout: no 2 GB limit on the tensors.
-#include "mx_quant.h"
+#include "attention_fwd_core.h"
 
 namespace {
-
-constexpr int HD = 64;
-struct AttnMx { uint8_t* q; long long ldq; uint8_t* s; long long rows; };
-
-typedef __attribute__((ext_vector_type(4))) short al_s16x4;
-typedef __attribute__((address_space(3))) al_s16x4* al_lds_s16x4_t;
 
 // blockIdx.x = (crop * H + head) * QBL + (query block - qb0); a query block = 128 rows, of which this launch's workgroups hold
 // the first NW * 32
@@ -53,10 +46,8 @@ __global__ __launch_bounds__(NW * 64, 2) void attention_long_kernel(const uint16
 
     // ---- Q fragments (B operand), straight from global ---------------------------------------------
     const int q = qb * 128 + wave * 32 + rl;
-    const int qc = q < N ? q : N - 1;
     bf16x8 fq[4];
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) fq[ks] = *(const bf16x8*)(base + (size_t)qc * ld + ks * 16 + hh * 8);
+    q_frags(base, q, N, ld, hh, fq);
 
     // ---- K / V staging: issue (global -> registers) and write (registers -> LDS) are separate steps ------
     u32x4 kst[TRIPS], vst[TRIPS];
@@ -64,7 +55,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attention_long_kernel(const uint16
 #pragma unroll
         for (int i = 0; i < TRIPS; ++i) {
             const int it = tid + i * T;
-            const int kl = (it < CH ? it : CH - 1) >> 3, c = it & 7;
+            const int kl = row_chunk(it < CH ? it : CH - 1).row, c = row_chunk(it).c;
             int key = t * KT + kl;
             key = key < N ? key : N - 1;
             const uint16_t* p = base + (size_t)key * ld + D + c * 8;
@@ -78,19 +69,12 @@ __global__ __launch_bounds__(NW * 64, 2) void attention_long_kernel(const uint16
         for (int i = 0; i < TRIPS; ++i) {
             const int it = tid + i * T;
             if (CH % T != 0 && it >= CH) break;
-            const int kl = it >> 3, c = it & 7;
-            *(u32x4*)(Kb + kl * 128 + ((c ^ ((kl >> 1) & 7)) << 4)) = kst[i];
-            *(u32x4*)(Kb + TILE + kl * 128 + ((c ^ (((kl >> 1) & 1) << 2)) << 4)) = vst[i];
+            const auto [kl, c] = row_chunk(it);
+            *(u32x4*)(Kb + k_off(kl, c)) = kst[i];
+            *(u32x4*)(Kb + TILE + v_off(kl, c)) = vst[i];
         }
     };
-    // V^T fragment addressing of the transposing read (attention_pipe_kernel): 16-lane group G = lane >> 4 takes d columns
-    // (G & 1) * 16 .. + 15 of the key rows kb + 4 (G >> 1) + q; lane 4 q + p of the group addresses row q, columns 4 p .. 4 p + 3
-    const int tG = lane >> 4, tq = (lane >> 2) & 3, tp = lane & 3;
-    const int tkq = 4 * (tG >> 1) + tq;
-    const int tsw = ((tkq >> 1) & 1) << 2;
-    const int tc = (tG & 1) * 2 + (tp >> 1);
-    const int voff0 = tkq * 128 + (((0 ^ tsw) + tc) << 4) + (tp & 1) * 8;      // mt = 0: chunks 0..3
-    const int voff1 = tkq * 128 + (((4 ^ tsw) + tc) << 4) + (tp & 1) * 8;      // mt = 1: chunks 4..7
+    const VtOff vto = vt_offsets(lane);                  // V^T fragment addressing of the transposing read
 
     f32x16 o[2];
 #pragma unroll
@@ -118,98 +102,28 @@ __global__ __launch_bounds__(NW * 64, 2) void attention_long_kernel(const uint16
         for (int gl = 0; gl < GPT; ++gl) {
             const int g = GPT * t + gl;
             if (g >= G) break;                           // wholly past N (wave- and block-uniform)
-            f32x16 sv;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) sv[e] = 0.f;
-            const int row = gl * 32 + rl;
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) {
-                const bf16x8 fk = *(const bf16x8*)(Ks + row * 128 + (((2 * ks + hh) ^ ((row >> 1) & 7)) << 4));
-                sv = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fk, fq[ks], sv, 0, 0, 0);
-            }
-            if (g * 32 + 32 > N) {                       // the group that straddles N
-#pragma unroll
-                for (int e = 0; e < 16; ++e) {
-                    const int key = g * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh;
-                    sv[e] = key < N ? sv[e] : -INFINITY;
-                }
-            }
-            float mxv = sv[0];
-#pragma unroll
-            for (int e = 1; e < 16; ++e) mxv = fmaxf(mxv, sv[e]);
-            mxv = fmaxf(mxv, __shfl_xor(mxv, 32, 64));
-            const float m_new = fmaxf(m_run, mxv);       // every live group holds >= 1 valid key for every row: finite from group 0 on
-            if (__any(m_new > m_run)) {                  // wave-uniform: some query's maximum grew
-                const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * scale_log2e);   // 1 for unchanged rows, 0 at the start
-                l_lane *= alpha;
-#pragma unroll
-                for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-                    for (int e = 0; e < 16; ++e) o[mt][e] *= alpha;
-                m_run = m_new;
-            }
-            const float mb = m_run * scale_log2e;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                sv[e] = __builtin_amdgcn_exp2f(fmaf(sv[e], scale_log2e, -mb));
-                l_lane += sv[e];
-            }
-#pragma unroll
-            for (int st = 0; st < 2; ++st) {
-                bf16x8 fp;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) fp[j] = (__bf16)sv[8 * st + j];
-                const int kb = gl * 32 + 16 * st;
-#pragma unroll
-                for (int mt = 0; mt < 2; ++mt) {
-                    const unsigned char* va = Vs + (mt ? voff1 : voff0) + kb * 128;
-                    const al_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((al_lds_s16x4_t)(va));
-                    const al_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((al_lds_s16x4_t)(va + 8 * 128));
-                    const u32x2 lo2 = __builtin_bit_cast(u32x2, lo), hi2 = __builtin_bit_cast(u32x2, hi);
-                    const u32x4 pk = {lo2[0], lo2[1], hi2[0], hi2[1]};
-                    o[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, pk), fp, o[mt], 0, 0, 0);
-                }
-            }
+            f32x16 sv = score_group(Ks, gl * 32, fq, rl, hh);
+            if (g * 32 + 32 > N) mask_group(sv, g * 32, N, hh);       // the group that straddles N
+            online_step(sv, m_run, l_lane, o, scale_log2e);
+            pv_product(sv, o, [&](int mt, int st) __attribute__((always_inline)) { return vt_frag_tr(Vs, vto, mt, gl * 32 + 16 * st); });
         }
         if (more) stash((t + 1) & 1);                    // that buffer's last readers passed the previous barrier
         __syncthreads();
     }
     const float l_run = l_lane + __shfl_xor(l_lane, 32, 64);
 
-    // ---- normalise and store: lane owns d = 32 mt + 8 g + 4 hh .. + 3 of its query -------------------
+    // ---- normalise and store (both lanes of a query are here: the exchanges run before the `q < N` of the stores) ------------
     const float inv = 1.0f / l_run;
-    if (lse && hh == 0 && q < N) lse[((size_t)r * H + hd) * N + q] = m_run * scale_log2e + log2f(l_run);   // log2 domain
-    if (mx.q && q < N) {
-        // a head's 64 columns are two MX blocks (d 0..31 = mt 0, d 32..63 = mt 1); a query's values of one block sit in this lane
-        // and in lane ^ 32 (same q: both are here); the bf16 rounding of the ordinary output is kept
-        const long long row = (long long)r * N + q;
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt) {
-            float f[16];
-#pragma unroll
-            for (int k = 0; k < 16; ++k) f[k] = bf16_to_f32(f32_to_bf16(o[mt][k] * inv));
-            uint32_t p[4];
-            const int e = mx_quant_block<32>(f, p);
-#pragma unroll
-            for (int g4 = 0; g4 < 4; ++g4) *(uint32_t*)(mx.q + row * mx.ldq + hd * HD + mt * 32 + 8 * g4 + 4 * hh) = p[g4];
-            if (hh == 0) mx.s[mx_scale_kmajor(hd * 2 + mt, mx.rows, row)] = (uint8_t)(e + 127);
-        }
-    }
+    store_lse(lse, r, H, hd, N, q, hh, m_run * scale_log2e, l_run);
+    if (mx.q && q < N) store_mx(o, inv, mx, r, N, hd, q, hh);
     if (!out) return;
-    // pairs of 4-column groups (g, g + 1) are exchanged between the half-waves so that lane hh = 0 owns d = 8 g .. 8 g + 7 and
-    // lane hh = 1 owns d = 8 (g + 1) .. + 7: 8 stores of 16 bytes per query row
-    uint16_t* orow = out + ((size_t)r * N + qc) * D + hd * HD;
+    uint16_t* orow = out + ((size_t)r * N + (q < N ? q : N - 1)) * D + hd * HD;
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
         for (int g4 = 0; g4 < 4; g4 += 2) {
-            const uint32_t a0 = pack_bf16x2(o[mt][4 * g4] * inv, o[mt][4 * g4 + 1] * inv);
-            const uint32_t a1 = pack_bf16x2(o[mt][4 * g4 + 2] * inv, o[mt][4 * g4 + 3] * inv);
-            const uint32_t b0 = pack_bf16x2(o[mt][4 * g4 + 4] * inv, o[mt][4 * g4 + 5] * inv);
-            const uint32_t b1 = pack_bf16x2(o[mt][4 * g4 + 6] * inv, o[mt][4 * g4 + 7] * inv);
-            const auto x0 = __builtin_amdgcn_permlane32_swap(a0, b0, false, false);
-            const auto x1 = __builtin_amdgcn_permlane32_swap(a1, b1, false, false);
-            if (q < N) *(uint4*)(orow + mt * 32 + 8 * (g4 + hh)) = make_uint4(x0[0], x1[0], x0[1], x1[1]);
+            const u32x4 pk = swapped_rows(o, inv, mt, g4);
+            if (q < N) *(u32x4*)(orow + swapped_col(mt, g4, hh)) = pk;
         }
 }
 
@@ -217,7 +131,7 @@ template <int NW>
 int launch_long(const uint16_t* qkv, int R, int N, int H, int qb0, int QBL, float scale, uint16_t* out, const int32_t* r_dev,
                 float* lse, hipStream_t st, AttnMx mx) {
     hipLaunchKernelGGL(attention_long_kernel<NW>, dim3(R * H * QBL), dim3(NW * 64), 0, st, qkv, R, N, H, qb0, QBL,
-                       scale * 1.4426950408889634f, out, r_dev, lse, mx);
+                       scale * LOG2E, out, r_dev, lse, mx);
     return yv_launch_status();
 }
 
