@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import torch
 
+import nms_cases
 from inputs import coord_image, seeded_boxes
 from oracle import boxes as ob
 from oracle import train as ot
@@ -98,8 +99,13 @@ def _rand_dets(B, A, nc, seed, dense=False):
                                           (2, 1000, 80, False), (5, 8400, 1, False), (3, 2100, 3, True)])
 def test_efficient_nms_vs_oracle(yv, B, A, nc, dense, single_kernel):
     """Both device forms (multi-workgroup = the pipeline's, single workgroup per image) against oracle/boxes.py, bit-exact.
-    Cases: sparse and dense score sets (dense: every score above the threshold -> the top-4096 selection path and classes
-    with thousands of candidates), one class (everything in one greedy chain), 80 classes (mostly empty classes)."""
+    Cases: sparse and dense score sets (dense: most scores above the threshold, up to 31,500 candidates per image), one class
+    (everything in one greedy chain), 80 classes (mostly empty classes, the atomic candidate list).  The boxes are spread
+    out, so max_out of them are kept among the first few hundred candidates: in the multi-workgroup form every image of
+    these seven cases is finished by the head (en2_head_body on 16 or, in the dense 8400 x 5 case, 44 register keys per
+    thread).  The exact top-4096 select, heavy classes and the rest of the general path are NOT reached here; they are
+    pinned by test_efficient_nms_path_pinned_cases.  The single-workgroup form does run its top-4096 select on the dense
+    cases."""
     boxes, scores = _rand_dets(B, A, nc, 5 + A + nc, dense)
     exp = ob.efficient_nms(boxes, scores)
     got = yv.efficient_nms(boxes.to(DEV), scores.to(DEV), single_kernel=single_kernel)
@@ -230,6 +236,22 @@ def test_efficient_nms_clustered_boxes_and_small_limits(yv):
     for x, y in zip(a, b):
         assert torch.equal(x, y)
     assert int(a[0].sum()) > 0
+
+
+@pytest.mark.parametrize("single_kernel", [False, True])
+@pytest.mark.parametrize("name", sorted(nms_cases.CASES))
+def test_efficient_nms_path_pinned_cases(yv, name, single_kernel):
+    """The inputs of tests/nms_cases.py, each of which provably (tests/test_nms_paths_cpu.py) leaves the head of the
+    multi-workgroup form for the general path - exact top-k select on register keys and bit-serial, heavy classes, in-place
+    compaction of the segmented list, global class counters, unaligned score blocks - against oracle/boxes.py, bit for bit,
+    in both device forms."""
+    boxes, scores = nms_cases.case_inputs(name)
+    kw = nms_cases.CASES[name][1]
+    exp = nms_cases.case_expected(name)
+    got = yv.efficient_nms(boxes.to(DEV), scores.to(DEV), kw.get("thr", 0.25), kw.get("iou", 0.65), kw.get("max_out", 100),
+                           kw.get("topk", 4096), single_kernel=single_kernel)
+    for e, g_ in zip(exp, got):
+        assert torch.equal(e, g_.cpu())
 
 
 # ------------------------------------------------------------------ postprocess + compaction

@@ -34,7 +34,7 @@ __device__ __forceinline__ float iou_f32(float4 a, float area_a, float4 b, float
     return __fdiv_rn(inter, uni);
 }
 
-__device__ __forceinline__ int next_pow2(int v, int lo) {
+__host__ __device__ __forceinline__ int next_pow2(int v, int lo) {
     int p = lo;
     while (p < v) p <<= 1;
     return p;
@@ -159,16 +159,10 @@ struct EnShared {
     uint32_t sel_bin, sel_before, n_sel, n_eq_taken, total_cnt;
 };
 
-__device__ __forceinline__ uint32_t block_count(bool flag, uint32_t* wave_cnt) {
-    uint64_t m = __ballot(flag);
-    int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    __syncthreads();
-    if (lane == 0) wave_cnt[wave] = (uint32_t)__builtin_popcountll(m);
-    __syncthreads();
-    uint32_t t = 0;
-    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += wave_cnt[w];
-    return t;
-}
+struct EnLds {                              // dynamic LDS of efficient_nms_kernel, as byte offsets: the kernel carves its pointers from it, the launcher asks for `bytes`
+    static constexpr size_t keys = 0, sb = keys + (size_t)EN_MAXK * 8, cls = sb + (size_t)EN_MAXK * 16, alive = cls + (size_t)EN_MAXK * 2,
+                            sh = alive + (EN_MAXK / 64) * 8, bytes = sh + sizeof(EnShared) + 16;
+};
 
 // exclusive rank of `flag` among the block's threads (thread order) + block total
 __device__ __forceinline__ uint32_t block_rank(bool flag, uint32_t* wave_cnt, uint32_t* total) {
@@ -192,11 +186,11 @@ __global__ __launch_bounds__(EN_THREADS) void efficient_nms_kernel(
     int max_out, int pre_topk, int32_t* __restrict__ num_dets, float* __restrict__ out_boxes,
     float* __restrict__ out_scores, int32_t* __restrict__ out_labels) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    uint64_t* keys = (uint64_t*)smem;                          // EN_MAXK
-    float4* sb = (float4*)(keys + EN_MAXK);                    // EN_MAXK
-    int16_t* cls = (int16_t*)(sb + EN_MAXK);                   // EN_MAXK
-    uint64_t* alive = (uint64_t*)(cls + EN_MAXK);              // EN_MAXK/64
-    EnShared* sh = (EnShared*)(alive + EN_MAXK / 64);
+    uint64_t* keys = (uint64_t*)(smem + EnLds::keys);          // EN_MAXK
+    float4* sb = (float4*)(smem + EnLds::sb);                  // EN_MAXK
+    int16_t* cls = (int16_t*)(smem + EnLds::cls);              // EN_MAXK
+    uint64_t* alive = (uint64_t*)(smem + EnLds::alive);        // EN_MAXK/64
+    EnShared* sh = (EnShared*)(smem + EnLds::sh);
 
     const int b = blockIdx.x, tid = threadIdx.x;
     const int total = A * nc;
@@ -1333,9 +1327,7 @@ __global__ void compact_crops_kernel(const int32_t* __restrict__ det_count, cons
 // ------------------------------------------------------------------------------------------- C ABI
 extern "C" size_t yv_custom_nms_ws_bytes(int n_sets, int n_max) {
     if (n_sets <= 0 || n_max <= 0) return 0;
-    int np = 64;
-    while (np < n_max) np <<= 1;
-    return np <= CN_LDS_BOX_MAX ? 0 : (size_t)n_sets * (size_t)n_max * sizeof(float4);
+    return next_pow2(n_max, 64) <= CN_LDS_BOX_MAX ? 0 : (size_t)n_sets * (size_t)n_max * sizeof(float4);
 }
 
 extern "C" int yv_custom_nms(const float* boxes, const float* scores, const int32_t* counts, int n_sets, int n_max,
@@ -1349,8 +1341,7 @@ extern "C" int yv_custom_nms(const float* boxes, const float* scores, const int3
     }
     if (!boxes || !scores) return YV_ERR_ARG;
     if (n_max > 16384) return YV_ERR_LIMIT;
-    int np = 64;
-    while (np < n_max) np <<= 1;
+    const int np = next_pow2(n_max, 64);
     size_t need = yv_custom_nms_ws_bytes(n_sets, n_max);
     if (need && (!ws || ws_bytes < need)) return YV_ERR_WORKSPACE;
     size_t lds = (size_t)np * 8 + (size_t)(((np >> 6) + 2) & ~1) * 8 + (np <= CN_LDS_BOX_MAX ? (size_t)np * 16 : 0);
@@ -1361,17 +1352,24 @@ extern "C" int yv_custom_nms(const float* boxes, const float* scores, const int3
     return yv_launch_status();
 }
 
-extern "C" int yv_efficient_nms(const float* boxes, const float* scores, int B, int A, int nc, float score_threshold,
-                                float iou_threshold, int max_out, int pre_topk, int32_t* num_dets, float* out_boxes,
-                                float* out_scores, int32_t* out_labels, void* stream) {
+// argument and limit checks shared by the two forms of EfficientNMS (B == 0 is valid: nothing to do, nothing else is looked at)
+static int en_check(const float* boxes, const float* scores, int B, int A, int nc, int max_out, int pre_topk,
+                    const int32_t* num_dets, const float* out_boxes, const float* out_scores, const int32_t* out_labels) {
     if (B < 0 || A <= 0 || nc <= 0 || max_out <= 0 || !boxes || !scores || !num_dets || !out_boxes || !out_scores ||
         !out_labels)
         return YV_ERR_ARG;
     if (B == 0) return YV_OK;
     if (pre_topk <= 0 || pre_topk > EN_MAXK || nc > 32767 || (long long)A * nc > 0x7fffffffLL) return YV_ERR_LIMIT;
-    size_t lds = (size_t)EN_MAXK * (8 + 16 + 2) + (EN_MAXK / 64) * 8 + sizeof(EnShared) + 16;
-    if (!yv_grant_lds((const void*)efficient_nms_kernel, lds)) return YV_ERR_LAUNCH;
-    hipLaunchKernelGGL(efficient_nms_kernel, dim3(B), dim3(EN_THREADS), lds, (hipStream_t)stream, boxes, scores, A, nc,
+    return YV_OK;
+}
+
+extern "C" int yv_efficient_nms(const float* boxes, const float* scores, int B, int A, int nc, float score_threshold,
+                                float iou_threshold, int max_out, int pre_topk, int32_t* num_dets, float* out_boxes,
+                                float* out_scores, int32_t* out_labels, void* stream) {
+    const int e = en_check(boxes, scores, B, A, nc, max_out, pre_topk, num_dets, out_boxes, out_scores, out_labels);
+    if (e != YV_OK || B == 0) return e;
+    if (!yv_grant_lds((const void*)efficient_nms_kernel, EnLds::bytes)) return YV_ERR_LAUNCH;
+    hipLaunchKernelGGL(efficient_nms_kernel, dim3(B), dim3(EN_THREADS), EnLds::bytes, (hipStream_t)stream, boxes, scores, A, nc,
                        score_threshold, iou_threshold, max_out, pre_topk, num_dets, out_boxes, out_scores, out_labels);
     return yv_launch_status();
 }
@@ -1412,12 +1410,9 @@ extern "C" size_t yv_efficient_nms_ws_bytes(int B, int A, int nc, int max_out, i
 extern "C" int yv_efficient_nms_ws(const float* boxes, const float* scores, int B, int A, int nc, float score_threshold,
                                    float iou_threshold, int max_out, int pre_topk, int32_t* num_dets, float* out_boxes,
                                    float* out_scores, int32_t* out_labels, void* ws, size_t ws_bytes, void* stream) {
-    if (B < 0 || A <= 0 || nc <= 0 || max_out <= 0 || !boxes || !scores || !num_dets || !out_boxes || !out_scores ||
-        !out_labels)
-        return YV_ERR_ARG;
-    if (B == 0) return YV_OK;
-    if (pre_topk <= 0 || pre_topk > EN_MAXK || nc > 32767 || (long long)A * nc > 0x7fffffffLL || max_out > EN_MAXK)
-        return YV_ERR_LIMIT;
+    const int e = en_check(boxes, scores, B, A, nc, max_out, pre_topk, num_dets, out_boxes, out_scores, out_labels);
+    if (e != YV_OK || B == 0) return e;
+    if (max_out > EN_MAXK) return YV_ERR_LIMIT;                  // the head's and the classes' kept lists live in LDS
     if (B > 65535 || nc > 65535) return YV_ERR_LIMIT;            // grid.y / grid.x
     En2Ws w;
     size_t zero_bytes = 0;
@@ -1460,8 +1455,7 @@ extern "C" int yv_postprocess_dets(const int32_t* num_dets, const float* bboxes,
     if (coord_mode != 0 && coord_mode != 1) return YV_ERR_ARG;
     if (B == 0) return YV_OK;
     if (slots > PP_MAX_SLOTS) return YV_ERR_LIMIT;
-    int np = 64;
-    while (np < slots) np <<= 1;
+    const int np = next_pow2(slots, 64);
     size_t lds = (size_t)np * (8 + 16 + 4) + ((size_t)(np >> 6) + 1) * 8 + 16;
     hipLaunchKernelGGL(postprocess_kernel, dim3(B), dim3(PP_THREADS), lds, (hipStream_t)stream, num_dets, bboxes,
                        scores, labels, slots, np, ratio, dwdh, img_wh, conf_threshold, dedupe_iou, coord_mode,
