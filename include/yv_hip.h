@@ -432,6 +432,46 @@ int yv_conv2d_stats(const yv_view* in0, int B, int Hout, int Wout, int ksize, in
  * than 2048 tiles, the chunk partials yv_bn_stats_finish folds them into (at most 2048 * 2 * Cout).  0 for T or Cout <= 0. */
 size_t yv_conv_stats_ws_floats(long long T, int Cout);
 
+/* yv_conv2d_ws as a DATA GRADIENT that also takes the two reductions of the BatchNorm backward of the block that produced its
+ * target (opt-in: YoloTrainer(fused_bn_bwd=True)).  out (bf16) is the gradient da of that block's output and receives the bits
+ * yv_conv2d_ws writes for the same arguments under "conv_splitk" = 0.  z (row stride ldz), mean, rstd, gamma, beta (Cout floats
+ * each) and act are the producer's operands as yv_bn_act_bwd takes them.  Every workgroup also writes, for its tile of 128 rows
+ * (tm = first row / 128) and each of its columns n < Cout,
+ *   stats_ws[(tm * 2 + 0) * Cout + n] = sum over the tile's rows m < B*Hout*Wout of g,   stats_ws[(tm * 2 + 1) * Cout + n] = sum of g * xhat,
+ * xhat = (z - mean) * rstd, g = d * act'(gamma * xhat + beta), d = the bf16-rounded value stored to out, back in f32: term by
+ * term what yv_bn_act_bwd's first pass adds (one device text), in the summation order and layout of yv_conv2d_stats (each float
+ * one plain store, nothing zeroed or accumulated in memory, bitwise reproducible).  Rows of z at or behind B*Hout*Wout are not
+ * read.  yv_bn_act_bwd_finish turns the partials into dgamma, dbeta and dz.
+ * Accepted: one source, bf16 output, flags of YV_EPI_BIAS | YV_EPI_RES_BF16 only (anything else YV_ERR_ARG), Cout % 8 == 0,
+ * ldz % 8 == 0, ldz >= Cout, act 0 or 1, 16-byte aligned z, out, res, stats_ws and constants, the other argument rules of
+ * yv_conv2d.  A batch yv_conv2d_ws would take in sub-batches is YV_ERR_LIMIT; stats_ws_floats <
+ * yv_conv_bnbwd_ws_floats(B*Hout*Wout, Cout) is YV_ERR_WORKSPACE.  All of these are decided on the host before any HIP call.
+ * The call never splits K (ws / ws_bytes are accepted for symmetry). */
+int yv_conv2d_bnbwd(const yv_view* in0, int B, int Hout, int Wout, int ksize, int stride, const void* weight, const float* bias,
+                    int Cout, void* out, int out_ld, const void* res, int res_ld, int flags, const void* z, int ldz,
+                    const float* mean, const float* rstd, const float* gamma, const float* beta, int act, float* stats_ws,
+                    size_t stats_ws_floats, void* ws, size_t ws_bytes, void* stream);
+/* Floats of yv_conv2d_bnbwd's workspace: yv_conv_stats_ws_floats(T, Cout) + 2 * Cout (the finaliser's mean(g), mean(g * xhat),
+ * behind the partials).  0 for T or Cout <= 0. */
+size_t yv_conv_bnbwd_ws_floats(long long T, int Cout);
+
+/* The route of yv_conv2d_bnbwd for a data gradient (B, Hout, Wout) x Cin (pixel stride in_ld) -> Cout, decided by the function the
+ * launch path itself calls.  Host only: nothing is dereferenced, launched or queried; 16-byte aligned bases are assumed; flags,
+ * out_ld, res_ld, ldz as the call takes them; ws_bytes is the split-K workspace yv_conv2d_ws would be given for the same call.
+ * Returns a negative YV_ERR_* code where yv_conv2d_bnbwd rejects the arguments, else YV_OK and *out. */
+typedef struct {
+    int kernel;     /* instance, numbered as yv_conv2d_instance bits 0-3, in its BNBWD form */
+    int staged;     /* 1: the staged epilogue runs (16-byte z loads), 0: the direct one (8-byte z loads) */
+    int tiles;      /* 128-row tiles = rows of the partials */
+    int workgroups; /* the launch: tiles x column tiles */
+    int splitk;     /* 1: yv_conv2d_ws would split K for the same call under the current options */
+    int use;        /* 0: keep yv_conv2d_ws + yv_bn_act_bwd - where splitk is 1 (the unfused call's bits are a split sum's) and where
+                       the fused pair was measured slower: the 64- / 128-wide instances at >= 100,000 rows, the 32-wide one at
+                       >= 400,000 rows with K >= 512 */
+} yv_conv_bnbwd_route_t;
+int yv_conv2d_bnbwd_route(int B, int Hout, int Wout, int ksize, int stride, int Cin, int in_ld, int Cout, int out_ld, int res_ld,
+                          int ldz, int flags, size_t ws_bytes, yv_conv_bnbwd_route_t* out);
+
 /* Linear: out[M,N] = A[M,K] @ W[N,K]^T (+bias)(+GELU)(+residual) on MFMA
  * (timm Attention.qkv/proj, Mlp.fc1/fc2, head; README.md:21-35).
  * A (M,K) bf16 row stride lda; W (N,K) bf16; bias (N) f32.
@@ -752,6 +792,14 @@ int yv_bn_act_fwd(const void* z, long long ldz, long long T, int C, const float*
 int yv_bn_act_bwd(const void* da, long long ldda, const void* z, long long ldz, long long T, int C, const float* mean,
                   const float* rstd, const float* gamma, const float* beta, int act, int batch_stats, float* dgamma,
                   float* dbeta, void* dz, long long lddz, float* ws, size_t ws_floats, void* stream);
+
+/* yv_bn_act_bwd behind yv_conv2d_bnbwd: stats_ws holds that call's tile partials of (sum g, sum g * xhat) over T = B*Hout*Wout
+ * rows of C = Cout channels (yv_conv_bnbwd_ws_floats(T, C) floats).  More than 2048 tiles are first folded as yv_bn_stats_finish
+ * folds them; then yv_bn_act_bwd's finaliser and apply pass run unchanged (dgamma, dbeta, dz as there; da is the gradient the
+ * convolution stored).  No pass over da and z for the sums. */
+int yv_bn_act_bwd_finish(const void* da, long long ldda, const void* z, long long ldz, long long T, int C, const float* mean,
+                         const float* rstd, const float* gamma, const float* beta, int act, int batch_stats, float* dgamma,
+                         float* dbeta, void* dz, long long lddz, float* stats_ws, void* stream);
 
 /* Element-wise view operations on (B,H,W,C) bf16 views.  mode 0 copy, 1 dst += src, 2 nearest-2x upsample
  * (dst (B,2H,2W) <- src (B,H,W)), 3 its adjoint accumulated (dst (B,H,W) += 2x2 block sums of src (B,2H,2W)),

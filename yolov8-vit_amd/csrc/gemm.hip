@@ -24,6 +24,7 @@
 #include <mutex>
 #include "gemm_common.h"
 #include "mx_quant.h"
+#include "bn_act_grad.h"
 
 using namespace yvgemm;
 
@@ -61,6 +62,10 @@ __device__ __attribute__((aligned(256))) uint32_t g_zero_page[64];
 // values it stores and of their squares, rows in ascending fragment order; rows >= M and columns >= N add nothing.
 // PHASE (yv_conv2d_dgrad_s2): row m = (b, i, j) of the Hout x Wout gradient grid is pixel (b, 2i + py, 2j + px) of the output and of
 // the residual, ph = py * 2 + px being the workgroup's phase.
+// BNBWD (yv_conv2d_bnbwd): the value stored is the gradient da of a BatchNorm block's output; cs / cq (as STATS) receive this lane's
+// column sums of g = da * act'(u) and of g * xhat (bn_act_grad_term: the text of chan_reduce_kernel<1>), da being the bf16-rounded
+// value it stores and z the block's pre-activation at the same row and column.  The z loads of all of the lane's rows are issued
+// before the first store, so that their latency lies under the bias / residual / store work of the fragment.
 template <bool PHASE>
 __device__ __forceinline__ long long phase_row(const GemmArgs& g, int m, int ph) {
     if constexpr (!PHASE) return m;
@@ -70,11 +75,29 @@ __device__ __forceinline__ long long phase_row(const GemmArgs& g, int m, int ph)
     return ((long long)b * (2 * g.Hout) + 2 * i + (ph >> 1)) * (2 * g.Wout) + 2 * j + (ph & 1);
 }
 
-template <int MF, int NF, bool STATS = false, bool PHASE = false>
+template <int MF, int NF, bool STATS = false, bool PHASE = false, bool BNBWD = false>
 __device__ __forceinline__ void epilogue(const GemmArgs& g, f32x4 (&acc)[NF][MF], int M, int m0, int n0, int wrow_m,
                                          int wrow_n, int fr, int fq, float* cs = nullptr, float* cq = nullptr, int ph = 0) {
     // ---- epilogue: lane owns channels n..n+3 of row m --------------------------------------
+    static_assert(!(BNBWD && (STATS || PHASE)), "one kind of column sums, none of a phase launch");
     const int flags = g.flags;
+    [[maybe_unused]] float4 c_mu[NF], c_rs[NF], c_ga[NF], c_be[NF];
+    [[maybe_unused]] uint2 zz[NF][MF];
+    if constexpr (BNBWD) {
+#pragma unroll
+        for (int i = 0; i < NF; ++i) {
+            const int n = n0 + wrow_n + i * 16 + fq * 4;
+            const bool ok = n < g.N;
+            const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+            c_mu[i] = ok ? *(const float4*)(g.bn_mean + n) : zero; c_rs[i] = ok ? *(const float4*)(g.bn_rstd + n) : zero;
+            c_ga[i] = ok ? *(const float4*)(g.bn_gamma + n) : zero; c_be[i] = ok ? *(const float4*)(g.bn_beta + n) : zero;
+#pragma unroll
+            for (int j = 0; j < MF; ++j) {
+                const int m = m0 + wrow_m + j * 16 + fr;
+                zz[i][j] = (ok && m < M) ? *(const uint2*)(g.z + (long long)m * g.ldz + n) : make_uint2(0u, 0u);
+            }
+        }
+    }
 #pragma unroll
     for (int j = 0; j < MF; ++j) {
         const int m = m0 + wrow_m + j * 16 + fr;
@@ -131,6 +154,19 @@ __device__ __forceinline__ void epilogue(const GemmArgs& g, f32x4 (&acc)[NF][MF]
                         cs[i * 4 + q] += f; cq[i * 4 + q] += f * f;
                     }
                 }
+                if constexpr (BNBWD) {
+                    const uint32_t pk[2] = {pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])}, zk[2] = {zz[i][j].x, zz[i][j].y};
+                    const float mu[4] = {c_mu[i].x, c_mu[i].y, c_mu[i].z, c_mu[i].w}, rs[4] = {c_rs[i].x, c_rs[i].y, c_rs[i].z, c_rs[i].w};
+                    const float ga[4] = {c_ga[i].x, c_ga[i].y, c_ga[i].z, c_ga[i].w}, be[4] = {c_be[i].x, c_be[i].y, c_be[i].z, c_be[i].w};
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        const float d = bf16_to_f32((uint16_t)(q & 1 ? pk[q >> 1] >> 16 : pk[q >> 1] & 0xffff));
+                        const float z = bf16_to_f32((uint16_t)(q & 1 ? zk[q >> 1] >> 16 : zk[q >> 1] & 0xffff));
+                        float xh;
+                        const float gr = bn_act_grad_term(d, z, mu[q], rs[q], ga[q], be[q], g.bn_act, xh);
+                        cs[i * 4 + q] += gr; cq[i * 4 + q] += gr * xh;
+                    }
+                }
             }
         }
     }
@@ -173,13 +209,29 @@ __device__ __forceinline__ int mx_quant_bf16x8(const uint4 pk, uint2& q8) {
 // (bf16) / 256-byte (f32) row segments with 16-byte stores; residual reads are coalesced the same way.
 // STATS (yv_conv2d_stats, bf16 output): cs / cq (8 floats each, zeroed by the caller) receive the column sums of the 8 channels
 // this lane stores (n = n0 + wrow_n + (lane & 7) * 8 ..) and of their squares, its rows (lane >> 3) + 8 * it in ascending order.
-template <int MF, bool STATS = false, bool PHASE = false /* bf16 output only: the row map of phase_row */>
+// BNBWD (yv_conv2d_bnbwd, bf16 output): cs / cq likewise receive the sums of g and g * xhat (see epilogue); the 16-byte z loads of
+// the lane's first MF rows are issued before the slab is written, so that the transpose covers them, those of the other MF rows and
+// the constants behind the slab writes, where the accumulators' registers are free (all at the top: one workgroup per CU fewer on
+// the 128-wide tiles).
+template <int MF, bool STATS = false, bool PHASE = false /* bf16 output only: the row map of phase_row */, bool BNBWD = false>
 __device__ __forceinline__ void epilogue_staged(const GemmArgs& g, f32x4 (&acc)[4][MF], int M, int m0, int n0,
                                                 int wrow_m, int wrow_n, int lane, unsigned char* stage, float* cs = nullptr,
                                                 float* cq = nullptr, int ph = 0) {
+    static_assert(!(BNBWD && (STATS || PHASE)), "one kind of column sums, none of a phase launch");
     const int flags = g.flags;
     const int fr = lane & 15, fq = lane >> 4;
     const int nb = n0 + wrow_n;
+    [[maybe_unused]] uint4 zq[MF * 2];
+    [[maybe_unused]] float c_mu[8], c_rs[8], c_ga[8], c_be[8];
+    auto z_rows = [&](int first) {                   // the 16-byte z loads of MF of the lane's MF * 2 rows
+        const int n = nb + (lane & 7) * 8;
+#pragma unroll
+        for (int it = first; it < first + MF; ++it) {
+            const int m = m0 + wrow_m + it * 8 + (lane >> 3);
+            zq[it] = (m < M && n < g.N) ? *(const uint4*)(g.z + (long long)m * g.ldz + n) : make_uint4(0u, 0u, 0u, 0u);
+        }
+    };
+    if constexpr (BNBWD) z_rows(0);                  // in flight under the slab writes
     float4 bv[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -226,6 +278,21 @@ __device__ __forceinline__ void epilogue_staged(const GemmArgs& g, f32x4 (&acc)[
                 value(i, j, v);
                 slab_put(stage, i, j, fr, fq, v);
             }
+        if constexpr (BNBWD) {                   // (here, not at the top: the accumulators are in the slab, their registers free)
+            z_rows(MF);                              // the other half: in flight under the first half's terms
+            const int n = nb + (lane & 7) * 8;
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const bool ok = n < g.N;                 // (N % 8 == 0: a lane's 8 columns are inside or outside together)
+                const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+                const float4 a = ok ? *(const float4*)(g.bn_mean + n + h * 4) : zero, b = ok ? *(const float4*)(g.bn_rstd + n + h * 4) : zero;
+                const float4 c = ok ? *(const float4*)(g.bn_gamma + n + h * 4) : zero, d = ok ? *(const float4*)(g.bn_beta + n + h * 4) : zero;
+                c_mu[h * 4] = a.x; c_mu[h * 4 + 1] = a.y; c_mu[h * 4 + 2] = a.z; c_mu[h * 4 + 3] = a.w;
+                c_rs[h * 4] = b.x; c_rs[h * 4 + 1] = b.y; c_rs[h * 4 + 2] = b.z; c_rs[h * 4 + 3] = b.w;
+                c_ga[h * 4] = c.x; c_ga[h * 4 + 1] = c.y; c_ga[h * 4 + 2] = c.z; c_ga[h * 4 + 3] = c.w;
+                c_be[h * 4] = d.x; c_be[h * 4 + 1] = d.y; c_be[h * 4 + 2] = d.z; c_be[h * 4 + 3] = d.w;
+            }
+        }
 #pragma unroll
         for (int it = 0; it < MF * 2; ++it) {
             const int row = it * 8 + (lane >> 3), ch = lane & 7;
@@ -261,6 +328,17 @@ __device__ __forceinline__ void epilogue_staged(const GemmArgs& g, f32x4 (&acc)[
                     for (int q = 0; q < 8; ++q) {
                         const float f = bf16_to_f32((uint16_t)(q & 1 ? a[q >> 1] >> 16 : a[q >> 1] & 0xffff));
                         cs[q] += f; cq[q] += f * f;
+                    }
+                }
+                if constexpr (BNBWD) {
+                    const uint32_t a[4] = {pk.x, pk.y, pk.z, pk.w}, b[4] = {zq[it].x, zq[it].y, zq[it].z, zq[it].w};
+#pragma unroll
+                    for (int q = 0; q < 8; ++q) {
+                        const float d = bf16_to_f32((uint16_t)(q & 1 ? a[q >> 1] >> 16 : a[q >> 1] & 0xffff));
+                        const float z = bf16_to_f32((uint16_t)(q & 1 ? b[q >> 1] >> 16 : b[q >> 1] & 0xffff));
+                        float xh;
+                        const float gr = bn_act_grad_term(d, z, c_mu[q], c_rs[q], c_ga[q], c_be[q], g.bn_act, xh);
+                        cs[q] += gr; cq[q] += gr * xh;
                     }
                 }
             }
@@ -309,11 +387,13 @@ __device__ __forceinline__ void epilogue_staged(const GemmArgs& g, f32x4 (&acc)[
 // butterfly (both partners compute the same sum), then the WM waves in wave order through LDS.  The scratch (WM x 2 x BN floats)
 // lies at the start of the tile buffers, i.e. inside the staged epilogue's slabs: a barrier that every wave reaches (its rows
 // may all lie past M - it then adds zeros) separates the two uses.  g.staged is the same for the whole launch.
-template <int MF, int NF, bool STATS = false, int WM = 1, int BN = 16, bool PHASE = false>
+// BNBWD (yv_conv2d_bnbwd): the same path and layout with the epilogues' other pair of sums (which 0: sum g, 1: sum g * xhat).
+template <int MF, int NF, bool STATS = false, int WM = 1, int BN = 16, bool PHASE = false, bool BNBWD = false>
 __device__ __forceinline__ void finish_tile(const GemmArgs& g, f32x4 (&acc)[NF][MF], int M, int m0, int n0, int wrow_m,
                                             int wrow_n, int lane, int wave, unsigned char* smem, int tm = 0, int ph = 0) {
-    static_assert(!(STATS && PHASE), "no column sums of a data gradient");
-    if constexpr (STATS) {
+    static_assert(!((STATS || BNBWD) && PHASE), "no column sums of a phase launch");
+    static_assert(!(STATS && BNBWD), "one kind of column sums");
+    if constexpr (STATS || BNBWD) {
         float* const sc = (float*)smem + (wrow_m / (MF * 16)) * 2 * BN + wrow_n;      // this wave's [which][column] rows
         bool staged = false;
         if constexpr (NF == 4 && (MF % 2) == 0) staged = g.staged;
@@ -322,7 +402,7 @@ __device__ __forceinline__ void finish_tile(const GemmArgs& g, f32x4 (&acc)[NF][
                 float cs[8], cq[8];
 #pragma unroll
                 for (int q = 0; q < 8; ++q) cs[q] = cq[q] = 0.f;
-                epilogue_staged<MF, true>(g, acc, M, m0, n0, wrow_m, wrow_n, lane, smem + wave * (MF * 16 * 128), cs, cq);
+                epilogue_staged<MF, STATS, false, BNBWD>(g, acc, M, m0, n0, wrow_m, wrow_n, lane, smem + wave * (MF * 16 * 128), cs, cq);
 #pragma unroll
                 for (int q = 0; q < 8; ++q)
 #pragma unroll
@@ -339,8 +419,8 @@ __device__ __forceinline__ void finish_tile(const GemmArgs& g, f32x4 (&acc)[NF][
 #pragma unroll
             for (int i = 0; i < NF; ++i) {
                 float cs[4] = {0.f, 0.f, 0.f, 0.f}, cq[4] = {0.f, 0.f, 0.f, 0.f};
-                epilogue<MF, 1, true>(g, reinterpret_cast<f32x4 (&)[1][MF]>(acc[i]), M, m0, n0, wrow_m, wrow_n + i * 16, lane & 15,
-                                      lane >> 4, cs, cq);
+                epilogue<MF, 1, STATS, false, BNBWD>(g, reinterpret_cast<f32x4 (&)[1][MF]>(acc[i]), M, m0, n0, wrow_m, wrow_n + i * 16,
+                                                     lane & 15, lane >> 4, cs, cq);
 #pragma unroll
                 for (int q = 0; q < 4; ++q)
 #pragma unroll
@@ -409,9 +489,11 @@ __device__ __forceinline__ PhaseStep phase_step(const GemmArgs& g, int ph, int k
 
 template <int MODE /*0 linear, 1 conv*/, int BM, int BN, int WM, int WN, bool TWO = false /*conv with two concatenated sources*/,
           bool STATS = false /*conv that also writes its tile's column sums (finish_tile)*/,
-          bool PHASE = false /*stride-2 data gradient by parity phase (above)*/>
+          bool PHASE = false /*stride-2 data gradient by parity phase (above)*/,
+          bool BNBWD = false /*data gradient that also writes its tile's BatchNorm backward sums (finish_tile)*/>
 __global__ __launch_bounds__(THREADS) void igemm_kernel(GemmArgs g) {
     static_assert(!PHASE || (MODE == 1 && !TWO && !STATS), "the phase form is a one-source convolution");
+    static_assert(!BNBWD || (MODE == 1 && !TWO && !STATS && !PHASE), "the sums form is a one-source convolution, no phase form");
     constexpr int MF = BM / WM / 16;               // activation fragments per wave
     constexpr int NF = BN / WN / 16;               // weight fragments per wave
     constexpr int A_CH = BM * 8 / THREADS;         // 16-byte chunks per thread per K step (activations)
@@ -653,7 +735,7 @@ __global__ __launch_bounds__(THREADS) void igemm_kernel(GemmArgs g) {
         }
         return;
     }
-    finish_tile<MF, NF, STATS, WM, BN, PHASE>(g, acc, M, m0, n0, wrow_m, wrow_n, lane, wave, smem, tm, ph);
+    finish_tile<MF, NF, STATS, WM, BN, PHASE, BNBWD>(g, acc, M, m0, n0, wrow_m, wrow_n, lane, wave, smem, tm, ph);
 }
 
 // second stage of a split-K conv: sum the K slices, then the usual epilogue (bias, SiLU, bf16 shortcut, store)
@@ -900,9 +982,10 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_dma_kernel(GemmArgs g) {
 // Eligibility (host): (c0 + c1) % 64 == 0, c1 == 0 or (1 x 1 and c0 % 64 == 0), Cout >= 64, staged epilogue usable.
 // ---------------------------------------------------------------------------------------------
 template <int BN, int WM, int WN, int ST = 2 /* LDS stages: ST - 1 K steps of DMA in flight */, bool STATS = false /* as igemm_kernel */,
-          bool PHASE = false /* as igemm_kernel */>
+          bool PHASE = false /* as igemm_kernel */, bool BNBWD = false /* as igemm_kernel */>
 __global__ __launch_bounds__(256) void cgemm_dma_kernel(GemmArgs g) {
     static_assert(!(PHASE && STATS), "the phase form is a plain convolution");
+    static_assert(!(BNBWD && (PHASE || STATS)), "one kind of column sums, none of a phase launch");
     constexpr int BM = 128, NW = 4;
     static_assert(WM * WN == NW, "four waves");
     constexpr int MF = BM / WM / 16, NF = BN / WN / 16;
@@ -1063,7 +1146,7 @@ __global__ __launch_bounds__(256) void cgemm_dma_kernel(GemmArgs g) {
         }
     }
     asm volatile("s_barrier" ::: "memory");                       // the staged epilogue reuses the tile buffers
-    finish_tile<MF, NF, STATS, WM, BN, PHASE>(g, acc, M, m0, n0, wrow_m, wrow_n, lane, wave, smem, tm, ph);
+    finish_tile<MF, NF, STATS, WM, BN, PHASE, BNBWD>(g, acc, M, m0, n0, wrow_m, wrow_n, lane, wave, smem, tm, ph);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1973,7 +2056,9 @@ int launch(GemmArgs& g, hipStream_t st) {
     if (lds < (size_t)THREADS / 64 * (BM / WM) * 128) lds = (size_t)THREADS / 64 * (BM / WM) * 128;   // the staged epilogue's slabs
     void (*kern)(GemmArgs) = igemm_kernel<MODE, BM, BN, WM, WN, false>;
     if constexpr (MODE == 1) { if (g.c1 > 0) kern = igemm_kernel<MODE, BM, BN, WM, WN, true>; }
-    if constexpr (MODE == 1 && BM == 128) { if (g.stats) kern = igemm_kernel<MODE, BM, BN, WM, WN, false, true>; }
+    if constexpr (MODE == 1 && BM == 128) {                  // (g.z: yv_conv2d_bnbwd, the BatchNorm backward sums in place of STATS')
+        if (g.stats) kern = g.z ? igemm_kernel<MODE, BM, BN, WM, WN, false, false, false, true> : igemm_kernel<MODE, BM, BN, WM, WN, false, true>;
+    }
     if (!yv_grant_lds((const void*)kern, lds)) return YV_ERR_LAUNCH;
     const int S = g.splitk > 1 ? g.splitk : 1;
     hipLaunchKernelGGL(kern, dim3(g.tiles_m * g.tiles_n * S), dim3(THREADS), lds, st, g);
@@ -2000,7 +2085,7 @@ int launch_cdma(GemmArgs& g, hipStream_t st) {
     g.tiles_n = (g.N + BN - 1) / BN;
     const size_t lds = ST * (size_t)(128 + BN) * 128;
     void (*kern)(GemmArgs) = cgemm_dma_kernel<BN, WM, WN, ST>;
-    if (g.stats) kern = cgemm_dma_kernel<BN, WM, WN, ST, true>;
+    if (g.stats) kern = g.z ? cgemm_dma_kernel<BN, WM, WN, ST, false, false, true> : cgemm_dma_kernel<BN, WM, WN, ST, true>;
     if (!yv_grant_lds((const void*)kern, lds)) return YV_ERR_LAUNCH;
     hipLaunchKernelGGL(kern, dim3(g.tiles_m * g.tiles_n), dim3(256), lds, st, g);
     return yv_launch_status();
@@ -2668,10 +2753,14 @@ extern "C" int yv_linear_route(int M, int N, int K, int lda, int ldo, int flags,
                           ldaux, &q);
 }
 
+// yv_conv2d_bnbwd: the BatchNorm block whose output gradient the convolution stores
+struct BnBwdOps { const void* z; int ldz; const float *mean, *rstd, *gamma, *beta; int act; };
+
 static int conv_impl_one(const yv_view* in0, const yv_view* in1, int B, int Hout, int Wout, int ksize, int stride,
                          const void* weight, const float* bias, int Cout, void* out, int out_ld, const void* res,
                          int res_ld, int flags, void* ws, size_t ws_bytes, void* stream, bool query = false,
-                         float* stats = nullptr /* yv_conv2d_stats: the tile partials; never split-K */) {
+                         float* stats = nullptr /* yv_conv2d_stats / _bnbwd: the tile partials; never split-K */,
+                         const BnBwdOps* bb = nullptr /* yv_conv2d_bnbwd: the sums are the BatchNorm backward's */) {
     if (!in0 || !in0->ptr || !weight || !out || B <= 0 || Hout <= 0 || Wout <= 0 || Cout <= 0) return YV_ERR_ARG;
     if (!(ksize == 1 || ksize == 3) || !(stride == 1 || stride == 2)) return YV_ERR_ARG;
     if (in1 && in1->ptr && ksize != 1) return YV_ERR_ARG;
@@ -2705,6 +2794,10 @@ static int conv_impl_one(const yv_view* in0, const yv_view* in1, int B, int Hout
     if (query) return conv_instance_code(g, kern);                // yv_conv2d_instance: the route, no launch
     if (g.splitk > 1) g.partial = (float*)ws;
     g.stats = stats;
+    if (bb) {
+        g.z = (const uint16_t*)bb->z; g.ldz = bb->ldz; g.bn_act = bb->act;
+        g.bn_mean = bb->mean; g.bn_rstd = bb->rstd; g.bn_gamma = bb->gamma; g.bn_beta = bb->beta;
+    }
     return launch_conv(g, kern, (hipStream_t)stream);
 }
 
@@ -2924,6 +3017,70 @@ extern "C" int yv_conv2d_stats(const yv_view* in0, int B, int Hout, int Wout, in
     if (stats_ws_floats < yv_conv_stats_ws_floats((long long)B * Hout * Wout, Cout)) return YV_ERR_WORKSPACE;
     return conv_impl_one(in0, nullptr, B, Hout, Wout, ksize, stride, weight, bias, Cout, out, out_ld, nullptr, 0, flags, ws, ws_bytes,
                          stream, false, stats_ws);
+}
+
+// One launch, one tile sequence: false where yv_conv2d_ws would take the batch in sub-batches
+static bool conv_one_batch(const yv_view* in0, int B, int Hout, int Wout, int stride) {
+    const long long Hin = (long long)Hout * stride, Win = (long long)Wout * stride;
+    const long long s0 = (Hin >> in0->up) * (Win >> in0->up) * in0->ld * 2;
+    return conv_sub_batch(s0, 0, (Win + 1) * in0->ld * 2) >= B;
+}
+
+extern "C" int yv_conv2d_bnbwd(const yv_view* in0, int B, int Hout, int Wout, int ksize, int stride, const void* weight,
+                               const float* bias, int Cout, void* out, int out_ld, const void* res, int res_ld, int flags,
+                               const void* z, int ldz, const float* mean, const float* rstd, const float* gamma, const float* beta,
+                               int act, float* stats_ws, size_t stats_ws_floats, void* ws, size_t ws_bytes, void* stream) {
+    if (!stats_ws || !z || !mean || !rstd || !gamma || !beta || (flags & ~(YV_EPI_BIAS | YV_EPI_RES_BF16)) || Cout <= 0 || (Cout & 7))
+        return YV_ERR_ARG;
+    if ((ldz & 7) || ldz < Cout || (act & ~1)) return YV_ERR_ARG;
+    if (((uintptr_t)z | (uintptr_t)out | (uintptr_t)res | (uintptr_t)stats_ws | (uintptr_t)mean | (uintptr_t)rstd | (uintptr_t)gamma |
+         (uintptr_t)beta) & 15)
+        return YV_ERR_ARG;
+    // the argument checks of yv_conv2d_ws, by its route query: nothing is launched
+    const int code = conv_impl_one(in0, nullptr, B, Hout, Wout, ksize, stride, weight, bias, Cout, out, out_ld, res, res_ld, flags, ws,
+                                   ws_bytes, stream, true, stats_ws);
+    if (code < 0) return code;
+    if (!conv_one_batch(in0, B, Hout, Wout, stride)) return YV_ERR_LIMIT;
+    if (stats_ws_floats < yv_conv_bnbwd_ws_floats((long long)B * Hout * Wout, Cout)) return YV_ERR_WORKSPACE;
+    const BnBwdOps bb = {z, ldz, mean, rstd, gamma, beta, act};
+    return conv_impl_one(in0, nullptr, B, Hout, Wout, ksize, stride, weight, bias, Cout, out, out_ld, res, res_ld, flags, ws, ws_bytes,
+                         stream, false, stats_ws, &bb);
+}
+
+extern "C" int yv_conv2d_bnbwd_route(int B, int Hout, int Wout, int ksize, int stride, int Cin, int in_ld, int Cout, int out_ld,
+                                     int res_ld, int ldz, int flags, size_t ws_bytes, yv_conv_bnbwd_route_t* route) {
+    // 16-byte aligned bases; nothing is dereferenced or launched
+    static unsigned char dummy[16] __attribute__((aligned(16)));
+    if (!route || Cin <= 0 || (flags & ~(YV_EPI_BIAS | YV_EPI_RES_BF16)) || Cout <= 0 || (Cout & 7) || (ldz & 7) || ldz < Cout)
+        return YV_ERR_ARG;
+    const yv_view v = {dummy, in_ld, Cin, 0};
+    const void* res = (flags & YV_EPI_RES_BF16) ? dummy : nullptr;
+    const int own = conv_impl_one(&v, nullptr, B, Hout, Wout, ksize, stride, dummy, (const float*)dummy, Cout, dummy, out_ld, res, res_ld,
+                                  flags, ws_bytes ? dummy : nullptr, ws_bytes, nullptr, true, (float*)dummy);
+    if (own < 0) return own;
+    if (!conv_one_batch(&v, B, Hout, Wout, stride)) return YV_ERR_LIMIT;
+    const int plain = conv_impl_one(&v, nullptr, B, Hout, Wout, ksize, stride, dummy, (const float*)dummy, Cout, dummy, out_ld, res,
+                                    res_ld, flags, ws_bytes ? dummy : nullptr, ws_bytes, nullptr, true);
+    if (plain < 0) return plain;
+    const int kern = own & 15, bn = (kern == CK_IGEMM_128 || kern >= CK_CDMA_128_2) ? 128 : (kern == CK_IGEMM_32 ? 32 : (kern == CK_IGEMM_16 ? 16 : 64));
+    const long long tiles = ((long long)B * Hout * Wout + 127) / 128;
+    route->kernel = kern;
+    route->staged = (own & 16) != 0;
+    route->tiles = (int)tiles;
+    route->workgroups = (int)(tiles * ((Cout + bn - 1) / bn));
+    route->splitk = (plain & 32) != 0;
+    // use: 0 where the unfused call splits K (its bits differ from a one-pass convolution's), and 0 where the per-pair measurement
+    // (profiles/bn_bwd_fused_layers.txt, DESIGN.md section 27: YOLOv8s and YOLOv8n at 16 x 640^2) had the fused pair slower than
+    // conv + bn_act_bwd by more than the spread of its rounds: there the z read and the terms at the end of every tile cost more
+    // than the pass over da and z they replace.  That is (a) every 64- and 128-wide instance on the large maps (>= 100 k rows, the
+    // 80 x 80 maps and above: x 1.06 - 1.13, the 128-wide igemm tile, which loses a workgroup per CU, x 1.42), and (b) the 32-wide
+    // tile on >= 400 k rows with K >= 512 (the two 3 x 3 gradients from 64 channels: x 1.06 and x 1.01).  Every pair below 100 k
+    // rows and every 16-wide one was faster (x 0.53 - 0.97).
+    const long long M = (long long)B * Hout * Wout;
+    const int K = ksize * ksize * Cin;
+    const bool slow = (kern >= CK_IGEMM_64 && M >= 100000) || (kern == CK_IGEMM_32 && M >= 400000 && K >= 512);
+    route->use = !route->splitk && !slow;
+    return YV_OK;
 }
 
 extern "C" int yv_conv2d_instance(int B, int Hout, int Wout, int ksize, int stride, int c0, int c1, int Cout, int out_ld,

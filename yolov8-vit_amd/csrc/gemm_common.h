@@ -58,6 +58,11 @@ struct GemmArgs {
     const uint8_t* mx_sw;
     long long mx_rows_a, mx_rows_w;
     float* stats;                // STATS convolutions (yv_conv2d_stats): per-tile column sums (tiles_m, 2, N), see finish_tile
+    // BNBWD convolutions (yv_conv2d_bnbwd; sums to `stats`): the BatchNorm block that produced this data gradient's target -
+    const uint16_t* z;           // its pre-activation, same rows and columns as `out` (row stride ldz) ...
+    int ldz;
+    int bn_act;                  // ... its activation (1 SiLU, 0 identity) and its per-channel constants (N floats each)
+    const float *bn_mean, *bn_rstd, *bn_gamma, *bn_beta;
 };
 
 // tuning options read in both units (defined and described in gemm_persistent.hip) and the persistent launchers

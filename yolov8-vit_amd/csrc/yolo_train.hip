@@ -14,6 +14,7 @@
 //   yv_conv_weight_dgrad (Cout, taps, Cin) -> (Cin, flipped taps, Cout): the data gradient is a conv with this weight
 // All HBM-bound element-wise / reduction kernels: 16-byte accesses over 8-channel groups, f32 math.
 #include "yv_common.h"
+#include "bn_act_grad.h"
 
 namespace {
 
@@ -28,7 +29,6 @@ __device__ __forceinline__ void unpack8(const uint4& v, float* f) {
 __device__ __forceinline__ uint4 pack8(const float* f) {
     return make_uint4(pack_bf16x2(f[0], f[1]), pack_bf16x2(f[2], f[3]), pack_bf16x2(f[4], f[5]), pack_bf16x2(f[6], f[7]));
 }
-__device__ __forceinline__ float sigmoid_f(float x) { return 1.0f / (1.0f + __expf(-x)); }
 
 __global__ __launch_bounds__(256) void blob_kernel(const uint8_t* __restrict__ img, long long pixels,
                                                    uint16_t* __restrict__ out) {
@@ -81,13 +81,8 @@ __global__ __launch_bounds__(256) void chan_reduce_kernel(RedArgs a) {
                 unpack8(dq, d);
 #pragma unroll
                 for (int i = 0; i < 8; ++i) {
-                    const float xh = (z[i] - mu[i]) * rs[i];
-                    float gr = d[i];
-                    if (a.act) {
-                        const float u = ga[i] * xh + be[i];
-                        const float sg = sigmoid_f(u);
-                        gr *= sg * (1.0f + u * (1.0f - sg));
-                    }
+                    float xh;
+                    const float gr = bn_act_grad_term(d[i], z[i], mu[i], rs[i], ga[i], be[i], a.act, xh);
                     s0[i] += gr; s1[i] += gr * xh;
                 }
             }
@@ -239,13 +234,8 @@ __global__ __launch_bounds__(256) void bn_act_kernel(ActArgs a) {
             unpack8(*(const uint4*)(a.da + r * a.ldda + g * 8), d);
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
-                const float xh = (z[i] - mu[i]) * rs[i];
-                float gr = d[i];
-                if (a.act) {
-                    const float u = gam[i] * xh + bet[i];
-                    const float sg = sigmoid_f(u);
-                    gr *= sg * (1.0f + u * (1.0f - sg));
-                }
+                float xh;
+                const float gr = bn_act_grad_term(d[i], z[i], mu[i], rs[i], gam[i], bet[i], a.act, xh);
                 o[i] = sc[i] * (gr - k1[i] - xh * k2[i]);
             }
         }
@@ -521,6 +511,41 @@ extern "C" int yv_bn_act_bwd(const void* da, long long ldda, const void* z, long
     float* coef = ws + (size_t)chunks * 2 * C;
     hipLaunchKernelGGL(chan_reduce_kernel<1>, dim3(chunks), dim3(256), (size_t)rp * 2 * C * sizeof(float), (hipStream_t)stream, r);
     hipLaunchKernelGGL(bn_bwd_final_kernel, dim3((C + 7) / 8), dim3(256), 0, (hipStream_t)stream, ws, chunks, C, T,
+                       batch_stats, dgamma, dbeta, coef);
+    ActArgs a = {};
+    a.z = (const uint16_t*)z; a.ldz = ldz; a.da = (const uint16_t*)da; a.ldda = ldda; a.out = (uint16_t*)dz; a.ldo = lddz;
+    a.T = T; a.C = C; a.mean = mean; a.rstd = rstd; a.gamma = gamma; a.beta = beta; a.coef = coef; a.act = act;
+    hipLaunchKernelGGL(bn_act_kernel<true>, dim3(act_blocks(T, C)), dim3(256), 0, (hipStream_t)stream, a);
+    return yv_launch_status();
+}
+
+extern "C" size_t yv_conv_bnbwd_ws_floats(long long T, int Cout) {
+    if (T <= 0 || Cout <= 0) return 0;
+    return yv_conv_stats_ws_floats(T, Cout) + 2 * (size_t)Cout;          // + coef (2, C) for the apply pass
+}
+
+// yv_bn_act_bwd with its first pass taken by yv_conv2d_bnbwd: the tile partials (tiles, 2, C) are chan_reduce_kernel<1>'s chunk
+// partials in layout, so the finaliser and the apply pass run as they are
+extern "C" int yv_bn_act_bwd_finish(const void* da, long long ldda, const void* z, long long ldz, long long T, int C,
+                                    const float* mean, const float* rstd, const float* gamma, const float* beta, int act,
+                                    int batch_stats, float* dgamma, float* dbeta, void* dz, long long lddz, float* stats_ws,
+                                    void* stream) {
+    if (!da || !z || !dz || !mean || !rstd || !gamma || !beta || !dgamma || !dbeta || !stats_ws) return YV_ERR_ARG;
+    if (!bn_shape_ok(T, C, ldz) || T > 0x7fffffffLL || (ldda & 7) || ldda < C || (lddz & 7) || lddz < C) return YV_ERR_ARG;
+    if (((uintptr_t)da | (uintptr_t)z | (uintptr_t)dz) & 15) return YV_ERR_ARG;
+    const int tiles = (int)((T + 127) / 128);
+    int group;
+    int chunks = stats_chunks(tiles, &group);
+    const float* partial = stats_ws;
+    if (tiles > 2048) {
+        hipLaunchKernelGGL(bn_stats_fold_kernel, dim3(blocks_for((long long)chunks * 2 * C)), dim3(256), 0, (hipStream_t)stream,
+                           stats_ws, tiles, group, chunks, C);
+        partial = stats_ws + (size_t)tiles * 2 * C;
+    } else {
+        chunks = tiles;
+    }
+    float* coef = stats_ws + yv_conv_stats_ws_floats(T, C);
+    hipLaunchKernelGGL(bn_bwd_final_kernel, dim3((C + 7) / 8), dim3(256), 0, (hipStream_t)stream, partial, chunks, C, T,
                        batch_stats, dgamma, dbeta, coef);
     ActArgs a = {};
     a.z = (const uint16_t*)z; a.ldz = ldz; a.da = (const uint16_t*)da; a.ldda = ldda; a.out = (uint16_t*)dz; a.ldo = lddz;

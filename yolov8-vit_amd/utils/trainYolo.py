@@ -50,7 +50,7 @@ def train(epochs, batch, data, weights=None, scale="n", size=640, save=None, dev
           optimizer="auto", lr0=1e-4, lrf=1e-4, momentum=0.937, weight_decay=5e-4, warmup_epochs=3.0, augment=True,
           close_mosaic=10, hsv_h=0.015, hsv_s=0.7, hsv_v=0.4, degrees=0.0, translate=0.1, aug_scale=0.5, shear=0.0,
           perspective=0.0, flipud=0.0, fliplr=0.5, mosaic=1.0, mixup=0.0, copy_paste=0.0, narrow_wgrad=None,
-          fused_bn_stats=None, phase_dgrad=None, gather_wgrad=None):
+          fused_bn_stats=None, phase_dgrad=None, gather_wgrad=None, fused_bn_bwd=None):
     """utils/trainYolo.py:6-35: `model.train(epochs=, batch=, data=, lr0=1e-4, lrf=1e-4)` with the ultralytics defaults
     around it: optimizer 'auto' (see _auto_optimizer), linear lr0 -> lr0*lrf schedule, warm-up over
     max(3 epochs, 100 iterations) (lr from 0 - biases from 0.1, 0.0 under AdamW - and momentum from 0.8), gradient
@@ -63,7 +63,7 @@ def train(epochs, batch, data, weights=None, scale="n", size=640, save=None, dev
     it pastes instance masks and the dataset format here holds boxes only.
     `narrow_wgrad` is YoloTrainer's opt-in of the same name (None: the YV_YOLO_NARROW_WGRAD environment variable).
     `fused_bn_stats` likewise (None: YV_YOLO_FUSED_BN_STATS), `phase_dgrad` (None: YV_YOLO_PHASE_DGRAD) and
-    `gather_wgrad` (None: YV_YOLO_GATHER_WGRAD).
+    `gather_wgrad` (None: YV_YOLO_GATHER_WGRAD) and `fused_bn_bwd` (None: YV_YOLO_FUSED_BN_BWD).
     Returns {"epochs": [...per-epoch mean (total, box, cls, dfl)...], "weights": path or None, "not_built": [...]}."""
     import numpy as np
     from yvhip.yolo_data import list_samples, load_batch, max_boxes_per_image, read_data_yaml
@@ -102,7 +102,7 @@ def train(epochs, batch, data, weights=None, scale="n", size=640, save=None, dev
     wd = weight_decay * B * accumulate / NBS
     tr = YoloTrainer(state, scale=scale, nc=nc, size=size, batch=B, lr=lr0, momentum=momentum, weight_decay=wd, device=device,
                      optimizer=opt, ema=True, narrow_wgrad=narrow_wgrad, fused_bn_stats=fused_bn_stats,
-                     phase_dgrad=phase_dgrad, gather_wgrad=gather_wgrad)
+                     phase_dgrad=phase_dgrad, gather_wgrad=gather_wgrad, fused_bn_bwd=fused_bn_bwd)
     G = max_boxes_per_image(samples)
     nb = max(len(samples) // B, 1)                             # batches per epoch (last short batch dropped)
     nw = max(round(warmup_epochs * nb), 100) if warmup_epochs > 0 else -1

@@ -110,6 +110,12 @@ _SIGS = {
     "yv_bn_stats_finish": (_i, [_vp, C.c_longlong, _i, _f, _f, _vp, _vp, _vp, _vp, _vp]),
     "yv_conv_stats_ws_floats": (_sz, [C.c_longlong, _i]),
     "yv_conv2d_stats": (_i, [C.POINTER(yv_view), _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _i, _i, _vp, _sz, _vp, _sz, _vp]),
+    "yv_conv2d_bnbwd": (_i, [C.POINTER(yv_view), _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp,
+                             _i, _vp, _sz, _vp, _sz, _vp]),
+    "yv_conv_bnbwd_ws_floats": (_sz, [C.c_longlong, _i]),
+    "yv_conv2d_bnbwd_route": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _sz, _vp]),
+    "yv_bn_act_bwd_finish": (_i, [_vp, C.c_longlong, _vp, C.c_longlong, C.c_longlong, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp,
+                                  _vp, C.c_longlong, _vp, _vp]),
     "yv_bn_act_fwd": (_i, [_vp, C.c_longlong, C.c_longlong, _i, _vp, _vp, _vp, _vp, _vp, C.c_longlong, _vp, C.c_longlong,
                            _i, _vp]),
     "yv_bn_act_bwd": (_i, [_vp, C.c_longlong, _vp, C.c_longlong, C.c_longlong, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp,
@@ -1094,6 +1100,55 @@ def conv_view_stats(in0: "yv_view", B: int, Hout: int, Wout: int, ksize: int, st
     ws = _conv_workspace(weight.device)
     check(lib.yv_conv2d_stats(C.byref(in0), B, Hout, Wout, ksize, stride, _p(weight), _p(bias), Cout, out.ptr, out.ld, flags,
                               _p(stats_ws), stats_ws.numel(), _p(ws), ws.numel() * 4, _st()), "yv_conv2d_stats")
+
+
+def conv_bnbwd_ws_floats(T: int, Cout: int) -> int:
+    """Floats of conv_view_bnbwd's `stats_ws` for T output rows: conv_stats_ws_floats + the 2 * Cout coefficients of the apply pass."""
+    return int(lib.yv_conv_bnbwd_ws_floats(T, Cout))
+
+
+ConvBnBwdRoute = collections.namedtuple("ConvBnBwdRoute", "kernel staged tiles workgroups splitk use")
+
+
+def conv_bnbwd_route(B: int, Hout: int, Wout: int, ksize: int, stride: int, Cin: int, Cout: int, in_ld: Optional[int] = None,
+                     out_ld: Optional[int] = None, res_ld: Optional[int] = None, ldz: Optional[int] = None,
+                     flags: Optional[int] = None, ws_bytes: int = CONV_WS_BYTES) -> ConvBnBwdRoute:
+    """Route conv_view_bnbwd takes for this data gradient under the current options (host only): see yv_conv2d_bnbwd_route in
+    include/yv_hip.h.  Dense rows, a residual of the output's stride (EPI_RES_BF16, as the trainer accumulates) and conv_view's
+    split-K workspace by default; raises YvError where the entry rejects the call; use = False: keep conv_view + bn_act_bwd."""
+    out = (C.c_int * 6)()
+    out_ld = Cout if out_ld is None else out_ld
+    check(lib.yv_conv2d_bnbwd_route(B, Hout, Wout, ksize, stride, Cin, Cin if in_ld is None else in_ld, Cout, out_ld,
+                                    out_ld if res_ld is None else res_ld, Cout if ldz is None else ldz,
+                                    EPI_RES_BF16 if flags is None else flags, ws_bytes, out), "yv_conv2d_bnbwd_route")
+    return ConvBnBwdRoute(out[0], bool(out[1]), out[2], out[3], bool(out[4]), bool(out[5]))
+
+
+def conv_view_bnbwd(in0: "yv_view", B: int, Hout: int, Wout: int, ksize: int, stride: int, weight: torch.Tensor, Cout: int,
+                    out: "yv_view", z: "yv_view", mean, rstd, gamma, beta, stats_ws: torch.Tensor, act: int = 1,
+                    res: Optional["yv_view"] = None, bias: Optional[torch.Tensor] = None, flags: int = 0):
+    """conv_view (bf16 out, optional bias and bf16 residual) as the data gradient that writes the gradient of a BatchNorm block's
+    output, leaving that block's backward sums per tile in `stats_ws` (f32, >= conv_bnbwd_ws_floats(B*Hout*Wout, Cout) floats)
+    for bn_act_bwd_finish: yv_conv2d_bnbwd.  z, mean, rstd, gamma, beta, act: the producer's, as bn_act_bwd takes them."""
+    if bias is not None:
+        flags |= EPI_BIAS
+    if res is not None:
+        flags |= EPI_RES_BF16
+    ws = _conv_workspace(weight.device)
+    check(lib.yv_conv2d_bnbwd(C.byref(in0), B, Hout, Wout, ksize, stride, _p(weight), _p(bias), Cout, out.ptr, out.ld,
+                              res.ptr if res is not None else None, res.ld if res is not None else 0, flags, z.ptr, z.ld,
+                              _p(mean), _p(rstd), _p(gamma), _p(beta), act, _p(stats_ws), stats_ws.numel(), _p(ws), ws.numel() * 4,
+                              _st()), "yv_conv2d_bnbwd")
+
+
+def bn_act_bwd_finish(da: "yv_view", z: "yv_view", T: int, mean, rstd, gamma, beta, dgamma, dbeta, dz: "yv_view", stats_ws,
+                      act: int = 1, batch_stats: bool = True):
+    """bn_act_bwd's finaliser and apply pass on the tile partials conv_view_bnbwd left in `stats_ws`: yv_bn_act_bwd_finish."""
+    if stats_ws.numel() < conv_bnbwd_ws_floats(T, z.c):
+        raise YvError("yv_bn_act_bwd_finish: stats_ws is smaller than conv_bnbwd_ws_floats(T, C)")
+    check(lib.yv_bn_act_bwd_finish(da.ptr, da.ld, z.ptr, z.ld, T, z.c, _p(mean), _p(rstd), _p(gamma), _p(beta), act,
+                                   1 if batch_stats else 0, _p(dgamma), _p(dbeta), dz.ptr, dz.ld, _p(stats_ws), _st()),
+          "yv_bn_act_bwd_finish")
 
 
 def mview(t: torch.Tensor, c_off: int = 0, c: Optional[int] = None) -> "yv_view":

@@ -28,7 +28,7 @@ import torch
 
 import yvhip as _yv
 from . import (OPT_ADAMW, OPT_SGD_NESTEROV, VIEW_ADD, VIEW_COPY, VIEW_PAD, VIEW_UP2, VIEW_UP2_BWD, VIEW_ZERO_INSERT, YvError, axpby,
-               blob_nhwc8, bn_act_bwd, bn_act_fwd, ema_update, optim_step,
+               blob_nhwc8, bn_act_bwd, bn_act_bwd_finish, bn_act_fwd, conv_view_bnbwd, ema_update, optim_step,
                bn_stats, bn_stats_finish, bn_ws_floats, cast_colsum, colsum_ws_floats, conv_stats_ws_floats, conv_view,
                conv_dgrad_s2, conv_dgrad_s2_route, conv_view_stats, conv_weight_dgrad, detect_loss,
                detect_loss_ws_bytes, im2col3, maxpool5_bwd, mview, require_gpu, sgd_step, sppf_pool, view_op, wgrad, wgrad_conv3,
@@ -138,6 +138,38 @@ def train_backward_order(scale: str, nc: int = 5) -> tuple:
     return tuple(scales + [u for u in reversed(units) if not isinstance(u[0].unit, tuple)])
 
 
+@functools.lru_cache(maxsize=None)
+def fused_bn_bwd_pairs(scale: str, nc: int = 5) -> Dict[str, str]:
+    """{producer key: consumer key} of the BatchNorm blocks whose output gradient is written completely by ONE launch, the data
+    gradient of the block that runs right before them in backward() (host only; the wiring's half of YoloTrainer(fused_bn_bwd=True),
+    DESIGN.md section 27).  A producer qualifies if exactly one entry of train_launches reads any channel of its output view, that
+    entry is a Block whose input view IS that view (no Concat, no Pool, no other block's residual slice) and the producer is the next
+    Block train_backward_order runs behind that consumer."""
+    launches = train_launches(scale, nc)
+    order = [e for group in train_backward_order(scale, nc) for e in group if isinstance(e, Block)]
+    nxt = {a.key: b.key for a, b in zip(order, order[1:])}
+    overlap = lambda buf, lo, n, view: buf == view[0] and lo < view[1] + view[2] and view[1] < lo + n
+
+    def readers(view):
+        for e in launches:
+            if isinstance(e, Block):
+                if overlap(*e.src, view) or (e.res_off is not None and overlap(e.out[0], e.res_off, e.out[2], view)):
+                    yield e
+            elif isinstance(e, Concat):
+                if any(name == view[0] for name, _, _, _ in e.srcs):
+                    yield e
+            elif overlap(e.buf, 0, 4 * e.c, view):
+                yield e
+
+    pairs = {}
+    for p in launches:
+        if isinstance(p, Block) and p.bn:
+            rd = list(readers(p.out))
+            if len(rd) == 1 and isinstance(rd[0], Block) and rd[0].src == p.out and rd[0].dgrad and nxt.get(rd[0].key) == p.key:
+                pairs[p.key] = rd[0].key
+    return pairs
+
+
 def _state_dict_order(launches) -> List[Block]:
     """The blocks in the order ultralytics registers them (which the flat parameter buffer follows): forward order, except that a
     C2f's cv2 sits in front of its bottlenecks."""
@@ -162,6 +194,28 @@ def _activations(launches) -> List[Tuple[str, int, int]]:
     rank = lambda name: ("x", "out", "y", "t", "cat", "det").index(re.match("[a-z]+", name).group())
     return [(name, d, c) for _, unit in itertools.groupby(dims.items(), key=lambda kv: kv[1][0])
             for name, (_, d, c) in sorted(unit, key=lambda kv: rank(kv[0]))]
+
+
+def fused_bn_bwd_plan(scale: str, nc: int, size: int, batch: int, phase_blocks=frozenset()) -> Dict[str, str]:
+    """{consumer key: producer key} of the pairs YoloTrainer(fused_bn_bwd=True) fuses at this size and batch (host only): the pairs
+    of fused_bn_bwd_pairs whose consumer's data gradient is not a phase launch (`phase_blocks`: the trainer's _phase_blocks; the
+    PHASE form takes no sums) and whose route says `use`, i.e. conv_view would not split K for the same call.  The route is reached
+    through the package so that a launch trace, which stubs the wrappers this module imports, gets the real answer."""
+    launches = train_launches(scale, nc)
+    by_key = {e.key: e for e in launches if isinstance(e, Block)}
+    width = {name: c for name, _, c in _activations(launches)}
+    plan = {}
+    for pkey, ckey in fused_bn_bwd_pairs(scale, nc).items():
+        c, hin, ld = by_key[ckey], size // by_key[ckey].down_in, width[by_key[ckey].src[0]]
+        if ckey in phase_blocks:
+            continue
+        try:                                            # the data gradient: (batch, hin, hin) x c.cout -> c.cin, stride 1
+            use = _yv.conv_bnbwd_route(batch, hin, hin, c.k, 1, c.cout, c.cin, out_ld=ld, res_ld=ld, ldz=by_key[pkey].cout).use
+        except YvError:
+            use = False
+        if use:
+            plan[ckey] = pkey
+    return plan
 
 
 def init_yolo_train_state(scale: str = "n", nc: int = 5, seed: int = 42) -> Dict[str, torch.Tensor]:
@@ -266,7 +320,8 @@ class YoloTrainer:
                  lr: float = 1e-4, momentum: float = 0.937, weight_decay: float = 5e-4, device: str = "cuda:0",
                  optimizer: str = "sgd", ema: bool = False, ema_decay: float = 0.9999, ema_tau: float = 2000.0,
                  overlap_wgrad: bool = True, implicit_wgrad: bool = True, narrow_wgrad: Optional[bool] = None,
-                 fused_bn_stats: Optional[bool] = None, phase_dgrad: Optional[bool] = None, gather_wgrad: Optional[bool] = None):
+                 fused_bn_stats: Optional[bool] = None, phase_dgrad: Optional[bool] = None, gather_wgrad: Optional[bool] = None,
+                 fused_bn_bwd: Optional[bool] = None):
         require_gpu()
         if size % 32:
             raise YvError("input size must be a multiple of 32")
@@ -289,6 +344,13 @@ class YoloTrainer:
         # trainer is the im2col statement); DESIGN.md section 26
         self.gather_wgrad = _env_flag(gather_wgrad, "YV_YOLO_GATHER_WGRAD")
         self._gather_blocks: set = set()
+        # opt-in: the two reductions of a BatchNorm block's backward from the epilogue of the data gradient that writes the block's
+        # output gradient (yv_conv2d_bnbwd + yv_bn_act_bwd_finish) in place of bn_act_bwd's pass over da and z, for the pairs of
+        # fused_bn_bwd_plan (asked once, at construction, and only with the flag on); DESIGN.md section 27
+        self.fused_bn_bwd = _env_flag(fused_bn_bwd, "YV_YOLO_FUSED_BN_BWD")
+        self._bnbwd_of: Dict[str, str] = {}               # consumer key -> producer key
+        self._bnbwd_producers: set = set()
+        self.bn_bwd_ws: Optional[torch.Tensor] = None      # the pairs' tile partials (not self.ws: the consumer's own bn_act_bwd uses that)
         if optimizer not in ("sgd", "sgd_nesterov", "adamw"):
             raise YvError("optimizer must be 'sgd', 'sgd_nesterov' or 'adamw'")
         self.optimizer, self.use_ema, self.ema_decay, self.ema_tau = optimizer, ema, ema_decay, ema_tau
@@ -463,6 +525,14 @@ class YoloTrainer:
         self.zi = torch.zeros(max(zi_n, 8), dtype=torch.bfloat16, device=dev)
         self.xp = torch.zeros(max(xp_n, 8), dtype=torch.bfloat16, device=dev)       # zero-initialised: its margins are read
         self.dzp = torch.zeros(max(dzp_n, 8), dtype=torch.bfloat16, device=dev)
+        if self.fused_bn_bwd:
+            bw_f = 0
+            self._bnbwd_of = fused_bn_bwd_plan(self.scale, self.nc, S, B, frozenset(self._phase_blocks))
+            self._bnbwd_producers = set(self._bnbwd_of.values())
+            for pkey in self._bnbwd_producers:
+                hout = self.geom[pkey][1]
+                bw_f = max(bw_f, _yv.conv_bnbwd_ws_floats(B * hout * hout, self.block[pkey].cout))
+            self.bn_bwd_ws = torch.zeros(max(bw_f, 16), device=dev)
         for b in self.blocks:
             b.bind(self)
 
@@ -503,7 +573,9 @@ class YoloTrainer:
         block's parameter gradients and, accumulated, the gradients of its input (b.dx) and of its residual (b.dres)."""
         hin, hout = self.geom[b.key]
         T = self.B * hout * hout
-        if b.bn:
+        if b.bn and b.key in self._bnbwd_producers:             # the sums are in bn_bwd_ws: the consumer's data gradient left them
+            bn_act_bwd_finish(b.dy, b.zv, T, *b.stat, *b.affine, *b.daffine, b.dzv, self.bn_bwd_ws)
+        elif b.bn:
             bn_act_bwd(b.dy, b.zv, T, *b.stat, *b.affine, *b.daffine, b.dzv, self.ws)
         else:                                                   # the f32 loss gradient (T, cout): cast + bias gradient
             cast_colsum(b.dy if da is None else da, self.dz[b.key], b.dbias, self.ws)
@@ -523,7 +595,12 @@ class YoloTrainer:
                     zi = self.zi[:self.B * hin * hin * b.cout].view(self.B * hin * hin, b.cout)
                     view_op(VIEW_ZERO_INSERT, b.dzv, mview(zi), self.B, hout, hout)
                     src = mview(zi)
-                conv_view(src, self.B, hin, hin, b.k, 1, wd.view(b.cin, b.taps * b.cout), b.cin, b.dx, res=b.dx)
+                if b.key in self._bnbwd_of:                     # b.dx is the producer's whole output gradient, written here only
+                    p = self.block[self._bnbwd_of[b.key]]
+                    conv_view_bnbwd(src, self.B, hin, hin, b.k, 1, wd.view(b.cin, b.taps * b.cout), b.cin, b.dx, p.zv, *p.stat, *p.affine,
+                                    self.bn_bwd_ws, res=b.dx)
+                else:
+                    conv_view(src, self.B, hin, hin, b.k, 1, wd.view(b.cin, b.taps * b.cout), b.cin, b.dx, res=b.dx)
         if b.dres is not None:                                  # behind the block, in front of the one that wrote the residual
             view_op(VIEW_ADD, b.dy, b.dres, self.B, hout, hout)
 
