@@ -755,6 +755,31 @@ int yv_transpose_bf16_batched(const void* src, void* dst, int rows, int cols, in
 int yv_optim_step(int kind, float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2,
                   float eps, float weight_decay, float grad_scale, int step, void* bf16_mirror, void* stream);
 
+/* Global-norm gradient clipping: torch.nn.utils.clip_grad_norm_(parameters, max_norm) ahead of the optimiser step (the
+ * published YOLOv8 trainer: max_norm 10), as a four-float record in device memory that the *_rec steps below read, so that no
+ * step waits on the host.  rec, each line one correctly rounded f32 operation:
+ *   rec[0] = S = f32(sum_i (double)g[i]^2)   accumulated in f64 (squares are exact there) in an order n alone decides, without
+ *                                            atomics: the same bits on every run and every device
+ *   rec[1] = N = sqrt(S) * |grad_scale|      the norm of the gradient as the optimiser sees it
+ *   rec[2] = c = min(1, max_norm / (N + 1e-6))
+ *   rec[3] = s = grad_scale * c              what the step multiplies g by
+ * N not finite (a NaN or Inf element, or S past f32): rec[2] = rec[3] = 0 and *skipped (optional) is incremented by one.
+ * Two launches: one f64 partial per workgroup into ws, then one workgroup for the record.
+ * ws: yv_grad_clip_ws_bytes(n) bytes (0 for n = 0; non-decreasing in n, constant once the grid is at its cap); less is
+ * YV_ERR_LIMIT.  g and ws 16-byte aligned, max_norm > 0 (+inf: measure, never clip), grad_scale finite, n > 0, no null g / ws /
+ * rec: otherwise YV_ERR_ARG.  All of these are decided on the host before any HIP call. */
+size_t yv_grad_clip_ws_bytes(size_t n);
+int yv_grad_clip_record(const float* g, size_t n, float grad_scale, float max_norm, void* ws, size_t ws_bytes, float* rec,
+                        int32_t* skipped, void* stream);
+
+/* yv_sgd_step / yv_optim_step with the record of yv_grad_clip_record in place of grad_scale: g is scaled by rec[3]; where
+ * rec[1] is not finite the launch stores nothing (p, m, v and the mirror keep their bits; a first step's m / v stay unread).
+ * Otherwise the bits of yv_sgd_step / yv_optim_step called with grad_scale = rec[3]: one device text serves both forms. */
+int yv_sgd_step_rec(float* p, const float* g, float* m, size_t n, float lr, float momentum, float weight_decay,
+                    const float* rec, int first, void* bf16_mirror, void* stream);
+int yv_optim_step_rec(int kind, float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2,
+                      float eps, float weight_decay, const float* rec, int step, void* bf16_mirror, void* stream);
+
 /* dst = a*dst + b*src (gradient accumulation over `accumulate` batches: a = b = 1). */
 int yv_axpby(float* dst, const float* src, size_t n, float a, float b, void* stream);
 

@@ -10,6 +10,7 @@ and after.  The pickled `/app/utils/weight/best.pt` cannot be read with a safe l
 seeded random initialisation.  Parity unpinned: every piece lives in `ultralytics`, absent from the reference tree.
 """
 import json
+import math
 import os
 import random
 
@@ -50,7 +51,7 @@ def train(epochs, batch, data, weights=None, scale="n", size=640, save=None, dev
           optimizer="auto", lr0=1e-4, lrf=1e-4, momentum=0.937, weight_decay=5e-4, warmup_epochs=3.0, augment=True,
           close_mosaic=10, hsv_h=0.015, hsv_s=0.7, hsv_v=0.4, degrees=0.0, translate=0.1, aug_scale=0.5, shear=0.0,
           perspective=0.0, flipud=0.0, fliplr=0.5, mosaic=1.0, mixup=0.0, copy_paste=0.0, narrow_wgrad=None,
-          fused_bn_stats=None, phase_dgrad=None, gather_wgrad=None, fused_bn_bwd=None):
+          fused_bn_stats=None, phase_dgrad=None, gather_wgrad=None, fused_bn_bwd=None, clip_grad=None):
     """utils/trainYolo.py:6-35: `model.train(epochs=, batch=, data=, lr0=1e-4, lrf=1e-4)` with the ultralytics defaults
     around it: optimizer 'auto' (see _auto_optimizer), linear lr0 -> lr0*lrf schedule, warm-up over
     max(3 epochs, 100 iterations) (lr from 0 - biases from 0.1, 0.0 under AdamW - and momentum from 0.8), gradient
@@ -64,12 +65,18 @@ def train(epochs, batch, data, weights=None, scale="n", size=640, save=None, dev
     `narrow_wgrad` is YoloTrainer's opt-in of the same name (None: the YV_YOLO_NARROW_WGRAD environment variable).
     `fused_bn_stats` likewise (None: YV_YOLO_FUSED_BN_STATS), `phase_dgrad` (None: YV_YOLO_PHASE_DGRAD) and
     `gather_wgrad` (None: YV_YOLO_GATHER_WGRAD) and `fused_bn_bwd` (None: YV_YOLO_FUSED_BN_BWD).
+    `clip_grad` is YoloTrainer's opt-in of the same name (None: YV_YOLO_CLIP_GRAD; 0: off): the max_norm to which the global L2
+    norm of the gradients is clipped ahead of every update, on the device; an update whose norm is not finite is skipped.  The
+    published trainer clips to 10.0; off is the default here.  With it on, every epoch row also carries `grad_norm` (the mean
+    norm over the epoch's optimiser steps, the skipped ones left out), `clipped` (the steps whose coefficient was below 1) and
+    `skipped`; the result carries `clip_grad` (None: off).
     Returns {"epochs": [...per-epoch mean (total, box, cls, dfl)...], "weights": path or None, "not_built": [...]}."""
     import numpy as np
     from yvhip.yolo_data import list_samples, load_batch, max_boxes_per_image, read_data_yaml
     from yvhip.yolo_val import validate
     from yvhip.yolo_augment import DetAugment, augment_batch
-    from yvhip.yolo_training import YoloTrainer, init_yolo_train_state
+    from yvhip.yolo_training import YoloTrainer, clip_grad_value, init_yolo_train_state
+    clip_grad = clip_grad_value(clip_grad)                     # a negative or NaN max_norm fails here, before any device is asked for
     if copy_paste != 0:
         raise yvhip.YvError("trainYolo.train: copy_paste is not built: it pastes instance masks, and the dataset format "
                             "(generate_annotation XML, YOLO txt boxes) carries none")
@@ -102,7 +109,8 @@ def train(epochs, batch, data, weights=None, scale="n", size=640, save=None, dev
     wd = weight_decay * B * accumulate / NBS
     tr = YoloTrainer(state, scale=scale, nc=nc, size=size, batch=B, lr=lr0, momentum=momentum, weight_decay=wd, device=device,
                      optimizer=opt, ema=True, narrow_wgrad=narrow_wgrad, fused_bn_stats=fused_bn_stats,
-                     phase_dgrad=phase_dgrad, gather_wgrad=gather_wgrad, fused_bn_bwd=fused_bn_bwd)
+                     phase_dgrad=phase_dgrad, gather_wgrad=gather_wgrad, fused_bn_bwd=fused_bn_bwd,
+                     clip_grad=0.0 if clip_grad is None else clip_grad)
     G = max_boxes_per_image(samples)
     nb = max(len(samples) // B, 1)                             # batches per epoch (last short batch dropped)
     nw = max(round(warmup_epochs * nb), 100) if warmup_epochs > 0 else -1
@@ -115,6 +123,7 @@ def train(epochs, batch, data, weights=None, scale="n", size=640, save=None, dev
     for ep in range(int(epochs)):
         lr = lr0 * lf(ep)
         acc, steps = torch.zeros(4), 0
+        norm_sum, opt_steps, clipped, skipped = 0.0, 0, 0, 0   # clip_grad: over the epoch's optimiser steps
         order = list(samples)
         order_rng.shuffle(order)                               # the trainer's loader shuffles every epoch
         if ep == int(epochs) - int(close_mosaic):              # the trainer closes the mosaic for the last epochs
@@ -133,10 +142,20 @@ def train(epochs, batch, data, weights=None, scale="n", size=640, save=None, dev
             loss = tr.step(img.to(device), gtb.to(device), gtl.to(device), gtn.to(device), lr, accumulate=acc_now, lrs=lrs,
                            momentum=mom)
             acc += loss.cpu()
+            if clip_grad is not None and tr.accumulated == 0:  # this call ended in an optimiser step: its record, read once
+                rec = tr.grad_norm_record.cpu().tolist()
+                opt_steps += 1
+                if math.isfinite(rec[1]):
+                    norm_sum += rec[1]
+                    clipped += rec[2] < 1.0
+                else:
+                    skipped += 1
             steps += 1
             ni += 1
         mean = (acc / max(steps, 1)).tolist()
         row = {"epoch": ep, "lr": lr, "loss": mean[0], "box": mean[1], "cls": mean[2], "dfl": mean[3], "steps": steps}
+        if clip_grad is not None:
+            row.update(grad_norm=norm_sum / max(opt_steps - skipped, 1), clipped=int(clipped), skipped=skipped)
         ema_state = tr.state_dict(ema=True)
         if val_samples:
             # the trainer validates the EMA weights after every epoch (conf 0.001, NMS IoU 0.7) and keeps the checkpoint
@@ -166,7 +185,8 @@ def train(epochs, batch, data, weights=None, scale="n", size=640, save=None, dev
     final = val(best_state, data, scale, size, 16, 0.25, 0.6, device)
     log(f"Validation results after training: {final}")
     return {"epochs": hist, "weights": out, "not_built": NOT_BUILT, "optimizer": opt, "lr0": lr0, "accumulate": accumulate,
-            "val_before": validation_results, "val_after": final, "best_epoch": best_epoch, "best_fitness": best_fit}
+            "val_before": validation_results, "val_after": final, "best_epoch": best_epoch, "best_fitness": best_fit,
+            "clip_grad": clip_grad}
 
 
 def yolo2dict(path_to_xml_dir):

@@ -100,6 +100,9 @@ _SIGS = {
     "yv_crop_debug": (_i, [_i]),
     "yv_c2f_fused": (_i, [_vp, C.c_longlong, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_longlong, _vp]),
     "yv_optim_step": (_i, [_i, _vp, _vp, _vp, _vp, _sz, _f, _f, _f, _f, _f, _f, _i, _vp, _vp]),
+    "yv_optim_step_rec": (_i, [_i, _vp, _vp, _vp, _vp, _sz, _f, _f, _f, _f, _f, _vp, _i, _vp, _vp]),
+    "yv_grad_clip_ws_bytes": (_sz, [_sz]),
+    "yv_grad_clip_record": (_i, [_vp, _sz, _f, _f, _vp, _sz, _vp, _vp, _vp]),
     "yv_ema_update": (_i, [_vp, _vp, _sz, _f, _vp]),
     "yv_axpby": (_i, [_vp, _vp, _sz, _f, _f, _vp]),
     "yv_detect_loss_ws_bytes": (_sz, [_i, _i, _i]),
@@ -171,6 +174,7 @@ _SIGS = {
     "yv_head_bwd": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
     "yv_loss_fwd_bwd": (_i, [_vp, _vp, _i, _i, _f, _f, _vp, _vp, _vp]),
     "yv_sgd_step": (_i, [_vp, _vp, _vp, _sz, _f, _f, _f, _f, _i, _vp, _vp]),
+    "yv_sgd_step_rec": (_i, [_vp, _vp, _vp, _sz, _f, _f, _f, _vp, _i, _vp, _vp]),
     "yv_transpose_bf16_batched": (_i, [_vp, _vp, _i, _i, _i, C.c_longlong, C.c_longlong, _vp]),
 }
 
@@ -547,8 +551,14 @@ def loss_fwd_bwd(logits: torch.Tensor, labels: torch.Tensor, w_lsce: float = 1.0
 
 def sgd_step(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, lr: float, momentum: float = 0.9,
              weight_decay: float = 1e-3, first: bool = False, grad_scale: float = 1.0,
-             mirror: Optional[torch.Tensor] = None):
+             mirror: Optional[torch.Tensor] = None, scale_rec: Optional[torch.Tensor] = None):
+    """scale_rec: the record of grad_clip_record in place of grad_scale (yv_sgd_step_rec); None: yv_sgd_step."""
     _chk_dev(p, g, m, mirror)
+    if scale_rec is not None:
+        _chk_rec(scale_rec, grad_scale)
+        check(lib.yv_sgd_step_rec(_p(p), _p(g), _p(m), p.numel(), float(lr), float(momentum), float(weight_decay), _p(scale_rec),
+                                  1 if first else 0, _p(mirror), _st()), "yv_sgd_step_rec")
+        return
     check(lib.yv_sgd_step(_p(p), _p(g), _p(m), p.numel(), float(lr), float(momentum), float(weight_decay),
                           float(grad_scale), 1 if first else 0, _p(mirror), _st()), "yv_sgd_step")
 
@@ -1179,11 +1189,43 @@ OPT_SGD_NESTEROV, OPT_ADAMW = 1, 2
 
 def optim_step(kind: int, p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: Optional[torch.Tensor], lr: float, step: int,
                beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8, weight_decay: float = 0.0, grad_scale: float = 1.0,
-               mirror: Optional[torch.Tensor] = None):
-    """torch.optim.SGD(nesterov=True) (kind 1) / torch.optim.AdamW (kind 2) on flat fp32 buffers; step counts from 1."""
+               mirror: Optional[torch.Tensor] = None, scale_rec: Optional[torch.Tensor] = None):
+    """torch.optim.SGD(nesterov=True) (kind 1) / torch.optim.AdamW (kind 2) on flat fp32 buffers; step counts from 1.
+    scale_rec: the record of grad_clip_record in place of grad_scale (yv_optim_step_rec); None: yv_optim_step."""
     _chk_dev(p, g, m, v, mirror)
+    if scale_rec is not None:
+        _chk_rec(scale_rec, grad_scale)
+        check(lib.yv_optim_step_rec(kind, _p(p), _p(g), _p(m), _p(v), p.numel(), float(lr), float(beta1), float(beta2), float(eps),
+                                    float(weight_decay), _p(scale_rec), int(step), _p(mirror), _st()), "yv_optim_step_rec")
+        return
     check(lib.yv_optim_step(kind, _p(p), _p(g), _p(m), _p(v), p.numel(), float(lr), float(beta1), float(beta2), float(eps),
                             float(weight_decay), float(grad_scale), int(step), _p(mirror), _st()), "yv_optim_step")
+
+
+def _chk_rec(rec: torch.Tensor, grad_scale: float = 1.0):
+    """A clip record: four f32 on the device; it carries the gradient scale, so a grad_scale next to it is a mistake."""
+    _chk_dev(rec)
+    if rec.dtype != torch.float32 or rec.numel() != 4:
+        raise YvError("a clip record is four float32 values")
+    if float(grad_scale) != 1.0:
+        raise YvError("scale_rec already holds grad_scale (grad_clip_record): pass one of the two")
+
+
+def grad_clip_ws_bytes(n: int) -> int:
+    return int(lib.yv_grad_clip_ws_bytes(int(n)))
+
+
+def grad_clip_record(g: torch.Tensor, grad_scale: float, max_norm: float, ws: torch.Tensor, rec: torch.Tensor,
+                     skipped: Optional[torch.Tensor] = None):
+    """torch.nn.utils.clip_grad_norm_(max_norm) over the flat f32 gradient g, on the device: rec (4 f32) = sum of squares, norm of
+    g * grad_scale, clip coefficient, grad_scale * coefficient; skipped (1 i32) counts the records whose norm is not finite.
+    ws: grad_clip_ws_bytes(g.numel()) bytes.  The record goes to sgd_step / optim_step as scale_rec."""
+    _chk_dev(g, ws, skipped)
+    _chk_rec(rec)
+    if g.dtype != torch.float32 or (skipped is not None and (skipped.dtype != torch.int32 or skipped.numel() != 1)):
+        raise YvError("grad_clip_record: g is float32, skipped one int32")
+    check(lib.yv_grad_clip_record(_p(g), g.numel(), float(grad_scale), float(max_norm), _p(ws), ws.numel() * ws.element_size(),
+                                  _p(rec), _p(skipped), _st()), "yv_grad_clip_record")
 
 
 def ema_update(ema: torch.Tensor, src: torch.Tensor, decay: float):

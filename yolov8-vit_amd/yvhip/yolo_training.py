@@ -32,7 +32,7 @@ from . import (OPT_ADAMW, OPT_SGD_NESTEROV, VIEW_ADD, VIEW_COPY, VIEW_PAD, VIEW_
                bn_stats, bn_stats_finish, bn_ws_floats, cast_colsum, colsum_ws_floats, conv_stats_ws_floats, conv_view,
                conv_dgrad_s2, conv_dgrad_s2_route, conv_view_stats, conv_weight_dgrad, detect_loss,
                detect_loss_ws_bytes, im2col3, maxpool5_bwd, mview, require_gpu, sgd_step, sppf_pool, view_op, wgrad, wgrad_conv3,
-               wgrad_conv3_gather)
+               wgrad_conv3_gather, grad_clip_record)
 from .engines import LAYER_STRIDE, REG_MAX, _env_flag, detect_widths, yolo_conv_keys, yolo_layers
 
 BN_EPS, BN_MOMENTUM = 1e-3, 0.03
@@ -40,6 +40,26 @@ BN_EPS, BN_MOMENTUM = 1e-3, 0.03
 
 def _r64(n: int) -> int:
     return (n + 63) // 64 * 64
+
+
+CLIP_GRAD_ENV = "YV_YOLO_CLIP_GRAD"
+
+
+def clip_grad_value(value, env: str = CLIP_GRAD_ENV) -> Optional[float]:
+    """The max_norm of global-norm gradient clipping, or None for off.  `value` None: the environment variable `env` (unset, empty
+    or 0: off).  A positive number (inf included) is max_norm, 0 is off; anything else - negative, NaN, no number - is an error."""
+    if value is None:
+        import os
+        value = os.environ.get(env, "").strip() or 0.0
+    try:
+        if isinstance(value, bool):
+            raise ValueError
+        v = float(value)
+    except (TypeError, ValueError):
+        raise YvError(f"clip_grad / {env}: {value!r} is no number") from None
+    if not v >= 0.0:
+        raise YvError(f"clip_grad / {env}: max_norm must be positive (0: off), got {value!r}")
+    return v if v > 0.0 else None
 
 
 # ---- the training network's launch list: entries of three kinds.  Buffers go by name: x0 (the image, 8 channels), out{idx} (a layer's
@@ -321,10 +341,13 @@ class YoloTrainer:
                  optimizer: str = "sgd", ema: bool = False, ema_decay: float = 0.9999, ema_tau: float = 2000.0,
                  overlap_wgrad: bool = True, implicit_wgrad: bool = True, narrow_wgrad: Optional[bool] = None,
                  fused_bn_stats: Optional[bool] = None, phase_dgrad: Optional[bool] = None, gather_wgrad: Optional[bool] = None,
-                 fused_bn_bwd: Optional[bool] = None):
+                 fused_bn_bwd: Optional[bool] = None, clip_grad: Optional[float] = None):
         require_gpu()
         if size % 32:
             raise YvError("input size must be a multiple of 32")
+        # opt-in: clip the global L2 norm of the gradients to this max_norm ahead of every update (torch's clip_grad_norm_; the
+        # published trainer: 10.0) and skip an update whose norm is not finite, all on the device; DESIGN.md section 28
+        self.clip_grad = clip_grad_value(clip_grad)
         self.scale, self.nc, self.size, self.B, self.dev = scale, nc, size, batch, torch.device(device)
         self.lr, self.momentum, self.weight_decay = lr, momentum, weight_decay
         self.overlap_wgrad, self.s_w, self._pending = overlap_wgrad, None, []
@@ -367,6 +390,25 @@ class YoloTrainer:
         self._loss_ws: Dict[int, torch.Tensor] = {}
         from .dist import BucketReducer
         self.reducer = BucketReducer(self.G, 1 << 62)            # 12-45 MB of gradients: one all-reduce after backward
+        self.clip_ws = self.clip_rec = self.clip_skipped = None
+        if self.clip_grad is not None:
+            self.clip_ws = torch.zeros(max(_yv.grad_clip_ws_bytes(self.n_param), 16), dtype=torch.uint8, device=self.dev)
+            self.clip_rec = torch.zeros(4, device=self.dev)       # sum of squares, norm, coefficient, grad_scale * coefficient
+            self.clip_skipped = torch.zeros(1, dtype=torch.int32, device=self.dev)
+
+    @property
+    def grad_norm_record(self) -> torch.Tensor:
+        """The device record of the last optimizer_step (yv_grad_clip_record's four floats; no copy)."""
+        if self.clip_rec is None:
+            raise YvError("trainer was built without clip_grad")
+        return self.clip_rec
+
+    @property
+    def skipped_steps(self) -> torch.Tensor:
+        """The device counter (1 i32) of the updates skipped for a gradient norm that was not finite."""
+        if self.clip_skipped is None:
+            raise YvError("trainer was built without clip_grad")
+        return self.clip_skipped
 
     # ------------------------------------------------------------------ parameters
     def _param(self, name: str, n: int, group: str) -> int:
@@ -740,11 +782,20 @@ class YoloTrainer:
     def optimizer_step(self, lr: Optional[float] = None, grad_scale: float = 1.0, lrs: Optional[Dict[str, float]] = None,
                        momentum: Optional[float] = None):
         """One update of every parameter group (ultralytics: weight decay on conv weights only; BatchNorm weights and
-        all biases undecayed) with torch.optim.SGD / SGD(nesterov) / AdamW semantics, then the ModelEMA update."""
+        all biases undecayed) with torch.optim.SGD / SGD(nesterov) / AdamW semantics, then the ModelEMA update.
+        With clip_grad: one grad_clip_record over all of G first (its padded positions are zero), and every group takes its
+        gradient scale from that record on the device - no host synchronisation.  A record whose norm is not finite makes the
+        three updates no-ops; step_count and the EMA still advance (unlike an update a loss scaler skips, which the published
+        trainer does not count: here the host never learns of the skip, and the EMA of unchanged weights moves towards them)."""
         lr = self.lr if lr is None else lr
         mom = self.momentum if momentum is None else momentum
         self.step_count += 1
         t = self.step_count
+        if self.clip_grad is not None:
+            grad_clip_record(self.G, grad_scale, self.clip_grad, self.clip_ws, self.clip_rec, self.clip_skipped)
+            clip = dict(scale_rec=self.clip_rec)                 # the record carries grad_scale
+        else:
+            clip = dict(grad_scale=grad_scale)
         for g, wd in (("w", self.weight_decay), ("bnw", 0.0), ("bias", 0.0)):
             lo, hi = self.group[g]
             if hi <= lo:
@@ -752,13 +803,13 @@ class YoloTrainer:
             glr = lrs[g] if lrs is not None and g in lrs else lr
             mirror = self.P16 if g == "w" else None
             if self.optimizer == "sgd":
-                sgd_step(self.P[lo:hi], self.G[lo:hi], self.Mo[lo:hi], glr, mom, wd, t == 1, grad_scale, mirror=mirror)
+                sgd_step(self.P[lo:hi], self.G[lo:hi], self.Mo[lo:hi], glr, mom, wd, t == 1, mirror=mirror, **clip)
             else:
                 if self.optimizer == "adamw" and self.V is None:
                     self.V = torch.zeros_like(self.P)
                 optim_step(OPT_ADAMW if self.optimizer == "adamw" else OPT_SGD_NESTEROV, self.P[lo:hi], self.G[lo:hi],
                            self.Mo[lo:hi], self.V[lo:hi] if self.V is not None else None, glr, t, beta1=mom, weight_decay=wd,
-                           grad_scale=grad_scale, mirror=mirror)
+                           mirror=mirror, **clip)
         if self.use_ema:
             self.ema_updates += 1
             d = self.ema_decay * (1.0 - math.exp(-self.ema_updates / self.ema_tau))
