@@ -229,6 +229,10 @@ int yv_crop_debug(int groups_per_block);
  * w x h corner; geom (B,6) i32 rows {w, h, nw, nh, left, top} (host-computed);
  * out (B,S,S,3) u8: bilinear resample into the window, 114 elsewhere. */
 int yv_letterbox(const uint8_t* src, int B, int Hc, int Wc, const int32_t* geom, int S, uint8_t* out, void* stream);
+/* The same kernel with a rectangular output (B,H,W,3): the stride-32 rectangles of the detector (YoloEngine(size=(H, W))).
+ * H, W <= 0 or not multiples of 32: YV_ERR_ARG. */
+int yv_letterbox_hw(const uint8_t* src, int B, int Hc, int Wc, const int32_t* geom, int H, int W, uint8_t* out,
+                    void* stream);
 
 /* Training augmentation of classifier crops fused with the patch-embed operand builder: replaces the stochastic part
  * of data_transforms['train'] (utils/trainClass.py:199-216: HorizontalFlip, RandomCrop+PadIfNeeded, ShiftScaleRotate,
@@ -290,6 +294,11 @@ int yv_mosaic_augment_ex(const uint8_t* tiles, int n_tiles, int B, int S, int la
 int yv_detect_decode(const float* box0, const float* box1, const float* box2, const float* cls0, const float* cls1,
                      const float* cls2, int cls_ld, int B, int size, int nc, float* boxes, float* scores,
                      void* stream);
+/* The same for an H x W network input (both multiples of 32, else YV_ERR_ARG): Hs = H / stride, Ws = W / stride, anchor order
+ * = scale, then y*Ws+x, A = sum Hs*Ws.  yv_detect_decode is this with H = W = size. */
+int yv_detect_decode_hw(const float* box0, const float* box1, const float* box2, const float* cls0, const float* cls1,
+                        const float* cls2, int cls_ld, int B, int H, int W, int nc, float* boxes, float* scores,
+                        void* stream);
 
 /* Fused Detect tail: the last 1 x 1 convolutions of both branches (ultralytics Detect cv2.i.2: 64 -> 4 x reg_max box logits,
  * cv3.i.2: c3 -> nc class logits; TensorRT builder docs/YOLO_TensorRT_Technical.md:160-212) + yv_detect_decode, three scales in
@@ -299,6 +308,10 @@ int yv_detect_decode(const float* box0, const float* box1, const float* box2, co
 int yv_detect_tail(const void* feat0, const void* feat1, const void* feat2, int ld, int c3, const void* const* w2,
                    const float* const* b2, const void* const* w3, const float* const* b3, int B, int size, int nc,
                    float* boxes, float* scores, void* stream);
+/* The same for an H x W network input (both multiples of 32, else YV_ERR_ARG); yv_detect_tail is this with H = W = size. */
+int yv_detect_tail_hw(const void* feat0, const void* feat1, const void* feat2, int ld, int c3, const void* const* w2,
+                      const float* const* b2, const void* const* w3, const float* const* b3, int B, int H, int W, int nc,
+                      float* boxes, float* scores, void* stream);
 
 /* ------------------------------------------------------------ dense math */
 

@@ -14,7 +14,7 @@ import yvhip
 from yvhip.pipeline import DetectClassifyPipeline
 
 from .config import CLASSES, COLORS
-from .models.utils import letterbox_geometry, path_to_list
+from .models.utils import letterbox_geometry, path_to_list, rect_net_shape
 
 BATCH = 32
 
@@ -42,19 +42,33 @@ def _pipeline(Engine, model_list) -> DetectClassifyPipeline:
     return DetectClassifyPipeline(Engine.engine, vits, Engine.score_threshold, Engine.iou_threshold, Engine.topk)
 
 
+def _rect_pipeline(Engine, pipe: DetectClassifyPipeline, cache: dict, hw) -> DetectClassifyPipeline:
+    """`pipe` with the detector resized to `hw` (shared weights, own buffers); one per shape."""
+    if hw not in cache:
+        cache[hw] = DetectClassifyPipeline(Engine.engine.resized(hw), pipe.vits, Engine.score_threshold, Engine.iou_threshold,
+                                           Engine.topk)
+    return cache[hw]
+
+
 def main(Engine, imgs, device=None, model_list: Optional[list] = None, transform=None, aliyunoss=None,
-         func: Optional[Callable] = None):
+         func: Optional[Callable] = None, rect: bool = False):
     """Detect + classify every image under `imgs` (directory, file or list).  Returns a JSON-serialisable dict
     {"output": [{"image": name, "objects": [{"sort", "det_sort", "confidence", "xmin", "ymin", "xmax", "ymax"}]}]}.
     `transform` is accepted for signature compatibility: its valid_test branch (nearest resize to 224 +
     Normalize(.5,.5)) is what the fused crop kernel implements.  `func(folder, filename, path, objects)` is
-    called per image like test.py:28 does with generate_annotation."""
+    called per image like test.py:28 does with generate_annotation.
+    rect=True: each chunk of images is letterboxed into the smallest stride-32 rectangle that holds it at the engine's size
+    (models.utils.rect_net_shape; the engine must be square) instead of the S x S square, and the detector runs at that
+    extent (YoloEngine.resized, one engine per shape).  Restored coordinates, crops and the result layout are the same."""
     yvhip.require_gpu()
     if not model_list:
         raise yvhip.YvError("model_list is empty")
     dev = torch.device(device) if device is not None else Engine.device
     S = Engine.size
     pipe = _pipeline(Engine, model_list)
+    if rect and not isinstance(S, int):
+        raise yvhip.YvError("rect=True takes a square engine: its size is the long side of every rectangle")
+    rect_pipes: dict = {}
     paths = path_to_list(imgs)
     results = []
     for s in range(0, len(paths), BATCH):
@@ -64,14 +78,19 @@ def main(Engine, imgs, device=None, model_list: Optional[list] = None, transform
         Hc, Wc = max(a.shape[0] for a in arrs), max(a.shape[1] for a in arrs)
         canvas = np.zeros((B, Hc, Wc, 3), dtype=np.uint8)
         geom, ratio, dwdh, wh = [], [], [], []
+        if rect:
+            Hn, Wn = rect_net_shape([a.shape[:2] for a in arrs], S)
+            new_shape, net, run = (Wn, Hn), (Hn, Wn), _rect_pipeline(Engine, pipe, rect_pipes, (Hn, Wn))
+        else:
+            new_shape, net, run = (S, S), S, pipe
         for i, a in enumerate(arrs):
             h, w = a.shape[:2]
             canvas[i, :h, :w] = a
-            r, (dw, dh), (nw, nh), (left, top) = letterbox_geometry(h, w, (S, S))
+            r, (dw, dh), (nw, nh), (left, top) = letterbox_geometry(h, w, new_shape)
             geom.append([w, h, nw, nh, left, top]); ratio.append(r); dwdh += [dw, dh]; wh += [w, h]
         src = torch.from_numpy(canvas).to(dev)
-        net_in = yvhip.letterbox(src, torch.tensor(geom, dtype=torch.int32, device=dev), S)
-        out = pipe(net_in, torch.tensor(ratio, dtype=torch.float32, device=dev),
+        net_in = yvhip.letterbox(src, torch.tensor(geom, dtype=torch.int32, device=dev), net)
+        out = run(net_in, torch.tensor(ratio, dtype=torch.float32, device=dev),
                    torch.tensor(dwdh, dtype=torch.float32, device=dev), torch.tensor(wh, dtype=torch.int32, device=dev),
                    src_images=src)
         cnt = out["det_count"].cpu().tolist()

@@ -42,9 +42,10 @@ def _guess_scale_nc(sd):
 
 
 class TRTModule(torch.nn.Module):
-    def __init__(self, weight: Union[str, dict], device: Optional[torch.device] = None, size: int = 640,
+    def __init__(self, weight: Union[str, dict], device: Optional[torch.device] = None, size=640,
                  dtype: str = "bf16") -> None:
-        """dtype: "bf16" (default) or "mxfp8" (the detector's eligible convolutions on MXFP8 operands, engines.mx_conv_plan)."""
+        """size: the network input's side, or its (H, W) (multiples of 32); `inp_info` gives (1, 3, H, W).
+        dtype: "bf16" (default) or "mxfp8" (the detector's eligible convolutions on MXFP8 operands, engines.mx_conv_plan)."""
         super().__init__()
         self.device = torch.device(device) if device is not None else torch.device('cuda:0')
         if isinstance(weight, dict):
@@ -62,8 +63,8 @@ class TRTModule(torch.nn.Module):
         sd = fold_batchnorm(sd)
         self.scale, self.nc = _guess_scale_nc(sd)
         self.engine = engines.YoloEngine(sd, self.scale, self.nc, size, device=str(self.device), dtype=dtype)
-        self.size = size
-        self.inp_info = [Tensor('images', torch.float32, (1, 3, size, size))]
+        self.size = self.engine.size
+        self.inp_info = [Tensor('images', torch.float32, (1, 3, *self.engine.hw))]
         self.out_info = [Tensor('num_dets', torch.int32, (1, 1)), Tensor('bboxes', torch.float32, (1, 100, 4)),
                          Tensor('scores', torch.float32, (1, 100)), Tensor('labels', torch.int32, (1, 100))]
         self.idx = list(range(4))
@@ -74,7 +75,7 @@ class TRTModule(torch.nn.Module):
             self.idx = [_OUTPUTS.index(n) for n in desired]
 
     def forward(self, *inputs):
-        """(B,3,S,S) float in [0,1] (the `blob`) or (B,S,S,3) uint8 -> (num_dets, bboxes, scores, labels)."""
+        """(B,3,H,W) float in [0,1] (the `blob`) or (B,H,W,3) uint8 -> (num_dets, bboxes, scores, labels)."""
         x = inputs[0]
         if x.dtype != torch.uint8:                              # blob = u8/255 exactly, so this is lossless
             x = (x.to(self.device).float() * 255.0).round().clamp(0, 255).to(torch.uint8).permute(0, 2, 3, 1)

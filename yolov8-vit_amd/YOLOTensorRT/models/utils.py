@@ -1,7 +1,8 @@
 """Host-side helpers named like the missing `YOLOTensorRT.models.utils` (解读.md:27-30)."""
+import math
 import os
 from pathlib import Path
-from typing import List, Tuple, Union
+from typing import List, Sequence, Tuple, Union
 
 import numpy as np
 
@@ -32,19 +33,29 @@ def letterbox_geometry(h: int, w: int, new_shape: Tuple[int, int] = (640, 640)):
     return r, (dw, dh), (nw, nh), (left, top)
 
 
+def rect_net_shape(hw_list: Sequence[Tuple[int, int]], S: int, stride: int = 32) -> Tuple[int, int]:
+    """The smallest stride-multiple rectangle (H, W) that holds every image of `hw_list` ((h, w) pairs) once its long side is
+    scaled to S: per image r = min(S/h, S/w), nh = round(h*r), nw = round(w*r); the result is the maxima, rounded up."""
+    nh = nw = 1
+    for h, w in hw_list:
+        r = min(S / h, S / w)
+        nh, nw = max(nh, int(round(h * r))), max(nw, int(round(w * r)))
+    return int(math.ceil(nh / stride) * stride), int(math.ceil(nw / stride) * stride)
+
+
 def letterbox(im: np.ndarray, new_shape: Tuple[int, int] = (640, 640), color=(114, 114, 114)):
     """Single-image host version returning (image, ratio, (dw, dh)) like the missing helper; runs the device
-    kernel on a batch of one (the batch path in inferdet.main calls yvhip.letterbox directly)."""
+    kernel on a batch of one (the batch path in inferdet.main calls yvhip.letterbox directly).  `new_shape` is (W, H); a
+    rectangle has both sides multiples of 32."""
     import torch
     import yvhip
     yvhip.require_gpu()
     h, w = im.shape[:2]
     r, dwdh, (nw, nh), (left, top) = letterbox_geometry(h, w, new_shape)
-    if new_shape[0] != new_shape[1]:
-        raise yvhip.YvError("square network input only")
     src = torch.from_numpy(np.ascontiguousarray(im[..., :3])).cuda()[None]
     geom = torch.tensor([[w, h, nw, nh, left, top]], dtype=torch.int32, device=src.device)
-    out = yvhip.letterbox(src.contiguous(), geom, new_shape[0])
+    W, H = new_shape
+    out = yvhip.letterbox(src.contiguous(), geom, W if W == H else (H, W))
     return out[0].cpu().numpy(), r, dwdh
 
 

@@ -174,19 +174,19 @@ __global__ __launch_bounds__(CR_THREADS) void crop_kernel(const uint8_t* __restr
 
 
 // Letterbox (YOLOTensorRT_yolodet_py_解读.md:67-69): aspect-preserving bilinear resize into the top-left
-// anchored window (left, top, nw, nh) of an S x S canvas filled with 114.  Geometry (ratio, padding) is
+// anchored window (left, top, nw, nh) of an H x W canvas filled with 114.  Geometry (ratio, padding) is
 // computed per image on the host in f64 exactly as the published upstream helper does; the kernel only
 // resamples.  Sampling rule: src = (dst + 0.5) * (src_size / dst_size) - 0.5, edge-clamped, f32 blend,
 // round half up (OpenCV's fixed-point INTER_LINEAR is not reproducible without the library: unpinned).
 __global__ __launch_bounds__(256) void letterbox_kernel(const uint8_t* __restrict__ src, int Hc, int Wc,
-                                                        const int32_t* __restrict__ geom, int S,
+                                                        const int32_t* __restrict__ geom, int H, int W,
                                                         uint8_t* __restrict__ out) {
     const int b = blockIdx.z;
     const int x = blockIdx.x * 16 + (threadIdx.x & 15), y = blockIdx.y * 16 + (threadIdx.x >> 4);
-    if (x >= S || y >= S) return;
+    if (x >= W || y >= H) return;
     const int32_t* gm = geom + b * 6;                       // w, h, nw, nh, left, top
     const int w = gm[0], h = gm[1], nw = gm[2], nh = gm[3], left = gm[4], top = gm[5];
-    uint8_t* o = out + (((size_t)b * S + y) * S + x) * 3;
+    uint8_t* o = out + (((size_t)b * H + y) * W + x) * 3;
     const int dx = x - left, dy = y - top;
     if (dx < 0 || dx >= nw || dy < 0 || dy >= nh) { o[0] = o[1] = o[2] = 114; return; }
     const uint8_t* im = src + (size_t)b * Hc * Wc * 3;
@@ -248,10 +248,19 @@ extern "C" int yv_crop_resize_norm(const uint8_t* images, int B, int H, int W, s
     return yv_launch_status();
 }
 
+extern "C" int yv_letterbox_hw(const uint8_t* src, int B, int Hc, int Wc, const int32_t* geom, int H, int W, uint8_t* out,
+                               void* stream) {
+    if (!src || !geom || !out || B <= 0 || Hc <= 0 || Wc <= 0) return YV_ERR_ARG;
+    if (H <= 0 || W <= 0 || (H % 32) || (W % 32)) return YV_ERR_ARG;
+    dim3 grid(W / 16, H / 16, B);
+    hipLaunchKernelGGL(letterbox_kernel, grid, dim3(256), 0, (hipStream_t)stream, src, Hc, Wc, geom, H, W, out);
+    return yv_launch_status();
+}
+
 extern "C" int yv_letterbox(const uint8_t* src, int B, int Hc, int Wc, const int32_t* geom, int S, uint8_t* out,
                             void* stream) {
     if (!src || !geom || !out || B <= 0 || Hc <= 0 || Wc <= 0 || S <= 0) return YV_ERR_ARG;
     dim3 grid((S + 15) / 16, (S + 15) / 16, B);
-    hipLaunchKernelGGL(letterbox_kernel, grid, dim3(256), 0, (hipStream_t)stream, src, Hc, Wc, geom, S, out);
+    hipLaunchKernelGGL(letterbox_kernel, grid, dim3(256), 0, (hipStream_t)stream, src, Hc, Wc, geom, S, S, out);
     return yv_launch_status();
 }

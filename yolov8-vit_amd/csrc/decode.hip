@@ -13,7 +13,7 @@ namespace {
 struct DecodeArgs {
     const float* box[3];
     const float* cls[3];
-    int hw[3];        // side length of each scale
+    int h[3], w[3];   // height and width of each scale's map
     int a0[3];        // first anchor index of each scale
 };
 
@@ -26,10 +26,10 @@ __global__ __launch_bounds__(256) void decode_kernel(DecodeArgs a, int cls_ld, i
     const int b = (int)(anchor_g / A);
     const int an = (int)(anchor_g - (long long)b * A);
     const int s = an >= a.a0[2] ? 2 : (an >= a.a0[1] ? 1 : 0);
-    const int w = a.hw[s];
+    const int w = a.w[s];
     const int local = an - a.a0[s];
     const int y = local / w, x = local - y * w;
-    const size_t pix = ((size_t)b * w + y) * w + x;
+    const size_t pix = ((size_t)b * a.h[s] + y) * w + x;
     const float4* p = (const float4*)(a.box[s] + pix * 64 + side * 16);
     float v[16];
 #pragma unroll
@@ -76,12 +76,12 @@ __global__ __launch_bounds__(256) void decode_kernel(DecodeArgs a, int cls_ld, i
 // c2 = 64 (YOLOv8 n / s / m), nc <= 16, c3 = 32 KC3 in {64, 128, 192}; anything else takes the unfused path.
 // ---------------------------------------------------------------------------------------------
 struct TailArgs {
-    const uint16_t* feat[3];       // (B * hw * hw, ld) bf16
+    const uint16_t* feat[3];       // (B * h * w, ld) bf16
     const uint16_t* w2[3];         // (64, 64) bf16 row-major (out channel, in channel)
     const float* b2[3];            // (64)
     const uint16_t* w3[3];         // (16, c3) bf16, rows >= nc zero
     const float* b3[3];            // (16)
-    int hw[3], a0[3], blk0[3];     // side length, first anchor, first workgroup of each scale
+    int h[3], w[3], a0[3], blk0[3];   // map height and width, first anchor, first workgroup of each scale
 };
 
 template <int KC3>
@@ -91,8 +91,9 @@ __global__ __launch_bounds__(256) void detect_tail_kernel(TailArgs a, int ld, in
     __shared__ __attribute__((aligned(16))) float ctile[4][16][16 + 1];           // per wave: 16 pixels x 16 class logits
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int s = (int)blockIdx.x >= a.blk0[2] ? 2 : ((int)blockIdx.x >= a.blk0[1] ? 1 : 0);
-    const int w = a.hw[s];
-    const long long npx = (long long)B * w * w;
+    const int w = a.w[s];
+    const long long hw2 = (long long)a.h[s] * w;
+    const long long npx = (long long)B * hw2;
     const long long p0 = (long long)((int)blockIdx.x - a.blk0[s]) * px_per_wg;
     const int fr = lane & 15, fq = lane >> 4;
     // weight fragments (A operand): lane (row fr, k group fq) holds W[i * 16 + fr][ks * 32 + fq * 8 .. + 7]
@@ -169,7 +170,6 @@ __global__ __launch_bounds__(256) void detect_tail_kernel(TailArgs a, int ld, in
             num += e * (float)q;
         }
         const float dist = num / den;
-        const long long hw2 = (long long)w * w;
         const int b = (int)((pg < npx ? pg : npx - 1) / hw2);
         const int local = (int)((pg < npx ? pg : npx - 1) - (long long)b * hw2);
         const int y = local / w, x = local - y * w;
@@ -190,51 +190,69 @@ __global__ __launch_bounds__(256) void detect_tail_kernel(TailArgs a, int ld, in
 
 }  // namespace
 
-extern "C" int yv_detect_decode(const float* box0, const float* box1, const float* box2, const float* cls0,
-                                const float* cls1, const float* cls2, int cls_ld, int B, int size, int nc,
-                                float* boxes, float* scores, void* stream) {
+extern "C" int yv_detect_decode_hw(const float* box0, const float* box1, const float* box2, const float* cls0,
+                                   const float* cls1, const float* cls2, int cls_ld, int B, int H, int W, int nc,
+                                   float* boxes, float* scores, void* stream) {
     if (!box0 || !box1 || !box2 || !cls0 || !cls1 || !cls2 || !boxes || !scores) return YV_ERR_ARG;
-    if (B <= 0 || size <= 0 || (size % 32) || nc <= 0 || cls_ld < nc) return YV_ERR_ARG;
+    if (B <= 0 || H <= 0 || W <= 0 || (H % 32) || (W % 32) || nc <= 0 || cls_ld < nc) return YV_ERR_ARG;
     DecodeArgs a;
     a.box[0] = box0; a.box[1] = box1; a.box[2] = box2;
     a.cls[0] = cls0; a.cls[1] = cls1; a.cls[2] = cls2;
-    int A = 0;
+    long long A = 0;
     for (int s = 0; s < 3; ++s) {
-        a.hw[s] = size / (8 << s);
-        a.a0[s] = A;
-        A += a.hw[s] * a.hw[s];
+        a.h[s] = H / (8 << s);
+        a.w[s] = W / (8 << s);
+        a.a0[s] = (int)A;
+        A += (long long)a.h[s] * a.w[s];
     }
+    if (A > 0x7fffffffLL) return YV_ERR_LIMIT;
     long long threads = (long long)B * A * 4;
+    if ((threads + 255) / 256 > 0x7fffffffLL) return YV_ERR_LIMIT;
     int blocks = (int)((threads + 255) / 256);
-    hipLaunchKernelGGL(decode_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a, cls_ld, B, A, nc, boxes,
+    hipLaunchKernelGGL(decode_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a, cls_ld, B, (int)A, nc, boxes,
                        scores);
+    return yv_launch_status();
+}
+
+extern "C" int yv_detect_decode(const float* box0, const float* box1, const float* box2, const float* cls0,
+                                const float* cls1, const float* cls2, int cls_ld, int B, int size, int nc,
+                                float* boxes, float* scores, void* stream) {
+    return yv_detect_decode_hw(box0, box1, box2, cls0, cls1, cls2, cls_ld, B, size, size, nc, boxes, scores, stream);
+}
+
+extern "C" int yv_detect_tail_hw(const void* feat0, const void* feat1, const void* feat2, int ld, int c3,
+                                 const void* const* w2, const float* const* b2, const void* const* w3, const float* const* b3,
+                                 int B, int H, int W, int nc, float* boxes, float* scores, void* stream) {
+    if (!feat0 || !feat1 || !feat2 || !w2 || !b2 || !w3 || !b3 || !boxes || !scores) return YV_ERR_ARG;
+    if (B <= 0 || H <= 0 || W <= 0 || (H % 32) || (W % 32) || nc <= 0 || nc > 16 || ld < 64 + c3 || (ld & 7)) return YV_ERR_ARG;
+    if (c3 != 64 && c3 != 128 && c3 != 192) return YV_ERR_LIMIT;
+    TailArgs a;
+    a.feat[0] = (const uint16_t*)feat0; a.feat[1] = (const uint16_t*)feat1; a.feat[2] = (const uint16_t*)feat2;
+    const int px_per_wg = 256;                                    // four 16-pixel groups per wave: ~1,050 workgroups at batch 32
+    long long A = 0, blk = 0;
+    for (int s = 0; s < 3; ++s) {
+        if (!w2[s] || !b2[s] || !w3[s] || !b3[s]) return YV_ERR_ARG;
+        a.w2[s] = (const uint16_t*)w2[s]; a.b2[s] = b2[s]; a.w3[s] = (const uint16_t*)w3[s]; a.b3[s] = b3[s];
+        a.h[s] = H / (8 << s);
+        a.w[s] = W / (8 << s);
+        a.a0[s] = (int)A;
+        A += (long long)a.h[s] * a.w[s];
+        a.blk0[s] = (int)blk;
+        const long long px = (long long)B * a.h[s] * a.w[s];
+        if (px > 0x7fffffffLL || A > 0x7fffffffLL) return YV_ERR_LIMIT;
+        blk += (px + px_per_wg - 1) / px_per_wg;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)blk);
+    const int An = (int)A;
+    if (c3 == 64) hipLaunchKernelGGL(detect_tail_kernel<2>, grid, dim3(256), 0, st, a, ld, B, An, nc, px_per_wg, boxes, scores);
+    else if (c3 == 128) hipLaunchKernelGGL(detect_tail_kernel<4>, grid, dim3(256), 0, st, a, ld, B, An, nc, px_per_wg, boxes, scores);
+    else hipLaunchKernelGGL(detect_tail_kernel<6>, grid, dim3(256), 0, st, a, ld, B, An, nc, px_per_wg, boxes, scores);
     return yv_launch_status();
 }
 
 extern "C" int yv_detect_tail(const void* feat0, const void* feat1, const void* feat2, int ld, int c3,
                               const void* const* w2, const float* const* b2, const void* const* w3, const float* const* b3,
                               int B, int size, int nc, float* boxes, float* scores, void* stream) {
-    if (!feat0 || !feat1 || !feat2 || !w2 || !b2 || !w3 || !b3 || !boxes || !scores) return YV_ERR_ARG;
-    if (B <= 0 || size <= 0 || (size % 32) || nc <= 0 || nc > 16 || ld < 64 + c3 || (ld & 7)) return YV_ERR_ARG;
-    if (c3 != 64 && c3 != 128 && c3 != 192) return YV_ERR_LIMIT;
-    TailArgs a;
-    a.feat[0] = (const uint16_t*)feat0; a.feat[1] = (const uint16_t*)feat1; a.feat[2] = (const uint16_t*)feat2;
-    const int px_per_wg = 256;                                    // four 16-pixel groups per wave: ~1,050 workgroups at batch 32
-    int A = 0, blk = 0;
-    for (int s = 0; s < 3; ++s) {
-        if (!w2[s] || !b2[s] || !w3[s] || !b3[s]) return YV_ERR_ARG;
-        a.w2[s] = (const uint16_t*)w2[s]; a.b2[s] = b2[s]; a.w3[s] = (const uint16_t*)w3[s]; a.b3[s] = b3[s];
-        a.hw[s] = size / (8 << s);
-        a.a0[s] = A;
-        A += a.hw[s] * a.hw[s];
-        a.blk0[s] = blk;
-        const long long px = (long long)B * a.hw[s] * a.hw[s];
-        if (px > 0x7fffffffLL) return YV_ERR_LIMIT;
-        blk += (int)((px + px_per_wg - 1) / px_per_wg);
-    }
-    hipStream_t st = (hipStream_t)stream;
-    if (c3 == 64) hipLaunchKernelGGL(detect_tail_kernel<2>, dim3(blk), dim3(256), 0, st, a, ld, B, A, nc, px_per_wg, boxes, scores);
-    else if (c3 == 128) hipLaunchKernelGGL(detect_tail_kernel<4>, dim3(blk), dim3(256), 0, st, a, ld, B, A, nc, px_per_wg, boxes, scores);
-    else hipLaunchKernelGGL(detect_tail_kernel<6>, dim3(blk), dim3(256), 0, st, a, ld, B, A, nc, px_per_wg, boxes, scores);
-    return yv_launch_status();
+    return yv_detect_tail_hw(feat0, feat1, feat2, ld, c3, w2, b2, w3, b3, B, size, size, nc, boxes, scores, stream);
 }

@@ -36,15 +36,16 @@ def _auto_optimizer(n_images, batch, epochs, nc, lr0, momentum):
     return "adamw", round(0.002 * 5 / (4 + nc), 6), 0.9
 
 
-def val(state, data, scale="n", imgsz=640, batch=16, conf=0.25, iou=0.6, device="cuda:0"):
+def val(state, data, scale="n", imgsz=640, batch=16, conf=0.25, iou=0.6, device="cuda:0", rect=False):
     """`model.val(data=, imgsz=640, batch=16, conf=0.25, iou=0.6, device='0')` (utils/trainYolo.py:21-26): detection
-    metrics of a state dict over the yaml's `val` split (yvhip/yolo_val.py)."""
+    metrics of a state dict over the yaml's `val` split (yvhip/yolo_val.py).  rect=True: the published validator's
+    rectangular batches (parity unpinned); train()'s own per-epoch validation stays square."""
     from yvhip.yolo_data import list_samples, read_data_yaml
     from yvhip.yolo_val import validate
     from yvhip.yolo_augment import DetAugment, augment_batch
     cfg = read_data_yaml(data)
     samples = list_samples(cfg["val"]) if cfg["val"] and os.path.isdir(cfg["val"]) else []
-    return validate(state, samples, scale, cfg["nc"], imgsz, batch, conf, iou, device)
+    return validate(state, samples, scale, cfg["nc"], imgsz, batch, conf, iou, device, rect=rect)
 
 
 def train(epochs, batch, data, weights=None, scale="n", size=640, save=None, device="cuda:0", seed=42, log=print,

@@ -32,6 +32,9 @@ class YvError(RuntimeError):
     pass
 
 
+from .extent import n_anchors, net_hw          # noqa: E402  (host helpers; the module imports YvError from here)
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise YvError(f"{LIB_PATH} is missing: build it with `make -C yolov8-vit_amd/csrc` "
@@ -90,12 +93,15 @@ _SIGS = {
     "yv_compact_crops_split": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "yv_crop_resize_norm": (_i, [_vp, _i, _i, _i, _sz, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "yv_letterbox": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp]),
+    "yv_letterbox_hw": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _vp, _vp]),
     "yv_augment_patchify": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "yv_train_crops": (_i, [_vp, _sz, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp]),
     "yv_mosaic_augment": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "yv_mosaic_augment_ex": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "yv_detect_decode": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "yv_detect_tail": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "yv_detect_decode_hw": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "yv_detect_tail_hw": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "yv_c2f_debug": (_i, [_vp]),
     "yv_crop_debug": (_i, [_i]),
     "yv_c2f_fused": (_i, [_vp, C.c_longlong, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_longlong, _vp]),
@@ -384,10 +390,16 @@ def crop_resize_norm(images: torch.Tensor, crop_list: torch.Tensor, crop_total: 
     return out
 
 
-def letterbox(src: torch.Tensor, geom: torch.Tensor, size: int) -> torch.Tensor:
-    """src (B,Hc,Wc,3) u8 canvas, geom (B,6) i32 {w,h,nw,nh,left,top} -> (B,size,size,3) u8."""
+def letterbox(src: torch.Tensor, geom: torch.Tensor, size) -> torch.Tensor:
+    """src (B,Hc,Wc,3) u8 canvas, geom (B,6) i32 {w,h,nw,nh,left,top} -> (B,size,size,3) u8; size an (H, W) pair of multiples
+    of 32: (B,H,W,3)."""
     _chk_dev(src, geom)
     B, Hc, Wc, _ = src.shape
+    if isinstance(size, (tuple, list)):
+        H, W = net_hw(size)
+        out = torch.empty((B, H, W, 3), dtype=torch.uint8, device=src.device)
+        check(lib.yv_letterbox_hw(_p(src), B, Hc, Wc, _p(geom), H, W, _p(out), _st()), "yv_letterbox_hw")
+        return out
     out = torch.empty((B, size, size, 3), dtype=torch.uint8, device=src.device)
     check(lib.yv_letterbox(_p(src), B, Hc, Wc, _p(geom), size, _p(out), _st()), "yv_letterbox")
     return out
@@ -496,13 +508,23 @@ def mosaic_augment_ex(tiles: torch.Tensor, rec_h: torch.Tensor, rec_i: torch.Ten
     return out
 
 
-def detect_decode(box_logits, cls_logits, size: int, nc: int):
-    """box_logits: 3 x (B,Hs,Ws,64) f32; cls_logits: 3 x (B,Hs,Ws,ld) f32 -> boxes (B,A,4), scores (B,A,nc)."""
+def detect_decode(box_logits, cls_logits, size, nc: int):
+    """box_logits: 3 x (B,Hs,Ws,64) f32; cls_logits: 3 x (B,Hs,Ws,ld) f32 -> boxes (B,A,4), scores (B,A,nc).  size: the network
+    input's side, or its (H, W)."""
     _chk_dev(*box_logits, *cls_logits)
     B = box_logits[0].shape[0]
     ld = cls_logits[0].shape[-1]
-    A = sum((size // s) ** 2 for s in (8, 16, 32))
     dev = box_logits[0].device
+    if isinstance(size, (tuple, list)):
+        H, W = net_hw(size)
+        A = n_anchors(H, W)
+        boxes = torch.empty((B, A, 4), dtype=torch.float32, device=dev)
+        scores = torch.empty((B, A, nc), dtype=torch.float32, device=dev)
+        check(lib.yv_detect_decode_hw(_p(box_logits[0]), _p(box_logits[1]), _p(box_logits[2]), _p(cls_logits[0]),
+                                      _p(cls_logits[1]), _p(cls_logits[2]), ld, B, H, W, nc, _p(boxes), _p(scores), _st()),
+              "yv_detect_decode_hw")
+        return boxes, scores
+    A = sum((size // s) ** 2 for s in (8, 16, 32))
     boxes = torch.empty((B, A, 4), dtype=torch.float32, device=dev)
     scores = torch.empty((B, A, nc), dtype=torch.float32, device=dev)
     check(lib.yv_detect_decode(_p(box_logits[0]), _p(box_logits[1]), _p(box_logits[2]), _p(cls_logits[0]),
@@ -511,17 +533,25 @@ def detect_decode(box_logits, cls_logits, size: int, nc: int):
     return boxes, scores
 
 
-def detect_tail(feats, c3: int, w2, b2, w3, b3, size: int, nc: int):
+def detect_tail(feats, c3: int, w2, b2, w3, b3, size, nc: int):
     """Fused Detect tail: feats 3 x (B,Hs,Ws,ld) bf16 (box-branch features in channels 0..63, class-branch features behind them);
     w2 3 x (64,64) bf16, b2 3 x (64) f32, w3 3 x (16,c3) bf16 (rows >= nc zero), b3 3 x (16) f32 -> boxes (B,A,4), scores (B,A,nc),
-    bit-identical to the two 1 x 1 convolutions + detect_decode."""
+    bit-identical to the two 1 x 1 convolutions + detect_decode.  size: the network input's side, or its (H, W)."""
     _chk_dev(*feats, *w2, *b2, *w3, *b3)
     B, ld = feats[0].shape[0], feats[0].shape[-1]
-    A = sum((size // s) ** 2 for s in (8, 16, 32))
     dev = feats[0].device
+    arr = lambda ts: (C.c_void_p * 3)(*[t.data_ptr() for t in ts])
+    if isinstance(size, (tuple, list)):
+        H, W = net_hw(size)
+        A = n_anchors(H, W)
+        boxes = torch.empty((B, A, 4), dtype=torch.float32, device=dev)
+        scores = torch.empty((B, A, nc), dtype=torch.float32, device=dev)
+        check(lib.yv_detect_tail_hw(_p(feats[0]), _p(feats[1]), _p(feats[2]), ld, c3, arr(w2), arr(b2), arr(w3), arr(b3), B, H, W,
+                                    nc, _p(boxes), _p(scores), _st()), "yv_detect_tail_hw")
+        return boxes, scores
+    A = sum((size // s) ** 2 for s in (8, 16, 32))
     boxes = torch.empty((B, A, 4), dtype=torch.float32, device=dev)
     scores = torch.empty((B, A, nc), dtype=torch.float32, device=dev)
-    arr = lambda ts: (C.c_void_p * 3)(*[t.data_ptr() for t in ts])
     check(lib.yv_detect_tail(_p(feats[0]), _p(feats[1]), _p(feats[2]), ld, c3, arr(w2), arr(b2), arr(w3), arr(b3), B, size, nc,
                              _p(boxes), _p(scores), _st()), "yv_detect_tail")
     return boxes, scores

@@ -19,6 +19,7 @@ from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import torch
 
+from .extent import n_anchors, net_hw
 from .guard import StepGuard
 from . import (EPI_GELU, EPI_OUT_F32, EPI_POSEMB, EPI_RES_BF16, EPI_RES_F32, EPI_SILU, RES_LN_WIDTHS, YvError, attention,
                attention_cls, attention_long, attention_mxfp8, c2f_fused, cls_rows, conv2d, conv2d_mxfp8, detect_decode,
@@ -139,7 +140,7 @@ class Conv(NamedTuple):
     res_off: Optional[int]      # channel offset in `out` of the bf16 residual, None = no residual
     flags: int                  # epilogue
     cout: int
-    down: int                   # the output grid is (size // down) x (size // down)
+    down: int                   # the output grid is (H // down) x (W // down)
     block: Optional[int]        # index of the C2f block the convolution is part of
 
 
@@ -254,20 +255,21 @@ def _khwc(w: torch.Tensor) -> torch.Tensor:
 
 
 class YoloEngine:
-    """images (B,S,S,3) u8 RGB on the device -> boxes (B,A,4) f32 xyxy, scores (B,A,nc) f32."""
+    """images (B,H,W,3) u8 RGB on the device -> boxes (B,A,4) f32 xyxy, scores (B,A,nc) f32."""
 
-    def __init__(self, state: Dict[str, torch.Tensor], scale: str = "n", nc: int = 5, size: int = 640,
+    def __init__(self, state: Dict[str, torch.Tensor], scale: str = "n", nc: int = 5, size=640,
                  device: str = "cuda:0", dtype: str = "bf16"):
-        """dtype "bf16" (default) or "mxfp8": the convolutions of mx_conv_plan(scale, nc) then run on OCP e4m3 operands with
+        """size: the network input's side, or its (H, W); both sides multiples of 32.  `hw` is always (H, W); `size` is the int
+        of a square engine and the pair of a rectangular one.  The launch list does not depend on the extent.
+        dtype "bf16" (default) or "mxfp8": the convolutions of mx_conv_plan(scale, nc) then run on OCP e4m3 operands with
         one E8M0 scale per 32 input channels (yv_conv2d_mxfp8; weights quantised once here), their inputs kept as MX maps
         next to the bf16 activations; the rest of the network is unchanged."""
         require_gpu()
-        if size % 32:
-            raise YvError("input size must be a multiple of 32")
+        hw = net_hw(size)
         if dtype not in ("bf16", "mxfp8"):
             raise YvError("dtype must be 'bf16' or 'mxfp8'")
         self.dtype = dtype
-        self.scale, self.nc, self.size, self.dev = scale, nc, size, torch.device(device)
+        self.scale, self.nc, self.dev = scale, nc, torch.device(device)
         self.layers = yolo_layers(scale)
         self.w: Dict[str, torch.Tensor] = {}
         self.b: Dict[str, torch.Tensor] = {}
@@ -310,34 +312,48 @@ class YoloEngine:
         heads = [(f"model.22.cv2.{s}.2", f"model.22.cv3.{s}.2.pad16") for s in range(3)]
         self._tail_operands = ([self.w[k] for k, _ in heads], [self.b[k] for k, _ in heads],
                                [self.w[k] for _, k in heads], [self.b[k] for _, k in heads])
+        self._set_extent(hw)
+
+    def _set_extent(self, hw: Tuple[int, int]):
+        """What depends on the input extent: the sizes, the anchor count, the buffer sets and their guard."""
+        self.hw = hw
+        self.size = hw[0] if hw[0] == hw[1] else hw
+        self.A = n_anchors(*hw)
         self._bufs: Dict[int, dict] = {}
         self.guard = StepGuard()                 # one replay of the launch list at a time (callers may be threads)
-        self.A = sum((size // s) ** 2 for s in (8, 16, 32))
+
+    def resized(self, size) -> "YoloEngine":
+        """A sibling engine for another input extent (an int or (H, W)): it shares this engine's weight, bias, MX weight and
+        tail-operand tensors (nothing is uploaded or quantised again) and has buffers and a StepGuard of its own."""
+        hw = net_hw(size)
+        sib = object.__new__(type(self))
+        sib.__dict__.update(self.__dict__)
+        sib._set_extent(hw)
+        return sib
 
     # -- buffers are allocated once per batch size and reused (no allocation in the step)
     def _buffers(self, B: int) -> dict:
         """"flat": the launch list's buffers by name; "out": the layers' outputs by index; "mx": the MX maps by buffer name."""
         if B in self._bufs:
             return self._bufs[B]
-        S = self.size
-        bf = lambda h, c: torch.zeros((B, h, h, c), dtype=torch.bfloat16, device=self.dev)
-        f32 = lambda h, c: torch.zeros((B, h, h, c), dtype=torch.float32, device=self.dev)
+        H, W = self.hw
+        bf = lambda d, c: torch.zeros((B, H // d, W // d, c), dtype=torch.bfloat16, device=self.dev)
+        f32 = lambda d, c: torch.zeros((B, H // d, W // d, c), dtype=torch.float32, device=self.dev)
         flat: Dict[str, torch.Tensor] = {}
         for idx, kind, p in self.layers:
-            h = S // LAYER_STRIDE[idx]
-            flat[f"out{idx}"] = bf(h, p["cout"])
+            d = LAYER_STRIDE[idx]
+            flat[f"out{idx}"] = bf(d, p["cout"])
             if kind == "c2f":
                 c = p["cout"] // 2
-                flat[f"y{idx}"] = bf(h, (2 + p["n"]) * c)
-                flat[f"t{idx}"] = bf(h, c)
+                flat[f"y{idx}"] = bf(d, (2 + p["n"]) * c)
+                flat[f"t{idx}"] = bf(d, c)
             elif kind == "sppf":
-                flat[f"y{idx}"] = bf(h, p["cin"] * 2)
-        for s, st in enumerate((8, 16, 32)):
-            hs = S // st
-            flat[f"det{s}.hb"] = bf(hs, self.c2 + self.c3)
-            flat[f"det{s}.hc"] = bf(hs, self.c2 + self.c3)
-            flat[f"det{s}.box"] = f32(hs, 4 * REG_MAX)
-            flat[f"det{s}.cls"] = f32(hs, self.ncp)
+                flat[f"y{idx}"] = bf(d, p["cin"] * 2)
+        for s, d in enumerate((8, 16, 32)):
+            flat[f"det{s}.hb"] = bf(d, self.c2 + self.c3)
+            flat[f"det{s}.hc"] = bf(d, self.c2 + self.c3)
+            flat[f"det{s}.box"] = f32(d, 4 * REG_MAX)
+            flat[f"det{s}.cls"] = f32(d, self.ncp)
         # every bf16 activation an MX convolution reads gets an MX map next to it, written by its producers (bf16 engine: none)
         mx_convs = [e for e in detect_launches(self.scale, self.nc) if type(e) is Conv and e.key in self.wq]
         read = sorted({b for e in mx_convs for b, *_ in e.srcs})
@@ -354,16 +370,16 @@ class YoloEngine:
 
     def _conv(self, bufs, B: int, e: Conv):
         flat, mx = bufs["flat"], bufs["mx"]
-        h, out = self.size // e.down, flat[e.out]
+        h, wd, out = self.hw[0] // e.down, self.hw[1] // e.down, flat[e.out]
         res = out if e.res_off is not None else None
         if e.key in self.wq:
             wq, ws = self.wq[e.key]
             v = [mx_view(mx[b], off, c, up) for b, off, c, up in e.srcs]
-            conv2d_mxfp8(v[0], v[1] if len(v) > 1 else None, B, h, h, e.k, e.stride, wq, ws, self.b[e.key], out, e.out_off,
+            conv2d_mxfp8(v[0], v[1] if len(v) > 1 else None, B, h, wd, e.k, e.stride, wq, ws, self.b[e.key], out, e.out_off,
                          e.flags, res=res, res_c_off=e.res_off or 0, out_mx=mx.get(e.out), outq_c_off=e.out_off)
         else:
             v = [view(flat[b], off, c, up) for b, off, c, up in e.srcs]
-            conv2d(v[0], v[1] if len(v) > 1 else None, B, h, h, e.k, e.stride, self.w[e.key], self.b[e.key], out, e.out_off,
+            conv2d(v[0], v[1] if len(v) > 1 else None, B, h, wd, e.k, e.stride, self.w[e.key], self.b[e.key], out, e.out_off,
                    e.flags, res=res, res_c_off=e.res_off or 0)
             self._produced(bufs, e.out, e.out_off, e.cout)
 
@@ -383,10 +399,10 @@ class YoloEngine:
         """Walks detect_launches (self.fused_c2f is read here, so it may be flipped between calls).  tail=False: stop in front of
         the last 1 x 1 convolutions and return the per-scale feature buffers (B,Hs,Ws,c2+c3)."""
         if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[-1] != 3:
-            raise YvError("images must be (B,S,S,3) uint8")
-        B, S = images.shape[0], images.shape[1]
-        if S != self.size or images.shape[2] != self.size:
-            raise YvError(f"engine built for {self.size}x{self.size}")
+            raise YvError("images must be (B,H,W,3) uint8")
+        B = images.shape[0]
+        if tuple(images.shape[1:3]) != self.hw:
+            raise YvError(f"engine built for {self.hw[0]}x{self.hw[1]}")
         bufs = self._buffers(B)
         flat, w, b = bufs["flat"], self.w, self.b
         for e in detect_launches(self.scale, self.nc, bool(self.fused_c2f), tail):

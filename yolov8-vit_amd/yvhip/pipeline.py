@@ -35,11 +35,11 @@ class DetectClassifyPipeline:
         self.parts = 2                                    # slices whose counts detect_stage publishes (PipelinedRunner: one per stream)
         self._const: Dict[int, dict] = {}
 
-    def _identity_geometry(self, B: int, S: int, dev):
-        key = (B, S)
+    def _identity_geometry(self, B: int, H: int, W: int, dev):
+        key = (B, H, W)
         if key not in self._const:
             self._const[key] = dict(ratio=torch.ones(B, device=dev), dwdh=torch.zeros(2 * B, device=dev),
-                                    wh=torch.full((2 * B,), S, dtype=torch.int32, device=dev))
+                                    wh=torch.tensor([W, H] * B, dtype=torch.int32, device=dev))
         return self._const[key]
 
     def detect(self, images: torch.Tensor):
@@ -49,10 +49,10 @@ class DetectClassifyPipeline:
     def detect_stage(self, images: torch.Tensor, ratio: Optional[torch.Tensor] = None,
                      dwdh: Optional[torch.Tensor] = None, img_wh: Optional[torch.Tensor] = None) -> dict:
         """Detector + NMS + restore/filter/dedupe/inflate + batch assembly: everything up to the crop list."""
-        B, S = images.shape[0], images.shape[1]
+        B, H, W = images.shape[0], images.shape[1], images.shape[2]
         dev = images.device
         if ratio is None:
-            c = self._identity_geometry(B, S, dev)
+            c = self._identity_geometry(B, H, W, dev)
             ratio, dwdh, img_wh = c["ratio"], c["dwdh"], c["wh"]
         num, bb, sc, lb = self.detect(images)
         post = postprocess_dets(num, bb, sc, lb, ratio, dwdh, img_wh, self.conf, self.dedupe_iou, self.coord_mode,
@@ -115,8 +115,8 @@ class DetectClassifyPipeline:
     def __call__(self, images: torch.Tensor, ratio: Optional[torch.Tensor] = None,
                  dwdh: Optional[torch.Tensor] = None, img_wh: Optional[torch.Tensor] = None,
                  src_images: Optional[torch.Tensor] = None) -> dict:
-        """images (B,S,S,3) u8 letterboxed network input; src_images (B,H,W,3) u8 originals the crops are
-        taken from (default: `images`, i.e. inputs that are already S x S: ratio 1, dwdh 0)."""
+        """images (B,Hn,Wn,3) u8 letterboxed network input (the detector engine's extent); src_images (B,H,W,3) u8 originals
+        the crops are taken from (default: `images`, i.e. inputs that already have the network's extent: ratio 1, dwdh 0)."""
         det = self.detect_stage(images, ratio, dwdh, img_wh)
         return self.classify_stage(images if src_images is None else src_images, det)
 

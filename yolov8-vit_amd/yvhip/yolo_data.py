@@ -2,12 +2,13 @@
 `images/{train,val}` + `labels/{train,val}` tree that utils/class_config.py:89-148 writes).
 
 Deliberately minimal (SURVEY.md 8(f) N4 - mosaic / HSV / flips of the ultralytics loader are not built): images are
-letterboxed to the square network input with the published letterbox arithmetic and labels are mapped into those
+letterboxed to the network input (a square, or the (H, W) rectangle of rect validation) with the published letterbox arithmetic and labels are mapped into those
 pixels.  Label files may carry the reference writer's literal backslash-n separators (utils/class_config.py:84)."""
 from __future__ import annotations
 
+import math
 import os
-from typing import Dict, List, Tuple
+from typing import Dict, List, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -55,27 +56,53 @@ def parse_label_text(text: str) -> np.ndarray:
     return np.asarray(rows, dtype=np.float64).reshape(-1, 5)
 
 
-def letterbox_host(im: np.ndarray, size: int, color: int = 114):
-    """(h,w,3) u8 -> (size,size,3) u8, ratio, (left, top): r = min(S/h, S/w); unpad = round(w*r), round(h*r);
-    pad = round(d - 0.1) (the arithmetic of YOLOTensorRT_yolodet_py_解读.md:67-69); bilinear resize (PIL)."""
+def _extent(size) -> Tuple[int, int]:
+    """(H, W) of a network extent given as an int (square) or an (H, W) pair."""
+    return (int(size[0]), int(size[1])) if isinstance(size, (tuple, list)) else (int(size), int(size))
+
+
+def letterbox_host(im: np.ndarray, size, color: int = 114):
+    """(h,w,3) u8 -> (H,W,3) u8, ratio, (left, top), with (H, W) = (size, size) or the pair `size`: r = min(H/h, W/w);
+    unpad = round(w*r), round(h*r); pad = round(d - 0.1) (the arithmetic of YOLOTensorRT_yolodet_py_解读.md:67-69); bilinear
+    resize (PIL)."""
     from PIL import Image
+    H, W = _extent(size)
     h, w = im.shape[:2]
-    r = min(size / h, size / w)
+    r = min(H / h, W / w)
     nw, nh = int(round(w * r)), int(round(h * r))
-    dw, dh = (size - nw) / 2, (size - nh) / 2
+    dw, dh = (W - nw) / 2, (H - nh) / 2
     top, left = int(round(dh - 0.1)), int(round(dw - 0.1))
     if (nw, nh) != (w, h):
         im = np.asarray(Image.fromarray(im).resize((nw, nh), Image.BILINEAR))
-    out = np.full((size, size, 3), color, dtype=np.uint8)
+    out = np.full((H, W, 3), color, dtype=np.uint8)
     out[top:top + nh, left:left + nw] = im
     return out, r, (left, top)
 
 
-def load_batch(samples: List[Tuple[str, str]], size: int, max_boxes: int):
-    """-> images (B,size,size,3) u8, gt_boxes (B,G,4) f32 xyxy letterboxed pixels, gt_labels (B,G) i32, counts (B) i32."""
+def rect_batches(shapes_hw: Sequence[Tuple[int, int]], batch: int, imgsz: int, stride: int = 32,
+                 pad: float = 0.5) -> List[Tuple[List[int], Tuple[int, int]]]:
+    """Rectangular validation batches with the published validator's arithmetic: images ((h, w) pairs) sorted by aspect
+    ratio h / w and cut into batches of `batch`; per batch, from its smallest and largest ratio, the relative shape [h, w] is
+    [max, 1] where max < 1 (all landscape), [1, 1 / min] where min > 1 (all portrait) and [1, 1] otherwise; the batch extent
+    is ceil([h, w] * imgsz / stride + pad) * stride (a square image at 640: 672).  -> [(image indices, (H, W))]."""
+    ar = np.asarray([h / w for h, w in shapes_hw], dtype=np.float64)
+    order = np.argsort(ar, kind="stable")
+    out = []
+    for s in range(0, len(order), batch):
+        idx = order[s:s + batch]
+        mini, maxi = float(ar[idx].min()), float(ar[idx].max())
+        rel = [maxi, 1.0] if maxi < 1 else ([1.0, 1.0 / mini] if mini > 1 else [1.0, 1.0])
+        H, W = (int(math.ceil(v * imgsz / stride + pad)) * stride for v in rel)
+        out.append(([int(i) for i in idx], (H, W)))
+    return out
+
+
+def load_batch(samples: List[Tuple[str, str]], size, max_boxes: int):
+    """-> images (B,H,W,3) u8 ((H, W) = (size, size) or the pair `size`), gt_boxes (B,G,4) f32 xyxy letterboxed pixels,
+    gt_labels (B,G) i32, counts (B) i32."""
     from PIL import Image
     B = len(samples)
-    imgs = np.zeros((B, size, size, 3), dtype=np.uint8)
+    imgs = np.zeros((B, *_extent(size), 3), dtype=np.uint8)
     boxes = np.zeros((B, max_boxes, 4), dtype=np.float32)
     labels = np.zeros((B, max_boxes), dtype=np.int32)
     counts = np.zeros((B,), dtype=np.int32)

@@ -3,7 +3,8 @@ folded-BatchNorm inference engine + class-aware NMS kernel (yv_efficient_nms: ca
 IoU > iou, 300 detections per image) over the `val` split, then the published ultralytics detection metrics on the
 host (numpy bookkeeping, as ultralytics does it): IoU matching at 0.50:0.05:0.95, per-class AP by 101-point
 interpolation of the precision envelope, mAP50, mAP50-95, precision / recall at the best mean-F1 confidence.
-Parity unpinned (ultralytics absent); the metric code is checked on hand-computable cases in tests/test_host_cpu.py."""
+rect=True walks the published validator's rectangular batches (yolo_data.rect_batches) instead of squares.
+Parity unpinned (ultralytics absent), the rectangular batches included; the metric code is checked on hand-computable cases in tests/test_host_cpu.py."""
 from __future__ import annotations
 
 from typing import Dict, List, Tuple
@@ -84,19 +85,37 @@ def ap_per_class(tp: np.ndarray, conf: np.ndarray, pred_cls: np.ndarray, target_
 
 
 def validate(state: Dict[str, torch.Tensor], samples: List[Tuple[str, str]], scale: str, nc: int, size: int = 640,
-             batch: int = 16, conf: float = 0.25, iou: float = 0.6, device: str = "cuda:0", max_det: int = 300) -> Dict:
-    """Detection metrics of an (un-fused or fused) ultralytics-layout state dict over YOLO-format samples."""
+             batch: int = 16, conf: float = 0.25, iou: float = 0.6, device: str = "cuda:0", max_det: int = 300,
+             rect: bool = False) -> Dict:
+    """Detection metrics of an (un-fused or fused) ultralytics-layout state dict over YOLO-format samples.
+    rect=True: the samples are sorted by aspect ratio and every batch runs at its own stride-32 rectangle
+    (yolo_data.rect_batches: the published validator's arithmetic, pad 0.5) on a YoloEngine.resized sibling per shape; each image
+    is letterboxed to its batch's rectangle with r = min(H/h, W/w).  Parity with the published validator is unpinned, as for
+    the rest of this function.  "shapes" lists the (H, W) of every batch in the order they ran."""
     from YOLOTensorRT.models import fold_batchnorm
     from . import efficient_nms
     from .engines import YoloEngine
-    from .yolo_data import load_batch, max_boxes_per_image
+    from .yolo_data import load_batch, max_boxes_per_image, rect_batches
     eng = YoloEngine(fold_batchnorm(state), scale, nc, size, device=device)
     G = max_boxes_per_image(samples) if samples else 1
     tps, confs, pcls, tcls = [], [], [], []
-    for i in range(0, len(samples), batch):
-        chunk = samples[i:i + batch]
-        img, gtb, gtl, gtn = load_batch(chunk, size, G)
-        boxes, scores = eng(img.to(device))
+    if rect:
+        from PIL import Image
+        hw = [Image.open(ip).size[::-1] for ip, _ in samples]
+        plan = [([samples[i] for i in idx], shape) for idx, shape in rect_batches(hw, batch, size)] if samples else []
+    else:
+        plan = [(samples[i:i + batch], size) for i in range(0, len(samples), batch)]
+    siblings: Dict[tuple, object] = {}                   # rect: one engine per batch shape, on eng's weights
+    shapes = []
+    for chunk, ext in plan:
+        run = eng
+        if rect:
+            if ext not in siblings:
+                siblings[ext] = eng.resized(ext)
+            run = siblings[ext]
+        shapes.append(run.hw)
+        img, gtb, gtl, gtn = load_batch(chunk, ext, G)
+        boxes, scores = run(img.to(device))
         num, ob, osc, ol = efficient_nms(boxes, scores, conf, iou, max_det)
         num, ob, osc, ol = num.cpu().numpy()[:, 0], ob.cpu().numpy(), osc.cpu().numpy(), ol.cpu().numpy()
         for b in range(len(chunk)):
@@ -116,4 +135,4 @@ def validate(state: Dict[str, torch.Tensor], samples: List[Tuple[str, str]], sca
     return {"images": len(samples), "instances": int(target_cls.shape[0]), "precision": float(res["p"].mean()) if res["p"].size else 0.0,
             "recall": float(res["r"].mean()) if res["r"].size else 0.0, "map50": res["map50"], "map50_95": res["map"],
             "ap_per_class": {int(c): res["ap"][k].tolist() for k, c in enumerate(res["classes"])},
-            "conf": conf, "iou": iou, "detections": int(sum(len(c) for c in confs))}
+            "conf": conf, "iou": iou, "detections": int(sum(len(c) for c in confs)), "shapes": shapes}
