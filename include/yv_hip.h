@@ -40,14 +40,16 @@ const char* yv_error_string(int code);
 int yv_device_is_gfx950(void);
 /* Tuning knobs (process-wide, not part of the reference surface): "linear_group_m" (M tiles per L2 group) and "linear_variant",
  * the kernel of yv_linear / yv_linear_ex (yv_linear_route reports what a value selects for a shape):
- *   1          the shipped rule: skinny, register-staged, split-K, persistent or 128 x 128 LDS-DMA tiles by shape and flags;
+ *   1          the shipped rule: skinny, register-staged, mid-M ("linear_mid": the largest M gemm_mid_kernel takes, 0 = off,
+ *              the default; "linear_mid_fill": it takes a shape that makes at most this many eighths of the CU count in
+ *              128 x 128 tiles, 5), split-K, persistent or 128 x 128 LDS-DMA tiles by shape and flags;
  *   0          igemm_kernel, register-staged 128 x 16 / 32 / 64 / 128 tiles, for every shape;
  *   2, 3, 4    gemm_dma_kernel with 256 x 128, 256 x 256, 128 x 256 tiles;
  *   9, 11      the persistent gemm_p8_kernel / gemm_p9_kernel where the shape and flags allow them, at any M (else 128 x 128);
  *   101 .. 104 gemm_dma_kernel 128 x 128 with one stage of its main loop taken out (ablations 1 .. 4, tools/gemm_bench.py);
  *   201 .. 204 the same ablations on 256 x 256 tiles;
  *   any other  128 x 128 LDS-DMA tiles.
- * Every value but 1 switches the skinny kernel off; N <= 64 or K % 64 != 0 always runs igemm_kernel; a split-K launch (a
+ * Every value but 1 switches the skinny and the mid-M kernel off; N <= 64 or K % 64 != 0 always runs igemm_kernel; a split-K launch (a
  * registered workspace, few tiles, a long K) takes 128 x 128 tiles whatever the value says.  The forced instances check less
  * than the shipped rule does: they are for benchmarks at shapes known to suit them. */
 int yv_set_option(const char* key, int value);
@@ -123,6 +125,7 @@ int yv_linear_mxfp8_instance(int M, int N, int K, int flags);
 #define YV_LIN_P8 3     /* gemm_p8_kernel<.., f32out>: persistent, 8-phase, tile_rows x 256                                 */
 #define YV_LIN_P9 4     /* gemm_p9_kernel<tile_rows / 32, f32out, 0, ext, mx>: persistent, free-running, tile_rows x 256    */
 #define YV_LIN_MX 5     /* gemm_mx_kernel<128, 128, 2, 2> (mx = 1 only)                                                     */
+#define YV_LIN_MID 6    /* gemm_mid_kernel, 64 x 64 tiles, K split over its two wave groups ("linear_mid" > 0 only)         */
 #define YV_ROUTE_M_DEV 0x40000000 /* yv_linear_route's `flags` only */
 typedef struct {
     int kernel;               /* YV_LIN_* */

@@ -1,0 +1,135 @@
+#!/usr/bin/env python3
+"""Dev tool (GPU box): latency of ONE DetectClassifyPipeline.__call__ at request size - what inferdet.main runs per chunk - for
+YOLOv8n + ViT-B/16 and YOLOv8n + ViT-B/8 at B = 1 and 4 images of 640 x 640 with 1, 3 and 8 detections per image, in four states:
+  default              the pipeline as it ships (classifier capacity B * topk = 100 B crops);
+  fit_crops            DetectClassifyPipeline(fit_crops=True);
+  fit_crops+mid_gemm   ... with VitEngine(mid_gemm=True);
+  mid_gemm             VitEngine(mid_gemm=True) alone.
+The detector runs on the images (its time is part of the call); the NMS then works on a synthetic candidate set in place of the
+random-weight detector's - 8400 boxes per image by the recipe of bench.py's postproc mode (centres uniform, sides U[16, 256]),
+with exactly d well-separated candidates above the thresholds - so that the crop count is the one asked for.
+The states are interleaved in one process, RB_RUNS (3) runs of RB_CALLS (20) calls each; a call is timed on the host from its
+start to the end of a device synchronisation.  Reported: the median call, the median detect stage alone (same method), and
+the peak of torch.cuda.max_memory_allocated over a call above what was allocated before the first call of that shape (the
+engines' activation buffers: every engine starts each shape with none)."""
+import gc, os, sys, time
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "yolov8-vit_amd"))
+import torch
+import yvhip
+from yvhip import engines
+from yvhip.pipeline import DetectClassifyPipeline
+
+dev = "cuda:0"
+RUNS = int(os.environ.get("RB_RUNS", 3))
+CALLS = int(os.environ.get("RB_CALLS", 20))
+S, A, NC = 640, 8400, 5
+STATES = [("default", False, False), ("fit_crops", True, False), ("fit_crops+mid_gemm", True, True), ("mid_gemm", False, True)]
+
+
+def candidates(B, d, seed=4321):
+    """(boxes (B, A, 4), scores (B, A, NC)): d disjoint 96 x 96 boxes per image score 0.9, every other candidate 0.01."""
+    g = torch.Generator().manual_seed(seed)
+    ctr = torch.rand(B, A, 2, generator=g) * S
+    wh = torch.rand(B, A, 2, generator=g) * 240 + 16
+    boxes = torch.cat([(ctr - wh / 2).clamp(0, S), (ctr + wh / 2).clamp(0, S)], -1).contiguous()
+    scores = torch.full((B, A, NC), 0.01)
+    for b in range(B):
+        for k in range(d):
+            x0, y0 = 16 + (k % 4) * 150, 16 + (k // 4) * 150
+            boxes[b, k] = torch.tensor([x0, y0, x0 + 96, y0 + 96], dtype=torch.float32)
+            scores[b, k, (b + k) % NC] = 0.9
+    return boxes.to(dev), scores.to(dev)
+
+
+def with_candidates(pipe, boxes, scores):
+    """pipe.detect: the detector runs (and is timed), the NMS sees the synthetic candidates."""
+    def detect(images):
+        pipe.yolo(images)
+        return yvhip.efficient_nms(boxes, scores, pipe.score_threshold, pipe.iou_threshold, pipe.topk)
+    pipe.detect = detect
+
+
+def wall(fn, n):
+    ts = []
+    for _ in range(n):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        ts.append((time.perf_counter() - t0) * 1e3)
+    return ts
+
+
+def median(v):
+    v = sorted(v)
+    return v[len(v) // 2]
+
+
+def trace_one():
+    """--trace: two default-state calls (B = 1, 3 detections, ViT-B/16) and nothing else, for a kernel trace of the default path
+    (rocprofv3 --kernel-trace -- python tools/request_bench.py --trace); uses nothing that an earlier commit lacks."""
+    yolo = engines.YoloEngine(engines.init_yolo_state("n", NC, seed=42, head_gain=4.0), "n", NC, S, device=dev)
+    name = "vit_base_patch16_224"
+    vit = engines.VitEngine(engines.init_vit_wrapper_state(name, NC, seed=42), name, NC, device=dev)
+    pipe = DetectClassifyPipeline(yolo, [vit])
+    with_candidates(pipe, *candidates(1, 3))
+    images = torch.randint(0, 256, (1, S, S, 3), generator=torch.Generator().manual_seed(1234), dtype=torch.uint8).to(dev)
+    for _ in range(2):
+        out = pipe(images)
+    torch.cuda.synchronize()
+    print("crops", int(out["crop_total"][0]), "labels", out["cls_label"][:3].tolist())
+
+
+def main():
+    print(f"# {torch.cuda.get_device_name(0)}; ms per call, median of {RUNS} x {CALLS} calls, states interleaved; "
+          f"memory: peak above the allocation before the shape's first call")
+    print(f"# {'classifier':22s} {'B':>2s} {'dets':>4s} {'crops':>5s}  {'state':20s} {'capacity':>8s} {'call ms':>8s} {'detect ms':>9s} "
+          f"{'classify ms':>11s} {'peak MB':>9s}  call / default")
+    yolo_sd = engines.init_yolo_state("n", NC, seed=42, head_gain=4.0)
+    yolo = engines.YoloEngine(yolo_sd, "n", NC, S, device=dev)
+    g = torch.Generator().manual_seed(1234)
+    for name in ("vit_base_patch16_224", "vit_base_patch8_224"):
+        vit_sd = engines.init_vit_wrapper_state(name, NC, seed=42)
+        vits = {mid: engines.VitEngine(vit_sd, name, NC, device=dev, mid_gemm=mid) for mid in (False, True)}
+        for B in (1, 4):
+            images = torch.randint(0, 256, (B, S, S, 3), generator=g, dtype=torch.uint8).to(dev)
+            for d in (1, 3, 8):
+                boxes, scores = candidates(B, d)
+                yolo(images)                                  # the detector's own buffers for this B exist before anything is measured
+                pipes, peak, cap, crops = {}, {}, {}, {}
+                for label, fit, mid in STATES:
+                    pipes[label] = p = DetectClassifyPipeline(yolo, [vits[mid]], fit_crops=fit)
+                    with_candidates(p, boxes, scores)
+                for label, fit, mid in STATES:                # memory: each state from engines without activation buffers
+                    for v in vits.values():
+                        v._bufs.clear()
+                    gc.collect(); torch.cuda.synchronize(); torch.cuda.empty_cache()
+                    base = torch.cuda.memory_allocated()
+                    torch.cuda.reset_peak_memory_stats()
+                    out = pipes[label](images)
+                    torch.cuda.synchronize()
+                    peak[label] = (torch.cuda.max_memory_allocated() - base) / 2 ** 20
+                    cap[label], crops[label] = out["capacity"], int(out["crop_total"][0])
+                    if crops[label] != B * d:
+                        print(f"# note: {label}: {crops[label]} crops where {B * d} were injected")
+                    del out
+                for label, _, _ in STATES:                    # buffers of every state back in place, then warm
+                    wall(lambda: pipes[label](images), 3)
+                call = {label: [] for label, _, _ in STATES}
+                det = []
+                for rd in range(RUNS):
+                    for label, _, _ in STATES:
+                        call[label] += wall(lambda: pipes[label](images), CALLS)
+                    det += wall(lambda: pipes["default"].detect_stage(images), CALLS)
+                t_det = median(det)
+                t0 = median(call["default"])
+                for label, _, _ in STATES:
+                    t = median(call[label])
+                    print(f"  {name:22s} {B:2d} {d:4d} {crops[label]:5d}  {label:20s} {cap[label]:8d} {t:8.3f} {t_det:9.3f} "
+                          f"{t - t_det:11.3f} {peak[label]:9.1f}  {t / t0:6.2f}", flush=True)
+                del pipes
+
+
+if __name__ == "__main__":
+    trace_one() if "--trace" in sys.argv[1:] else main()

@@ -11,6 +11,7 @@ import numpy as np
 import torch
 
 import yvhip
+from yvhip.engines import _env_flag
 from yvhip.pipeline import DetectClassifyPipeline
 
 from .config import CLASSES, COLORS
@@ -37,21 +38,22 @@ def _load_rgb(path: str) -> np.ndarray:
     return np.asarray(Image.open(path).convert("RGB"))
 
 
-def _pipeline(Engine, model_list) -> DetectClassifyPipeline:
+def _pipeline(Engine, model_list, fit_crops: bool = False) -> DetectClassifyPipeline:
     vits = [m.engine() for m in model_list]
-    return DetectClassifyPipeline(Engine.engine, vits, Engine.score_threshold, Engine.iou_threshold, Engine.topk)
+    return DetectClassifyPipeline(Engine.engine, vits, Engine.score_threshold, Engine.iou_threshold, Engine.topk,
+                                  fit_crops=fit_crops)
 
 
 def _rect_pipeline(Engine, pipe: DetectClassifyPipeline, cache: dict, hw) -> DetectClassifyPipeline:
     """`pipe` with the detector resized to `hw` (shared weights, own buffers); one per shape."""
     if hw not in cache:
         cache[hw] = DetectClassifyPipeline(Engine.engine.resized(hw), pipe.vits, Engine.score_threshold, Engine.iou_threshold,
-                                           Engine.topk)
+                                           Engine.topk, fit_crops=pipe.fit_crops)
     return cache[hw]
 
 
 def main(Engine, imgs, device=None, model_list: Optional[list] = None, transform=None, aliyunoss=None,
-         func: Optional[Callable] = None, rect: bool = False):
+         func: Optional[Callable] = None, rect: bool = False, fit_crops: Optional[bool] = None):
     """Detect + classify every image under `imgs` (directory, file or list).  Returns a JSON-serialisable dict
     {"output": [{"image": name, "objects": [{"sort", "det_sort", "confidence", "xmin", "ymin", "xmax", "ymax"}]}]}.
     `transform` is accepted for signature compatibility: its valid_test branch (nearest resize to 224 +
@@ -59,13 +61,16 @@ def main(Engine, imgs, device=None, model_list: Optional[list] = None, transform
     called per image like test.py:28 does with generate_annotation.
     rect=True: each chunk of images is letterboxed into the smallest stride-32 rectangle that holds it at the engine's size
     (models.utils.rect_net_shape; the engine must be square) instead of the S x S square, and the detector runs at that
-    extent (YoloEngine.resized, one engine per shape).  Restored coordinates, crops and the result layout are the same."""
+    extent (YoloEngine.resized, one engine per shape).  Restored coordinates, crops and the result layout are the same.
+    fit_crops=True (None: the environment variable YV_FIT_CROPS, "1" = on): the classifier of each chunk is sized to the crops
+    the detector found instead of topk per image (DetectClassifyPipeline(fit_crops=True)): for request-sized calls.  The result
+    is the same dict; classifiers built with mid_gemm=True use their mid-M GEMM, main does not switch it on."""
     yvhip.require_gpu()
     if not model_list:
         raise yvhip.YvError("model_list is empty")
     dev = torch.device(device) if device is not None else Engine.device
     S = Engine.size
-    pipe = _pipeline(Engine, model_list)
+    pipe = _pipeline(Engine, model_list, _env_flag(fit_crops, "YV_FIT_CROPS"))
     if rect and not isinstance(S, int):
         raise yvhip.YvError("rect=True takes a square engine: its size is the long side of every rectangle")
     rect_pipes: dict = {}

@@ -2036,6 +2036,138 @@ int launch_skinny(GemmArgs& g, hipStream_t st) {
     return yv_launch_status();
 }
 
+// ---------------------------------------------------------------------------------------------
+// Mid-M linear (256 < M <= "linear_mid": the classifier at the handful of crops one request carries).  128 x 128 tiles make
+// 42 .. 168 workgroups of the ViT-B products at 788 rows, each walking all of K alone; the skinny kernel's global fragment reads
+// fetch A once per 16 columns.  Here a workgroup owns 64 x 64 outputs (four times the workgroups) and splits K inside itself: its
+// 8 waves are two K halves x (2 x 2 waves of 32 x 32), half h taking the 64-deep K steps h, h + 2, ...  Each half stages its own
+// steps by LDS-DMA (the 128-byte rows, source-side chunk swizzle and fragment reads of gemm_dma_kernel) into its own two-stage
+// ring: 2 halves x 2 stages x (64 + 64) rows x 128 B = 64 KB, two workgroups per CU.  One barrier per pair of K steps, shared
+// by the halves; with an odd step count half 1 idles through the last one.
+// The two partial tiles meet in LDS, overlaying the rings after the last step: each half hands the other the 16-row fragments it
+// does not finish (half 0 keeps rows 0 .. 15 of every wave tile, half 1 rows 16 .. 31), the sum is half 0 + half 1 in that order
+// on both sides, and all 8 waves run gemm_dma_kernel's direct epilogue on the sums.  One launch, no workspace, no atomics.
+// Host: N % 64 == 0, K % 64 == 0, flags within BIAS | GELU | RES_F32 | OUT_F32.
+// ---------------------------------------------------------------------------------------------
+int g_opt_mid = 0;                  // largest M taken by gemm_mid_kernel ("linear_mid"; 0 = off)
+constexpr int MID_FLOOR = 256;      // ... and the M it starts above, whatever "linear_skinny" says
+int g_opt_mid_fill = 5;             // ... where 128 x 128 tiles number at most this many eighths of the CU count ("linear_mid_fill";
+                                    // tools/mid_gemm_bench.py raises it to time the kernel on the shapes the rule leaves out)
+
+__global__ __launch_bounds__(512, 2) void gemm_mid_kernel(GemmArgs g) {
+    constexpr int BM = 64, BN = 64, MF = 2, NF = 2;
+    constexpr int STAGE = (BM + BN) * 128, RING = 2 * STAGE;    // bytes: one K step of a half, a half's two stages
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int half = wave >> 2, w4 = wave & 3;
+
+    int M = g.M;
+    if (g.m_dev) { long long md = (long long)g.m_dev[0] * g.m_mul; M = md < M ? (int)md : M; }
+    int bid = blockIdx.x;
+    {
+        const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, x = bid & 7;
+        bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
+    }
+    int tm, tn;
+    {
+        const int GM = g.group_m, per = GM * g.tiles_n;
+        const int grp = bid / per, first = grp * GM;
+        const int gsz = (g.tiles_m - first) < GM ? (g.tiles_m - first) : GM;
+        const int in = bid - grp * per;
+        tm = first + in % gsz;
+        tn = in / gsz;
+    }
+    const int m0 = tm * BM, n0 = tn * BN;
+    if (m0 >= M) return;
+
+    // a half's four waves fill its stage: 8 rows x 128 B per wave-instruction, 2 for A and 2 for W per wave
+    const int lrow = lane >> 3, lch = lane & 7;
+    const uint16_t* a_src[2];
+    const uint16_t* w_src[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int r = (j * 4 + w4) * 8 + lrow;
+        int m = m0 + r;
+        m = m < g.M ? m : g.M - 1;                              // rows past the end: the last row, never stored
+        a_src[j] = g.a0 + (long long)m * g.lda0 + ((lch ^ (r & 7)) << 3);
+        w_src[j] = g.w + (long long)(n0 + r) * g.K + ((lch ^ (r & 7)) << 3);
+    }
+    unsigned char* const ring = smem + half * RING;
+    auto issue = [&](int kt, int buf) {
+        unsigned char* A = ring + buf * STAGE;
+        unsigned char* W = A + BM * 128;
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+            __builtin_amdgcn_global_load_lds((gptr_t)(a_src[j] + kt * BK), (lptr_t)(A + (j * 4 + w4) * 1024), 16, 0, 0);
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+            __builtin_amdgcn_global_load_lds((gptr_t)(w_src[j] + kt * BK), (lptr_t)(W + (j * 4 + w4) * 1024), 16, 0, 0);
+    };
+
+    f32x4 acc[NF][MF];
+#pragma unroll
+    for (int i = 0; i < NF; ++i)
+#pragma unroll
+        for (int j = 0; j < MF; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    const int wrow_m = (w4 >> 1) * 32, wrow_n = (w4 & 1) * 32;
+    const int fr = lane & 15, fq = lane >> 4;
+
+    const int nk = g.K / BK, trips = (nk + 1) >> 1;             // trip t: K step 2 t + half (half 1 may lack the last one)
+    if (half < nk) issue(half, 0);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    for (int t = 0; t < trips; ++t) {
+        const int cur = t & 1, kt = 2 * t + half;
+        if (kt + 2 < nk) issue(kt + 2, cur ^ 1);
+        if (kt < nk) {
+            const unsigned char* A = ring + cur * STAGE;
+            const unsigned char* W = A + BM * 128;
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks) {
+                bf16x8 fa[MF], fw[NF];
+                const int kc = ks * 4 + fq;
+#pragma unroll
+                for (int j = 0; j < MF; ++j) {
+                    const int rr = wrow_m + j * 16 + fr;
+                    fa[j] = *(const bf16x8*)(A + rr * 128 + ((kc ^ (rr & 7)) << 4));
+                }
+#pragma unroll
+                for (int i = 0; i < NF; ++i) {
+                    const int rr = wrow_n + i * 16 + fr;
+                    fw[i] = *(const bf16x8*)(W + rr * 128 + ((kc ^ (rr & 7)) << 4));
+                }
+#pragma unroll
+                for (int i = 0; i < NF; ++i)
+#pragma unroll
+                    for (int j = 0; j < MF; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fw[i], fa[j], acc[i][j], 0, 0, 0);
+            }
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();                                        // (the last one: every fragment read is done, the rings are free)
+    }
+    // exchange: xch[half][w4][i][lane] holds the fragments (i, 1 - half) of that wave, which the OTHER half finishes
+    f32x4* const xch = (f32x4*)smem;
+#pragma unroll
+    for (int i = 0; i < NF; ++i) xch[((half * 4 + w4) * NF + i) * 64 + lane] = half ? acc[i][0] : acc[i][1];
+    __syncthreads();
+    f32x4 sum[NF][1];
+#pragma unroll
+    for (int i = 0; i < NF; ++i) {
+        const f32x4 other = xch[(((1 - half) * 4 + w4) * NF + i) * 64 + lane];
+        sum[i][0] = half ? other + acc[i][1] : acc[i][0] + other;           // half 0 + half 1
+    }
+    epilogue<1, NF>(g, sum, M, m0, n0, wrow_m + half * 16, wrow_n, fr, fq);
+}
+
+int launch_mid(GemmArgs& g, hipStream_t st) {
+    g.tiles_m = (g.M + 63) / 64;
+    g.tiles_n = g.N >> 6;
+    const size_t lds = 2 * 2 * (size_t)(64 + 64) * 128;
+    if (!yv_grant_lds((const void*)gemm_mid_kernel, lds)) return YV_ERR_LAUNCH;
+    launch_timed(gemm_mid_kernel, g.tiles_m * g.tiles_n, 512, lds, st, g);
+    return yv_launch_status();
+}
+
 template <int BM, int BN, int WM, int WN, int ABL = 0, bool WT = false>
 int launch_dma(GemmArgs& g, hipStream_t st) {
     g.tiles_m = (g.M + BM - 1) / BM;
@@ -2286,6 +2418,15 @@ LinearRoute linear_route(const GemmArgs& g, bool have_ws, size_t ws_bytes, int n
     // 1. one row per crop (the classifier's cls-row tail, the head): gemm_skinny_kernel; 2. register-staged tiles
     if (v == 1 && M <= g_opt_skinny && !(N & 15) && !(K & 31) && plain) return route_of(g, YV_LIN_SKINNY, 64, 16);
     if ((K % BK) || N <= 64 || v == 0) return route_of(g, YV_LIN_IGEMM, 128, 16 << igemm_pick(N));
+    // 2a. a handful of crops ("linear_mid", off by default; section 31): gemm_mid_kernel's 64 x 64 tiles with the K range split
+    // inside the workgroup, for the rows above the skinny kernel's - never below 257, whatever "linear_skinny" says - where
+    // 128 x 128 tiles would make at most "linear_mid_fill" / 8 = 5/8 of a workgroup per CU (160 on 256 CUs).  Measured: up to that count the kernel takes
+    // x 0.46 - 0.91 of the 128 x 128 route's time, from 168 tiles on (qkv / fc1 of ViT-L at 4 crops, of ViT-B at 8) x 1.03 - 1.86:
+    // those shapes go on to the steps below
+    const long long tiles128 = (long long)((M + 127) / 128) * ((N + 127) / 128);
+    if (v == 1 && M > (g_opt_skinny > MID_FLOOR ? g_opt_skinny : MID_FLOOR) && M <= g_opt_mid && !(N & 63) && plain &&
+        tiles128 * 8 <= (long long)g_opt_mid_fill * n_cu)
+        return route_of(g, YV_LIN_MID, 64, 64);
     // 3. split-K for wgrad-shaped problems (few 128 x 128 tiles, a long reduction), partial sums in the stream's workspace, added in
     // slice order by splitk_reduce_kernel; not where the free-running kernel's 96-row tiles fill the chip (the 6,304 x 768 x 768
     // data gradients).  It comes before a forced variant, which it overrides.
@@ -2639,6 +2780,8 @@ static const struct { const char* key; int* (*at)(); } k_options[] = {
     {"conv_splitk", [] { return &g_opt_splitk; }},
     {"linear_splitk", [] { return &g_opt_linear_splitk; }},
     {"linear_skinny", [] { return &g_opt_skinny; }},
+    {"linear_mid", [] { return &g_opt_mid; }},
+    {"linear_mid_fill", [] { return &g_opt_mid_fill; }},
     {"wgrad_mx_split", [] { return &g_opt_wgrad_mx_split; }},
     {"conv_dma", [] { return &g_opt_conv_dma; }},
     {"dgrad_s2_split", [] { return &g_opt_dgrad_s2_split; }},
@@ -2669,6 +2812,7 @@ static int launch_linear(GemmArgs& g, const LinearRoute& r, void* ws, int n_cu, 
     if (r.splitk > 1) g.partial = (float*)ws;
     switch (r.kernel) {
         case YV_LIN_SKINNY: return launch_skinny(g, st);
+        case YV_LIN_MID: return launch_mid(g, st);
         case YV_LIN_P8: return launch_p8(g, st, r.tile_rows, n_cu);
         case YV_LIN_P9: return launch_p9(g, st, r.tile_rows, n_cu, r.mx);
     }

@@ -1411,7 +1411,7 @@ def linear_mxfp8_instance(M: int, N: int, K: int, flags: int = 0) -> int:
 
 STREAM_WS_BYTES = 16 * 1024 * 1024 * 4      # the split-K workspace _st() registers per stream (what linear_route assumes by default)
 # linear_route: kernel families (yv_linear_route_t.kernel, include/yv_hip.h)
-LIN_SKINNY, LIN_IGEMM, LIN_DMA, LIN_P8, LIN_P9, LIN_MX = 0, 1, 2, 3, 4, 5
+LIN_SKINNY, LIN_IGEMM, LIN_DMA, LIN_P8, LIN_P9, LIN_MX, LIN_MID = 0, 1, 2, 3, 4, 5, 6
 ROUTE_M_DEV = 0x40000000                     # linear_route flag: the launch passes a device row count
 LinearRoute = collections.namedtuple("LinearRoute", "kernel tile_rows tile_cols f32out ext abl mx splitk staged grid")
 

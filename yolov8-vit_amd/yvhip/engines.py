@@ -438,6 +438,9 @@ VIT_CFGS = {
 }
 
 
+MID_GEMM_ROWS = 3152      # "linear_mid" of a VitEngine(mid_gemm=True) pass: the bound measured in DESIGN.md section 31
+
+
 def _env_flag(value: Optional[bool], var: str) -> bool:
     """An opt-in constructor flag: the argument where one is given, else the environment variable `var` ("1" = on, unset = off)."""
     return os.environ.get(var, "0") == "1" if value is None else bool(value)
@@ -481,7 +484,7 @@ class VitEngine:
 
     def __init__(self, state: Dict[str, torch.Tensor], name: str, num_classes: int = 5, img: int = 224,
                  device: str = "cuda:0", dtype: str = "bf16", cls_tail: bool = True, fused_ln: Optional[bool] = None,
-                 long_attn: Optional[bool] = None):
+                 long_attn: Optional[bool] = None, mid_gemm: Optional[bool] = None):
         """cls_tail (bf16 path): the last block runs on the cls rows only - nothing reads its other rows (see _last_block_cls);
         False gives the full last block.  The mxfp8 pass runs every block in full whatever cls_tail says, and it ignores
         full_cus_from (the attribute PipelinedRunner sets): both are properties of the bf16 block loop.
@@ -497,7 +500,11 @@ class VitEngine:
         tiles; dtype "mxfp8": writing the proj operand directly) in place of attention / attention_mxfp8.  Effective only where the
         engine's token count exceeds 224 (/8 models at 224, /16 models at 384): a shorter-sequence engine accepts the flag and
         keeps calling attention, whose single-tile kernel is the tuned one there.  attention_cls of the cls tail is unchanged.
-        None reads the environment variable YV_VIT_LONG_ATTN ("1" = on, unset = off).  Works together with fused_ln and cls_tail."""
+        None reads the environment variable YV_VIT_LONG_ATTN ("1" = on, unset = off).  Works together with fused_ln and cls_tail.
+        mid_gemm (opt-in): the pass runs with the option "linear_mid" at MID_GEMM_ROWS, so its bf16 linears of 257 .. that many
+        rows - the block products at a handful of crops, as DetectClassifyPipeline(fit_crops=True) sizes them - take
+        gemm_mid_kernel's 64 x 64 tiles instead of 128 x 128 ones; the option is restored after the pass.  None reads the
+        environment variable YV_VIT_MID_GEMM ("1" = on, unset = off).  Off: the option is not touched."""
         require_gpu()
         if dtype not in ("bf16", "mxfp8"):
             raise YvError("dtype must be 'bf16' or 'mxfp8'")
@@ -507,6 +514,7 @@ class VitEngine:
         if self.fused_ln and dtype != "bf16":
             raise YvError("fused_ln is a property of the bf16 path (dtype='mxfp8' hands LayerNorm outputs over in MXFP8)")
         self.long_attn = _env_flag(long_attn, "YV_VIT_LONG_ATTN")
+        self.mid_gemm = _env_flag(mid_gemm, "YV_VIT_MID_GEMM")
         self.fuse_attention_quant = os.environ.get("YV_MX_ATTN_FUSED", "1") == "1"     # A/B switch of the mxfp8 path
         self.P, self.D, self.L, self.H = vit_cfg(name)
         if self.D // self.H != 64:
@@ -602,6 +610,16 @@ class VitEngine:
             return feats if outer else feats.clone()         # bare call: a copy that the next replay cannot overwrite
 
     def _backbone(self, patches: torch.Tensor, cap: int, count: Optional[torch.Tensor], slot: int) -> torch.Tensor:
+        if not self.mid_gemm:
+            return self._backbone_tail(patches, cap, count, slot)
+        mid = get_option("linear_mid")
+        set_option("linear_mid", MID_GEMM_ROWS)
+        try:
+            return self._backbone_tail(patches, cap, count, slot)
+        finally:
+            set_option("linear_mid", mid)
+
+    def _backbone_tail(self, patches: torch.Tensor, cap: int, count: Optional[torch.Tensor], slot: int) -> torch.Tensor:
         if self.cls_tail:
             return self._backbone_pass(patches, cap, count, slot)
         skinny = get_option("linear_skinny")            # the full path as it was before the cls tail: its kernels, its bits

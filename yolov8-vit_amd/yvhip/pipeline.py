@@ -18,10 +18,24 @@ from . import (YvError, compact_crops, crop_resize_norm, efficient_nms, postproc
 from .engines import VitEngine, YoloEngine
 
 
+def fit_capacity(total: int, cap: int) -> int:
+    """Classifier capacity for `total` crops of at most `cap`: the smallest power of two >= total, at least 1 and at most cap;
+    0 for no crops.  Powers of two bound the buffer sets an engine keeps (VitEngine._bufs is keyed by capacity)."""
+    if total <= 0:
+        return 0
+    return min(1 << (int(total) - 1).bit_length(), int(cap))
+
+
 class DetectClassifyPipeline:
     def __init__(self, yolo: YoloEngine, vits: Sequence[VitEngine], score_threshold: float = 0.25,
                  iou_threshold: float = 0.65, topk: int = 100, conf: float = 0.35, dedupe_iou: float = 0.45,
-                 coord_mode: str = "trunc", max_crops_per_image: int = 0, crops_capacity: Optional[int] = None):
+                 coord_mode: str = "trunc", max_crops_per_image: int = 0, crops_capacity: Optional[int] = None,
+                 fit_crops: bool = False):
+        """fit_crops (opt-in, __call__ only): read the crop count on the host after the detect stage - one small device-to-host
+        copy, i.e. a synchronisation per call - and run the classifier at fit_capacity(count, capacity) instead of the capacity
+        (B * topk unless max_crops_per_image / crops_capacity say otherwise).  For request-sized calls (inferdet.main on a few
+        images): buffers, grids and GEMM routes then follow the crops there are.  The device count still goes to every kernel, so
+        results do not change; no crops: no classifier launch, cls_logits (0, nc)."""
         if not vits:
             raise YvError("model_list is empty")
         p = {(v.P, v.img) for v in vits}
@@ -32,6 +46,7 @@ class DetectClassifyPipeline:
         self.conf, self.dedupe_iou, self.coord_mode = conf, dedupe_iou, coord_mode
         self.max_crops = max_crops_per_image
         self.capacity = crops_capacity
+        self.fit_crops = bool(fit_crops)
         self.parts = 2                                    # slices whose counts detect_stage publishes (PipelinedRunner: one per stream)
         self._const: Dict[int, dict] = {}
 
@@ -77,6 +92,10 @@ class DetectClassifyPipeline:
         v0 = self.vits[0]
         logits = torch.empty((cap, v0.nc), dtype=torch.float32, device=dev)     # rows past the crop count: 0 / -1, written by the
         labels = torch.empty((cap,), dtype=torch.int32, device=dev)             # head kernel of the first ensemble member
+        if cap == 0:                                                            # fit_crops, no crops: nothing to launch
+            det = dict(det)
+            det.update(cls_logits=logits, cls_label=labels)
+            return det
         w = 1.0 / len(self.vits)                      # ensemble = mean of logits (defined by this build)
         parts = [(0, cap, total, 0, None)]
         if streams is not None and len(streams) >= 2 and cap >= len(streams):
@@ -118,6 +137,8 @@ class DetectClassifyPipeline:
         """images (B,Hn,Wn,3) u8 letterboxed network input (the detector engine's extent); src_images (B,H,W,3) u8 originals
         the crops are taken from (default: `images`, i.e. inputs that already have the network's extent: ratio 1, dwdh 0)."""
         det = self.detect_stage(images, ratio, dwdh, img_wh)
+        if self.fit_crops:                                # crop_list keeps its allocation: classify_stage reads its first rows
+            det["capacity"] = fit_capacity(int(det["crop_total"][0]), det["capacity"])
         return self.classify_stage(images if src_images is None else src_images, det)
 
 
@@ -153,6 +174,10 @@ class PipelinedRunner:
         256 CUs taken the kernels of the other streams (detector, the other half-batch's LayerNorm / attention) can only
         start when a GEMM ends; leaving 48 CUs free lets them run alongside: 8.07 -> 7.75 ms per step measured (208 and 200
         equal, 224 7.85, 192 and below worse again).  None keeps the library default (every CU)."""
+        if getattr(pipe, "fit_crops", False):
+            raise YvError("PipelinedRunner submits the classifier without waiting for the detector; fit_crops reads the crop "
+                          "count on the host between the two stages, which would serialise its streams: build the pipeline "
+                          "with fit_crops=False")
         self.pipe = pipe
         self.gemm_cus = None if gemm_cus is None else int(gemm_cus)
         self.full_cus_from = full_cus_from                         # transformer block from which the GEMMs take every CU again
