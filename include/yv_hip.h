@@ -148,7 +148,7 @@ int yv_wgrad_mxfp8(const void* dYt, long long ldy, const void* sdy, long long dy
                    const void* sx, long long x_rows_pad, int T_pad, int N, int K, float* dW, int ldw, void* stream);
 
 /* Measurement hook (bench.py): the NEXT LDS-DMA GEMM launch issued by the calling thread (yv_linear / yv_linear_ex /
- * yv_linear_nn) records its start / stop timestamps into these hipEvent_t handles through hipExtLaunchKernel, i.e. from
+ * yv_linear_nn; yv_conv2d / yv_conv2d_ws on cgemm_dma_kernel or cgemm_small_kernel) records its start / stop timestamps into these hipEvent_t handles through hipExtLaunchKernel, i.e. from
  * the kernel's own dispatch packet.  Either may be null; the setting is consumed by that launch. */
 int yv_set_launch_timing(void* start_event, void* stop_event);
 /* Registers (ws != NULL) or removes a caller-owned f32 scratch buffer for split-K partial sums used by launches
@@ -361,12 +361,17 @@ int yv_conv2d(const yv_view* in0, const yv_view* in1, int B, int Hout, int Wout,
               const void* weight, const float* bias, int Cout, void* out, int out_ld, const void* res, int res_ld,
               int flags, void* stream);
 
-/* Diagnostic, host only (no HIP call): the route yv_conv2d_ws takes for this shape under the current options, for dense sources
+/* Diagnostic, host only (no HIP call, except that once "conv_small" is set the CU count of the then-current device is queried
+ * and kept for the life of the process - one kind of device per process is assumed; 256 where there is no device):
+ * the route yv_conv2d_ws takes for this shape under the current options, for dense sources
  * (pixel stride = c0 / c1, no upsample - neither changes the route) and base pointers aligned to 16 bytes (a base that is not
  * clears the staged bit and with it every LDS-DMA route); ws_bytes = 0: no workspace (yv_conv2d).  For a batch that is taken in
  * sub-batches, the route of the first one.  Returns a negative YV_ERR_* code where yv_conv2d rejects the arguments, else
  *   bits 0-3  kernel instance: 0 .. 3 igemm_kernel with 128 x 16 / 32 / 64 / 128 tiles;
- *             4 cgemm_dma_kernel<64,4,1,2>, 5 <64,4,1,3>, 6 <64,4,1,4>, 7 <128,2,2,2>, 8 <128,2,2,3>  (<tile width, waves, stages>)
+ *             4 cgemm_dma_kernel<64,4,1,2>, 5 <64,4,1,3>, 6 <64,4,1,4>, 7 <128,2,2,2>, 8 <128,2,2,3>  (<tile width, waves, stages>);
+ *             9 cgemm_small_kernel<64,2>, 10 <32,4>  (<tile rows, K groups>; only with the option "conv_small" > 0: at most that
+ *             many output pixels, 128 x 64 tiles at most "conv_small_fill" eighths of the CU count, eligibility of 4 .. 8; they
+ *             take the direct epilogue, so bit 4 is clear)
  *   bit 4 (16) the staged epilogue runs (see yv_conv2d for what that means for the shortcut's rounding)
  *   bit 5 (32) split-K: partial sums in the workspace, epilogue in the reduce pass
  *   bit 6 (64) the two-source instantiation of igemm_kernel (c1 > 0; the LDS-DMA kernels have no separate one). */

@@ -1,15 +1,19 @@
 #!/usr/bin/env python3
 """Dev tool (GPU box): latency of ONE DetectClassifyPipeline.__call__ at request size - what inferdet.main runs per chunk - for
-YOLOv8n + ViT-B/16 and YOLOv8n + ViT-B/8 at B = 1 and 4 images of 640 x 640 with 1, 3 and 8 detections per image, in four states:
+YOLOv8n + ViT-B/16 and YOLOv8n + ViT-B/8 at B = 1 and 4 images of 640 x 640 with 1, 3 and 8 detections per image, in six states:
   default              the pipeline as it ships (classifier capacity B * topk = 100 B crops);
   fit_crops            DetectClassifyPipeline(fit_crops=True);
   fit_crops+mid_gemm   ... with VitEngine(mid_gemm=True);
-  mid_gemm             VitEngine(mid_gemm=True) alone.
+  mid_gemm             VitEngine(mid_gemm=True) alone;
+  small_maps           YoloEngine(small_maps=True) alone (a sibling of the detector: the same weights);
+  fit+mid+small_maps   ... on top of fit_crops + mid_gemm.
+RB_MODELS (comma-separated classifier names) restricts the classifiers.
 The detector runs on the images (its time is part of the call); the NMS then works on a synthetic candidate set in place of the
 random-weight detector's - 8400 boxes per image by the recipe of bench.py's postproc mode (centres uniform, sides U[16, 256]),
 with exactly d well-separated candidates above the thresholds - so that the crop count is the one asked for.
 The states are interleaved in one process, RB_RUNS (3) runs of RB_CALLS (20) calls each; a call is timed on the host from its
-start to the end of a device synchronisation.  Reported: the median call, the median detect stage alone (same method), and
+start to the end of a device synchronisation.  Reported: the median call, the median detect stage alone (same method, once for
+the unflagged detector and once for the small_maps one; each state is listed with its own detector's), and
 the peak of torch.cuda.max_memory_allocated over a call above what was allocated before the first call of that shape (the
 engines' activation buffers: every engine starts each shape with none)."""
 import gc, os, sys, time
@@ -24,7 +28,9 @@ dev = "cuda:0"
 RUNS = int(os.environ.get("RB_RUNS", 3))
 CALLS = int(os.environ.get("RB_CALLS", 20))
 S, A, NC = 640, 8400, 5
-STATES = [("default", False, False), ("fit_crops", True, False), ("fit_crops+mid_gemm", True, True), ("mid_gemm", False, True)]
+STATES = [("default", False, False, False), ("fit_crops", True, False, False), ("fit_crops+mid_gemm", True, True, False),
+          ("mid_gemm", False, True, False), ("small_maps", False, False, True), ("fit+mid+small_maps", True, True, True)]
+MODELS = [m for m in os.environ.get("RB_MODELS", "vit_base_patch16_224,vit_base_patch8_224").split(",") if m]
 
 
 def candidates(B, d, seed=4321):
@@ -87,21 +93,23 @@ def main():
     print(f"# {'classifier':22s} {'B':>2s} {'dets':>4s} {'crops':>5s}  {'state':20s} {'capacity':>8s} {'call ms':>8s} {'detect ms':>9s} "
           f"{'classify ms':>11s} {'peak MB':>9s}  call / default")
     yolo_sd = engines.init_yolo_state("n", NC, seed=42, head_gain=4.0)
-    yolo = engines.YoloEngine(yolo_sd, "n", NC, S, device=dev)
+    yolo = engines.YoloEngine(yolo_sd, "n", NC, S, device=dev, small_maps=False)
+    yolo_small = yolo.resized(S)
+    yolo_small.small_maps = True
     g = torch.Generator().manual_seed(1234)
-    for name in ("vit_base_patch16_224", "vit_base_patch8_224"):
+    for name in MODELS:
         vit_sd = engines.init_vit_wrapper_state(name, NC, seed=42)
         vits = {mid: engines.VitEngine(vit_sd, name, NC, device=dev, mid_gemm=mid) for mid in (False, True)}
         for B in (1, 4):
             images = torch.randint(0, 256, (B, S, S, 3), generator=g, dtype=torch.uint8).to(dev)
             for d in (1, 3, 8):
                 boxes, scores = candidates(B, d)
-                yolo(images)                                  # the detector's own buffers for this B exist before anything is measured
+                yolo(images); yolo_small(images)              # the detectors' own buffers for this B exist before anything is measured
                 pipes, peak, cap, crops = {}, {}, {}, {}
-                for label, fit, mid in STATES:
-                    pipes[label] = p = DetectClassifyPipeline(yolo, [vits[mid]], fit_crops=fit)
+                for label, fit, mid, small in STATES:
+                    pipes[label] = p = DetectClassifyPipeline(yolo_small if small else yolo, [vits[mid]], fit_crops=fit)
                     with_candidates(p, boxes, scores)
-                for label, fit, mid in STATES:                # memory: each state from engines without activation buffers
+                for label, fit, mid, small in STATES:         # memory: each state from engines without activation buffers
                     for v in vits.values():
                         v._bufs.clear()
                     gc.collect(); torch.cuda.synchronize(); torch.cuda.empty_cache()
@@ -114,18 +122,18 @@ def main():
                     if crops[label] != B * d:
                         print(f"# note: {label}: {crops[label]} crops where {B * d} were injected")
                     del out
-                for label, _, _ in STATES:                    # buffers of every state back in place, then warm
+                for label, *_ in STATES:                      # buffers of every state back in place, then warm
                     wall(lambda: pipes[label](images), 3)
-                call = {label: [] for label, _, _ in STATES}
-                det = []
+                call = {label: [] for label, *_ in STATES}
+                det = {False: [], True: []}
                 for rd in range(RUNS):
-                    for label, _, _ in STATES:
+                    for label, *_ in STATES:
                         call[label] += wall(lambda: pipes[label](images), CALLS)
-                    det += wall(lambda: pipes["default"].detect_stage(images), CALLS)
-                t_det = median(det)
+                    det[False] += wall(lambda: pipes["default"].detect_stage(images), CALLS)
+                    det[True] += wall(lambda: pipes["small_maps"].detect_stage(images), CALLS)
                 t0 = median(call["default"])
-                for label, _, _ in STATES:
-                    t = median(call[label])
+                for label, _, _, small in STATES:
+                    t, t_det = median(call[label]), median(det[small])
                     print(f"  {name:22s} {B:2d} {d:4d} {crops[label]:5d}  {label:20s} {cap[label]:8d} {t:8.3f} {t_det:9.3f} "
                           f"{t - t_det:11.3f} {peak[label]:9.1f}  {t / t0:6.2f}", flush=True)
                 del pipes

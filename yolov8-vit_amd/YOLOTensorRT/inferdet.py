@@ -38,22 +38,37 @@ def _load_rgb(path: str) -> np.ndarray:
     return np.asarray(Image.open(path).convert("RGB"))
 
 
-def _pipeline(Engine, model_list, fit_crops: bool = False) -> DetectClassifyPipeline:
+def _pipeline(Engine, det, model_list, fit_crops: bool = False) -> DetectClassifyPipeline:
     vits = [m.engine() for m in model_list]
-    return DetectClassifyPipeline(Engine.engine, vits, Engine.score_threshold, Engine.iou_threshold, Engine.topk,
+    return DetectClassifyPipeline(det, vits, Engine.score_threshold, Engine.iou_threshold, Engine.topk,
                                   fit_crops=fit_crops)
+
+
+def _detector(Engine, small_maps: Optional[bool]):
+    """Engine.engine, or - where small_maps is given and differs from its flag - its sibling in that state (shared weights, own
+    buffers), built once per Engine and kept on it: later calls reuse its activation buffers."""
+    det = Engine.engine
+    if small_maps is None or bool(small_maps) == det.small_maps:
+        return det
+    sib = getattr(Engine, "_small_maps_sibling", None)
+    if sib is None or sib.w is not det.w or sib.hw != det.hw or sib.small_maps != bool(small_maps):
+        sib = det.resized(det.size)
+        sib.small_maps = bool(small_maps)
+        Engine._small_maps_sibling = sib
+    return sib
 
 
 def _rect_pipeline(Engine, pipe: DetectClassifyPipeline, cache: dict, hw) -> DetectClassifyPipeline:
     """`pipe` with the detector resized to `hw` (shared weights, own buffers); one per shape."""
     if hw not in cache:
-        cache[hw] = DetectClassifyPipeline(Engine.engine.resized(hw), pipe.vits, Engine.score_threshold, Engine.iou_threshold,
+        cache[hw] = DetectClassifyPipeline(pipe.yolo.resized(hw), pipe.vits, Engine.score_threshold, Engine.iou_threshold,
                                            Engine.topk, fit_crops=pipe.fit_crops)
     return cache[hw]
 
 
 def main(Engine, imgs, device=None, model_list: Optional[list] = None, transform=None, aliyunoss=None,
-         func: Optional[Callable] = None, rect: bool = False, fit_crops: Optional[bool] = None):
+         func: Optional[Callable] = None, rect: bool = False, fit_crops: Optional[bool] = None,
+         small_maps: Optional[bool] = None):
     """Detect + classify every image under `imgs` (directory, file or list).  Returns a JSON-serialisable dict
     {"output": [{"image": name, "objects": [{"sort", "det_sort", "confidence", "xmin", "ymin", "xmax", "ymax"}]}]}.
     `transform` is accepted for signature compatibility: its valid_test branch (nearest resize to 224 +
@@ -64,13 +79,16 @@ def main(Engine, imgs, device=None, model_list: Optional[list] = None, transform
     extent (YoloEngine.resized, one engine per shape).  Restored coordinates, crops and the result layout are the same.
     fit_crops=True (None: the environment variable YV_FIT_CROPS, "1" = on): the classifier of each chunk is sized to the crops
     the detector found instead of topk per image (DetectClassifyPipeline(fit_crops=True)): for request-sized calls.  The result
-    is the same dict; classifiers built with mid_gemm=True use their mid-M GEMM, main does not switch it on."""
+    is the same dict; classifiers built with mid_gemm=True use their mid-M GEMM, main does not switch it on.
+    small_maps (None: as the engine was built): the detector of this call runs with YoloEngine(small_maps=) in that state - where
+    it differs from Engine.engine's, on a sibling that shares its weights (YoloEngine.resized), built once and kept on Engine."""
     yvhip.require_gpu()
     if not model_list:
         raise yvhip.YvError("model_list is empty")
     dev = torch.device(device) if device is not None else Engine.device
     S = Engine.size
-    pipe = _pipeline(Engine, model_list, _env_flag(fit_crops, "YV_FIT_CROPS"))
+    det = _detector(Engine, small_maps)
+    pipe = _pipeline(Engine, det, model_list, _env_flag(fit_crops, "YV_FIT_CROPS"))
     if rect and not isinstance(S, int):
         raise yvhip.YvError("rect=True takes a square engine: its size is the long side of every rectangle")
     rect_pipes: dict = {}

@@ -43,9 +43,11 @@ def _guess_scale_nc(sd):
 
 class TRTModule(torch.nn.Module):
     def __init__(self, weight: Union[str, dict], device: Optional[torch.device] = None, size=640,
-                 dtype: str = "bf16") -> None:
+                 dtype: str = "bf16", small_maps: Optional[bool] = None) -> None:
         """size: the network input's side, or its (H, W) (multiples of 32); `inp_info` gives (1, 3, H, W).
-        dtype: "bf16" (default) or "mxfp8" (the detector's eligible convolutions on MXFP8 operands, engines.mx_conv_plan)."""
+        dtype: "bf16" (default) or "mxfp8" (the detector's eligible convolutions on MXFP8 operands, engines.mx_conv_plan).
+        small_maps: YoloEngine(small_maps=): the small-map convolution tiles for request-sized batches (opt-in; None reads
+        YV_YOLO_SMALL_MAPS)."""
         super().__init__()
         self.device = torch.device(device) if device is not None else torch.device('cuda:0')
         if isinstance(weight, dict):
@@ -62,7 +64,8 @@ class TRTModule(torch.nn.Module):
                 raise yvhip.YvError(f"{weight}: expected a YOLOv8 state dict (ultralytics key layout)")
         sd = fold_batchnorm(sd)
         self.scale, self.nc = _guess_scale_nc(sd)
-        self.engine = engines.YoloEngine(sd, self.scale, self.nc, size, device=str(self.device), dtype=dtype)
+        self.engine = engines.YoloEngine(sd, self.scale, self.nc, size, device=str(self.device), dtype=dtype,
+                                         small_maps=small_maps)
         self.size = self.engine.size
         self.inp_info = [Tensor('images', torch.float32, (1, 3, *self.engine.hw))]
         self.out_info = [Tensor('num_dets', torch.int32, (1, 1)), Tensor('bboxes', torch.float32, (1, 100, 4)),

@@ -981,6 +981,88 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_dma_kernel(GemmArgs g) {
 // VALU issue of exactly that gather and staging.  Epilogues: finish_tile (bias, SiLU, bf16 shortcut, f32 output).
 // Eligibility (host): (c0 + c1) % 64 == 0, c1 == 0 or (1 x 1 and c0 % 64 == 0), Cout >= 64, staged epilogue usable.
 // ---------------------------------------------------------------------------------------------
+// ---- device text shared by cgemm_dma_kernel and cgemm_small_kernel ----
+// What lane (lrow, lch) of the wave-instruction that fills tile row r contributes for the whole tile: the byte offset of output
+// pixel m's centre in each source (the upsampled-source shifts applied) + its swizzled 16-byte chunk, and the nine tap-validity
+// bits (none for a row past M: every read of it is out of range, i.e. zeros).
+template <bool PHASE>
+__device__ __forceinline__ void cdma_lane_pixel(const GemmArgs& g, int M, int hw, int m, int r, int lch, uint32_t& off0, uint32_t& off1,
+                                                uint32_t& tap_bits) {
+    const int mc = m < M ? m : M - 1;
+    const int b = mc / hw, rem = mc - b * hw;
+    const int oy = rem / g.Wout;
+    const int cy = oy * g.stride, cx = (rem - oy * g.Wout) * g.stride;
+    const uint32_t sw = (uint32_t)((lch ^ (r & 7)) << 4);
+    off0 = (uint32_t)((((long long)b * (g.Hin >> g.up0) + (cy >> g.up0)) * (g.Win >> g.up0) + (cx >> g.up0)) * g.lda0 * 2) + sw;
+    off1 = g.c1 ? (uint32_t)((((long long)b * (g.Hin >> g.up1) + (cy >> g.up1)) * (g.Win >> g.up1) + (cx >> g.up1)) * g.lda1 * 2) + sw : 0u;
+    uint32_t taps = 0;
+    if (m < M) {
+        if constexpr (PHASE) {
+            taps = phase_taps(g, cy, cx);
+        } else if (g.ksize == 3) {
+#pragma unroll
+            for (int t = 0; t < 9; ++t) {
+                const int iy = cy + t / 3 - 1, ix = cx + t % 3 - 1;
+                taps |= (iy >= 0 && iy < g.Hin && ix >= 0 && ix < g.Win) ? (1u << t) : 0u;
+            }
+        } else {
+            taps = 1u;
+        }
+    }
+    tap_bits = taps;
+}
+// ... and for weight row r of the column tile at n0 (rows past N: the last row, never stored)
+__device__ __forceinline__ uint32_t cdma_lane_weight(const GemmArgs& g, int n0, int r, int lch) {
+    int n = n0 + r;
+    n = n < g.N ? n : g.N - 1;
+    return (uint32_t)(((long long)n * g.K + ((lch ^ (r & 7)) << 3)) * 2);
+}
+// the scalar offset is unsigned: source 0's descriptor starts one row + one pixel before the tensor (3 x 3 only)
+template <bool PHASE>
+__device__ __forceinline__ uint32_t cdma_bias0(const GemmArgs& g) {
+    return !PHASE && g.ksize == 3 ? (uint32_t)((g.Win + 1) * g.lda0 * 2) : 0u;
+}
+// The wave-uniform part of the K step at element kb (not the phase form): the tap whose validity bit gates the lanes and the scalar
+// offset of the step in source 0's descriptor - the tap's pixel displacement + the channel base.  (The second source of a
+// two-source 1 x 1, kb >= g.c0, has tap 0 and the offset (kb - g.c0) * 2 in its own descriptor.)
+// Cin = g.c0 + g.c1 and pad = g.ksize >> 1 are the caller's, computed once per tile.
+__device__ __forceinline__ uint32_t cdma_step0(const GemmArgs& g, int kb, uint32_t bias0, int Cin, int pad, int& tap) {
+    tap = 0;
+    uint32_t so = bias0 + (uint32_t)(kb * 2);
+    if (g.ksize == 3) {
+        tap = g.cin_shift >= 0 ? (kb >> g.cin_shift) : kb / Cin;
+        const int cin = kb - tap * Cin;
+        const int ky = tap >= 6 ? 2 : (tap >= 3 ? 1 : 0), kx = tap - ky * 3;
+        so = bias0 + (uint32_t)((((ky - pad) * g.Win + (kx - pad)) * g.lda0 + cin) * 2);
+    }
+    return so;
+}
+// one 64-deep K step of a wave tile of MF x NF fragments at rows wrow_m of A and wrow_n of W (128-byte rows, chunks swizzled)
+template <int MF, int NF>
+__device__ __forceinline__ void cdma_mfma_step(const unsigned char* A, const unsigned char* W, int wrow_m, int wrow_n, int fr, int fq,
+                                               f32x4 (&acc)[NF][MF]) {
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+        bf16x8 fa[MF], fw[NF];
+        const int kc = ks * 4 + fq;
+#pragma unroll
+        for (int j = 0; j < MF; ++j) {
+            const int rr = wrow_m + j * 16 + fr;
+            fa[j] = *(const bf16x8*)(A + rr * 128 + ((kc ^ (rr & 7)) << 4));
+        }
+#pragma unroll
+        for (int i = 0; i < NF; ++i) {
+            const int rr = wrow_n + i * 16 + fr;
+            fw[i] = *(const bf16x8*)(W + rr * 128 + ((kc ^ (rr & 7)) << 4));
+        }
+#pragma unroll
+        for (int i = 0; i < NF; ++i)
+#pragma unroll
+            for (int j = 0; j < MF; ++j)
+                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fw[i], fa[j], acc[i][j], 0, 0, 0);
+    }
+}
+
 template <int BN, int WM, int WN, int ST = 2 /* LDS stages: ST - 1 K steps of DMA in flight */, bool STATS = false /* as igemm_kernel */,
           bool PHASE = false /* as igemm_kernel */, bool BNBWD = false /* as igemm_kernel */>
 __global__ __launch_bounds__(256) void cgemm_dma_kernel(GemmArgs g) {
@@ -1012,39 +1094,11 @@ __global__ __launch_bounds__(256) void cgemm_dma_kernel(GemmArgs g) {
 #pragma unroll
     for (int j = 0; j < A_INS; ++j) {
         const int r = (j * NW + wave) * 8 + lrow;
-        const int m = m0 + r;
-        const int mc = m < M ? m : M - 1;
-        const int b = mc / hw, rem = mc - b * hw;
-        const int oy = rem / g.Wout;
-        const int cy = oy * g.stride, cx = (rem - oy * g.Wout) * g.stride;
-        const uint32_t sw = (uint32_t)((lch ^ (r & 7)) << 4);
-        a_off0[j] = (uint32_t)((((long long)b * (g.Hin >> g.up0) + (cy >> g.up0)) * (g.Win >> g.up0) + (cx >> g.up0)) * g.lda0 * 2) + sw;
-        a_off1[j] = g.c1 ? (uint32_t)((((long long)b * (g.Hin >> g.up1) + (cy >> g.up1)) * (g.Win >> g.up1) + (cx >> g.up1)) * g.lda1 * 2) + sw : 0u;
-        uint32_t taps = 0;
-        if (m < M) {
-            if constexpr (PHASE) {
-                taps = phase_taps(g, cy, cx);
-            } else if (g.ksize == 3) {
-#pragma unroll
-                for (int t = 0; t < 9; ++t) {
-                    const int iy = cy + t / 3 - 1, ix = cx + t % 3 - 1;
-                    taps |= (iy >= 0 && iy < g.Hin && ix >= 0 && ix < g.Win) ? (1u << t) : 0u;
-                }
-            } else {
-                taps = 1u;
-            }
-        }
-        a_taps[j] = taps;
+        cdma_lane_pixel<PHASE>(g, M, hw, m0 + r, r, lch, a_off0[j], a_off1[j], a_taps[j]);
     }
 #pragma unroll
-    for (int j = 0; j < W_INS; ++j) {
-        const int r = (j * NW + wave) * 8 + lrow;
-        int n = n0 + r;
-        n = n < g.N ? n : g.N - 1;
-        w_off[j] = (uint32_t)(((long long)n * g.K + ((lch ^ (r & 7)) << 3)) * 2);
-    }
-    // the scalar offset is unsigned: source 0's descriptor starts one row + one pixel before the tensor (3 x 3 only)
-    const uint32_t bias0 = !PHASE && g.ksize == 3 ? (uint32_t)((g.Win + 1) * g.lda0 * 2) : 0u;
+    for (int j = 0; j < W_INS; ++j) w_off[j] = cdma_lane_weight(g, n0, (j * NW + wave) * 8 + lrow, lch);
+    const uint32_t bias0 = cdma_bias0<PHASE>(g);
     const auto rs0 = __builtin_amdgcn_make_buffer_rsrc((void*)((const unsigned char*)g.a0 - bias0), 0, 0x7fffffff, 0x00020000);
     const auto rs1 = __builtin_amdgcn_make_buffer_rsrc((void*)(g.c1 ? g.a1 : g.a0), 0, 0x7fffffff, 0x00020000);
     const auto rsW = __builtin_amdgcn_make_buffer_rsrc((void*)g.w, 0, 0x7fffffff, 0x00020000);
@@ -1072,14 +1126,8 @@ __global__ __launch_bounds__(256) void cgemm_dma_kernel(GemmArgs g) {
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rs1, (lptr_t)(A + (j * NW + wave) * 1024), 16,
                                                          (int)((a_taps[j] & 1u) ? a_off1[j] : OOB), so, 0, 0);
         } else {
-            int tap = 0;
-            uint32_t so = bias0 + (uint32_t)(kb * 2);
-            if (g.ksize == 3) {
-                tap = g.cin_shift >= 0 ? (kb >> g.cin_shift) : kb / Cin;
-                const int cin = kb - tap * Cin;
-                const int ky = tap >= 6 ? 2 : (tap >= 3 ? 1 : 0), kx = tap - ky * 3;
-                so = bias0 + (uint32_t)((((ky - pad) * g.Win + (kx - pad)) * g.lda0 + cin) * 2);
-            }
+            int tap;
+            const uint32_t so = cdma_step0(g, kb, bias0, Cin, pad, tap);
 #pragma unroll
             for (int j = 0; j < A_INS; ++j)
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rs0, (lptr_t)(A + (j * NW + wave) * 1024), 16,
@@ -1124,29 +1172,133 @@ __global__ __launch_bounds__(256) void cgemm_dma_kernel(GemmArgs g) {
         const unsigned char* A = smem + slot * (A_BYTES + W_BYTES);
         const unsigned char* W = A + A_BYTES;
         slot = slot + 1 == ST ? 0 : slot + 1;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            bf16x8 fa[MF], fw[NF];
-            const int kc = ks * 4 + fq;
-#pragma unroll
-            for (int j = 0; j < MF; ++j) {
-                const int rr = wrow_m + j * 16 + fr;
-                fa[j] = *(const bf16x8*)(A + rr * 128 + ((kc ^ (rr & 7)) << 4));
-            }
-#pragma unroll
-            for (int i = 0; i < NF; ++i) {
-                const int rr = wrow_n + i * 16 + fr;
-                fw[i] = *(const bf16x8*)(W + rr * 128 + ((kc ^ (rr & 7)) << 4));
-            }
-#pragma unroll
-            for (int i = 0; i < NF; ++i)
-#pragma unroll
-                for (int j = 0; j < MF; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fw[i], fa[j], acc[i][j], 0, 0, 0);
-        }
+        cdma_mfma_step<MF, NF>(A, W, wrow_m, wrow_n, fr, fq, acc);
     }
     asm volatile("s_barrier" ::: "memory");                       // the staged epilogue reuses the tile buffers
     finish_tile<MF, NF, STATS, WM, BN, PHASE, BNBWD>(g, acc, M, m0, n0, wrow_m, wrow_n, lane, wave, smem, tm, ph);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Small-map convolution ("conv_small", off by default): the detector at the one or few images a request
+// carries.  A 20 x 20 map is four 128-row tiles per 64 columns - 8 or 16 workgroups on 256 CUs, each walking 18 K steps alone.
+// Here a workgroup owns BM x 64 outputs and splits K inside itself, as gemm_mid_kernel does for the linears: its 8 waves are KS
+// groups of 8 / KS waves, group q taking the 64-deep K steps q, q + KS, ... into its own two-stage ring.
+//   <64, 2>: two halves x (2 x 2 waves of 32 x 32), 2 x 2 x (64 + 64) rows x 128 B = 64 KB, two workgroups per CU;
+//   <32, 4>: four quarters x (1 x 2 waves of 32 x 32), 4 x 2 x (32 + 64) rows x 128 B = 96 KB, one workgroup per CU.
+// The gather is cgemm_dma_kernel's, by the same device text: per-lane pixel offset and tap bits once per tile, padding through the
+// descriptor's range check, tap displacement / channel base / source of a K step in the DMA's scalar offset.  One barrier per trip
+// (KS K steps), shared by the groups; a group whose step does not exist on the last trip idles through it (K of one step: group 0
+// alone works, the others add zeros).
+// The partial tiles meet in LDS, overlaying the rings after the last barrier: every group writes its four 16 x 16 fragments, and
+// wave w of group q finishes the 4 / KS fragments f = q, q + KS (f = column fragment * 2 + row fragment) of wave tile w as
+// group 0 + group 1 (+ group 2 + group 3), left to right in that order, whichever group the wave belongs to.  All 8 waves then run
+// finish_tile on the sums (the direct epilogue: bias, SiLU, bf16 shortcut, f32 output, channel offset and pixel stride through
+// out / ldo).  One launch, no workspace, no atomics: the result does not depend on the launch.
+// Eligibility (host): cgemm_dma_kernel's.  No STATS, PHASE, BNBWD or MXFP8 form.
+// ---------------------------------------------------------------------------------------------
+template <int BM, int KS>
+__global__ __launch_bounds__(512, KS == 2 ? 2 : 1) void cgemm_small_kernel(GemmArgs g) {
+    constexpr int BN = 64, GW = 8 / KS, WGM = GW / 2;            // waves per group, as WGM x 2 wave tiles of 32 x 32
+    static_assert((KS == 2 || KS == 4) && BM == WGM * 32, "64-row halves or 32-row quarters");
+    constexpr int MF = 2, NF = 2, NS = 4 / KS;                   // fragments of a wave tile; those a wave finishes
+    constexpr int STAGE = (BM + BN) * 128, RING = 2 * STAGE;     // bytes: one K step of a group, a group's two stages
+    constexpr int A_INS = BM / (8 * GW), W_INS = BN / (8 * GW);
+    static_assert(8 * 4 * 64 * 16 <= KS * RING, "the exchange overlays the rings");
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int grp = wave / GW, gw = wave - grp * GW;
+    const int M = g.M;
+    int bid = blockIdx.x;
+    {
+        const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, x = bid & 7;
+        bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
+    }
+    const int tm = bid / g.tiles_n, tn = bid - tm * g.tiles_n;
+    const int m0 = tm * BM, n0 = tn * BN;
+    if (m0 >= M) return;
+
+    // a group's waves fill its stage: 8 rows x 128 B per wave-instruction
+    const int lrow = lane >> 3, lch = lane & 7;
+    constexpr uint32_t OOB = 0x80000000u;
+    uint32_t a_off0[A_INS], a_off1[A_INS], a_taps[A_INS], w_off[W_INS];
+    const int hw = g.Hout * g.Wout;
+#pragma unroll
+    for (int j = 0; j < A_INS; ++j) {
+        const int r = (j * GW + gw) * 8 + lrow;
+        cdma_lane_pixel<false>(g, M, hw, m0 + r, r, lch, a_off0[j], a_off1[j], a_taps[j]);
+    }
+#pragma unroll
+    for (int j = 0; j < W_INS; ++j) w_off[j] = cdma_lane_weight(g, n0, (j * GW + gw) * 8 + lrow, lch);
+    const uint32_t bias0 = cdma_bias0<false>(g);
+    const auto rs0 = __builtin_amdgcn_make_buffer_rsrc((void*)((const unsigned char*)g.a0 - bias0), 0, 0x7fffffff, 0x00020000);
+    const auto rs1 = __builtin_amdgcn_make_buffer_rsrc((void*)(g.c1 ? g.a1 : g.a0), 0, 0x7fffffff, 0x00020000);
+    const auto rsW = __builtin_amdgcn_make_buffer_rsrc((void*)g.w, 0, 0x7fffffff, 0x00020000);
+    const int Cin = g.c0 + g.c1;
+    const int pad = g.ksize >> 1;
+    unsigned char* const ring = smem + grp * RING;
+    auto issue = [&](int kt, int buf) __attribute__((always_inline)) {
+        unsigned char* A = ring + buf * STAGE;
+        unsigned char* W = A + BM * 128;
+        const int kb = kt * BK;                                  // (uniform)
+        if (g.c1 && kb >= g.c0) {                                // second source of a two-source 1 x 1
+            const int so = (kb - g.c0) * 2;
+#pragma unroll
+            for (int j = 0; j < A_INS; ++j)
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rs1, (lptr_t)(A + (j * GW + gw) * 1024), 16,
+                                                         (int)((a_taps[j] & 1u) ? a_off1[j] : OOB), so, 0, 0);
+        } else {
+            int tap;
+            const uint32_t so = cdma_step0(g, kb, bias0, Cin, pad, tap);
+#pragma unroll
+            for (int j = 0; j < A_INS; ++j)
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rs0, (lptr_t)(A + (j * GW + gw) * 1024), 16,
+                                                         (int)(((a_taps[j] >> tap) & 1u) ? a_off0[j] : OOB), (int)so, 0, 0);
+        }
+#pragma unroll
+        for (int j = 0; j < W_INS; ++j)
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsW, (lptr_t)(W + (j * GW + gw) * 1024), 16, (int)w_off[j], kb * 2, 0, 0);
+    };
+
+    f32x4 acc[NF][MF];
+#pragma unroll
+    for (int i = 0; i < NF; ++i)
+#pragma unroll
+        for (int j = 0; j < MF; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    const int wrow_m = (gw >> 1) * 32, wrow_n = (gw & 1) * 32;
+    const int fr = lane & 15, fq = lane >> 4;
+
+    const int nk = g.K / BK, trips = (nk + KS - 1) / KS;         // trip t: K step KS t + grp (the last trip may lack it)
+    if (grp < nk) issue(grp, 0);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    for (int t = 0; t < trips; ++t) {
+        const int cur = t & 1, kt = KS * t + grp;
+        if (kt + KS < nk) issue(kt + KS, cur ^ 1);              // (the stage read on trip t - 1: every wave passed its barrier)
+        if (kt < nk) {
+            const unsigned char* A = ring + cur * STAGE;
+            cdma_mfma_step<MF, NF>(A, A + BM * 128, wrow_m, wrow_n, fr, fq, acc);
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();                                        // (the last one: every fragment read is done, the rings are free)
+    }
+    // exchange: xch[grp][gw][f][lane], f = i * 2 + j, holds fragment (i, j) of that wave's partial tile
+    f32x4* const xch = (f32x4*)smem;
+#pragma unroll
+    for (int i = 0; i < NF; ++i)
+#pragma unroll
+        for (int j = 0; j < MF; ++j) xch[((grp * GW + gw) * 4 + i * 2 + j) * 64 + lane] = acc[i][j];
+    __syncthreads();
+    f32x4 sum[NS][1];
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        const int f = grp + KS * s;
+        f32x4 v = xch[(gw * 4 + f) * 64 + lane];
+#pragma unroll
+        for (int p = 1; p < KS; ++p) v = v + xch[((p * GW + gw) * 4 + f) * 64 + lane];      // group 0 + 1 (+ 2 + 3), in that order
+        sum[s][0] = v;
+    }
+    // f = grp + KS s: row fragment grp & 1, column fragments (grp >> 1) + (KS / 2) s - consecutive for NS = 2 (grp >> 1 = 0)
+    finish_tile<1, NS>(g, sum, M, m0, n0, wrow_m + (grp & 1) * 16, wrow_n + (grp >> 1) * 16, lane, wave, smem);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2219,7 +2371,18 @@ int launch_cdma(GemmArgs& g, hipStream_t st) {
     void (*kern)(GemmArgs) = cgemm_dma_kernel<BN, WM, WN, ST>;
     if (g.stats) kern = g.z ? cgemm_dma_kernel<BN, WM, WN, ST, false, false, true> : cgemm_dma_kernel<BN, WM, WN, ST, true>;
     if (!yv_grant_lds((const void*)kern, lds)) return YV_ERR_LAUNCH;
-    hipLaunchKernelGGL(kern, dim3(g.tiles_m * g.tiles_n), dim3(256), lds, st, g);
+    launch_timed(kern, g.tiles_m * g.tiles_n, 256, lds, st, g);      // (yv_set_launch_timing: tools/conv_small_bench.py)
+    return yv_launch_status();
+}
+
+template <int BM, int KS>
+int launch_csmall(GemmArgs& g, hipStream_t st) {
+    g.tiles_m = (g.M + BM - 1) / BM;
+    g.tiles_n = (g.N + 63) / 64;
+    const size_t lds = KS * 2 * (size_t)(BM + 64) * 128;
+    void (*kern)(GemmArgs) = cgemm_small_kernel<BM, KS>;
+    if (!yv_grant_lds((const void*)kern, lds)) return YV_ERR_LAUNCH;
+    launch_timed(kern, g.tiles_m * g.tiles_n, 512, lds, st, g);
     return yv_launch_status();
 }
 
@@ -2235,16 +2398,58 @@ int launch_cmx(ConvMxArgs& a, hipStream_t st) {       // two LDS stages of 128 +
 // Kernel instances of a convolution (the low four bits of yv_conv2d_instance's code, include/yv_hip.h)
 enum ConvKern {
     CK_IGEMM_16 = 0, CK_IGEMM_32 = 1, CK_IGEMM_64 = 2, CK_IGEMM_128 = 3,              // igemm_kernel<1, 128, BN, ..>
-    CK_CDMA_64_2 = 4, CK_CDMA_64_3 = 5, CK_CDMA_64_4 = 6, CK_CDMA_128_2 = 7, CK_CDMA_128_3 = 8   // cgemm_dma_kernel<BN, .., ST>
+    CK_CDMA_64_2 = 4, CK_CDMA_64_3 = 5, CK_CDMA_64_4 = 6, CK_CDMA_128_2 = 7, CK_CDMA_128_3 = 8,  // cgemm_dma_kernel<BN, .., ST>
+    CK_SMALL_64 = 9, CK_SMALL_32 = 10                                                             // cgemm_small_kernel<BM, KS>
 };
+
+int g_opt_conv_small = 0;           // largest M (output pixels) taken by cgemm_small_kernel ("conv_small"; 0 = the step does not exist)
+int g_opt_conv_small_fill = 5;      // ... where 128 x 64 tiles number at most this many eighths of the CU count ("conv_small_fill")
+constexpr int SMALL_32_BELOW = 128;  // ... on 32-pixel tiles where 64-pixel tiles would number fewer than this, else on 64-pixel tiles
+int g_opt_conv_small_rows = 0;      // ... unless forced: 64 or 32 = that instance for every launch the step takes ("conv_small_rows";
+                                    // tools/conv_small_bench.py and the tests time and check each instance on every shape)
+
+// CU count for the fill rule: that of the device current at the first call, kept for the life of the process (one kind of device
+// per process is assumed); 256 where no device is present (a route query on a host without one)
+int conv_cus() {
+    static int n_cu = 0;
+    if (!n_cu) {
+        int dev = 0; hipDeviceProp_t prop;
+        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) { (void)hipGetLastError(); return 256; }
+        n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    }
+    return n_cu;
+}
 
 int igemm_pick(int N) { return N > 64 ? CK_IGEMM_128 : (N > 32 ? CK_IGEMM_64 : (N > 16 ? CK_IGEMM_32 : CK_IGEMM_16)); }
 
 // The route of one convolution launch: ONE rule for conv_impl_one (which launches it) and yv_conv2d_instance (which reports it).
 // Reads the shape, flags, strides and base pointers of g; writes g.staged and g.splitk (g.partial is the caller's) and returns the
-// kernel instance.
-int conv_route(GemmArgs& g, bool have_ws, size_t ws_bytes) {
+// kernel instance.  sums: a yv_conv2d_stats / yv_conv2d_bnbwd call (g.stats / g.z) or a query on the trainer's behalf, which keep
+// their route whatever "conv_small" says.
+int conv_route(GemmArgs& g, bool have_ws, size_t ws_bytes, bool sums) {
     g.staged = g_opt_staged && epi_can_stage(g);
+    const int Cin = g.c0 + g.c1;
+    // what cgemm_dma_kernel and cgemm_small_kernel ask of a layer
+    const bool dma_ok = g.N >= 64 && (Cin % 64) == 0 && (g.c1 == 0 || (g.ksize == 1 && (g.c0 % 64) == 0)) && g.staged && !g.m_dev &&
+                        (g.K % BK) == 0;
+    // small maps ("conv_small", off by default): the detector at a request's one or few images.  Ahead of
+    // split-K and of the "conv_dma" rule, as step 2a of linear_route is ahead of its split-K.  Measured
+    // (tools/conv_small_bench.py, profiles/conv_small_layers.txt: every eligible layer of YOLOv8n / s at 1, 2, 4 images of 640 x 640
+    // and one of 384 x 640): up to 150 tiles of 128 x 64 every layer takes x 0.46 - 0.86 of cgemm_dma_kernel<64, 4, 1, 3>'s time on
+    // the instance chosen below; at 200 tiles the 64-pixel instance takes x 0.85 - 1.04, at 300 x 1.10, at 400 x 1.24 - 1.35.  Hence
+    // "conv_small_fill" = 5 (at most 5/8 of a 128 x 64 tile per CU: 160 on 256 CUs; the 200-tile layers stay on the parent's
+    // route), and engines.SMALL_MAP_PIXELS = 12,800, the largest M of a layer inside that count.  The 32-pixel tiles where 64-pixel
+    // tiles would number fewer than 128: up to 120 such tiles they are the faster instance on all but a few layers (x 0.46 - 0.82
+    // against x 0.59 - 0.85), from 150 on the slower one (x 0.83 - 0.90 against x 0.70 - 0.72; at 200, x 0.86 - 1.19 against x 0.67 - 0.86).
+    if (g_opt_conv_small > 0 && !sums && dma_ok && g.M <= g_opt_conv_small) {
+        const long long cols = (g.N + 63) / 64;
+        const long long tiles128 = (long long)((g.M + 127) / 128) * cols, tiles64 = (long long)((g.M + 63) / 64) * cols;
+        if (tiles128 * 8 <= (long long)g_opt_conv_small_fill * conv_cus()) {
+            g.splitk = 1;
+            if (g_opt_conv_small_rows == 64 || g_opt_conv_small_rows == 32) return g_opt_conv_small_rows == 32 ? CK_SMALL_32 : CK_SMALL_64;
+            return tiles64 < SMALL_32_BELOW ? CK_SMALL_32 : CK_SMALL_64;
+        }
+    }
     // split-K: deep small-resolution layers (20x20 / 40x40 maps) give 100-400 tiles for 256 CUs and a serial chain of
     // 9-36 K steps per tile at one workgroup per CU; slicing K puts >= 2 workgroups on every CU and shortens the chain
     g.splitk = 1;
@@ -2257,10 +2462,7 @@ int conv_route(GemmArgs& g, bool have_ws, size_t ws_bytes) {
         if (S > 8) S = 8;
         if (S >= 2 && (size_t)S * g.M * g.N * sizeof(float) <= ws_bytes && !(g.N & 3)) g.splitk = S;
     }
-    const int Cin = g.c0 + g.c1;
-    if (g_opt_conv_dma && g.N >= 64 && (Cin % 64) == 0 && (g.c1 == 0 || (g.ksize == 1 && (g.c0 % 64) == 0)) && g.staged &&
-        g.splitk <= 1 && !g.m_dev && (g.K % BK) == 0)
-    {
+    if (g_opt_conv_dma && dma_ok && g.splitk <= 1) {
         // conv_dma: 1 = two stages (128-wide tiles for Cout > 64), 2 = three stages, 64-wide tiles (two workgroups per CU, four K
         // steps in flight per CU), 3 = three stages, 128-wide tiles (one workgroup per CU), 4 = four stages, 64-wide tiles,
         // 5 .. 8 mixtures.  Shipped: 8 = three stages / 64-wide, except the 128-channel layers of the large maps (>= 100 k output
@@ -2300,6 +2502,8 @@ int launch_conv(GemmArgs& g, int kern, hipStream_t st) {
     case CK_CDMA_64_4: return launch_cdma<64, 4, 1, 4>(g, st);
     case CK_CDMA_128_2: return launch_cdma<128, 2, 2, 2>(g, st);
     case CK_CDMA_128_3: return launch_cdma<128, 2, 2, 3>(g, st);
+    case CK_SMALL_64: return launch_csmall<64, 2>(g, st);
+    case CK_SMALL_32: return launch_csmall<32, 4>(g, st);
     default: return launch_igemm<1>(g, kern, st);
     }
 }
@@ -2364,10 +2568,11 @@ int launch_dgrad_s2(GemmArgs& g, int kern, hipStream_t st) {
 }
 
 // the code yv_conv2d_instance documents: the staged bit is set where the staged epilogue RUNS (finish_tile takes it on the 64-column
-// wave tiles only, and a split-K launch leaves the epilogue to splitk_reduce_kernel)
+// wave tiles only, and a split-K launch leaves the epilogue to splitk_reduce_kernel; cgemm_small_kernel's 32-column wave tiles take
+// the direct one)
 int conv_instance_code(const GemmArgs& g, int kern) {
     const bool split = g.splitk > 1;
-    const bool staged = g.staged && !split && kern >= CK_IGEMM_64;
+    const bool staged = g.staged && !split && kern >= CK_IGEMM_64 && kern < CK_SMALL_64;
     const bool two = g.c1 > 0 && kern <= CK_IGEMM_128;
     return kern | (staged ? 16 : 0) | (split ? 32 : 0) | (two ? 64 : 0);
 }
@@ -2784,6 +2989,9 @@ static const struct { const char* key; int* (*at)(); } k_options[] = {
     {"linear_mid_fill", [] { return &g_opt_mid_fill; }},
     {"wgrad_mx_split", [] { return &g_opt_wgrad_mx_split; }},
     {"conv_dma", [] { return &g_opt_conv_dma; }},
+    {"conv_small", [] { return &g_opt_conv_small; }},
+    {"conv_small_fill", [] { return &g_opt_conv_small_fill; }},
+    {"conv_small_rows", [] { return &g_opt_conv_small_rows; }},
     {"dgrad_s2_split", [] { return &g_opt_dgrad_s2_split; }},
 };
 static int* option_at(const char* key) {
@@ -2904,7 +3112,8 @@ static int conv_impl_one(const yv_view* in0, const yv_view* in1, int B, int Hout
                          const void* weight, const float* bias, int Cout, void* out, int out_ld, const void* res,
                          int res_ld, int flags, void* ws, size_t ws_bytes, void* stream, bool query = false,
                          float* stats = nullptr /* yv_conv2d_stats / _bnbwd: the tile partials; never split-K */,
-                         const BnBwdOps* bb = nullptr /* yv_conv2d_bnbwd: the sums are the BatchNorm backward's */) {
+                         const BnBwdOps* bb = nullptr /* yv_conv2d_bnbwd: the sums are the BatchNorm backward's */,
+                         bool trainer = false /* a query for the trainer's plain call, which never sets "conv_small" */) {
     if (!in0 || !in0->ptr || !weight || !out || B <= 0 || Hout <= 0 || Wout <= 0 || Cout <= 0) return YV_ERR_ARG;
     if (!(ksize == 1 || ksize == 3) || !(stride == 1 || stride == 2)) return YV_ERR_ARG;
     if (in1 && in1->ptr && ksize != 1) return YV_ERR_ARG;
@@ -2934,7 +3143,7 @@ static int conv_impl_one(const yv_view* in0, const yv_view* in1, int B, int Hout
     g.w = (const uint16_t*)weight; g.bias = bias;
     g.M = B * Hout * Wout; g.N = Cout; g.K = ksize * ksize * Cin;
     g.out = out; g.ldo = out_ld; g.res = (const uint16_t*)res; g.ldres = res_ld; g.flags = flags;
-    const int kern = conv_route(g, ws != nullptr && !stats, ws_bytes);
+    const int kern = conv_route(g, ws != nullptr && !stats, ws_bytes, stats != nullptr || bb != nullptr || trainer);
     if (query) return conv_instance_code(g, kern);                // yv_conv2d_instance: the route, no launch
     if (g.splitk > 1) g.partial = (float*)ws;
     g.stats = stats;
@@ -3203,8 +3412,9 @@ extern "C" int yv_conv2d_bnbwd_route(int B, int Hout, int Wout, int ksize, int s
                                   flags, ws_bytes ? dummy : nullptr, ws_bytes, nullptr, true, (float*)dummy);
     if (own < 0) return own;
     if (!conv_one_batch(&v, B, Hout, Wout, stride)) return YV_ERR_LIMIT;
+    // (the unfused call is the trainer's, which never sets "conv_small": its route is asked with the step absent)
     const int plain = conv_impl_one(&v, nullptr, B, Hout, Wout, ksize, stride, dummy, (const float*)dummy, Cout, dummy, out_ld, res,
-                                    res_ld, flags, ws_bytes ? dummy : nullptr, ws_bytes, nullptr, true);
+                                    res_ld, flags, ws_bytes ? dummy : nullptr, ws_bytes, nullptr, true, nullptr, nullptr, true);
     if (plain < 0) return plain;
     const int kern = own & 15, bn = (kern == CK_IGEMM_128 || kern >= CK_CDMA_128_2) ? 128 : (kern == CK_IGEMM_32 ? 32 : (kern == CK_IGEMM_16 ? 16 : 64));
     const long long tiles = ((long long)B * Hout * Wout + 127) / 128;

@@ -604,6 +604,7 @@ def transpose_bf16_batched(src: torch.Tensor, dst: torch.Tensor, rows: int, cols
 # ------------------------------------------------------------- dense math
 EPI_BIAS, EPI_SILU, EPI_GELU, EPI_RES_F32, EPI_RES_BF16, EPI_OUT_F32, EPI_POSEMB = 1, 2, 4, 8, 16, 32, 64
 LINEAR_HOOK = None      # callable(M, N, K, start_event, end_event) or None
+CONV_HOOK = None        # the same for conv2d (tools/conv_small_bench.py): the LDS-DMA routes attach the events, igemm_kernel's do not
 
 
 _HIP = None
@@ -743,10 +744,17 @@ def conv2d(in0: "yv_view", in1: Optional["yv_view"], B: int, Hout: int, Wout: in
     optr = C.c_void_p(out.data_ptr() + esz * out_c_off)
     rptr = None if res is None else C.c_void_p(res.data_ptr() + 2 * res_c_off)
     ws = _conv_workspace(out.device)
+    hook = CONV_HOOK
+    if hook is not None:
+        e0, e1 = _timing_event(), _timing_event()
+        check(lib.yv_set_launch_timing(e0.handle, e1.handle), "yv_set_launch_timing")
     check(lib.yv_conv2d_ws(C.byref(in0), C.byref(in1) if in1 is not None else None, B, Hout, Wout, ksize, stride,
                            _p(weight), _p(bias), Cout, optr, out.shape[-1], rptr,
                            0 if res is None else res.shape[-1], flags | EPI_BIAS, _p(ws), ws.numel() * 4, _st()),
           "yv_conv2d_ws")
+    if hook is not None:
+        lib.yv_set_launch_timing(None, None)             # not consumed where the call took igemm_kernel or split K
+        hook(B * Hout * Wout, Cout, e0, e1)
     return out
 
 
@@ -754,6 +762,7 @@ CONV_WS_BYTES = 16 * 1024 * 1024 * 4      # the workspace conv2d passes (what co
 # conv2d_instance codes: kernel instance in the low four bits ...
 CONV_IGEMM_16, CONV_IGEMM_32, CONV_IGEMM_64, CONV_IGEMM_128 = 0, 1, 2, 3
 CONV_DMA_64_2, CONV_DMA_64_3, CONV_DMA_64_4, CONV_DMA_128_2, CONV_DMA_128_3 = 4, 5, 6, 7, 8
+CONV_SMALL_64, CONV_SMALL_32 = 9, 10      # cgemm_small_kernel<64, 2> / <32, 4>: only under the option "conv_small"
 # ... and flag bits: the staged epilogue runs, split-K, the two-source igemm instantiation
 CONV_STAGED, CONV_SPLITK, CONV_TWO = 16, 32, 64
 

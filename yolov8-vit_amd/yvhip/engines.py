@@ -248,6 +248,14 @@ def mx_conv_plan(scale: str, nc: int = 5, speed_filter: bool = True, min_width: 
     return out
 
 
+SMALL_MAP_PIXELS = 12800   # "conv_small" of a YoloEngine(small_maps=True) pass: the bound measured in DESIGN.md section 32
+
+
+def _env_flag(value: Optional[bool], var: str) -> bool:
+    """An opt-in constructor flag: the argument where one is given, else the environment variable `var` ("1" = on, unset = off)."""
+    return os.environ.get(var, "0") == "1" if value is None else bool(value)
+
+
 def _khwc(w: torch.Tensor) -> torch.Tensor:
     """(Cout,Cin,k,k) f32 -> (Cout, k*k*Cin) bf16 with K order (ky,kx,cin)."""
     co = w.shape[0]
@@ -258,17 +266,23 @@ class YoloEngine:
     """images (B,H,W,3) u8 RGB on the device -> boxes (B,A,4) f32 xyxy, scores (B,A,nc) f32."""
 
     def __init__(self, state: Dict[str, torch.Tensor], scale: str = "n", nc: int = 5, size=640,
-                 device: str = "cuda:0", dtype: str = "bf16"):
+                 device: str = "cuda:0", dtype: str = "bf16", small_maps: Optional[bool] = None):
         """size: the network input's side, or its (H, W); both sides multiples of 32.  `hw` is always (H, W); `size` is the int
         of a square engine and the pair of a rectangular one.  The launch list does not depend on the extent.
         dtype "bf16" (default) or "mxfp8": the convolutions of mx_conv_plan(scale, nc) then run on OCP e4m3 operands with
         one E8M0 scale per 32 input channels (yv_conv2d_mxfp8; weights quantised once here), their inputs kept as MX maps
-        next to the bf16 activations; the rest of the network is unchanged."""
+        next to the bf16 activations; the rest of the network is unchanged.
+        small_maps (opt-in, both dtypes): the pass runs with the option "conv_small" at SMALL_MAP_PIXELS, so its bf16 convolutions
+        with 64-aligned channels on maps of at most that many output pixels - the lower levels at the one or few images a request
+        carries - take cgemm_small_kernel's 64- / 32-pixel tiles; the option is restored afterwards.  None:
+        the environment variable YV_YOLO_SMALL_MAPS ("1" = on, unset = off).  Off: the option is not touched.  The launch list
+        and the MXFP8 convolutions are the same either way."""
         require_gpu()
         hw = net_hw(size)
         if dtype not in ("bf16", "mxfp8"):
             raise YvError("dtype must be 'bf16' or 'mxfp8'")
         self.dtype = dtype
+        self.small_maps = _env_flag(small_maps, "YV_YOLO_SMALL_MAPS")
         self.scale, self.nc, self.dev = scale, nc, torch.device(device)
         self.layers = yolo_layers(scale)
         self.w: Dict[str, torch.Tensor] = {}
@@ -324,7 +338,8 @@ class YoloEngine:
 
     def resized(self, size) -> "YoloEngine":
         """A sibling engine for another input extent (an int or (H, W)): it shares this engine's weight, bias, MX weight and
-        tail-operand tensors (nothing is uploaded or quantised again) and has buffers and a StepGuard of its own."""
+        tail-operand tensors (nothing is uploaded or quantised again) and has buffers and a StepGuard of its own.  It keeps the
+        small_maps flag."""
         hw = net_hw(size)
         sib = object.__new__(type(self))
         sib.__dict__.update(self.__dict__)
@@ -396,6 +411,16 @@ class YoloEngine:
             return tuple([t.clone() for t in part] for part in res)
 
     def _forward_raw(self, images: torch.Tensor, tail: bool = True):
+        if not self.small_maps:
+            return self._launch_list(images, tail)
+        small = get_option("conv_small")
+        set_option("conv_small", SMALL_MAP_PIXELS)
+        try:
+            return self._launch_list(images, tail)
+        finally:
+            set_option("conv_small", small)
+
+    def _launch_list(self, images: torch.Tensor, tail: bool = True):
         """Walks detect_launches (self.fused_c2f is read here, so it may be flipped between calls).  tail=False: stop in front of
         the last 1 x 1 convolutions and return the per-scale feature buffers (B,Hs,Ws,c2+c3)."""
         if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[-1] != 3:
@@ -439,11 +464,6 @@ VIT_CFGS = {
 
 
 MID_GEMM_ROWS = 3152      # "linear_mid" of a VitEngine(mid_gemm=True) pass: the bound measured in DESIGN.md section 31
-
-
-def _env_flag(value: Optional[bool], var: str) -> bool:
-    """An opt-in constructor flag: the argument where one is given, else the environment variable `var` ("1" = on, unset = off)."""
-    return os.environ.get(var, "0") == "1" if value is None else bool(value)
 
 
 def vit_cfg(name: str):
