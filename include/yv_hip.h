@@ -148,7 +148,8 @@ int yv_wgrad_mxfp8(const void* dYt, long long ldy, const void* sdy, long long dy
                    const void* sx, long long x_rows_pad, int T_pad, int N, int K, float* dW, int ldw, void* stream);
 
 /* Measurement hook (bench.py): the NEXT LDS-DMA GEMM launch issued by the calling thread (yv_linear / yv_linear_ex /
- * yv_linear_nn; yv_conv2d / yv_conv2d_ws on cgemm_dma_kernel or cgemm_small_kernel) records its start / stop timestamps into these hipEvent_t handles through hipExtLaunchKernel, i.e. from
+ * yv_linear_nn; yv_conv2d / yv_conv2d_ws on cgemm_dma_kernel or cgemm_small_kernel; the first such launch of yv_conv2d_group,
+ * grouped or single) records its start / stop timestamps into these hipEvent_t handles through hipExtLaunchKernel, i.e. from
  * the kernel's own dispatch packet.  Either may be null; the setting is consumed by that launch. */
 int yv_set_launch_timing(void* start_event, void* stop_event);
 /* Registers (ws != NULL) or removes a caller-owned f32 scratch buffer for split-K partial sums used by launches
@@ -377,6 +378,52 @@ int yv_conv2d(const yv_view* in0, const yv_view* in1, int B, int Hout, int Wout,
  *   bit 6 (64) the two-source instantiation of igemm_kernel (c1 > 0; the LDS-DMA kernels have no separate one). */
 int yv_conv2d_instance(int B, int Hout, int Wout, int ksize, int stride, int c0, int c1, int Cout, int out_ld, int res_ld,
                        int flags, size_t ws_bytes);
+
+/* Grouped convolution launch (opt-in: YoloEngine(grouped_head=True)): n independent yv_conv2d problems,
+ * the eligible ones as ONE grid per kernel instance.  A member is the argument list of yv_conv2d (in1.ptr null: one source). */
+#define YV_CONV_GROUP_MAX 8   /* members of one grouped launch: their descriptors travel in the 4 KB kernel-argument segment */
+typedef struct yv_conv2d_desc {
+    yv_view in0, in1;
+    int B, Hout, Wout, ksize, stride;
+    const void* weight;
+    const float* bias;
+    int Cout;
+    void* out;
+    int out_ld;
+    const void* res;
+    int res_ld;
+    int flags;
+} yv_conv2d_desc;
+
+/* Runs the n members.  Each member is routed as yv_conv2d routes it alone (no workspace, hence never split-K) under the current
+ * options.  Members on cgemm_dma_kernel<64,4,1,3>, cgemm_small_kernel<64,2> or cgemm_small_kernel<32,4> (instance 5, 9, 10 of
+ * yv_conv2d_instance) that yv_conv2d would not take in sub-batches are eligible: per instance they are ordered by descending work
+ * (tiles x K steps) and issued YV_CONV_GROUP_MAX at a time as one launch each, a single leftover member as its ordinary launch.
+ * Every other member (igemm_kernel, the 128-wide tiles, a sub-batched call) is then launched alone, in the order given.
+ * yv_conv2d_group_plan reports the partition.
+ * Each member's output is, bit for bit, what yv_conv2d writes for that member alone under the same options.
+ * The argument rules are yv_conv2d's, per member, and all are checked before anything is launched: the first member that breaks
+ * one gives its code and nothing has run.  n <= 0, a null d, or two members with the same `out` pointer: YV_ERR_ARG.  Beyond that
+ * it is the CALLER's contract that no member reads (source, residual) what another member writes, and that no two members'
+ * outputs overlap: the members run concurrently, in no order. */
+int yv_conv2d_group(const yv_conv2d_desc* d, int n, void* stream);
+
+/* Host only, in the manner of yv_conv2d_instance (nothing is dereferenced or launched; works without a device): the partition
+ * yv_conv2d_group makes of n members of these shapes (dense sources, 16-byte aligned bases, distinct outputs) under the current
+ * options, decided by the function yv_conv2d_group itself uses.  out[i] describes member i. */
+typedef struct yv_conv2d_shape {
+    int B, Hout, Wout, ksize, stride, c0, c1, Cout, out_ld, res_ld, flags;
+} yv_conv2d_shape;
+typedef struct yv_conv2d_group_plan_t {
+    int launch;     /* index of the launch that runs the member, in issue order: the grouped launches first, then the single ones */
+    int instance;   /* the member's yv_conv2d_instance code (ws_bytes = 0) */
+    int first_wg;   /* its first workgroup in that launch's grid, a multiple of 8 (0 for a member launched alone) */
+    int position;   /* its position among the members of that launch (descending work) */
+    int work;       /* tiles x K steps of the member on its instance */
+} yv_conv2d_group_plan_t;
+/* Returns YV_OK and fills out[0 .. n) and *n_launches (a member yv_conv2d takes in sub-batches counts as one launch), or the
+ * YV_ERR_* code with which yv_conv2d_group would reject the arguments. */
+int yv_conv2d_group_plan(const yv_conv2d_shape* shapes, int n, yv_conv2d_group_plan_t* out, int* n_launches);
 
 /* MXFP8 convolutions (BASELINE.json configs[4]: FP8 detector convolutions; opt-in, YoloEngine(dtype="mxfp8")).
  * An "MX map" is an NHWC activation in the operand format of the block-scaled MFMA: e4m3 bytes q (B,H,W,ld) and one E8M0

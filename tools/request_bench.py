@@ -1,21 +1,25 @@
 #!/usr/bin/env python3
 """Dev tool (GPU box): latency of ONE DetectClassifyPipeline.__call__ at request size - what inferdet.main runs per chunk - for
-YOLOv8n + ViT-B/16 and YOLOv8n + ViT-B/8 at B = 1 and 4 images of 640 x 640 with 1, 3 and 8 detections per image, in six states:
+YOLOv8n + ViT-B/16 and YOLOv8n + ViT-B/8 at B = 1 and 4 images of 640 x 640 with 1, 3 and 8 detections per image, in eight states:
   default              the pipeline as it ships (classifier capacity B * topk = 100 B crops);
   fit_crops            DetectClassifyPipeline(fit_crops=True);
   fit_crops+mid_gemm   ... with VitEngine(mid_gemm=True);
   mid_gemm             VitEngine(mid_gemm=True) alone;
   small_maps           YoloEngine(small_maps=True) alone (a sibling of the detector: the same weights);
-  fit+mid+small_maps   ... on top of fit_crops + mid_gemm.
+  fit+mid+small_maps   ... on top of fit_crops + mid_gemm;
+  grouped_head         YoloEngine(grouped_head=True) alone (likewise a sibling);
+  fit+mid+small_maps+grouped   every switch.
 RB_MODELS (comma-separated classifier names) restricts the classifiers.
 The detector runs on the images (its time is part of the call); the NMS then works on a synthetic candidate set in place of the
 random-weight detector's - 8400 boxes per image by the recipe of bench.py's postproc mode (centres uniform, sides U[16, 256]),
 with exactly d well-separated candidates above the thresholds - so that the crop count is the one asked for.
 The states are interleaved in one process, RB_RUNS (3) runs of RB_CALLS (20) calls each; a call is timed on the host from its
-start to the end of a device synchronisation.  Reported: the median call, the median detect stage alone (same method, once for
-the unflagged detector and once for the small_maps one; each state is listed with its own detector's), and
-the peak of torch.cuda.max_memory_allocated over a call above what was allocated before the first call of that shape (the
-engines' activation buffers: every engine starts each shape with none)."""
+start to the end of a device synchronisation.  Reported: the median call; the median detect stage alone (same method, once for
+each detector - unflagged, small_maps, grouped_head, both - and each state is listed with its own detector's); the launches of one
+detect stage, DERIVED, not observed: the entries of the detector's launch list, a ConvGroup entry counted as the launches that
+yvhip.conv2d_group_plan - the partition function of the launch itself - reports for it under the pass's options, plus the tail's
+one; and the peak of torch.cuda.max_memory_allocated over a call above what was allocated before the first call of that shape
+(the engines' activation buffers: every engine starts each shape with none)."""
 import gc, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "yolov8-vit_amd"))
@@ -28,8 +32,12 @@ dev = "cuda:0"
 RUNS = int(os.environ.get("RB_RUNS", 3))
 CALLS = int(os.environ.get("RB_CALLS", 20))
 S, A, NC = 640, 8400, 5
-STATES = [("default", False, False, False), ("fit_crops", True, False, False), ("fit_crops+mid_gemm", True, True, False),
-          ("mid_gemm", False, True, False), ("small_maps", False, False, True), ("fit+mid+small_maps", True, True, True)]
+# (label, fit_crops, mid_gemm, (small_maps, grouped_head))
+STATES = [("default", False, False, (False, False)), ("fit_crops", True, False, (False, False)),
+          ("fit_crops+mid_gemm", True, True, (False, False)), ("mid_gemm", False, True, (False, False)),
+          ("small_maps", False, False, (True, False)), ("fit+mid+small_maps", True, True, (True, False)),
+          ("grouped_head", False, False, (False, True)), ("fit+mid+small_maps+grouped", True, True, (True, True))]
+DETECTORS = [(False, False), (True, False), (False, True), (True, True)]
 MODELS = [m for m in os.environ.get("RB_MODELS", "vit_base_patch16_224,vit_base_patch8_224").split(",") if m]
 
 
@@ -72,6 +80,27 @@ def median(v):
     return v[len(v) // 2]
 
 
+def detect_launch_count(eng, B):
+    """Launches of one detect stage of `eng` at B images: see the module text."""
+    H, W = eng.hw
+    tail = not eng.fused_tail
+    old = yvhip.get_option("conv_small")
+    if eng.small_maps:
+        yvhip.set_option("conv_small", engines.SMALL_MAP_PIXELS)
+    try:
+        n = 1                                                  # detect_tail / detect_decode
+        for e in engines.detect_launches(eng.scale, eng.nc, True, tail, eng.grouped_head):
+            if type(e) is engines.ConvGroup:
+                bufs = eng._buffers(B)["flat"]
+                n += yvhip.conv2d_group_plan([(B, H // c.down, W // c.down, c.k, c.stride, c.srcs[0][2], 0, c.cout,
+                                               bufs[c.out].shape[-1], 0, c.flags) for c in e.convs])[0]
+            else:
+                n += 1
+    finally:
+        yvhip.set_option("conv_small", old)
+    return n
+
+
 def trace_one():
     """--trace: two default-state calls (B = 1, 3 detections, ViT-B/16) and nothing else, for a kernel trace of the default path
     (rocprofv3 --kernel-trace -- python tools/request_bench.py --trace); uses nothing that an earlier commit lacks."""
@@ -91,11 +120,13 @@ def main():
     print(f"# {torch.cuda.get_device_name(0)}; ms per call, median of {RUNS} x {CALLS} calls, states interleaved; "
           f"memory: peak above the allocation before the shape's first call")
     print(f"# {'classifier':22s} {'B':>2s} {'dets':>4s} {'crops':>5s}  {'state':20s} {'capacity':>8s} {'call ms':>8s} {'detect ms':>9s} "
-          f"{'classify ms':>11s} {'peak MB':>9s}  call / default")
+          f"{'classify ms':>11s} {'peak MB':>9s}  call / default  detect launches (derived from the launch list and conv2d_group_plan, not observed)")
     yolo_sd = engines.init_yolo_state("n", NC, seed=42, head_gain=4.0)
     yolo = engines.YoloEngine(yolo_sd, "n", NC, S, device=dev, small_maps=False)
-    yolo_small = yolo.resized(S)
-    yolo_small.small_maps = True
+    dets = {}
+    for small, grouped in DETECTORS:
+        dets[(small, grouped)] = e = yolo if not (small or grouped) else yolo.resized(S)
+        e.small_maps, e.grouped_head = small, grouped
     g = torch.Generator().manual_seed(1234)
     for name in MODELS:
         vit_sd = engines.init_vit_wrapper_state(name, NC, seed=42)
@@ -104,12 +135,13 @@ def main():
             images = torch.randint(0, 256, (B, S, S, 3), generator=g, dtype=torch.uint8).to(dev)
             for d in (1, 3, 8):
                 boxes, scores = candidates(B, d)
-                yolo(images); yolo_small(images)              # the detectors' own buffers for this B exist before anything is measured
+                for e in dets.values():                       # the detectors' own buffers for this B exist before anything is measured
+                    e(images)
                 pipes, peak, cap, crops = {}, {}, {}, {}
-                for label, fit, mid, small in STATES:
-                    pipes[label] = p = DetectClassifyPipeline(yolo_small if small else yolo, [vits[mid]], fit_crops=fit)
+                for label, fit, mid, which in STATES:
+                    pipes[label] = p = DetectClassifyPipeline(dets[which], [vits[mid]], fit_crops=fit)
                     with_candidates(p, boxes, scores)
-                for label, fit, mid, small in STATES:         # memory: each state from engines without activation buffers
+                for label, fit, mid, which in STATES:         # memory: each state from engines without activation buffers
                     for v in vits.values():
                         v._bufs.clear()
                     gc.collect(); torch.cuda.synchronize(); torch.cuda.empty_cache()
@@ -125,17 +157,18 @@ def main():
                 for label, *_ in STATES:                      # buffers of every state back in place, then warm
                     wall(lambda: pipes[label](images), 3)
                 call = {label: [] for label, *_ in STATES}
-                det = {False: [], True: []}
+                det = {which: [] for which in DETECTORS}
+                first = {which: next(label for label, _, _, w in STATES if w == which) for which in DETECTORS}
                 for rd in range(RUNS):
                     for label, *_ in STATES:
                         call[label] += wall(lambda: pipes[label](images), CALLS)
-                    det[False] += wall(lambda: pipes["default"].detect_stage(images), CALLS)
-                    det[True] += wall(lambda: pipes["small_maps"].detect_stage(images), CALLS)
+                    for which in DETECTORS:
+                        det[which] += wall(lambda: pipes[first[which]].detect_stage(images), CALLS)
                 t0 = median(call["default"])
-                for label, _, _, small in STATES:
-                    t, t_det = median(call[label]), median(det[small])
+                for label, _, _, which in STATES:
+                    t, t_det = median(call[label]), median(det[which])
                     print(f"  {name:22s} {B:2d} {d:4d} {crops[label]:5d}  {label:20s} {cap[label]:8d} {t:8.3f} {t_det:9.3f} "
-                          f"{t - t_det:11.3f} {peak[label]:9.1f}  {t / t0:6.2f}", flush=True)
+                          f"{t - t_det:11.3f} {peak[label]:9.1f}  {t / t0:6.2f}  {detect_launch_count(dets[which], B):15d}", flush=True)
                 del pipes
 
 

@@ -44,17 +44,19 @@ def _pipeline(Engine, det, model_list, fit_crops: bool = False) -> DetectClassif
                                   fit_crops=fit_crops)
 
 
-def _detector(Engine, small_maps: Optional[bool]):
-    """Engine.engine, or - where small_maps is given and differs from its flag - its sibling in that state (shared weights, own
-    buffers), built once per Engine and kept on it: later calls reuse its activation buffers."""
+def _detector(Engine, small_maps: Optional[bool], grouped_head: Optional[bool] = None):
+    """Engine.engine, or - where small_maps or grouped_head is given and differs from its flag - its sibling in that state (shared
+    weights, own buffers), built once per Engine and state and kept on it: later calls reuse its activation buffers."""
     det = Engine.engine
-    if small_maps is None or bool(small_maps) == det.small_maps:
+    want = (det.small_maps if small_maps is None else bool(small_maps),
+            det.grouped_head if grouped_head is None else bool(grouped_head))
+    if want == (det.small_maps, det.grouped_head):
         return det
-    sib = getattr(Engine, "_small_maps_sibling", None)
-    if sib is None or sib.w is not det.w or sib.hw != det.hw or sib.small_maps != bool(small_maps):
-        sib = det.resized(det.size)
-        sib.small_maps = bool(small_maps)
-        Engine._small_maps_sibling = sib
+    cache = Engine.__dict__.setdefault("_detector_siblings", {})
+    sib = cache.get(want)
+    if sib is None or sib.w is not det.w or sib.hw != det.hw:
+        sib = cache[want] = det.resized(det.size)
+        sib.small_maps, sib.grouped_head = want
     return sib
 
 
@@ -68,7 +70,7 @@ def _rect_pipeline(Engine, pipe: DetectClassifyPipeline, cache: dict, hw) -> Det
 
 def main(Engine, imgs, device=None, model_list: Optional[list] = None, transform=None, aliyunoss=None,
          func: Optional[Callable] = None, rect: bool = False, fit_crops: Optional[bool] = None,
-         small_maps: Optional[bool] = None):
+         small_maps: Optional[bool] = None, grouped_head: Optional[bool] = None):
     """Detect + classify every image under `imgs` (directory, file or list).  Returns a JSON-serialisable dict
     {"output": [{"image": name, "objects": [{"sort", "det_sort", "confidence", "xmin", "ymin", "xmax", "ymax"}]}]}.
     `transform` is accepted for signature compatibility: its valid_test branch (nearest resize to 224 +
@@ -81,13 +83,14 @@ def main(Engine, imgs, device=None, model_list: Optional[list] = None, transform
     the detector found instead of topk per image (DetectClassifyPipeline(fit_crops=True)): for request-sized calls.  The result
     is the same dict; classifiers built with mid_gemm=True use their mid-M GEMM, main does not switch it on.
     small_maps (None: as the engine was built): the detector of this call runs with YoloEngine(small_maps=) in that state - where
-    it differs from Engine.engine's, on a sibling that shares its weights (YoloEngine.resized), built once and kept on Engine."""
+    it differs from Engine.engine's, on a sibling that shares its weights (YoloEngine.resized), built once and kept on Engine.
+    grouped_head (None: as the engine was built): likewise for YoloEngine(grouped_head=); one sibling per pair of the two flags."""
     yvhip.require_gpu()
     if not model_list:
         raise yvhip.YvError("model_list is empty")
     dev = torch.device(device) if device is not None else Engine.device
     S = Engine.size
-    det = _detector(Engine, small_maps)
+    det = _detector(Engine, small_maps, grouped_head)
     pipe = _pipeline(Engine, det, model_list, _env_flag(fit_crops, "YV_FIT_CROPS"))
     if rect and not isinstance(S, int):
         raise yvhip.YvError("rect=True takes a square engine: its size is the long side of every rectangle")

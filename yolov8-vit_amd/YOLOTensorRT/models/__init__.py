@@ -43,11 +43,13 @@ def _guess_scale_nc(sd):
 
 class TRTModule(torch.nn.Module):
     def __init__(self, weight: Union[str, dict], device: Optional[torch.device] = None, size=640,
-                 dtype: str = "bf16", small_maps: Optional[bool] = None) -> None:
+                 dtype: str = "bf16", small_maps: Optional[bool] = None, grouped_head: Optional[bool] = None) -> None:
         """size: the network input's side, or its (H, W) (multiples of 32); `inp_info` gives (1, 3, H, W).
         dtype: "bf16" (default) or "mxfp8" (the detector's eligible convolutions on MXFP8 operands, engines.mx_conv_plan).
         small_maps: YoloEngine(small_maps=): the small-map convolution tiles for request-sized batches (opt-in; None reads
-        YV_YOLO_SMALL_MAPS)."""
+        YV_YOLO_SMALL_MAPS).
+        grouped_head: YoloEngine(grouped_head=): each step of the Detect head as one grouped launch (opt-in; None reads
+        YV_YOLO_GROUPED_HEAD)."""
         super().__init__()
         self.device = torch.device(device) if device is not None else torch.device('cuda:0')
         if isinstance(weight, dict):
@@ -65,7 +67,7 @@ class TRTModule(torch.nn.Module):
         sd = fold_batchnorm(sd)
         self.scale, self.nc = _guess_scale_nc(sd)
         self.engine = engines.YoloEngine(sd, self.scale, self.nc, size, device=str(self.device), dtype=dtype,
-                                         small_maps=small_maps)
+                                         small_maps=small_maps, grouped_head=grouped_head)
         self.size = self.engine.size
         self.inp_info = [Tensor('images', torch.float32, (1, 3, *self.engine.hw))]
         self.out_info = [Tensor('num_dets', torch.int32, (1, 1)), Tensor('bboxes', torch.float32, (1, 100, 4)),

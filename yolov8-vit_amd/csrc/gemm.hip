@@ -20,8 +20,10 @@
 //   M tile (activation rows stay in that XCD's L2).
 #include <string.h>
 #include <type_traits>
+#include <algorithm>
 #include <map>
 #include <mutex>
+#include <vector>
 #include "gemm_common.h"
 #include "mx_quant.h"
 #include "bn_act_grad.h"
@@ -1063,9 +1065,14 @@ __device__ __forceinline__ void cdma_mfma_step(const unsigned char* A, const uns
     }
 }
 
-template <int BN, int WM, int WN, int ST = 2 /* LDS stages: ST - 1 K steps of DMA in flight */, bool STATS = false /* as igemm_kernel */,
-          bool PHASE = false /* as igemm_kernel */, bool BNBWD = false /* as igemm_kernel */>
-__global__ __launch_bounds__(256) void cgemm_dma_kernel(GemmArgs g) {
+// One tile of cgemm_dma_kernel: ONE text for the kernel below and for cgemm_dma_group_kernel.  bid: the workgroup's index among the
+// nwg workgroups that walk g's tiles (the launch's grid, a phase's share of it, or a group member's share), ph: the phase (PHASE).
+// The LDS base is the launch's dynamic LDS, named here as the kernels named it: handed in as a pointer argument it changed the
+// register allocation of the BNBWD instances (136 -> 134 VGPRs), declared here every existing instance compiles to the parent's
+// report (profiles/conv_group_resources.txt).
+template <int BN, int WM, int WN, int ST, bool STATS, bool PHASE, bool BNBWD>
+__device__ __forceinline__ void cdma_tile(const GemmArgs& g, int bid, const int nwg, const int ph = 0) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     static_assert(!(PHASE && STATS), "the phase form is a plain convolution");
     static_assert(!(BNBWD && (PHASE || STATS)), "one kind of column sums, none of a phase launch");
     constexpr int BM = 128, NW = 4;
@@ -1073,12 +1080,8 @@ __global__ __launch_bounds__(256) void cgemm_dma_kernel(GemmArgs g) {
     constexpr int MF = BM / WM / 16, NF = BN / WN / 16;
     constexpr int A_BYTES = BM * 128, W_BYTES = BN * 128;
     constexpr int A_INS = BM / (8 * NW), W_INS = BN / (8 * NW);
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int M = g.M;
-    int bid = blockIdx.x;
-    int nwg = gridDim.x, ph = 0;
-    if constexpr (PHASE) { ph = phase_of_block(g, bid); nwg = g.tiles_m * g.tiles_n; }
     {
         const int q = nwg >> 3, r = nwg & 7, x = bid & 7;
         bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
@@ -1178,6 +1181,15 @@ __global__ __launch_bounds__(256) void cgemm_dma_kernel(GemmArgs g) {
     finish_tile<MF, NF, STATS, WM, BN, PHASE, BNBWD>(g, acc, M, m0, n0, wrow_m, wrow_n, lane, wave, smem, tm, ph);
 }
 
+template <int BN, int WM, int WN, int ST = 2 /* LDS stages: ST - 1 K steps of DMA in flight */, bool STATS = false /* as igemm_kernel */,
+          bool PHASE = false /* as igemm_kernel */, bool BNBWD = false /* as igemm_kernel */>
+__global__ __launch_bounds__(256) void cgemm_dma_kernel(GemmArgs g) {
+    int bid = blockIdx.x;
+    int nwg = gridDim.x, ph = 0;
+    if constexpr (PHASE) { ph = phase_of_block(g, bid); nwg = g.tiles_m * g.tiles_n; }
+    cdma_tile<BN, WM, WN, ST, STATS, PHASE, BNBWD>(g, bid, nwg, ph);
+}
+
 // ---------------------------------------------------------------------------------------------
 // Small-map convolution ("conv_small", off by default): the detector at the one or few images a request
 // carries.  A 20 x 20 map is four 128-row tiles per 64 columns - 8 or 16 workgroups on 256 CUs, each walking 18 K steps alone.
@@ -1196,21 +1208,21 @@ __global__ __launch_bounds__(256) void cgemm_dma_kernel(GemmArgs g) {
 // out / ldo).  One launch, no workspace, no atomics: the result does not depend on the launch.
 // Eligibility (host): cgemm_dma_kernel's.  No STATS, PHASE, BNBWD or MXFP8 form.
 // ---------------------------------------------------------------------------------------------
+// One tile of cgemm_small_kernel: ONE text for the kernel below and for cgemm_small_group_kernel (bid, nwg, the LDS: as cdma_tile).
 template <int BM, int KS>
-__global__ __launch_bounds__(512, KS == 2 ? 2 : 1) void cgemm_small_kernel(GemmArgs g) {
+__device__ __forceinline__ void csmall_tile(const GemmArgs& g, int bid, const int nwg) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int BN = 64, GW = 8 / KS, WGM = GW / 2;            // waves per group, as WGM x 2 wave tiles of 32 x 32
     static_assert((KS == 2 || KS == 4) && BM == WGM * 32, "64-row halves or 32-row quarters");
     constexpr int MF = 2, NF = 2, NS = 4 / KS;                   // fragments of a wave tile; those a wave finishes
     constexpr int STAGE = (BM + BN) * 128, RING = 2 * STAGE;     // bytes: one K step of a group, a group's two stages
     constexpr int A_INS = BM / (8 * GW), W_INS = BN / (8 * GW);
     static_assert(8 * 4 * 64 * 16 <= KS * RING, "the exchange overlays the rings");
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int grp = wave / GW, gw = wave - grp * GW;
     const int M = g.M;
-    int bid = blockIdx.x;
     {
-        const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, x = bid & 7;
+        const int q = nwg >> 3, r = nwg & 7, x = bid & 7;
         bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
     }
     const int tm = bid / g.tiles_n, tn = bid - tm * g.tiles_n;
@@ -1299,6 +1311,54 @@ __global__ __launch_bounds__(512, KS == 2 ? 2 : 1) void cgemm_small_kernel(GemmA
     }
     // f = grp + KS s: row fragment grp & 1, column fragments (grp >> 1) + (KS / 2) s - consecutive for NS = 2 (grp >> 1 = 0)
     finish_tile<1, NS>(g, sum, M, m0, n0, wrow_m + (grp & 1) * 16, wrow_n + (grp >> 1) * 16, lane, wave, smem);
+}
+
+template <int BM, int KS>
+__global__ __launch_bounds__(512, KS == 2 ? 2 : 1) void cgemm_small_kernel(GemmArgs g) {
+    csmall_tile<BM, KS>(g, blockIdx.x, gridDim.x);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Grouped launch ("conv2d_group"): ONE grid whose workgroups belong to up to YV_CONV_GROUP_MAX independent
+// convolutions of one kernel instance - the Detect head's three levels in one step.  The members travel in the kernel arguments by
+// value (no device table, no copy): their GemmArgs, in launch order, and first[i], the first workgroup of member i (first[n]: the
+// grid).  Every first[i] is a multiple of 8, so a workgroup's position in the round robin over the eight XCDs is the same in the
+// grid and inside its member, and the tile bodies' remap runs on the member-local index with the member's own workgroup count
+// (tiles_m * tiles_n): what it means in a single launch.  The workgroups between a member's last tile and the next multiple of 8
+// return at once.  A workgroup finds its member by a uniform scan of first[]; the member's descriptor is then read where it lies, in
+// the kernel-argument segment, through scalar loads (no private copy: the resource report shows no scratch).
+// No state crosses members: each member's output is, bit for bit, what the single launch of the same instance writes.
+// ---------------------------------------------------------------------------------------------
+struct ConvGroupArgs {
+    GemmArgs m[YV_CONV_GROUP_MAX];
+    int first[YV_CONV_GROUP_MAX + 1];
+    int n;
+};
+static_assert(sizeof(ConvGroupArgs) + 256 <= 4096, "the member table (+ the hidden arguments) stays inside the 4 KB kernel-argument segment");
+
+// the member of workgroup bid (uniform) and bid's index inside it; false: a padding workgroup
+__device__ __forceinline__ bool conv_group_member(const ConvGroupArgs& p, int bid, int& member, int& local) {
+    int i = 0;
+    while (i + 1 < p.n && bid >= p.first[i + 1]) ++i;
+    member = i;
+    local = bid - p.first[i];
+    return local < p.m[i].tiles_m * p.m[i].tiles_n;
+}
+
+template <int BN, int WM, int WN, int ST>
+__global__ __launch_bounds__(256) void cgemm_dma_group_kernel(ConvGroupArgs p) {
+    int i, local;
+    if (!conv_group_member(p, blockIdx.x, i, local)) return;
+    const GemmArgs& g = p.m[i];
+    cdma_tile<BN, WM, WN, ST, false, false, false>(g, local, g.tiles_m * g.tiles_n);
+}
+
+template <int BM, int KS>
+__global__ __launch_bounds__(512, KS == 2 ? 2 : 1) void cgemm_small_group_kernel(ConvGroupArgs p) {
+    int i, local;
+    if (!conv_group_member(p, blockIdx.x, i, local)) return;
+    const GemmArgs& g = p.m[i];
+    csmall_tile<BM, KS>(g, local, g.tiles_m * g.tiles_n);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -3108,12 +3168,10 @@ extern "C" int yv_linear_route(int M, int N, int K, int lda, int ldo, int flags,
 // yv_conv2d_bnbwd: the BatchNorm block whose output gradient the convolution stores
 struct BnBwdOps { const void* z; int ldz; const float *mean, *rstd, *gamma, *beta; int act; };
 
-static int conv_impl_one(const yv_view* in0, const yv_view* in1, int B, int Hout, int Wout, int ksize, int stride,
-                         const void* weight, const float* bias, int Cout, void* out, int out_ld, const void* res,
-                         int res_ld, int flags, void* ws, size_t ws_bytes, void* stream, bool query = false,
-                         float* stats = nullptr /* yv_conv2d_stats / _bnbwd: the tile partials; never split-K */,
-                         const BnBwdOps* bb = nullptr /* yv_conv2d_bnbwd: the sums are the BatchNorm backward's */,
-                         bool trainer = false /* a query for the trainer's plain call, which never sets "conv_small" */) {
+// The argument checks of one convolution launch and its GemmArgs (everything but the route): ONE text for conv_impl_one and for
+// conv_group_partition, which checks every member of a group before anything is launched.
+static int conv_args(const yv_view* in0, const yv_view* in1, int B, int Hout, int Wout, int ksize, int stride, const void* weight,
+                     const float* bias, int Cout, void* out, int out_ld, const void* res, int res_ld, int flags, GemmArgs& g) {
     if (!in0 || !in0->ptr || !weight || !out || B <= 0 || Hout <= 0 || Wout <= 0 || Cout <= 0) return YV_ERR_ARG;
     if (!(ksize == 1 || ksize == 3) || !(stride == 1 || stride == 2)) return YV_ERR_ARG;
     if (in1 && in1->ptr && ksize != 1) return YV_ERR_ARG;
@@ -3133,7 +3191,7 @@ static int conv_impl_one(const yv_view* in0, const yv_view* in1, int B, int Hout
             (long long)Cout * ksize * ksize * Cin * 2 >= 0x7fffffffLL)
             return YV_ERR_LIMIT;
     }
-    GemmArgs g = {};
+    g = GemmArgs{};
     g.cin_shift = (Cin & (Cin - 1)) == 0 ? __builtin_ctz((unsigned)Cin) : -1;
     g.tap_uniform = (Cin % 64) == 0;
     g.a0 = (const uint16_t*)in0->ptr; g.lda0 = in0->ld; g.c0 = in0->c; g.up0 = in0->up;
@@ -3143,6 +3201,18 @@ static int conv_impl_one(const yv_view* in0, const yv_view* in1, int B, int Hout
     g.w = (const uint16_t*)weight; g.bias = bias;
     g.M = B * Hout * Wout; g.N = Cout; g.K = ksize * ksize * Cin;
     g.out = out; g.ldo = out_ld; g.res = (const uint16_t*)res; g.ldres = res_ld; g.flags = flags;
+    return YV_OK;
+}
+
+static int conv_impl_one(const yv_view* in0, const yv_view* in1, int B, int Hout, int Wout, int ksize, int stride,
+                         const void* weight, const float* bias, int Cout, void* out, int out_ld, const void* res,
+                         int res_ld, int flags, void* ws, size_t ws_bytes, void* stream, bool query = false,
+                         float* stats = nullptr /* yv_conv2d_stats / _bnbwd: the tile partials; never split-K */,
+                         const BnBwdOps* bb = nullptr /* yv_conv2d_bnbwd: the sums are the BatchNorm backward's */,
+                         bool trainer = false /* a query for the trainer's plain call, which never sets "conv_small" */) {
+    GemmArgs g;
+    const int rc = conv_args(in0, in1, B, Hout, Wout, ksize, stride, weight, bias, Cout, out, out_ld, res, res_ld, flags, g);
+    if (rc != YV_OK) return rc;
     const int kern = conv_route(g, ws != nullptr && !stats, ws_bytes, stats != nullptr || bb != nullptr || trainer);
     if (query) return conv_instance_code(g, kern);                // yv_conv2d_instance: the route, no launch
     if (g.splitk > 1) g.partial = (float*)ws;
@@ -3445,6 +3515,147 @@ extern "C" int yv_conv2d_instance(int B, int Hout, int Wout, int ksize, int stri
     const yv_view v0 = {dummy, c0, c0, 0}, v1 = {dummy, c1, c1, 0};
     return conv_impl(&v0, c1 ? &v1 : nullptr, B, Hout, Wout, ksize, stride, dummy, (const float*)dummy, Cout, dummy, out_ld,
                      (flags & YV_EPI_RES_BF16) ? dummy : nullptr, res_ld, flags, ws_bytes ? dummy : nullptr, ws_bytes, nullptr, true);
+}
+
+// ------------------------------------------------------------------------------------------------ grouped convolution launch
+// (kernels and their contract: the comment at cgemm_dma_group_kernel)
+struct GroupMember {
+    GemmArgs g;                     // routed; tiles_m / tiles_n those of its instance where it is eligible
+    int kern;                       // ConvKern, -1: a call conv_impl takes in sub-batches
+    bool eligible;
+    yv_conv2d_group_plan_t plan;
+};
+struct GroupLaunch { int kern; std::vector<int> members; };     // members: indices into the call's array, in grid order
+
+static int group_tile_rows(int kern) { return kern == CK_CDMA_64_3 ? 128 : (kern == CK_SMALL_64 ? 64 : 32); }
+
+// The partition of a group: ONE rule for yv_conv2d_group (which launches it) and yv_conv2d_group_plan (which reports it).  Checks
+// every member (conv_args, the 2 GB limits), routes it as yv_conv2d would alone (conv_route without a workspace), then: the
+// eligible members per instance by descending work (tiles x K steps, as yv_conv2d_dgrad_s2 orders its phases; ties in the order
+// given), YV_CONV_GROUP_MAX to a launch, each member's first workgroup rounded up to a multiple of 8; the others one launch each.
+// query: a plan on dummy pointers - the outputs are taken to be distinct.
+static int conv_group_partition(const yv_conv2d_desc* d, int n, bool query, std::vector<GroupMember>& ms, std::vector<GroupLaunch>& launches) {
+    if (!d || n <= 0) return YV_ERR_ARG;
+    ms.assign((size_t)n, GroupMember{});
+    launches.clear();
+    for (int i = 0; i < n; ++i) {
+        const yv_conv2d_desc& m = d[i];
+        GroupMember& x = ms[i];
+        const yv_view* in1 = m.in1.ptr ? &m.in1 : nullptr;
+        const int rc = conv_args(&m.in0, in1, m.B, m.Hout, m.Wout, m.ksize, m.stride, m.weight, m.bias, m.Cout, m.out, m.out_ld, m.res,
+                                 m.res_ld, m.flags, x.g);
+        if (rc != YV_OK) return rc;
+        const long long Hin = (long long)m.Hout * m.stride, Win = (long long)m.Wout * m.stride;
+        const long long s0 = (Hin >> m.in0.up) * (Win >> m.in0.up) * m.in0.ld * 2;
+        const long long s1 = in1 ? (Hin >> in1->up) * (Win >> in1->up) * in1->ld * 2 : 0;
+        const long long nb = conv_sub_batch(s0, s1, (Win + 1) * m.in0.ld * 2);
+        if (nb < 1) return YV_ERR_LIMIT;
+        if (nb < m.B) {                                           // sub-batches: conv_impl's loop, the first one's route reported
+            x.kern = -1;
+            x.plan.instance = conv_impl(&m.in0, in1, m.B, m.Hout, m.Wout, m.ksize, m.stride, m.weight, m.bias, m.Cout, m.out, m.out_ld,
+                                        m.res, m.res_ld, m.flags, nullptr, 0, nullptr, true);
+            if (x.plan.instance < 0) return x.plan.instance;
+            continue;
+        }
+        x.kern = conv_route(x.g, false, 0, false);
+        x.plan.instance = conv_instance_code(x.g, x.kern);
+        x.eligible = x.kern == CK_CDMA_64_3 || x.kern == CK_SMALL_64 || x.kern == CK_SMALL_32;
+        if (x.eligible) {
+            const int rows = group_tile_rows(x.kern);
+            x.g.tiles_m = (x.g.M + rows - 1) / rows;
+            x.g.tiles_n = (x.g.N + 63) / 64;
+            const long long work = (long long)x.g.tiles_m * x.g.tiles_n * (x.g.K / BK);
+            x.plan.work = (int)(work < 0x7fffffffLL ? work : 0x7fffffffLL);
+        }
+    }
+    if (!query)
+        for (int i = 0; i < n; ++i)
+            for (int j = 0; j < i; ++j)
+                if (d[i].out == d[j].out) return YV_ERR_ARG;
+    for (const int kern : {(int)CK_CDMA_64_3, (int)CK_SMALL_64, (int)CK_SMALL_32}) {
+        std::vector<int> idx;
+        for (int i = 0; i < n; ++i)
+            if (ms[i].eligible && ms[i].kern == kern) idx.push_back(i);
+        std::stable_sort(idx.begin(), idx.end(), [&](int a, int b) { return ms[a].plan.work > ms[b].plan.work; });
+        for (size_t at = 0; at < idx.size(); at += YV_CONV_GROUP_MAX) {
+            const size_t end = at + YV_CONV_GROUP_MAX < idx.size() ? at + YV_CONV_GROUP_MAX : idx.size();
+            long long first = 0;
+            for (size_t k = at; k < end; ++k) {
+                GroupMember& x = ms[idx[k]];
+                x.plan.launch = (int)launches.size();
+                x.plan.position = (int)(k - at);
+                x.plan.first_wg = (int)first;
+                first = (first + (long long)x.g.tiles_m * x.g.tiles_n + 7) & ~7LL;
+                if (first > 0x7fffffffLL) return YV_ERR_LIMIT;
+            }
+            launches.push_back(GroupLaunch{kern, std::vector<int>(idx.begin() + at, idx.begin() + end)});
+        }
+    }
+    for (int i = 0; i < n; ++i)
+        if (!ms[i].eligible) {
+            ms[i].plan.launch = (int)launches.size();
+            launches.push_back(GroupLaunch{ms[i].kern, std::vector<int>(1, i)});
+        }
+    return YV_OK;
+}
+
+static int launch_conv_group(int kern, const ConvGroupArgs& p, hipStream_t st) {
+    void (*k)(ConvGroupArgs) = cgemm_dma_group_kernel<64, 4, 1, 3>;
+    unsigned threads = 256;
+    size_t lds = 3 * (size_t)(128 + 64) * 128;                    // (launch_cdma<64, 4, 1, 3>'s)
+    if (kern == CK_SMALL_64) { k = cgemm_small_group_kernel<64, 2>; threads = 512; lds = 2 * 2 * (size_t)(64 + 64) * 128; }
+    if (kern == CK_SMALL_32) { k = cgemm_small_group_kernel<32, 4>; threads = 512; lds = 4 * 2 * (size_t)(32 + 64) * 128; }
+    if (!yv_grant_lds((const void*)k, lds)) return YV_ERR_LAUNCH;
+    launch_timed(k, (unsigned)p.first[p.n], threads, lds, st, p);
+    return yv_launch_status();
+}
+
+extern "C" int yv_conv2d_group(const yv_conv2d_desc* d, int n, void* stream) {
+    std::vector<GroupMember> ms;
+    std::vector<GroupLaunch> launches;
+    int rc = conv_group_partition(d, n, false, ms, launches);
+    for (size_t l = 0; rc == YV_OK && l < launches.size(); ++l) {
+        const GroupLaunch& L = launches[l];
+        if (L.members.size() == 1) {
+            const yv_conv2d_desc& m = d[L.members[0]];
+            GroupMember& x = ms[L.members[0]];
+            rc = x.kern >= 0 ? launch_conv(x.g, x.kern, (hipStream_t)stream)
+                             : conv_impl(&m.in0, m.in1.ptr ? &m.in1 : nullptr, m.B, m.Hout, m.Wout, m.ksize, m.stride, m.weight, m.bias,
+                                         m.Cout, m.out, m.out_ld, m.res, m.res_ld, m.flags, nullptr, 0, stream);
+            continue;
+        }
+        ConvGroupArgs p = {};
+        p.n = (int)L.members.size();
+        for (int k = 0; k < p.n; ++k) {
+            const GroupMember& x = ms[L.members[k]];
+            p.m[k] = x.g;
+            p.first[k] = x.plan.first_wg;
+            p.first[k + 1] = x.plan.first_wg + x.g.tiles_m * x.g.tiles_n;      // (the last one: the grid)
+        }
+        rc = launch_conv_group(L.kern, p, (hipStream_t)stream);
+    }
+    return rc;
+}
+
+extern "C" int yv_conv2d_group_plan(const yv_conv2d_shape* shapes, int n, yv_conv2d_group_plan_t* out, int* n_launches) {
+    // dense sources at 16-byte aligned bases, as yv_conv2d_instance; nothing is dereferenced or launched
+    static unsigned char dummy[16] __attribute__((aligned(16)));
+    if (!shapes || !out || !n_launches || n <= 0) return YV_ERR_ARG;
+    std::vector<yv_conv2d_desc> d((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        const yv_conv2d_shape& s = shapes[i];
+        if (s.c0 <= 0 || s.c1 < 0) return YV_ERR_ARG;
+        d[i] = yv_conv2d_desc{{dummy, s.c0, s.c0, 0}, {s.c1 ? dummy : nullptr, s.c1, s.c1, 0}, s.B, s.Hout, s.Wout, s.ksize, s.stride,
+                              dummy, (const float*)dummy, s.Cout, dummy, s.out_ld, (s.flags & YV_EPI_RES_BF16) ? dummy : nullptr,
+                              s.res_ld, s.flags};
+    }
+    std::vector<GroupMember> ms;
+    std::vector<GroupLaunch> launches;
+    const int rc = conv_group_partition(d.data(), n, true, ms, launches);
+    if (rc != YV_OK) return rc;
+    for (int i = 0; i < n; ++i) out[i] = ms[i].plan;
+    *n_launches = (int)launches.size();
+    return YV_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------- stride-2 data gradient by phase

@@ -55,6 +55,20 @@ class yv_mx_view(C.Structure):
     _fields_ = [("q", _vp), ("s", _vp), ("ld", _i), ("c", _i), ("up", _i)]
 
 
+class yv_conv2d_desc(C.Structure):
+    _fields_ = [("in0", yv_view), ("in1", yv_view), ("B", _i), ("Hout", _i), ("Wout", _i), ("ksize", _i), ("stride", _i),
+                ("weight", _vp), ("bias", _vp), ("Cout", _i), ("out", _vp), ("out_ld", _i), ("res", _vp), ("res_ld", _i),
+                ("flags", _i)]
+
+
+class yv_conv2d_shape(C.Structure):
+    _fields_ = [(n, _i) for n in ("B", "Hout", "Wout", "ksize", "stride", "c0", "c1", "Cout", "out_ld", "res_ld", "flags")]
+
+
+class yv_conv2d_group_plan_t(C.Structure):
+    _fields_ = [(n, _i) for n in ("launch", "instance", "first_wg", "position", "work")]
+
+
 _SIGS = {
     "yv_version": (_i, []),
     "yv_error_string": (C.c_char_p, [_i]),
@@ -136,6 +150,8 @@ _SIGS = {
     "yv_conv2d": (_i, [C.POINTER(yv_view), C.POINTER(yv_view), _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _i, _vp, _i,
                        _i, _vp]),
     "yv_conv2d_instance": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _sz]),
+    "yv_conv2d_group": (_i, [C.POINTER(yv_conv2d_desc), _i, _vp]),
+    "yv_conv2d_group_plan": (_i, [C.POINTER(yv_conv2d_shape), _i, C.POINTER(yv_conv2d_group_plan_t), C.POINTER(_i)]),
     "yv_conv2d_dgrad_s2": (_i, [C.POINTER(yv_view), _i, _i, _i, _vp, _i, _i, _vp, _i, _vp, _i, _vp, _sz, _vp]),
     "yv_conv2d_dgrad_s2_route": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "yv_conv2d_ws": (_i, [C.POINTER(yv_view), C.POINTER(yv_view), _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _i, _vp, _i,
@@ -775,6 +791,63 @@ def conv2d_instance(B: int, Hout: int, Wout: int, ksize: int, stride: int, c0: i
     r = lib.yv_conv2d_instance(B, Hout, Wout, ksize, stride, c0, c1, Cout, out_ld, res_ld, flags | EPI_BIAS, ws_bytes)
     check(min(r, 0), "yv_conv2d_instance")
     return r
+
+
+CONV_GROUP_MAX = 8                        # YV_CONV_GROUP_MAX: members of one grouped launch
+CONV_GROUP_INSTANCES = (CONV_DMA_64_3, CONV_SMALL_64, CONV_SMALL_32)     # the instances that have a grouped form
+
+
+def conv2d_group(members):
+    """Independent convolutions as one call (yv_conv2d_group): `members` is a sequence of conv2d's argument lists,
+    (in0, in1, B, Hout, Wout, ksize, stride, weight, bias, out, out_c_off, flags[, res[, res_c_off]]).  The members on one of
+    CONV_GROUP_INSTANCES run as one grid per instance (CONV_GROUP_MAX at most), the others alone; every member's output is, bit
+    for bit, what conv2d without split-K writes for it alone.  No member may read what another writes: they run concurrently.
+    With CONV_HOOK set, the events are armed for the call's FIRST LDS-DMA launch only and the hook gets them with M = N = 0:
+    time a call whose members are exactly one launch of conv2d_group_plan (tools/conv_group_bench.py); a call without an LDS-DMA
+    member hands the hook events that were never recorded."""
+    d = (yv_conv2d_desc * max(len(members), 1))()
+    for x, m in zip(d, members):
+        in0, in1, B, Hout, Wout, ksize, stride, weight, bias, out, out_c_off, flags = m[:12]
+        res = m[12] if len(m) > 12 else None
+        res_c_off = m[13] if len(m) > 13 else 0
+        esz = 4 if (flags & EPI_OUT_F32) else 2
+        x.in0 = in0
+        if in1 is not None:
+            x.in1 = in1
+        x.B, x.Hout, x.Wout, x.ksize, x.stride = B, Hout, Wout, ksize, stride
+        x.weight, x.bias, x.Cout = weight.data_ptr(), bias.data_ptr(), weight.shape[0]
+        x.out, x.out_ld = out.data_ptr() + esz * out_c_off, out.shape[-1]
+        if res is not None:
+            x.res, x.res_ld = res.data_ptr() + 2 * res_c_off, res.shape[-1]
+        x.flags = flags | EPI_BIAS
+    hook = CONV_HOOK
+    if hook is not None:
+        e0, e1 = _timing_event(), _timing_event()
+        check(lib.yv_set_launch_timing(e0.handle, e1.handle), "yv_set_launch_timing")
+    try:
+        check(lib.yv_conv2d_group(d, len(members), _st()), "yv_conv2d_group")
+    finally:
+        if hook is not None:
+            lib.yv_set_launch_timing(None, None)         # (also where the call failed: nothing stays armed for a later launch)
+    if hook is not None:
+        hook(0, 0, e0, e1)
+
+
+def conv2d_group_plan(shapes):
+    """The partition conv2d_group makes of members of these shapes under the current options (host only, no GPU needed; see
+    yv_conv2d_group_plan in include/yv_hip.h).  `shapes`: (B, Hout, Wout, ksize, stride, c0, c1, Cout, out_ld[, res_ld[, flags]])
+    per member, flags as conv2d takes them (EPI_BIAS is added).  Returns (number of launches, [per member: dict(launch, instance,
+    first_wg, position, work)]); `instance` is conv2d_instance(..., ws_bytes=0) of the member alone."""
+    n = len(shapes)
+    sh = (yv_conv2d_shape * max(n, 1))()
+    for x, s in zip(sh, shapes):
+        s = tuple(s) + (0, 0)[len(s) - 9:]
+        x.B, x.Hout, x.Wout, x.ksize, x.stride, x.c0, x.c1, x.Cout, x.out_ld, x.res_ld = s[:10]
+        x.flags = s[10] | EPI_BIAS
+    out = (yv_conv2d_group_plan_t * max(n, 1))()
+    launches = C.c_int(0)
+    check(lib.yv_conv2d_group_plan(sh, n, out, C.byref(launches)), "yv_conv2d_group_plan")
+    return int(launches.value), [{f: int(getattr(o, f)) for f, _ in yv_conv2d_group_plan_t._fields_} for o in out[:n]]
 
 
 def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, y: torch.Tensor, rows: int, D: int,

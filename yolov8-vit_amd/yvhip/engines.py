@@ -22,7 +22,7 @@ import torch
 from .extent import n_anchors, net_hw
 from .guard import StepGuard
 from . import (EPI_GELU, EPI_OUT_F32, EPI_POSEMB, EPI_RES_BF16, EPI_RES_F32, EPI_SILU, RES_LN_WIDTHS, YvError, attention,
-               attention_cls, attention_long, attention_mxfp8, c2f_fused, cls_rows, conv2d, conv2d_mxfp8, detect_decode,
+               attention_cls, attention_long, attention_mxfp8, c2f_fused, cls_rows, conv2d, conv2d_group, conv2d_mxfp8, detect_decode,
                detect_tail, get_option, layernorm, layernorm_mxfp8, linear, linear_mxfp8, linear_mxfp8_q, linear_res_ln, mx_map,
                mx_view, quant_conv_weight_mxfp8, quant_mxfp8, quant_mxfp8_map, require_gpu, set_option, sppf_pool, stem_conv,
                view, wrapper_head)
@@ -159,11 +159,16 @@ class Pool(NamedTuple):
     c: int
 
 
+class ConvGroup(NamedTuple):
+    convs: tuple                # Conv entries that are independent of each other: one conv2d_group call (grouped_head)
+
+
 @functools.lru_cache(maxsize=None)
-def detect_launches(scale: str, nc: int = 5, fused_c2f: bool = True, tail: bool = True) -> tuple:
+def detect_launches(scale: str, nc: int = 5, fused_c2f: bool = True, tail: bool = True, grouped_head: bool = False) -> tuple:
     """What YoloEngine launches in front of the decode, in order: Stem, Conv, C2fFused and Pool entries.  fused_c2f: the blocks of
     _fused_c2f_block as one entry each, else layer by layer.  tail=False: without the last 1 x 1 convolutions of the head (the
-    fused Detect tail runs them)."""
+    fused Detect tail runs them).  grouped_head: the head's convolutions as ConvGroup entries, one per step - the three det{s}.0,
+    the six .1, (tail) the six .2 - behind the unchanged backbone and neck."""
     layers = yolo_layers(scale)
     width = {idx: p["cout"] for idx, _, p in layers}
     out: list = []
@@ -207,6 +212,11 @@ def detect_launches(scale: str, nc: int = 5, fused_c2f: bool = True, tail: bool 
         if tail:
             conv(f"model.22.cv2.{s}.2", [(hc, 0, c2, 0)], 1, 1, f"det{s}.box", 4 * REG_MAX, d, flags=EPI_OUT_F32)
             conv(f"model.22.cv3.{s}.2.pad", [(hc, c2, c3, 0)], 1, 1, f"det{s}.cls", ncp, d, flags=EPI_OUT_F32)
+    if grouped_head:                # per level the head is 1 + 2 (+ 2) entries, step after step; the levels do not meet
+        per = 5 if tail else 3
+        head, out = out[-3 * per:], out[:-3 * per]
+        for step in ((0,), (1, 2), (3, 4))[:2 + tail]:
+            out.append(ConvGroup(tuple(head[s * per + i] for s in range(3) for i in step)))
     return tuple(out)
 
 
@@ -266,7 +276,8 @@ class YoloEngine:
     """images (B,H,W,3) u8 RGB on the device -> boxes (B,A,4) f32 xyxy, scores (B,A,nc) f32."""
 
     def __init__(self, state: Dict[str, torch.Tensor], scale: str = "n", nc: int = 5, size=640,
-                 device: str = "cuda:0", dtype: str = "bf16", small_maps: Optional[bool] = None):
+                 device: str = "cuda:0", dtype: str = "bf16", small_maps: Optional[bool] = None,
+                 grouped_head: Optional[bool] = None):
         """size: the network input's side, or its (H, W); both sides multiples of 32.  `hw` is always (H, W); `size` is the int
         of a square engine and the pair of a rectangular one.  The launch list does not depend on the extent.
         dtype "bf16" (default) or "mxfp8": the convolutions of mx_conv_plan(scale, nc) then run on OCP e4m3 operands with
@@ -276,13 +287,19 @@ class YoloEngine:
         with 64-aligned channels on maps of at most that many output pixels - the lower levels at the one or few images a request
         carries - take cgemm_small_kernel's 64- / 32-pixel tiles; the option is restored afterwards.  None:
         the environment variable YV_YOLO_SMALL_MAPS ("1" = on, unset = off).  Off: the option is not touched.  The launch list
-        and the MXFP8 convolutions are the same either way."""
+        and the MXFP8 convolutions are the same either way.
+        grouped_head (opt-in, both dtypes): each step of the Detect head - the three det{s}.0, the six .1, the six .2 where the
+        tail is not fused - is one conv2d_group call: the levels' convolutions on the same kernel instance share one grid (DESIGN.md
+        section 33).  The MXFP8 convolutions of an mxfp8 engine and the members conv2d_group does not group run alone; every
+        output keeps its bits.  None: the environment variable YV_YOLO_GROUPED_HEAD ("1" = on, unset = off).  Composes with
+        small_maps: the group is routed inside the same "conv_small" window."""
         require_gpu()
         hw = net_hw(size)
         if dtype not in ("bf16", "mxfp8"):
             raise YvError("dtype must be 'bf16' or 'mxfp8'")
         self.dtype = dtype
         self.small_maps = _env_flag(small_maps, "YV_YOLO_SMALL_MAPS")
+        self.grouped_head = _env_flag(grouped_head, "YV_YOLO_GROUPED_HEAD")
         self.scale, self.nc, self.dev = scale, nc, torch.device(device)
         self.layers = yolo_layers(scale)
         self.w: Dict[str, torch.Tensor] = {}
@@ -339,7 +356,7 @@ class YoloEngine:
     def resized(self, size) -> "YoloEngine":
         """A sibling engine for another input extent (an int or (H, W)): it shares this engine's weight, bias, MX weight and
         tail-operand tensors (nothing is uploaded or quantised again) and has buffers and a StepGuard of its own.  It keeps the
-        small_maps flag."""
+        small_maps and grouped_head flags."""
         hw = net_hw(size)
         sib = object.__new__(type(self))
         sib.__dict__.update(self.__dict__)
@@ -382,6 +399,24 @@ class YoloEngine:
         """A bf16 producer wrote channels [c_off, c_off+c) of `name`: bring its MX map, if it has one, up to date."""
         if name in bufs["mx"]:
             quant_mxfp8_map(bufs["flat"][name], bufs["mx"][name], c_off, c, c_off)
+
+    def _conv_group(self, bufs, B: int, e: ConvGroup):
+        """One step of the head: the MXFP8 members alone, the bf16 members as one conv2d_group call, then their MX maps."""
+        flat = bufs["flat"]
+        members, bf16 = [], [c for c in e.convs if c.key not in self.wq]
+        for c in e.convs:
+            if c.key in self.wq:
+                self._conv(bufs, B, c)
+        for c in bf16:
+            v = [view(flat[b], off, ch, up) for b, off, ch, up in c.srcs]
+            out = flat[c.out]
+            members.append((v[0], v[1] if len(v) > 1 else None, B, self.hw[0] // c.down, self.hw[1] // c.down, c.k, c.stride,
+                            self.w[c.key], self.b[c.key], out, c.out_off, c.flags, out if c.res_off is not None else None,
+                            c.res_off or 0))
+        if members:
+            conv2d_group(members)
+        for c in bf16:
+            self._produced(bufs, c.out, c.out_off, c.cout)
 
     def _conv(self, bufs, B: int, e: Conv):
         flat, mx = bufs["flat"], bufs["mx"]
@@ -430,9 +465,11 @@ class YoloEngine:
             raise YvError(f"engine built for {self.hw[0]}x{self.hw[1]}")
         bufs = self._buffers(B)
         flat, w, b = bufs["flat"], self.w, self.b
-        for e in detect_launches(self.scale, self.nc, bool(self.fused_c2f), tail):
+        for e in detect_launches(self.scale, self.nc, bool(self.fused_c2f), tail, bool(self.grouped_head)):
             if type(e) is Conv:
                 self._conv(bufs, B, e)
+            elif type(e) is ConvGroup:
+                self._conv_group(bufs, B, e)
             elif type(e) is Pool:
                 sppf_pool(flat[e.buf], e.c)
             else:
