@@ -372,7 +372,13 @@ int yv_conv2d(const yv_view* in0, const yv_view* in1, int B, int Hout, int Wout,
  *             4 cgemm_dma_kernel<64,4,1,2>, 5 <64,4,1,3>, 6 <64,4,1,4>, 7 <128,2,2,2>, 8 <128,2,2,3>  (<tile width, waves, stages>);
  *             9 cgemm_small_kernel<64,2>, 10 <32,4>  (<tile rows, K groups>; only with the option "conv_small" > 0: at most that
  *             many output pixels, 128 x 64 tiles at most "conv_small_fill" eighths of the CU count, eligibility of 4 .. 8; they
- *             take the direct epilogue, so bit 4 is clear)
+ *             take the direct epilogue, so bit 4 is clear);
+ *             11 cgemm_dma32_kernel<64,4,1,3>, 13 <128,2,2,2>  (<tile width, waves, stages>; only with the option "conv_dma32"
+ *             != 0, which is 0 by default: Cout >= 64, every source a multiple of 32 channels but not what 4 .. 8 ask (64), one
+ *             source or a 1 x 1, a stageable output, no device row count, no split-K, a plain yv_conv2d / yv_conv2d_ws call;
+ *             "conv_dma32_cols" = 64 / 128 forces that instance, any other value is the measured rule of conv_route, which
+ *             leaves Cout = 64 on igemm_kernel; both take the staged epilogue; 12 is the 96-wide instance, which measured
+ *             fastest on no layer and is not built: no route reports it)
  *   bit 4 (16) the staged epilogue runs (see yv_conv2d for what that means for the shortcut's rounding)
  *   bit 5 (32) split-K: partial sums in the workspace, epilogue in the reduce pass
  *   bit 6 (64) the two-source instantiation of igemm_kernel (c1 > 0; the LDS-DMA kernels have no separate one). */

@@ -43,13 +43,16 @@ def _guess_scale_nc(sd):
 
 class TRTModule(torch.nn.Module):
     def __init__(self, weight: Union[str, dict], device: Optional[torch.device] = None, size=640,
-                 dtype: str = "bf16", small_maps: Optional[bool] = None, grouped_head: Optional[bool] = None) -> None:
+                 dtype: str = "bf16", small_maps: Optional[bool] = None, grouped_head: Optional[bool] = None,
+                 dma32: Optional[bool] = None) -> None:
         """size: the network input's side, or its (H, W) (multiples of 32); `inp_info` gives (1, 3, H, W).
         dtype: "bf16" (default) or "mxfp8" (the detector's eligible convolutions on MXFP8 operands, engines.mx_conv_plan).
         small_maps: YoloEngine(small_maps=): the small-map convolution tiles for request-sized batches (opt-in; None reads
         YV_YOLO_SMALL_MAPS).
         grouped_head: YoloEngine(grouped_head=): each step of the Detect head as one grouped launch (opt-in; None reads
-        YV_YOLO_GROUPED_HEAD)."""
+        YV_YOLO_GROUPED_HEAD).
+        dma32: YoloEngine(dma32=): the LDS-DMA convolution for input channels that are a multiple of 32 but not of 64 (opt-in;
+        None reads YV_YOLO_DMA32)."""
         super().__init__()
         self.device = torch.device(device) if device is not None else torch.device('cuda:0')
         if isinstance(weight, dict):
@@ -67,7 +70,7 @@ class TRTModule(torch.nn.Module):
         sd = fold_batchnorm(sd)
         self.scale, self.nc = _guess_scale_nc(sd)
         self.engine = engines.YoloEngine(sd, self.scale, self.nc, size, device=str(self.device), dtype=dtype,
-                                         small_maps=small_maps, grouped_head=grouped_head)
+                                         small_maps=small_maps, grouped_head=grouped_head, dma32=dma32)
         self.size = self.engine.size
         self.inp_info = [Tensor('images', torch.float32, (1, 3, *self.engine.hw))]
         self.out_info = [Tensor('num_dets', torch.int32, (1, 1)), Tensor('bboxes', torch.float32, (1, 100, 4)),

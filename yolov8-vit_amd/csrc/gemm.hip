@@ -1191,6 +1191,160 @@ __global__ __launch_bounds__(256) void cgemm_dma_kernel(GemmArgs g) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// LDS-DMA convolution for 32-aligned input channels ("conv_dma32", off by default): cgemm_dma_kernel's
+// organisation for the layers its eligibility leaves on igemm_kernel - Cin % 32 == 0 but not % 64 (YOLOv8m's 96 and 288) - as a
+// plain inference convolution (no STATS, PHASE or BNBWD form).  A 64-deep K step is two 32-channel BLOCKS, each its own LDS panel
+// of 64-byte rows ([rows][32 bf16]; a stage: two A panels, then two W panels).  A block never straddles a tap or a source
+// (Cin % 32 == 0; c0 % 32 == 0 for a two-source 1 x 1), so what changes along K stays in the DMA's scalar offset, per block
+// (cdma_step0 at the block's element); a wave-instruction fills 16 rows x 64 B = 1,024 contiguous bytes of one panel
+// (lane -> row lane >> 2, chunk lane & 3), and what a lane contributes is fixed for the tile, by cdma_lane_pixel / cdma_lane_weight.
+// Swizzle: chunk c of row r lies at slot c ^ cdma32_swz(r).  ds_read_b128 serves four 16-lane groups, {0-3, 12-15, 20-27},
+// {4-11, 16-19, 28-31} and the same + 32; a fragment read has lane = fq * 16 + fr at row fr, chunk fq, i.e. 16-byte slot
+// (fr & 3) * 4 + (fq ^ swz) of the 256-byte bank row.  With swz = (r >> 2) & 3 lanes 0-3 and 20-23 (and 12-15 and 24-27) of a group
+// meet on the same four slots: 2-way.  With swz = -(r >> 2) & 3 = {0, 3, 2, 1} the four quads of every group take
+// {0, 1, 2, 3} ^ const: conflict-free.
+// K ascends, one mfma_f32_16x16x32_bf16 per block and fragment into the same accumulators: a tile's accumulation order is
+// cgemm_dma_kernel's.  Odd block count (K = 9 * 96: 13.5 steps; Cin = 32 at 1 x 1: half a step): the last step's missing block is
+// ISSUED, activations and weights, at the out-of-range offset, so the descriptor's range check leaves zeros in both panels and
+// the counted vmcnt is the same in every step (in range the weight read would reach the next output channel's row).
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ int cdma32_swz(int r) { return (0 - (r >> 2)) & 3; }
+// the chunk argument with which cdma_lane_pixel / cdma_lane_weight, whose swizzle is arg ^ (r & 7), read source chunk
+// lch ^ cdma32_swz(r) for the lane that fills slot lch of row r
+__device__ __forceinline__ int cdma32_lane_chunk(int r, int lch) { return lch ^ cdma32_swz(r) ^ (r & 7); }
+// one 64-deep K step (two blocks) of a wave tile of MF x NF fragments: panels of AP / WP bytes, 64-byte rows
+template <int MF, int NF, int AP, int WP>
+__device__ __forceinline__ void cdma32_mfma_step(const unsigned char* A, const unsigned char* W, int wrow_m, int wrow_n, int fr, int fq,
+                                                 f32x4 (&acc)[NF][MF]) {
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+        bf16x8 fa[MF], fw[NF];
+#pragma unroll
+        for (int j = 0; j < MF; ++j) {
+            const int rr = wrow_m + j * 16 + fr;
+            fa[j] = *(const bf16x8*)(A + ks * AP + rr * 64 + ((fq ^ cdma32_swz(rr)) << 4));
+        }
+#pragma unroll
+        for (int i = 0; i < NF; ++i) {
+            const int rr = wrow_n + i * 16 + fr;
+            fw[i] = *(const bf16x8*)(W + ks * WP + rr * 64 + ((fq ^ cdma32_swz(rr)) << 4));
+        }
+#pragma unroll
+        for (int i = 0; i < NF; ++i)
+#pragma unroll
+            for (int j = 0; j < MF; ++j)
+                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fw[i], fa[j], acc[i][j], 0, 0, 0);
+    }
+}
+
+template <int BN, int WM, int WN, int ST>
+__global__ __launch_bounds__(256) void cgemm_dma32_kernel(GemmArgs g) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    constexpr int BM = 128, NW = 4;
+    static_assert(WM * WN == NW, "four waves");
+    constexpr int MF = BM / WM / 16, NF = BN / WN / 16;
+    constexpr int AP = BM * 64, WP = BN * 64, STAGE = 2 * (AP + WP);     // bytes: a panel of A, of W; one K step
+    constexpr int A_RG = BM / (16 * NW);                                  // 16-row groups of an A panel per wave (both panels)
+    constexpr int W_RG = BN / 16, W_INS = 2 * W_RG / NW;                  // 16-row groups of a W panel; W instructions per wave
+    static_assert(2 * W_RG % NW == 0 && NF == 4, "every wave issues the same count; 64-column wave tiles (the staged epilogue)");
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int M = g.M;
+    int bid = blockIdx.x;
+    {
+        const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, x = bid & 7;
+        bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
+    }
+    const int tm = bid / g.tiles_n, tn = bid - tm * g.tiles_n;
+    const int m0 = tm * BM, n0 = tn * BN;
+    if (m0 >= M) return;
+
+    const int lrow = lane >> 2, lch = lane & 3;
+    constexpr uint32_t OOB = 0x80000000u;
+    uint32_t a_off0[A_RG], a_off1[A_RG], a_taps[A_RG], w_off[W_INS];
+    const int hw = g.Hout * g.Wout;
+#pragma unroll
+    for (int q = 0; q < A_RG; ++q) {
+        const int r = (q * NW + wave) * 16 + lrow;
+        cdma_lane_pixel<false>(g, M, hw, m0 + r, r, cdma32_lane_chunk(r, lch), a_off0[q], a_off1[q], a_taps[q]);
+    }
+    // W instruction j of this wave: index j * NW + wave among the 2 * W_RG of a step, panel-major
+#pragma unroll
+    for (int j = 0; j < W_INS; ++j) {
+        const int r = ((j * NW + wave) % W_RG) * 16 + lrow;
+        w_off[j] = cdma_lane_weight(g, n0, r, cdma32_lane_chunk(r, lch));
+    }
+    const uint32_t bias0 = cdma_bias0<false>(g);
+    const auto rs0 = __builtin_amdgcn_make_buffer_rsrc((void*)((const unsigned char*)g.a0 - bias0), 0, 0x7fffffff, 0x00020000);
+    const auto rs1 = __builtin_amdgcn_make_buffer_rsrc((void*)(g.c1 ? g.a1 : g.a0), 0, 0x7fffffff, 0x00020000);
+    const auto rsW = __builtin_amdgcn_make_buffer_rsrc((void*)g.w, 0, 0x7fffffff, 0x00020000);
+    const int Cin = g.c0 + g.c1;
+    const int pad = g.ksize >> 1;
+    auto issue = [&](int kt, int buf) __attribute__((always_inline)) {
+        unsigned char* A = smem + buf * STAGE;
+        unsigned char* W = A + 2 * AP;
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+            const int kb = kt * BK + p * 32;                         // (uniform) the block's first element
+            const bool live = kb < g.K;                              // false: the missing block of an odd count - zeros
+            if (g.c1 && kb >= g.c0) {                                // second source of a two-source 1 x 1
+                const int so = (kb - g.c0) * 2;
+#pragma unroll
+                for (int q = 0; q < A_RG; ++q)
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs1, (lptr_t)(A + p * AP + (q * NW + wave) * 1024), 16,
+                                                             (int)((live && (a_taps[q] & 1u)) ? a_off1[q] : OOB), so, 0, 0);
+            } else {
+                int tap;
+                const uint32_t so = cdma_step0(g, kb, bias0, Cin, pad, tap);
+#pragma unroll
+                for (int q = 0; q < A_RG; ++q)
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs0, (lptr_t)(A + p * AP + (q * NW + wave) * 1024), 16,
+                                                             (int)((live && ((a_taps[q] >> tap) & 1u)) ? a_off0[q] : OOB), (int)so, 0, 0);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < W_INS; ++j) {
+            const int idx = j * NW + wave, p = idx / W_RG, rg = idx - p * W_RG;
+            const int kb = kt * BK + p * 32;
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsW, (lptr_t)(W + p * WP + rg * 1024), 16, (int)(kb < g.K ? w_off[j] : OOB), kb * 2, 0,
+                                                     0);
+        }
+    };
+
+    f32x4 acc[NF][MF];
+#pragma unroll
+    for (int i = 0; i < NF; ++i)
+#pragma unroll
+        for (int j = 0; j < MF; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    const int wm = wave / WN, wn = wave - wm * WN;
+    const int wrow_m = wm * (BM / WM), wrow_n = wn * (BN / WN);
+    const int fr = lane & 15, fq = lane >> 4;
+    const int nk = (g.K / 32 + 1) / 2;
+    // the ring of cdma_tile: ST stages, ST - 1 K steps in flight, a counted wait and ONE raw barrier per step
+    constexpr int INS = 2 * A_RG + W_INS;
+    int issued = 0;
+#pragma unroll
+    for (int p = 0; p < ST - 1; ++p)
+        if (p < nk) { issue(p, p); ++issued; }
+    int slot = 0, islot = (ST - 1) % ST;
+    for (int kt = 0; kt < nk; ++kt) {
+        if (issued - kt - 1 >= ST - 2 && ST > 2) {
+            if constexpr (ST == 3) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(INS) : "memory");
+            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        } else {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+        asm volatile("s_barrier" ::: "memory");
+        __builtin_amdgcn_sched_barrier(0);
+        if (issued < nk) { issue(issued, islot); ++issued; islot = islot + 1 == ST ? 0 : islot + 1; }
+        const unsigned char* A = smem + slot * STAGE;
+        slot = slot + 1 == ST ? 0 : slot + 1;
+        cdma32_mfma_step<MF, NF, AP, WP>(A, A + 2 * AP, wrow_m, wrow_n, fr, fq, acc);
+    }
+    asm volatile("s_barrier" ::: "memory");                       // the staged epilogue reuses the tile buffers
+    finish_tile<MF, NF, false, WM, BN>(g, acc, M, m0, n0, wrow_m, wrow_n, lane, wave, smem, tm);
+}
+
+// ---------------------------------------------------------------------------------------------
 // Small-map convolution ("conv_small", off by default): the detector at the one or few images a request
 // carries.  A 20 x 20 map is four 128-row tiles per 64 columns - 8 or 16 workgroups on 256 CUs, each walking 18 K steps alone.
 // Here a workgroup owns BM x 64 outputs and splits K inside itself, as gemm_mid_kernel does for the linears: its 8 waves are KS
@@ -2405,7 +2559,10 @@ int launch(GemmArgs& g, hipStream_t st) {
     }
     if (!yv_grant_lds((const void*)kern, lds)) return YV_ERR_LAUNCH;
     const int S = g.splitk > 1 ? g.splitk : 1;
-    hipLaunchKernelGGL(kern, dim3(g.tiles_m * g.tiles_n * S), dim3(THREADS), lds, st, g);
+    // (a convolution attaches armed timing events - tools/conv_dma32_bench.py times this route as the parent's; unarmed, and for
+    // the linears, the launch is the plain one)
+    if constexpr (MODE == 1) launch_timed(kern, g.tiles_m * g.tiles_n * S, THREADS, lds, st, g);
+    else hipLaunchKernelGGL(kern, dim3(g.tiles_m * g.tiles_n * S), dim3(THREADS), lds, st, g);
     return launch_splitk_reduce(g, st);
 }
 
@@ -2435,6 +2592,17 @@ int launch_cdma(GemmArgs& g, hipStream_t st) {
     return yv_launch_status();
 }
 
+template <int BN, int WM, int WN, int ST>
+int launch_cdma32(GemmArgs& g, hipStream_t st) {
+    g.tiles_m = (g.M + 127) / 128;
+    g.tiles_n = (g.N + BN - 1) / BN;
+    const size_t lds = ST * (size_t)(128 + BN) * 128;
+    void (*kern)(GemmArgs) = cgemm_dma32_kernel<BN, WM, WN, ST>;
+    if (!yv_grant_lds((const void*)kern, lds)) return YV_ERR_LAUNCH;
+    launch_timed(kern, g.tiles_m * g.tiles_n, 256, lds, st, g);
+    return yv_launch_status();
+}
+
 template <int BM, int KS>
 int launch_csmall(GemmArgs& g, hipStream_t st) {
     g.tiles_m = (g.M + BM - 1) / BM;
@@ -2459,7 +2627,8 @@ int launch_cmx(ConvMxArgs& a, hipStream_t st) {       // two LDS stages of 128 +
 enum ConvKern {
     CK_IGEMM_16 = 0, CK_IGEMM_32 = 1, CK_IGEMM_64 = 2, CK_IGEMM_128 = 3,              // igemm_kernel<1, 128, BN, ..>
     CK_CDMA_64_2 = 4, CK_CDMA_64_3 = 5, CK_CDMA_64_4 = 6, CK_CDMA_128_2 = 7, CK_CDMA_128_3 = 8,  // cgemm_dma_kernel<BN, .., ST>
-    CK_SMALL_64 = 9, CK_SMALL_32 = 10                                                             // cgemm_small_kernel<BM, KS>
+    CK_SMALL_64 = 9, CK_SMALL_32 = 10,                                                            // cgemm_small_kernel<BM, KS>
+    CK_DMA32_64 = 11, CK_DMA32_128 = 13           // cgemm_dma32_kernel<BN, ..> (12: the 96-wide instance, measured and not built)
 };
 
 int g_opt_conv_small = 0;           // largest M (output pixels) taken by cgemm_small_kernel ("conv_small"; 0 = the step does not exist)
@@ -2479,6 +2648,11 @@ int conv_cus() {
     }
     return n_cu;
 }
+
+int g_opt_conv_dma32 = 0;           // non-zero: the convolutions with 32- but not 64-aligned input channels on cgemm_dma32_kernel
+                                    // ("conv_dma32"; 0 = the step does not exist)
+int g_opt_conv_dma32_cols = 0;      // ... 64 or 128: that instance for every launch the step takes; else the measured rule
+                                    // ("conv_dma32_cols"; tools/conv_dma32_bench.py and the tests time and check each instance)
 
 int igemm_pick(int N) { return N > 64 ? CK_IGEMM_128 : (N > 32 ? CK_IGEMM_64 : (N > 16 ? CK_IGEMM_32 : CK_IGEMM_16)); }
 
@@ -2542,6 +2716,24 @@ int conv_route(GemmArgs& g, bool have_ws, size_t ws_bytes, bool sums) {
             return g.K >= 1024 ? CK_CDMA_64_3 : CK_CDMA_64_2;
         return two_stage;
     }
+    // 32- but not 64-aligned input channels ("conv_dma32", off by default): what dma_ok asks, with 32 for 64.
+    // The 64-aligned layers (Cin % 64 == 0, and c0 % 64 == 0 where there are two sources) keep their route above, whatever
+    // "conv_dma" says; a two-source 1 x 1 of 64-aligned Cin whose boundary is only 32-aligned (96 + 32) is this step's.  A sums
+    // call and a split-K launch keep igemm_kernel.
+    const bool chan64 = (Cin % 64) == 0 && (g.c1 == 0 || (g.ksize == 1 && (g.c0 % 64) == 0));
+    const bool chan32 = (Cin % 32) == 0 && (g.c1 == 0 || (g.ksize == 1 && (g.c0 % 32) == 0));
+    if (g_opt_conv_dma32 && !sums && g.N >= 64 && chan32 && !chan64 && g.staged && !g.m_dev && g.splitk <= 1) {
+        if (g_opt_conv_dma32_cols == 64) return CK_DMA32_64;
+        if (g_opt_conv_dma32_cols == 128) return CK_DMA32_128;
+        // Measured (tools/conv_dma32_bench.py, profiles/conv_dma32_layers.txt: the 22 layers of YOLOv8m at 64, 4 and 1 images of
+        // 640 x 640, the 32 -> 64 and 96 -> 64 layers of YOLOv8s / n at 32, against igemm_kernel, launch by launch): the 128-wide
+        // two-stage tiles from 25,600 output pixels on a shallow reduction (K < 1024: the 96-channel layers, x 0.85 - 0.93 of the
+        // parent's time, where the 64-wide tiles take x 0.80 - 1.26), the 64-wide three-stage tiles below that and on a deep one
+        // (the 288-channel layers x 0.72 - 0.84, the 6,400-pixel layers of one image x 0.69 - 0.70; the 128-wide tiles x 0.85 -
+        // 0.90 there).  Cout = 64 stays out: all three such layers measured slower on either instance (x 1.06 - 1.13 on the
+        // 64-wide tiles, x 1.38 - 1.46 on the 128-wide ones).  A 96-wide instance was fastest on no layer and is not built.
+        if (g.N > 64) return (g.M >= 25600 && g.K < 1024) ? CK_DMA32_128 : CK_DMA32_64;
+    }
     return igemm_pick(g.N);
 }
 
@@ -2564,6 +2756,8 @@ int launch_conv(GemmArgs& g, int kern, hipStream_t st) {
     case CK_CDMA_128_3: return launch_cdma<128, 2, 2, 3>(g, st);
     case CK_SMALL_64: return launch_csmall<64, 2>(g, st);
     case CK_SMALL_32: return launch_csmall<32, 4>(g, st);
+    case CK_DMA32_64: return launch_cdma32<64, 4, 1, 3>(g, st);
+    case CK_DMA32_128: return launch_cdma32<128, 2, 2, 2>(g, st);
     default: return launch_igemm<1>(g, kern, st);
     }
 }
@@ -2632,7 +2826,7 @@ int launch_dgrad_s2(GemmArgs& g, int kern, hipStream_t st) {
 // the direct one)
 int conv_instance_code(const GemmArgs& g, int kern) {
     const bool split = g.splitk > 1;
-    const bool staged = g.staged && !split && kern >= CK_IGEMM_64 && kern < CK_SMALL_64;
+    const bool staged = g.staged && !split && ((kern >= CK_IGEMM_64 && kern < CK_SMALL_64) || kern == CK_DMA32_64 || kern == CK_DMA32_128);
     const bool two = g.c1 > 0 && kern <= CK_IGEMM_128;
     return kern | (staged ? 16 : 0) | (split ? 32 : 0) | (two ? 64 : 0);
 }
@@ -3052,6 +3246,8 @@ static const struct { const char* key; int* (*at)(); } k_options[] = {
     {"conv_small", [] { return &g_opt_conv_small; }},
     {"conv_small_fill", [] { return &g_opt_conv_small_fill; }},
     {"conv_small_rows", [] { return &g_opt_conv_small_rows; }},
+    {"conv_dma32", [] { return &g_opt_conv_dma32; }},
+    {"conv_dma32_cols", [] { return &g_opt_conv_dma32_cols; }},
     {"dgrad_s2_split", [] { return &g_opt_dgrad_s2_split; }},
 };
 static int* option_at(const char* key) {

@@ -620,7 +620,8 @@ def transpose_bf16_batched(src: torch.Tensor, dst: torch.Tensor, rows: int, cols
 # ------------------------------------------------------------- dense math
 EPI_BIAS, EPI_SILU, EPI_GELU, EPI_RES_F32, EPI_RES_BF16, EPI_OUT_F32, EPI_POSEMB = 1, 2, 4, 8, 16, 32, 64
 LINEAR_HOOK = None      # callable(M, N, K, start_event, end_event) or None
-CONV_HOOK = None        # the same for conv2d (tools/conv_small_bench.py): the LDS-DMA routes attach the events, igemm_kernel's do not
+CONV_HOOK = None        # the same for conv2d (tools/conv_small_bench.py, tools/conv_dma32_bench.py): every bf16 convolution kernel attaches
+                        # the events to its launch (a split-K launch to its main kernel, not to the reduce pass)
 
 
 _HIP = None
@@ -769,7 +770,7 @@ def conv2d(in0: "yv_view", in1: Optional["yv_view"], B: int, Hout: int, Wout: in
                            0 if res is None else res.shape[-1], flags | EPI_BIAS, _p(ws), ws.numel() * 4, _st()),
           "yv_conv2d_ws")
     if hook is not None:
-        lib.yv_set_launch_timing(None, None)             # not consumed where the call took igemm_kernel or split K
+        lib.yv_set_launch_timing(None, None)             # (nothing stays armed for a later launch)
         hook(B * Hout * Wout, Cout, e0, e1)
     return out
 
@@ -779,6 +780,8 @@ CONV_WS_BYTES = 16 * 1024 * 1024 * 4      # the workspace conv2d passes (what co
 CONV_IGEMM_16, CONV_IGEMM_32, CONV_IGEMM_64, CONV_IGEMM_128 = 0, 1, 2, 3
 CONV_DMA_64_2, CONV_DMA_64_3, CONV_DMA_64_4, CONV_DMA_128_2, CONV_DMA_128_3 = 4, 5, 6, 7, 8
 CONV_SMALL_64, CONV_SMALL_32 = 9, 10      # cgemm_small_kernel<64, 2> / <32, 4>: only under the option "conv_small"
+# cgemm_dma32_kernel<64, ..> / <128, ..>: only under the option "conv_dma32" (12: the 96-wide instance, measured and not built)
+CONV_DMA32_64, CONV_DMA32_96, CONV_DMA32_128 = 11, 12, 13
 # ... and flag bits: the staged epilogue runs, split-K, the two-source igemm instantiation
 CONV_STAGED, CONV_SPLITK, CONV_TWO = 16, 32, 64
 
@@ -802,9 +805,8 @@ def conv2d_group(members):
     (in0, in1, B, Hout, Wout, ksize, stride, weight, bias, out, out_c_off, flags[, res[, res_c_off]]).  The members on one of
     CONV_GROUP_INSTANCES run as one grid per instance (CONV_GROUP_MAX at most), the others alone; every member's output is, bit
     for bit, what conv2d without split-K writes for it alone.  No member may read what another writes: they run concurrently.
-    With CONV_HOOK set, the events are armed for the call's FIRST LDS-DMA launch only and the hook gets them with M = N = 0:
-    time a call whose members are exactly one launch of conv2d_group_plan (tools/conv_group_bench.py); a call without an LDS-DMA
-    member hands the hook events that were never recorded."""
+    With CONV_HOOK set, the events are armed for the call's FIRST launch only and the hook gets them with M = N = 0:
+    time a call whose members are exactly one launch of conv2d_group_plan (tools/conv_group_bench.py)."""
     d = (yv_conv2d_desc * max(len(members), 1))()
     for x, m in zip(d, members):
         in0, in1, B, Hout, Wout, ksize, stride, weight, bias, out, out_c_off, flags = m[:12]

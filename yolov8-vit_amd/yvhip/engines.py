@@ -21,8 +21,9 @@ import torch
 
 from .extent import n_anchors, net_hw
 from .guard import StepGuard
-from . import (EPI_GELU, EPI_OUT_F32, EPI_POSEMB, EPI_RES_BF16, EPI_RES_F32, EPI_SILU, RES_LN_WIDTHS, YvError, attention,
-               attention_cls, attention_long, attention_mxfp8, c2f_fused, cls_rows, conv2d, conv2d_group, conv2d_mxfp8, detect_decode,
+from . import (CONV_DMA32_64, CONV_DMA32_96, CONV_DMA32_128, EPI_GELU, EPI_OUT_F32, EPI_POSEMB, EPI_RES_BF16, EPI_RES_F32, EPI_SILU,
+               RES_LN_WIDTHS, YvError, attention, attention_cls, attention_long, attention_mxfp8, c2f_fused, cls_rows, conv2d,
+               conv2d_group, conv2d_instance, conv2d_mxfp8, detect_decode,
                detect_tail, get_option, layernorm, layernorm_mxfp8, linear, linear_mxfp8, linear_mxfp8_q, linear_res_ln, mx_map,
                mx_view, quant_conv_weight_mxfp8, quant_mxfp8, quant_mxfp8_map, require_gpu, set_option, sppf_pool, stem_conv,
                view, wrapper_head)
@@ -258,6 +259,33 @@ def mx_conv_plan(scale: str, nc: int = 5, speed_filter: bool = True, min_width: 
     return out
 
 
+def dma32_layers(scale: str, nc: int, B: int, hw) -> List[str]:
+    """Keys of the Conv entries of detect_launches(scale, nc) that YoloEngine at B images of hw = (H, W) pixels launches on
+    cgemm_dma32_kernel under the CURRENT options (host only: conv2d_instance of each entry's shape, output and residual stride;
+    empty while "conv_dma32" is 0).  An MXFP8 engine runs those of them that are not in mx_conv_plan."""
+    ld = {}
+    for idx, kind, p in yolo_layers(scale):
+        ld[f"out{idx}"] = p["cout"]
+        if kind == "c2f":
+            ld[f"y{idx}"], ld[f"t{idx}"] = (2 + p["n"]) * (p["cout"] // 2), p["cout"] // 2
+        elif kind == "sppf":
+            ld[f"y{idx}"] = p["cin"] * 2
+    _, c2, c3, ncp = detect_widths(scale, nc)
+    for s in range(3):
+        ld.update({f"det{s}.hb": c2 + c3, f"det{s}.hc": c2 + c3, f"det{s}.box": 4 * REG_MAX, f"det{s}.cls": ncp})
+    H, W = hw
+    out = []
+    for e in detect_launches(scale, nc):
+        if type(e) is not Conv:
+            continue
+        c = [x[2] for x in e.srcs] + [0]
+        code = conv2d_instance(B, H // e.down, W // e.down, e.k, e.stride, c[0], c[1], e.cout, ld[e.out],
+                               ld[e.out] if e.res_off is not None else 0, e.flags)
+        if code & 15 in (CONV_DMA32_64, CONV_DMA32_96, CONV_DMA32_128):
+            out.append(e.key)
+    return out
+
+
 SMALL_MAP_PIXELS = 12800   # "conv_small" of a YoloEngine(small_maps=True) pass: the bound measured in DESIGN.md section 32
 
 
@@ -277,7 +305,7 @@ class YoloEngine:
 
     def __init__(self, state: Dict[str, torch.Tensor], scale: str = "n", nc: int = 5, size=640,
                  device: str = "cuda:0", dtype: str = "bf16", small_maps: Optional[bool] = None,
-                 grouped_head: Optional[bool] = None):
+                 grouped_head: Optional[bool] = None, dma32: Optional[bool] = None):
         """size: the network input's side, or its (H, W); both sides multiples of 32.  `hw` is always (H, W); `size` is the int
         of a square engine and the pair of a rectangular one.  The launch list does not depend on the extent.
         dtype "bf16" (default) or "mxfp8": the convolutions of mx_conv_plan(scale, nc) then run on OCP e4m3 operands with
@@ -292,7 +320,12 @@ class YoloEngine:
         tail is not fused - is one conv2d_group call: the levels' convolutions on the same kernel instance share one grid (DESIGN.md
         section 33).  The MXFP8 convolutions of an mxfp8 engine and the members conv2d_group does not group run alone; every
         output keeps its bits.  None: the environment variable YV_YOLO_GROUPED_HEAD ("1" = on, unset = off).  Composes with
-        small_maps: the group is routed inside the same "conv_small" window."""
+        small_maps: the group is routed inside the same "conv_small" window.
+        dma32 (opt-in, both dtypes): the pass runs with the option "conv_dma32" at 1, so its bf16 convolutions whose input channels
+        are a multiple of 32 but not of 64 (dma32_layers: YOLOv8m's 96- and 288-channel layers) take cgemm_dma32_kernel instead of
+        igemm_kernel; the option is restored afterwards.  None: the environment variable YV_YOLO_DMA32
+        ("1" = on, unset = off).  Off: the option is not touched.  The launch list and the MXFP8 convolutions are the same either
+        way; the eligibility is disjoint from that of small_maps and grouped_head, so the flags compose."""
         require_gpu()
         hw = net_hw(size)
         if dtype not in ("bf16", "mxfp8"):
@@ -300,6 +333,7 @@ class YoloEngine:
         self.dtype = dtype
         self.small_maps = _env_flag(small_maps, "YV_YOLO_SMALL_MAPS")
         self.grouped_head = _env_flag(grouped_head, "YV_YOLO_GROUPED_HEAD")
+        self.dma32 = _env_flag(dma32, "YV_YOLO_DMA32")
         self.scale, self.nc, self.dev = scale, nc, torch.device(device)
         self.layers = yolo_layers(scale)
         self.w: Dict[str, torch.Tensor] = {}
@@ -356,7 +390,7 @@ class YoloEngine:
     def resized(self, size) -> "YoloEngine":
         """A sibling engine for another input extent (an int or (H, W)): it shares this engine's weight, bias, MX weight and
         tail-operand tensors (nothing is uploaded or quantised again) and has buffers and a StepGuard of its own.  It keeps the
-        small_maps and grouped_head flags."""
+        small_maps, grouped_head and dma32 flags."""
         hw = net_hw(size)
         sib = object.__new__(type(self))
         sib.__dict__.update(self.__dict__)
@@ -446,14 +480,21 @@ class YoloEngine:
             return tuple([t.clone() for t in part] for part in res)
 
     def _forward_raw(self, images: torch.Tensor, tail: bool = True):
-        if not self.small_maps:
+        want = {}                               # the options of this pass (small_maps, dma32): set around it, restored after it
+        if self.small_maps:
+            want["conv_small"] = SMALL_MAP_PIXELS
+        if self.dma32:
+            want["conv_dma32"] = 1
+        if not want:
             return self._launch_list(images, tail)
-        small = get_option("conv_small")
-        set_option("conv_small", SMALL_MAP_PIXELS)
+        saved = {k: get_option(k) for k in want}
+        for k, v in want.items():
+            set_option(k, v)
         try:
             return self._launch_list(images, tail)
         finally:
-            set_option("conv_small", small)
+            for k, v in saved.items():
+                set_option(k, v)
 
     def _launch_list(self, images: torch.Tensor, tail: bool = True):
         """Walks detect_launches (self.fused_c2f is read here, so it may be flipped between calls).  tail=False: stop in front of
