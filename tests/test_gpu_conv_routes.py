@@ -260,7 +260,8 @@ def test_subbatched_source_on_the_lds_dma_route(yv):
 
 
 # ------------------------------------------------------------------------------------------------ B.2
-SWEEP = ["igemm16", "igemm32_cin24", "dma64_1x1_nk1", "dma64_3x3_cin64", "dma64_3x3_cin128", "dma64_two_src_128up_128", "dma64_33x17_cin192", "dma64_slices_3x3_s2",
+# (dma64_1x1_nk1, dma64_1x1_nk2_n80, dma64_stride2_1x1: one and two K steps - the four-stage ring's prologue runs out of steps)
+SWEEP = ["igemm16", "igemm32_cin24", "dma64_1x1_nk1", "dma64_1x1_nk2_n80", "dma64_stride2_1x1", "dma64_3x3_cin64", "dma64_3x3_cin128", "dma64_two_src_128up_128", "dma64_33x17_cin192", "dma64_slices_3x3_s2",
          "dma64_two_src_128up_64", "dma64_two_src_slices", "dma128_b16_80x80_3x3"]
 
 

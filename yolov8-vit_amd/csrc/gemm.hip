@@ -57,6 +57,14 @@ constexpr int THREADS = 256;
 // x * sigmoid(x) through the hardware reciprocal (1 ulp) instead of an IEEE division: the division's scale / fixup sequence was
 // ~12 of the ~20 VALU instructions per output value of every detector convolution, in kernels that are VALU-issue-bound.
 __device__ __forceinline__ float silu_f(float x) { return x * __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
+// XCD-aware bijective remap of a 1-D grid of nwg workgroups: the hardware deals workgroups round robin over the eight XCDs, so XCD
+// x takes the x-th contiguous run of tiles (q + 1 tiles for the first nwg & 7 XCDs, q for the rest) and neighbours share its L2
+__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
+    const int q = nwg >> 3, r = nwg & 7, x = bid & 7;
+    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
+}
+// what a DMA lane passes for a row that reads nothing: past the descriptor's range, i.e. zeros in LDS
+constexpr uint32_t DMA_OOB = 0x80000000u;
 // 256 bytes of zeros: where a staged chunk is padding (outside the image, past K, past the last row) the conv / linear gather
 // reads THIS instead of branching around the load or masking the data afterwards
 __device__ __attribute__((aligned(256))) uint32_t g_zero_page[64];
@@ -512,10 +520,7 @@ __global__ __launch_bounds__(THREADS) void igemm_kernel(GemmArgs g) {
     int bid = blockIdx.x;
     int nwg = gridDim.x, ph = 0;
     if constexpr (PHASE) { ph = phase_of_block(g, bid); nwg = g.tiles_m * g.tiles_n; }
-    {
-        const int q = nwg >> 3, r = nwg & 7, x = bid & 7;
-        bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
-    }
+    bid = xcd_remap(bid, nwg);
     const int S = g.splitk > 1 ? g.splitk : 1;
     const int slice = bid % S;                 // K slices of one tile are neighbours: their A/W rows share L2
     bid /= S;
@@ -845,11 +850,7 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_dma_kernel(GemmArgs g) {
 
     int M = g.M;
     if (g.m_dev) { long long md = (long long)g.m_dev[0] * g.m_mul; M = md < M ? (int)md : M; }
-    int bid = blockIdx.x;
-    {
-        const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, x = bid & 7;
-        bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
-    }
+    int bid = xcd_remap(blockIdx.x, gridDim.x);
     // split-K (wgrad-shaped problems: few output tiles, long K): slices of one tile are neighbouring workgroups
     const int S = g.splitk > 1 ? g.splitk : 1;
     const int slice = bid % S;
@@ -983,20 +984,18 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_dma_kernel(GemmArgs g) {
 // VALU issue of exactly that gather and staging.  Epilogues: finish_tile (bias, SiLU, bf16 shortcut, f32 output).
 // Eligibility (host): (c0 + c1) % 64 == 0, c1 == 0 or (1 x 1 and c0 % 64 == 0), Cout >= 64, staged epilogue usable.
 // ---------------------------------------------------------------------------------------------
-// ---- device text shared by cgemm_dma_kernel and cgemm_small_kernel ----
-// What lane (lrow, lch) of the wave-instruction that fills tile row r contributes for the whole tile: the byte offset of output
-// pixel m's centre in each source (the upsampled-source shifts applied) + its swizzled 16-byte chunk, and the nine tap-validity
-// bits (none for a row past M: every read of it is out of range, i.e. zeros).
+// ---- device text shared by the LDS-DMA convolution kernels ----
+// Geometry of output pixel m (cgemm_dma_kernel, cgemm_dma32_kernel, cgemm_small_kernel, cgemm_mx_kernel): the index of the pixel at
+// its centre in each source (the upsampled-source shifts applied; p1 = 0 without a second source) and the nine tap-validity bits
+// (none for a row past M: every read of it is out of range, i.e. zeros).
 template <bool PHASE>
-__device__ __forceinline__ void cdma_lane_pixel(const GemmArgs& g, int M, int hw, int m, int r, int lch, uint32_t& off0, uint32_t& off1,
-                                                uint32_t& tap_bits) {
+__device__ __forceinline__ void conv_pixel_geom(const GemmArgs& g, int M, int hw, int m, long long& p0, long long& p1, uint32_t& tap_bits) {
     const int mc = m < M ? m : M - 1;
     const int b = mc / hw, rem = mc - b * hw;
     const int oy = rem / g.Wout;
     const int cy = oy * g.stride, cx = (rem - oy * g.Wout) * g.stride;
-    const uint32_t sw = (uint32_t)((lch ^ (r & 7)) << 4);
-    off0 = (uint32_t)((((long long)b * (g.Hin >> g.up0) + (cy >> g.up0)) * (g.Win >> g.up0) + (cx >> g.up0)) * g.lda0 * 2) + sw;
-    off1 = g.c1 ? (uint32_t)((((long long)b * (g.Hin >> g.up1) + (cy >> g.up1)) * (g.Win >> g.up1) + (cx >> g.up1)) * g.lda1 * 2) + sw : 0u;
+    p0 = ((long long)b * (g.Hin >> g.up0) + (cy >> g.up0)) * (g.Win >> g.up0) + (cx >> g.up0);
+    p1 = g.c1 ? ((long long)b * (g.Hin >> g.up1) + (cy >> g.up1)) * (g.Win >> g.up1) + (cx >> g.up1) : 0;
     uint32_t taps = 0;
     if (m < M) {
         if constexpr (PHASE) {
@@ -1012,6 +1011,17 @@ __device__ __forceinline__ void cdma_lane_pixel(const GemmArgs& g, int M, int hw
         }
     }
     tap_bits = taps;
+}
+// What lane (lrow, lch) of the wave-instruction that fills tile row r contributes for the whole tile (bf16 kernels): the geometry
+// of output pixel m as the byte offset of its centre in each source + the lane's swizzled 16-byte chunk ...
+template <bool PHASE>
+__device__ __forceinline__ void cdma_lane_pixel(const GemmArgs& g, int M, int hw, int m, int r, int lch, uint32_t& off0, uint32_t& off1,
+                                                uint32_t& tap_bits) {
+    long long p0, p1;
+    conv_pixel_geom<PHASE>(g, M, hw, m, p0, p1, tap_bits);
+    const uint32_t sw = (uint32_t)((lch ^ (r & 7)) << 4);
+    off0 = (uint32_t)(p0 * g.lda0 * 2) + sw;
+    off1 = g.c1 ? (uint32_t)(p1 * g.lda1 * 2) + sw : 0u;
 }
 // ... and for weight row r of the column tile at n0 (rows past N: the last row, never stored)
 __device__ __forceinline__ uint32_t cdma_lane_weight(const GemmArgs& g, int n0, int r, int lch) {
@@ -1038,6 +1048,95 @@ __device__ __forceinline__ uint32_t cdma_step0(const GemmArgs& g, int kb, uint32
         so = bias0 + (uint32_t)((((ky - pad) * g.Win + (kx - pad)) * g.lda0 + cin) * 2);
     }
     return so;
+}
+// What a lane holds for the life of a tile, stated ONCE for cdma_tile and csmall_tile, whose stage is filled by NWG waves, wave w
+// of them writing 8 rows x 128 B per wave-instruction (instruction j: rows (j * NWG + w) * 8 .., lane -> row lane >> 3, chunk
+// lane & 7): for each of its AI activation and WI weight instructions of a K step the offsets of cdma_lane_pixel /
+// cdma_lane_weight and the tap bits, and what is uniform: bias0, Cin and pad (cdma_step0's).
+template <int AI, int WI, int NWG>
+struct CdmaLanes {
+    uint32_t a_off0[AI], a_off1[AI], a_taps[AI], w_off[WI], bias0;
+    int Cin, pad;
+};
+// the buffer descriptor of a DMA source at p: raw, byte offsets, range to 2 GB (a lane's DMA_OOB lies past it).  The bodies build
+// theirs once per tile: built at the loads, a grouped launch re-read the fields from the kernel arguments in every K step.
+__device__ __forceinline__ auto cdma_rsrc(const void* p) { return __builtin_amdgcn_make_buffer_rsrc((void*)p, 0, 0x7fffffff, 0x00020000); }
+template <bool PHASE, int AI, int WI, int NWG>
+__device__ __forceinline__ CdmaLanes<AI, WI, NWG> cdma_lanes(const GemmArgs& g, int M, int m0, int n0, int w, int lane) {
+    CdmaLanes<AI, WI, NWG> L;
+    const int hw = g.Hout * g.Wout, lrow = lane >> 3, lch = lane & 7;
+#pragma unroll
+    for (int j = 0; j < AI; ++j) {
+        const int r = (j * NWG + w) * 8 + lrow;
+        cdma_lane_pixel<PHASE>(g, M, hw, m0 + r, r, lch, L.a_off0[j], L.a_off1[j], L.a_taps[j]);
+    }
+#pragma unroll
+    for (int j = 0; j < WI; ++j) L.w_off[j] = cdma_lane_weight(g, n0, (j * NWG + w) * 8 + lrow, lch);
+    L.bias0 = cdma_bias0<PHASE>(g);
+    L.Cin = g.c0 + g.c1;
+    L.pad = g.ksize >> 1;
+    return L;
+}
+// The activations of the K step at element kb (uniform; not the phase form), instruction j to LDS address dst(j): the second
+// source of a two-source 1 x 1, or source 0 at cdma_step0's offset under the tap's validity bit
+template <int AI, int WI, int NWG, class R, class Dst>
+__device__ __forceinline__ void cdma_gather(const GemmArgs& g, const CdmaLanes<AI, WI, NWG>& L, const R rs0, const R rs1, int kb,
+                                            const Dst& dst) {
+    if (g.c1 && kb >= g.c0) {
+        const int so = (kb - g.c0) * 2;
+#pragma unroll
+        for (int j = 0; j < AI; ++j)
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs1, (lptr_t)dst(j), 16, (int)((L.a_taps[j] & 1u) ? L.a_off1[j] : DMA_OOB), so, 0, 0);
+    } else {
+        int tap;
+        const uint32_t so = cdma_step0(g, kb, L.bias0, L.Cin, L.pad, tap);
+#pragma unroll
+        for (int j = 0; j < AI; ++j)
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs0, (lptr_t)dst(j), 16, (int)(((L.a_taps[j] >> tap) & 1u) ? L.a_off0[j] : DMA_OOB), (int)so, 0, 0);
+    }
+}
+// The K loop of cdma_tile (cgemm_dma32_kernel keeps its own copy): a ring of ST stages, ST - 1 K steps in flight, INS wave-instructions per step.
+// The launches are latency-bound (9 .. 36 K steps per tile, one L2 / HBM round trip each when only the next step is in flight), and
+// inside the pipeline the detector runs on the few CUs the classifier leaves free, where a tile's latency is all that counts.
+// Step kt: counted wait (the ST - 2 younger steps stay in flight), ONE raw barrier (step kt visible to every wave; every wave is
+// done with step kt-1, whose stage the next issue refills), issue(step, stage), step(stage): the MFMAs.  Closing barrier: the
+// staged epilogue reuses the tile buffers.
+template <int ST, int INS, class Issue, class Step>
+__device__ __forceinline__ void cdma_ring(int nk, const Issue& issue, const Step& step) {
+    static_assert(ST >= 2 && ST <= 4, "the counted waits below");
+    int issued = 0;
+#pragma unroll
+    for (int p = 0; p < ST - 1; ++p)
+        if (p < nk) { issue(p, p); ++issued; }
+    int slot = 0, islot = (ST - 1) % ST;
+    for (int kt = 0; kt < nk; ++kt) {
+        // steps issued so far: `issued` (all of them once the prologue / earlier iterations ran out of steps)
+        if (issued - kt - 1 >= ST - 2 && ST > 2) {
+            if constexpr (ST == 3) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(INS) : "memory");
+            else asm volatile("s_waitcnt vmcnt(%0)" :: "n"(2 * INS) : "memory");
+        } else {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+        asm volatile("s_barrier" ::: "memory");
+        __builtin_amdgcn_sched_barrier(0);
+        if (issued < nk) { issue(issued, islot); ++issued; islot = islot + 1 == ST ? 0 : islot + 1; }
+        const int cur = slot;
+        slot = slot + 1 == ST ? 0 : slot + 1;
+        step(cur);
+    }
+    asm volatile("s_barrier" ::: "memory");
+}
+// A wave's share of a BM x BN tile cut into WM x WN wave tiles of MF x NF fragments: the first row and column of wave tile
+// `wave`, the lane's fragment row and quad, and the accumulators at zero.
+struct WaveTile { int wrow_m, wrow_n, fr, fq; };
+template <int BM, int BN, int WM, int WN, int MF, int NF>
+__device__ __forceinline__ WaveTile wave_tile(int wave, int lane, f32x4 (&acc)[NF][MF]) {
+#pragma unroll
+    for (int i = 0; i < NF; ++i)
+#pragma unroll
+        for (int j = 0; j < MF; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    const int wm = wave / WN, wn = wave - wm * WN;
+    return {wm * (BM / WM), wn * (BN / WN), lane & 15, lane >> 4};
 }
 // one 64-deep K step of a wave tile of MF x NF fragments at rows wrow_m of A and wrow_n of W (128-byte rows, chunks swizzled)
 template <int MF, int NF>
@@ -1082,103 +1181,40 @@ __device__ __forceinline__ void cdma_tile(const GemmArgs& g, int bid, const int 
     constexpr int A_INS = BM / (8 * NW), W_INS = BN / (8 * NW);
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int M = g.M;
-    {
-        const int q = nwg >> 3, r = nwg & 7, x = bid & 7;
-        bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
-    }
+    bid = xcd_remap(bid, nwg);
     const int tm = bid / g.tiles_n, tn = bid - tm * g.tiles_n;
     const int m0 = tm * BM, n0 = tn * BN;
     if (m0 >= M) return;
 
-    const int lrow = lane >> 3, lch = lane & 7;
-    constexpr uint32_t OOB = 0x80000000u;
-    uint32_t a_off0[A_INS], a_off1[A_INS], a_taps[A_INS], w_off[W_INS];
-    const int hw = g.Hout * g.Wout;
-#pragma unroll
-    for (int j = 0; j < A_INS; ++j) {
-        const int r = (j * NW + wave) * 8 + lrow;
-        cdma_lane_pixel<PHASE>(g, M, hw, m0 + r, r, lch, a_off0[j], a_off1[j], a_taps[j]);
-    }
-#pragma unroll
-    for (int j = 0; j < W_INS; ++j) w_off[j] = cdma_lane_weight(g, n0, (j * NW + wave) * 8 + lrow, lch);
-    const uint32_t bias0 = cdma_bias0<PHASE>(g);
-    const auto rs0 = __builtin_amdgcn_make_buffer_rsrc((void*)((const unsigned char*)g.a0 - bias0), 0, 0x7fffffff, 0x00020000);
-    const auto rs1 = __builtin_amdgcn_make_buffer_rsrc((void*)(g.c1 ? g.a1 : g.a0), 0, 0x7fffffff, 0x00020000);
-    const auto rsW = __builtin_amdgcn_make_buffer_rsrc((void*)g.w, 0, 0x7fffffff, 0x00020000);
-    const int Cin = g.c0 + g.c1;
-    const int pad = g.ksize >> 1;
-    auto issue = [&](int kt, int buf) __attribute__((always_inline)) {
+    const CdmaLanes<A_INS, W_INS, NW> L = cdma_lanes<PHASE, A_INS, W_INS, NW>(g, M, m0, n0, wave, lane);
+    const auto rs0 = cdma_rsrc((const unsigned char*)g.a0 - L.bias0), rs1 = cdma_rsrc(g.c1 ? g.a1 : g.a0), rsW = cdma_rsrc(g.w);
+    const auto issue = [&](int kt, int buf) __attribute__((always_inline)) {
         unsigned char* A = smem + buf * (A_BYTES + W_BYTES);
-        unsigned char* W = A + A_BYTES;
         const int kb = kt * BK;                                  // (uniform)
+        uint32_t wcol = (uint32_t)(kb * 2);
         if constexpr (PHASE) {
             const PhaseStep ps = phase_step(g, ph, kb);
+            wcol = ps.wcol;
 #pragma unroll
             for (int j = 0; j < A_INS; ++j)
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rs0, (lptr_t)(A + (j * NW + wave) * 1024), 16,
-                                                         (int)(((a_taps[j] >> ps.slot) & 1u) ? a_off0[j] : OOB), (int)ps.src, 0, 0);
-#pragma unroll
-            for (int j = 0; j < W_INS; ++j)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsW, (lptr_t)(W + (j * NW + wave) * 1024), 16, (int)w_off[j], (int)ps.wcol, 0, 0);
-            return;
-        }
-        if (g.c1 && kb >= g.c0) {                                // second source of a two-source 1 x 1
-            const int so = (kb - g.c0) * 2;
-#pragma unroll
-            for (int j = 0; j < A_INS; ++j)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rs1, (lptr_t)(A + (j * NW + wave) * 1024), 16,
-                                                         (int)((a_taps[j] & 1u) ? a_off1[j] : OOB), so, 0, 0);
+                                                         (int)(((L.a_taps[j] >> ps.slot) & 1u) ? L.a_off0[j] : DMA_OOB), (int)ps.src, 0, 0);
         } else {
-            int tap;
-            const uint32_t so = cdma_step0(g, kb, bias0, Cin, pad, tap);
-#pragma unroll
-            for (int j = 0; j < A_INS; ++j)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rs0, (lptr_t)(A + (j * NW + wave) * 1024), 16,
-                                                         (int)(((a_taps[j] >> tap) & 1u) ? a_off0[j] : OOB), (int)so, 0, 0);
+            cdma_gather(g, L, rs0, rs1, kb, [&](int j) __attribute__((always_inline)) { return A + (j * NW + wave) * 1024; });
         }
 #pragma unroll
         for (int j = 0; j < W_INS; ++j)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsW, (lptr_t)(W + (j * NW + wave) * 1024), 16, (int)w_off[j], kb * 2, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsW, (lptr_t)(A + A_BYTES + (j * NW + wave) * 1024), 16, (int)L.w_off[j], (int)wcol, 0, 0);
     };
 
     f32x4 acc[NF][MF];
-#pragma unroll
-    for (int i = 0; i < NF; ++i)
-#pragma unroll
-        for (int j = 0; j < MF; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    const int wm = wave / WN, wn = wave - wm * WN;
-    const int wrow_m = wm * (BM / WM), wrow_n = wn * (BN / WN);
-    const int fr = lane & 15, fq = lane >> 4;
-    const int nk = PHASE ? phase_ksteps(g, ph) : g.K / BK;
-    // ring of ST stages, ST - 1 K steps in flight: the launches are latency-bound (9 .. 36 K steps per tile, one L2 / HBM round trip
-    // each when only the next step is in flight), and inside the pipeline the detector runs on the few CUs the classifier leaves
-    // free, where a tile's latency is all that counts.  Step kt: counted wait (the ST - 2 younger steps stay in flight), ONE raw
-    // barrier (step kt visible to every wave; every wave is done with step kt-1, whose stage the next issue refills), issue, MFMAs.
-    constexpr int INS = A_INS + W_INS;
-    int issued = 0;
-#pragma unroll
-    for (int p = 0; p < ST - 1; ++p)
-        if (p < nk) { issue(p, p); ++issued; }
-    int slot = 0, islot = (ST - 1) % ST;
-    for (int kt = 0; kt < nk; ++kt) {
-        // steps issued so far: `issued` (all of them once the prologue / earlier iterations ran out of steps)
-        if (issued - kt - 1 >= ST - 2 && ST > 2) {
-            if constexpr (ST == 3) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(INS) : "memory");
-            else if constexpr (ST == 4) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(2 * INS) : "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        } else {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        asm volatile("s_barrier" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-        if (issued < nk) { issue(issued, islot); ++issued; islot = islot + 1 == ST ? 0 : islot + 1; }
-        const unsigned char* A = smem + slot * (A_BYTES + W_BYTES);
-        const unsigned char* W = A + A_BYTES;
-        slot = slot + 1 == ST ? 0 : slot + 1;
-        cdma_mfma_step<MF, NF>(A, W, wrow_m, wrow_n, fr, fq, acc);
-    }
-    asm volatile("s_barrier" ::: "memory");                       // the staged epilogue reuses the tile buffers
-    finish_tile<MF, NF, STATS, WM, BN, PHASE, BNBWD>(g, acc, M, m0, n0, wrow_m, wrow_n, lane, wave, smem, tm, ph);
+    const WaveTile wt = wave_tile<BM, BN, WM, WN>(wave, lane, acc);
+    const auto step = [&](int buf) __attribute__((always_inline)) {
+        const unsigned char* A = smem + buf * (A_BYTES + W_BYTES);
+        cdma_mfma_step<MF, NF>(A, A + A_BYTES, wt.wrow_m, wt.wrow_n, wt.fr, wt.fq, acc);
+    };
+    cdma_ring<ST, A_INS + W_INS>(PHASE ? phase_ksteps(g, ph) : g.K / BK, issue, step);
+    finish_tile<MF, NF, STATS, WM, BN, PHASE, BNBWD>(g, acc, M, m0, n0, wt.wrow_m, wt.wrow_n, lane, wave, smem, tm, ph);
 }
 
 template <int BN, int WM, int WN, int ST = 2 /* LDS stages: ST - 1 K steps of DMA in flight */, bool STATS = false /* as igemm_kernel */,
@@ -1249,17 +1285,12 @@ __global__ __launch_bounds__(256) void cgemm_dma32_kernel(GemmArgs g) {
     static_assert(2 * W_RG % NW == 0 && NF == 4, "every wave issues the same count; 64-column wave tiles (the staged epilogue)");
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int M = g.M;
-    int bid = blockIdx.x;
-    {
-        const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, x = bid & 7;
-        bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
-    }
+    const int bid = xcd_remap(blockIdx.x, gridDim.x);
     const int tm = bid / g.tiles_n, tn = bid - tm * g.tiles_n;
     const int m0 = tm * BM, n0 = tn * BN;
     if (m0 >= M) return;
 
     const int lrow = lane >> 2, lch = lane & 3;
-    constexpr uint32_t OOB = 0x80000000u;
     uint32_t a_off0[A_RG], a_off1[A_RG], a_taps[A_RG], w_off[W_INS];
     const int hw = g.Hout * g.Wout;
 #pragma unroll
@@ -1274,9 +1305,7 @@ __global__ __launch_bounds__(256) void cgemm_dma32_kernel(GemmArgs g) {
         w_off[j] = cdma_lane_weight(g, n0, r, cdma32_lane_chunk(r, lch));
     }
     const uint32_t bias0 = cdma_bias0<false>(g);
-    const auto rs0 = __builtin_amdgcn_make_buffer_rsrc((void*)((const unsigned char*)g.a0 - bias0), 0, 0x7fffffff, 0x00020000);
-    const auto rs1 = __builtin_amdgcn_make_buffer_rsrc((void*)(g.c1 ? g.a1 : g.a0), 0, 0x7fffffff, 0x00020000);
-    const auto rsW = __builtin_amdgcn_make_buffer_rsrc((void*)g.w, 0, 0x7fffffff, 0x00020000);
+    const auto rs0 = cdma_rsrc((const unsigned char*)g.a0 - bias0), rs1 = cdma_rsrc(g.c1 ? g.a1 : g.a0), rsW = cdma_rsrc(g.w);
     const int Cin = g.c0 + g.c1;
     const int pad = g.ksize >> 1;
     auto issue = [&](int kt, int buf) __attribute__((always_inline)) {
@@ -1291,21 +1320,21 @@ __global__ __launch_bounds__(256) void cgemm_dma32_kernel(GemmArgs g) {
 #pragma unroll
                 for (int q = 0; q < A_RG; ++q)
                     __builtin_amdgcn_raw_ptr_buffer_load_lds(rs1, (lptr_t)(A + p * AP + (q * NW + wave) * 1024), 16,
-                                                             (int)((live && (a_taps[q] & 1u)) ? a_off1[q] : OOB), so, 0, 0);
+                                                             (int)((live && (a_taps[q] & 1u)) ? a_off1[q] : DMA_OOB), so, 0, 0);
             } else {
                 int tap;
                 const uint32_t so = cdma_step0(g, kb, bias0, Cin, pad, tap);
 #pragma unroll
                 for (int q = 0; q < A_RG; ++q)
                     __builtin_amdgcn_raw_ptr_buffer_load_lds(rs0, (lptr_t)(A + p * AP + (q * NW + wave) * 1024), 16,
-                                                             (int)((live && ((a_taps[q] >> tap) & 1u)) ? a_off0[q] : OOB), (int)so, 0, 0);
+                                                             (int)((live && ((a_taps[q] >> tap) & 1u)) ? a_off0[q] : DMA_OOB), (int)so, 0, 0);
             }
         }
 #pragma unroll
         for (int j = 0; j < W_INS; ++j) {
             const int idx = j * NW + wave, p = idx / W_RG, rg = idx - p * W_RG;
             const int kb = kt * BK + p * 32;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsW, (lptr_t)(W + p * WP + rg * 1024), 16, (int)(kb < g.K ? w_off[j] : OOB), kb * 2, 0,
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsW, (lptr_t)(W + p * WP + rg * 1024), 16, (int)(kb < g.K ? w_off[j] : DMA_OOB), kb * 2, 0,
                                                      0);
         }
     };
@@ -1319,7 +1348,8 @@ __global__ __launch_bounds__(256) void cgemm_dma32_kernel(GemmArgs g) {
     const int wrow_m = wm * (BM / WM), wrow_n = wn * (BN / WN);
     const int fr = lane & 15, fq = lane >> 4;
     const int nk = (g.K / 32 + 1) / 2;
-    // the ring of cdma_tile: ST stages, ST - 1 K steps in flight, a counted wait and ONE raw barrier per step
+    // cdma_ring's loop, and above cdma_lanes' set-up and cdma_gather's issue, in this kernel's own text: on the shared ones the
+    // 128-wide instance took 4 more SGPRs and measured 0.5 % slower (profiles/conv_one_text_bench.txt)
     constexpr int INS = 2 * A_RG + W_INS;
     int issued = 0;
 #pragma unroll
@@ -1375,57 +1405,25 @@ __device__ __forceinline__ void csmall_tile(const GemmArgs& g, int bid, const in
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int grp = wave / GW, gw = wave - grp * GW;
     const int M = g.M;
-    {
-        const int q = nwg >> 3, r = nwg & 7, x = bid & 7;
-        bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
-    }
+    bid = xcd_remap(bid, nwg);
     const int tm = bid / g.tiles_n, tn = bid - tm * g.tiles_n;
     const int m0 = tm * BM, n0 = tn * BN;
     if (m0 >= M) return;
 
-    // a group's waves fill its stage: 8 rows x 128 B per wave-instruction
-    const int lrow = lane >> 3, lch = lane & 7;
-    constexpr uint32_t OOB = 0x80000000u;
-    uint32_t a_off0[A_INS], a_off1[A_INS], a_taps[A_INS], w_off[W_INS];
-    const int hw = g.Hout * g.Wout;
-#pragma unroll
-    for (int j = 0; j < A_INS; ++j) {
-        const int r = (j * GW + gw) * 8 + lrow;
-        cdma_lane_pixel<false>(g, M, hw, m0 + r, r, lch, a_off0[j], a_off1[j], a_taps[j]);
-    }
-#pragma unroll
-    for (int j = 0; j < W_INS; ++j) w_off[j] = cdma_lane_weight(g, n0, (j * GW + gw) * 8 + lrow, lch);
-    const uint32_t bias0 = cdma_bias0<false>(g);
-    const auto rs0 = __builtin_amdgcn_make_buffer_rsrc((void*)((const unsigned char*)g.a0 - bias0), 0, 0x7fffffff, 0x00020000);
-    const auto rs1 = __builtin_amdgcn_make_buffer_rsrc((void*)(g.c1 ? g.a1 : g.a0), 0, 0x7fffffff, 0x00020000);
-    const auto rsW = __builtin_amdgcn_make_buffer_rsrc((void*)g.w, 0, 0x7fffffff, 0x00020000);
-    const int Cin = g.c0 + g.c1;
-    const int pad = g.ksize >> 1;
+    // a group's waves fill its stage
+    const CdmaLanes<A_INS, W_INS, GW> L = cdma_lanes<false, A_INS, W_INS, GW>(g, M, m0, n0, gw, lane);
+    const auto rs0 = cdma_rsrc((const unsigned char*)g.a0 - L.bias0), rs1 = cdma_rsrc(g.c1 ? g.a1 : g.a0), rsW = cdma_rsrc(g.w);
     unsigned char* const ring = smem + grp * RING;
-    auto issue = [&](int kt, int buf) __attribute__((always_inline)) {
+    const auto issue = [&](int kt, int buf) __attribute__((always_inline)) {
         unsigned char* A = ring + buf * STAGE;
-        unsigned char* W = A + BM * 128;
-        const int kb = kt * BK;                                  // (uniform)
-        if (g.c1 && kb >= g.c0) {                                // second source of a two-source 1 x 1
-            const int so = (kb - g.c0) * 2;
-#pragma unroll
-            for (int j = 0; j < A_INS; ++j)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rs1, (lptr_t)(A + (j * GW + gw) * 1024), 16,
-                                                         (int)((a_taps[j] & 1u) ? a_off1[j] : OOB), so, 0, 0);
-        } else {
-            int tap;
-            const uint32_t so = cdma_step0(g, kb, bias0, Cin, pad, tap);
-#pragma unroll
-            for (int j = 0; j < A_INS; ++j)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rs0, (lptr_t)(A + (j * GW + gw) * 1024), 16,
-                                                         (int)(((a_taps[j] >> tap) & 1u) ? a_off0[j] : OOB), (int)so, 0, 0);
-        }
+        cdma_gather(g, L, rs0, rs1, kt * BK, [&](int j) __attribute__((always_inline)) { return A + (j * GW + gw) * 1024; });
 #pragma unroll
         for (int j = 0; j < W_INS; ++j)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsW, (lptr_t)(W + (j * GW + gw) * 1024), 16, (int)w_off[j], kb * 2, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsW, (lptr_t)(A + (BM + j * GW * 8 + gw * 8) * 128), 16, (int)L.w_off[j], kt * BK * 2, 0, 0);
     };
 
     f32x4 acc[NF][MF];
+    // (wave_tile<BM, BN, WGM, 2> written out: through the helper these kernels take 4 more VGPRs, profiles/conv_one_text_resources.txt)
 #pragma unroll
     for (int i = 0; i < NF; ++i)
 #pragma unroll
@@ -1548,11 +1546,7 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_mx_kernel(MxArgs a) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     int M = g.M;
     if (g.m_dev) { long long md = (long long)g.m_dev[0] * g.m_mul; M = md < M ? (int)md : M; }
-    int bid = blockIdx.x;
-    {
-        const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, x = bid & 7;
-        bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
-    }
+    int bid = xcd_remap(blockIdx.x, gridDim.x);
     // split-K (the MX weight gradient, yv_wgrad_mxfp8: few output tiles, long token reduction): the slices of one tile are
     // neighbouring workgroups; partial sums go to g.partial, splitk_reduce_kernel adds them in slice order
     const int nsplit = g.splitk > 1 ? g.splitk : 1;
@@ -1790,47 +1784,22 @@ __global__ __launch_bounds__(256) void cgemm_mx_kernel(ConvMxArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int M = g.M;
-    int bid = blockIdx.x;
-    {
-        const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, x = bid & 7;
-        bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
-    }
+    const int bid = xcd_remap(blockIdx.x, gridDim.x);
     const int tm = bid / g.tiles_n, tn = bid - tm * g.tiles_n;
     const int m0 = tm * BM, n0 = tn * BN;
     if (m0 >= M) return;
 
-    constexpr uint32_t OOB = 0x80000000u;
     const int Cin = g.c0 + g.c1, KK = g.ksize * g.ksize;
     const int hw = g.Hout * g.Wout;
     const int sld0 = g.lda0 >> 5, sld1 = g.lda1 >> 5;
-    // pixel geometry of an output row: source pixel offsets (in pixels) and the 3 x 3 tap-validity bits
-    auto geom = [&](int m, int& p0, int& p1, uint32_t& taps) __attribute__((always_inline)) {
-        const int mc = m < M ? m : M - 1;
-        const int b = mc / hw, rem = mc - b * hw;
-        const int oy = rem / g.Wout;
-        const int cy = oy * g.stride, cx = (rem - oy * g.Wout) * g.stride;
-        p0 = ((b * (g.Hin >> g.up0) + (cy >> g.up0)) * (g.Win >> g.up0) + (cx >> g.up0));
-        p1 = g.c1 ? ((b * (g.Hin >> g.up1) + (cy >> g.up1)) * (g.Win >> g.up1) + (cx >> g.up1)) : 0;
-        taps = 0;
-        if (m < M) {
-            if (g.ksize == 3) {
-#pragma unroll
-                for (int t = 0; t < 9; ++t) {
-                    const int iy = cy + t / 3 - 1, ix = cx + t % 3 - 1;
-                    taps |= (iy >= 0 && iy < g.Hin && ix >= 0 && ix < g.Win) ? (1u << t) : 0u;
-                }
-            } else {
-                taps = 1u;
-            }
-        }
-    };
-    // DMA lanes: lane l writes half l & 1 of row l >> 1 of a 32-row piece; the half it fetches is swapped on rows with bit 3 set
+    // DMA lanes: lane l writes half l & 1 of row l >> 1 of a 32-row piece; the half it fetches is swapped on rows with bit 3 set.
+    // The pixel geometry of an output row is conv_pixel_geom's, here times the pixel stride in bytes (e4m3) + the half.
     const int lr = lane >> 1, hsrc = ((lane & 1) ^ ((lr >> 3) & 1)) << 4;
     uint32_t a_off0[A_INS], a_off1[A_INS], a_taps[A_INS], w_off[W_INS];
 #pragma unroll
     for (int j = 0; j < A_INS; ++j) {
-        int p0, p1;
-        geom(m0 + j * 32 + lr, p0, p1, a_taps[j]);
+        long long p0, p1;
+        conv_pixel_geom<false>(g, M, hw, m0 + j * 32 + lr, p0, p1, a_taps[j]);
         a_off0[j] = (uint32_t)(p0 * g.lda0 + hsrc);
         a_off1[j] = (uint32_t)(p1 * g.lda1 + hsrc);
     }
@@ -1840,18 +1809,18 @@ __global__ __launch_bounds__(256) void cgemm_mx_kernel(ConvMxArgs a) {
         n = n < g.N ? n : g.N - 1;
         w_off[j] = (uint32_t)(n * g.K + hsrc);
     }
-    const int wm = wave / WN, wn = wave - wm * WN;
-    const int wrow_m = wm * (BM / WM), wrow_n = wn * (BN / WN);
-    const int fr = lane & 15, fq = lane >> 4;
+    f32x4 acc[NF][MF];
+    const WaveTile wv = wave_tile<BM, BN, WM, WN>(wave, lane, acc);
+    const int wrow_m = wv.wrow_m, wrow_n = wv.wrow_n, fr = wv.fr, fq = wv.fq;
     // scale lanes: lane (fr, fq) of fragment row j / column i
     int s_pix0[MF], s_pix1[MF];
     uint32_t s_taps[MF];
 #pragma unroll
     for (int j = 0; j < MF; ++j) {
-        int p0, p1;
-        geom(m0 + wrow_m + j * 16 + fr, p0, p1, s_taps[j]);
-        s_pix0[j] = p0 * sld0;
-        s_pix1[j] = p1 * sld1;
+        long long p0, p1;
+        conv_pixel_geom<false>(g, M, hw, m0 + wrow_m + j * 16 + fr, p0, p1, s_taps[j]);
+        s_pix0[j] = (int)(p0 * sld0);
+        s_pix1[j] = (int)(p1 * sld1);
     }
     const uint8_t* sw_row[NF];
 #pragma unroll
@@ -1879,12 +1848,12 @@ __global__ __launch_bounds__(256) void cgemm_mx_kernel(ConvMxArgs a) {
         if (wt >= KK) {                                          // K padding: zeros
 #pragma unroll
             for (int j = 0; j < A_INS; ++j)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rs0, (lptr_t)(A + j * 1024), 16, (int)OOB, 0, 0, 0);
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rs0, (lptr_t)(A + j * 1024), 16, (int)DMA_OOB, 0, 0, 0);
         } else if (g.c1 && wc >= g.c0) {                         // second source of a two-source 1 x 1
 #pragma unroll
             for (int j = 0; j < A_INS; ++j)
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rs1, (lptr_t)(A + j * 1024), 16,
-                                                         (int)((a_taps[j] & 1u) ? a_off1[j] : OOB), wc - g.c0, 0, 0);
+                                                         (int)((a_taps[j] & 1u) ? a_off1[j] : DMA_OOB), wc - g.c0, 0, 0);
         } else {
             uint32_t so = (uint32_t)wc;
             if (g.ksize == 3) {
@@ -1894,7 +1863,7 @@ __global__ __launch_bounds__(256) void cgemm_mx_kernel(ConvMxArgs a) {
 #pragma unroll
             for (int j = 0; j < A_INS; ++j)
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rs0, (lptr_t)(A + j * 1024), 16,
-                                                         (int)(((a_taps[j] >> wt) & 1u) ? a_off0[j] : OOB), (int)so, 0, 0);
+                                                         (int)(((a_taps[j] >> wt) & 1u) ? a_off0[j] : DMA_OOB), (int)so, 0, 0);
         }
 #pragma unroll
         for (int j = 0; j < W_INS; ++j)
@@ -1927,11 +1896,6 @@ __global__ __launch_bounds__(256) void cgemm_mx_kernel(ConvMxArgs a) {
         while (lc >= Cin) { lc -= Cin; ++lt; }
     };
 
-    f32x4 acc[NF][MF];
-#pragma unroll
-    for (int i = 0; i < NF; ++i)
-#pragma unroll
-        for (int j = 0; j < MF; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
     const int nk = g.K >> 7;
     issue(0, 0);
     load_scales(0);
@@ -2429,11 +2393,7 @@ __global__ __launch_bounds__(512, 2) void gemm_mid_kernel(GemmArgs g) {
 
     int M = g.M;
     if (g.m_dev) { long long md = (long long)g.m_dev[0] * g.m_mul; M = md < M ? (int)md : M; }
-    int bid = blockIdx.x;
-    {
-        const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, x = bid & 7;
-        bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
-    }
+    const int bid = xcd_remap(blockIdx.x, gridDim.x);
     int tm, tn;
     {
         const int GM = g.group_m, per = GM * g.tiles_n;
@@ -2546,10 +2506,21 @@ int launch_dma(GemmArgs& g, hipStream_t st) {
     return launch_splitk_reduce(g, st);
 }
 
-template <int MODE, int BM, int BN, int WM, int WN>
-int launch(GemmArgs& g, hipStream_t st) {
+// What every tiled convolution launch does first: g's tile counts for BM x BN tiles and the grant of kern's dynamic LDS ...
+bool tiles_and_lds(void (*kern)(GemmArgs), GemmArgs& g, int BM, int BN, size_t lds) {
     g.tiles_m = (g.M + BM - 1) / BM;
     g.tiles_n = (g.N + BN - 1) / BN;
+    return yv_grant_lds((const void*)kern, lds);
+}
+// ... and the launch of one workgroup per tile (timed where yv_set_launch_timing armed events: the tools/conv_*_bench.py)
+int launch_tiles(void (*kern)(GemmArgs), GemmArgs& g, int BM, int BN, int threads, size_t lds, hipStream_t st) {
+    if (!tiles_and_lds(kern, g, BM, BN, lds)) return YV_ERR_LAUNCH;
+    launch_timed(kern, g.tiles_m * g.tiles_n, threads, lds, st, g);
+    return yv_launch_status();
+}
+
+template <int MODE, int BM, int BN, int WM, int WN>
+int launch(GemmArgs& g, hipStream_t st) {
     size_t lds = (size_t)(BM + BN) * 128;
     if (lds < (size_t)THREADS / 64 * (BM / WM) * 128) lds = (size_t)THREADS / 64 * (BM / WM) * 128;   // the staged epilogue's slabs
     void (*kern)(GemmArgs) = igemm_kernel<MODE, BM, BN, WM, WN, false>;
@@ -2557,7 +2528,7 @@ int launch(GemmArgs& g, hipStream_t st) {
     if constexpr (MODE == 1 && BM == 128) {                  // (g.z: yv_conv2d_bnbwd, the BatchNorm backward sums in place of STATS')
         if (g.stats) kern = g.z ? igemm_kernel<MODE, BM, BN, WM, WN, false, false, false, true> : igemm_kernel<MODE, BM, BN, WM, WN, false, true>;
     }
-    if (!yv_grant_lds((const void*)kern, lds)) return YV_ERR_LAUNCH;
+    if (!tiles_and_lds(kern, g, BM, BN, lds)) return YV_ERR_LAUNCH;
     const int S = g.splitk > 1 ? g.splitk : 1;
     // (a convolution attaches armed timing events - tools/conv_dma32_bench.py times this route as the parent's; unarmed, and for
     // the linears, the launch is the plain one)
@@ -2582,36 +2553,19 @@ int g_opt_conv_dma = 8;             // convolutions with 64-aligned input channe
 
 template <int BN, int WM, int WN, int ST>
 int launch_cdma(GemmArgs& g, hipStream_t st) {
-    g.tiles_m = (g.M + 127) / 128;
-    g.tiles_n = (g.N + BN - 1) / BN;
-    const size_t lds = ST * (size_t)(128 + BN) * 128;
     void (*kern)(GemmArgs) = cgemm_dma_kernel<BN, WM, WN, ST>;
     if (g.stats) kern = g.z ? cgemm_dma_kernel<BN, WM, WN, ST, false, false, true> : cgemm_dma_kernel<BN, WM, WN, ST, true>;
-    if (!yv_grant_lds((const void*)kern, lds)) return YV_ERR_LAUNCH;
-    launch_timed(kern, g.tiles_m * g.tiles_n, 256, lds, st, g);      // (yv_set_launch_timing: tools/conv_small_bench.py)
-    return yv_launch_status();
+    return launch_tiles(kern, g, 128, BN, 256, ST * (size_t)(128 + BN) * 128, st);
 }
 
 template <int BN, int WM, int WN, int ST>
 int launch_cdma32(GemmArgs& g, hipStream_t st) {
-    g.tiles_m = (g.M + 127) / 128;
-    g.tiles_n = (g.N + BN - 1) / BN;
-    const size_t lds = ST * (size_t)(128 + BN) * 128;
-    void (*kern)(GemmArgs) = cgemm_dma32_kernel<BN, WM, WN, ST>;
-    if (!yv_grant_lds((const void*)kern, lds)) return YV_ERR_LAUNCH;
-    launch_timed(kern, g.tiles_m * g.tiles_n, 256, lds, st, g);
-    return yv_launch_status();
+    return launch_tiles(cgemm_dma32_kernel<BN, WM, WN, ST>, g, 128, BN, 256, ST * (size_t)(128 + BN) * 128, st);
 }
 
 template <int BM, int KS>
 int launch_csmall(GemmArgs& g, hipStream_t st) {
-    g.tiles_m = (g.M + BM - 1) / BM;
-    g.tiles_n = (g.N + 63) / 64;
-    const size_t lds = KS * 2 * (size_t)(BM + 64) * 128;
-    void (*kern)(GemmArgs) = cgemm_small_kernel<BM, KS>;
-    if (!yv_grant_lds((const void*)kern, lds)) return YV_ERR_LAUNCH;
-    launch_timed(kern, g.tiles_m * g.tiles_n, 512, lds, st, g);
-    return yv_launch_status();
+    return launch_tiles(cgemm_small_kernel<BM, KS>, g, BM, 64, 512, KS * 2 * (size_t)(BM + 64) * 128, st);
 }
 
 template <int BN, int WM, int WN>
@@ -2654,6 +2608,13 @@ int g_opt_conv_dma32 = 0;           // non-zero: the convolutions with 32- but n
 int g_opt_conv_dma32_cols = 0;      // ... 64 or 128: that instance for every launch the step takes; else the measured rule
                                     // ("conv_dma32_cols"; tools/conv_dma32_bench.py and the tests time and check each instance)
 
+// a K block of `al` (64 or 32) channels lies inside one tap and one source: what the LDS-DMA gathers ask of a layer's channels
+bool chan_aligned(const GemmArgs& g, int al) { return ((g.c0 + g.c1) % al) == 0 && (g.c1 == 0 || (g.ksize == 1 && (g.c0 % al) == 0)); }
+// the large-map rule of "conv_dma" 8, of the phase launches and of the MXFP8 convolution: from 100 k output pixels the layers
+// with more than 64 output channels read their pixels once, on 128-wide tiles
+constexpr int LARGE_MAP = 100000;
+bool large_map_wide(long long M, int N) { return M >= LARGE_MAP && N > 64; }
+
 int igemm_pick(int N) { return N > 64 ? CK_IGEMM_128 : (N > 32 ? CK_IGEMM_64 : (N > 16 ? CK_IGEMM_32 : CK_IGEMM_16)); }
 
 // The route of one convolution launch: ONE rule for conv_impl_one (which launches it) and yv_conv2d_instance (which reports it).
@@ -2662,10 +2623,8 @@ int igemm_pick(int N) { return N > 64 ? CK_IGEMM_128 : (N > 32 ? CK_IGEMM_64 : (
 // their route whatever "conv_small" says.
 int conv_route(GemmArgs& g, bool have_ws, size_t ws_bytes, bool sums) {
     g.staged = g_opt_staged && epi_can_stage(g);
-    const int Cin = g.c0 + g.c1;
     // what cgemm_dma_kernel and cgemm_small_kernel ask of a layer
-    const bool dma_ok = g.N >= 64 && (Cin % 64) == 0 && (g.c1 == 0 || (g.ksize == 1 && (g.c0 % 64) == 0)) && g.staged && !g.m_dev &&
-                        (g.K % BK) == 0;
+    const bool dma_ok = g.N >= 64 && chan_aligned(g, 64) && g.staged && !g.m_dev && (g.K % BK) == 0;
     // small maps ("conv_small", off by default): the detector at a request's one or few images.  Ahead of
     // split-K and of the "conv_dma" rule, as step 2a of linear_route is ahead of its split-K.  Measured
     // (tools/conv_small_bench.py, profiles/conv_small_layers.txt: every eligible layer of YOLOv8n / s at 1, 2, 4 images of 640 x 640
@@ -2709,9 +2668,9 @@ int conv_route(GemmArgs& g, bool have_ws, size_t ws_bytes, bool sums) {
         if (g_opt_conv_dma == 5)        // by reduction depth: deep K (>= 1024) three stages / 64-wide, shallow K two stages
             return g.K >= 1024 ? CK_CDMA_64_3 : two_stage;
         if (g_opt_conv_dma == 7)        // by rows: the large maps (>= 100 k output pixels) two stages, 128-wide where Cout allows
-            return g.M >= 100000 ? two_stage : CK_CDMA_64_3;
+            return g.M >= LARGE_MAP ? two_stage : CK_CDMA_64_3;
         if (g_opt_conv_dma == 8)        // as 7, only the 128-wide layers of the large maps
-            return (g.M >= 100000 && g.N > 64) ? CK_CDMA_128_2 : CK_CDMA_64_3;
+            return large_map_wide(g.M, g.N) ? CK_CDMA_128_2 : CK_CDMA_64_3;
         if (g_opt_conv_dma == 6)        // as 5, but 64-wide tiles everywhere
             return g.K >= 1024 ? CK_CDMA_64_3 : CK_CDMA_64_2;
         return two_stage;
@@ -2720,9 +2679,7 @@ int conv_route(GemmArgs& g, bool have_ws, size_t ws_bytes, bool sums) {
     // The 64-aligned layers (Cin % 64 == 0, and c0 % 64 == 0 where there are two sources) keep their route above, whatever
     // "conv_dma" says; a two-source 1 x 1 of 64-aligned Cin whose boundary is only 32-aligned (96 + 32) is this step's.  A sums
     // call and a split-K launch keep igemm_kernel.
-    const bool chan64 = (Cin % 64) == 0 && (g.c1 == 0 || (g.ksize == 1 && (g.c0 % 64) == 0));
-    const bool chan32 = (Cin % 32) == 0 && (g.c1 == 0 || (g.ksize == 1 && (g.c0 % 32) == 0));
-    if (g_opt_conv_dma32 && !sums && g.N >= 64 && chan32 && !chan64 && g.staged && !g.m_dev && g.splitk <= 1) {
+    if (g_opt_conv_dma32 && !sums && g.N >= 64 && chan_aligned(g, 32) && !chan_aligned(g, 64) && g.staged && !g.m_dev && g.splitk <= 1) {
         if (g_opt_conv_dma32_cols == 64) return CK_DMA32_64;
         if (g_opt_conv_dma32_cols == 128) return CK_DMA32_128;
         // Measured (tools/conv_dma32_bench.py, profiles/conv_dma32_layers.txt: the 22 layers of YOLOv8m at 64, 4 and 1 images of
@@ -2781,22 +2738,18 @@ int launch_phases(void (*kern)(GemmArgs), GemmArgs& g, int threads, size_t lds, 
 
 template <int BN, int WM, int WN>
 int launch_phase_igemm(GemmArgs& g, hipStream_t st) {
-    g.tiles_m = (g.M + 127) / 128;
-    g.tiles_n = (g.N + BN - 1) / BN;
     size_t lds = (size_t)(128 + BN) * 128;
     if (lds < (size_t)THREADS / 64 * (128 / WM) * 128) lds = (size_t)THREADS / 64 * (128 / WM) * 128;   // the staged epilogue's slabs
     void (*kern)(GemmArgs) = igemm_kernel<1, 128, BN, WM, WN, false, false, true>;
-    if (!yv_grant_lds((const void*)kern, lds)) return YV_ERR_LAUNCH;
+    if (!tiles_and_lds(kern, g, 128, BN, lds)) return YV_ERR_LAUNCH;
     return launch_phases(kern, g, THREADS, lds, st);
 }
 
 template <int BN, int WM, int WN, int ST>
 int launch_phase_cdma(GemmArgs& g, hipStream_t st) {
-    g.tiles_m = (g.M + 127) / 128;
-    g.tiles_n = (g.N + BN - 1) / BN;
     const size_t lds = ST * (size_t)(128 + BN) * 128;
     void (*kern)(GemmArgs) = cgemm_dma_kernel<BN, WM, WN, ST, false, true>;
-    if (!yv_grant_lds((const void*)kern, lds)) return YV_ERR_LAUNCH;
+    if (!tiles_and_lds(kern, g, 128, BN, lds)) return YV_ERR_LAUNCH;
     return launch_phases(kern, g, 256, lds, st);
 }
 
@@ -2806,7 +2759,7 @@ int launch_phase_cdma(GemmArgs& g, hipStream_t st) {
 int dgrad_s2_route(GemmArgs& g) {
     g.staged = g_opt_staged && epi_can_stage(g);
     g.splitk = 1;
-    if (g_opt_conv_dma && g.N >= 64 && g.staged) return (g.M >= 100000 && g.N > 64) ? CK_CDMA_128_2 : CK_CDMA_64_3;
+    if (g_opt_conv_dma && g.N >= 64 && g.staged) return large_map_wide(g.M, g.N) ? CK_CDMA_128_2 : CK_CDMA_64_3;
     return igemm_pick(g.N);
 }
 
@@ -3934,7 +3887,7 @@ extern "C" int yv_quant_mxfp8_map(const void* x, long long ldx, long long pixels
 
 // instance of cgemm_mx_kernel for M output pixels, N output channels: the rule of the bf16 kernel (conv_dma 8) - 128-wide
 // tiles for the layers of the large maps (>= 100 k output pixels) with more than 64 output channels, else 64-wide
-static int conv_mx_pick(long long M, int N) { return (M >= 100000 && N > 64) ? 1 : 0; }
+static int conv_mx_pick(long long M, int N) { return large_map_wide(M, N) ? 1 : 0; }
 
 static int conv_mx_impl_one(const yv_mx_view* in0, const yv_mx_view* in1, int B, int Hout, int Wout, int ksize, int stride,
                             const void* wq, const void* wscale, long long w_rows_pad, const float* bias, int Cout,
