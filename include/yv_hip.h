@@ -51,7 +51,8 @@ int yv_device_is_gfx950(void);
  *   any other  128 x 128 LDS-DMA tiles.
  * Every value but 1 switches the skinny and the mid-M kernel off; N <= 64 or K % 64 != 0 always runs igemm_kernel; a split-K launch (a
  * registered workspace, few tiles, a long K) takes 128 x 128 tiles whatever the value says.  The forced instances check less
- * than the shipped rule does: they are for benchmarks at shapes known to suit them. */
+ * than the shipped rule does: they are for benchmarks at shapes known to suit them.
+ * "linear_ln_mid" / "linear_ln_fill": the fused LayerNorm + linear step of yv_linear_ln (see there; 0 / 0: it does not exist). */
 int yv_set_option(const char* key, int value);
 /* Current value of a knob.  "linear_p8_cus" (workgroups of the persistent classifier GEMMs; 0 = every CU) is PER THREAD: it
  * applies to the launches the calling thread makes (a pipelined runner lowers it around its own classifier submissions so that
@@ -568,6 +569,32 @@ int yv_linear_ex(const void* A, int lda, const void* W, const float* bias, int M
  * HIP call: the kernel reads float4 and writes uint2); D <= 1024 (YV_ERR_LIMIT). */
 int yv_layernorm(const float* x, size_t ldx, const float* gamma, const float* beta, int rows, int D, float eps,
                  void* y, size_t ldy, const int32_t* count_dev, int rows_per_count, void* stream);
+
+/* LayerNorm + Linear, the norm1 -> qkv and norm2 -> fc1 steps of a timm Block (README.md:21-29):
+ *   out[M,N] = LayerNorm(x[M,K]; gamma[K], beta[K], eps) @ w[N,K]^T (+bias)(+GELU), bf16 or (YV_EPI_OUT_F32) f32, row stride ldo
+ * x f32 with row stride ldx, w bf16, h (M,K) bf16 with row stride ldh: the LayerNorm output where the call writes it.
+ * Where yv_linear_ln_route answers fused = 1 the call is ONE launch of gemm_mid_ln_kernel - gemm_mid_kernel's 64 x 64 tiles, each
+ * computing the statistics of its 64 rows and normalising them while it stages them - and h is not touched.  Everywhere else it
+ * is yv_layernorm into h followed by yv_linear, the two launches of a caller without this entry.  Either way `out` has the bits of
+ * yv_layernorm followed by yv_linear on the YV_LIN_MID route.
+ * Fused: "linear_variant" 1, 256 < M <= option "linear_ln_mid" (0, the default: never) and the shape makes at most option
+ * "linear_ln_fill" eighths of the CU count in 128 x 128 tiles.  "linear_ln_fill" ships at 0 - no shape: the fused launch measured
+ * slower than the pair at every shape - and is raised by tools/ln_mid_bench.py and the tests.
+ * Checked before anything is launched, whatever the route: K % 64 == 0, N % 64 == 0, ldx % 4 == 0, ldh % 8 == 0, ldo % 4 == 0,
+ * strides not below the row length, flags within YV_EPI_BIAS | YV_EPI_GELU | YV_EPI_OUT_F32, bias where its flag is set, every
+ * pointer 16-byte aligned (YV_ERR_ARG); K <= 1024 (YV_ERR_LIMIT).  m_dev / m_mul as in yv_linear. */
+int yv_linear_ln(const float* x, size_t ldx, const float* gamma, const float* beta, float eps, void* h, int ldh, const void* w,
+                 const float* bias, void* out, int ldo, int M, int N, int K, int flags, const int32_t* m_dev, int m_mul,
+                 void* stream);
+/* The decision yv_linear_ln makes for this shape and flags under the current options, by the function the entry itself calls.
+ * Host only.  n_cu as in yv_linear_route.  A shape or flag set the fused kernel does not take answers fused = 0 (the entry may
+ * still reject it).  fused = 0: the other fields are 0. */
+typedef struct {
+    int fused;            /* 1: one launch of gemm_mid_ln_kernel, 0: yv_layernorm + yv_linear */
+    int tiles_m, tiles_n; /* 64 x 64 tiles of the fused launch: ceil(M / 64), N / 64 */
+    int workgroups;       /* tiles_m * tiles_n */
+} yv_linear_ln_route_t;
+int yv_linear_ln_route(int M, int N, int K, int flags, int n_cu, yv_linear_ln_route_t* out);
 
 /* Residual Linear + LayerNorm in one launch (timm Block: x = x + proj(attn) followed by norm2, x = x + fc2(mlp) followed
  * by the next block's norm1; README.md:21-29):

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Dev tool (GPU box): latency of ONE DetectClassifyPipeline.__call__ at request size - what inferdet.main runs per chunk - for
-YOLOv8n + ViT-B/16 and YOLOv8n + ViT-B/8 at B = 1 and 4 images of 640 x 640 with 1, 3 and 8 detections per image, in eight states:
+YOLOv8n + ViT-B/16 and YOLOv8n + ViT-B/8 at B = 1 and 4 images of 640 x 640 with 1, 3 and 8 detections per image, in ten states:
   default              the pipeline as it ships (classifier capacity B * topk = 100 B crops);
   fit_crops            DetectClassifyPipeline(fit_crops=True);
   fit_crops+mid_gemm   ... with VitEngine(mid_gemm=True);
@@ -8,8 +8,12 @@ YOLOv8n + ViT-B/16 and YOLOv8n + ViT-B/8 at B = 1 and 4 images of 640 x 640 with
   small_maps           YoloEngine(small_maps=True) alone (a sibling of the detector: the same weights);
   fit+mid+small_maps   ... on top of fit_crops + mid_gemm;
   grouped_head         YoloEngine(grouped_head=True) alone (likewise a sibling);
-  fit+mid+small_maps+grouped   every switch.
-RB_MODELS (comma-separated classifier names) restricts the classifiers.
+  fit+mid+small_maps+grouped   every switch of the above;
+  fit+mid+ln_gemm      VitEngine(mid_gemm=True, ln_gemm=True) on top of fit_crops;
+  fit+mid+small+grouped+ln     ... and on top of every switch.
+RB_MODELS (comma-separated classifier names) restricts the classifiers, RB_STATES (comma-separated labels) the states; the ratio
+column is against "default" where that state runs, else against the first state, and an ln_gemm state is also set against the
+same state without the flag.
 The detector runs on the images (its time is part of the call); the NMS then works on a synthetic candidate set in place of the
 random-weight detector's - 8400 boxes per image by the recipe of bench.py's postproc mode (centres uniform, sides U[16, 256]),
 with exactly d well-separated candidates above the thresholds - so that the crop count is the one asked for.
@@ -32,12 +36,16 @@ dev = "cuda:0"
 RUNS = int(os.environ.get("RB_RUNS", 3))
 CALLS = int(os.environ.get("RB_CALLS", 20))
 S, A, NC = 640, 8400, 5
-# (label, fit_crops, mid_gemm, (small_maps, grouped_head))
-STATES = [("default", False, False, (False, False)), ("fit_crops", True, False, (False, False)),
-          ("fit_crops+mid_gemm", True, True, (False, False)), ("mid_gemm", False, True, (False, False)),
-          ("small_maps", False, False, (True, False)), ("fit+mid+small_maps", True, True, (True, False)),
-          ("grouped_head", False, False, (False, True)), ("fit+mid+small_maps+grouped", True, True, (True, True))]
-DETECTORS = [(False, False), (True, False), (False, True), (True, True)]
+# (label, fit_crops, (mid_gemm, ln_gemm), (small_maps, grouped_head))
+STATES = [("default", False, (False, False), (False, False)), ("fit_crops", True, (False, False), (False, False)),
+          ("fit_crops+mid_gemm", True, (True, False), (False, False)), ("mid_gemm", False, (True, False), (False, False)),
+          ("small_maps", False, (False, False), (True, False)), ("fit+mid+small_maps", True, (True, False), (True, False)),
+          ("grouped_head", False, (False, False), (False, True)), ("fit+mid+small_maps+grouped", True, (True, False), (True, True)),
+          ("fit+mid+ln_gemm", True, (True, True), (False, False)), ("fit+mid+small+grouped+ln", True, (True, True), (True, True))]
+WITHOUT_LN = {"fit+mid+ln_gemm": "fit_crops+mid_gemm", "fit+mid+small+grouped+ln": "fit+mid+small_maps+grouped"}
+if os.environ.get("RB_STATES"):
+    STATES = [s for s in STATES if s[0] in os.environ["RB_STATES"].split(",")]
+DETECTORS = [w for w in [(False, False), (True, False), (False, True), (True, True)] if any(s[3] == w for s in STATES)]
 MODELS = [m for m in os.environ.get("RB_MODELS", "vit_base_patch16_224,vit_base_patch8_224").split(",") if m]
 
 
@@ -124,13 +132,13 @@ def main():
     yolo_sd = engines.init_yolo_state("n", NC, seed=42, head_gain=4.0)
     yolo = engines.YoloEngine(yolo_sd, "n", NC, S, device=dev, small_maps=False)
     dets = {}
-    for small, grouped in DETECTORS:
+    for small, grouped in [(False, False)] + [w for w in DETECTORS if any(w)]:
         dets[(small, grouped)] = e = yolo if not (small or grouped) else yolo.resized(S)
         e.small_maps, e.grouped_head = small, grouped
     g = torch.Generator().manual_seed(1234)
     for name in MODELS:
         vit_sd = engines.init_vit_wrapper_state(name, NC, seed=42)
-        vits = {mid: engines.VitEngine(vit_sd, name, NC, device=dev, mid_gemm=mid) for mid in (False, True)}
+        vits = {k: engines.VitEngine(vit_sd, name, NC, device=dev, mid_gemm=k[0], ln_gemm=k[1]) for k in sorted({s[2] for s in STATES})}
         for B in (1, 4):
             images = torch.randint(0, 256, (B, S, S, 3), generator=g, dtype=torch.uint8).to(dev)
             for d in (1, 3, 8):
@@ -164,11 +172,13 @@ def main():
                         call[label] += wall(lambda: pipes[label](images), CALLS)
                     for which in DETECTORS:
                         det[which] += wall(lambda: pipes[first[which]].detect_stage(images), CALLS)
-                t0 = median(call["default"])
+                t0 = median(call["default" if "default" in call else STATES[0][0]])
                 for label, _, _, which in STATES:
                     t, t_det = median(call[label]), median(det[which])
+                    twin = WITHOUT_LN.get(label)
+                    vs = f"  x {t / median(call[twin]):.3f} of {twin}" if twin in call else ""
                     print(f"  {name:22s} {B:2d} {d:4d} {crops[label]:5d}  {label:20s} {cap[label]:8d} {t:8.3f} {t_det:9.3f} "
-                          f"{t - t_det:11.3f} {peak[label]:9.1f}  {t / t0:6.2f}  {detect_launch_count(dets[which], B):15d}", flush=True)
+                          f"{t - t_det:11.3f} {peak[label]:9.1f}  {t / t0:6.2f}  {detect_launch_count(dets[which], B):15d}{vs}", flush=True)
                 del pipes
 
 

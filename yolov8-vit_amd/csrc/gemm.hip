@@ -2494,6 +2494,235 @@ int launch_mid(GemmArgs& g, hipStream_t st) {
     return yv_launch_status();
 }
 
+// ---------------------------------------------------------------------------------------------
+// gemm_mid_kernel with the LayerNorm that feeds it as a prologue ("linear_ln_mid": norm1 -> qkv and norm2 -> fc1 of the classifier
+// at a handful of crops).  The A operand is the f32 residual stream x (M, K <= 1024): a 64 x 64 tile walks
+// the whole row of its 64 input rows anyway, so it computes their statistics itself and normalises while it stages them, and the
+// LayerNorm launch in front of the GEMM goes away.
+//   statistics  wave w plays layernorm_kernel's wave for rows 8 w .. 8 w + 7 of the tile: lane l adds float4 chunks l, l + 64, ...
+//               as (x + y) + (z + w), wave_sum, the second pass over v - mean in the same form (the summation-order contract at the
+//               top of vit_misc.hip).  mean / rstd of the 64 rows and gamma / beta go to LDS behind the rings.  The first weight
+//               step is on its way by LDS-DMA while this runs.
+//   A staging   per K step of a half its four waves load the 64 x 64 f32 sub-tile into registers (two (row, 8-element) units per
+//               lane), form (v - mean) * rstd * g + b in layernorm_kernel's expression order, pack to bf16 and write the 16-byte
+//               chunk where gemm_mid_kernel's LDS-DMA would have put it: fragment reads, MFMA chain, exchange and epilogue are
+//               that kernel's text, and so are the result's bits.  Step kt + 2 is loaded before the MFMAs of step kt and
+//               converted after them, in front of the trip's wait and barrier.
+// W stays on LDS-DMA.  LDS: 64 KB of rings + 2 x 4 KB gamma / beta + 512 B statistics = 72.5 KB, two workgroups per CU.
+// The LayerNorm operands travel in a second argument block: GemmArgs keeps its layout (and every kernel its hidden arguments).
+// ---------------------------------------------------------------------------------------------
+int g_opt_ln_mid = 0;               // largest M the fused LayerNorm + linear takes ("linear_ln_mid"; 0 = the step does not exist)
+int g_opt_ln_mid_fill = 0;          // ... where 128 x 128 tiles number at most this many eighths of the CU count ("linear_ln_fill").
+                                    // 0: nowhere - the fused launch measured x 1.5 - 4.2 of the pair's time at every shape
+                                    // (profiles/ln_mid_kernels.txt); tools/ln_mid_bench.py and the tests raise it
+constexpr int LN_MID_MAXK = 1024;   // layernorm_kernel's LN_MAXC float4 chunks per lane
+
+struct LnOps { const float* x; long long ldx; const float* gamma; const float* beta; float eps; };
+
+__global__ __launch_bounds__(512, 2) void gemm_mid_ln_kernel(GemmArgs g, LnOps p) {
+    constexpr int BM = 64, BN = 64, MF = 2, NF = 2;
+    constexpr int STAGE = (BM + BN) * 128, RING = 2 * STAGE;    // bytes: one K step of a half, a half's two stages
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    float* const s_gamma = (float*)(smem + 2 * RING);
+    float* const s_beta = s_gamma + LN_MID_MAXK;
+    float* const s_mean = s_beta + LN_MID_MAXK;
+    float* const s_rstd = s_mean + BM;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int half = wave >> 2, w4 = wave & 3;
+
+    int M = g.M;
+    if (g.m_dev) { long long md = (long long)g.m_dev[0] * g.m_mul; M = md < M ? (int)md : M; }
+    const int bid = xcd_remap(blockIdx.x, gridDim.x);
+    int tm, tn;
+    {
+        const int GM = g.group_m, per = GM * g.tiles_n;
+        const int grp = bid / per, first = grp * GM;
+        const int gsz = (g.tiles_m - first) < GM ? (g.tiles_m - first) : GM;
+        const int in = bid - grp * per;
+        tm = first + in % gsz;
+        tn = in / gsz;
+    }
+    const int m0 = tm * BM, n0 = tn * BN;
+    if (m0 >= M) return;
+
+    // a half's four waves fill its stage: W by LDS-DMA (8 rows x 128 B per wave-instruction, 2 per wave), A through registers
+    // (lane = row lrow of the same 8-row group, 8-element chunk lch of the K step)
+    const int lrow = lane >> 3, lch = lane & 7;
+    const float* x_src[2];
+    const uint16_t* w_src[2];
+    int a_dst[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int r = (j * 4 + w4) * 8 + lrow;
+        int m = m0 + r;
+        m = m < g.M ? m : g.M - 1;                              // rows past the end: the last row, never stored
+        x_src[j] = p.x + (long long)m * p.ldx + (lch << 3);
+        w_src[j] = g.w + (long long)(n0 + r) * g.K + ((lch ^ (r & 7)) << 3);
+        a_dst[j] = r * 128 + ((lch ^ (r & 7)) << 4);
+    }
+    unsigned char* const ring = smem + half * RING;
+    auto issue_w = [&](int kt, int buf) {
+        unsigned char* W = ring + buf * STAGE + BM * 128;
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+            __builtin_amdgcn_global_load_lds((gptr_t)(w_src[j] + kt * BK), (lptr_t)(W + (j * 4 + w4) * 1024), 16, 0, 0);
+    };
+
+    const int nk = g.K / BK, trips = (nk + 1) >> 1;             // trip t: K step 2 t + half (half 1 may lack the last one)
+    if (half < nk) issue_w(half, 0);
+
+    // ---- prologue: gamma / beta to LDS, statistics of the tile's 64 rows ----
+    const int D = g.K, nch = D >> 2;
+    if (tid < nch) {
+        ((float4*)s_gamma)[tid] = ((const float4*)p.gamma)[tid];
+        ((float4*)s_beta)[tid] = ((const float4*)p.beta)[tid];
+    }
+    for (int r4 = 0; r4 < 8; r4 += 4) {                          // four rows' loads in flight at a time
+        float4 v[4][4];
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) {
+            int m = m0 + wave * 8 + r4 + rr;
+            m = m < g.M ? m : g.M - 1;
+            const float* xr = p.x + (long long)m * p.ldx;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int c = lane + 64 * i;
+                v[rr][i] = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (c < nch) v[rr][i] = ((const float4*)xr)[c];
+            }
+        }
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) {
+            float s = 0.f;
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                if (lane + 64 * i < nch) s += (v[rr][i].x + v[rr][i].y) + (v[rr][i].z + v[rr][i].w);
+            const float mean = wave_sum(s) / (float)D;
+            float q = 0.f;
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                if (lane + 64 * i < nch) {
+                    const float a = v[rr][i].x - mean, b = v[rr][i].y - mean, cc = v[rr][i].z - mean, d = v[rr][i].w - mean;
+                    q += (a * a + b * b) + (cc * cc + d * d);
+                }
+            const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)D + p.eps);
+            if (lane == 0) { s_mean[wave * 8 + r4 + rr] = mean; s_rstd[wave * 8 + r4 + rr] = rstd; }
+        }
+    }
+    __syncthreads();
+    float mean[2], rstd[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int r = (j * 4 + w4) * 8 + lrow;
+        mean[j] = s_mean[r]; rstd[j] = s_rstd[r];
+    }
+
+    float4 xa[2][2];                                            // the K step in flight: [unit][low / high four elements]
+    auto load_a = [&](int kt) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            xa[j][0] = *(const float4*)(x_src[j] + kt * BK);
+            xa[j][1] = *(const float4*)(x_src[j] + kt * BK + 4);
+        }
+    };
+    auto store_a = [&](int kt, int buf) {
+        unsigned char* A = ring + buf * STAGE;
+        const int k = kt * BK + (lch << 3);
+        const float4 g0 = *(const float4*)(s_gamma + k), g1 = *(const float4*)(s_gamma + k + 4);
+        const float4 b0 = *(const float4*)(s_beta + k), b1 = *(const float4*)(s_beta + k + 4);
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const float mu = mean[j], rs = rstd[j];
+            const float o0 = (xa[j][0].x - mu) * rs * g0.x + b0.x, o1 = (xa[j][0].y - mu) * rs * g0.y + b0.y;
+            const float o2 = (xa[j][0].z - mu) * rs * g0.z + b0.z, o3 = (xa[j][0].w - mu) * rs * g0.w + b0.w;
+            const float o4 = (xa[j][1].x - mu) * rs * g1.x + b1.x, o5 = (xa[j][1].y - mu) * rs * g1.y + b1.y;
+            const float o6 = (xa[j][1].z - mu) * rs * g1.z + b1.z, o7 = (xa[j][1].w - mu) * rs * g1.w + b1.w;
+            *(uint4*)(A + a_dst[j]) = make_uint4(pack_bf16x2(o0, o1), pack_bf16x2(o2, o3), pack_bf16x2(o4, o5), pack_bf16x2(o6, o7));
+        }
+    };
+
+    f32x4 acc[NF][MF];
+#pragma unroll
+    for (int i = 0; i < NF; ++i)
+#pragma unroll
+        for (int j = 0; j < MF; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    const int wrow_m = (w4 >> 1) * 32, wrow_n = (w4 & 1) * 32;
+    const int fr = lane & 15, fq = lane >> 4;
+
+    if (half < nk) { load_a(half); store_a(half, 0); }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    for (int t = 0; t < trips; ++t) {
+        const int cur = t & 1, kt = 2 * t + half;
+        const bool more = kt + 2 < nk;
+        if (more) { issue_w(kt + 2, cur ^ 1); load_a(kt + 2); }
+        if (kt < nk) {
+            const unsigned char* A = ring + cur * STAGE;
+            const unsigned char* W = A + BM * 128;
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks) {
+                bf16x8 fa[MF], fw[NF];
+                const int kc = ks * 4 + fq;
+#pragma unroll
+                for (int j = 0; j < MF; ++j) {
+                    const int rr = wrow_m + j * 16 + fr;
+                    fa[j] = *(const bf16x8*)(A + rr * 128 + ((kc ^ (rr & 7)) << 4));
+                }
+#pragma unroll
+                for (int i = 0; i < NF; ++i) {
+                    const int rr = wrow_n + i * 16 + fr;
+                    fw[i] = *(const bf16x8*)(W + rr * 128 + ((kc ^ (rr & 7)) << 4));
+                }
+#pragma unroll
+                for (int i = 0; i < NF; ++i)
+#pragma unroll
+                    for (int j = 0; j < MF; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fw[i], fa[j], acc[i][j], 0, 0, 0);
+            }
+        }
+        if (more) store_a(kt + 2, cur ^ 1);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();                                        // (the last one: every fragment read is done, the rings are free)
+    }
+    // exchange: xch[half][w4][i][lane] holds the fragments (i, 1 - half) of that wave, which the OTHER half finishes
+    f32x4* const xch = (f32x4*)smem;
+#pragma unroll
+    for (int i = 0; i < NF; ++i) xch[((half * 4 + w4) * NF + i) * 64 + lane] = half ? acc[i][0] : acc[i][1];
+    __syncthreads();
+    f32x4 sum[NF][1];
+#pragma unroll
+    for (int i = 0; i < NF; ++i) {
+        const f32x4 other = xch[(((1 - half) * 4 + w4) * NF + i) * 64 + lane];
+        sum[i][0] = half ? other + acc[i][1] : acc[i][0] + other;           // half 0 + half 1
+    }
+    epilogue<1, NF>(g, sum, M, m0, n0, wrow_m + half * 16, wrow_n, fr, fq);
+}
+
+int launch_mid_ln(GemmArgs& g, const LnOps& p, hipStream_t st) {
+    g.tiles_m = (g.M + 63) / 64;
+    g.tiles_n = g.N >> 6;
+    const size_t lds = 2 * 2 * (size_t)(64 + 64) * 128 + 2 * LN_MID_MAXK * sizeof(float) + 2 * 64 * sizeof(float);
+    if (!yv_grant_lds((const void*)gemm_mid_ln_kernel, lds)) return YV_ERR_LAUNCH;
+    const dim3 grid(g.tiles_m * g.tiles_n), block(512);
+    if (t_time_start || t_time_stop) {                          // (launch_timed, for a kernel of two argument blocks)
+        hipExtLaunchKernelGGL(gemm_mid_ln_kernel, grid, block, (uint32_t)lds, st, t_time_start, t_time_stop, 0, g, p);
+        t_time_start = t_time_stop = nullptr;
+    } else {
+        hipLaunchKernelGGL(gemm_mid_ln_kernel, grid, block, lds, st, g, p);
+    }
+    return yv_launch_status();
+}
+
+// The route of yv_linear_ln: ONE rule for its launch and for yv_linear_ln_route.  Pure: shape, flags and options in.  Fused where the
+// step exists ("linear_ln_mid" > 0) and the shape is one gemm_mid_ln_kernel takes - MID_FLOOR < M <= "linear_ln_mid", whole 64-wide
+// tiles and K steps, K within layernorm_kernel's bound, the epilogues of a qkv / fc1 product - and 128 x 128 tiles would number at
+// most "linear_ln_fill" eighths of the CU count; everywhere else the pair yv_layernorm + yv_linear.
+bool linear_ln_fused(int M, int N, int K, int flags, int n_cu) {
+    if (g_opt_variant != 1 || g_opt_ln_mid <= 0 || M <= MID_FLOOR || M > g_opt_ln_mid) return false;
+    if ((N & 63) || (K & 63) || K > LN_MID_MAXK || (flags & ~(YV_EPI_BIAS | YV_EPI_GELU | YV_EPI_OUT_F32))) return false;
+    const long long tiles128 = (long long)((M + 127) / 128) * ((N + 127) / 128);
+    return tiles128 * 8 <= (long long)g_opt_ln_mid_fill * n_cu;
+}
+
 template <int BM, int BN, int WM, int WN, int ABL = 0, bool WT = false>
 int launch_dma(GemmArgs& g, hipStream_t st) {
     g.tiles_m = (g.M + BM - 1) / BM;
@@ -3194,6 +3423,8 @@ static const struct { const char* key; int* (*at)(); } k_options[] = {
     {"linear_skinny", [] { return &g_opt_skinny; }},
     {"linear_mid", [] { return &g_opt_mid; }},
     {"linear_mid_fill", [] { return &g_opt_mid_fill; }},
+    {"linear_ln_mid", [] { return &g_opt_ln_mid; }},
+    {"linear_ln_fill", [] { return &g_opt_ln_mid_fill; }},
     {"wgrad_mx_split", [] { return &g_opt_wgrad_mx_split; }},
     {"conv_dma", [] { return &g_opt_conv_dma; }},
     {"conv_small", [] { return &g_opt_conv_small; }},
@@ -3312,6 +3543,44 @@ extern "C" int yv_linear_route(int M, int N, int K, int lda, int ldo, int flags,
     return linear_mx_impl(dummy, lda, dummy, (M + 127) / 128 * 128LL, dummy, dummy, (N + 127) / 128 * 128LL, f, M, N, K, dummy, ldo,
                           flags, m_dev, 1, nullptr, 0, nullptr, 0, nullptr, has_res_f32 ? f : nullptr, ldaux > 0 ? dummy : nullptr,
                           ldaux, &q);
+}
+
+extern "C" int yv_linear_ln_route(int M, int N, int K, int flags, int n_cu, yv_linear_ln_route_t* out) {
+    if (!out || M <= 0 || N <= 0 || K <= 0 || n_cu < 0) return YV_ERR_ARG;
+    n_cu = persistent_cus(n_cu);
+    if (!n_cu) return YV_ERR_LAUNCH;
+    *out = yv_linear_ln_route_t{};
+    if (linear_ln_fused(M, N, K, flags, n_cu)) {
+        out->fused = 1; out->tiles_m = (M + 63) / 64; out->tiles_n = N >> 6; out->workgroups = out->tiles_m * out->tiles_n;
+    }
+    return YV_OK;
+}
+
+extern "C" int yv_linear_ln(const float* x, size_t ldx, const float* gamma, const float* beta, float eps, void* h, int ldh,
+                            const void* w, const float* bias, void* out, int ldo, int M, int N, int K, int flags,
+                            const int32_t* m_dev, int m_mul, void* stream) {
+    if (!x || !gamma || !beta || !h || !w || !out || M < 0 || N <= 0 || K <= 0) return YV_ERR_ARG;
+    if ((K & 63) || (N & 63) || (ldx & 3) || ldx < (size_t)K || (ldh & 7) || ldh < K || (ldo & 3) || ldo < N) return YV_ERR_ARG;
+    if (flags & ~(YV_EPI_BIAS | YV_EPI_GELU | YV_EPI_OUT_F32)) return YV_ERR_ARG;
+    if ((flags & YV_EPI_BIAS) && !bias) return YV_ERR_ARG;
+    if (((uintptr_t)x | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)h | (uintptr_t)w | (uintptr_t)out) & 15) return YV_ERR_ARG;
+    if ((flags & YV_EPI_BIAS) && ((uintptr_t)bias & 15)) return YV_ERR_ARG;
+    if (K > LN_MID_MAXK) return YV_ERR_LIMIT;
+    if (M == 0) return YV_OK;
+    const int n_cu = persistent_cus();
+    if (!n_cu) return YV_ERR_LAUNCH;
+    if (!linear_ln_fused(M, N, K, flags, n_cu)) {               // the pair, exactly the two launches of a caller without this entry
+        const int rc = yv_layernorm(x, ldx, gamma, beta, M, K, eps, h, (size_t)ldh, m_dev, m_mul, stream);
+        return rc != YV_OK ? rc : yv_linear(h, ldh, w, bias, M, N, K, out, ldo, nullptr, 0, flags, m_dev, m_mul, stream);
+    }
+    GemmArgs g = {};
+    g.c0 = K;                                                   // (a0 stays null: the A operand lies behind LnOps)
+    g.w = (const uint16_t*)w; g.bias = bias; g.M = M; g.N = N; g.K = K;
+    g.out = out; g.ldo = ldo; g.flags = flags; g.m_dev = m_dev; g.m_mul = m_mul;
+    g.ksize = 1; g.stride = 1; g.splitk = 1;
+    g.group_m = g_opt_group_m > 0 ? g_opt_group_m : 8;
+    const LnOps p = {x, (long long)ldx, gamma, beta, eps};
+    return launch_mid_ln(g, p, (hipStream_t)stream);
 }
 
 // yv_conv2d_bnbwd: the BatchNorm block whose output gradient the convolution stores

@@ -95,6 +95,8 @@ _SIGS = {
                                 _vp, _i, _vp]),
     "yv_linear_mxfp8_instance": (_i, [_i, _i, _i, _i]),
     "yv_linear_route": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _sz, _i, _vp]),
+    "yv_linear_ln": (_i, [_vp, _sz, _vp, _vp, _f, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp]),
+    "yv_linear_ln_route": (_i, [_i, _i, _i, _i, _i, _vp]),
     "yv_wgrad_mxfp8": (_i, [_vp, C.c_longlong, _vp, C.c_longlong, _vp, C.c_longlong, _vp, C.c_longlong, _i, _i, _i, _vp, _i, _vp]),
     "yv_custom_nms_ws_bytes": (_sz, [_i, _i]),
     "yv_custom_nms": (_i, [_vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _sz, _vp]),
@@ -710,6 +712,48 @@ def linear(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], out: 
         lib.yv_set_launch_timing(None, None)             # not consumed when the call took a non-DMA kernel path
         hook(Mr, N, K, e0, e1)
     return out
+
+
+def linear_ln(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, h: torch.Tensor, w: torch.Tensor,
+              bias: Optional[torch.Tensor], out: torch.Tensor, flags: int = 0, eps: float = 1e-6,
+              m_dev: Optional[torch.Tensor] = None, m_mul: int = 1, M: Optional[int] = None):
+    """out[M,N] = LayerNorm(x[M,K] f32; gamma, beta, eps) @ w[N,K]^T with the epilogue `flags` select: one launch where
+    linear_ln_route answers fused (h is then not written), else layernorm into h followed by linear.  See yv_linear_ln."""
+    _chk_dev(w, bias, gamma, beta, m_dev)
+    for t in (x, h, out):                    # row-strided 2-D views are operands as they are
+        if not t.is_cuda or t.dim() != 2 or t.stride(1) != 1:
+            raise YvError("expected a device matrix with unit column stride")
+    Mr = x.shape[0] if M is None else M
+    K = x.shape[1]
+    N = w.shape[0]
+    assert w.shape[1] == K and h.shape[1] == K and out.shape[1] == N
+    assert x.dtype == torch.float32 and h.dtype == torch.bfloat16 and w.dtype == torch.bfloat16
+    assert gamma.dtype == beta.dtype == torch.float32 and gamma.numel() == beta.numel() == K
+    assert out.dtype == (torch.float32 if flags & EPI_OUT_F32 else torch.bfloat16)
+    assert min(x.shape[0], h.shape[0], out.shape[0]) >= Mr
+    if bias is not None:
+        flags |= EPI_BIAS
+    hook = LINEAR_HOOK
+    if hook is not None:                     # HIP events attached to the launch itself (the linear's, where the pair runs)
+        e0, e1 = _timing_event(), _timing_event()
+        check(lib.yv_set_launch_timing(e0.handle, e1.handle), "yv_set_launch_timing")
+    check(lib.yv_linear_ln(_p(x), x.stride(0), _p(gamma), _p(beta), float(eps), _p(h), h.stride(0), _p(w), _p(bias), _p(out),
+                           out.stride(0), Mr, N, K, flags, _p(m_dev), m_mul, _st()), "yv_linear_ln")
+    if hook is not None:
+        lib.yv_set_launch_timing(None, None)
+        hook(Mr, N, K, e0, e1)
+    return out
+
+
+LinearLnRoute = collections.namedtuple("LinearLnRoute", "fused tiles_m tiles_n workgroups")
+
+
+def linear_ln_route(M: int, N: int, K: int, flags: int = 0, n_cu: int = 0) -> LinearLnRoute:
+    """What linear_ln does for this shape under the current options (host only): see yv_linear_ln_route in include/yv_hip.h.
+    `flags` as the C entry takes them (EPI_BIAS is NOT added); n_cu = 0: the current device's CU count (needs a GPU)."""
+    out = (C.c_int * len(LinearLnRoute._fields))()
+    check(lib.yv_linear_ln_route(M, N, K, flags, n_cu, out), "yv_linear_ln_route")
+    return LinearLnRoute(*out)
 
 
 RES_LN_WIDTHS = (128, 768, 1024)          # output widths yv_linear_res_ln has an instance for (a tile spans the row)

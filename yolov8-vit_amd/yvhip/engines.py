@@ -24,7 +24,7 @@ from .guard import StepGuard
 from . import (CONV_DMA32_64, CONV_DMA32_96, CONV_DMA32_128, EPI_GELU, EPI_OUT_F32, EPI_POSEMB, EPI_RES_BF16, EPI_RES_F32, EPI_SILU,
                RES_LN_WIDTHS, YvError, attention, attention_cls, attention_long, attention_mxfp8, c2f_fused, cls_rows, conv2d,
                conv2d_group, conv2d_instance, conv2d_mxfp8, detect_decode,
-               detect_tail, get_option, layernorm, layernorm_mxfp8, linear, linear_mxfp8, linear_mxfp8_q, linear_res_ln, mx_map,
+               detect_tail, get_option, layernorm, layernorm_mxfp8, linear, linear_ln, linear_mxfp8, linear_mxfp8_q, linear_res_ln, mx_map,
                mx_view, quant_conv_weight_mxfp8, quant_mxfp8, quant_mxfp8_map, require_gpu, set_option, sppf_pool, stem_conv,
                view, wrapper_head)
 
@@ -579,10 +579,11 @@ class VitEngine:
     through the Network_Wrapper head, class logits (cap, nc) + labels (cap)."""
 
     long_attn = False                                   # opt-in (see __init__)
+    ln_gemm = False
 
     def __init__(self, state: Dict[str, torch.Tensor], name: str, num_classes: int = 5, img: int = 224,
                  device: str = "cuda:0", dtype: str = "bf16", cls_tail: bool = True, fused_ln: Optional[bool] = None,
-                 long_attn: Optional[bool] = None, mid_gemm: Optional[bool] = None):
+                 long_attn: Optional[bool] = None, mid_gemm: Optional[bool] = None, ln_gemm: Optional[bool] = None):
         """cls_tail (bf16 path): the last block runs on the cls rows only - nothing reads its other rows (see _last_block_cls);
         False gives the full last block.  The mxfp8 pass runs every block in full whatever cls_tail says, and it ignores
         full_cus_from (the attribute PipelinedRunner sets): both are properties of the bf16 block loop.
@@ -602,7 +603,14 @@ class VitEngine:
         mid_gemm (opt-in): the pass runs with the option "linear_mid" at MID_GEMM_ROWS, so its bf16 linears of 257 .. that many
         rows - the block products at a handful of crops, as DetectClassifyPipeline(fit_crops=True) sizes them - take
         gemm_mid_kernel's 64 x 64 tiles instead of 128 x 128 ones; the option is restored after the pass.  None reads the
-        environment variable YV_VIT_MID_GEMM ("1" = on, unset = off).  Off: the option is not touched."""
+        environment variable YV_VIT_MID_GEMM ("1" = on, unset = off).  Off: the option is not touched.
+        ln_gemm (bf16 path, opt-in): norm1 -> qkv and norm2 -> fc1 of the full blocks run as linear_ln, and the pass runs with the
+        option "linear_ln_mid" at MID_GEMM_ROWS (restored after it): at 257 .. that many rows, where "linear_ln_fill" admits the
+        shape, each pair is ONE launch whose 64 x 64 tiles normalise their own rows; at any other size - one crop of a /16 model,
+        a batch - linear_ln runs the layernorm + linear pair as before.  The cls tail, the final LayerNorm and the mxfp8 pass are
+        unchanged.  None reads the environment variable YV_VIT_LN_GEMM ("1" = on, unset = off; a bf16 engine without fused_ln
+        only, any other ignores the variable).  True with fused_ln or dtype "mxfp8": YvError.  Independent of mid_gemm, long_attn
+        and cls_tail."""
         require_gpu()
         if dtype not in ("bf16", "mxfp8"):
             raise YvError("dtype must be 'bf16' or 'mxfp8'")
@@ -613,6 +621,9 @@ class VitEngine:
             raise YvError("fused_ln is a property of the bf16 path (dtype='mxfp8' hands LayerNorm outputs over in MXFP8)")
         self.long_attn = _env_flag(long_attn, "YV_VIT_LONG_ATTN")
         self.mid_gemm = _env_flag(mid_gemm, "YV_VIT_MID_GEMM")
+        self.ln_gemm = _env_flag(ln_gemm, "YV_VIT_LN_GEMM") and (ln_gemm is not None or (dtype == "bf16" and not self.fused_ln))
+        if self.ln_gemm and (dtype != "bf16" or self.fused_ln):
+            raise YvError("ln_gemm is a property of the bf16 path without fused_ln (which leaves no LayerNorm in front of a linear)")
         self.fuse_attention_quant = os.environ.get("YV_MX_ATTN_FUSED", "1") == "1"     # A/B switch of the mxfp8 path
         self.P, self.D, self.L, self.H = vit_cfg(name)
         if self.D // self.H != 64:
@@ -708,6 +719,16 @@ class VitEngine:
             return feats if outer else feats.clone()         # bare call: a copy that the next replay cannot overwrite
 
     def _backbone(self, patches: torch.Tensor, cap: int, count: Optional[torch.Tensor], slot: int) -> torch.Tensor:
+        if not self.ln_gemm:
+            return self._backbone_mid(patches, cap, count, slot)
+        ln_mid = get_option("linear_ln_mid")
+        set_option("linear_ln_mid", MID_GEMM_ROWS)
+        try:
+            return self._backbone_mid(patches, cap, count, slot)
+        finally:
+            set_option("linear_ln_mid", ln_mid)
+
+    def _backbone_mid(self, patches: torch.Tensor, cap: int, count: Optional[torch.Tensor], slot: int) -> torch.Tensor:
         if not self.mid_gemm:
             return self._backbone_tail(patches, cap, count, slot)
         mid = get_option("linear_mid")
@@ -761,23 +782,32 @@ class VitEngine:
         rows = cap * N
         # fused_ln: every proj also writes its block's norm2 output and every fc2 (but the last block's) the NEXT block's norm1 output
         # (linear_res_ln), so of the 2L block LayerNorms only block 0's norm1 - its input comes from patch-embed + cls_rows - remains
-        fused = self.fused_ln
+        # ln_gemm: norm1 -> qkv and norm2 -> fc1 are linear_ln calls (one launch where its route fuses, else the same pair; h is
+        # written on the pair route only - nothing else reads it in a full block)
+        fused, ln_gemm = self.fused_ln, self.ln_gemm
         for i, blk in enumerate(self.blocks):
             if self.full_cus_from is not None and i == self.full_cus_from:
                 set_option("linear_p8_cus", 0)          # the caller (PipelinedRunner) restores its own setting after the pass
             if self.cls_tail and i == self.L - 1:
                 self._last_block_cls(b, blk, cap, count, norm1_done=fused and i > 0)
                 break
-            if not (fused and i > 0):
-                layernorm(x, blk["n1w"], blk["n1b"], h, rows, D, D, D, count_dev=count, rows_per_count=N)
-            linear(h, blk["wqkv"], blk["bqkv"], qkv, m_dev=count, m_mul=N)
+            if ln_gemm:
+                linear_ln(x, blk["n1w"], blk["n1b"], h, blk["wqkv"], blk["bqkv"], qkv, m_dev=count, m_mul=N)
+            else:
+                if not (fused and i > 0):
+                    layernorm(x, blk["n1w"], blk["n1b"], h, rows, D, D, D, count_dev=count, rows_per_count=N)
+                linear(h, blk["wqkv"], blk["bqkv"], qkv, m_dev=count, m_mul=N)
             self._attention(b, cap, count)
             if fused:
                 linear_res_ln(o, blk["wproj"], blk["bproj"], x, blk["n2w"], blk["n2b"], h, m_dev=count, m_mul=N)
             else:
                 linear(o, blk["wproj"], blk["bproj"], x, flags=EPI_RES_F32, m_dev=count, m_mul=N)
-                layernorm(x, blk["n2w"], blk["n2b"], h, rows, D, D, D, count_dev=count, rows_per_count=N)
-            linear(h, blk["wfc1"], blk["bfc1"], gbuf, flags=EPI_GELU, m_dev=count, m_mul=N)
+                if not ln_gemm:
+                    layernorm(x, blk["n2w"], blk["n2b"], h, rows, D, D, D, count_dev=count, rows_per_count=N)
+            if ln_gemm:
+                linear_ln(x, blk["n2w"], blk["n2b"], h, blk["wfc1"], blk["bfc1"], gbuf, flags=EPI_GELU, m_dev=count, m_mul=N)
+            else:
+                linear(h, blk["wfc1"], blk["bfc1"], gbuf, flags=EPI_GELU, m_dev=count, m_mul=N)
             if fused and i + 1 < self.L:
                 nxt = self.blocks[i + 1]
                 linear_res_ln(gbuf, blk["wfc2"], blk["bfc2"], x, nxt["n1w"], nxt["n1b"], h, m_dev=count, m_mul=N)
