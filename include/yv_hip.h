@@ -227,6 +227,22 @@ int yv_compact_crops_split(const int32_t* det_count, const int32_t* crop_rect, c
 int yv_crop_resize_norm(const uint8_t* images, int B, int H, int W, size_t img_stride, const int32_t* crop_list,
                         const int32_t* crop_total, int cap, int out_size, int patch, int layout, void* out,
                         void* stream);
+/* One packed result record per request (yvhip.request.RequestSession): the join of crop_list with the detection arrays and the
+ * classifier's outputs that YOLOTensorRT inferdet.main does per object (YOLOTensorRT_yolodet_py_解读.md:100-116), as one buffer
+ * of 32-bit words that one copy brings to the host.  out (1 + cap, W) i32, W = 9 + nc:
+ *   row 0      {total, B, slots, cap, nc, 0, ...} with total = min(crop_total[0], cap)
+ *   row 1 + k  (k < total), from crop_list[k] = {image, x0, y0, x1, y1, slot}:
+ *              {image, slot, det_box[image, slot, 0..3], det_label[image, slot], cls_label[k], bits of det_score[image, slot],
+ *               bits of cls_logits[k, 0..nc)}
+ *   rows past total: zero (every word of out is written on every launch).
+ * The order is crop_list's: image ascending, then score order.  det_* are yv_postprocess_dets' (B, slots, ..) outputs;
+ * cls_label (>= cap) i32 and cls_logits (>= cap, nc) f32 the classifier's.  One launch, no workspace, no atomics, nothing but
+ * the launch in the call (it is captured into graphs).  A null pointer, B, slots or nc <= 0, cap < 0: YV_ERR_ARG, decided on the
+ * host before any HIP call; cap == 0 writes the header only. */
+int yv_pack_results(const int32_t* crop_list, const int32_t* crop_total, const int32_t* det_box, const float* det_score,
+                    const int32_t* det_label, const int32_t* cls_label, const float* cls_logits, int B, int slots, int cap,
+                    int nc, int32_t* out, void* stream);
+
 /* Diagnostics: forced number of 16-row groups a block of the crop kernel walks (0 = chosen from the crop count). */
 int yv_crop_debug(int groups_per_block);
 

@@ -23,7 +23,9 @@ each detector - unflagged, small_maps, grouped_head, both - and each state is li
 detect stage, DERIVED, not observed: the entries of the detector's launch list, a ConvGroup entry counted as the launches that
 yvhip.conv2d_group_plan - the partition function of the launch itself - reports for it under the pass's options, plus the tail's
 one; and the peak of torch.cuda.max_memory_allocated over a call above what was allocated before the first call of that shape
-(the engines' activation buffers: every engine starts each shape with none)."""
+(the engines' activation buffers: every engine starts each shape with none).
+--e2e times instead host arrays in to records out - inferdet.run_chunk, eager, against yvhip.request.RequestSession.run, two graph
+replays - at the same shapes (end_to_end; RB_ROWS restricts its rows); profiles/request_bench_graph.txt is its output."""
 import gc, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "yolov8-vit_amd"))
@@ -182,5 +184,127 @@ def main():
                 del pipes
 
 
+# --e2e rows: (label, session?, fit_crops, mid_gemm, (small_maps, grouped_head))
+E2E_ROWS = [("eager chunk", False, False, False, (False, False)),
+            ("eager chunk fit+mid", False, True, True, (False, False)),
+            ("eager chunk fit+mid+small+grouped", False, True, True, (True, True)),
+            ("session", True, True, False, (False, False)),
+            ("session mid", True, True, True, (False, False)),
+            ("session small+grouped", True, True, False, (True, True)),
+            ("session mid+small+grouped", True, True, True, (True, True))]
+E2E_CAND = {}                                                       # B -> (boxes, scores): static, the scores rewritten in place
+
+
+def e2e_candidates(B, d):
+    """candidates(B, 8)'s boxes once per B; the scores of the first d per image raised in place (a captured graph reads them)."""
+    if B not in E2E_CAND:
+        boxes, _ = candidates(B, 8)
+        E2E_CAND[B] = (boxes, torch.full((B, A, NC), 0.01, device=dev))
+    s = torch.full((B, A, NC), 0.01)
+    for b in range(B):
+        for k in range(d):
+            s[b, k, (b + k) % NC] = 0.9
+    E2E_CAND[B][1].copy_(s)
+    torch.cuda.synchronize()
+
+
+def e2e_detect(pipe):
+    def detect(images):
+        pipe.yolo(images)
+        boxes, scores = E2E_CAND[images.shape[0]]
+        return yvhip.efficient_nms(boxes, scores, pipe.score_threshold, pipe.iou_threshold, pipe.topk)
+    pipe.detect = detect
+    return pipe
+
+
+def end_to_end():
+    """--e2e: host arrays in to records out, per chunk of B images of 640 x 640 - what inferdet.main does per chunk besides reading
+    the files: the eager chunk function (inferdet.run_chunk: canvas + four geometry uploads, letterbox, the pipeline call, seven
+    reads) against yvhip.request.RequestSession.run (one canvas + one block upload, two graph replays, one count read, one record
+    download) over the same engines, rows interleaved in one process, same shapes and method as the ten states.  A session is
+    built once per row and classifier and keeps its keys across B and detections, as a server's would.  Reported: the median
+    call; the session's two stages apart (host clock: uploads -> crop count, -> records); per key's first visit (eager warm-up,
+    capture, first replay) the peak of torch.cuda.max_memory_allocated above the allocation before it, what stays allocated after
+    it, and the growth of the reserved pool - the engines' buffer sets of that size exist before (an eager fitted chunk on the same
+    engines runs first), the session's stream has its workspace, so this is the static buffers and the graphs' pools."""
+    from YOLOTensorRT.inferdet import run_chunk
+    from yvhip.request import RequestSession
+    rows = [r for r in E2E_ROWS if not os.environ.get("RB_ROWS") or r[0] in os.environ["RB_ROWS"].split(",")]
+    print(f"# {torch.cuda.get_device_name(0)}; host arrays in -> records out, ms per chunk, median of {RUNS} x {CALLS} calls, rows "
+          f"interleaved; memory in MB at the first visit of the row's key (B, 640, 640, capacity)")
+    print(f"# {'classifier':22s} {'B':>2s} {'dets':>4s} {'crops':>5s}  {'row':34s} {'capacity':>8s} {'call ms':>8s} {'stage1 ms':>9s} "
+          f"{'stage2 ms':>9s}  {'/ eager':>7s} {'/ fit+mid':>9s}  {'peak MB':>8s} {'held MB':>8s} {'reserved MB':>11s}")
+    yolo = engines.YoloEngine(engines.init_yolo_state("n", NC, seed=42, head_gain=4.0), "n", NC, S, device=dev, small_maps=False)
+    dets = {(False, False): yolo}
+    if any(r[4] == (True, True) for r in rows):
+        dets[(True, True)] = e = yolo.resized(S)
+        e.small_maps, e.grouped_head = True, True
+    g = torch.Generator().manual_seed(1234)
+    for name in MODELS:
+        vit_sd = engines.init_vit_wrapper_state(name, NC, seed=42)
+        vits = {m: engines.VitEngine(vit_sd, name, NC, device=dev, mid_gemm=m) for m in sorted({r[3] for r in rows})}
+        pipes, sessions, fitted = {}, {}, {}
+        for label, ses, fit, mid, which in rows:
+            pipes[label] = e2e_detect(DetectClassifyPipeline(dets[which], [vits[mid]], fit_crops=fit))
+            if ses:
+                fitted[label] = e2e_detect(DetectClassifyPipeline(dets[which], [vits[mid]], fit_crops=True))
+                sessions[label] = s = RequestSession(pipes[label])
+                with torch.cuda.stream(s.stream):
+                    yvhip._st()                                   # the stream's split-K workspace: not a cost of a key
+        seen = set()
+        for B in (1, 4):
+            arrs = [a.numpy() for a in torch.randint(0, 256, (B, S, S, 3), generator=g, dtype=torch.uint8)]
+            for d in (1, 3, 8):
+                e2e_candidates(B, d)
+                timing = {label: [] for label in sessions}
+
+                def call(label):
+                    if label in sessions:
+                        t = {}
+                        rec = sessions[label].run(arrs, timing=t)
+                        timing[label].append(t)
+                        return len(rec["image"])
+                    return len(run_chunk(pipes[label], arrs, (S, S), S, dev)[4])
+                mem, crops, cap = {}, {}, {}
+                for label, ses, *_ in rows:                     # first visits
+                    if ses:                                     # the engines' buffer sets of this size exist before the key is made
+                        run_chunk(fitted[label], arrs, (S, S), S, dev)
+                    gc.collect(); torch.cuda.synchronize(); torch.cuda.empty_cache()
+                    base, rbase = torch.cuda.memory_allocated(), torch.cuda.memory_reserved()
+                    torch.cuda.reset_peak_memory_stats()
+                    crops[label] = call(label)
+                    torch.cuda.synchronize()
+                    key = (label, B, sessions[label].last["capacity"]) if ses else None
+                    if ses and key not in seen:
+                        seen.add(key)
+                        mem[label] = ((torch.cuda.max_memory_allocated() - base) / 2 ** 20, (torch.cuda.memory_allocated() - base) / 2 ** 20,
+                                      (torch.cuda.memory_reserved() - rbase) / 2 ** 20)
+                    cap[label] = sessions[label].last["capacity"] if ses else "-"
+                    if crops[label] != B * d:
+                        print(f"# note: {label}: {crops[label]} crops where {B * d} were injected")
+                for label, *_ in rows:
+                    wall(lambda: call(label), 3)
+                for t in timing.values():
+                    t.clear()
+                ms = {label: [] for label, *_ in rows}
+                for rd in range(RUNS):
+                    for label, *_ in rows:
+                        ms[label] += wall(lambda: call(label), CALLS)
+                t0 = median(ms[rows[0][0]])
+                t1 = median(ms["eager chunk fit+mid"]) if "eager chunk fit+mid" in ms else None
+                for label, ses, *_ in rows:
+                    t = median(ms[label])
+                    st = (f"{median([x['stage1'] for x in timing[label]]) * 1e3:9.3f} {median([x['stage2'] for x in timing[label]]) * 1e3:9.3f}"
+                          if ses else f"{'-':>9s} {'-':>9s}")
+                    m = "  ".join(f"{v:8.1f}" for v in mem[label]) if label in mem else ""
+                    r1 = f"{t / t1:9.2f}" if t1 else f"{'-':>9s}"
+                    print(f"  {name:22s} {B:2d} {d:4d} {crops[label]:5d}  {label:34s} {str(cap[label]):>8s} {t:8.3f} {st}  {t / t0:7.2f} {r1}  {m}",
+                          flush=True)
+        for label, s in sessions.items():
+            print(f"# {name}, {label}: stats {s.stats}, keys {[(k, sorted(v.stage2)) for k, v in s.keys.items()]}")
+        del pipes, sessions, fitted
+
+
 if __name__ == "__main__":
-    trace_one() if "--trace" in sys.argv[1:] else main()
+    args = sys.argv[1:]
+    trace_one() if "--trace" in args else end_to_end() if "--e2e" in args else main()

@@ -108,6 +108,7 @@ _SIGS = {
     "yv_compact_crops": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "yv_compact_crops_split": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "yv_crop_resize_norm": (_i, [_vp, _i, _i, _i, _sz, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "yv_pack_results": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "yv_letterbox": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp]),
     "yv_letterbox_hw": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _vp, _vp]),
     "yv_augment_patchify": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
@@ -405,6 +406,31 @@ def crop_resize_norm(images: torch.Tensor, crop_list: torch.Tensor, crop_total: 
             out = torch.zeros((cap * g * g, 3 * patch * patch), dtype=torch.bfloat16, device=dev)
     check(lib.yv_crop_resize_norm(_p(images), B, H, W, H * W * 3, _p(crop_list), _p(crop_total), cap, out_size,
                                   patch, layout, _p(out), _st()), "yv_crop_resize_norm")
+    return out
+
+
+def pack_results(det: dict, cls_label: torch.Tensor, cls_logits: torch.Tensor, cap: int,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """det: the detect stage's dict (crop_list, crop_total, det_box, det_score, det_label); cls_label (>= cap) i32 and cls_logits
+    (>= cap, nc) f32 the classifier's -> (1 + cap, 9 + nc) i32 records (yv_pack_results; yvhip.request.unpack_results reads
+    them).  One launch and nothing else, so it can be captured; out: a buffer of that shape to write instead of a new one."""
+    cl, ct, box, sc, lab = det["crop_list"], det["crop_total"], det["det_box"], det["det_score"], det["det_label"]
+    _chk_dev(cl, ct, box, sc, lab, cls_label, cls_logits, out)
+    cap = int(cap)
+    if cls_logits.dim() != 2 or sc.dim() != 2:
+        raise YvError("pack_results: det_score is (B, slots) and cls_logits (cap, nc)")
+    (B, slots), nc = sc.shape, cls_logits.shape[1]
+    if cap < 0 or cap > cl.shape[0] or cap > cls_logits.shape[0] or cap > cls_label.shape[0]:
+        raise YvError("pack_results: cap exceeds the crop list or the classifier's outputs")
+    if (cl.dtype, ct.dtype, box.dtype, lab.dtype, cls_label.dtype) != (torch.int32,) * 5 or \
+            (sc.dtype, cls_logits.dtype) != (torch.float32,) * 2 or tuple(box.shape) != (B, slots, 4) or tuple(lab.shape) != (B, slots):
+        raise YvError("pack_results: operands do not have the detect stage's types and shapes")
+    if out is None:
+        out = torch.empty((1 + cap, 9 + nc), dtype=torch.int32, device=sc.device)
+    elif out.dtype != torch.int32 or tuple(out.shape) != (1 + cap, 9 + nc):
+        raise YvError(f"pack_results: out must be ({1 + cap}, {9 + nc}) int32")
+    check(lib.yv_pack_results(_p(cl), _p(ct), _p(box), _p(sc), _p(lab), _p(cls_label), _p(cls_logits), B, slots, cap, nc,
+                              _p(out), _st()), "yv_pack_results")
     return out
 
 
