@@ -52,7 +52,12 @@ int yv_device_is_gfx950(void);
  * Every value but 1 switches the skinny and the mid-M kernel off; N <= 64 or K % 64 != 0 always runs igemm_kernel; a split-K launch (a
  * registered workspace, few tiles, a long K) takes 128 x 128 tiles whatever the value says.  The forced instances check less
  * than the shipped rule does: they are for benchmarks at shapes known to suit them.
- * "linear_ln_mid" / "linear_ln_fill": the fused LayerNorm + linear step of yv_linear_ln (see there; 0 / 0: it does not exist). */
+ * "linear_ln_mid" / "linear_ln_fill": the fused LayerNorm + linear step of yv_linear_ln (see there; 0 / 0: it does not exist).
+ * "linear_mx_mid" / "linear_mx_mid_fill": the mid-M step of the MXFP8 linears (yv_linear_mxfp8 / yv_linear_mxfp8_q), ahead of their
+ * persistent rule.  "linear_mx_mid" is the largest M gemm_mx_mid_kernel takes (0 = the step does not exist, the default;
+ * "linear_variant" does not bear on it); it takes 1 <= M <= that, N % 64 == 0, N > 64, K % 128 == 0, flags within BIAS | GELU |
+ * RES_F32 | OUT_F32 (| OUT_MXFP8 from yv_linear_mxfp8_q), no separate residual source and no aux tensor, where 128 x 128 tiles
+ * number at most "linear_mx_mid_fill" eighths of the CU count. */
 int yv_set_option(const char* key, int value);
 /* Current value of a knob.  "linear_p8_cus" (workgroups of the persistent classifier GEMMs; 0 = every CU) is PER THREAD: it
  * applies to the launches the calling thread makes (a pipelined runner lowers it around its own classifier submissions so that
@@ -127,6 +132,7 @@ int yv_linear_mxfp8_instance(int M, int N, int K, int flags);
 #define YV_LIN_P9 4     /* gemm_p9_kernel<tile_rows / 32, f32out, 0, ext, mx>: persistent, free-running, tile_rows x 256    */
 #define YV_LIN_MX 5     /* gemm_mx_kernel<128, 128, 2, 2> (mx = 1 only)                                                     */
 #define YV_LIN_MID 6    /* gemm_mid_kernel, 64 x 64 tiles, K split over its two wave groups ("linear_mid" > 0 only)         */
+#define YV_LIN_MX_MID 7 /* gemm_mx_mid_kernel, 64 x 64 tiles, K steps dealt to two wave groups (mx = 1, "linear_mx_mid" > 0)   */
 #define YV_ROUTE_M_DEV 0x40000000 /* yv_linear_route's `flags` only */
 typedef struct {
     int kernel;               /* YV_LIN_* */
@@ -141,6 +147,10 @@ typedef struct {
 } yv_linear_route_t;
 int yv_linear_route(int M, int N, int K, int lda, int ldo, int flags, int has_res_f32, int ldaux, int mx, size_t ws_bytes,
                     int n_cu, yv_linear_route_t* out);
+/* The route of yv_linear_mxfp8_q (which yv_linear_route, like yv_linear_mxfp8, rejects: YV_EPI_OUT_MXFP8 is internal).  Host only,
+ * as yv_linear_route: dense operands and output (lda = K, ldq = N bytes), scale rows rounded up to 128; flags within YV_EPI_BIAS |
+ * YV_EPI_GELU (| YV_ROUTE_M_DEV), N a multiple of 128 - what yv_linear_mxfp8_q checks, else its YV_ERR_ARG. */
+int yv_linear_mxfp8_q_route(int M, int N, int K, int flags, int n_cu, yv_linear_route_t* out);
 /* MX weight gradient: dW (N, K) f32 (row stride ldw) = dY^T . X over T_pad tokens, from the column forms of
  * yv_quant_mxfp8_2d: dYt (N, T_pad) bytes (row stride ldy) + scales (T_pad/128, dy_rows_pad, 4), Xt (K, T_pad) bytes (row
  * stride ldx) + scales (T_pad/128, x_rows_pad, 4).  Split over tokens through the stream's workspace (yv_set_workspace);

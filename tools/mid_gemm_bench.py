@@ -9,7 +9,11 @@ The engine's own flags, row count on the device (m_dev = crops, m_mul = tokens) 
 tools/tail_bench.py: kernel times from the launch's own dispatch packet (yv_set_launch_timing), every launch of a series on
 another copy of its weights (MGB_COPIES, default 12), median of the launches of MGB_ROUNDS interleaved rounds.
 Prints the table and, per model and over all, the largest M up to which every product the route step takes is at least as fast
-on the mid kernel as on the parent's route (the bound "linear_mid" ships with is at most 4,096)."""
+on the mid kernel as on the parent's route (the bound "linear_mid" ships with is at most 4,096).
+--mx: the same models, products and crop counts for an mxfp8 engine (linear_mxfp8; fc1 as linear_mxfp8_q, its fc1 -> fc2 hand-over)
+on two routes: parent ("linear_mx_mid" = 0: gemm_mx_kernel 128 x 128, the persistent kernel where its rule takes the shape) and
+mid (gemm_mx_mid_kernel, "linear_mx_mid" = M, from one row on), measured the same way; the column "tiles" is the count of
+128 x 128 tiles "linear_mx_mid_fill" is compared with (tiles * 8 <= fill * CUs)."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "yolov8-vit_amd"))
@@ -107,5 +111,80 @@ def main():
     print(f"# all models: every product the step takes is at least as fast up to M = {max(good) if good else 0} "
           f"(largest M measured with such a product: {max(every) if every else 0}; the bound is at most 4,096)")
 
+def main_mx():
+    keys = ("linear_mx_mid", "linear_mx_mid_fill")
+    shipped = {k: yvhip.get_option(k) for k in keys}
+    n_cu = torch.cuda.get_device_properties(0).multi_processor_count
+    kname = {**KERNEL, E.LIN_MX: "mx128", E.LIN_MX_MID: "mxmid"}
+    print(f"# {torch.cuda.get_device_name(0)}, {n_cu} CUs; MXFP8 operands; us per launch, median of {ROUNDS} x {2 * COPIES} launches; "
+          f"mid / parent in the last columns; shipped linear_mx_mid_fill = {shipped['linear_mx_mid_fill']}")
+    print(f"# {'model':22s} {'product':5s} {'crops':>5s} {'M':>6s} {'N':>5s} {'K':>5s} {'tiles':>5s}  {'parent':>16s} {'mid':>8s}  mid/parent routed")
+    rows = []                                                # (tiles, M, ratio, routed)
+    for name, D, tok in MODELS:
+        products = [("qkv", 3 * D, D, 0, torch.bfloat16, False), ("proj", D, D, E.EPI_RES_F32, torch.float32, False),
+                    ("fc1", 4 * D, D, E.EPI_GELU, None, True), ("fc2", D, 4 * D, E.EPI_RES_F32, torch.float32, False)]
+        for crops in CROPS:
+            M = crops * tok
+            cnt = torch.tensor([crops], dtype=torch.int32, device=dev)
+            for pname, n, k, flags, odt, qform in products:
+                aq, asc = yvhip.quant_mxfp8(torch.randn(M, k, generator=g, device=dev).to(torch.bfloat16))
+                ws = [yvhip.quant_mxfp8((torch.randn(n, k, generator=g, device=dev) * 0.05).to(torch.bfloat16)) for _ in range(COPIES)]
+                bias = torch.randn(n, generator=g, device=dev)
+                if qform:
+                    oq = torch.zeros(M, n, dtype=torch.uint8, device=dev)
+                    osc = torch.zeros(n // 128, (M + 255) // 256 * 256, 4, dtype=torch.uint8, device=dev)
+                    call = lambda i: yvhip.linear_mxfp8_q(aq, asc, ws[i % COPIES][0], ws[i % COPIES][1], bias, oq, osc, flags=flags,
+                                                          m_dev=cnt, m_mul=tok)
+                    route = lambda: yvhip.linear_mxfp8_q_route(M, n, k, flags | E.EPI_BIAS, m_dev=True)
+                else:
+                    out = torch.zeros(M, n, dtype=odt, device=dev)
+                    call = lambda i: yvhip.linear_mxfp8(aq, asc, ws[i % COPIES][0], ws[i % COPIES][1], bias, out, flags=flags,
+                                                        m_dev=cnt, m_mul=tok)
+                    route = lambda: yvhip.linear_route(M, n, k, flags | E.EPI_BIAS, mx=True, m_dev=True)
+                routes = {"parent": dict(linear_mx_mid=0, linear_mx_mid_fill=shipped["linear_mx_mid_fill"])}
+                routed = False
+                if M <= MID_MAX:
+                    routes["mid"] = dict(linear_mx_mid=M, linear_mx_mid_fill=1 << 20)
+                    yvhip.set_option("linear_mx_mid", M)
+                    routed = route().kernel == E.LIN_MX_MID
+                    yvhip.set_option("linear_mx_mid", shipped["linear_mx_mid"])
+                ts = {r: [] for r in routes}
+                kern = {}
+                try:
+                    for rd in range(ROUNDS):
+                        for r, opts in routes.items():
+                            for key, v in opts.items():
+                                yvhip.set_option(key, v)
+                            kern[r] = kname[route().kernel]
+                            ts[r] += timed_linear(call, 2 * COPIES)
+                finally:
+                    for key, v in shipped.items():
+                        yvhip.set_option(key, v)
+                assert kern.get("mid", "mxmid") == "mxmid" and kern["parent"] in ("mx128", "p9"), kern
+                t = {r: median(v) for r, v in ts.items()}
+                tiles = ((M + 127) // 128) * ((n + 127) // 128)
+                ratio = t["mid"] / t["parent"] if "mid" in t else None
+                if ratio is not None:
+                    rows.append((tiles, M, ratio, routed))
+                mid = f"{t['mid']:8.1f}" if "mid" in t else f"{'-':>8s}"
+                print(f"  {name:22s} {pname:5s} {crops:5d} {M:6d} {n:5d} {k:5d} {tiles:5d}  {t['parent']:8.1f} {kern['parent']:>7s} {mid}  "
+                      f"{'' if ratio is None else f'{ratio:6.2f}     ' + ('yes' if routed else 'no')}", flush=True)
+                del aq, asc, ws
+    print("#")
+    rows.sort()
+    lost = [r for r in rows if r[2] > 1.0]
+    first_lost = lost[0][0] if lost else None
+    won_to = max([r[0] for r in rows if first_lost is None or r[0] < first_lost], default=0)
+    fill = (first_lost * 8 - 1) // n_cu if lost else 1 << 20    # the largest fill that admits no product measured slower
+    print(f"# {len(rows)} products timed on both routes; mid at least as fast at every product of up to {won_to} tiles"
+          + (f", slower first at {first_lost} tiles: the largest fill that takes none measured slower is {fill} eighths of {n_cu} CUs "
+             f"(up to {fill * n_cu // 8} tiles)" if lost else "; slower nowhere"))
+    good_m = max([r[1] for r in rows if r[0] * 8 <= fill * n_cu], default=0)
+    print(f"# under that fill the largest M with a product the step takes: {good_m}")
+    print(f"# products measured slower on mid: {[(tl, M, round(x, 2)) for tl, M, x, _ in lost]}")
+    taken = [r for r in rows if r[3]]
+    print(f"# under the shipped fill the step takes {len(taken)} of them; slower among those: {[(tl, M, round(x, 2)) for tl, M, x, _ in taken if x > 1.0]}")
+
+
 if __name__ == "__main__":
-    main()
+    main_mx() if "--mx" in sys.argv[1:] else main()

@@ -25,7 +25,10 @@ yvhip.conv2d_group_plan - the partition function of the launch itself - reports 
 one; and the peak of torch.cuda.max_memory_allocated over a call above what was allocated before the first call of that shape
 (the engines' activation buffers: every engine starts each shape with none).
 --e2e times instead host arrays in to records out - inferdet.run_chunk, eager, against yvhip.request.RequestSession.run, two graph
-replays - at the same shapes (end_to_end; RB_ROWS restricts its rows); profiles/request_bench_graph.txt is its output."""
+replays - at the same shapes (end_to_end; RB_ROWS restricts its rows); profiles/request_bench_graph.txt is its output.
+--e2e --mx: the rows of an mxfp8 classifier - VitEngine(dtype="mxfp8") without and with mid_gemm, eager and in a session - beside the
+bf16 rows with mid_gemm, in the same process; each mxfp8 row is also set against its twin (the same row without mid_gemm; for the
+rows without it, the bf16 row of the same kind); profiles/request_bench_mx.txt is its output."""
 import gc, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "yolov8-vit_amd"))
@@ -192,6 +195,15 @@ E2E_ROWS = [("eager chunk", False, False, False, (False, False)),
             ("session mid", True, True, True, (False, False)),
             ("session small+grouped", True, True, False, (True, True)),
             ("session mid+small+grouped", True, True, True, (True, True))]
+# --e2e --mx rows: the same fields and the classifier's dtype; E2E_TWIN: the row each is also set against
+E2E_MX_ROWS = [("eager fit+mid bf16", False, True, True, (False, False), "bf16"),
+               ("session mid bf16", True, True, True, (False, False), "bf16"),
+               ("eager fit mxfp8", False, True, False, (False, False), "mxfp8"),
+               ("eager fit+mid mxfp8", False, True, True, (False, False), "mxfp8"),
+               ("session mxfp8", True, True, False, (False, False), "mxfp8"),
+               ("session mid mxfp8", True, True, True, (False, False), "mxfp8")]
+E2E_TWIN = {"eager fit mxfp8": "eager fit+mid bf16", "eager fit+mid mxfp8": "eager fit mxfp8", "session mxfp8": "session mid bf16",
+            "session mid mxfp8": "session mxfp8"}
 E2E_CAND = {}                                                       # B -> (boxes, scores): static, the scores rewritten in place
 
 
@@ -229,7 +241,9 @@ def end_to_end():
     engines runs first), the session's stream has its workspace, so this is the static buffers and the graphs' pools."""
     from YOLOTensorRT.inferdet import run_chunk
     from yvhip.request import RequestSession
-    rows = [r for r in E2E_ROWS if not os.environ.get("RB_ROWS") or r[0] in os.environ["RB_ROWS"].split(",")]
+    rows = [r for r in (E2E_MX_ROWS if "--mx" in sys.argv[1:] else E2E_ROWS)
+            if not os.environ.get("RB_ROWS") or r[0] in os.environ["RB_ROWS"].split(",")]
+    rows = [tuple(r) + ("bf16",) * (6 - len(r)) for r in rows]
     print(f"# {torch.cuda.get_device_name(0)}; host arrays in -> records out, ms per chunk, median of {RUNS} x {CALLS} calls, rows "
           f"interleaved; memory in MB at the first visit of the row's key (B, 640, 640, capacity)")
     print(f"# {'classifier':22s} {'B':>2s} {'dets':>4s} {'crops':>5s}  {'row':34s} {'capacity':>8s} {'call ms':>8s} {'stage1 ms':>9s} "
@@ -242,12 +256,12 @@ def end_to_end():
     g = torch.Generator().manual_seed(1234)
     for name in MODELS:
         vit_sd = engines.init_vit_wrapper_state(name, NC, seed=42)
-        vits = {m: engines.VitEngine(vit_sd, name, NC, device=dev, mid_gemm=m) for m in sorted({r[3] for r in rows})}
+        vits = {k: engines.VitEngine(vit_sd, name, NC, device=dev, mid_gemm=k[0], dtype=k[1]) for k in sorted({(r[3], r[5]) for r in rows})}
         pipes, sessions, fitted = {}, {}, {}
-        for label, ses, fit, mid, which in rows:
-            pipes[label] = e2e_detect(DetectClassifyPipeline(dets[which], [vits[mid]], fit_crops=fit))
+        for label, ses, fit, mid, which, dtype in rows:
+            pipes[label] = e2e_detect(DetectClassifyPipeline(dets[which], [vits[(mid, dtype)]], fit_crops=fit))
             if ses:
-                fitted[label] = e2e_detect(DetectClassifyPipeline(dets[which], [vits[mid]], fit_crops=True))
+                fitted[label] = e2e_detect(DetectClassifyPipeline(dets[which], [vits[(mid, dtype)]], fit_crops=True))
                 sessions[label] = s = RequestSession(pipes[label])
                 with torch.cuda.stream(s.stream):
                     yvhip._st()                                   # the stream's split-K workspace: not a cost of a key
@@ -298,7 +312,9 @@ def end_to_end():
                           if ses else f"{'-':>9s} {'-':>9s}")
                     m = "  ".join(f"{v:8.1f}" for v in mem[label]) if label in mem else ""
                     r1 = f"{t / t1:9.2f}" if t1 else f"{'-':>9s}"
-                    print(f"  {name:22s} {B:2d} {d:4d} {crops[label]:5d}  {label:34s} {str(cap[label]):>8s} {t:8.3f} {st}  {t / t0:7.2f} {r1}  {m}",
+                    twin = E2E_TWIN.get(label)
+                    vs = f"  x {t / median(ms[twin]):.3f} of {twin}" if twin in ms else ""
+                    print(f"  {name:22s} {B:2d} {d:4d} {crops[label]:5d}  {label:34s} {str(cap[label]):>8s} {t:8.3f} {st}  {t / t0:7.2f} {r1}  {m}{vs}",
                           flush=True)
         for label, s in sessions.items():
             print(f"# {name}, {label}: stats {s.stats}, keys {[(k, sorted(v.stage2)) for k, v in s.keys.items()]}")

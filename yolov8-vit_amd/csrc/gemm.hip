@@ -2495,6 +2495,176 @@ int launch_mid(GemmArgs& g, hipStream_t st) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// Mid-M MXFP8 linear (1 <= M <= "linear_mx_mid": the mxfp8 classifier at the handful of crops one request carries; DESIGN.md
+// section 38).  gemm_mid_kernel's organisation on gemm_mx_kernel's operands: a workgroup owns 64 x 64 outputs, its 8 waves are two
+// K groups x (2 x 2 waves of 32 x 32), group h taking the 128-element K steps h, h + 2, ...  Each group fills its own two-stage ring
+// by LDS-DMA: per stage 64 A rows and 64 W rows of 128 B (gemm_mx_kernel's source-side chunk swizzle, its fragment reads of chunks
+// fq and 4 + fq) and the tile's 128 scale dwords of that K step (A's 64, then W's 64; one wave-instruction of the group's first
+// wave, whose upper 32 lanes re-fetch a valid address into the slack of the 1 KB slot so that exec stays full).
+// 2 groups x 2 stages x (16 KB + 1 KB) = 68 KB, two workgroups per CU.  One vmcnt(0) + barrier per trip, shared by the groups;
+// with an odd step count group 1 idles through the last trip, with K = 128 it adds zeros.
+// Exchange and sum as in gemm_mid_kernel (group 0 + group 1 on both sides, over the rings after the last barrier), then every wave
+// finishes a 16-row x 32-column piece: the direct epilogue, or - YV_EPI_OUT_MXFP8 - the piece IS one MX block per row, held by the
+// lanes fr, fr + 16, fr + 32, fr + 48: value (bias, GELU), bf16 rounding, mx_quant_piece16x32, the e4m3 bytes and one scale byte.
+// Host: N % 64 == 0, K % 128 == 0, flags within BIAS | GELU | RES_F32 | OUT_F32 | OUT_MXFP8, no separate residual source.
+// ---------------------------------------------------------------------------------------------
+int g_opt_mx_mid = 0;               // largest M taken by gemm_mx_mid_kernel ("linear_mx_mid"; 0 = off)
+int g_opt_mx_mid_fill = 5;          // ... where 128 x 128 tiles number at most this many eighths of the CU count ("linear_mx_mid_fill";
+                                    // measured: up to 150 tiles x 0.46 - 0.92 of the 128 x 128 route's time, at 168 x 0.84 - 1.02, beyond slower)
+
+__global__ __launch_bounds__(512, 2) void gemm_mx_mid_kernel(MxArgs a) {
+    const GemmArgs& g = a.g;
+    constexpr int BM = 64, BN = 64, MF = 2, NF = 2;
+    constexpr int A_BYTES = BM * 128, W_BYTES = BN * 128, S_BYTES = 1024;   // (scales: 512 B + the slack of the DMA's upper lanes)
+    constexpr int STAGE = A_BYTES + W_BYTES + S_BYTES, RING = 2 * STAGE;    // bytes: one K step of a group, a group's two stages
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int half = wave >> 2, w4 = wave & 3;
+
+    int M = g.M;
+    if (g.m_dev) { long long md = (long long)g.m_dev[0] * g.m_mul; M = md < M ? (int)md : M; }
+    const int bid = xcd_remap(blockIdx.x, gridDim.x);
+    int tm, tn;
+    {
+        const int GM = g.group_m, per = GM * g.tiles_n;
+        const int grp = bid / per, first = grp * GM;
+        const int gsz = (g.tiles_m - first) < GM ? (g.tiles_m - first) : GM;
+        const int in = bid - grp * per;
+        tm = first + in % gsz;
+        tn = in / gsz;
+    }
+    const int m0 = tm * BM, n0 = tn * BN;
+    if (m0 >= M) return;
+
+    // a group's four waves fill its stage: 8 rows x 128 B per wave-instruction, 2 for A and 2 for W per wave
+    const int lrow = lane >> 3, lch = lane & 7;
+    const uint8_t* a_src[2];
+    const uint8_t* w_src[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int r = (j * 4 + w4) * 8 + lrow;
+        int m = m0 + r;
+        m = m < g.M ? m : g.M - 1;                              // rows past the end: the last row, never stored
+        a_src[j] = (const uint8_t*)g.a0 + (long long)m * g.lda0 + ((lch ^ (r & 7)) << 4);
+        w_src[j] = (const uint8_t*)g.w + (long long)(n0 + r) * g.K + ((lch ^ (r & 7)) << 4);
+    }
+    // scale DMA (the group's wave 0): lane l < 32 fetches the dwords 4 l .. 4 l + 3 of the tile's 64 A + 64 W scale dwords
+    const int s_dw = lane * 4;
+    const bool s_on = s_dw < BM + BN;
+    const uint8_t* const s_src = s_dw < BM ? a.sa + ((long long)m0 + s_dw) * 4 : a.sw + ((long long)n0 + (s_on ? s_dw - BM : 0)) * 4;
+    const long long s_step = (s_dw < BM ? a.rows_a : a.rows_w) * 4;
+    unsigned char* const ring = smem + half * RING;
+    auto issue = [&](int kt, int buf) {
+        unsigned char* A = ring + buf * STAGE;
+        unsigned char* W = A + A_BYTES;
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+            __builtin_amdgcn_global_load_lds((gptr_t)(a_src[j] + kt * 128), (lptr_t)(A + (j * 4 + w4) * 1024), 16, 0, 0);
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+            __builtin_amdgcn_global_load_lds((gptr_t)(w_src[j] + kt * 128), (lptr_t)(W + (j * 4 + w4) * 1024), 16, 0, 0);
+        if (w4 == 0)        // (lanes past the 128 dwords re-fetch the first W dwords into their unused slot: exec stays full)
+            __builtin_amdgcn_global_load_lds((gptr_t)(s_src + kt * s_step), (lptr_t)(W + W_BYTES), 16, 0, 0);
+    };
+
+    f32x4 acc[NF][MF];
+#pragma unroll
+    for (int i = 0; i < NF; ++i)
+#pragma unroll
+        for (int j = 0; j < MF; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    const int wrow_m = (w4 >> 1) * 32, wrow_n = (w4 & 1) * 32;
+    const int fr = lane & 15, fq = lane >> 4;
+
+    const int nk = g.K >> 7, trips = (nk + 1) >> 1;             // trip t: K step 2 t + half (group 1 may lack the last one)
+    if (half < nk) issue(half, 0);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    for (int t = 0; t < trips; ++t) {
+        const int cur = t & 1, kt = 2 * t + half;
+        if (kt + 2 < nk) issue(kt + 2, cur ^ 1);
+        if (kt < nk) {
+            const unsigned char* A = ring + cur * STAGE;
+            const unsigned char* W = A + A_BYTES;
+            const unsigned char* S = W + W_BYTES;
+            i32x8 fa[MF], fw[NF];
+            int sca[MF], scw[NF];
+#pragma unroll
+            for (int j = 0; j < MF; ++j) {
+                const int rr = wrow_m + j * 16 + fr;
+                const u32x4 lo = *(const u32x4*)(A + rr * 128 + (((fq) ^ (rr & 7)) << 4));
+                const u32x4 hi = *(const u32x4*)(A + rr * 128 + (((4 + fq) ^ (rr & 7)) << 4));
+                fa[j] = (i32x8){(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3], (int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
+                sca[j] = (int)(*(const uint32_t*)(S + rr * 4) >> (8 * fq));              // byte 0 = scale of block fq
+            }
+#pragma unroll
+            for (int i = 0; i < NF; ++i) {
+                const int rr = wrow_n + i * 16 + fr;
+                const u32x4 lo = *(const u32x4*)(W + rr * 128 + (((fq) ^ (rr & 7)) << 4));
+                const u32x4 hi = *(const u32x4*)(W + rr * 128 + (((4 + fq) ^ (rr & 7)) << 4));
+                fw[i] = (i32x8){(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3], (int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
+                scw[i] = (int)(*(const uint32_t*)(S + BM * 4 + rr * 4) >> (8 * fq));
+            }
+#pragma unroll
+            for (int i = 0; i < NF; ++i)
+#pragma unroll
+                for (int j = 0; j < MF; ++j)
+                    acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fw[i], fa[j], acc[i][j], 0, 0, 0, scw[i], 0, sca[j]);
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();                                        // (the last one: every fragment read is done, the rings are free)
+    }
+    // exchange: xch[half][w4][i][lane] holds the fragments (i, 1 - half) of that wave, which the OTHER group finishes
+    f32x4* const xch = (f32x4*)smem;
+#pragma unroll
+    for (int i = 0; i < NF; ++i) xch[((half * 4 + w4) * NF + i) * 64 + lane] = half ? acc[i][0] : acc[i][1];
+    __syncthreads();
+    f32x4 sum[NF][1];
+#pragma unroll
+    for (int i = 0; i < NF; ++i) {
+        const f32x4 other = xch[(((1 - half) * 4 + w4) * NF + i) * 64 + lane];
+        sum[i][0] = half ? other + acc[i][1] : acc[i][0] + other;           // group 0 + group 1
+    }
+    if (!(g.flags & YV_EPI_OUT_MXFP8)) {
+        epilogue<1, NF>(g, sum, M, m0, n0, wrow_m + half * 16, wrow_n, fr, fq);
+        return;
+    }
+    // the fc1 -> fc2 hand-over: this lane holds columns fq * 4 .. + 3 and 16 + fq * 4 .. + 3 of the block nb .. nb + 31 of row m
+    const int m = m0 + wrow_m + half * 16 + fr, nb = n0 + wrow_n;
+    float v[8];
+#pragma unroll
+    for (int i = 0; i < NF; ++i) {
+        const int n = nb + i * 16 + fq * 4;
+        float4 b = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (g.flags & YV_EPI_BIAS) b = *(const float4*)(g.bias + n);
+        float u[4] = {sum[i][0][0] + b.x, sum[i][0][1] + b.y, sum[i][0][2] + b.z, sum[i][0][3] + b.w};
+        if (g.flags & YV_EPI_GELU) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) u[q] = gelu_f(u[q]);
+        }
+        const uint32_t p0 = pack_bf16x2(u[0], u[1]), p1 = pack_bf16x2(u[2], u[3]);      // the bf16 value the staged epilogue quantises
+        v[i * 4] = bf16_to_f32((uint16_t)(p0 & 0xffff)); v[i * 4 + 1] = bf16_to_f32((uint16_t)(p0 >> 16));
+        v[i * 4 + 2] = bf16_to_f32((uint16_t)(p1 & 0xffff)); v[i * 4 + 3] = bf16_to_f32((uint16_t)(p1 >> 16));
+    }
+    uint32_t q8[2];
+    const int e = mx_quant_piece16x32(v, q8);                   // (every lane: rows past M quantise the clamped row, store nothing)
+    if (m >= M) return;
+    uint8_t* const o = g.mxq + (long long)m * g.ldmxq + nb + fq * 4;
+    *(uint32_t*)o = q8[0];
+    *(uint32_t*)(o + 16) = q8[1];
+    if (fq == 0) g.mxs[mx_scale_kmajor(nb >> 5, g.mx_rows, m)] = (uint8_t)(e + 127);
+}
+
+int launch_mx_mid(MxArgs& a, hipStream_t st) {
+    GemmArgs& g = a.g;
+    g.tiles_m = (g.M + 63) / 64;
+    g.tiles_n = g.N >> 6;
+    const size_t lds = 2 * 2 * (size_t)((64 + 64) * 128 + 1024);
+    if (!yv_grant_lds((const void*)gemm_mx_mid_kernel, lds)) return YV_ERR_LAUNCH;
+    launch_timed(gemm_mx_mid_kernel, g.tiles_m * g.tiles_n, 512, lds, st, a);
+    return yv_launch_status();
+}
+
+// ---------------------------------------------------------------------------------------------
 // gemm_mid_kernel with the LayerNorm that feeds it as a prologue ("linear_ln_mid": norm1 -> qkv and norm2 -> fc1 of the classifier
 // at a handful of crops).  The A operand is the f32 residual stream x (M, K <= 1024): a 64 x 64 tile walks
 // the whole row of its 64 input rows anyway, so it computes their statistics itself and normalises while it stages them, and the
@@ -3108,11 +3278,23 @@ LinearRoute linear_route(const GemmArgs& g, bool have_ws, size_t ws_bytes, int n
     return route_of(g, YV_LIN_DMA, 128, 128);
 }
 
-// MXFP8 operands: the free-running persistent kernel (tests/test_gpu_mx_train.py::test_mx_linear_ex_epilogues reaches each
-// epilogue family on it and on the other), else gemm_mx_kernel<128, 128, 2, 2>
+// MXFP8 operands: the mid-M step where "linear_mx_mid" admits the shape (off by default), then the free-running persistent kernel
+// (tests/test_gpu_mx_train.py::test_mx_linear_ex_epilogues reaches each epilogue family on it and on the other), else
+// gemm_mx_kernel<128, 128, 2, 2>
 LinearRoute mx_linear_route(const GemmArgs& g, long long lda, long long a_rows, long long w_rows, int n_cu) {
     const int M = g.M, N = g.N, K = g.K, flags = g.flags, nkm = K >> 7;
     const bool f32o = flags & (YV_EPI_RES_F32 | YV_EPI_OUT_F32), ext = flags & (YV_EPI_SAVE_PRE | YV_EPI_GELU_BWD);
+    // a handful of crops ("linear_mx_mid", off by default; section 38): gemm_mx_mid_kernel's 64 x 64 tiles with the K steps dealt to
+    // two wave groups, from one row on (the MX route has no skinny kernel), where 128 x 128 tiles would make at most
+    // "linear_mx_mid_fill" / 8 of a workgroup per CU.  The forms of the inference engine only: no trainer epilogue, no separate
+    // residual source
+    const long long tiles128 = (long long)((M + 127) / 128) * ((N + 127) / 128);
+    if (M >= 1 && M <= g_opt_mx_mid && !(N & 63) && N > 64 && !(K & 127) &&
+        !(flags & ~(YV_EPI_BIAS | YV_EPI_GELU | YV_EPI_RES_F32 | YV_EPI_OUT_F32 | YV_EPI_OUT_MXFP8)) && !((flags & YV_EPI_OUT_MXFP8) && f32o) &&
+        !g.resf && !g.aux && tiles128 * 8 <= (long long)g_opt_mx_mid_fill * n_cu) {
+        LinearRoute r = route_of(g, YV_LIN_MX_MID, 64, 64);
+        return r.mx = 1, r;
+    }
     if (g_opt_p8 >= 3 && g_opt_variant == 1 && M >= 2048 && tiles_of(M, N, 160) >= 192 &&
         persistent_ok(M, N, K, lda, g.ldo, flags, ext, g.ldaux, 1) && !((flags & YV_EPI_OUT_MXFP8) && f32o) && !(f32o && (nkm & 1)) &&
         (long long)nkm * a_rows * 4 < 0x7fffffffLL && (long long)nkm * w_rows * 4 < 0x7fffffffLL)
@@ -3256,12 +3438,17 @@ extern "C" int yv_linear_mxfp8(const void* Aq, long long lda, const void* Ascale
                           nullptr, 0, nullptr, 0, stream);
 }
 
+// what the _q form asks on top of linear_mx_impl (yv_linear_mxfp8_q and its route report)
+static bool mx_q_args_ok(const void* out_q, const void* out_scales, int M, int N, int flags, long long ldq, long long out_rows_pad) {
+    if (!out_q || !out_scales || (N & 127) || (ldq & 15) || ldq < N || out_rows_pad < M || (out_rows_pad & 127)) return false;
+    return !(flags & ~(YV_EPI_BIAS | YV_EPI_GELU));
+}
+
 extern "C" int yv_linear_mxfp8_q(const void* Aq, long long lda, const void* Ascale, long long a_rows_pad, const void* Wq,
                                  const void* Wscale, long long w_rows_pad, const float* bias, int M, int N, int K, int flags,
                                  const int32_t* m_dev, int m_mul, void* out_q, long long ldq, void* out_scales,
                                  long long out_rows_pad, void* stream) {
-    if (!out_q || !out_scales || (N & 127) || (ldq & 15) || ldq < N || out_rows_pad < M || (out_rows_pad & 127)) return YV_ERR_ARG;
-    if (flags & ~(YV_EPI_BIAS | YV_EPI_GELU)) return YV_ERR_ARG;
+    if (!mx_q_args_ok(out_q, out_scales, M, N, flags, ldq, out_rows_pad)) return YV_ERR_ARG;
     return linear_mx_impl(Aq, lda, Ascale, a_rows_pad, Wq, Wscale, w_rows_pad, bias, M, N, K, out_q, (int)ldq,
                           flags | YV_EPI_OUT_MXFP8, m_dev, m_mul, out_q, ldq, out_scales, out_rows_pad, stream);
 }
@@ -3326,6 +3513,7 @@ static int linear_mx_impl(const void* Aq, long long lda, const void* Ascale, lon
     const LinearRoute r = mx_linear_route(g, lda, a_rows_pad, w_rows_pad, n_cu);
     if (q) { *q->out = r; return YV_OK; }
     if (r.kernel == YV_LIN_P9) return launch_p9(g, (hipStream_t)stream, r.tile_rows, n_cu, true);
+    if (r.kernel == YV_LIN_MX_MID) return launch_mx_mid(a, (hipStream_t)stream);
     return launch_mx128(a, (hipStream_t)stream);
 }
 
@@ -3423,6 +3611,8 @@ static const struct { const char* key; int* (*at)(); } k_options[] = {
     {"linear_skinny", [] { return &g_opt_skinny; }},
     {"linear_mid", [] { return &g_opt_mid; }},
     {"linear_mid_fill", [] { return &g_opt_mid_fill; }},
+    {"linear_mx_mid", [] { return &g_opt_mx_mid; }},
+    {"linear_mx_mid_fill", [] { return &g_opt_mx_mid_fill; }},
     {"linear_ln_mid", [] { return &g_opt_ln_mid; }},
     {"linear_ln_fill", [] { return &g_opt_ln_mid_fill; }},
     {"wgrad_mx_split", [] { return &g_opt_wgrad_mx_split; }},
@@ -3543,6 +3733,19 @@ extern "C" int yv_linear_route(int M, int N, int K, int lda, int ldo, int flags,
     return linear_mx_impl(dummy, lda, dummy, (M + 127) / 128 * 128LL, dummy, dummy, (N + 127) / 128 * 128LL, f, M, N, K, dummy, ldo,
                           flags, m_dev, 1, nullptr, 0, nullptr, 0, nullptr, has_res_f32 ? f : nullptr, ldaux > 0 ? dummy : nullptr,
                           ldaux, &q);
+}
+
+// yv_linear_mxfp8_q's checks and route on dummy bases: dense operands (lda = ldq = K / N bytes), scale rows rounded up to 128
+extern "C" int yv_linear_mxfp8_q_route(int M, int N, int K, int flags, int n_cu, yv_linear_route_t* out) {
+    static unsigned char dummy[16] __attribute__((aligned(16)));
+    if (!out || M <= 0 || n_cu < 0) return YV_ERR_ARG;
+    const LinearQuery q = {out, 0, persistent_cus(n_cu)};
+    const int32_t* m_dev = (flags & YV_ROUTE_M_DEV) ? (const int32_t*)dummy : nullptr;
+    flags &= ~YV_ROUTE_M_DEV;
+    const long long rows_pad = (M + 127) / 128 * 128LL;
+    if (!mx_q_args_ok(dummy, dummy, M, N, flags, N, rows_pad)) return YV_ERR_ARG;
+    return linear_mx_impl(dummy, K, dummy, rows_pad, dummy, dummy, (N + 127) / 128 * 128LL, (const float*)dummy, M, N, K, dummy, N,
+                          flags | YV_EPI_OUT_MXFP8, m_dev, 1, dummy, N, dummy, rows_pad, nullptr, nullptr, nullptr, 0, &q);
 }
 
 extern "C" int yv_linear_ln_route(int M, int N, int K, int flags, int n_cu, yv_linear_ln_route_t* out) {

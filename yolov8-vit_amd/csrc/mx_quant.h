@@ -42,6 +42,12 @@ __device__ __forceinline__ int mx_quant_block(const float (&v)[N], uint32_t (&ou
     return e;
 }
 
+// Lane-stride form: a 16-row x 32-column piece of an MFMA accumulator tile (C^T layout, two 16-column fragments).  Lane (fr, fq) =
+// (lane & 15, lane >> 4) holds, of row fr's one block, columns 4 fq .. 4 fq + 3 (v[0 .. 3]) and 16 + 4 fq .. (v[4 .. 7]); the rest
+// of the block sits in the lanes at stride 16 (fr + 16, fr + 32, fr + 48), i.e. at the xor distances 16 and 32.  out[0] / out[1]
+// are the four bytes at column 4 fq / 16 + 4 fq of the block.
+__device__ __forceinline__ int mx_quant_piece16x32(const float (&v)[8], uint32_t (&out)[2]) { return mx_quant_block<16, 32>(v, out); }
+
 // Where the scale byte of block bk (= k / 32) of a row lives.  K-step-major (K / 128, rows_pad, 4): the four bytes of a row's
 // 128-deep K step are one dword (the operand layout of the block-scaled MFMA loops).  MX map: (pixel, C / 32), ldq bytes per pixel.
 __device__ __forceinline__ long long mx_scale_kmajor(int bk, long long rows_pad, long long row) {

@@ -97,6 +97,7 @@ _SIGS = {
     "yv_linear_route": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _sz, _i, _vp]),
     "yv_linear_ln": (_i, [_vp, _sz, _vp, _vp, _f, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp]),
     "yv_linear_ln_route": (_i, [_i, _i, _i, _i, _i, _vp]),
+    "yv_linear_mxfp8_q_route": (_i, [_i, _i, _i, _i, _i, _vp]),
     "yv_wgrad_mxfp8": (_i, [_vp, C.c_longlong, _vp, C.c_longlong, _vp, C.c_longlong, _vp, C.c_longlong, _i, _i, _i, _vp, _i, _vp]),
     "yv_custom_nms_ws_bytes": (_sz, [_i, _i]),
     "yv_custom_nms": (_i, [_vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _sz, _vp]),
@@ -1438,7 +1439,9 @@ def quant_mxfp8(x: torch.Tensor, q: Optional[torch.Tensor] = None, scales: Optio
 def linear_mxfp8(aq: torch.Tensor, a_scale: torch.Tensor, wq: torch.Tensor, w_scale: torch.Tensor,
                  bias: Optional[torch.Tensor], out: torch.Tensor, flags: int = 0, m_dev: Optional[torch.Tensor] = None,
                  m_mul: int = 1):
-    _chk_dev(aq, a_scale, wq, w_scale, bias, out, m_dev)
+    """aq (M, K) e4m3 bytes, read with its row stride (a view of a wider buffer is fine); the other tensors contiguous."""
+    _chk_rows(aq)
+    _chk_dev(a_scale, wq, w_scale, bias, out, m_dev)
     M, K = aq.shape
     N = wq.shape[0]
     if bias is not None:
@@ -1565,7 +1568,7 @@ def linear_mxfp8_instance(M: int, N: int, K: int, flags: int = 0) -> int:
 
 STREAM_WS_BYTES = 16 * 1024 * 1024 * 4      # the split-K workspace _st() registers per stream (what linear_route assumes by default)
 # linear_route: kernel families (yv_linear_route_t.kernel, include/yv_hip.h)
-LIN_SKINNY, LIN_IGEMM, LIN_DMA, LIN_P8, LIN_P9, LIN_MX, LIN_MID = 0, 1, 2, 3, 4, 5, 6
+LIN_SKINNY, LIN_IGEMM, LIN_DMA, LIN_P8, LIN_P9, LIN_MX, LIN_MID, LIN_MX_MID = 0, 1, 2, 3, 4, 5, 6, 7
 ROUTE_M_DEV = 0x40000000                     # linear_route flag: the launch passes a device row count
 LinearRoute = collections.namedtuple("LinearRoute", "kernel tile_rows tile_cols f32out ext abl mx splitk staged grid")
 
@@ -1580,6 +1583,14 @@ def linear_route(M: int, N: int, K: int, flags: int = 0, lda: Optional[int] = No
     check(lib.yv_linear_route(M, N, K, K if lda is None else lda, N if ldo is None else ldo, flags | (ROUTE_M_DEV if m_dev else 0),
                               int(res_f32), ldaux, int(mx),
                               ws_bytes, n_cu, out), "yv_linear_route")
+    return LinearRoute(*out)
+
+
+def linear_mxfp8_q_route(M: int, N: int, K: int, flags: int = 0, n_cu: int = 0, m_dev: bool = False) -> LinearRoute:
+    """Route linear_mxfp8_q takes for this shape under the current options (host only; linear_route rejects its output form):
+    see yv_linear_mxfp8_q_route in include/yv_hip.h.  `flags` within EPI_BIAS | EPI_GELU, as the C entry takes them."""
+    out = (C.c_int * len(LinearRoute._fields))()
+    check(lib.yv_linear_mxfp8_q_route(M, N, K, flags | (ROUTE_M_DEV if m_dev else 0), n_cu, out), "yv_linear_mxfp8_q_route")
     return LinearRoute(*out)
 
 
@@ -1724,8 +1735,10 @@ def layernorm_mxfp8(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, q:
 def linear_mxfp8_q(aq: torch.Tensor, a_scale: torch.Tensor, wq: torch.Tensor, w_scale: torch.Tensor,
                    bias: Optional[torch.Tensor], out_q: torch.Tensor, out_scale: torch.Tensor, flags: int = 0,
                    m_dev: Optional[torch.Tensor] = None, m_mul: int = 1):
-    """MXFP8 linear whose output is again an MXFP8 operand (bias / GELU -> bf16 rounding -> e4m3 + E8M0)."""
-    _chk_dev(aq, a_scale, wq, w_scale, bias, out_q, out_scale, m_dev)
+    """MXFP8 linear whose output is again an MXFP8 operand (bias / GELU -> bf16 rounding -> e4m3 + E8M0).  aq is read with its
+    row stride, as in linear_mxfp8."""
+    _chk_rows(aq)
+    _chk_dev(a_scale, wq, w_scale, bias, out_q, out_scale, m_dev)
     M, K = aq.shape
     N = wq.shape[0]
     if bias is not None:

@@ -542,6 +542,7 @@ VIT_CFGS = {
 
 
 MID_GEMM_ROWS = 3152      # "linear_mid" of a VitEngine(mid_gemm=True) pass: the bound measured in DESIGN.md section 31
+MX_MID_GEMM_ROWS = 3152   # "linear_mx_mid" of a VitEngine(dtype="mxfp8", mid_gemm=True) pass: DESIGN.md section 38
 
 
 def vit_cfg(name: str):
@@ -603,7 +604,11 @@ class VitEngine:
         mid_gemm (opt-in): the pass runs with the option "linear_mid" at MID_GEMM_ROWS, so its bf16 linears of 257 .. that many
         rows - the block products at a handful of crops, as DetectClassifyPipeline(fit_crops=True) sizes them - take
         gemm_mid_kernel's 64 x 64 tiles instead of 128 x 128 ones; the option is restored after the pass.  None reads the
-        environment variable YV_VIT_MID_GEMM ("1" = on, unset = off).  Off: the option is not touched.
+        environment variable YV_VIT_MID_GEMM ("1" = on, unset = off).  Off: the option is not touched.  dtype "mxfp8": the pass
+        also runs with "linear_mx_mid" at MX_MID_GEMM_ROWS (restored after it), so its four block linears - linear_mxfp8 and the
+        fc1 -> fc2 hand-over linear_mxfp8_q - take gemm_mx_mid_kernel's 64 x 64 tiles wherever "linear_mx_mid_fill" admits the shape,
+        from one crop on.  This is the one combination whose results differ from mid_gemm=False in the last bits (another order
+        of the K sum); an mxfp8 engine without the flag never touches the option.
         ln_gemm (bf16 path, opt-in): norm1 -> qkv and norm2 -> fc1 of the full blocks run as linear_ln, and the pass runs with the
         option "linear_ln_mid" at MID_GEMM_ROWS (restored after it): at 257 .. that many rows, where "linear_ln_fill" admits the
         shape, each pair is ONE launch whose 64 x 64 tiles normalise their own rows; at any other size - one crop of a /16 model,
@@ -732,11 +737,16 @@ class VitEngine:
         if not self.mid_gemm:
             return self._backbone_tail(patches, cap, count, slot)
         mid = get_option("linear_mid")
+        mx_mid = get_option("linear_mx_mid") if self.dtype == "mxfp8" else None
         set_option("linear_mid", MID_GEMM_ROWS)
+        if mx_mid is not None:
+            set_option("linear_mx_mid", MX_MID_GEMM_ROWS)
         try:
             return self._backbone_tail(patches, cap, count, slot)
         finally:
             set_option("linear_mid", mid)
+            if mx_mid is not None:
+                set_option("linear_mx_mid", mx_mid)
 
     def _backbone_tail(self, patches: torch.Tensor, cap: int, count: Optional[torch.Tensor], slot: int) -> torch.Tensor:
         if self.cls_tail:
