@@ -92,6 +92,9 @@ int yv_layernorm_mxfp8(const float* x, size_t ldx, const float* gamma, const flo
 /* Diagnostic: ONE v_mfma_scale_f32_16x16x128_f8f6f4 on caller-provided register images: a, b (64 lanes x 32 bytes),
  * sa, sb (64 x int32 scale registers), opsel 0..3 for both; d (64 lanes x 4 f32). */
 int yv_mx_probe(const void* a, const void* b, const void* sa, const void* sb, int opsel, void* d, void* stream);
+/* The same for ONE v_mfma_scale_f32_32x32x64_f8f6f4 (the QK^T product of yv_attention_fp8): a, b (64 lanes x 32 bytes), sa, sb
+ * (64 x int32), opsel 0..3 for both; d (64 lanes x 16 f32, the C/D layout of the 32x32x16 forms). */
+int yv_mx_probe32(const void* a, const void* b, const void* sa, const void* sb, int opsel, void* d, void* stream);
 
 int yv_quant_mxfp8(const void* x, long long ldx, long long rows, int K, void* q, long long ldq, void* scales,
                    long long rows_pad, void* stream);
@@ -663,6 +666,24 @@ int yv_attention_cls(const void* q, const void* qkv, int R, int N, int H, float 
  * whatever R, the crop's index and the grid. */
 int yv_attention_long(const void* qkv, int R, int N, int H, float scale, void* out, const int32_t* r_dev, float* lse,
                       void* out_q, long long ldq, void* out_scales, long long rows_pad, void* stream);
+
+/* yv_attention_long on an MXFP8 qkv operand (inference only: no lse), the blocking and the softmax unchanged.  The input is what
+ * yv_linear_mxfp8_q writes for N = 3 * H * 64 output columns: qkv_q (R*N, 3*H*64) e4m3 bytes, row stride ld_in bytes; qkv_scales
+ * K-step-major (3*H*64 / 128, in_rows_pad, 4) E8M0 - a head's 64 dimensions are two 32-blocks, bytes {0, 1} or {2, 3} of one dword.
+ * QK^T is one block-scaled v_mfma_scale_f32_32x32x64_f8f6f4 per 32 x 32 score group (K rows and Q rows as stored, scales applied by
+ * the instruction); V is dequantised exactly to bf16 on its way into LDS (e4m3 * 2^e) and PV runs as in yv_attention_long, P in
+ * bf16.  On operands whose scores are exact in f32 the outputs are the bytes of yv_attention_long on the dequantised bf16 qkv.
+ * Outputs out / out_q / out_scales / r_dev as yv_attention_long, with its rules.  YV_ERR_ARG, before any device call: a NULL
+ * qkv_q / qkv_scales, neither output or out_q without out_scales, R < 0, N <= 0, H <= 0, H odd ((64 H) % 128 != 0),
+ * ld_in < 3 * 64 * H or ld_in % 16 != 0, in_rows_pad < R*N or in_rows_pad % 128 != 0, qkv_q / out / out_q not 16-byte or
+ * qkv_scales not 4-byte aligned.  A grid past 2^31 - 1 workgroups is YV_ERR_LIMIT; R = 0 is YV_OK without a launch.  No read
+ * leaves rows [0, R*N) of either input array. */
+int yv_attention_fp8(const void* qkv_q, long long ld_in, const void* qkv_scales, long long in_rows_pad, int R, int N, int H,
+                     float scale, void* out, const int32_t* r_dev, void* out_q, long long ldq, void* out_scales,
+                     long long rows_pad, void* stream);
+/* Diagnostic: the V dequantisation of yv_attention_fp8 on its own: q (n e4m3 bytes, n % 4 == 0, 4-byte aligned) at the block scale
+ * byte `scale_byte` (E8M0, 0 .. 254) -> out (n bf16). */
+int yv_attention_fp8_dequant(const void* q, long long n, int scale_byte, void* out, void* stream);
 
 /* Diagnostic builds of the attention kernel (0 = normal; 1 no K/V loads, 2 no compute, 3 no V^T writes). */
 int yv_attention_debug(int ablate);

@@ -139,6 +139,65 @@ __device__ __forceinline__ bf16x8 vt_frag_tr(const unsigned char* Vs, const VtOf
     return __builtin_bit_cast(bf16x8, pk);
 }
 
+// ---- MXFP8 operands (attention_fp8.hip) ------------------------------------------------------------------
+// v_mfma_scale_f32_32x32x64_f8f6f4 (layout measured with yv_mx_probe32, tests/test_gpu_attn_fp8.py::test_mx_mfma32_layout): lane
+// (row / column rl = lane & 31, half hh = lane >> 5) holds K elements 16 hh .. + 15 in its first 16 bytes and 32 + 16 hh .. + 15 in
+// its second 16 bytes, i.e. the 16-byte chunks hh and 2 + hh of a 64-byte row; the scale of the MX block j (k = 32 j .. + 31) of that
+// row is byte `opsel` of the scale register of lane (rl, half j).  C/D as the 32x32x16 forms (key_of).
+typedef __attribute__((ext_vector_type(8))) int i32x8;
+__device__ __forceinline__ i32x8 mx_frag(const u32x4 lo, const u32x4 hi) {
+    return i32x8{(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3], (int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
+}
+// K image of e4m3 bytes: 64-byte rows of 4 chunks of 16 bytes, chunk c of row `row` at position c ^ ((row >> 2) & 3) (its own
+// inverse).  A 16-lane group of ds_read_b128 ({0-3, 12-15, 20-27} / {4-11, 16-19, 28-31} and the same + 32) reads one chunk index of
+// 16 rows: four rows of each row & 3 (which picks the 64-byte quarter of the 256-byte bank row), whose row >> 2 are {0, 3, 5, 6} /
+// {1, 2, 4, 7} - distinct modulo 4, so the xor sends them to the four 16-byte slots of that quarter: conflict-free
+// (tests/test_attn_fp8_cpu.py::test_k8_swizzle_is_conflict_free enumerates it).
+__device__ __forceinline__ int k8_off(int row, int c) { return row * 64 + ((c ^ ((row >> 2) & 3)) << 4); }
+// write side: slot i is chunk i & 3 of row i >> 2
+__device__ __forceinline__ RowChunk row_chunk8(int i) { return {i >> 2, i & 3}; }
+// where the two scale bytes of head hd's blocks of `row` live in a K-step-major scale array (kstep0: the K step of the tensor's
+// column 0: 0 for Q, D / 128 for K, 2 D / 128 for V); 2-byte aligned, byte 0 = d 0..31, byte 1 = d 32..63
+__device__ __forceinline__ long long mx_head_scales(int kstep0, int hd, long long rows_pad, long long row) {
+    return mx_scale_kmajor((kstep0 << 2) + 2 * hd, rows_pad, row);
+}
+// Q (B operand) of query q with its scale register (block hh's byte in byte 0), straight from global: qb = the crop's Q bytes of
+// this head, sq = the scale pair of the crop's row 0 (4 bytes per row); a query past N reads row N - 1
+__device__ __forceinline__ void q8_frag(const uint8_t* qb, long long ld, const uint8_t* sq, int q, int N, int hh, i32x8& fq, int& sc) {
+    const int qc = q < N ? q : N - 1;
+    const uint8_t* p = qb + (size_t)qc * ld + hh * 16;
+    fq = mx_frag(*(const u32x4*)p, *(const u32x4*)(p + 32));
+    sc = sq[(size_t)qc * 4 + hh];
+}
+// S^T of the 32 keys whose rows start at row0 of the byte image Kimg; Ksc: the keys' scale pairs (2 bytes per key)
+__device__ __forceinline__ f32x16 score_group8(const unsigned char* Kimg, const unsigned char* Ksc, int row0, const i32x8& fq, int sq,
+                                               int rl, int hh) {
+    f32x16 sv;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) sv[e] = 0.f;
+    const int row = row0 + rl;
+    const i32x8 fk = mx_frag(*(const u32x4*)(Kimg + k8_off(row, hh)), *(const u32x4*)(Kimg + k8_off(row, 2 + hh)));
+    const int sk = Ksc[2 * row + hh];
+    return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(fk, fq, sv, 0, 0, 0, sk, 0, sq);
+}
+// 2^(s - 127) of an E8M0 byte s <= 254 (s = 0: the f32 denormal 2^-127)
+__device__ __forceinline__ float mx_scale_f32(uint32_t s) { return __uint_as_float(s ? s << 23 : 0x00400000u); }
+// four e4m3 bytes at the block scale sf -> four bf16 (v_cvt_scalef32_pk_bf16_fp8: e4m3 * 2^e has 4 significant bits, exact in bf16
+// wherever it is a bf16 normal)
+__device__ __forceinline__ u32x2 mx_dequant4_bf16(uint32_t w, float sf) {
+    typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
+    const bf16x2_t lo = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, sf, false);
+    const bf16x2_t hi = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, sf, true);
+    return u32x2{__builtin_bit_cast(uint32_t, lo), __builtin_bit_cast(uint32_t, hi)};
+}
+// 16 bytes of V row `row` (d = 16 c .. + 15, block c >> 1) -> the bf16 chunks 2 c and 2 c + 1 of the row-major V image
+__device__ __forceinline__ void stash_v8(unsigned char* Vimg, int row, int c, const u32x4 bytes, float sf) {
+    const u32x2 a = mx_dequant4_bf16(bytes[0], sf), b = mx_dequant4_bf16(bytes[1], sf);
+    const u32x2 d = mx_dequant4_bf16(bytes[2], sf), e = mx_dequant4_bf16(bytes[3], sf);
+    *(u32x4*)(Vimg + v_off(row, 2 * c)) = u32x4{a[0], a[1], b[0], b[1]};
+    *(u32x4*)(Vimg + v_off(row, 2 * c + 1)) = u32x4{d[0], d[1], e[0], e[1]};
+}
+
 // ---- epilogue: query q < N of (crop r, head hd); inv = 1 / row sum ------------------------------------------------------------
 // log2-sum-exp for the backward: mb = the row maximum * scale_log2e, l = the row sum
 __device__ __forceinline__ void store_lse(float* lse, int r, int H, int hd, int N, int q, int hh, float mb, float l) {

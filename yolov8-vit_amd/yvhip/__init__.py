@@ -82,6 +82,10 @@ _SIGS = {
     "yv_attention_mxfp8": (_i, [_vp, _i, _i, _i, _f, _vp, C.c_longlong, _vp, C.c_longlong, _vp, _vp]),
     "yv_layernorm_mxfp8": (_i, [_vp, _sz, _vp, _vp, _i, _i, _f, _vp, _sz, _vp, C.c_longlong, _vp, _i, _vp]),
     "yv_mx_probe": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp]),
+    "yv_mx_probe32": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp]),
+    "yv_attention_fp8": (_i, [_vp, C.c_longlong, _vp, C.c_longlong, _i, _i, _i, _f, _vp, _vp, _vp, C.c_longlong, _vp,
+                              C.c_longlong, _vp]),
+    "yv_attention_fp8_dequant": (_i, [_vp, C.c_longlong, _i, _vp, _vp]),
     "yv_quant_mxfp8": (_i, [_vp, C.c_longlong, C.c_longlong, _i, _vp, C.c_longlong, _vp, C.c_longlong, _vp]),
     "yv_quant_mxfp8_map": (_i, [_vp, C.c_longlong, C.c_longlong, _i, _vp, C.c_longlong, _vp, _vp]),
     "yv_conv2d_mxfp8": (_i, [C.POINTER(yv_mx_view), C.POINTER(yv_mx_view), _i, _i, _i, _i, _i, _vp, _vp, C.c_longlong, _vp, _i,
@@ -1761,3 +1765,51 @@ def attention_mxfp8(qkv: torch.Tensor, R: int, N: int, H: int, out_q: torch.Tens
     check(lib.yv_attention_mxfp8(_p(qkv), R, N, H, float(64 ** -0.5 if scale is None else scale), _p(out_q), out_q.stride(0),
                                  _p(out_scale), out_scale.shape[1], _p(r_dev), _st()), "yv_attention_mxfp8")
 
+
+def attention_fp8(qkv_q: torch.Tensor, qkv_scale: torch.Tensor, R: int, N: int, H: int, out: Optional[torch.Tensor] = None,
+                  scale: Optional[float] = None, r_dev: Optional[torch.Tensor] = None, out_q: Optional[torch.Tensor] = None,
+                  out_scale: Optional[torch.Tensor] = None):
+    """attention_long on an MXFP8 qkv operand (yv_attention_fp8; any N >= 1, inference only): qkv_q (>= R*N, 3*H*64) e4m3 bytes read
+    with its row stride, qkv_scale (3*H*64 // 128, rows_pad, 4) E8M0 - what linear_mxfp8_q(flags=0) writes for the qkv product.  QK^T
+    runs on the block-scaled FP8 MFMA, V is dequantised to bf16 in the kernel, P stays bf16.  Outputs as attention_long: out
+    (R*N, H*64) bf16 and / or the proj operand out_q / out_scale; r_dev: crop count."""
+    _chk_rows(qkv_q)
+    _chk_dev(qkv_scale, out, r_dev, out_q, out_scale)
+    if (out_q is None) != (out_scale is None):
+        raise YvError("attention_fp8: out_q and out_scale come together")
+    if out is None and out_q is None:
+        raise YvError("attention_fp8: one of out / out_q is required")
+    if H <= 0 or H % 2:
+        raise YvError("attention_fp8: the MXFP8 qkv operand has whole 128-column K steps per tensor (H even)")
+    _mx_shape_check("attention_fp8 qkv_q", qkv_q, torch.uint8, R * N, 3 * H * 64)
+    _mx_scale_check("attention_fp8 qkv_scale", qkv_scale, 3 * H * 64 // 128, R * N)
+    _mx_shape_check("attention_fp8 out", out, torch.bfloat16, R * N, H * 64, exact_cols=True)
+    _mx_shape_check("attention_fp8 out_q", out_q, torch.uint8, R * N, H * 64)
+    _mx_scale_check("attention_fp8 out_scale", out_scale, H * 64 // 128, R * N)
+    check(lib.yv_attention_fp8(_p(qkv_q), qkv_q.stride(0), _p(qkv_scale), qkv_scale.shape[1], R, N, H,
+                               float(64 ** -0.5 if scale is None else scale), _p(out), _p(r_dev), _p(out_q),
+                               0 if out_q is None else out_q.stride(0), _p(out_scale),
+                               0 if out_scale is None else out_scale.shape[1], _st()), "yv_attention_fp8")
+    return out
+
+
+def mx_probe32(a: torch.Tensor, b: torch.Tensor, sa: torch.Tensor, sb: torch.Tensor, opsel: int = 0) -> torch.Tensor:
+    """ONE v_mfma_scale_f32_32x32x64_f8f6f4 on register images (yv_mx_probe32): a, b (64, 32) uint8, sa, sb (64,) int32 -> (64, 16)
+    f32, lane-major."""
+    _chk_dev(a, b, sa, sb)
+    for t, shape, dt in ((a, (64, 32), torch.uint8), (b, (64, 32), torch.uint8), (sa, (64,), torch.int32), (sb, (64,), torch.int32)):
+        if tuple(t.shape) != shape or t.dtype != dt:
+            raise YvError(f"mx_probe32: expected {dt} {shape}, got {t.dtype} {tuple(t.shape)}")
+    d = torch.zeros((64, 16), dtype=torch.float32, device=a.device)
+    check(lib.yv_mx_probe32(_p(a), _p(b), _p(sa), _p(sb), int(opsel), _p(d), _st()), "yv_mx_probe32")
+    return d
+
+
+def attention_fp8_dequant(q: torch.Tensor, scale_byte: int) -> torch.Tensor:
+    """The V dequantisation of attention_fp8 on its own (yv_attention_fp8_dequant): e4m3 bytes at one E8M0 scale byte -> bf16."""
+    _chk_dev(q)
+    if q.dtype != torch.uint8:
+        raise YvError("attention_fp8_dequant: expected uint8 bytes")
+    out = torch.empty(q.shape, dtype=torch.bfloat16, device=q.device)
+    check(lib.yv_attention_fp8_dequant(_p(q), q.numel(), int(scale_byte), _p(out), _st()), "yv_attention_fp8_dequant")
+    return out

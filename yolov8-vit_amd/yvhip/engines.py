@@ -22,7 +22,7 @@ import torch
 from .extent import n_anchors, net_hw
 from .guard import StepGuard
 from . import (CONV_DMA32_64, CONV_DMA32_96, CONV_DMA32_128, EPI_GELU, EPI_OUT_F32, EPI_POSEMB, EPI_RES_BF16, EPI_RES_F32, EPI_SILU,
-               RES_LN_WIDTHS, YvError, attention, attention_cls, attention_long, attention_mxfp8, c2f_fused, cls_rows, conv2d,
+               RES_LN_WIDTHS, YvError, attention, attention_cls, attention_fp8, attention_long, attention_mxfp8, c2f_fused, cls_rows, conv2d,
                conv2d_group, conv2d_instance, conv2d_mxfp8, detect_decode,
                detect_tail, get_option, layernorm, layernorm_mxfp8, linear, linear_ln, linear_mxfp8, linear_mxfp8_q, linear_res_ln, mx_map,
                mx_view, quant_conv_weight_mxfp8, quant_mxfp8, quant_mxfp8_map, require_gpu, set_option, sppf_pool, stem_conv,
@@ -581,10 +581,12 @@ class VitEngine:
 
     long_attn = False                                   # opt-in (see __init__)
     ln_gemm = False
+    fp8_attn = False
 
     def __init__(self, state: Dict[str, torch.Tensor], name: str, num_classes: int = 5, img: int = 224,
                  device: str = "cuda:0", dtype: str = "bf16", cls_tail: bool = True, fused_ln: Optional[bool] = None,
-                 long_attn: Optional[bool] = None, mid_gemm: Optional[bool] = None, ln_gemm: Optional[bool] = None):
+                 long_attn: Optional[bool] = None, mid_gemm: Optional[bool] = None, ln_gemm: Optional[bool] = None,
+                 fp8_attn: Optional[bool] = None):
         """cls_tail (bf16 path): the last block runs on the cls rows only - nothing reads its other rows (see _last_block_cls);
         False gives the full last block.  The mxfp8 pass runs every block in full whatever cls_tail says, and it ignores
         full_cus_from (the attribute PipelinedRunner sets): both are properties of the bf16 block loop.
@@ -615,7 +617,13 @@ class VitEngine:
         a batch - linear_ln runs the layernorm + linear pair as before.  The cls tail, the final LayerNorm and the mxfp8 pass are
         unchanged.  None reads the environment variable YV_VIT_LN_GEMM ("1" = on, unset = off; a bf16 engine without fused_ln
         only, any other ignores the variable).  True with fused_ln or dtype "mxfp8": YvError.  Independent of mid_gemm, long_attn
-        and cls_tail."""
+        and cls_tail.
+        fp8_attn (mxfp8 path, opt-in): the qkv product of every block is linear_mxfp8_q(flags=0) into the MXFP8 buffer pair
+        qkv8 / qkv8s (the bf16 qkv buffer is not allocated) and the attention is attention_fp8 - QK^T on the block-scaled FP8 MFMA,
+        V dequantised in the kernel, the proj operand written directly - whatever the token count; it takes precedence over
+        long_attn and YV_MX_ATTN_FUSED.  Q, K and V are then rounded to e4m3: the results differ from the unflagged engine's
+        (DESIGN.md section 40).  None reads the environment variable YV_VIT_FP8_ATTN ("1" = on, unset = off; an mxfp8 engine only,
+        a bf16 engine ignores the variable).  True with dtype "bf16": YvError.  Works together with mid_gemm."""
         require_gpu()
         if dtype not in ("bf16", "mxfp8"):
             raise YvError("dtype must be 'bf16' or 'mxfp8'")
@@ -629,6 +637,9 @@ class VitEngine:
         self.ln_gemm = _env_flag(ln_gemm, "YV_VIT_LN_GEMM") and (ln_gemm is not None or (dtype == "bf16" and not self.fused_ln))
         if self.ln_gemm and (dtype != "bf16" or self.fused_ln):
             raise YvError("ln_gemm is a property of the bf16 path without fused_ln (which leaves no LayerNorm in front of a linear)")
+        self.fp8_attn = _env_flag(fp8_attn, "YV_VIT_FP8_ATTN") and (fp8_attn is not None or dtype == "mxfp8")
+        if self.fp8_attn and dtype != "mxfp8":
+            raise YvError("fp8_attn is a property of the mxfp8 path (the bf16 engine has no MXFP8 qkv operand)")
         self.fuse_attention_quant = os.environ.get("YV_MX_ATTN_FUSED", "1") == "1"     # A/B switch of the mxfp8 path
         self.P, self.D, self.L, self.H = vit_cfg(name)
         if self.D // self.H != 64:
@@ -696,9 +707,13 @@ class VitEngine:
         if key not in self._bufs:
             dev, D, N = self.dev, self.D, self.N
             z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
+            rp = (cap * N + 255) // 256 * 256
+            # fp8_attn: the qkv product is an MXFP8 operand image (bytes + K-step-major block scales) instead of the bf16 buffer
+            qkv = dict(qkv=z((cap * N, 3 * D), torch.bfloat16)) if not self.fp8_attn else \
+                dict(qkv8=z((cap * N, 3 * D), torch.uint8), qkv8s=z((3 * D // 128, rp, 4), torch.uint8))
             self._bufs[key] = dict(
                 x=z((cap * N, D), torch.float32), h=z((cap * N, D), torch.bfloat16),
-                qkv=z((cap * N, 3 * D), torch.bfloat16), o=z((cap * N, D), torch.bfloat16),
+                **qkv, o=z((cap * N, D), torch.bfloat16),
                 g=z((cap * N, 4 * D), torch.bfloat16), c=z((cap, D), torch.bfloat16),
                 # compact cls-row operands of the pruned last block: q, attention output, LN2 output, GELU output
                 tq=z((cap, D), torch.bfloat16), to=z((cap, D), torch.bfloat16), th=z((cap, D), torch.bfloat16),
@@ -775,7 +790,11 @@ class VitEngine:
         mx: the result is the proj operand (q, qs) instead - written by the kernel itself (attention_long, or attention_mxfp8 unless
         YV_MX_ATTN_FUSED=0), else by a quantisation pass over o.  Both MX kernels take an even head count, which an mxfp8 engine
         always has: H = D / 64 and D is a multiple of 128."""
-        N, H, qkv, o = self.N, self.H, b["qkv"], b["o"]
+        N, H = self.N, self.H
+        if self.fp8_attn:                                # an mxfp8 engine: the qkv operand is MXFP8 (see _blocks_mxfp8), any N
+            attention_fp8(b["qkv8"], b["qkv8s"], cap, N, H, r_dev=count, out_q=b["q"], out_scale=b["qs"])
+            return
+        qkv, o = b["qkv"], b["o"]
         long = self.long_attn and N > 224
         if mx and long:
             attention_long(qkv, cap, N, H, r_dev=count, out_q=b["q"], out_scale=b["qs"])
@@ -849,12 +868,15 @@ class VitEngine:
         writes the fc2 operand directly (GELU output never exists in bf16 in HBM), attention writes the proj operand
         directly: no separate quantisation pass is left."""
         D, N = self.D, self.N
-        x, qkv = b["x"], b["qkv"]
+        x = b["x"]
         hq, hs, gq, gs = b["q"], b["qs"], b["gq"], b["gs"]
         rows = cap * N
         for blk in self.blocks:
             layernorm_mxfp8(x, blk["n1w"], blk["n1b"], hq, hs, rows, D, D, count_dev=count, rows_per_count=N)
-            linear_mxfp8(hq, hs, blk["wqkv_q"], blk["wqkv_s"], blk["bqkv"], qkv, m_dev=count, m_mul=N)
+            if self.fp8_attn:                            # the qkv product stays MXFP8: attention_fp8 consumes these bytes
+                linear_mxfp8_q(hq, hs, blk["wqkv_q"], blk["wqkv_s"], blk["bqkv"], b["qkv8"], b["qkv8s"], m_dev=count, m_mul=N)
+            else:
+                linear_mxfp8(hq, hs, blk["wqkv_q"], blk["wqkv_s"], blk["bqkv"], b["qkv"], m_dev=count, m_mul=N)
             self._attention(b, cap, count, mx=True)
             linear_mxfp8(hq, hs, blk["wproj_q"], blk["wproj_s"], blk["bproj"], x, flags=EPI_RES_F32, m_dev=count, m_mul=N)
             layernorm_mxfp8(x, blk["n2w"], blk["n2b"], hq, hs, rows, D, D, count_dev=count, rows_per_count=N)
